@@ -252,6 +252,35 @@ def gpu_same_shape(spa3d, dev):
   return out
 
 
+DUMP_BUDGET = 64 << 20  # bytes written by --dump-outputs, all files together
+DUMP_SAMPLE = 2_000_000  # elements sampled from each parameter-sized array when the whole arrays would not fit the budget
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, state, metrics):
+  """What the timed path handed its caller after the last step: the metrics train_step returned and the state it updated (parameters,
+  gradients, Adam moments, each a flat fp32 vector).  float64 scalars for the metrics; the parameter-sized vectors whole when all four fit
+  DUMP_BUDGET, else the same fixed, seeded, sorted sample of positions from each (sample_index.npy, float64: exact below 2**53)."""
+  import numpy as np
+  os.makedirs(out_dir, exist_ok=True)
+  arrays = {'train_' + k.split('/', 1)[1]: np.asarray(float(v), dtype=np.float64) for k, v in metrics.items()}
+  vecs = {'params': state.flat, 'grads': state.grads, 'adam_m': state.m, 'adam_v': state.v}
+  n = state.flat.numel()
+  if 4 * len(vecs) * n > DUMP_BUDGET:
+    g = torch.Generator().manual_seed(DUMP_SEED)
+    idx = torch.unique(torch.randint(0, n, (DUMP_SAMPLE,), generator=g))  # sorted, duplicates dropped
+    arrays['sample_index'] = idx.numpy().astype(np.float64)
+    idx = idx.to(state.flat.device)
+    vecs = {k: v.index_select(0, idx) for k, v in vecs.items()}
+  for k, v in vecs.items():
+    arrays[k] = v.detach().float().cpu().numpy()
+  total = sum(a.nbytes for a in arrays.values())
+  assert total <= DUMP_BUDGET, f'--dump-outputs would write {total} bytes'
+  for k, a in arrays.items():
+    np.save(os.path.join(out_dir, k + '.npy'), a)
+  return sorted(arrays), total
+
+
 def spawn_ranks(n: int, argv) -> int:
   """Start the n ranks of this same command under torch.distributed.run as a CHILD process (never an exec: the parent has not
   touched the GPU and does not need to, but a child keeps that true by construction), relay its output, return its exit status."""
@@ -297,7 +326,11 @@ def main():
   ap.add_argument('--frames', type=int, default=None)
   ap.add_argument('--no-cpu-baseline', action='store_true')
   ap.add_argument('--launch-check', action='store_true', help='prove the N-rank launch path over gloo and exit before any GPU call')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='after the timed steps, write what the last step returned and updated as DIR/<name>.npy (float32/float64, <= 64 MB)')
   args = ap.parse_args()
+  if args.steps < 1:
+    ap.error('--steps must be at least 1')
 
   if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:  # plain `python bench.py --gpus N`: start the ranks; nothing has touched a GPU
     sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -369,6 +402,10 @@ def main():
     dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
   dt = float(tmax.item())
   loss = float(metrics['train/loss'])
+  dumped = None
+  if args.dump_outputs and rank == 0:  # outside the timed region; every rank holds the same parameters and reduced gradients
+    names, nbytes = dump_outputs(args.dump_outputs, state, metrics)
+    dumped = {'dir': args.dump_outputs, 'files': names, 'bytes': nbytes}
   # N > 1 only, OUTSIDE the timed region: the same step with the gradient all-reduce in stream order behind the backward instead of under its last
   # chunk -- the A/B of the overlap ("record the A/B in the JSON when a node appears").  Two extra steps per rank.
   overlap_ab = None
@@ -402,6 +439,8 @@ def main():
     }
     if overlap_ab:
       out['config']['grad_allreduce_overlap_ab'] = overlap_ab
+    if dumped:
+      out['dumped_outputs'] = dumped
     if args.config in F_REF_FWD_PER_STEP_B64:
       scale = (B / 64.0) * (N / 2048.0) * (T / 150.0)  # F_ref scales ~linearly in B; other dims only for dev runs
       out['step_mfma_frac_F_ref'] = (3 * F_REF_FWD_PER_STEP_B64[args.config] * scale / (ms / 1e3)) / peak  # reference graph, nothing pruned

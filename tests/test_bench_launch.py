@@ -53,3 +53,44 @@ def test_config5_argument_path_and_whole_step_hbm_fields():
   assert 1e12 < by < 2e13  # TB per step: the activations of every op round-trip through HBM
   assert (warn is None) == (int(tag[1:]) >= bench.current_round())
   assert 'embed' in bench.CLASS_INFO
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path):
+  """--dump-outputs: the metrics and the four parameter-sized vectors of the state, float32 / float64, within the 64 MB budget; a state too large for
+  the budget is written as the same seeded sample of positions from each vector, identical from call to call."""
+  import types
+  import numpy as np
+  import torch
+  sys.path.insert(0, ROOT)
+  import bench
+  metrics = {'train/loss': torch.tensor(1.5), 'train/learning_rate': 1e-4, 'train/grad_norm': torch.tensor(2.0)}
+
+  def state(n):
+    g = torch.Generator().manual_seed(n)
+    return types.SimpleNamespace(**{k: torch.randn(n, generator=g) for k in ('flat', 'grads', 'm', 'v')})
+
+  small = state(1000)
+  names, nbytes = bench.dump_outputs(str(tmp_path / 'small'), small, metrics)
+  assert 'sample_index' not in names and nbytes <= bench.DUMP_BUDGET
+  assert np.array_equal(np.load(tmp_path / 'small' / 'grads.npy'), small.grads.numpy())
+  assert float(np.load(tmp_path / 'small' / 'train_loss.npy')) == 1.5
+
+  n = bench.DUMP_BUDGET // 16 + 1  # four fp32 vectors one element over the budget
+  big = state(n)
+  for d in ('a', 'b'):
+    names, nbytes = bench.dump_outputs(str(tmp_path / d), big, metrics)
+    assert 'sample_index' in names and nbytes <= bench.DUMP_BUDGET
+  total = 0
+  for f in os.listdir(tmp_path / 'a'):
+    a, b = np.load(tmp_path / 'a' / f), np.load(tmp_path / 'b' / f)
+    assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)
+    total += os.path.getsize(tmp_path / 'a' / f)
+  assert total <= bench.DUMP_BUDGET
+  idx = np.load(tmp_path / 'a' / 'sample_index.npy').astype(np.int64)
+  assert np.all(np.diff(idx) > 0) and idx[-1] < n
+  assert np.array_equal(np.load(tmp_path / 'a' / 'adam_v.npy'), big.v.numpy()[idx])
+
+
+def test_steps_must_be_positive():
+  r = _run(['--gpus', '1', '--steps', '0', '--launch-check'])
+  assert r.returncode == 2 and '--steps' in r.stderr

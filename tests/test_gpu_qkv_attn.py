@@ -97,7 +97,7 @@ def test_qkv_attention_fused_vs_oracle_and_two_kernel_path(lib, nseq, S, H, dtyp
 
 
 @pytest.mark.parametrize('precision', ['bf16', 'fp16'])
-def test_qkv_attention_fused_in_model_equals_the_two_kernel_path(precision):
+def test_qkv_attention_fused_in_model_equals_the_two_kernel_path(precision, tmp_path):
   """attn_impl 6 (the fused kernel in the track encoder's blocks, ragged pruned sequences included) against the default dispatch on the full-size T = 150 model:
   same rounding points, a different projection kernel (fp32 summation order), so the two runs differ like any two 16-bit paths of the suite do."""
   import os, sys
@@ -120,7 +120,7 @@ def test_qkv_attention_fused_in_model_equals_the_two_kernel_path(precision):
     ld, grads, preds = model.loss_and_grads({'params': gp}, gb, noise=noise.cuda(), return_predictions=True)
     torch.cuda.synchronize()
     lib_.spa3d_prof_dump.restype = C.c_int; lib_.spa3d_prof_dump.argtypes = [C.c_void_p, C.c_char_p]
-    path = f'/tmp/qa_prof_{precision}_{impl}.csv'
+    path = str(tmp_path / f'qa_prof_{precision}_{impl}.csv')
     assert lib_.spa3d_prof_dump(h, path.encode()) == 0
     lib_.spa3d_prof_enable(h, 0)
     spa3d._lib.check(lib_.spa3d_set_option(h, b'attn_impl', 0.0), h)
