@@ -104,27 +104,50 @@ __device__ __forceinline__ float wave_max(float v) {
 
 // ---- deterministic parameter gradients (spa3d_set_option "det_grads").  Every reduction INTO the flat gradient buffer (split-M dW tiles, bias / scale column sums,
 // broadcast gradients) is a float atomic by default: fast, and its result depends on arrival order in the last bits.  In this mode the same call sites add 64-bit FIXED-POINT
-// integers (2^-32 units: exact, order-independent) into a shadow of the gradient buffer, which det_flush adds to the float buffer once a range is final.  The switch is a
-// per-translation-unit device variable (no relocatable device code here), uploaded by det_upload_* at the start of a call; nullptr = float atomics.
-struct DetCfg { float* gbase; long long* shadow; long long n; unsigned* flag; };
+// integers (exact, order-independent) into a shadow of the gradient buffer, which det_flush adds to the float buffer once a range is final.  The switch is a
+// per-translation-unit device variable (no relocatable device code here), uploaded by det_upload_* on the call's stream at the start of a train call and cleared (all
+// null) at its end, and stated null by every op-level backward (ops.hip); nullptr = float atomics.
+// Unit: one integer step is 1 / *unit of the buffer's value, *unit = 2^(32 + e) with e = floor(log2(denom / (n_vis * loss scale))) clamped to [DET_E_MIN, DET_E_MAX]
+// (k_det_unit: a power of two, so the flush is exact; a gradient of this call scales as n_vis * loss scale / denom).  At a real batch n_vis ~ denom, so the unit is
+// 2^-32 as it always was (2^-(32 + log2 ranks) data-parallel); it only gets finer when the denominator exceeds the call's own visible count.  Range: an addend of
+// 2^55 units or more (or a NaN) sets the sticky flag instead of being added; a shadow sum of 2^62 units or more is taken as overflow by det_flush -- both flush NaN,
+// never a wrapped finite value.  2^62 / 2^55 = 128 addends at the bound fit; a sum can only wrap past the flush check with 384 or more addends all near the bound.
+// The single-query attention backward pre-sums in LDS and bounds its addends by 2^62 / (its problem count), so that sum cannot wrap either.
+struct DetCfg { float* gbase; long long* shadow; long long n; unsigned* flag; const float* unit; float scale; };   // scale: *unit, filled in by det_load
 static __device__ DetCfg det_cfg_dev;
-// A kernel with many additions loads the switch ONCE (det_load: scalar loads into SGPRs) and passes it along; re-reading the device variable at every addition cost the
-// large-tile dW kernel's 384-atomic epilogue and the single-query attention backward's inner loop 60 ms/step with the mode OFF (round 5, first version).
-__device__ __forceinline__ DetCfg det_load() { return det_cfg_dev; }
+constexpr float DET_ADDEND_MAX = 36028797018963968.f;   // 2^55 units
+constexpr long long DET_SUM_MAX = 1ll << 62;
+constexpr int DET_E_MIN = -24, DET_E_MAX = 40;   // the unit's exponent range (k_det_unit)
+// A kernel with many additions loads the switch ONCE (det_load: scalar loads into SGPRs, plus the unit when the mode is on) and passes it along; re-reading the device
+// variable at every addition cost the large-tile dW kernel's 384-atomic epilogue and the single-query attention backward's inner loop 60 ms/step with the mode OFF
+// (round 5, first version).
+__device__ __forceinline__ DetCfg det_load() { DetCfg d = det_cfg_dev; d.scale = d.shadow ? *d.unit : 4294967296.f; return d; }
 __device__ __forceinline__ bool det_on() { return det_cfg_dev.shadow != nullptr; }
 __device__ __forceinline__ void grad_add(const DetCfg& dc, float* p, float v) {
   if (dc.shadow) {
     const long long i = p - dc.gbase;
     if ((unsigned long long)i < (unsigned long long)dc.n) {
-      const float f = v * 4294967296.f;
-      if (fabsf(f) < 9.0e18f) atomicAdd((unsigned long long*)(dc.shadow + i), (unsigned long long)__float2ll_rn(f));   // NaN fails the comparison too
-      else atomicOr(dc.flag, 1u);                                                                                    // sticky: det_flush then writes NaN
+      const float f = v * dc.scale;
+      if (fabsf(f) < DET_ADDEND_MAX) atomicAdd((unsigned long long*)(dc.shadow + i), (unsigned long long)__float2ll_rn(f));   // NaN fails the comparison too
+      else atomicOr(dc.flag, 1u);                                                                                              // sticky: det_flush then writes NaN
       return;
     }
   }
   atomicAdd(p, v);
 }
 __device__ __forceinline__ void grad_add(float* p, float v) { grad_add(det_load(), p, v); }   // cold sites: one addition per thread at a workgroup's end
+// an addend already in fixed point (a workgroup's exact integer sum): straight into the shadow, no second rounding; |q| >= 2^62 is overflow
+__device__ __forceinline__ void grad_add_q(const DetCfg& dc, float* p, long long q) {
+  if (dc.shadow) {
+    const long long i = p - dc.gbase;
+    if ((unsigned long long)i < (unsigned long long)dc.n) {
+      if (q < DET_SUM_MAX && q > -DET_SUM_MAX) atomicAdd((unsigned long long*)(dc.shadow + i), (unsigned long long)q);
+      else atomicOr(dc.flag, 1u);
+      return;
+    }
+  }
+  atomicAdd(p, (float)((double)q / (double)dc.scale));
+}
 // (a one-thread kernel, not hipMemcpyToSymbolAsync: a copy from pageable host memory may block the host until the stream has drained)
 #define SPA_DET_UPLOAD_DEF(fn)                                                         \
   __global__ void fn##_kernel(DetCfg d) { det_cfg_dev = d; }                           \
@@ -214,8 +237,7 @@ struct spa3d_ctx {
   int qkv_attn = 0;       // track-encoder QKV projection + attention forward as ONE kernel (qkv_attn.hip): built and measured in round 5, 1.47x SLOWER than the
                           // projection GEMM + attention kernel pair (profiles/r05_qkv_attn_fused.log), so opt-in only: attn_impl 6
   int det_grads = 0;      // spa3d_set_option "det_grads": order-independent parameter gradients (fixed-point shadow accumulation, DetCfg above); costs a few %
-  int det_uploaded = 0;   // the device-side switch currently holds a live shadow (must be cleared by the next call that runs without it)
-  SPA_NS::DetCfg det_host = {nullptr, nullptr, 0, nullptr};  // what was uploaded last (kept alive for the asynchronous copy)
+  SPA_NS::DetCfg det_host = {nullptr, nullptr, 0, nullptr, nullptr, 0.f};  // what was uploaded last (kept alive for the asynchronous copy)
   int poison = 0;         // spa3d_set_option "poison": NaN-fill the workspace before every chunk and every op output before its launch (tests)
   bool tn_colsum_fused = false;  // set by gemm_tn_bf16: the last call also produced GemmDesc::colsum_out
   Prof prof;
@@ -401,7 +423,9 @@ void k_loss_finalize(spa3d_ctx*, const float* sums, const unsigned* poison, cons
 void k_adamw(spa3d_ctx*, float* p, const float* g, float* m, float* v, int64_t n, float lr, int64_t step, float clip, float b1, float b2,
              float eps, float wd, float* scratch);
 void k_uniform_noise(spa3d_ctx*, float* out, int64_t n, uint32_t k0, uint32_t k1);
-void k_det_flush(spa3d_ctx*, float* g, long long* shadow, const unsigned* flag, int64_t n);  // g[i] += shadow[i] * 2^-32; shadow[i] = 0; NaN when *flag
+void k_det_flush(spa3d_ctx*, float* g, long long* shadow, const unsigned* flag, const float* unit, int64_t n);  // g[i] += shadow[i] / *unit; shadow[i] = 0; NaN when *flag or |shadow[i]| >= 2^62
+void k_det_unit(spa3d_ctx*, const float* sums, const unsigned* poison, const float* denom_dev, const float* scale_dev, float* unit);  // DetCfg unit rule
+void det_upload_all(spa3d_ctx*, const SPA_NS::DetCfg*);  // every translation unit's switch, on the context's stream
 // single-query attention of the pruned last block (kernels.hip)
 template <typename T> void k_attn_q1_fwd(spa3d_ctx*, const T* q0, int64_t ldq0, const T* k, const T* v, int64_t ldk, int64_t ldv,
                                          const float* sq, const float* sk, const float* km, int64_t nseq, int S, int H, int Dh, T* o0,

@@ -1770,17 +1770,42 @@ __global__ void uniform_noise_kernel(float* __restrict__ out, int64_t n, int64_t
     if (half + j < n) out[half + j] = __uint_as_float((x1 >> 9) | 0x3F800000u) - 1.0f;
   }
 }
-// deterministic mode: fold the fixed-point shadow of a range of the gradient buffer into it (and clear the shadow: a later flush of the same range adds nothing)
-__global__ __launch_bounds__(256) void det_flush_kernel(float* __restrict__ g, long long* __restrict__ shadow, const unsigned* __restrict__ flag, int64_t n) {
+// deterministic mode: fold the fixed-point shadow of a range of the gradient buffer into it (and clear the shadow: a later flush of the same range adds nothing).
+// A sum of 2^62 units or more is overflow (common.hpp DetCfg): NaN, like the sticky flag -- a wrapped sum must never reach the buffer as a finite value.
+__global__ __launch_bounds__(256) void det_flush_kernel(float* __restrict__ g, long long* __restrict__ shadow, const unsigned* __restrict__ flag,
+                                                        const float* __restrict__ unit, int64_t n) {
   const bool bad = *flag != 0;
+  const double inv = 1.0 / (double)*unit;   // a power of two: exact
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const long long q = shadow[i];
-    if (q != 0 || bad) { g[i] = bad ? __int_as_float(0x7fc00000) : g[i] + (float)((double)q * (1.0 / 4294967296.0)); shadow[i] = 0; }
+    if (q != 0 || bad) {
+      const bool ovf = bad || q >= DET_SUM_MAX || q <= -DET_SUM_MAX;
+      g[i] = ovf ? __int_as_float(0x7fc00000) : g[i] + (float)((double)q * inv); shadow[i] = 0;
+    }
   }
 }
-void k_det_flush(spa3d_ctx* c, float* g, long long* shadow, const unsigned* flag, int64_t n) {
+void k_det_flush(spa3d_ctx* c, float* g, long long* shadow, const unsigned* flag, const float* unit, int64_t n) {
   if (c->dry || n <= 0) return;
-  det_flush_kernel<<<(unsigned)std::min<int64_t>(cdiv(n, 256), 8192), 256, 0, c->stream>>>(g, shadow, flag, n); SPA_LAUNCH_CHECK(c);
+  det_flush_kernel<<<(unsigned)std::min<int64_t>(cdiv(n, 256), 8192), 256, 0, c->stream>>>(g, shadow, flag, unit, n); SPA_LAUNCH_CHECK(c);
+}
+// the fixed-point unit of a det_grads call (common.hpp DetCfg): 2^(32 + e), e = floor(log2(denom / (n_vis * loss scale))) clamped to [-24, 40].  Inputs are the call's
+// global denominator, its own visible count and its loss scale, so the unit is a function of the call's inputs alone (bit-equal run to run and whatever the
+// all-reduce schedule).  -24 covers the fp16 mode at BASELINE configs[2] (e ~ -14); below it the unit stops coarsening and the range guards take over.
+__global__ void det_unit_kernel(const float* sums, const unsigned* poison, const float* denom_dev, const float* scale_dev, float* unit) {
+  const float nvis = fmaxf(loss_acc_read((const unsigned long long*)sums + 2, poison), 1.f);   // fmaxf(NaN, 1) = 1
+  const float r = *denom_dev / (nvis * (scale_dev ? *scale_dev : 1.f));
+  int e = 0;
+  if (r > 0.f && r <= 3.0e38f) { (void)frexpf(r, &e); e = min(max(e - 1, DET_E_MIN), DET_E_MAX); }   // r = m 2^e', m in [0.5, 1): floor(log2 r) = e' - 1, exactly
+  *unit = ldexpf(1.f, 32 + e);
+}
+void k_det_unit(spa3d_ctx* c, const float* sums, const unsigned* poison, const float* denom_dev, const float* scale_dev, float* unit) {
+  if (c->dry) return;
+  det_unit_kernel<<<1, 1, 0, c->stream>>>(sums, poison, denom_dev, scale_dev, unit); SPA_LAUNCH_CHECK(c);
+}
+void det_upload_all(spa3d_ctx* c, const DetCfg* d) {
+  if (c->dry) return;
+  det_upload_kernels(c->stream, d); det_upload_gemm_fast(c->stream, d); det_upload_gemm_tnb(c->stream, d); det_upload_gemm_generic(c->stream, d);
+  det_upload_attn(c->stream, d);
 }
 void k_uniform_noise(spa3d_ctx* c, float* out, int64_t n, uint32_t k0, uint32_t k1) {
   if (c->dry || n == 0) return;
@@ -1983,7 +2008,7 @@ __global__ __launch_bounds__(256) void attn_q1_bwd_kernel(const T* __restrict__ 
   __shared__ float dps[4][Q1_MAXS];
   __shared__ float scl[2][4 * CC];  // s_q, s_k in lane-channel order [part][j]
   __shared__ float red[2][4 * CC];  // block accumulators of d s_q, d s_k
-  __shared__ unsigned long long redq[DET ? 2 : 1][DET ? 4 * CC : 1];  // DET: the same in 2^-32 fixed point (integer LDS atomics do not depend on arrival order)
+  __shared__ unsigned long long redq[DET ? 2 : 1][DET ? 4 * CC : 1];  // DET: the same in the shadow's fixed point (integer LDS atomics do not depend on arrival order)
   constexpr int Dh = CC * 4;
   constexpr int NV = VecOf<T>::N;
   constexpr int G = (CC % NV == 0) ? NV : 1;  // output chunk; vec implies G == NV
@@ -1998,6 +2023,14 @@ __global__ __launch_bounds__(256) void attn_q1_bwd_kernel(const T* __restrict__ 
     const int ch = q1_chan<T, CC>(j, pt, vec);
     scl[0][t] = sq[ch]; scl[1][t] = sk[ch]; red[0][t] = 0.f; red[1][t] = 0.f;
     if constexpr (DET) { redq[0][t] = 0ull; redq[1][t] = 0ull; }
+  }
+  DetCfg dc{};
+  float qlim = 0.f;
+  if constexpr (DET) {   // the unit and the overflow flag of the call (common.hpp DetCfg)
+    dc = det_load();
+    // one redq entry takes one addend per problem of this workgroup: bounding each by 2^62 / (that count) keeps the LDS sum below 2^62, so it cannot wrap
+    const int64_t per = 4 * ((nprob + 4 * (int64_t)gridDim.x - 1) / (4 * (int64_t)gridDim.x));
+    qlim = fminf(DET_ADDEND_MAX, 4.6116860184273879e18f / (float)(per > 0 ? per : 1));
   }
   __syncthreads();
   for (int64_t prob = (int64_t)blockIdx.x * 4 + wv; prob < nprob; prob += (int64_t)gridDim.x * 4) {
@@ -2095,8 +2128,11 @@ __global__ __launch_bounds__(256) void attn_q1_bwd_kernel(const T* __restrict__ 
         const float dqh = u[j] * skl[j];
         // (deterministic mode: LDS float atomics depend on arrival order too -- every contribution goes straight to the fixed-point shadow)
         if constexpr (DET) {
-          atomicAdd(&redq[1][part * CC + j], (unsigned long long)__float2ll_rn(qs[j] * u[j] * 4294967296.f));
-          atomicAdd(&redq[0][part * CC + j], (unsigned long long)__float2ll_rn(dqh * xq[j] * 4294967296.f));
+          const float fk = qs[j] * u[j] * dc.scale, fq = dqh * xq[j] * dc.scale;   // grad_add's per-addend bound, tightened to the workgroup's count (NaN fails it too)
+          if (fabsf(fk) < qlim && fabsf(fq) < qlim) {
+            atomicAdd(&redq[1][part * CC + j], (unsigned long long)__float2ll_rn(fk));
+            atomicAdd(&redq[0][part * CC + j], (unsigned long long)__float2ll_rn(fq));
+          } else atomicOr(dc.flag, 1u);
         } else { atomicAdd(&red[1][part * CC + j], qs[j] * u[j]); atomicAdd(&red[0][part * CC + j], dqh * xq[j]); }
         xq[j] = rq * (dqh * sql[j] - xq[j] * gq);
       }
@@ -2107,8 +2143,8 @@ __global__ __launch_bounds__(256) void attn_q1_bwd_kernel(const T* __restrict__ 
   for (int t = threadIdx.x; t < 4 * CC; t += 256) {
     const int pt = t / CC, j = t - pt * CC;
     const int ch = q1_chan<T, CC>(j, pt, vec);
-    if constexpr (DET) {  // (a non-finite partial saturates the conversion: the 16-bit dq / dk / dv beside it are NaN already and reach every upstream leaf)
-      grad_add(dsq + ch, (float)((double)(long long)redq[0][t] * (1.0 / 4294967296.0))); grad_add(dsk + ch, (float)((double)(long long)redq[1][t] * (1.0 / 4294967296.0)));
+    if constexpr (DET) {  // the workgroup's exact integer sums go to the shadow as they are (|sum| >= 2^62: the flag)
+      grad_add_q(dc, dsq + ch, (long long)redq[0][t]); grad_add_q(dc, dsk + ch, (long long)redq[1][t]);
     } else { atomicAdd(dsq + ch, red[0][t]); atomicAdd(dsk + ch, red[1][t]); }
   }
 }

@@ -166,8 +166,14 @@ int spa3d_adamw_step(float* params, const float* grads, float* m, float* v, int6
  *   "attn_impl"       0 product dispatch | 1 generic composition | 2 fused kernels | 3, 4 fused with the split-pass backward on 4 / 8 waves (tests) |
  *                     6 fused kernels with the track encoder's QKV projection + attention forward as one launch (built in round 5, slower than the pair: opt-in)
  *   "det_grads"  0/1  order-independent parameter gradients: every reduction into the gradient buffer (split-M dW tiles, bias / scale column sums, broadcast
- *                     gradients) adds 64-bit fixed-point integers (2^-32 units) into a shadow of the buffer instead of float atomics, so two runs -- and two
- *                     data-parallel schedules -- give the same bits.  Costs 8 bytes of workspace per parameter and ~3.6 % of the step at BASELINE configs[2]
+ *                     gradients) adds 64-bit fixed-point integers into a shadow of the buffer instead of float atomics, so two runs -- and two
+ *                     data-parallel schedules -- give the same bits.  Unit: 2^-(32 + e) of the buffer's value with e = floor(log2(denom / (n_vis *
+ *                     loss scale))), n_vis = this call's visible query points, clamped to [-24, 40]: a power of two chosen per call from its inputs alone.
+ *                     With a real batch n_vis ~ denom, so the unit is 2^-32 as before (2^-(32 + log2 ranks) data-parallel; fp16: follows the loss
+ *                     scale); it is finer only when the denominator exceeds the call's own visible count.  Range: an addend of 2^55 units or more, or a
+ *                     shadow sum of 2^62 units or more, turns the whole gradient buffer of the call into NaN -- never a wrapped finite value.  The switch holds only for the
+ *                     train call that set it: it is cleared on the call's stream at its end, and the spa3d_op_*_bwd entry points always use float atomics.
+ *                     Costs 8 bytes of workspace per parameter and ~3.6 % of the step at BASELINE configs[2]
  *                     (1.82 -> 1.88 s: 64-bit atomics in the dW epilogues, the 1-channel depth gradient on the GEMM path); off by default.
  * and one test mode: "poison" 0/1 -- the workspace is filled with 16-bit NaN patterns before every sample chunk, so a read of a row that this
  * call has not written (the rounded-up tails of pruned GEMMs, chunk-to-chunk reuse of the bump allocator) shows up as NaN instead of as a

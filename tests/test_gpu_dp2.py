@@ -116,5 +116,8 @@ def test_hip_trainstate_world2_several_chunks_overlap_on_and_off(tmp_path, prec,
     assert d01 < 1e-5 and all(abs(x - y) <= 1e-6 * abs(x) for x, y in zip(outs['ov1'][0]['losses'], outs['ov0'][0]['losses']))
     assert diff < 3e-5
   else:  # 16-bit activations: an AdamW step at lr 1e-2 moves a parameter by <= 1e-2 whatever the gradient's size, so last-bit gradient noise of tiny leaves shows
-    assert d01 < 2e-2 and all(abs(x - y) <= 1e-3 * abs(x) for x, y in zip(outs['ov1'][0]['losses'], outs['ov0'][0]['losses']))
-    assert diff < 3e-2
+    # measured: d01 1.376e-4 (profiles/r05_det_grads.log), 3.174e-4 (profiles/r06_det_grads_edges.log, fp16 det 0); diff 2.921e-4 (det 0), 2.497e-4 (det 1), same
+    # log.  The old gates (2e-2, 3e-2) were the largest
+    # move AdamW at lr 1e-2 can make in three steps, so they could not fail
+    assert d01 < 2e-3 and all(abs(x - y) <= 1e-3 * abs(x) for x, y in zip(outs['ov1'][0]['losses'], outs['ov0'][0]['losses']))
+    assert diff < 3e-3
