@@ -213,6 +213,8 @@ struct spa3d_ctx {
   int gemm_impl = 0;  // 0 auto, 1 generic only, 2 tiled (see apply_gemm_impl)
   int attn_impl = 0;  // 0 auto, 1 generic, 2 fused (see apply_attn_impl)
   int chunk = 0;      // samples per chunk: 0 = as many as fit the workspace (spa3d_set_option "chunk")
+  int query_chunk = 0;    // spa3d_set_option "query_chunk": readout over chunks of this many queries (0 = all Q at once); implies one sample per chunk
+  int track_chunk = 0;    // spa3d_set_option "track_chunk": track encoder over chunks of this many tracks, recomputed in the backward (0 = off); one sample per chunk
   int ro_share = 1;       // readout block 1: LayerNorm / QKV once per distinct (sample, query frame) instead of per query (16-bit modes); SPA3D_RO_SHARE=0 disables
   int prune = 1;          // drop masked frame tokens from the track encoder (3DSPA model, fused 16-bit attention path); SPA3D_PRUNE=0 disables
   float loss_scale = 1.f;  // the 16-bit backward runs at loss x scale, parameter gradients are scaled back at the end: 1 = off (bf16 / fp32),
@@ -410,7 +412,7 @@ template <typename T> void k_share_expand(spa3d_ctx*, const T* srcU, const int32
 template <typename T> void k_share_reduce(spa3d_ctx*, const T* src, const int32_t* slot, const int32_t* slot_b, int64_t nslot, int64_t nseq, int Q, int S, int d,
                                           T* dstU);
 template <typename T> void k_assemble_readout_bwd(spa3d_ctx*, const T* dseq, const int32_t* qframe, int64_t B, int Q, int L, int Cl, int D,
-                                                  T* dqtok, float* dlat);
+                                                  T* dqtok, float* dlat, bool accumulate = false);
 void k_loss_fwd(spa3d_ctx*, const float* head, int64_t nq, int T_, const float* tgt, const float* tvis, float* tracks, float* vlog,
                 float* clog, float* sums, unsigned* poison, int NC = 3);
 void k_loss_from_preds(spa3d_ctx*, const float* tracks, const float* vlog, int64_t n, const float* tgt, const float* tvis, float* sums,

@@ -1469,7 +1469,8 @@ void k_assemble_readout(spa3d_ctx* c, const T* qtok, const T* lat, const int32_t
   SPA_LAUNCH_CHECK(c);
 }
 // backward: dqtok = dseq[:, :, 0, :] ; dlat[b][n][c] = sum_q dseq[b][q][1+n][c] + sum_q dseq[b][q][1+n][Cl + c-5t_q] 1[0<=c-5t_q<D-Cl]
-template <typename T>
+// ACC: dlat += that sum instead (query chunks, model.hip: one plain fp32 add per element in stream order -- no atomics, fixed order)
+template <typename T, bool ACC>
 __global__ void assemble_bwd_lat_kernel(const T* __restrict__ dseq, const int32_t* __restrict__ qframe, int64_t B, int Q, int L, int Cl,
                                         int D, float* __restrict__ dlat) {
   const int64_t tot = B * L * Cl;
@@ -1488,15 +1489,17 @@ __global__ void assemble_bwd_lat_kernel(const T* __restrict__ dseq, const int32_
     int q = 0;
     for (; q + 3 < Q; q += 4) { s0 += term(q); s1 += term(q + 1); s2 += term(q + 2); s3 += term(q + 3); }
     for (; q < Q; ++q) s0 += term(q);
-    dlat[i] = (s0 + s1) + (s2 + s3);
+    const float s = (s0 + s1) + (s2 + s3);
+    if (ACC) dlat[i] += s; else dlat[i] = s;
   }
 }
 template <typename T>
 void k_assemble_readout_bwd(spa3d_ctx* c, const T* dseq, const int32_t* qframe, int64_t B, int Q, int L, int Cl, int D, T* dqtok,
-                            float* dlat) {
+                            float* dlat, bool accumulate) {
   if (c->dry || B == 0) return;
   k_gather_rows<T>(c, dseq, L + 1, dqtok, B * Q, D);
-  assemble_bwd_lat_kernel<T><<<GRID1D(B * L * Cl, 256), 256, 0, c->stream>>>(dseq, qframe, B, Q, L, Cl, D, dlat);
+  if (accumulate) assemble_bwd_lat_kernel<T, true><<<GRID1D(B * L * Cl, 256), 256, 0, c->stream>>>(dseq, qframe, B, Q, L, Cl, D, dlat);
+  else assemble_bwd_lat_kernel<T, false><<<GRID1D(B * L * Cl, 256), 256, 0, c->stream>>>(dseq, qframe, B, Q, L, Cl, D, dlat);
   SPA_LAUNCH_CHECK(c);
 }
 
@@ -1847,7 +1850,7 @@ void k_uniform_noise(spa3d_ctx* c, float* out, int64_t n, uint32_t k0, uint32_t 
   template void k_share_assemble<T>(spa3d_ctx*, const T*, const T*, const int32_t*, const int32_t*, int64_t, int64_t, int, int, int, T*);   \
   template void k_share_expand<T>(spa3d_ctx*, const T*, const int32_t*, const int32_t*, int64_t, int64_t, int, int, const T*, T*);    \
   template void k_share_reduce<T>(spa3d_ctx*, const T*, const int32_t*, const int32_t*, int64_t, int64_t, int, int, int, T*);         \
-  template void k_assemble_readout_bwd<T>(spa3d_ctx*, const T*, const int32_t*, int64_t, int, int, int, int, T*, float*);              \
+  template void k_assemble_readout_bwd<T>(spa3d_ctx*, const T*, const int32_t*, int64_t, int, int, int, int, T*, float*, bool);              \
   template void k_loss_bwd<T>(spa3d_ctx*, const float*, int64_t, int, const float*, const float*, const float*, float, float, T*, int, const float*);
 INST(float)
 INST(bf16_t)

@@ -469,6 +469,9 @@ template <typename T> struct Net {
   // ------------------------------------------------------------------ per-chunk state
   struct Chunk {
     int64_t Bc, nseq; int N, Q, T_, S;
+    // intra-sample slices (run_body: "track_chunk" / "query_chunk", one sample per chunk): the track encoder runs on tracks [n_off, n_off + Nc) of the
+    // sample (nseq = Bc * Nc; the cross attention of tracks_to_latents still sees all N), the readout on queries [q_off, q_off + Qc)
+    int64_t n_off = 0, q_off = 0; int Nc = 0, Qc = 0; bool count_plan = true;  // count_plan: false for the backward's recompute (spa3d_plan_stats counts pass A only)
     // encoder
     T* sinbuf; const void* dino; const void* depthf; float* km; T* tok0; std::vector<BlockStash<T>> enc_st; T* enc_last; T* r0; float* st_r0;
     T* enc_out; LastStash enc_lst, ro_lst; T* enc_ln_all = nullptr; float* st_all = nullptr; const float* sup_vis = nullptr;
@@ -483,10 +486,15 @@ template <typename T> struct Net {
 
   // E1-E7 + L1-L3 (track_autoencoder_3d.py:123-204)
   void encode_chunk(Chunk& k, const spa3d_batch* b, int64_t b0, bool train) {
+    encode_tracks(k, b, b0, train);
+    encode_latents(k, train);
+  }
+  // E1-E7 on tracks [k.n_off, k.n_off + k.Nc) of samples [b0, b0 + k.Bc) -> k.enc_out [nseq, d] (written to enc_dst when given, else allocated here)
+  void encode_tracks(Chunk& k, const spa3d_batch* b, int64_t b0, bool train, T* enc_dst = nullptr) {
     const int d = g.track_token_dim, nf = g.num_frequencies, T_ = k.T_, S = k.S;
-    const int64_t nseq = k.nseq;
-    const float* tracks = b->support_tracks + b0 * k.N * T_ * NC;
-    k.sup_vis = b->support_tracks_visible + b0 * k.N * T_;
+    const int64_t nseq = k.nseq, trk0 = b0 * k.N + k.n_off;  // first track row of the slice (tracks of a sample chunk are contiguous when Nc < N: Bc = 1)
+    const float* tracks = b->support_tracks + trk0 * T_ * NC;
+    k.sup_vis = b->support_tracks_visible + trk0 * T_;
     // embed stage (3d:123-165) as one profile class: algorithmic bytes = what a single pass would move (xyz f32 + visibility + the 16-bit
     // dino / depth planes in, the kept token rows out); FLOPs of its projections
     ProfScope* eps = nullptr;
@@ -498,8 +506,8 @@ template <typename T> struct Net {
     k.sinbuf = alloc<T>(nseq * T_ * (NC + 1) * 2 * nf);
     k_embed_tokens<T>(c, tracks, nseq * T_, T_, nf, g.track_scale_factor, k.sinbuf, NC);             // 3d:126-134 / ta:186-199
     k.km = alloc<float>(nseq * S);
-    if (twoD) k_keymask2d(c, k.sup_vis, b->boundary_frame + b0, nseq, k.N, T_, k.km);                // ta:213-223
-    else k_keymask(c, k.sup_vis, b->boundary_frame + b0, nseq, k.N, T_, k.km);                       // 3d:167-180 (R2,R3)
+    if (twoD) k_keymask2d(c, k.sup_vis, b->boundary_frame + b0, nseq, k.Nc, T_, k.km);               // ta:213-223
+    else k_keymask(c, k.sup_vis, b->boundary_frame + b0, nseq, k.Nc, T_, k.km);                      // 3d:167-180 (R2,R3)
     // Token pruning (3DSPA, fused 16-bit attention): a frame token whose key is masked is attended to by nobody, and only token 0 leaves
     // the stack (3d:187-188), so its row influences neither the output nor any gradient: the encoder runs on the kept rows only.
     k.enc_rg = Rag(); k.row_src = nullptr;
@@ -507,13 +515,13 @@ template <typename T> struct Net {
     if (can_prune) {
       int32_t* cnt = alloc<int32_t>(nseq); int32_t* off = alloc<int32_t>(nseq + 1); k.row_src = alloc<int32_t>(nseq * S);
       const int64_t kept = k_prune_plan(c, k.km, nseq, S, cnt, off, k.row_src);
-      if (!c->dry) { c->plan_stats[0] += (double)kept; c->plan_stats[1] += (double)(nseq * S); }
+      if (!c->dry && k.count_plan) { c->plan_stats[0] += (double)kept; c->plan_stats[1] += (double)(nseq * S); }
       if (c->dry || kept < nseq * S) { k.enc_rg.off = off; k.enc_rg.rows = kept; }   // (the sizing dry run takes this branch at the dense count)
     }
     const Rag& rg = k.enc_rg;
     const int64_t rows = rg.off ? rg.rows : nseq * S, rows_g = rg.off ? (rows + 7) & ~int64_t(7) : rows;
-    k.dino = (!twoD && g.dino_feature_dim > 0 && b->dino_features) ? (const T*)b->dino_features + b0 * k.N * T_ * g.dino_feature_dim : nullptr;
-    k.depthf = (!twoD && g.depth_feature_dim > 0 && b->depth_features) ? (const T*)b->depth_features + b0 * k.N * T_ * g.depth_feature_dim : nullptr;
+    k.dino = (!twoD && g.dino_feature_dim > 0 && b->dino_features) ? (const T*)b->dino_features + trk0 * T_ * g.dino_feature_dim : nullptr;
+    k.depthf = (!twoD && g.depth_feature_dim > 0 && b->depth_features) ? (const T*)b->depth_features + trk0 * T_ * g.depth_feature_dim : nullptr;
     bool emb_done = false;
     if constexpr (sizeof(T) == 2) {
       // K1: the three Denses are ONE Dense on the concatenated row (repair R4) -- one GEMM over K = 256 sin features + 768 DINO columns
@@ -572,7 +580,7 @@ template <typename T> struct Net {
       x = y;
     }
     k.enc_last = const_cast<T*>(x);
-    k.enc_out = alloc<T>(nseq * d);
+    k.enc_out = enc_dst ? enc_dst : alloc<T>(nseq * d);
     if (twoD) {
       k.enc_ln_all = alloc<T>(nseq * S * d); k.st_all = alloc<float>(nseq * S * 2);
       k_layernorm<T>(c, x, enc.norm_enc, k.enc_ln_all, k.st_all, nseq * S, d);                       // attention.py:49-51
@@ -582,8 +590,11 @@ template <typename T> struct Net {
       block_fwd_last(enc.blocks[nenc - 1], x, k.r0, nseq, S, km, train ? &k.enc_lst : nullptr, rg);  // token 0 only: 3d:187-188
       k_layernorm<T>(c, k.r0, enc.norm_enc, k.enc_out, k.st_r0, nseq, d);                            // attention.py:49-51 (row 0 only)
     }
-    // L1-L3
+  }
+  // L1-L3: k.enc_out holds all k.Bc * k.N encoder outputs
+  void encode_latents(Chunk& k, bool train) {
     const int L = g.num_latent_tokens, dl = g.encoder_latent_dim;
+    const T* x;
     k.lat_in = alloc<T>(k.Bc * L * dl);
     k_broadcast_rows<T>(c, lat0, L, dl, k.lat_in, k.Bc);                                             // 3d:200
     x = k.lat_in;
@@ -600,10 +611,10 @@ template <typename T> struct Net {
     lin_fwd(comp, k.t2l_n, k.latents, k.Bc * L, EPI_NONE, nullptr, 1);                               // 3d:203
   }
 
-  // D1-D8 (track_autoencoder_3d.py:206-307).  latents_in: [Bc,L,Ld] f32
-  void decode_chunk(Chunk& k, const spa3d_batch* b, int64_t b0, const float* latents_in, const float* noise, bool train) {
-    const int L = g.num_latent_tokens, Ld = g.latent_token_dim, dd = g.decoder_num_channels, Cl = dd - 128, nf = g.num_frequencies;
-    const int64_t nl = k.Bc * L, nq = k.Bc * k.Q;
+  // D1-D7: discretise, decompressor, decoder stack -> k.latd [Bc,L,Cl] (once per sample chunk)
+  void decode_latents(Chunk& k, const spa3d_batch* b, const float* latents_in, const float* noise, int64_t b0, bool train) {
+    const int L = g.num_latent_tokens, Ld = g.latent_token_dim, dd = g.decoder_num_channels, Cl = dd - 128;
+    const int64_t nl = k.Bc * L;
     k.clipmask = alloc<float>(nl * Ld); k.lat_q = alloc<float>(nl * Ld); k.lat_qT = alloc<T>(nl * Ld);
     k_discretize(c, latents_in, noise ? noise + b0 * L * Ld : nullptr, b->discretize, k.lat_q, k.clipmask, nl * Ld);  // 3d:251-260
     k_cast_from_f32<T>(c, k.lat_q, k.lat_qT, nl * Ld);
@@ -619,10 +630,21 @@ template <typename T> struct Net {
     k.dec_last = const_cast<T*>(x);
     k.st_dec = alloc<float>(nl * 2); k.latd = alloc<T>(nl * Cl);
     k_layernorm<T>(c, x, dec.norm_enc, k.latd, k.st_dec, nl, Cl);
+  }
+  // D1-D8 (track_autoencoder_3d.py:206-307).  latents_in: [Bc,L,Ld] f32
+  void decode_chunk(Chunk& k, const spa3d_batch* b, int64_t b0, const float* latents_in, const float* noise, bool train) {
+    decode_latents(k, b, latents_in, noise, b0, train);
+    decode_queries(k, b, b0, train);
+  }
+  // query tokens, readout stack and head of queries [k.q_off, k.q_off + k.Qc) of samples [b0, b0 + k.Bc) against k.latd
+  void decode_queries(Chunk& k, const spa3d_batch* b, int64_t b0, bool train) {
+    const int L = g.num_latent_tokens, dd = g.decoder_num_channels, Cl = dd - 128, nf = g.num_frequencies;
+    const int64_t nq = k.Bc * k.Qc;
+    const T* x;
     // query tokens                                                                                     3d:209-233,265-275
     const int F = NC * 2 * nf + 1;
     k.feat = alloc<float>(nq * F); k.qframe = alloc<int32_t>(nq);
-    k_query_embed1(c, b->query_points + b0 * k.Q * (NC + 1), nq, nf, g.track_scale_factor, g.time_scale_factor, k.feat, k.qframe, NC);
+    k_query_embed1(c, b->query_points + (b0 * k.Q + k.q_off) * (NC + 1), nq, nf, g.track_scale_factor, g.time_scale_factor, k.feat, k.qframe, NC);
     k.sin2 = alloc<T>(nq * F * 2 * nf);
     k_sin_embed<T>(c, k.feat, nq, F, nf, g.track_scale_factor, k.sin2);
     k.qtok = alloc<T>(nq * dd);
@@ -630,20 +652,20 @@ template <typename T> struct Net {
     // readout sequences                                                                                3d:276-285
     const int S = L + 1;
     k.seq0 = alloc<T>(nq * S * dd);
-    k_assemble_readout<T>(c, k.qtok, k.latd, k.qframe, k.Bc, k.Q, L, Cl, dd, k.seq0);
+    k_assemble_readout<T>(c, k.qtok, k.latd, k.qframe, k.Bc, k.Qc, L, Cl, dd, k.seq0);
     x = k.seq0;
     const int nro = (int)ro.blocks.size();
     k.ro_st.resize(nro);
     // first block: LN1 / QKV once per distinct (sample, query frame) -- see Share.  One stream sync reads the slot count.
     k.ro_sh = Share<T>(); k.ro_share = false;
-    if (sizeof(T) == 2 && c->ro_share && nro >= 2 && dd % 8 == 0 && Cl % 8 == 0 && k.Q >= 8) {
+    if (sizeof(T) == 2 && c->ro_share && nro >= 2 && dd % 8 == 0 && Cl % 8 == 0 && k.Qc >= 8) {
       int32_t* slot = alloc<int32_t>(nq); int32_t* slot_b = alloc<int32_t>(nq); int32_t* slot_f = alloc<int32_t>(nq);
       int32_t* slot_q0 = alloc<int32_t>(nq); int32_t* scratch = alloc<int32_t>(nq + k.Bc + 1);
       Share<T>& sh = k.ro_sh;
-      sh.slot = slot; sh.slot_b = slot_b; sh.slot_q0 = slot_q0; sh.Q = k.Q;
+      sh.slot = slot; sh.slot_b = slot_b; sh.slot_q0 = slot_q0; sh.Q = k.Qc;
       if (c->dry) { sh.nslot = (int64_t)(SHARE_MAX_FRAC * (double)nq); sh.probe = true; k.ro_share = true; }
       else {
-        sh.nslot = k_share_plan(c, k.qframe, k.Bc, k.Q, slot, slot_b, slot_f, slot_q0, scratch);
+        sh.nslot = k_share_plan(c, k.qframe, k.Bc, k.Qc, slot, slot_b, slot_f, slot_q0, scratch);
         c->plan_stats[2] += (double)sh.nslot; c->plan_stats[3] += (double)nq;
         if ((double)sh.nslot <= SHARE_MAX_FRAC * (double)nq) {
           T* xU = alloc<T>(((sh.rows(nq, S) + 7) & ~int64_t(7)) * dd);
@@ -690,16 +712,24 @@ template <typename T> struct Net {
   }
   // full backward of one chunk; parameter gradients accumulate into G
   void backward_chunk(Chunk& k, const spa3d_batch* b, int64_t b0, const float* denom_dev) {
-    const int L = g.num_latent_tokens, Ld = g.latent_token_dim, dd = g.decoder_num_channels, Cl = dd - 128, To = g.num_output_frames;
-    const int d = g.track_token_dim, dl = g.encoder_latent_dim, T_ = k.T_;
-    const int64_t nl = k.Bc * L, nq = k.Bc * k.Q, nseq = k.nseq;
+    const int L = g.num_latent_tokens, Cl = g.decoder_num_channels - 128;
     const int64_t mk0 = c->ar.mark();
-    float* dlatd32 = alloc<float>(nl * Cl);
-    {  // ---- head, readout transformer, assembly, query encoder
+    float* dlatd32 = alloc<float>(k.Bc * L * Cl);
+    backward_queries(k, b, b0, denom_dev, dlatd32, false);
+    grad_segment_done(0);  // track_readout_attn, query_encoder, track_predictor: final once the LAST chunk has come this far
+    T* denc_out = backward_latents(k, dlatd32);
+    backward_tracks(k, denc_out);
+    c->ar.release(mk0);
+  }
+  // head, readout transformer, assembly, query encoder of queries [k.q_off, k.q_off + k.Qc): dlatd32 [Bc,L,Cl] = (accumulate ? += : =) the latent-side gradient
+  void backward_queries(Chunk& k, const spa3d_batch* b, int64_t b0, const float* denom_dev, float* dlatd32, bool accumulate) {
+    const int L = g.num_latent_tokens, dd = g.decoder_num_channels, Cl = dd - 128, To = g.num_output_frames;
+    const int64_t nq = k.Bc * k.Qc, qrow = b0 * k.Q + k.q_off;
+    {
       const int S = L + 1;
       const int64_t mk = c->ar.mark();
       T* dhead = alloc<T>(nq * 4 * To);
-      k_loss_bwd<T>(c, k.head, nq, To, b->query_tracks + b0 * k.Q * To * NC, b->query_tracks_visible + b0 * k.Q * To, denom_dev,
+      k_loss_bwd<T>(c, k.head, nq, To, b->query_tracks + qrow * To * NC, b->query_tracks_visible + qrow * To, denom_dev,
                     L1_WEIGHT, BCE_WEIGHT, dhead, NC, c->loss_scale != 1.f ? denom_dev + 1 : nullptr);  // + loss scale in fp16 mode
       lin_bwd_w(pred, k.q0n, dhead, nq);
       T* dq0n = alloc<T>(nq * dd);
@@ -712,12 +742,16 @@ template <typename T> struct Net {
       block_bwd_last(ro.blocks[nro - 1], k.ro_lst, dq0, dseq, nq, S, nullptr);
       for (int i = nro - 2; i >= 0; --i)
         block_bwd(ro.blocks[i], k.ro_st[i], dseq, dseq, nq, S, nullptr, nullptr, 0, nullptr, Rag(), (i == 0 && k.ro_share) ? &k.ro_sh : nullptr);
-      k_assemble_readout_bwd<T>(c, dseq, k.qframe, k.Bc, k.Q, L, Cl, dd, dqtok, dlatd32);
+      k_assemble_readout_bwd<T>(c, dseq, k.qframe, k.Bc, k.Qc, L, Cl, dd, dqtok, dlatd32, accumulate);
       lin_bwd_w(qenc, k.sin2, dqtok, nq);
       c->ar.release(mk);
     }
-    grad_segment_done(0);  // track_readout_attn, query_encoder, track_predictor: final once the LAST chunk has come this far
-    // ---- decompress_attn, decompressor, straight-through clip, compressor
+  }
+  // decompress_attn, decompressor, straight-through clip, compressor, tracks_to_latents (+ state_init) from the latent-side gradient -> d enc_out [Bc * N, d]
+  T* backward_latents(Chunk& k, const float* dlatd32) {
+    const int L = g.num_latent_tokens, Ld = g.latent_token_dim, dd = g.decoder_num_channels, Cl = dd - 128;
+    const int d = g.track_token_dim, dl = g.encoder_latent_dim;
+    const int64_t nl = k.Bc * L;
     T* ddec = alloc<T>(nl * Cl);
     {
       T* dlatd = alloc<T>(nl * Cl);
@@ -738,13 +772,18 @@ template <typename T> struct Net {
     lin_bwd_x(comp, dlq, dt2ln, nl);
     T* dt2l = alloc<T>(nl * dl);
     k_layernorm_bwd<T>(c, k.t2l_last, t2l.norm_enc, k.st_t2l, dt2ln, dt2l, t2l.g_norm_enc, nl, dl, nullptr);
-    T* denc_out = alloc<T>(nseq * d);
-    k_zero(c, denc_out, nseq * d * (int64_t)sizeof(T));
+    T* denc_out = alloc<T>(k.Bc * k.N * d);
+    k_zero(c, denc_out, k.Bc * k.N * d * (int64_t)sizeof(T));
     for (int i = (int)t2l.blocks.size() - 1; i >= 0; --i)
       block_bwd(t2l.blocks[i], k.t2l_st[i], dt2l, dt2l, k.Bc, L, nullptr, k.enc_out, k.N, denc_out);
     grad_segment_done(1);  // tracks_to_latents, compressor, decompressor, decompress_attn
     k_bcast_grad<T>(c, dt2l, (int64_t)L * dl, k.Bc, (int64_t)L * dl, g_lat0);
-    // ---- track encoder
+    return denc_out;
+  }
+  // track encoder (E7-E1) of the tracks of k (k.nseq sequences, stashed by encode_tracks(train = true)) against their rows denc_out [nseq, d]
+  void backward_tracks(Chunk& k, const T* denc_out) {
+    const int d = g.track_token_dim, T_ = k.T_;
+    const int64_t nseq = k.nseq;
     const int S = k.S;
     const int64_t erows = k.enc_rg.off ? (k.enc_rg.rows + 7) & ~int64_t(7) : nseq * S;
     T* dtok = alloc<T>(erows * d);
@@ -782,13 +821,94 @@ template <typename T> struct Net {
       if (k.depthf && !(sizeof(T) == 2 && depth.nseg == 1 && k_rank_bwd<T>(c, (const T*)k.depthf, dtok_dense, nseq * T_, depth.N, depth.K, d, T_, 1, depth.gw[0], depth.gb)))
         lin_bwd_w(depth, (const T*)k.depthf, dtok_dense, nseq * T_, 0, T_, 1);
     }
-    c->ar.release(mk0);
   }
 };
 
 // ---------------------------------------------------------------------------------------------
 // drivers
 // ---------------------------------------------------------------------------------------------
+// test mode "poison": everything allocated from arena offset `mark` on starts as NaN (0xFFFF / 0xFFFFFFFF) instead of what an earlier
+// chunk left there
+static void poison_from(spa3d_ctx* c, int64_t mark) {
+  if (!c->poison || c->dry) return;
+  const int64_t o = (mark + 255) & ~int64_t(255);
+  if (o < c->ar.cap) (void)hipMemsetAsync(c->ar.base + o, 0xFF, (size_t)(c->ar.cap - o), c->stream);
+}
+
+// outputs and loss sums of the queries [k.q_off, k.q_off + k.Qc) of samples [b0, b0 + k.Bc) from k.head
+template <typename T>
+static void emit_outputs(spa3d_ctx* c, const RunArgs& a, Net<T>& net, typename Net<T>::Chunk& k, int64_t b0, float* sums, unsigned* poison) {
+  const spa3d_batch* b = a.b; const int To = c->cfg.num_output_frames, NC = net.NC;
+  const bool train = a.mode == MODE_TRAIN;
+  const int64_t nq = k.Bc * k.Qc, qrow = b0 * b->Q + k.q_off;
+  float* tr = a.out && a.out->tracks ? a.out->tracks + qrow * To * NC : nullptr;
+  float* vl = a.out && a.out->visible_logits ? a.out->visible_logits + qrow * To : nullptr;
+  float* cl = a.out && a.out->certain_logits ? a.out->certain_logits + qrow * To : nullptr;
+  k_loss_fwd(c, k.head, nq, To, train ? b->query_tracks + qrow * To * NC : nullptr, train ? b->query_tracks_visible + qrow * To : nullptr,
+             tr, vl, cl, sums, poison, NC);
+}
+
+// One sample with intra-sample chunks (spa3d_set_option "track_chunk" / "query_chunk"; k.Bc == 1).
+//  track_chunk: pass A runs the track encoder over chunks of tracks without a stash (the no-stash ping-pong path) into one persistent
+//    [N, d] enc_out; tracks_to_latents sees all N keys as before.  Pass B, after the latent-side backward has produced d enc_out for all N
+//    tracks, re-runs each chunk's encoder forward WITH its stash and its backward against its rows (the reference's nn.remat idea, applied to
+//    the largest stash).  Parameter gradients accumulate as they do across sample chunks.
+//  query_chunk: readout rows depend on their query and the sample's latents only, and the loss denominator is batch-global and known up front,
+//    so each chunk of queries runs embed -> readout -> head -> loss -> readout backward and releases its arena; the latent-side gradient
+//    dlatd32 is written by the first chunk and accumulated (fp32, fixed order, no atomics) by the others.
+template <typename T>
+static void run_sample_intra(spa3d_ctx* c, const RunArgs& a, Net<T>& net, typename Net<T>::Chunk& k, int64_t b0, const float* noise, float* sums,
+                             unsigned* poison, const float* denom_dev) {
+  const spa3d_batch* b = a.b; const spa3d_config& g = c->cfg;
+  const int L = g.num_latent_tokens, Ld = g.latent_token_dim, Cl = g.decoder_num_channels - 128, d = g.track_token_dim;
+  const bool train = a.mode == MODE_TRAIN;
+  const int tc = c->track_chunk > 0 ? std::min(c->track_chunk, b->N) : b->N, qc = c->query_chunk > 0 ? std::min(c->query_chunk, b->Q) : b->Q;
+  auto track_slice = [&](int64_t n0) { k.n_off = n0; k.Nc = (int)std::min<int64_t>(tc, b->N - n0); k.nseq = k.Nc; };
+  if (a.mode != MODE_DECODE) {
+    if (c->track_chunk > 0) {  // pass A
+      T* enc_all = net.template alloc<T>((int64_t)b->N * d);
+      for (int64_t n0 = 0; n0 < b->N; n0 += tc) {
+        track_slice(n0);
+        const int64_t mk = c->ar.mark();
+        poison_from(c, mk);
+        net.encode_tracks(k, b, b0, false, enc_all + n0 * d);
+        c->ar.release(mk);
+      }
+      k.enc_out = enc_all; k.n_off = 0; k.Nc = b->N; k.nseq = b->N;
+    } else {
+      net.encode_tracks(k, b, b0, train);
+    }
+    net.encode_latents(k, train);
+    float* lo = a.latents_out ? a.latents_out : (a.out && a.out->latents ? a.out->latents : nullptr);
+    if (lo && !c->dry) (void)hipMemcpyAsync(lo + b0 * L * Ld, k.latents, (size_t)L * Ld * 4, hipMemcpyDeviceToDevice, c->stream);
+  }
+  if (a.mode == MODE_ENCODE) return;
+  net.decode_latents(k, b, a.mode == MODE_DECODE ? a.latents_in + b0 * L * Ld : k.latents, noise, b0, train);
+  float* dlatd32 = train ? net.template alloc<float>((int64_t)L * Cl) : nullptr;
+  for (int64_t q0 = 0; q0 < b->Q; q0 += qc) {
+    k.q_off = q0; k.Qc = (int)std::min<int64_t>(qc, b->Q - q0);
+    const int64_t mk = c->ar.mark();
+    poison_from(c, mk);
+    net.decode_queries(k, b, b0, train);
+    emit_outputs<T>(c, a, net, k, b0, sums, poison);
+    if (train) net.backward_queries(k, b, b0, denom_dev, dlatd32, q0 > 0);
+    c->ar.release(mk);
+  }
+  if (!train) return;
+  net.grad_segment_done(0);  // after the last query chunk (of the last sample chunk: grad_segment_done checks)
+  const T* denc_out = net.backward_latents(k, dlatd32);
+  if (c->track_chunk <= 0) { net.backward_tracks(k, denc_out); return; }
+  k.count_plan = false;  // pass B: recompute + backward per track chunk
+  for (int64_t n0 = 0; n0 < b->N; n0 += tc) {
+    track_slice(n0);
+    const int64_t mk = c->ar.mark();
+    poison_from(c, mk);
+    net.encode_tracks(k, b, b0, true);
+    net.backward_tracks(k, denc_out + n0 * d);
+    c->ar.release(mk);
+  }
+}
+
 template <typename T>
 void run_body(spa3d_ctx* c, const RunArgs& a, int Bc) {
   const spa3d_config& g = c->cfg; const spa3d_batch* b = a.b;
@@ -830,6 +950,7 @@ void run_body(spa3d_ctx* c, const RunArgs& a, int Bc) {
   // left its (now dead) shadow pointer behind must never be what the next handle's kernels see (found by tests/test_gpu_poison.py running behind tests/test_gpu_det.py)
   // -- and a call that set a live shadow clears it again at its end (below)
   if (train) det_upload_all(c, &c->det_host);
+  const bool intra = c->query_chunk > 0 || c->track_chunk > 0;  // run() has made Bc = 1
   // The ragged chunk (B % Bc samples) runs FIRST, so the last chunk -- the one under whose track-encoder backward the gradient segments are all-reduced -- is a
   // full one (B = 64, Bc = 9: 9 samples of encoder backward to hide behind instead of 1)
   for (int64_t b0 = 0, cur = 0; b0 < b->B; b0 += cur) {
@@ -837,11 +958,10 @@ void run_body(spa3d_ctx* c, const RunArgs& a, int Bc) {
     cur = (b0 == 0 && b->B % Bc) ? b->B % Bc : std::min<int64_t>(Bc, b->B - b0);
     c->last_chunk = b0 + cur >= b->B;
     k.Bc = cur; k.N = b->N; k.Q = b->Q; k.T_ = b->T; k.S = b->T + (g.model_kind == 1 ? 0 : 1); k.nseq = k.Bc * b->N;
+    k.Nc = b->N; k.Qc = b->Q;
     const int64_t mk = c->ar.mark();
-    if (c->poison && !c->dry) {  // test mode: everything this chunk may allocate starts as NaN (0xFFFF / 0xFFFFFFFF) instead of the previous chunk's values
-      const int64_t o = (mk + 255) & ~int64_t(255);
-      if (o < c->ar.cap) (void)hipMemsetAsync(c->ar.base + o, 0xFF, (size_t)(c->ar.cap - o), c->stream);
-    }
+    poison_from(c, mk);
+    if (intra) { run_sample_intra<T>(c, a, net, k, b0, noise, sums, poison, denom_dev); c->ar.release(mk); continue; }
     const float* lat = nullptr;
     if (a.mode != MODE_DECODE) {
       net.encode_chunk(k, b, b0, train);
@@ -853,13 +973,7 @@ void run_body(spa3d_ctx* c, const RunArgs& a, int Bc) {
     }
     if (a.mode != MODE_ENCODE) {
       net.decode_chunk(k, b, b0, lat, noise, train);
-      const int64_t nq = k.Bc * k.Q;
-      const int NC = net.NC;
-      float* tr = a.out && a.out->tracks ? a.out->tracks + b0 * b->Q * To * NC : nullptr;
-      float* vl = a.out && a.out->visible_logits ? a.out->visible_logits + b0 * b->Q * To : nullptr;
-      float* cl = a.out && a.out->certain_logits ? a.out->certain_logits + b0 * b->Q * To : nullptr;
-      k_loss_fwd(c, k.head, nq, To, train ? b->query_tracks + b0 * b->Q * To * NC : nullptr,
-                 train ? b->query_tracks_visible + b0 * b->Q * To : nullptr, tr, vl, cl, sums, poison, NC);
+      emit_outputs<T>(c, a, net, k, b0, sums, poison);
       if (train) net.backward_chunk(k, b, b0, denom_dev);
     }
     c->ar.release(mk);
@@ -992,6 +1106,10 @@ static int run(spa3d_ctx* c, RunArgs a, void* ws, int64_t ws_bytes, void* stream
   c->stream = (hipStream_t)stream;
   int lo = 1, hi = a.b->B;
   if (a.chunk <= 0) a.chunk = c->chunk;  // spa3d_set_option "chunk" / SPA3D_CHUNK: fixed samples per chunk (tests: chunk-to-chunk reuse of the arena)
+  if (c->query_chunk > 0 || c->track_chunk > 0) {  // intra-sample chunks: one sample per sample chunk
+    if (a.chunk > 1) { c->err = "\"chunk\" > 1 cannot be combined with \"query_chunk\" / \"track_chunk\" (they imply one sample per chunk)"; return SPA3D_ERR_ARG; }
+    a.chunk = 1;
+  }
   if (a.chunk > 0) { lo = hi = std::min(a.chunk, a.b->B); }
   if (dry_need(c, a, lo) > ws_bytes) {
     c->err = "workspace too small: need " + std::to_string(dry_need(c, a, lo)) + " bytes for chunk " + std::to_string(lo);
@@ -1032,7 +1150,7 @@ int spa3d_create(const spa3d_config* cfg, spa3d_handle* out) {
   // at loss x 2^k (k chosen per call from the loss denominator, k_set_loss_scale) and the fp32 parameter gradients are scaled back once
   // at the end (exact for powers of two)
   if (cfg->precision == SPA3D_F16) c->loss_scale = -16.f;
-  // the six switches (include/spa3d.h, spa3d_set_option) may be preset from the environment; nothing else is read from it
+  // the nine switches (include/spa3d.h, spa3d_set_option) may be preset from the environment; nothing else is read from it
   const char* e = getenv("SPA3D_GEMM_IMPL"); if (e) apply_gemm_impl(c, atoi(e));
   e = getenv("SPA3D_ATTN_IMPL"); if (e) apply_attn_impl(c, atoi(e));
   e = getenv("SPA3D_LOSS_SCALE"); if (e && cfg->precision == SPA3D_F16) c->loss_scale = (float)atof(e);
@@ -1040,6 +1158,8 @@ int spa3d_create(const spa3d_config* cfg, spa3d_handle* out) {
   e = getenv("SPA3D_RO_SHARE"); if (e) c->ro_share = atoi(e);
   e = getenv("SPA3D_CHUNK"); if (e) c->chunk = atoi(e);
   e = getenv("SPA3D_DET_GRADS"); if (e) c->det_grads = atoi(e) != 0;
+  e = getenv("SPA3D_QUERY_CHUNK"); if (e) c->query_chunk = std::max(0, atoi(e));
+  e = getenv("SPA3D_TRACK_CHUNK"); if (e) c->track_chunk = std::max(0, atoi(e));
   *out = c;
   return SPA3D_OK;
 }
@@ -1068,6 +1188,7 @@ int64_t spa3d_workspace_bytes(spa3d_handle h, int32_t B, int32_t N, int32_t Q, i
   b.dino_features = h->cfg.dino_feature_dim > 0 ? (const void*)fake : nullptr;
   b.depth_features = h->cfg.depth_feature_dim > 0 ? (const void*)fake : nullptr;
   RunArgs a{}; a.mode = train ? MODE_TRAIN : MODE_FORWARD; a.b = &b; a.G = train ? (float*)0x100000 : nullptr;
+  if (h->query_chunk > 0 || h->track_chunk > 0) chunk = 1;  // intra-sample chunks process one sample at a time
   return dry_need(h, a, std::max(1, std::min(chunk, B)));
 }
 
@@ -1119,7 +1240,15 @@ int spa3d_set_option(spa3d_handle h, const char* name, double value) {
   else if (n == "loss_scale") { if (h->cfg.precision != SPA3D_F16) { h->err = "loss_scale applies to SPA3D_F16 handles only"; return SPA3D_ERR_ARG; } h->loss_scale = (float)value; }
   else if (n == "attn_impl") apply_attn_impl(h, (int)value);
   else if (n == "gemm_impl") apply_gemm_impl(h, (int)value);
-  else if (n == "chunk") h->chunk = value > 0 ? (int)value : 0;
+  else if (n == "chunk") {
+    if (value > 1 && (h->query_chunk > 0 || h->track_chunk > 0)) { h->err = "\"chunk\" > 1 cannot be combined with \"query_chunk\" / \"track_chunk\""; return SPA3D_ERR_ARG; }
+    h->chunk = value > 0 ? (int)value : 0;
+  }
+  else if (n == "query_chunk" || n == "track_chunk") {
+    if (!(value >= 0 && value <= 2147483647.0)) { h->err = n + " must be >= 0"; return SPA3D_ERR_ARG; }
+    if (value >= 1 && h->chunk > 1) { h->err = "\"" + n + "\" cannot be combined with \"chunk\" > 1 (it implies one sample per chunk)"; return SPA3D_ERR_ARG; }
+    (n == "query_chunk" ? h->query_chunk : h->track_chunk) = (int)value;
+  }
   else if (n == "poison") h->poison = value != 0;
   else if (n == "det_grads") h->det_grads = value != 0;
   else { h->err = "unknown option: " + n; return SPA3D_ERR_ARG; }

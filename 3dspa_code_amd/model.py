@@ -99,7 +99,9 @@ class TrackAutoEncoder3D:
                track_token_dim: int = 384, encoder_latent_dim: int = 512, decoder_num_channels: int = 1280,
                dino_feature_dim: int = 768, depth_feature_dim: int = 256, use_dino: bool = True, use_depth: bool = True,
                decoder_scan_chunk_size: Optional[int] = None, precision: str = 'bf16',
-               workspace_fraction: float = 0.80):
+               workspace_fraction: float = 0.80, track_chunk_size: Optional[int] = None):
+    # track_chunk_size is NOT part of the reference's signature (product-only): the track encoder runs over chunks of that many tracks and is
+    # recomputed chunk by chunk in the backward (spa3d_set_option "track_chunk"; one extra encoder forward per training step)
     if precision not in _PRECISIONS:
       raise ValueError(f"precision must be one of {sorted(_PRECISIONS)}, got {precision!r}")
     self.num_output_frames = num_output_frames
@@ -115,7 +117,9 @@ class TrackAutoEncoder3D:
     self.depth_feature_dim = depth_feature_dim
     self.use_dino = use_dino
     self.use_depth = use_depth
-    self.decoder_scan_chunk_size = decoder_scan_chunk_size  # numerically a no-op (3d:312-349); chunking is internal
+    # 3d:312-349: the readout runs over chunks of this many queries (spa3d_set_option "query_chunk"); Q must be a multiple of it
+    self.decoder_scan_chunk_size = decoder_scan_chunk_size
+    self.track_chunk_size = track_chunk_size
     self.precision = precision
     self.workspace_fraction = workspace_fraction
     # transformer sizes of setup() (3d:89-112)
@@ -129,6 +133,7 @@ class TrackAutoEncoder3D:
     self._handles: Dict[Any, Any] = {}
     self._ws: Optional[torch.Tensor] = None
     self._kind, self._nc = 0, 3  # 0: 3DSPA (x,y,z); the 2-D TRAJAN subclass sets (1, 2)
+    self._chunk_set: Dict[Any, Any] = {}  # handle -> (query_chunk, track_chunk) last stated by _chunk_options
     self._ws_cap = 0  # size of a budget-limited workspace (0: none / large enough for every request so far)
 
   # -------------------------------------------------------------------------------- handles / layout
@@ -310,6 +315,22 @@ class TrackAutoEncoder3D:
     q = torch.stack(cols, dim=-1).reshape(-1, self._nc + 1)
     return q[None].expand(support_tracks.shape[0], -1, -1).contiguous()
 
+  def _chunk_options(self, h, Q: Optional[int]):
+    """States the intra-sample chunk sizes on the handle before a call.  Q: the call's query count (None: no readout)."""
+    qc, tc = self.decoder_scan_chunk_size, self.track_chunk_size
+    for name, v in (('decoder_scan_chunk_size', qc), ('track_chunk_size', tc)):
+      if v is not None and (not isinstance(v, int) or isinstance(v, bool) or v <= 0):
+        raise ValueError(f'{name} must be a positive int or None, got {v!r}')
+    if qc is not None and Q is not None and Q % qc:  # as the reference's rearrange('(Q H) ...') over the scan (3d:312-349)
+      raise ValueError(f'decoder_scan_chunk_size={qc} must divide the number of queries Q={Q}')
+    # a size left at None leaves the handle's option alone (an SPA3D_QUERY_CHUNK / SPA3D_TRACK_CHUNK preset stays in force) unless this model set it before
+    lib = _lib.load()
+    prev = self._chunk_set.get(h.value, (None, None))
+    for name, v, p in ((b'query_chunk', qc, prev[0]), (b'track_chunk', tc, prev[1])):
+      if v is not None or p is not None:
+        _lib.check(lib.spa3d_set_option(h, name, float(v or 0)), h, 'spa3d_set_option')
+    self._chunk_set[h.value] = (qc, tc)
+
   # -------------------------------------------------------------------------------- workspace
   def _workspace(self, h, B, N, Q, T, train, device):
     lib = _lib.load()
@@ -338,6 +359,7 @@ class TrackAutoEncoder3D:
     flat = self.flat_from_tree(params)
     dev = flat.device
     lat = torch.empty(b.B, self.num_latent_tokens, self.latent_token_dim, dtype=torch.float32, device=dev)
+    self._chunk_options(h, None)
     ws = self._workspace(h, b.B, b.N, 1, b.T, False, dev)
     _lib.check(_lib.load().spa3d_encode(h, flat.data_ptr(), C.byref(b), lat.data_ptr(), ws.data_ptr(), ws.numel(), _stream(flat)),
                h, 'spa3d_encode')
@@ -363,6 +385,7 @@ class TrackAutoEncoder3D:
     lat = self._f32(latents, 'latents')
     if tuple(lat.shape) != (b.B, self.num_latent_tokens, self.latent_token_dim):
       raise ValueError('latents must be [B, num_latent_tokens, latent_token_dim]')
+    self._chunk_options(h, b.Q)
     res, out = self._alloc_outputs(b.B, b.Q, dev)
     ws = self._workspace(h, b.B, 1, b.Q, 1, False, dev)
     _lib.check(_lib.load().spa3d_decode(h, flat.data_ptr(), C.byref(b), lat.data_ptr(), C.byref(out), ws.data_ptr(), ws.numel(),
@@ -384,6 +407,7 @@ class TrackAutoEncoder3D:
     flat = self.flat_from_tree(params)
     dev = flat.device
     b, keep = self._marshal(inputs, dino, depth, discretize=discretize, noise=noise)
+    self._chunk_options(h, b.Q)
     res, out = self._alloc_outputs(b.B, b.Q, dev)
     ws = self._workspace(h, b.B, b.N, b.Q, b.T, False, dev)
     _lib.check(_lib.load().spa3d_forward(h, flat.data_ptr(), C.byref(b), C.byref(out), ws.data_ptr(), ws.numel(), _stream(flat)),
@@ -411,6 +435,7 @@ class TrackAutoEncoder3D:
     flat = self.flat_from_tree(params)
     dev = flat.device
     b, keep = self._marshal(batch, dino, depth, targets=True, discretize=discretize, noise=noise)
+    self._chunk_options(h, b.Q)
     if grads_flat is None:
       grads_flat = torch.empty(n, dtype=torch.float32, device=dev)
       accumulate = False
@@ -476,12 +501,14 @@ class TrackAutoEncoder(TrackAutoEncoder3D):
   def __init__(self, num_output_frames: int = 150, num_latent_tokens: int = 128, latent_token_dim: int = 64, num_frequencies: int = 32,
                track_scale_factor: float = 1.0, time_scale_factor: float = 150.0, track_token_dim: int = 256,
                encoder_latent_dim: int = 512, decoder_num_channels: int = 1024, decoder_scan_chunk_size: Optional[int] = None,
-               precision: str = 'bf16', workspace_fraction: float = 0.80):
+               precision: str = 'bf16', workspace_fraction: float = 0.80, track_chunk_size: Optional[int] = None):
+    # track_chunk_size: product-only, not part of the reference's signature (see TrackAutoEncoder3D)
     super().__init__(num_output_frames=num_output_frames, num_latent_tokens=num_latent_tokens, latent_token_dim=latent_token_dim,
                      num_frequencies=num_frequencies, track_scale_factor=track_scale_factor, time_scale_factor=time_scale_factor,
                      track_token_dim=track_token_dim, encoder_latent_dim=encoder_latent_dim, decoder_num_channels=decoder_num_channels,
                      dino_feature_dim=0, depth_feature_dim=0, use_dino=False, use_depth=False,
-                     decoder_scan_chunk_size=decoder_scan_chunk_size, precision=precision, workspace_fraction=workspace_fraction)
+                     decoder_scan_chunk_size=decoder_scan_chunk_size, precision=precision, workspace_fraction=workspace_fraction,
+                     track_chunk_size=track_chunk_size)
     self._kind, self._nc = 1, 2
     # transformer sizes of setup() (track_autoencoder.py:149-172)
     self.num_heads, self.qkv_size = 8, 64 * 8

@@ -23,7 +23,7 @@
  * modes, two 4-byte plan counts per sample chunk (kept frame tokens; distinct query frames) are
  * read back to the host, which synchronises the stream at those points (spa3d_set_option(h, "prune", 0) and
  * spa3d_set_option(h, "ro_share", 0) remove the reads together with the savings they size; no compute path reads the environment --
- * the six options may only be PRESET from it when spa3d_create runs);
+ * the nine options may only be PRESET from it when spa3d_create runs);
  * one handle per stream (thread-compatible, not thread-safe).  All tensors are row-major contiguous in the
  * reference's layouts.  Parameters and gradients are ONE flat float32 buffer each whose
  * leaf order / offsets the library defines (spa3d_leaf_*); names are the Flax paths of
@@ -151,12 +151,21 @@ int spa3d_adamw_step(float* params, const float* grads, float* m, float* v, int6
                      int64_t step, float clip, float b1, float b2, float eps, float wd,
                      float* scratch, void* stream);
 
-/* Per-handle switches -- the only ones the library has (seven + one test mode); each may be preset at spa3d_create from the environment variable of the same name in
- * capitals with an SPA3D_ prefix (SPA3D_PRUNE ...).  Unknown names return SPA3D_ERR_ARG.
+/* Per-handle switches -- the only ones the library has (nine + one test mode); each may be preset at spa3d_create from the environment variable of the same name in
+ * capitals with an SPA3D_ prefix (SPA3D_PRUNE, SPA3D_QUERY_CHUNK, SPA3D_TRACK_CHUNK ...).  Unknown names return SPA3D_ERR_ARG.
  *   "prune"      0/1  token pruning of the track encoder (16-bit modes)            } with both 0 every entry point is fully asynchronous
  *   "ro_share"   0/1  shared latent rows of the first readout block (16-bit modes) } (no plan count is read back)
  *   "loss_scale"      SPA3D_F16 handles: > 0 fixed, < 0 automatic with that head-gradient target
  *   "chunk"           samples processed at a time; 0 = as many as fit the workspace
+ *   "query_chunk"  q  readout over chunks of q queries (0 = off, the default): per chunk the query embedding, readout stack, head, loss and (training)
+ *                     the readout backward run and release their workspace; the latent stacks run once per sample and their gradient accumulates
+ *                     over the chunks in fp32 in a fixed order.  The reference's decoder_scan_chunk_size (track_autoencoder_3d.py:312-349).  No recompute.
+ *   "track_chunk"  n  track encoder over chunks of n tracks (0 = off, the default): the forward keeps only the [N, 384] encoder output, and the
+ *                     backward re-runs each chunk's encoder forward with its stash before that chunk's backward -- one extra track-encoder forward
+ *                     per training step, for a stash of n instead of N tracks (the reference's nn.remat, applied to the largest stash).
+ *                     Either of the two > 0 processes ONE sample per sample chunk: "chunk" > 1 together with either is refused (SPA3D_ERR_ARG), and
+ *                     spa3d_workspace_bytes then sizes one sample whatever its `chunk` argument.  A ragged last chunk is allowed.  Same values as
+ *                     unchunked up to summation order; spa3d_plan_stats counts the forward pass only.
  *   "gemm_impl"       0 product dispatch | 1 generic strided MFMA kernel only | 2 tiled kernels | diagnostics that put small problems on the big
  *                     kernels: 3 every eligible GEMM on the 8-phase kernels, 4 the same with the non-persistent 128x384 kernel, 5 without the
  *                     single-buffer short-K kernel, 6 tiled GEMMs without the round-4 / round-5 kernels (MLP forward as two GEMMs, multi-pass input embedding, no row-stationary K = 384 kernel,
@@ -175,7 +184,7 @@ int spa3d_adamw_step(float* params, const float* grads, float* m, float* v, int6
  *                     train call that set it: it is cleared on the call's stream at its end, and the spa3d_op_*_bwd entry points always use float atomics.
  *                     Costs 8 bytes of workspace per parameter and ~3.6 % of the step at BASELINE configs[2]
  *                     (1.82 -> 1.88 s: 64-bit atomics in the dW epilogues, the 1-channel depth gradient on the GEMM path); off by default.
- * and one test mode: "poison" 0/1 -- the workspace is filled with 16-bit NaN patterns before every sample chunk, so a read of a row that this
+ * and one test mode: "poison" 0/1 -- the workspace is filled with 16-bit NaN patterns before every sample chunk (and every track / query chunk), so a read of a row that this
  * call has not written (the rounded-up tails of pruned GEMMs, chunk-to-chunk reuse of the bump allocator) shows up as NaN instead of as a
  * plausible stale value (tests/test_gpu_poison.py). */
 int spa3d_set_option(spa3d_handle h, const char* name, double value);
