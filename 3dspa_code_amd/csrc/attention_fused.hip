@@ -387,7 +387,7 @@ __global__ __launch_bounds__(256) void xattn_combine_kernel(const float* __restr
 // and the q-scale gradient.  Grid-stride over rows so that the scale gradient costs 96 atomics per workgroup, not per row.
 __global__ __launch_bounds__(256) void xattn_dq_finish_kernel(const float* __restrict__ dqpart, int nsplit, int Sq, int H, int64_t nrows,
                                                               const bf16_t* __restrict__ q, int64_t ldq, const float* __restrict__ sq,
-                                                              bf16_t* __restrict__ dq, float* __restrict__ dsq) {
+                                                              bf16_t* __restrict__ dq, float* __restrict__ dsq, const DetCfg* det) {
   __shared__ float red[4][DH];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const bool hi = lane < DH - 64;
@@ -411,7 +411,7 @@ __global__ __launch_bounds__(256) void xattn_dq_finish_kernel(const float* __res
   }
   red[w][lane] = a0; if (hi) red[w][64 + lane] = a1;
   __syncthreads();
-  if (tid < DH) grad_add(dsq + tid, red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid]);
+  if (tid < DH) grad_add(det_read(det), dsq + tid, red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid]);
 }
 
 static bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
@@ -506,6 +506,7 @@ struct AttnBwdArgs {
   // cross attention (attn_bwd8_kernel<8, true>): S = query rows per sequence (<= 128); the Sk keys of a sequence are cut into nsplit chunks
   // of 128, one workgroup pass per (sequence, head, chunk); dq^ (before the RMSNorm backward) leaves as fp32 partials per chunk
   int Sk, nsplit; float* dqpart;  // [nprob][nsplit][S][96]
+  const DetCfg* det;  // the call's deterministic-gradient mode (common.hpp): the scale gradients
 #if SPA3D_ABL_ATTN  // tools/ablate_attn.py builds a separate diagnostic library with this; never defined for libspa3d_hip.so
   int ablate;          // 1: no tile work, 2: no staging (garbage operands), 4: no dq/dk/dv stores
 #endif
@@ -780,6 +781,7 @@ __device__ __forceinline__ void flush_scale_grads(const AttnBwdArgs& g, float* s
   __syncthreads();
   for (int t = tid; t < 2 * DH; t += NTHREADS) sred[t] = 0.f;
   __syncthreads();
+  const DetCfg dc = det_read(g.det);
 #pragma unroll
   for (int dt = 0; dt < 6; ++dt)
 #pragma unroll
@@ -788,9 +790,9 @@ __device__ __forceinline__ void flush_scale_grads(const AttnBwdArgs& g, float* s
 #pragma unroll
       for (int o = 1; o < 16; o <<= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
       if (fr == 0) {
-        if (det_on()) {  // deterministic mode: LDS float atomics depend on arrival order too -- every wave adds straight into the fixed-point shadow
-          if (has_q) grad_add(g.dsq + dt * 16 + fq * 4 + r, a);
-          if (has_k) grad_add(g.dsk + dt * 16 + fq * 4 + r, b);
+        if (dc.shadow) {  // deterministic mode: LDS float atomics depend on arrival order too -- every wave adds straight into the fixed-point shadow
+          if (has_q) grad_add(dc, g.dsq + dt * 16 + fq * 4 + r, a);
+          if (has_k) grad_add(dc, g.dsk + dt * 16 + fq * 4 + r, b);
         } else {
           if (has_q) atomicAdd(sred + dt * 16 + fq * 4 + r, a);
           if (has_k) atomicAdd(sred + DH + dt * 16 + fq * 4 + r, b);
@@ -798,7 +800,7 @@ __device__ __forceinline__ void flush_scale_grads(const AttnBwdArgs& g, float* s
       }
     }
   __syncthreads();
-  if (det_on()) return;
+  if (dc.shadow) return;
   if (tid < DH) atomicAdd(g.dsq + tid, sred[tid]);
   else if (tid < 2 * DH) atomicAdd(g.dsk + tid - DH, sred[tid]);
 }
@@ -1120,7 +1122,7 @@ bool attn_fused_bwd_bf16(spa3d_ctx* c, const bf16_t* q, const bf16_t* k, const b
     if (!c->dry) {
       AttnBwdArgs a; a.q = q; a.k = k; a.v = v; a.o = o; a.d_o = d_o; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.sq = sq; a.sk = sk; a.km = km;
       a.lse = lse; a.S = Sq; a.H = H; a.nprob = nprob; a.dq = dq; a.dk = dk; a.dv = dv; a.dsq = dsq; a.dsk = dsk; a.seq_off = nullptr;
-      a.Sk = Sk; a.nsplit = nsplit; a.dqpart = dqpart;
+      a.Sk = Sk; a.nsplit = nsplit; a.dqpart = dqpart; a.det = c->det;
 #if SPA3D_ABL_ATTN
       a.ablate = 0;
 #endif
@@ -1132,7 +1134,7 @@ bool attn_fused_bwd_bf16(spa3d_ctx* c, const bf16_t* q, const bf16_t* k, const b
       if (!attr_set) { (void)hipFuncSetAttribute((const void*)attn_bwd8_kernel<KT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds4); attr_set = true; }
       attn_bwd8_kernel<KT, true><<<(unsigned)std::min<int64_t>(nprob * nsplit, 1024), 512, lds4, c->stream>>>(a);
       const int64_t nrows = nprob * Sq;
-      xattn_dq_finish_kernel<<<(unsigned)std::min<int64_t>((nrows + 3) / 4, 512), 256, 0, c->stream>>>(dqpart, nsplit, Sq, H, nrows, q, ldq, sq, dq, dsq);
+      xattn_dq_finish_kernel<<<(unsigned)std::min<int64_t>((nrows + 3) / 4, 512), 256, 0, c->stream>>>(dqpart, nsplit, Sq, H, nrows, q, ldq, sq, dq, dsq, c->det);
       SPA_LAUNCH_CHECK(c);
     }
     c->ar.release(mk);
@@ -1146,7 +1148,7 @@ bool attn_fused_bwd_bf16(spa3d_ctx* c, const bf16_t* q, const bf16_t* k, const b
   if (c->dry) return true;
   AttnBwdArgs a; a.q = q; a.k = k; a.v = v; a.o = o; a.d_o = d_o; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.sq = sq; a.sk = sk; a.km = km;
   a.lse = lse; a.S = Sk; a.H = H; a.nprob = nseq * H; a.dq = dq; a.dk = dk; a.dv = dv; a.dsq = dsq; a.dsk = dsk; a.seq_off = seq_off;
-  a.Sk = Sk; a.nsplit = 1; a.dqpart = nullptr;
+  a.Sk = Sk; a.nsplit = 1; a.dqpart = nullptr; a.det = c->det;
   const double rows = total_rows > 0 ? (double)total_rows : (double)nseq * Sk;
 #if SPA3D_ABL_ATTN
   { const char* e = getenv("SPA3D_ABLATE"); a.ablate = e ? atoi(e) : 0; }
@@ -1172,5 +1174,4 @@ bool attn_fused_bwd_bf16(spa3d_ctx* c, const bf16_t* q, const bf16_t* k, const b
   SPA_LAUNCH_CHECK(c);
   return true;
 }
-SPA_DET_UPLOAD_DEF(det_upload_attn)
 }  // namespace SPA_NS

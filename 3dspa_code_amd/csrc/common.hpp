@@ -22,6 +22,23 @@
 #endif
 typedef unsigned short bf16_t;  // raw 16-bit pattern (bf16, or fp16 in the SPA_F16 build); arithmetic is always done in f32
 
+// ---- deterministic parameter gradients (spa3d_set_option "det_grads").  Every reduction INTO the flat gradient buffer (split-M dW tiles, bias / scale column sums,
+// broadcast gradients) is a float atomic by default: fast, and its result depends on arrival order in the last bits.  In this mode the same call sites add 64-bit FIXED-POINT
+// integers (exact, order-independent) into a shadow of the gradient buffer, which det_flush adds to the float buffer once a range is final.  The mode is per call: a
+// det_grads train call writes its DetCfg into its own workspace (k_det_unit) and passes a pointer to it (spa3d_ctx::det) to every kernel that adds into the gradient
+// buffer; nullptr = float atomics.  (A pointer, not the struct by value: kernel arguments are loaded at kernel entry, so the fields would stay live in SGPRs
+// through the main loops -- SGPR spills in the LayerNorm backward, more VGPRs in the single-query attention backward; the struct is read where it is used.)
+// Unit: one integer step is 1 / scale of the buffer's value, scale = 2^(32 + e) with e = floor(log2(denom / (n_vis * loss scale))) clamped to [DET_E_MIN, DET_E_MAX]
+// (k_det_unit: a power of two, so the flush is exact; a gradient of this call scales as n_vis * loss scale / denom).  At a real batch n_vis ~ denom, so the unit is
+// 2^-32 as it always was (2^-(32 + log2 ranks) data-parallel); it only gets finer when the denominator exceeds the call's own visible count.  Range: an addend of
+// 2^55 units or more (or a NaN) sets the sticky flag instead of being added; a shadow sum of 2^62 units or more is taken as overflow by det_flush -- both flush NaN,
+// never a wrapped finite value.  2^62 / 2^55 = 128 addends at the bound fit; a sum can only wrap past the flush check with 384 or more addends all near the bound.
+// The single-query attention backward pre-sums in LDS and bounds its addends by 2^62 / (its problem count), so that sum cannot wrap either.
+struct DetCfg { float* gbase; long long* shadow; long long n; unsigned* flag; float scale; };   // scale: the unit (k_det_unit)
+constexpr float DET_ADDEND_MAX = 36028797018963968.f;   // 2^55 units
+constexpr long long DET_SUM_MAX = 1ll << 62;
+constexpr int DET_E_MIN = -24, DET_E_MAX = 40;   // the unit's exponent range (k_det_unit)
+
 namespace SPA_NS {
 #if SPA_F16
 __device__ __forceinline__ float bf2f(bf16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
@@ -102,27 +119,8 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
-// ---- deterministic parameter gradients (spa3d_set_option "det_grads").  Every reduction INTO the flat gradient buffer (split-M dW tiles, bias / scale column sums,
-// broadcast gradients) is a float atomic by default: fast, and its result depends on arrival order in the last bits.  In this mode the same call sites add 64-bit FIXED-POINT
-// integers (exact, order-independent) into a shadow of the gradient buffer, which det_flush adds to the float buffer once a range is final.  The switch is a
-// per-translation-unit device variable (no relocatable device code here), uploaded by det_upload_* on the call's stream at the start of a train call and cleared (all
-// null) at its end, and stated null by every op-level backward (ops.hip); nullptr = float atomics.
-// Unit: one integer step is 1 / *unit of the buffer's value, *unit = 2^(32 + e) with e = floor(log2(denom / (n_vis * loss scale))) clamped to [DET_E_MIN, DET_E_MAX]
-// (k_det_unit: a power of two, so the flush is exact; a gradient of this call scales as n_vis * loss scale / denom).  At a real batch n_vis ~ denom, so the unit is
-// 2^-32 as it always was (2^-(32 + log2 ranks) data-parallel); it only gets finer when the denominator exceeds the call's own visible count.  Range: an addend of
-// 2^55 units or more (or a NaN) sets the sticky flag instead of being added; a shadow sum of 2^62 units or more is taken as overflow by det_flush -- both flush NaN,
-// never a wrapped finite value.  2^62 / 2^55 = 128 addends at the bound fit; a sum can only wrap past the flush check with 384 or more addends all near the bound.
-// The single-query attention backward pre-sums in LDS and bounds its addends by 2^62 / (its problem count), so that sum cannot wrap either.
-struct DetCfg { float* gbase; long long* shadow; long long n; unsigned* flag; const float* unit; float scale; };   // scale: *unit, filled in by det_load
-static __device__ DetCfg det_cfg_dev;
-constexpr float DET_ADDEND_MAX = 36028797018963968.f;   // 2^55 units
-constexpr long long DET_SUM_MAX = 1ll << 62;
-constexpr int DET_E_MIN = -24, DET_E_MAX = 40;   // the unit's exponent range (k_det_unit)
-// A kernel with many additions loads the switch ONCE (det_load: scalar loads into SGPRs, plus the unit when the mode is on) and passes it along; re-reading the device
-// variable at every addition cost the large-tile dW kernel's 384-atomic epilogue and the single-query attention backward's inner loop 60 ms/step with the mode OFF
-// (round 5, first version).
-__device__ __forceinline__ DetCfg det_load() { DetCfg d = det_cfg_dev; d.scale = d.shadow ? *d.unit : 4294967296.f; return d; }
-__device__ __forceinline__ bool det_on() { return det_cfg_dev.shadow != nullptr; }
+// A kernel with many additions reads the mode ONCE and passes it along; the cold sites (one addition per thread at a workgroup's end) read it at the addition.
+__device__ __forceinline__ DetCfg det_read(const DetCfg* d) { return d ? *d : DetCfg{nullptr, nullptr, 0, nullptr, 4294967296.f}; }
 __device__ __forceinline__ void grad_add(const DetCfg& dc, float* p, float v) {
   if (dc.shadow) {
     const long long i = p - dc.gbase;
@@ -135,7 +133,6 @@ __device__ __forceinline__ void grad_add(const DetCfg& dc, float* p, float v) {
   }
   atomicAdd(p, v);
 }
-__device__ __forceinline__ void grad_add(float* p, float v) { grad_add(det_load(), p, v); }   // cold sites: one addition per thread at a workgroup's end
 // an addend already in fixed point (a workgroup's exact integer sum): straight into the shadow, no second rounding; |q| >= 2^62 is overflow
 __device__ __forceinline__ void grad_add_q(const DetCfg& dc, float* p, long long q) {
   if (dc.shadow) {
@@ -148,16 +145,6 @@ __device__ __forceinline__ void grad_add_q(const DetCfg& dc, float* p, long long
   }
   atomicAdd(p, (float)((double)q / (double)dc.scale));
 }
-// (a one-thread kernel, not hipMemcpyToSymbolAsync: a copy from pageable host memory may block the host until the stream has drained)
-#define SPA_DET_UPLOAD_DEF(fn)                                                         \
-  __global__ void fn##_kernel(DetCfg d) { det_cfg_dev = d; }                           \
-  void fn(hipStream_t st_, const DetCfg* d) { fn##_kernel<<<1, 1, 0, st_>>>(*d); }
-void det_upload_kernels(hipStream_t, const DetCfg*);
-void det_upload_gemm_fast(hipStream_t, const DetCfg*);
-void det_upload_gemm_tnb(hipStream_t, const DetCfg*);
-void det_upload_gemm_generic(hipStream_t, const DetCfg*);
-void det_upload_attn(hipStream_t, const DetCfg*);
-
 }  // namespace SPA_NS
 
 // ------------------------------------------------------------------------------------------
@@ -239,7 +226,7 @@ struct spa3d_ctx {
   int qkv_attn = 0;       // track-encoder QKV projection + attention forward as ONE kernel (qkv_attn.hip): built and measured in round 5, 1.47x SLOWER than the
                           // projection GEMM + attention kernel pair (profiles/r05_qkv_attn_fused.log), so opt-in only: attn_impl 6
   int det_grads = 0;      // spa3d_set_option "det_grads": order-independent parameter gradients (fixed-point shadow accumulation, DetCfg above); costs a few %
-  SPA_NS::DetCfg det_host = {nullptr, nullptr, 0, nullptr, nullptr, 0.f};  // what was uploaded last (kept alive for the asynchronous copy)
+  const DetCfg* det = nullptr;  // the running det_grads train call's mode, in its workspace, passed to every kernel that adds into G; nullptr = float atomics
   int poison = 0;         // spa3d_set_option "poison": NaN-fill the workspace before every chunk and every op output before its launch (tests)
   bool tn_colsum_fused = false;  // set by gemm_tn_bf16: the last call also produced GemmDesc::colsum_out
   Prof prof;
@@ -425,9 +412,10 @@ void k_loss_finalize(spa3d_ctx*, const float* sums, const unsigned* poison, cons
 void k_adamw(spa3d_ctx*, float* p, const float* g, float* m, float* v, int64_t n, float lr, int64_t step, float clip, float b1, float b2,
              float eps, float wd, float* scratch);
 void k_uniform_noise(spa3d_ctx*, float* out, int64_t n, uint32_t k0, uint32_t k1);
-void k_det_flush(spa3d_ctx*, float* g, long long* shadow, const unsigned* flag, const float* unit, int64_t n);  // g[i] += shadow[i] / *unit; shadow[i] = 0; NaN when *flag or |shadow[i]| >= 2^62
-void k_det_unit(spa3d_ctx*, const float* sums, const unsigned* poison, const float* denom_dev, const float* scale_dev, float* unit);  // DetCfg unit rule
-void det_upload_all(spa3d_ctx*, const SPA_NS::DetCfg*);  // every translation unit's switch, on the context's stream
+// over [lo, lo + n) of c->det: g[i] += shadow[i] / scale; shadow[i] = 0; NaN when *flag or |shadow[i]| >= 2^62
+void k_det_flush(spa3d_ctx* c, int64_t lo, int64_t n);
+// *out = d with the call's unit as its scale (DetCfg unit rule)
+void k_det_unit(spa3d_ctx*, const float* sums, const unsigned* poison, const float* denom_dev, const float* scale_dev, const DetCfg& d, DetCfg* out);
 // single-query attention of the pruned last block (kernels.hip)
 template <typename T> void k_attn_q1_fwd(spa3d_ctx*, const T* q0, int64_t ldq0, const T* k, const T* v, int64_t ldk, int64_t ldv,
                                          const float* sq, const float* sk, const float* km, int64_t nseq, int S, int H, int Dh, T* o0,

@@ -1178,7 +1178,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(TnArgs g) {
   if (nt == 0) return;
   // ---- epilogue: 32x32 C/D map col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5); one register = two 128-B row segments
   const int col = lane & 31, rb = 4 * (lane >> 5);
-  const DetCfg dc = det_load();   // deterministic-gradient switch (common.hpp), read once
+  const DetCfg dc = det_read(g.det);   // deterministic-gradient mode (common.hpp), read once
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -1371,12 +1371,12 @@ __global__ __launch_bounds__(512, 2) void gemm_tn8p_kernel(TnArgs g) {
     for (int j = 0; j < WNT; ++j) {
       const float t = cs[j] + __shfl_xor(cs[j], 32, 64);
       const int gn = n0 + wc * (WNT * 32) + j * 32 + (lane & 31);
-      if (lane < 32 && gn < g.N) grad_add(g.colsum + gn, t);
+      if (lane < 32 && gn < g.N) grad_add(det_read(g.det), g.colsum + gn, t);
     }
   }
   // ---- epilogue: 32x32 C/D map col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5); one register = two 128-B row segments
   const int col = lane & 31, rb = 4 * (lane >> 5);
-  const DetCfg dc = det_load();   // deterministic-gradient switch (common.hpp), read once
+  const DetCfg dc = det_read(g.det);   // deterministic-gradient mode (common.hpp), read once
 #pragma unroll
   for (int i = 0; i < WIT; ++i)
 #pragma unroll
@@ -1441,6 +1441,7 @@ bool gemm_tn_bf16(spa3d_ctx* c, const GemmDesc& d) {
   g.tiles_i = (Ki + 127) / 128; g.tiles_n = (N + 127) / 128;
   g.brow_group = d.brow_group; g.brow_skip = d.brow_skip; g.colsum = nullptr;
   g.seg_n = d.seg_n; g.Cseg[0] = (float*)d.C_seg[0]; g.Cseg[1] = (float*)d.C_seg[1];
+  g.det = c->det;
   if (d.seg_n > 0 && (d.seg_n % 32 || N % d.seg_n || N / d.seg_n > 3 || d.colsum_out)) return false;
   c->tn_colsum_fused = false;
   if (c->tn_big && (M >= 65536 || c->tn_big == 2) && ((Ki % 384 == 0 && N % 256 == 0) || (Ki % 256 == 0 && N % 384 == 0))) {  // large register tile (gemm_tnb.hip)
@@ -1486,5 +1487,4 @@ bool gemm_tn_bf16(spa3d_ctx* c, const GemmDesc& d) {
   SPA_LAUNCH_CHECK(c);
   return true;
 }
-SPA_DET_UPLOAD_DEF(det_upload_gemm_fast)
 }  // namespace SPA_NS

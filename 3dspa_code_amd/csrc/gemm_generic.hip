@@ -26,6 +26,7 @@ struct GemmArgs {
   int tiles_m, tiles_n, ksplit; int64_t kchunk;
   int crow_group, crow_skip, brow_group, brow_skip;
   void* pre_out;
+  const DetCfg* det;   // the call's deterministic-gradient mode (common.hpp): the split-K atomics
 };
 
 template <typename T>
@@ -148,7 +149,7 @@ __global__ __launch_bounds__(256) void gemm_generic_kernel(GemmArgs g) {
         }
         if (g.out_f32) {
           float* cp = (float*)g.C + ci;
-          if (g.atomic) grad_add(cp, v);
+          if (g.atomic) grad_add(det_read(g.det), cp, v);
           else if (g.accumulate) *cp += v;
           else *cp = v;
         } else {
@@ -169,6 +170,7 @@ void gemm_generic(spa3d_ctx* c, const GemmDesc& d) {
   g.alpha = d.alpha; g.bias = d.bias; g.epi = d.epi; g.aux = d.aux; g.aux_is_residual = d.aux_is_residual;
   g.out_f32 = d.out_f32; g.accumulate = d.accumulate; g.atomic = 0;
   g.crow_group = d.crow_group; g.crow_skip = d.crow_skip; g.brow_group = d.brow_group; g.brow_skip = d.brow_skip; g.pre_out = d.pre_out;
+  g.det = c->det;
   g.tiles_m = (int)((d.M + 63) / 64); g.tiles_n = (d.N + 63) / 64;
   int64_t nbatch = (int64_t)d.nb1 * d.nb2;
   int64_t blocks = nbatch * g.tiles_m * g.tiles_n;
@@ -194,5 +196,4 @@ void gemm_generic(spa3d_ctx* c, const GemmDesc& d) {
 }
 template void gemm_generic<float>(spa3d_ctx*, const GemmDesc&);
 template void gemm_generic<bf16_t>(spa3d_ctx*, const GemmDesc&);
-SPA_DET_UPLOAD_DEF(det_upload_gemm_generic)
 }  // namespace SPA_NS

@@ -233,13 +233,13 @@ __global__ __launch_bounds__(256, 1) void gemm_tnb_kernel(TnArgs g) {
       for (int k = 0; k < (WB ? 2 : 3); ++k) {
         const float t = cs[k] + __shfl_xor(cs[k], 32, 64);
         const int gn = n0 + (WB ? 32 * (2 * w + k) : 96 * w + 32 * k) + (lane & 31);
-        if (lane < 32) grad_add(g.colsum + gn, t);
+        if (lane < 32) grad_add(det_read(g.det), g.colsum + gn, t);
       }
     }
   }
   // ---- epilogue: 32x32 C/D map col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5); one register = two 128-B row segments (the full-rate atomic shape)
   const int col = lane & 31, rb = 4 * (lane >> 5);
-  const DetCfg dc = det_load();   // deterministic-gradient switch (common.hpp), read once: nullptr = float atomics
+  const DetCfg dc = det_read(g.det);   // deterministic-gradient mode (common.hpp), read once: shadow nullptr = float atomics
   tn_for<0, 24>([&](auto t_) {
     constexpr int t = decltype(t_)::v; constexpr int j = t / 3, i = t % 3;
     const int it = WB ? 3 * w + i : j, jt = WB ? j : 3 * w + i;   // the tile's place in the workgroup tile
@@ -271,8 +271,8 @@ __global__ __launch_bounds__(256) void gemm_tn_tail_kernel(TnArgs g, int64_t m0,
   }
   float* cb = g.C; int cn = n;
   if (g.seg_n > 0) { const int sg = n / g.seg_n; if (sg > 0) { cb = g.Cseg[sg > 1]; cn -= sg * g.seg_n; } }
-  grad_add(cb + (int64_t)i * g.ldc + cn, s);
-  if (g.colsum && i == 0) grad_add(g.colsum + n, sb);
+  grad_add(det_read(g.det), cb + (int64_t)i * g.ldc + cn, s);
+  if (g.colsum && i == 0) grad_add(det_read(g.det), g.colsum + n, sb);
 }
 
 template <bool WB, bool CS, bool REMAP>
@@ -323,6 +323,4 @@ bool gemm_tnb(spa3d_ctx* c, TnArgs g) {
   }
   return true;
 }
-
-SPA_DET_UPLOAD_DEF(det_upload_gemm_tnb)
 }  // namespace SPA_NS

@@ -36,7 +36,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, co
 template <typename T>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ x, const float* __restrict__ scale,
                                                      const float* __restrict__ stats, const T* __restrict__ dy, const T* add,
-                                                     T* dx, float* __restrict__ dscale, int64_t rows, int d) {
+                                                     T* dx, float* __restrict__ dscale, int64_t rows, int d, const DetCfg* det) {
   __shared__ float red[4][64 * LN_MAXJ / 4];  // reused per quarter below
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   float acc[LN_MAXJ];
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ x, co
         int i = lane + 64 * (j0 + j);
         if (i < d) {
           float s = red[0][j * 64 + lane] + red[1][j * 64 + lane] + red[2][j * 64 + lane] + red[3][j * 64 + lane];
-          grad_add(dscale + i, s);
+          grad_add(det_read(det), dscale + i, s);
         }
       }
     }
@@ -221,7 +221,8 @@ __global__ __launch_bounds__(256) void ln_fwd_part_kernel(const T* __restrict__ 
 // backward in the same row partition (d = 384: LPR = 16, CH = 3)
 template <typename T, int LPR, int CH>
 __global__ __launch_bounds__(256) void ln_bwd_part_kernel(const T* __restrict__ x, const float* __restrict__ scale, const float* __restrict__ stats,
-                                                          const T* __restrict__ dy, const T* add, T* dx, float* __restrict__ dscale, int64_t rows, int d) {
+                                                          const T* __restrict__ dy, const T* add, T* dx, float* __restrict__ dscale, int64_t rows, int d,
+                                                          const DetCfg* det) {
   constexpr int NV = VecOf<T>::N, RPB = 256 / LPR, DV = LPR * CH * NV;
   __shared__ float red[4][DV];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, sub = threadIdx.x & (LPR - 1);
@@ -273,7 +274,7 @@ __global__ __launch_bounds__(256) void ln_bwd_part_kernel(const T* __restrict__ 
       if (lane < LPR) red[w][(sub + LPR * c) * NV + j] = a;
     }
   __syncthreads();
-  for (int t = threadIdx.x; t < DV; t += 256) grad_add(dscale + t, red[0][t] + red[1][t] + red[2][t] + red[3][t]);
+  for (int t = threadIdx.x; t < DV; t += 256) grad_add(det_read(det), dscale + t, red[0][t] + red[1][t] + red[2][t] + red[3][t]);
 }
 template <typename T>
 void k_layernorm(spa3d_ctx* c, const T* x, const float* scale, T* y, float* stats, int64_t rows, int d) {
@@ -304,7 +305,7 @@ void k_layernorm(spa3d_ctx* c, const T* x, const float* scale, T* y, float* stat
 template <typename T, int STEPS, int U>
 __global__ __launch_bounds__(256) void ln_bwd_vec_kernel(const T* __restrict__ x, const float* __restrict__ scale,
                                                          const float* __restrict__ stats, const T* __restrict__ dy, const T* add, T* dx,
-                                                         float* __restrict__ dscale, int64_t rows, int d) {
+                                                         float* __restrict__ dscale, int64_t rows, int d, const DetCfg* det) {
   constexpr int NV = VecOf<T>::N;
   __shared__ float red[4][64 * NV];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -377,7 +378,7 @@ __global__ __launch_bounds__(256) void ln_bwd_vec_kernel(const T* __restrict__ x
       if (c < nch)
 #pragma unroll
         for (int j = 0; j < NV; ++j)
-          grad_add(dscale + c * NV + j, red[0][lane * NV + j] + red[1][lane * NV + j] + red[2][lane * NV + j] + red[3][lane * NV + j]);
+          grad_add(det_read(det), dscale + c * NV + j, red[0][lane * NV + j] + red[1][lane * NV + j] + red[2][lane * NV + j] + red[3][lane * NV + j]);
     }
   }
 }
@@ -397,15 +398,15 @@ void k_layernorm_bwd(spa3d_ctx* c, const T* x, const float* scale, const float* 
   if (d % NV == 0 && al && d <= 64 * NV * 4) {
     const int steps = (d / NV + 63) / 64;
     if constexpr (sizeof(T) == 2) {  // row-partitioned kernels: 4.9 -> 5.2 TB/s at d = 384 (2.8 -> 5.3 below 0.5 M rows), 4.85 -> 5.45 at d = 1280
-      if (d == 384) { ln_bwd_part_kernel<T, 16, 3><<<(unsigned)std::min<int64_t>(cdiv(rows, 16), 2 * gcapb), 256, 0, c->stream>>>(x, scale, stats, dy, add, dx, dscale, rows, d); SPA_LAUNCH_CHECK(c); return; }
-      if (d == 1280) { ln_bwd_part_kernel<T, 32, 5><<<(unsigned)std::min<int64_t>(cdiv(rows, 8), 2 * gcapb), 256, 0, c->stream>>>(x, scale, stats, dy, add, dx, dscale, rows, d); SPA_LAUNCH_CHECK(c); return; }
+      if (d == 384) { ln_bwd_part_kernel<T, 16, 3><<<(unsigned)std::min<int64_t>(cdiv(rows, 16), 2 * gcapb), 256, 0, c->stream>>>(x, scale, stats, dy, add, dx, dscale, rows, d, c->det); SPA_LAUNCH_CHECK(c); return; }
+      if (d == 1280) { ln_bwd_part_kernel<T, 32, 5><<<(unsigned)std::min<int64_t>(cdiv(rows, 8), 2 * gcapb), 256, 0, c->stream>>>(x, scale, stats, dy, add, dx, dscale, rows, d, c->det); SPA_LAUNCH_CHECK(c); return; }
     }
-    if (steps == 1) ln_bwd_vec_kernel<T, 1, 1><<<g, 256, 0, c->stream>>>(x, scale, stats, dy, add, dx, dscale, rows, d);  // U = 4 measured 3.7 vs 4.7 TB/s
-    else if (steps == 2) ln_bwd_vec_kernel<T, 2, 2><<<g, 256, 0, c->stream>>>(x, scale, stats, dy, add, dx, dscale, rows, d);
-    else if (steps == 3) ln_bwd_vec_kernel<T, 3, 2><<<g, 256, 0, c->stream>>>(x, scale, stats, dy, add, dx, dscale, rows, d);
-    else ln_bwd_vec_kernel<T, 4, 1><<<g, 256, 0, c->stream>>>(x, scale, stats, dy, add, dx, dscale, rows, d);
+    if (steps == 1) ln_bwd_vec_kernel<T, 1, 1><<<g, 256, 0, c->stream>>>(x, scale, stats, dy, add, dx, dscale, rows, d, c->det);  // U = 4 measured 3.7 vs 4.7 TB/s
+    else if (steps == 2) ln_bwd_vec_kernel<T, 2, 2><<<g, 256, 0, c->stream>>>(x, scale, stats, dy, add, dx, dscale, rows, d, c->det);
+    else if (steps == 3) ln_bwd_vec_kernel<T, 3, 2><<<g, 256, 0, c->stream>>>(x, scale, stats, dy, add, dx, dscale, rows, d, c->det);
+    else ln_bwd_vec_kernel<T, 4, 1><<<g, 256, 0, c->stream>>>(x, scale, stats, dy, add, dx, dscale, rows, d, c->det);
   } else {
-    ln_bwd_kernel<T><<<g, 256, 0, c->stream>>>(x, scale, stats, dy, add, dx, dscale, rows, d);
+    ln_bwd_kernel<T><<<g, 256, 0, c->stream>>>(x, scale, stats, dy, add, dx, dscale, rows, d, c->det);
   }
   SPA_LAUNCH_CHECK(c);
 }
@@ -442,7 +443,7 @@ void k_rmsnorm_heads(spa3d_ctx* c, const T* x, int64_t ldx, const float* scale, 
 template <typename T>
 __global__ __launch_bounds__(256) void rms_heads_bwd_kernel(const T* __restrict__ x, int64_t ldx, const float* __restrict__ scale,
                                                             const T* __restrict__ dy, int64_t lddy, T* __restrict__ dx, int64_t lddx,
-                                                            float* __restrict__ dscale, int64_t rows, int H, int Dh) {
+                                                            float* __restrict__ dscale, int64_t rows, int H, int Dh, const DetCfg* det) {
   __shared__ float red[4][128];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   float a0 = 0.f, a1 = 0.f;
@@ -467,8 +468,8 @@ __global__ __launch_bounds__(256) void rms_heads_bwd_kernel(const T* __restrict_
   red[w][lane] = a0; red[w][lane + 64] = a1;
   __syncthreads();
   if (w == 0) {
-    if (lane < Dh) grad_add(dscale + lane, red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane]);
-    if (lane + 64 < Dh) grad_add(dscale + lane + 64, red[0][lane + 64] + red[1][lane + 64] + red[2][lane + 64] + red[3][lane + 64]);
+    if (lane < Dh) grad_add(det_read(det), dscale + lane, red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane]);
+    if (lane + 64 < Dh) grad_add(det_read(det), dscale + lane + 64, red[0][lane + 64] + red[1][lane + 64] + red[2][lane + 64] + red[3][lane + 64]);
   }
 }
 template <typename T>
@@ -476,7 +477,7 @@ void k_rmsnorm_heads_bwd(spa3d_ctx* c, const T* x, int64_t ldx, const float* sca
                          float* dscale, int64_t rows, int H, int Dh) {
   if (c->dry || rows == 0) return;
   unsigned g = (unsigned)std::min<int64_t>(cdiv(rows * H, 4), 2048);
-  rms_heads_bwd_kernel<T><<<g, 256, 0, c->stream>>>(x, ldx, scale, dy, lddy, dx, lddx, dscale, rows, H, Dh);
+  rms_heads_bwd_kernel<T><<<g, 256, 0, c->stream>>>(x, ldx, scale, dy, lddy, dx, lddx, dscale, rows, H, Dh, c->det);
   SPA_LAUNCH_CHECK(c);
 }
 
@@ -672,7 +673,7 @@ void k_query_embed1(spa3d_ctx* c, const float* qp, int64_t nq, int nf, float tra
 // ---------------------------------------------------------------------------------------------
 template <typename T>
 __global__ void colsum_kernel(const T* __restrict__ x, int64_t rows, int n, int64_t ld_, float* __restrict__ out, int64_t rows_per_block,
-                              int rgroup, int rskip) {
+                              int rgroup, int rskip, const DetCfg* det) {
   // block (64 cols x 4 row-lanes); grid (ceil(n/64), row_splits)
   __shared__ float red[4][64];
   const int col = blockIdx.x * 64 + (threadIdx.x & 63), w = threadIdx.x >> 6;
@@ -684,12 +685,12 @@ __global__ void colsum_kernel(const T* __restrict__ x, int64_t rows, int n, int6
   }
   red[w][threadIdx.x & 63] = s;
   __syncthreads();
-  if (w == 0 && col < n) grad_add(out + col, red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x]);
+  if (w == 0 && col < n) grad_add(det_read(det), out + col, red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x]);
 }
 // vectorised: a thread owns one 16-byte column chunk and walks rows; block = 32 chunks x 8 row lanes
 template <typename T>
 __global__ __launch_bounds__(256) void colsum_vec_kernel(const T* __restrict__ x, int64_t rows, int n, int64_t ld_, float* __restrict__ out,
-                                                         int64_t rows_per_block, int rgroup, int rskip) {
+                                                         int64_t rows_per_block, int rgroup, int rskip, const DetCfg* det) {
   constexpr int NV = VecOf<T>::N;
   __shared__ float red[8][32 * NV];
   const int cx = threadIdx.x & 31, ry = threadIdx.x >> 5;
@@ -714,7 +715,7 @@ __global__ __launch_bounds__(256) void colsum_vec_kernel(const T* __restrict__ x
       float s_ = 0.f;
 #pragma unroll
       for (int k = 0; k < 8; ++k) s_ += red[k][cx * NV + j];
-      grad_add(out + ch * NV + j, s_);
+      grad_add(det_read(det), out + ch * NV + j, s_);
     }
 }
 template <typename T>
@@ -725,13 +726,13 @@ void k_colsum(spa3d_ctx* c, const T* x, int64_t rows, int n, int64_t ld_, float*
     const int64_t gx = cdiv(n / NV, 32);
     int64_t sp = std::max<int64_t>(1, std::min<int64_t>(cdiv(rows, 64), 2048 / gx + 1));   // (was rows / 512: at 1 408 rows three row splits, 59 dependent loads per thread)
     int64_t rpb_ = cdiv(rows, sp);
-    colsum_vec_kernel<T><<<dim3((unsigned)gx, (unsigned)cdiv(rows, rpb_)), 256, 0, c->stream>>>(x, rows, n, ld_, out, rpb_, rgroup, rskip);
+    colsum_vec_kernel<T><<<dim3((unsigned)gx, (unsigned)cdiv(rows, rpb_)), 256, 0, c->stream>>>(x, rows, n, ld_, out, rpb_, rgroup, rskip, c->det);
     SPA_LAUNCH_CHECK(c);
     return;
   }
   int64_t splits = std::max<int64_t>(1, std::min<int64_t>(cdiv(rows, 256), 1024 / std::max<int64_t>(1, cdiv(n, 64)) + 1));
   int64_t rpb = cdiv(rows, splits);
-  colsum_kernel<T><<<dim3((unsigned)cdiv(n, 64), (unsigned)cdiv(rows, rpb)), 256, 0, c->stream>>>(x, rows, n, ld_, out, rpb, rgroup, rskip);
+  colsum_kernel<T><<<dim3((unsigned)cdiv(n, 64), (unsigned)cdiv(rows, rpb)), 256, 0, c->stream>>>(x, rows, n, ld_, out, rpb, rgroup, rskip, c->det);
   SPA_LAUNCH_CHECK(c);
 }
 
@@ -1212,7 +1213,8 @@ template <typename T> void k_broadcast_rows(spa3d_ctx* c, const float* src, int 
   bcast_rows_kernel<T><<<GRID1D((int64_t)rows * d * B, 256), 256, 0, c->stream>>>(src, (int64_t)rows * d, dst, B); SPA_LAUNCH_CHECK(c);
 }
 template <typename T>
-__global__ void bcast_grad_kernel(const T* __restrict__ dsrc, int64_t per, int64_t B, int64_t bstride, float* __restrict__ dparam, int64_t bchunk) {
+__global__ void bcast_grad_kernel(const T* __restrict__ dsrc, int64_t per, int64_t B, int64_t bstride, float* __restrict__ dparam, int64_t bchunk,
+                                  const DetCfg* det) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= per) return;
   const int64_t b0 = (int64_t)blockIdx.y * bchunk; int64_t b1 = b0 + bchunk; if (b1 > B) b1 = B;
@@ -1224,7 +1226,7 @@ __global__ void bcast_grad_kernel(const T* __restrict__ dsrc, int64_t per, int64
   }
   for (; b < b1; ++b) s0 += ld(dsrc + b * bstride + i);
   const float s = (s0 + s1) + (s2 + s3);
-  if (gridDim.y == 1) dparam[i] += s; else grad_add(dparam + i, s);
+  if (gridDim.y == 1) dparam[i] += s; else grad_add(det_read(det), dparam + i, s);
 }
 // dparam[per] += sum_b dsrc[b*bstride + :per]   (B up to ~10^5 strided rows: split over blockIdx.y, one f32 atomic per column per slice)
 template <typename T> void k_bcast_grad(spa3d_ctx* c, const T* dsrc, int64_t per, int64_t B, int64_t bstride, float* dparam) {
@@ -1232,7 +1234,7 @@ template <typename T> void k_bcast_grad(spa3d_ctx* c, const T* dsrc, int64_t per
   const int64_t gx = cdiv(per, 256);
   int64_t gy = std::max<int64_t>(1, std::min<int64_t>(B / 32, std::max<int64_t>(1, 2048 / gx)));
   const int64_t bchunk = cdiv(B, gy); gy = cdiv(B, bchunk);
-  bcast_grad_kernel<T><<<dim3((unsigned)gx, (unsigned)gy), 256, 0, c->stream>>>(dsrc, per, B, bstride, dparam, bchunk); SPA_LAUNCH_CHECK(c);
+  bcast_grad_kernel<T><<<dim3((unsigned)gx, (unsigned)gy), 256, 0, c->stream>>>(dsrc, per, B, bstride, dparam, bchunk, c->det); SPA_LAUNCH_CHECK(c);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1340,9 +1342,9 @@ __global__ void rank_bwd_kernel(const T* __restrict__ x, const T* __restrict__ d
   }
   __syncthreads();
   for (int t = threadIdx.x; t < N; t += 256) {
-    if (gb) grad_add(gb + t, rb[t]);
+    if (gb) atomicAdd(gb + t, rb[t]);   // plain float atomics: k_rank_bwd refuses the deterministic mode
 #pragma unroll
-    for (int k = 0; k < K; ++k) grad_add(gw + (int64_t)k * N + t, rw[k * N + t]);
+    for (int k = 0; k < K; ++k) atomicAdd(gw + (int64_t)k * N + t, rw[k * N + t]);
   }
 }
 template <typename T>
@@ -1361,7 +1363,7 @@ bool k_rank_fwd(spa3d_ctx* c, const T* x, const T* w, const float* bias, T* out,
 }
 template <typename T>
 bool k_rank_bwd(spa3d_ctx* c, const T* x, const T* dy, int64_t M, int N, int K, int64_t ldy, int rgroup, int rskip, float* gw, float* gb) {
-  if (c->det_grads) return false;  // its workgroup-level reduction uses LDS float atomics (arrival order): the deterministic mode takes the GEMM path
+  if (c->det) return false;  // its workgroup-level reduction uses LDS float atomics (arrival order): the deterministic mode takes the GEMM path
   if (K < 1 || K > 4 || N % 8 || N / 8 > 256 || ldy % 8 || (((uintptr_t)dy) & 15) || M >= 0x7fffffffLL) return false;
   if (c->dry || M == 0) return true;
   const int64_t rpb = std::max<int64_t>(256, cdiv(M, 1024));
@@ -1775,10 +1777,12 @@ __global__ void uniform_noise_kernel(float* __restrict__ out, int64_t n, int64_t
 }
 // deterministic mode: fold the fixed-point shadow of a range of the gradient buffer into it (and clear the shadow: a later flush of the same range adds nothing).
 // A sum of 2^62 units or more is overflow (common.hpp DetCfg): NaN, like the sticky flag -- a wrapped sum must never reach the buffer as a finite value.
-__global__ __launch_bounds__(256) void det_flush_kernel(float* __restrict__ g, long long* __restrict__ shadow, const unsigned* __restrict__ flag,
-                                                        const float* __restrict__ unit, int64_t n) {
-  const bool bad = *flag != 0;
-  const double inv = 1.0 / (double)*unit;   // a power of two: exact
+__global__ __launch_bounds__(256) void det_flush_kernel(const DetCfg* __restrict__ det, int64_t lo, int64_t n) {
+  const DetCfg d = *det;
+  float* __restrict__ g = d.gbase + lo;
+  long long* __restrict__ shadow = d.shadow + lo;
+  const bool bad = *d.flag != 0;
+  const double inv = 1.0 / (double)d.scale;   // a power of two: exact
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const long long q = shadow[i];
     if (q != 0 || bad) {
@@ -1787,28 +1791,25 @@ __global__ __launch_bounds__(256) void det_flush_kernel(float* __restrict__ g, l
     }
   }
 }
-void k_det_flush(spa3d_ctx* c, float* g, long long* shadow, const unsigned* flag, const float* unit, int64_t n) {
+void k_det_flush(spa3d_ctx* c, int64_t lo, int64_t n) {
   if (c->dry || n <= 0) return;
-  det_flush_kernel<<<(unsigned)std::min<int64_t>(cdiv(n, 256), 8192), 256, 0, c->stream>>>(g, shadow, flag, unit, n); SPA_LAUNCH_CHECK(c);
+  det_flush_kernel<<<(unsigned)std::min<int64_t>(cdiv(n, 256), 8192), 256, 0, c->stream>>>(c->det, lo, n); SPA_LAUNCH_CHECK(c);
 }
 // the fixed-point unit of a det_grads call (common.hpp DetCfg): 2^(32 + e), e = floor(log2(denom / (n_vis * loss scale))) clamped to [-24, 40].  Inputs are the call's
 // global denominator, its own visible count and its loss scale, so the unit is a function of the call's inputs alone (bit-equal run to run and whatever the
 // all-reduce schedule).  -24 covers the fp16 mode at BASELINE configs[2] (e ~ -14); below it the unit stops coarsening and the range guards take over.
-__global__ void det_unit_kernel(const float* sums, const unsigned* poison, const float* denom_dev, const float* scale_dev, float* unit) {
+// Writes the call's DetCfg, with the unit as its scale, where the call's kernels read it.
+__global__ void det_unit_kernel(const float* sums, const unsigned* poison, const float* denom_dev, const float* scale_dev, DetCfg d, DetCfg* out) {
   const float nvis = fmaxf(loss_acc_read((const unsigned long long*)sums + 2, poison), 1.f);   // fmaxf(NaN, 1) = 1
   const float r = *denom_dev / (nvis * (scale_dev ? *scale_dev : 1.f));
   int e = 0;
   if (r > 0.f && r <= 3.0e38f) { (void)frexpf(r, &e); e = min(max(e - 1, DET_E_MIN), DET_E_MAX); }   // r = m 2^e', m in [0.5, 1): floor(log2 r) = e' - 1, exactly
-  *unit = ldexpf(1.f, 32 + e);
+  d.scale = ldexpf(1.f, 32 + e);
+  *out = d;
 }
-void k_det_unit(spa3d_ctx* c, const float* sums, const unsigned* poison, const float* denom_dev, const float* scale_dev, float* unit) {
+void k_det_unit(spa3d_ctx* c, const float* sums, const unsigned* poison, const float* denom_dev, const float* scale_dev, const DetCfg& d, DetCfg* out) {
   if (c->dry) return;
-  det_unit_kernel<<<1, 1, 0, c->stream>>>(sums, poison, denom_dev, scale_dev, unit); SPA_LAUNCH_CHECK(c);
-}
-void det_upload_all(spa3d_ctx* c, const DetCfg* d) {
-  if (c->dry) return;
-  det_upload_kernels(c->stream, d); det_upload_gemm_fast(c->stream, d); det_upload_gemm_tnb(c->stream, d); det_upload_gemm_generic(c->stream, d);
-  det_upload_attn(c->stream, d);
+  det_unit_kernel<<<1, 1, 0, c->stream>>>(sums, poison, denom_dev, scale_dev, d, out); SPA_LAUNCH_CHECK(c);
 }
 void k_uniform_noise(spa3d_ctx* c, float* out, int64_t n, uint32_t k0, uint32_t k1) {
   if (c->dry || n == 0) return;
@@ -2007,7 +2008,7 @@ __global__ __launch_bounds__(256) void attn_q1_bwd_kernel(const T* __restrict__ 
                                                           const float* __restrict__ km, int64_t nprob, int Smax, int H,
                                                           const float* __restrict__ p0, const T* __restrict__ d_o0, T* __restrict__ dq0,
                                                           T* __restrict__ dk, T* __restrict__ dv, float* __restrict__ dsq, float* __restrict__ dsk,
-                                                          int vec_, const int32_t* __restrict__ seq_off) {
+                                                          int vec_, const int32_t* __restrict__ seq_off, const DetCfg* det) {
   __shared__ float dps[4][Q1_MAXS];
   __shared__ float scl[2][4 * CC];  // s_q, s_k in lane-channel order [part][j]
   __shared__ float red[2][4 * CC];  // block accumulators of d s_q, d s_k
@@ -2030,7 +2031,7 @@ __global__ __launch_bounds__(256) void attn_q1_bwd_kernel(const T* __restrict__ 
   DetCfg dc{};
   float qlim = 0.f;
   if constexpr (DET) {   // the unit and the overflow flag of the call (common.hpp DetCfg)
-    dc = det_load();
+    dc = det_read(det);
     // one redq entry takes one addend per problem of this workgroup: bounding each by 2^62 / (that count) keeps the LDS sum below 2^62, so it cannot wrap
     const int64_t per = 4 * ((nprob + 4 * (int64_t)gridDim.x - 1) / (4 * (int64_t)gridDim.x));
     qlim = fminf(DET_ADDEND_MAX, 4.6116860184273879e18f / (float)(per > 0 ? per : 1));
@@ -2165,8 +2166,8 @@ void k_attn_q1_bwd(spa3d_ctx* c, const T* q0, int64_t ldq0, const T* k, const T*
   const int vec = (Dh % (4 * NV) == 0 && ldk % NV == 0 && ldv % NV == 0 && ldq0 % NV == 0 &&
                    ((((uintptr_t)k) | ((uintptr_t)v) | ((uintptr_t)dk) | ((uintptr_t)dv) | ((uintptr_t)q0) | ((uintptr_t)d_o0) |
                      ((uintptr_t)dq0)) & 15) == 0) ? 1 : 0;
-#define Q1B(CCv) do { if (c->det_grads) attn_q1_bwd_kernel<T, CCv, true><<<g, 256, 0, c->stream>>>(q0, ldq0, k, v, ldk, ldv, sq, sk, km, nprob, S, H, p0, d_o0, dq0, dk, dv, dsq, dsk, vec, seq_off); \
-                      else attn_q1_bwd_kernel<T, CCv, false><<<g, 256, 0, c->stream>>>(q0, ldq0, k, v, ldk, ldv, sq, sk, km, nprob, S, H, p0, d_o0, dq0, dk, dv, dsq, dsk, vec, seq_off); } while (0)
+#define Q1B(CCv) do { if (c->det) attn_q1_bwd_kernel<T, CCv, true><<<g, 256, 0, c->stream>>>(q0, ldq0, k, v, ldk, ldv, sq, sk, km, nprob, S, H, p0, d_o0, dq0, dk, dv, dsq, dsk, vec, seq_off, c->det); \
+                      else attn_q1_bwd_kernel<T, CCv, false><<<g, 256, 0, c->stream>>>(q0, ldq0, k, v, ldk, ldv, sq, sk, km, nprob, S, H, p0, d_o0, dq0, dk, dv, dsq, dsk, vec, seq_off, c->det); } while (0)
   switch (Dh / 4) { case 24: Q1B(24); break; case 16: Q1B(16); break; case 32: Q1B(32); break; case 8: Q1B(8); break; case 4: Q1B(4); break;
     case 2: Q1B(2); break; default: if (!c->hip_err) { c->hip_err = -3; c->err = "attn_q1: unsupported head width"; } return; }
 #undef Q1B
@@ -2244,5 +2245,4 @@ template void k_vis_mean_pool<float>(spa3d_ctx*, const float*, const float*, int
 template void k_vis_mean_pool<bf16_t>(spa3d_ctx*, const bf16_t*, const float*, int64_t, int, int, bf16_t*);
 template void k_vis_mean_pool_bwd<float>(spa3d_ctx*, const float*, const float*, int64_t, int, int, float*);
 template void k_vis_mean_pool_bwd<bf16_t>(spa3d_ctx*, const bf16_t*, const float*, int64_t, int, int, bf16_t*);
-SPA_DET_UPLOAD_DEF(det_upload_kernels)
 }  // namespace SPA_NS

@@ -695,13 +695,12 @@ template <typename T> struct Net {
   // each is recorded on the launch stream when its segment of the flat gradient buffer (spa3d_grad_segments) has received its last
   // contribution; the third segment (embedding, track encoder, state_init leaves) is final when the call's work is.  With a loss scale (fp16) a
   // finished segment is unscaled right before its event; the rest of the buffer at the end of the call.
-  long long* det_shadow = nullptr; const unsigned* det_flag = nullptr; const float* det_unit = nullptr;   // deterministic mode: the fixed-point shadow of G (common.hpp DetCfg)
   int64_t seg_lo[2] = {0, 0}, seg_hi[2] = {0, 0};  // flat ranges of segment 0 ([b2, n): readout side) and 1 ([b1, b2): latent stacks), spa3d_grad_segments
   const float* scale_dev = nullptr;                  // fp16 mode: the call's loss scale (device)
   bool seg_unscaled[2] = {false, false};
   void grad_segment_done(int i) {
     if (c->dry || !c->last_chunk || !c->grad_ev[i]) return;
-    if (det_shadow && seg_hi[i] > seg_lo[i]) k_det_flush(c, G + seg_lo[i], det_shadow + seg_lo[i], det_flag, det_unit, seg_hi[i] - seg_lo[i]);   // the segment's shadow sums are final too
+    if (c->det && seg_hi[i] > seg_lo[i]) k_det_flush(c, seg_lo[i], seg_hi[i] - seg_lo[i]);   // the segment's shadow sums are final too
     if (c->loss_scale != 1.f) {  // fp16: bring the finished segment back to true scale NOW (a power of two: exact) so that its all-reduce can start behind the event
       if (!scale_dev || seg_hi[i] <= seg_lo[i]) return;
       k_unscale(c, G + seg_lo[i], scale_dev, seg_hi[i] - seg_lo[i]);
@@ -937,19 +936,15 @@ void run_body(spa3d_ctx* c, const RunArgs& a, int Bc) {
     if (spa3d_grad_segments(c, b4) == SPA3D_OK) { net.seg_lo[0] = b4[2]; net.seg_hi[0] = b4[3]; net.seg_lo[1] = b4[1]; net.seg_hi[1] = b4[2]; }
     if (c->loss_scale != 1.f) net.scale_dev = denom_dev + 1;
   }
-  // deterministic parameter gradients: every reduction into G goes through a 64-bit fixed-point shadow (common.hpp DetCfg, grad_add)
+  // deterministic parameter gradients: every reduction into G goes through a 64-bit fixed-point shadow (common.hpp DetCfg, grad_add).  c->det belongs to this
+  // call alone: every launch that adds into G passes it, and it is null again before the call returns (the shadow lives in this call's workspace)
   if (train && c->det_grads) {
     long long* sh = net.template alloc<long long>(c->nparams); unsigned* fl = net.template alloc<unsigned>(64);
     k_zero(c, sh, c->nparams * 8); k_zero(c, fl, 256);
-    float* unit = (float*)(fl + 1);   // fl[0]: the sticky overflow flag, fl[1]: the fixed-point unit of this call
-    k_det_unit(c, sums, poison, denom_dev, c->loss_scale != 1.f ? denom_dev + 1 : nullptr, unit);
-    net.det_shadow = sh; net.det_flag = fl; net.det_unit = unit;
-    c->det_host = DetCfg{a.G, sh, (long long)c->nparams, fl, unit, 0.f};
-  } else c->det_host = DetCfg{nullptr, nullptr, 0, nullptr, nullptr, 0.f};
-  // The switch lives in device variables shared by every handle of the process: EVERY train call states it, on its stream, before its first kernel -- a handle that
-  // left its (now dead) shadow pointer behind must never be what the next handle's kernels see (found by tests/test_gpu_poison.py running behind tests/test_gpu_det.py)
-  // -- and a call that set a live shadow clears it again at its end (below)
-  if (train) det_upload_all(c, &c->det_host);
+    DetCfg* dc = (DetCfg*)(fl + 2);   // fl[0]: the sticky overflow flag, fl[2...]: the DetCfg of this call, with its fixed-point unit
+    k_det_unit(c, sums, poison, denom_dev, c->loss_scale != 1.f ? denom_dev + 1 : nullptr, DetCfg{a.G, sh, (long long)c->nparams, fl, 0.f}, dc);
+    c->det = dc;
+  }
   const bool intra = c->query_chunk > 0 || c->track_chunk > 0;  // run() has made Bc = 1
   // The ragged chunk (B % Bc samples) runs FIRST, so the last chunk -- the one under whose track-encoder backward the gradient segments are all-reduced -- is a
   // full one (B = 64, Bc = 9: 9 samples of encoder backward to hide behind instead of 1)
@@ -978,11 +973,9 @@ void run_body(spa3d_ctx* c, const RunArgs& a, int Bc) {
     }
     c->ar.release(mk);
   }
-  if (net.det_shadow) {
-    k_det_flush(c, a.G, net.det_shadow, net.det_flag, net.det_unit, c->nparams);   // what the segment flushes left (flushed ranges hold zeros)
-    // the shadow lives in this call's workspace: no later kernel (an op backward, the next call of any handle) may add into it (tests/test_gpu_det_edges.py)
-    c->det_host = DetCfg{nullptr, nullptr, 0, nullptr, nullptr, 0.f};
-    det_upload_all(c, &c->det_host);
+  if (c->det) {
+    k_det_flush(c, 0, c->nparams);   // what the segment flushes left (flushed ranges hold zeros)
+    c->det = nullptr;   // no later launch of this handle (an op backward, its next call) may add into the dead shadow (tests/test_gpu_det_edges.py)
   }
   if (train && c->loss_scale != 1.f) {  // fp32 gradient buffer back to true scale (exact: power of two); segments already unscaled at their events are skipped
     const int64_t lo1 = net.seg_lo[1], lo0 = net.seg_lo[0];

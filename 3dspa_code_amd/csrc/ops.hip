@@ -13,8 +13,6 @@ struct OpCtx : spa3d_ctx {
   }
   template <typename U> U* alloc(int64_t n) { return (U*)ar.alloc(n * (int64_t)sizeof(U)); }
   int status() { return ar.overflow ? SPA3D_ERR_WORKSPACE : (hip_err ? SPA3D_ERR_HIP : SPA3D_OK); }
-  // backward entries: float atomics, stated on the op's stream -- never whatever deterministic-gradient switch a train call left (common.hpp DetCfg)
-  void det_off() { det_upload_all(this, &det_host); }
 };
 
 template <typename T>
@@ -164,7 +162,6 @@ int spa3d_op_linear_bwd(const void* A, const void* B, const void* dC, void* dA, 
   FWD16(spa3d_op_linear_bwd_f16(A, B, dC, dA, dB, dbias, M, N, K, dtype, impl, ws, ws_bytes, stream))
   if (!A || !B || !dC) return SPA3D_ERR_ARG;
   OpCtx c(stream, ws, ws_bytes);
-  c.det_off();
   if (dtype == SPA3D_F32) return op_linear_bwd<float>(c, (const float*)A, (const float*)B, (const float*)dC, (float*)dA, dB, dbias, M, N, K, impl);
   return op_linear_bwd<bf16_t>(c, (const bf16_t*)A, (const bf16_t*)B, (const bf16_t*)dC, (bf16_t*)dA, dB, dbias, M, N, K, impl);
 }
@@ -210,7 +207,6 @@ int spa3d_op_layernorm_bwd(const void* x, const float* scale, const float* stats
   FWD16(spa3d_op_layernorm_bwd_f16(x, scale, stats, dy, dx, dscale, rows, d, dtype, stream))
   if (!x || !scale || !stats || !dy || !dx || !dscale || d <= 0 || d > 2048) return SPA3D_ERR_ARG;
   OpCtx c(stream, nullptr, 0);
-  c.det_off();
   if (dtype == SPA3D_F32) k_layernorm_bwd<float>(&c, (const float*)x, scale, stats, (const float*)dy, (float*)dx, dscale, rows, d, nullptr);
   else k_layernorm_bwd<bf16_t>(&c, (const bf16_t*)x, scale, stats, (const bf16_t*)dy, (bf16_t*)dx, dscale, rows, d, nullptr);
   return c.status();
@@ -240,7 +236,6 @@ int spa3d_op_attention_bwd(const void* q, const void* k, const void* v, int64_t 
                                    dscale_k, dtype, impl, ws, ws_bytes, stream))
   if (!q || !k || !v || !d_o || !dq || !dk || !dv || !dscale_q || !dscale_k || Dh > 128) return SPA3D_ERR_ARG;
   OpCtx c(stream, ws, ws_bytes);
-  c.det_off();
   apply_attn_impl(&c, impl);
   if (dtype == SPA3D_F32)
     attention_bwd<float>(&c, (const float*)q, (const float*)k, (const float*)v, ldq, ldk, ldv, scale_q, scale_k, keymask, nseq, Sq, Sk, H, Dh,

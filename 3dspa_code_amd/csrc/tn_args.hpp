@@ -14,6 +14,7 @@ struct TnArgs {
   // 8-phase / large-tile kernels only: the N output columns are seg_n-wide segments that live in different buffers (the q / k / v kernels of a fused
   // projection are separate leaves): columns [s seg_n, (s+1) seg_n) go to Cseg[s - 1] for s >= 1, row stride ldc in each.  0 = one buffer.
   int seg_n; float* Cseg[2];
+  const DetCfg* det;   // the call's deterministic-gradient mode (common.hpp)
 };
 
 // large-register-tile kernel (gemm_tnb.hip): true when the shape is covered (Ki % 384 == 0 and N % 256 == 0, or Ki % 256 == 0 and N % 384 == 0;

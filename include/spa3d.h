@@ -180,8 +180,9 @@ int spa3d_adamw_step(float* params, const float* grads, float* m, float* v, int6
  *                     loss scale))), n_vis = this call's visible query points, clamped to [-24, 40]: a power of two chosen per call from its inputs alone.
  *                     With a real batch n_vis ~ denom, so the unit is 2^-32 as before (2^-(32 + log2 ranks) data-parallel; fp16: follows the loss
  *                     scale); it is finer only when the denominator exceeds the call's own visible count.  Range: an addend of 2^55 units or more, or a
- *                     shadow sum of 2^62 units or more, turns the whole gradient buffer of the call into NaN -- never a wrapped finite value.  The switch holds only for the
- *                     train call that set it: it is cleared on the call's stream at its end, and the spa3d_op_*_bwd entry points always use float atomics.
+ *                     shadow sum of 2^62 units or more, turns the whole gradient buffer of the call into NaN -- never a wrapped finite value.  The mode is
+ *                     per handle and per train call: it travels with each launch of that call, so handles on other streams and the spa3d_op_*_bwd
+ *                     entry points (always float atomics) never see it.
  *                     Costs 8 bytes of workspace per parameter and ~3.6 % of the step at BASELINE configs[2]
  *                     (1.82 -> 1.88 s: 64-bit atomics in the dW epilogues, the 1-channel depth gradient on the GEMM path); off by default.
  * and one test mode: "poison" 0/1 -- the workspace is filled with 16-bit NaN patterns before every sample chunk (and every track / query chunk), so a read of a row that this

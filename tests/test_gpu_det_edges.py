@@ -1,8 +1,9 @@
 """Edges of the deterministic-gradient mode (spa3d_set_option "det_grads", include/spa3d.h) that tests/test_gpu_det.py does not reach:
 
-- the device-side switch must not outlive the train call that set it: an op backward (spa3d_op_*_bwd) that runs after a det_grads call and writes into the
-  range of that call's gradient buffer must still produce its full result (the caller's workspace, which held the shadow, stays alive here on purpose so that a
-  stale switch shows up as a wrong answer, never as a stray write);
+- the mode must not outlive the train call that used it: an op backward (spa3d_op_*_bwd) that runs after a det_grads call and writes into the range of that
+  call's gradient buffer must still produce its full result (the caller's workspace, which held the shadow, stays alive here on purpose so that a shadow that
+  outlived its call shows up as a wrong answer, never as a stray write);
+- the mode belongs to one handle: two handles training at the same time on two streams of one process keep each its own mode (bit-equal det_grads gradients);
 - a gradient beyond the fixed-point range must come out NaN, never as a finite value of the wrong sign or size (loss denominators far below the visible count
   drive every gradient up by the same factor, without touching the model);
 - the fixed-point unit follows denom / (visible count of the call): a denominator far above the call's own visible count (a small batch under a large global
@@ -50,29 +51,33 @@ def c772():
   return cfg, O.tree_map(lambda t: t.cuda(), p), batch, noise.cuda()
 
 
-# ------------------------------------------------------------------------------------------------ A1: the switch does not outlive its train call
+# ------------------------------------------------------------------------------------------------ A1: the mode does not outlive its train call
 class DetCall:
   """One det_grads train call through the C ABI (model.loss_and_grads without the wrapper), with the gradient buffer G and the workspace owned here and kept
-  alive until the test ends: before the switch was cleared at the end of the call, its shadow pointer pointed into this very workspace."""
+  alive until the test ends: when the mode was a device-side switch that a call cleared at its end, a stale shadow pointer pointed into this very workspace.
+  run=False: handle, G and workspace only, calls issued with enqueue() (the mode stays set)."""
 
-  def __init__(self, spa3d, inputs, precision='bf16', det=1):
+  def __init__(self, spa3d, inputs, precision='bf16', det=1, run=True):
     cfg, gp, batch, noise = inputs
     self.model = product_model(spa3d, cfg, precision)
-    lib = spa3d._lib.load()
+    self.spa3d, self.lib = spa3d, spa3d._lib.load()
     dino, depth = self.model._dims_from_params(gp)
-    h, _, n = self.model._handle(dino, depth)
-    spa3d._lib.check(lib.spa3d_set_option(h, b'det_grads', float(det)), h)
+    self.h, self.leaves, n = self.model._handle(dino, depth)
+    spa3d._lib.check(self.lib.spa3d_set_option(self.h, b'det_grads', float(det)), self.h)
     self.flat = self.model.flat_from_tree(gp)
-    b, self.keep = self.model._marshal(_gpu_batch(batch, precision), dino, depth, targets=True, discretize=True, noise=noise)
+    self.b, self.keep = self.model._marshal(_gpu_batch(batch, precision), dino, depth, targets=True, discretize=True, noise=noise)
     self.G = torch.zeros(n, dtype=torch.float32, device='cuda')
     self.loss3 = torch.empty(4, dtype=torch.float32, device='cuda')
-    self.ws = self.model._workspace(h, b.B, b.N, b.Q, b.T, True, self.G.device)
-    spa3d._lib.check(lib.spa3d_loss_and_grads(h, self.flat.data_ptr(), C.byref(b), 0.0, self.G.data_ptr(), 0, self.loss3.data_ptr(), None,
-                                              self.ws.data_ptr(), self.ws.numel(), _s()), h, 'spa3d_loss_and_grads')
-    torch.cuda.synchronize()
-    spa3d._lib.check(lib.spa3d_set_option(h, b'det_grads', 0.0), h)
-    self.b = b
+    self.ws = self.model._workspace(self.h, self.b.B, self.b.N, self.b.Q, self.b.T, True, self.G.device)
     self.n = n
+    if run:
+      self.enqueue(_s())
+      torch.cuda.synchronize()
+      spa3d._lib.check(self.lib.spa3d_set_option(self.h, b'det_grads', 0.0), self.h)
+
+  def enqueue(self, stream):
+    self.spa3d._lib.check(self.lib.spa3d_loss_and_grads(self.h, self.flat.data_ptr(), C.byref(self.b), 0.0, self.G.data_ptr(), 0, self.loss3.data_ptr(), None,
+                                                        self.ws.data_ptr(), self.ws.numel(), stream), self.h, 'spa3d_loss_and_grads')
 
   def view(self, offset, numel):
     assert 0 <= offset and offset + numel <= self.n
@@ -196,13 +201,47 @@ def test_attention_bwd_scale_grads_after_a_det_grads_call(c772, dtype, impl, nse
 
 def test_op_after_a_det_call_and_a_plain_call_on_another_handle(c772):
   """det_grads train call on one handle, plain train call on a second one, then an op backward: the op sees float atomics whatever the order of the calls.
-  A regression guard for the order independence, not a reproduction of the stale switch: the plain call states the switch off at its start, so this passed
-  before the switch was cleared at the end of a det_grads call too."""
+  A regression guard for the order independence, not a reproduction of the stale mode: when the mode was a device-side switch, the plain call stated it off
+  at its start, so this passed before the switch was cleared at the end of a det_grads call too."""
   import spa3d
   call = DetCall(spa3d, c772, 'bf16', det=1)
   plain = DetCall(spa3d, c772, 'fp32', det=0)
   assert plain.model is not call.model
   _linear_bwd_into(spa3d._lib.load(), call, 5000, 384, 256, 2)
+
+
+@pytest.mark.parametrize('prec_a,prec_b,det_b', [('fp32', 'fp32', 1), ('fp32', 'bf16', 1), ('fp32', 'fp32', 0)])
+def test_two_handles_on_two_streams(c772, prec_a, prec_b, det_b):
+  """Two handles train at the same time on two streams of one process (include/spa3d.h: one handle per stream), four calls each, alternating, with no host
+  synchronisation in between: handle A (det_grads 1) must give the bits of its solo run in every call, handle B those of its solo run with det_grads 1, or
+  stay within the float-atomic gate of tests/test_gpu_det.py with det_grads 0.  A is fp32, which reads nothing back mid-call, so the host runs whole calls
+  ahead of the device and the two streams overlap.  When the mode was a process-wide device variable, B's call stated B's mode between A's kernels.
+  A regression guard: whether calls overlap depends on timing."""
+  import spa3d
+  calls = (DetCall(spa3d, c772, prec_a, det=1, run=False), DetCall(spa3d, c772, prec_b, det=det_b, run=False))
+  solo = []
+  for call in calls:
+    call.enqueue(_s())
+    torch.cuda.synchronize()
+    solo.append(call.G.clone())
+  streams = (torch.cuda.Stream(), torch.cuda.Stream())
+  got = ([], [])
+  for _ in range(4):
+    for call, st, out in zip(calls, streams, got):
+      call.enqueue(C.c_void_p(st.cuda_stream))
+      with torch.cuda.stream(st):
+        out.append(call.G.clone())   # in stream order: after this call, before the next one zeroes G
+  torch.cuda.synchronize()
+  for name, call, det, ref, out in zip('AB', calls, (1, det_b), solo, got):
+    for i, g in enumerate(out):
+      if det:
+        diff = [k for k, shape, off in call.leaves if not torch.equal(g[off:off + math.prod(shape)], ref[off:off + math.prod(shape)])]
+        assert not diff, f'handle {name} ({call.model.precision}, det_grads) call {i}: {len(diff)} leaves differ from its solo run, e.g. {diff[:3]}'
+      else:
+        worst = max((rel_err(g[off:off + math.prod(shape)], ref[off:off + math.prod(shape)]), k) for k, shape, off in call.leaves
+                    if float(ref[off:off + math.prod(shape)].double().norm()) > 0)
+        print(f'handle {name} ({call.model.precision}, float atomics) call {i}: worst leaf vs its solo run {worst}')
+        assert worst[0] < 5e-5, f'handle {name} call {i}: {worst}'
 
 
 # ------------------------------------------------------------------------------------------------ A2 / A3: range and resolution of the fixed point
