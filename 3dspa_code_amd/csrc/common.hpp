@@ -7,6 +7,7 @@
 
 #include "../../include/spa3d.h"
 #include "ablate.inc"  // every work-skipping diagnostic mask, all 0 in libspa3d_hip.so
+#include "gemm_plan.hpp"  // GemmDesc and the kernel choice (host-only)
 
 // One translation unit is compiled for exactly ONE 16-bit activation type: bf16 (default) or IEEE fp16 (-DSPA_F16=1, BASELINE
 // cfg#5).  The raw 16-bit storage type is `bf16_t` (unsigned short) in both builds; what differs -- the two conversions, the MFMA
@@ -197,7 +198,7 @@ struct spa3d_ctx {
   Arena ar;
   bool dry = false;   // orchestration runs without launching (workspace sizing)
   int hip_err = 0;
-  int gemm_impl = 0;  // 0 auto, 1 generic only, 2 tiled (see apply_gemm_impl)
+  GemmPolicy gemm;    // "gemm_impl": which kernels the GEMMs may run on (gemm_plan.hpp)
   int attn_impl = 0;  // 0 auto, 1 generic, 2 fused (see apply_attn_impl)
   int chunk = 0;      // samples per chunk: 0 = as many as fit the workspace (spa3d_set_option "chunk")
   int query_chunk = 0;    // spa3d_set_option "query_chunk": readout over chunks of this many queries (0 = all Q at once); implies one sample per chunk
@@ -211,41 +212,16 @@ struct spa3d_ctx {
   bool last_chunk = false;
   const float* loss_scale_state = nullptr;  // caller-owned device float (spa3d_set_loss_scale_state): dynamic multiplier of the loss scale
   double plan_stats[4] = {0, 0, 0, 0};  // last train call: encoder rows kept, encoder rows dense, readout slots, queries (spa3d_plan_stats)
-  // kernel-choice knobs behind gemm_impl / attn_impl (spa3d_set_option; values 3+ are test hooks that put small problems on the big kernels)
+  // attention kernel-choice knobs behind attn_impl (spa3d_set_option; values 3+ are test hooks)
   int attn_bwd_mode = 0;  // fused attention backward structure: 0 auto (1 up to S = 160, else 3), 1 four images + concurrent roles, 2 split-pass 4 waves, 3 split-pass 8 waves
-  int nt_8p = 1;          // 8-phase NT kernels (256x256 / 128x384): 1 for M >= 16 384, 2 for any M (tests), 0 off
-  int nt_8pp = 5;         // their persistent forms: 5 both tiles (default), 1 the 256x256 one only (tests: the non-persistent 128x384 kernel), 0 off
-  int tn_8p = 1;          // 8-phase TN (dW) kernels: 1 by size, 2 forced (tests), 0 off
-  int tn_big = 1;         // large-register-tile TN (dW) kernel (gemm_tnb.hip): 1 by size, 2 forced (tests), 0 off (gemm_impl 6 / 8)
-  int nt_occ = 1;         // single-buffer 4-workgroups/CU NT kernel for K <= 512; 0 (tests) = the double-buffered kernel
-  int nt_stream = 1;      // non-temporal stores for 16-bit outputs >= 512 MB
-  int embed_fused = 1;    // input embedding as ONE GEMM over the concatenated K written once, in compact row order (model.hip encode_chunk); gemm_impl 6 = the multi-pass path
-  int mlp_fused = 1;      // track-encoder MLP forward as ONE sequence-resident kernel (mlp_fused.hip); gemm_impl 6 = the two tiled GEMMs
-  int nt_big = 1;         // large-register-tile NT kernel (gemm_ntb.hip) for the N = 384 dX GEMMs of the track encoder; 2 forced for any M (tests, gemm_impl 9), 0 off (gemm_impl 6 / 8)
-  int rs_gemm = 1;        // K = 384 projections on the row-stationary kernel (gemm_rs.hip); gemm_impl 6 = the tiled kernels; 7 (ops) = required
   int qkv_attn = 0;       // track-encoder QKV projection + attention forward as ONE kernel (qkv_attn.hip): built and measured in round 5, 1.47x SLOWER than the
                           // projection GEMM + attention kernel pair (profiles/r05_qkv_attn_fused.log), so opt-in only: attn_impl 6
   int det_grads = 0;      // spa3d_set_option "det_grads": order-independent parameter gradients (fixed-point shadow accumulation, DetCfg above); costs a few %
   const DetCfg* det = nullptr;  // the running det_grads train call's mode, in its workspace, passed to every kernel that adds into G; nullptr = float atomics
   int poison = 0;         // spa3d_set_option "poison": NaN-fill the workspace before every chunk and every op output before its launch (tests)
-  bool tn_colsum_fused = false;  // set by gemm_tn_bf16: the last call also produced GemmDesc::colsum_out
   Prof prof;
 };
 
-// gemm_impl: 0 product dispatch | 1 generic kernels only | 2 tiled kernels, product tile choice (ops: error when unusable) -- and test hooks that put
-// SMALL problems on the big kernels: 3 every eligible GEMM on the 8-phase kernels (persistent forms included; dW on the 8-wave kernels), 4 the same with the non-persistent
-// 128x384 kernel, 5 tiled without the single-buffer short-K kernel, 6 tiled GEMMs without the round-4 kernels (MLP forward as two GEMMs, multi-pass input embedding, no row-stationary
-// K = 384 kernel, no round-5 large-tile dW kernel), 7 (ops only) the row-stationary kernel or an error, 8 the product dispatch without the round-5 large-tile dW kernel, 9 = 3 with every divisible dW on the large-tile kernel
-inline void apply_gemm_impl(spa3d_ctx* c, int v) {
-  c->gemm_impl = v == 1 ? 1 : (v >= 2 ? 2 : 0);
-  c->nt_8p = 1; c->nt_8pp = 5; c->tn_8p = 1; c->tn_big = 1; c->nt_big = 1; c->nt_occ = 1; c->mlp_fused = 1; c->embed_fused = 1; c->rs_gemm = 1;
-  if (v == 3 || v == 4) { c->nt_8p = 2; c->tn_8p = 2; c->tn_big = 0; c->nt_big = 0; }
-  if (v == 9) { c->nt_8p = 2; c->tn_8p = 2; c->tn_big = 2; c->nt_big = 2; }
-  if (v == 4) c->nt_8pp = 1;
-  if (v == 5) c->nt_occ = 0;
-  if (v == 6) { c->mlp_fused = 0; c->embed_fused = 0; c->rs_gemm = 0; c->tn_big = 0; c->nt_big = 0; }
-  if (v == 8) { c->tn_big = 0; c->nt_big = 0; }
-}
 // attn_impl: 0 product dispatch | 1 generic composition (GEMMs + softmax kernels) | 2 fused kernels (ops: error when unusable) | 3 / 4 fused with the
 // split-pass backward on 4 / 8 waves also where the four-image kernel would run (S <= 160; tests) | 6 fused kernels with the track encoder's QKV projection + attention forward as ONE launch (qkv_attn.hip)
 inline void apply_attn_impl(spa3d_ctx* c, int v) {
@@ -276,70 +252,42 @@ struct ProfScope {  // records an event pair around the launches issued in its l
     }                                                                             \
   } while (0)
 
-// ------------------------------------------------------------------------------------------
-// GEMM descriptor (generic, batched, strided).  C[b][m][n] (op)= alpha*sum_k A[b][m][k]*B[b][k][n]
-// ------------------------------------------------------------------------------------------
-enum { EPI_NONE = 0, EPI_GELU = 1, EPI_MUL_GELU_GRAD = 2 };
-struct GemmDesc {
-  const void* A; const void* B; void* C;
-  int64_t M; int32_t N; int32_t K;
-  int64_t sAm, sAk, sBk, sBn, sCm;   // element strides (C is n-contiguous)
-  int32_t nb1 = 1, nb2 = 1;          // two-level batch: blockIdx.z = b1*nb2 + b2
-  int64_t bA1 = 0, bA2 = 0, bB1 = 0, bB2 = 0, bC1 = 0, bC2 = 0;
-  float alpha = 1.f;
-  const float* bias = nullptr;       // [N] f32, added before act
-  int epi = EPI_NONE;
-  const void* aux = nullptr;         // residual (added after act) or pre-activation (EPI_MUL_GELU_GRAD); C layout, T
-  int aux_is_residual = 1;
-  int out_f32 = 0;                   // C is float regardless of T
-  int accumulate = 0;                // C += (non-atomic)
-  int atomic = 0;                    // C += via atomicAdd (f32 C only)
-  float* colsum_out = nullptr;       // TN (dW) only: also accumulate the column sums of B (bias gradient) when the kernel can;
-                                     // the callee reports it in spa3d_ctx::tn_colsum_fused
-  const void* Bt = nullptr;          // optional copy of B stored [N][K] (K contiguous, row stride ldBt) for the tiled kernels
-  int64_t ldBt = 0;
-  int32_t crow_group = 0, crow_skip = 0;  // C row m is stored at row m + (m/crow_group + 1)*crow_skip (token rows behind a readout row)
-  int32_t brow_group = 0, brow_skip = 0;  // same remap on B's k index (dW over token rows that skip the readout row)
-  void* pre_out = nullptr;                // with EPI_GELU: the pre-activation (T, C layout) is stored here as well
-  const void* zero_page = nullptr;        // >= 16 B of zeros (tiled TN kernel: rows past the end of the reduction)
-  // one-pass input embedding (tiled NT, N == 384, 16-bit): K columns [0, K1) from A, [K1, K) from A2 (row stride sA2m); input rows gathered through
-  // arow_idx (both sources; also indexes r1_x), output rows scattered through crow_idx (< 0 = dropped); epilogue += r1_x[input row] * r1_w[n] in f32.
-  // gemm_nt_bf16 returns false when it cannot honour them (the caller then takes the multi-pass path)
-  const void* A2 = nullptr; int64_t sA2m = 0; int32_t K1 = 0; const int32_t* arow_idx = nullptr; const int32_t* crow_idx = nullptr;
-  const void* r1_x = nullptr; const float* r1_w = nullptr;
-  int32_t seg_n = 0; void* C_seg[2] = {nullptr, nullptr};  // tiled TN (dW) only: output columns in seg_n-wide segments, segment s >= 1 in C_seg[s-1]
-                                                          // (the q / k / v kernels of a fused projection are separate leaves); gemm_tn_bf16 returns
-                                                          // false when it cannot honour it
-};
-
 namespace SPA_NS {
 template <typename T> void gemm_generic(spa3d_ctx* c, const GemmDesc& d);
-// tiled bf16 kernels (gemm_fast.hip).  Return false if the shape/layout is not supported.
-bool gemm_nt_bf16(spa3d_ctx* c, const GemmDesc& d);
-bool gemm_tn_bf16(spa3d_ctx* c, const GemmDesc& d);
+// The GEMM launchers: each launches the kernel gemm_plan.hpp chose for the descriptor (never a refused or dry-run plan: gemm_launch)
+void gemm_nt_bf16(spa3d_ctx* c, const GemmDesc& d, GemmKernel k);   // the tiled NT kernels (gemm_fast.hip)
+void gemm_tn_bf16(spa3d_ctx* c, const GemmDesc& d, GemmKernel k);   // the dW kernels (gemm_fast.hip, gemm_tnb.hip)
 // large-register-tile NT GEMM (gemm_ntb.hip): C[M,N] (16-bit) = A[M,K] . W (+ bias), N a multiple of 384 (tile 256 x 384) or 256 (384 x 256), K % 32 == 0;
-// W pre-packed by gemm_ntb_pack (element (k, n) of W at w[k*sk + n*sn])
-bool gemm_ntb_ok(int K, int N);
+// W pre-packed by gemm_ntb_pack (element (k, n) of W at w[k*sk + n*sn]) as d.ntb_pk
 int64_t gemm_ntb_pack_elems(int K, int N);
 template <typename S> void gemm_ntb_pack(spa3d_ctx* c, const S* w, int64_t sk, int64_t sn, int K, int N, bf16_t* wpk);
-bool gemm_ntb(spa3d_ctx* c, const bf16_t* A, int64_t lda, const bf16_t* wpk, const float* bias, bf16_t* C, int64_t ldc, int64_t M, int N, int K);
+void gemm_ntb(spa3d_ctx* c, const GemmDesc& d);
 // row-stationary K = 384 GEMM (gemm_rs.hip): C[M,N] = A[M,384] . W (+ bias) with W pre-packed into the kernel's fragment stream (element (k, n) of W at w[k*sk + n*sn])
-bool gemm_rs_ok(int K, int N);
+// as d.rs_pk; EPI_MUL_GELU_GRAD: C = (A . W + bias) o gelu'(d.aux) (C's layout): the MLP backward's dh
 int64_t gemm_rs_pack_elems(int N);
 template <typename S> void gemm_rs_pack(spa3d_ctx* c, const S* w, int64_t sk, int64_t sn, int N, bf16_t* wpk);
-// gelu_pre != null: C = (A . W + bias) o gelu'(gelu_pre) (gelu_pre in C's layout, row stride ldpre): the MLP backward's dh
-bool gemm_rs(spa3d_ctx* c, const bf16_t* A, int64_t lda, const bf16_t* wpk, const float* bias, bf16_t* C, int64_t ldc, int64_t M, int N,
-             const bf16_t* gelu_pre = nullptr, int64_t ldpre = 0);
+void gemm_rs(spa3d_ctx* c, const GemmDesc& d);
 // QKV projection + attention forward of one (sequence, head) per workgroup pass (qkv_attn.hip): d = 384, Dh = 96, S <= 160; false = shape not covered
 int64_t qkv_attn_pack_elems(int H);
 template <typename S> void qkv_attn_pack(spa3d_ctx* c, const S* wq, const S* wk, const S* wv /* [384][E] */, int E, int H, bf16_t* wpk);
 bool qkv_attn_fwd(spa3d_ctx* c, const bf16_t* nq, int64_t ldn, const bf16_t* wpk, const float* sq, const float* sk, const float* km, int64_t nseq, int S, int H,
                   int Dh, int d, bf16_t* qkv, bf16_t* o, float* lse, const int32_t* seq_off, int64_t total_rows);
-// sequence-resident MLP forward for d = 384, mlp = 1536 (mlp_fused.hip): y = a + MLP(na), h / hpre kept; false = shape not covered
+// sequence-resident MLP forward for d = 384, mlp = 1536 (mlp_fused.hip): y = a + MLP(na), h / hpre kept; launched when plan_mlp says MlpFused
 template <typename S> void mlp_fused_pack(spa3d_ctx* c, const S* w_in /*[384][1536]*/, const S* w_out /*[1536][384]*/, bf16_t* wpk);
 int64_t mlp_fused_pack_elems();
-bool mlp_fused_fwd(spa3d_ctx* c, const bf16_t* na, const bf16_t* a, bf16_t* y, bf16_t* h, bf16_t* hpre, int64_t M, int d, int mlp,
-                   const bf16_t* wpk, const float* b_in, const float* b_out);
+void mlp_fused_fwd(spa3d_ctx* c, const bf16_t* na, const bf16_t* a, bf16_t* y, bf16_t* h, bf16_t* hpre, int64_t M, const bf16_t* wpk,
+                   const float* b_in, const float* b_out);
+// runs a planned GEMM (not Refuse); nothing in the dry run, which only needed the plan
+template <typename T> void gemm_launch(spa3d_ctx* c, const GemmDesc& d, GemmKernel k) {
+  if (c->dry) return;
+  if constexpr (sizeof(T) == 2) {
+    if (k == GemmKernel::Rs) return gemm_rs(c, d);
+    if (k == GemmKernel::Ntb) return gemm_ntb(c, d);
+    if (gemm_is_tn(k)) return gemm_tn_bf16(c, d, k);
+    if (k != GemmKernel::Generic) return gemm_nt_bf16(c, d, k);
+  }
+  gemm_generic<T>(c, d);
+}
 
 // ------------------------------------------------------------------------------------------
 // elementwise / reduction kernels (kernels.hip), all asynchronous on c->stream; no-ops when c->dry

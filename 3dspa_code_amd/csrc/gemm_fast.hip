@@ -974,31 +974,9 @@ __global__ __launch_bounds__(512, 2) void gemm_nt8pp_kernel(NtArgs g) {
   }
 }
 
-static bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
-bool gemm_nt_bf16(spa3d_ctx* c, const GemmDesc& d) {
-  // needs B as [N][K] with K contiguous: either the explicit transposed copy or B itself when sBk == 1
-  const bf16_t* Bt = nullptr; int64_t ldb = 0;
-  if (d.Bt) { Bt = (const bf16_t*)d.Bt; ldb = d.ldBt; }
-  else if (d.sBk == 1) { Bt = (const bf16_t*)d.B; ldb = d.sBn; }
-  else return false;
-  if (d.sAk != 1 || d.nb1 != 1 || d.nb2 != 1 || d.atomic) return false;
-  if (d.K % 64 || d.N % 8 || d.M < 1 || d.K < 64) return false;
-  if (d.sAm % 8 || ldb % 8 || d.sCm % 8 || !aligned16(d.A) || !aligned16(Bt) || !aligned16(d.C)) return false;
-  if (d.aux && (!aligned16(d.aux) || d.out_f32)) return false;
-  if (d.bias && !aligned16(d.bias)) return false;
-  if (d.pre_out && (!aligned16(d.pre_out) || d.out_f32)) return false;
-  if ((int64_t)d.M * d.N < 128 * 128) return false;  // tiny problems: the generic kernel has less tail waste
-  const bool emb = d.A2 || d.arow_idx || d.crow_idx || d.r1_x;
-  if (emb) {  // one-pass input embedding: only the non-persistent 128 x 384 8-phase kernel carries these operands.  Checked BEFORE the dry-run return: the sizing pass
-              // must refuse exactly what the real run refuses, or the caller's fallback allocates buffers the workspace was never sized for
-    if (d.N != 384 || d.out_f32 || d.accumulate || d.aux || d.pre_out || d.epi != EPI_NONE || d.crow_group) return false;
-    if (d.A2 && (d.K1 % 64 || d.K1 <= 0 || d.K1 >= d.K || d.sA2m % 8 || (!c->dry && !aligned16(d.A2)))) return false;
-    if (d.r1_x && !d.r1_w) return false;
-  }
-  if (c->dry) return true;
+void gemm_nt_bf16(spa3d_ctx* c, const GemmDesc& d, GemmKernel k) {
   NtArgs g;
-  g.A = (const bf16_t*)d.A; g.Bt = Bt; g.C = d.C; g.M = d.M; g.N = d.N; g.K = d.K; g.lda = d.sAm; g.ldb = ldb; g.ldc = d.sCm;
+  g.A = (const bf16_t*)d.A; g.Bt = (const bf16_t*)(d.Bt ? d.Bt : d.B); g.C = d.C; g.M = d.M; g.N = d.N; g.K = d.K; g.lda = d.sAm; g.ldb = d.Bt ? d.ldBt : d.sBn; g.ldc = d.sCm;
   g.bias = d.bias; g.aux = (const bf16_t*)d.aux; g.pre_out = (bf16_t*)d.pre_out; g.epi = d.epi; g.out_f32 = d.out_f32; g.accumulate = d.accumulate; g.alpha = d.alpha;
   g.tiles_m = (int)((d.M + 127) / 128); g.tiles_n = (d.N + 127) / 128;
   g.crow_group = d.crow_group; g.crow_skip = d.crow_skip;
@@ -1006,23 +984,17 @@ bool gemm_nt_bf16(spa3d_ctx* c, const GemmDesc& d) {
 #if SPA3D_ABL_NT
   { const char* e = getenv("SPA3D_ABLATE"); g.ablate = e ? atoi(e) : 0; }
 #endif
-  g.nt_store = (!d.out_f32 && (double)d.M * d.N * 2.0 >= 512e6 && c->nt_stream) ? 1 : 0;
+  g.nt_store = (!d.out_f32 && (double)d.M * d.N * 2.0 >= 512e6) ? 1 : 0;   // non-temporal stores for 16-bit outputs >= 512 MB
   const int64_t blocks = (int64_t)((g.tiles_m + 7) / 8) * 8 * g.tiles_n;
-  if (blocks > 0x7fffffffLL) return false;
   static bool attr_set = false;
   if (!attr_set) { (void)hipFuncSetAttribute((const void*)gemm_nt_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 65536); attr_set = true; }
   // algorithmic bytes: A, B, C once, plus the residual / pre-activation operand read and the second (pre-activation) output
   ProfScope ps(c, PROF_GEMM_NT, 2.0 * (double)d.M * d.N * d.K,
                ((double)d.M * d.K + (double)d.K * d.N + (double)d.M * d.N * (d.out_f32 ? 2.0 : 1.0) * (d.accumulate ? 2.0 : 1.0) + (double)d.M * d.N * ((d.aux ? 1.0 : 0.0) + (d.pre_out ? 1.0 : 0.0))) * 2.0);
-  ps.tag(d.M, d.N, d.K, d.epi | (d.aux ? 4 : 0) | (d.pre_out ? 8 : 0) | (d.out_f32 ? 16 : 0) | (d.accumulate ? 32 : 0) | (d.crow_group ? 64 : 0) | (d.sAm != d.K ? 128 : 0));
-  const int KT = d.K / 64;
-  if (emb) { g.nt_store = 0; launch_nt8p<4, 6, true>(c, g); SPA_LAUNCH_CHECK(c); return true; }
-  // 8-phase kernels: 256x256 when 256 | N, 128x384 when 384 | N (see the kernel header for the measurements); nt_8p == 2 (tests): any M
-  if (c->nt_8p && (d.N % 256 == 0 || d.N % 384 == 0) && (d.M >= 256 * 64 || c->nt_8p == 2)) {
-    // persistent forms (nt_8pp; accumulate would add loads to the counted wait).  nt_8pp == 1 (tests): the 256x256 one only
-    const bool pers_ok = c->nt_8pp && d.K >= 128 && !d.accumulate && d.crow_group == 0 && d.M % 8 == 0 && (!d.aux || (!d.pre_out && !d.out_f32));
-    const bool use384 = pers_ok && c->nt_8pp == 5 && !d.pre_out && !d.out_f32 && d.N % 384 == 0 && d.N % 256 != 0;
-    if (pers_ok && d.N % 256 == 0) {
+  ps.tag(d.M, d.N, d.K, gemm_prof_flags(k, d, 0));
+  switch (k) {
+    case GemmKernel::NtEmbed: g.nt_store = 0; launch_nt8p<4, 6, true>(c, g); break;
+    case GemmKernel::Nt8pp256: {
       NtArgs g2 = g; g2.tiles_m = (int)((g.M + 255) / 256); g2.tiles_n = g.N / 256;
       static bool attrp = false;
       if (!attrp) {
@@ -1032,7 +1004,9 @@ bool gemm_nt_bf16(spa3d_ctx* c, const GemmDesc& d) {
       }
       if (d.aux) gemm_nt8pp_kernel<8, 4, true, true><<<256, 512, 163840, c->stream>>>(g2);
       else gemm_nt8pp_kernel<8, 4, true, false><<<256, 512, 163840, c->stream>>>(g2);
-    } else if (use384) {  // persistent 128x384: slower than the non-persistent kernel on a PLAIN epilogue at K = 768 (759 vs 840 TF/s), faster on every N = 384 shape of the step, whose epilogues mostly carry a residual (out-projection +19 %, MLP-out +12 %, dX shapes +1.5 %)
+      break;
+    }
+    case GemmKernel::Nt8pp384: {  // persistent 128x384: slower than the non-persistent kernel on a PLAIN epilogue at K = 768 (759 vs 840 TF/s), faster on every N = 384 shape of the step, whose epilogues mostly carry a residual (out-projection +19 %, MLP-out +12 %, dX shapes +1.5 %)
       NtArgs g2 = g; g2.tiles_m = (int)((g.M + 127) / 128); g2.tiles_n = g.N / 384;
       static bool attrq = false;
       if (!attrq) {
@@ -1042,19 +1016,14 @@ bool gemm_nt_bf16(spa3d_ctx* c, const GemmDesc& d) {
       }
       if (d.aux) gemm_nt8pp_kernel<4, 6, false, true><<<256, 512, 163840, c->stream>>>(g2);
       else gemm_nt8pp_kernel<4, 6, false, false><<<256, 512, 163840, c->stream>>>(g2);
-    } else if (d.N % 256 == 0) launch_nt8p<8, 4>(c, g);
-    else launch_nt8p<4, 6>(c, g);
-    SPA_LAUNCH_CHECK(c);
-    return true;
+      break;
+    }
+    case GemmKernel::Nt8p256: launch_nt8p<8, 4>(c, g); break;
+    case GemmKernel::Nt8p384: launch_nt8p<4, 6>(c, g); break;
+    case GemmKernel::NtOcc: gemm_nt_occ_kernel<<<(unsigned)blocks, 256, 32768, c->stream>>>(g); break;   // (+12 % at K = 384: 594 -> 667 TF/s)
+    default: gemm_nt_kernel<<<(unsigned)blocks, 256, 65536, c->stream>>>(g); break;
   }
-  if (c->nt_occ && KT <= 8) {  // short K: single LDS buffer, 4 workgroups/CU (+12 % at K = 384: 594 -> 667 TF/s)
-    gemm_nt_occ_kernel<<<(unsigned)blocks, 256, 32768, c->stream>>>(g);
-    SPA_LAUNCH_CHECK(c);
-    return true;
-  }
-  gemm_nt_kernel<<<(unsigned)blocks, 256, 65536, c->stream>>>(g);
   SPA_LAUNCH_CHECK(c);
-  return true;
 }
 
 // =================================================================================================================
@@ -1427,48 +1396,26 @@ static void launch_tn8p(spa3d_ctx* c, const TnArgs& g, int rounds) {
   launch_tn8p_q<WIT, WNT, 2>(c, g, rounds);  // two quarters per phase (+7-10 % over one: NOTEBOOK.md, "How the GEMMs got ...", item 5)
 }
 
-bool gemm_tn_bf16(spa3d_ctx* c, const GemmDesc& d) {
-  // A[m'=i][k'=m] = X[m][i]: sAm == 1, sAk == lda ; B[k'=m][n]: sBn == 1, sBk == ldb ; f32 accumulate
-  if (d.sAm != 1 || d.sBn != 1 || !d.out_f32 || !d.accumulate || d.nb1 != 1 || d.nb2 != 1) return false;
-  if (d.epi != EPI_NONE || d.aux || d.bias || d.alpha != 1.f || !d.zero_page) return false;
+void gemm_tn_bf16(spa3d_ctx* c, const GemmDesc& d, GemmKernel k) {
   const int Ki = (int)d.M, N = d.N; const int64_t M = d.K;
-  if (Ki % 8 || N % 8 || Ki < 8 || N < 8 || M < 256) return false;
-  if (d.sAk % 8 || d.sBk % 8 || !aligned16(d.A) || !aligned16(d.B)) return false;
-  if (c->dry) return true;
   TnArgs g;
   g.A = (const bf16_t*)d.A; g.B = (const bf16_t*)d.B; g.C = (float*)d.C; g.zero = (const bf16_t*)d.zero_page;
   g.M = M; g.Ki = Ki; g.N = N; g.lda = d.sAk; g.ldb = d.sBk; g.ldc = d.sCm;
   g.tiles_i = (Ki + 127) / 128; g.tiles_n = (N + 127) / 128;
-  g.brow_group = d.brow_group; g.brow_skip = d.brow_skip; g.colsum = nullptr;
+  g.brow_group = d.brow_group; g.brow_skip = d.brow_skip; g.colsum = gemm_tn_fuses_colsum(k, d) ? d.colsum_out : nullptr;
   g.seg_n = d.seg_n; g.Cseg[0] = (float*)d.C_seg[0]; g.Cseg[1] = (float*)d.C_seg[1];
   g.det = c->det;
-  if (d.seg_n > 0 && (d.seg_n % 32 || N % d.seg_n || N / d.seg_n > 3 || d.colsum_out)) return false;
-  c->tn_colsum_fused = false;
-  if (c->tn_big && (M >= 65536 || c->tn_big == 2) && ((Ki % 384 == 0 && N % 256 == 0) || (Ki % 256 == 0 && N % 384 == 0))) {  // large register tile (gemm_tnb.hip)
+  if (k != GemmKernel::Tn) {
     ProfScope ps(c, PROF_GEMM_TN, 2.0 * (double)M * Ki * N, ((double)M * Ki + (double)M * N) * 2.0);
-    ps.tag(M, N, Ki, 1 << 20);
-    g.colsum = d.colsum_out;
-    if (gemm_tnb(c, g)) { c->tn_colsum_fused = d.colsum_out != nullptr; SPA_LAUNCH_CHECK(c); return true; }
-    g.colsum = nullptr; ps.on = false;
+    ps.tag(M, N, Ki, gemm_prof_flags(k, d, 0));
+    const int rounds = 0;  // 8-phase kernels: M-split count from the makespan model
+    if (k == GemmKernel::Tnb) gemm_tnb(c, g);
+    else if (k == GemmKernel::Tn8p256) launch_tn8p<4, 2>(c, g, rounds);
+    else if (k == GemmKernel::Tn8p128x384) launch_tn8p<2, 3>(c, g, rounds);
+    else launch_tn8p<6, 1>(c, g, rounds);
+    SPA_LAUNCH_CHECK(c);
+    return;
   }
-  if (c->tn_8p && (M >= 65536 || c->tn_8p == 2) && (g.brow_group == 0 || g.brow_group >= 16)) {
-    // tile shape with the least padding: 384 x 128 / 128 x 384 when one dimension is an odd multiple of 384, else 256 x 256
-    auto waste = [&](int TI, int TNN) { return (double)((Ki + TI - 1) / TI * TI) * ((N + TNN - 1) / TNN * TNN) / ((double)Ki * N); };
-    const double w0 = waste(256, 256), w1 = waste(128, 384), w2 = waste(384, 128);
-    const double wb = std::min(w0, std::min(w1, w2));
-    if (wb <= 1.25 || c->tn_8p == 2) {
-      ProfScope ps(c, PROF_GEMM_TN, 2.0 * (double)M * Ki * N, ((double)M * Ki + (double)M * N) * 2.0);
-      ps.tag(M, N, Ki, 0);
-      const int rounds = 0;  // M-split count from the makespan model
-      g.colsum = d.colsum_out; c->tn_colsum_fused = d.colsum_out != nullptr;
-      if (w0 <= wb * 1.0001) launch_tn8p<4, 2>(c, g, rounds);
-      else if (w1 <= wb * 1.0001) launch_tn8p<2, 3>(c, g, rounds);
-      else launch_tn8p<6, 1>(c, g, rounds);
-      SPA_LAUNCH_CHECK(c);
-      return true;
-    }
-  }
-  if (d.seg_n > 0) return false;  // segmented outputs exist in the 8-phase kernels only: the caller falls back to one GEMM per segment
   const int64_t tiles = (int64_t)g.tiles_i * g.tiles_n;
   // enough workgroups to fill 256 CUs several times over, but >= 4096 reduction rows per split so the
   // f32 atomic traffic (4 B per output element per split) stays a few % of the tile's MFMA time
@@ -1482,9 +1429,8 @@ bool gemm_tn_bf16(spa3d_ctx* c, const GemmDesc& d) {
   static bool attr_set = false;
   if (!attr_set) { (void)hipFuncSetAttribute((const void*)gemm_tn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 65536); attr_set = true; }
   ProfScope ps(c, PROF_GEMM_TN, 2.0 * (double)M * Ki * N, ((double)M * Ki + (double)M * N) * 2.0 + (double)Ki * N * 4.0 * splits);
-  ps.tag(M, N, Ki, splits);
+  ps.tag(M, N, Ki, gemm_prof_flags(k, d, splits));
   gemm_tn_kernel<<<(unsigned)(tiles * ((splits + 7) / 8 * 8)), 256, 65536, c->stream>>>(g);
   SPA_LAUNCH_CHECK(c);
-  return true;
 }
 }  // namespace SPA_NS

@@ -309,8 +309,6 @@ __global__ __launch_bounds__(256, 1) void gemm_ntb_kernel(NtbArgs g) {
 }
 
 // ---- host
-int ntb_wn(int N) { return N % 384 == 0 ? 6 : (N % 256 == 0 ? 4 : 0); }
-bool gemm_ntb_ok(int K, int N) { return ntb_wn(N) != 0 && K % 32 == 0 && K >= 64; }   // K >= 64: the kernel's phase loop is a do-while behind the peeled first phase
 int64_t gemm_ntb_pack_elems(int K, int N) { return (int64_t)K * N; }
 
 template <typename S> void gemm_ntb_pack(spa3d_ctx* c, const S* w, int64_t sk, int64_t sn, int K, int N, bf16_t* wpk) {
@@ -333,20 +331,16 @@ static void launch_ntb(spa3d_ctx* c, NtbArgs g) {
   gemm_ntb_kernel<WM, WN, BIAS><<<256, 256, 4 * NTB_PH, c->stream>>>(g);
 }
 
-// C[M, N] (16-bit) = A[M, K] . W (+ bias) with W as gemm_ntb_pack's stream.  False when the shape / layout is not this kernel's.
-bool gemm_ntb(spa3d_ctx* c, const bf16_t* A, int64_t lda, const bf16_t* wpk, const float* bias, bf16_t* C, int64_t ldc, int64_t M, int N, int K) {
-  if (!wpk || !gemm_ntb_ok(K, N) || M < 1) return false;
-  if (lda % 8 || ldc % 8 || lda > (1 << 20) || ldc > (1 << 20) || (((uintptr_t)A | (uintptr_t)C | (uintptr_t)wpk) & 15) || (bias && ((uintptr_t)bias & 15))) return false;
-  if (((M + 255) / 256) * (int64_t)(N / 256 + 1) > (int64_t(1) << 30)) return false;   // the kernel's tile ids are 32-bit
-  if (c->dry) return true;
+// C[M, N] (16-bit) = A[M, K] . W (+ bias) with W as gemm_ntb_pack's stream (d.ntb_pk), for a descriptor gemm_plan.hpp's ntb_takes accepted
+void gemm_ntb(spa3d_ctx* c, const GemmDesc& d) {
+  const int64_t M = d.M; const int N = d.N, K = d.K; const float* bias = d.bias;
   NtbArgs g{};
-  g.A = A; g.lda = lda; g.wpk = (const char*)wpk; g.C = C; g.ldc = ldc; g.bias = bias; g.M = M; g.N = N; g.K = K;
+  g.A = (const bf16_t*)d.A; g.lda = d.sAm; g.wpk = (const char*)d.ntb_pk; g.C = (bf16_t*)d.C; g.ldc = d.sCm; g.bias = bias; g.M = M; g.N = N; g.K = K;
   ProfScope ps(c, PROF_GEMM_NT, 2.0 * (double)M * N * K, ((double)M * K + (double)K * N + (double)M * N) * 2.0);
-  ps.tag(M, N, K, (1 << 21) | (bias ? 1 : 0));
+  ps.tag(M, N, K, gemm_prof_flags(GemmKernel::Ntb, d, 0));
   if (ntb_wn(N) == 6) { if (bias) launch_ntb<4, 6, true>(c, g); else launch_ntb<4, 6, false>(c, g); }
   else { if (bias) launch_ntb<6, 4, true>(c, g); else launch_ntb<6, 4, false>(c, g); }
   SPA_LAUNCH_CHECK(c);
-  return true;
 }
 
 }  // namespace SPA_NS

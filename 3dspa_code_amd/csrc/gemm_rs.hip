@@ -30,10 +30,8 @@ typedef __attribute__((ext_vector_type(2))) _Float16 rs_h16x2;
 typedef __attribute__((ext_vector_type(2))) __bf16 rs_h16x2;
 #endif
 
-constexpr int RS_K = 384;
 constexpr int RS_SEG = 48 * 1024;   // one phase's weights: 48 fragments of 1 KiB = 64 output columns x 384 k
 constexpr int RS_RING = 3 * RS_SEG;
-constexpr int RS_MAXN = 2304;       // bias rows in LDS: 144 KiB ring + 9 KiB
 constexpr int RS_LDS = RS_RING + RS_MAXN * 4;
 
 // ---- weight stream.  Segment c (output columns 64c .. 64c+63), fragment f = t*24 + s (1 KiB = 64 lanes x 8 elements), lane (r = lane & 31, hh = lane >> 5),
@@ -358,20 +356,17 @@ template <typename S> void gemm_rs_pack(spa3d_ctx* c, const S* w, int64_t sk, in
 template void gemm_rs_pack<float>(spa3d_ctx*, const float*, int64_t, int64_t, int, bf16_t*);
 template void gemm_rs_pack<bf16_t>(spa3d_ctx*, const bf16_t*, int64_t, int64_t, int, bf16_t*);
 
-bool gemm_rs_ok(int K, int N) { return K == RS_K && N >= 256 && N <= RS_MAXN && N % 128 == 0; }
 int64_t gemm_rs_pack_elems(int N) { return (int64_t)(N / 64) * 48 * 512; }
 
-// C[M, N] = A[M, 384] . W (+ bias) with W as the packed stream.  Returns false when the shape / layout is not this kernel's.
-bool gemm_rs(spa3d_ctx* c, const bf16_t* A, int64_t lda, const bf16_t* wpk, const float* bias, bf16_t* C, int64_t ldc, int64_t M, int N, const bf16_t* gelu_pre,
-             int64_t ldpre) {
-  if (!wpk || !gemm_rs_ok(RS_K, N) || M < 1 || lda % 8 || ldc % 8 || (((uintptr_t)A | (uintptr_t)C) & 15)) return false;
-  if (gelu_pre && (ldpre % 8 || ((uintptr_t)gelu_pre & 15))) return false;
-  if (c->dry) return true;
+// C[M, N] = A[M, 384] . W (+ bias) with W as the packed stream (d.rs_pk), for a descriptor gemm_plan.hpp's rs_takes accepted
+void gemm_rs(spa3d_ctx* c, const GemmDesc& d) {
+  const int64_t M = d.M; const int N = d.N;
+  const bf16_t* gelu_pre = d.epi == EPI_MUL_GELU_GRAD ? (const bf16_t*)d.aux : nullptr;   // in C's layout
   RsArgs g{};
-  g.A = A; g.lda = lda; g.C = C; g.ldc = ldc; g.wpk = (const char*)wpk; g.bias = bias; g.M = M; g.N = N; g.nseg = N / 64;
-  g.aux = gelu_pre; g.ldaux = ldpre;
+  g.A = (const bf16_t*)d.A; g.lda = d.sAm; g.C = (bf16_t*)d.C; g.ldc = d.sCm; g.wpk = (const char*)d.rs_pk; g.bias = d.bias; g.M = M; g.N = N; g.nseg = N / 64;
+  g.aux = gelu_pre; g.ldaux = gelu_pre ? d.sCm : 0;
   g.tiles = (int)((M + 255) / 256);
-  g.nt_store = (c->nt_stream && (double)M * N * 2.0 >= 512.0 * 1024 * 1024) ? 1 : 0;
+  g.nt_store = ((double)M * N * 2.0 >= 512.0 * 1024 * 1024) ? 1 : 0;   // non-temporal stores for outputs >= 512 MB
 #ifdef SPA3D_RS_PLAIN_ST
   g.nt_store = 0;
 #endif
@@ -384,12 +379,11 @@ bool gemm_rs(spa3d_ctx* c, const bf16_t* A, int64_t lda, const bf16_t* wpk, cons
     attr = true;
   }
   ProfScope ps(c, PROF_GEMM_NT, 2.0 * (double)M * N * RS_K, ((double)M * (RS_K + N * (gelu_pre ? 2.0 : 1.0)) + (double)RS_K * N) * 2.0);
-  ps.tag(M, N, RS_K, gelu_pre ? 512 + 6 : 512);
+  ps.tag(M, N, RS_K, gemm_prof_flags(GemmKernel::Rs, d, 0));
   const int grid = g.tiles < 256 ? g.tiles : 256;
   if (gelu_pre) gemm_rs_kernel<true><<<grid, 256, RS_LDS, c->stream>>>(g);
   else gemm_rs_kernel<false><<<grid, 256, RS_LDS, c->stream>>>(g);
   SPA_LAUNCH_CHECK(c);
-  return true;
 }
 
 }  // namespace SPA_NS

@@ -288,15 +288,8 @@ static void launch_tnb(spa3d_ctx* c, const TnArgs& g, unsigned blocks) {
   else { if (rm) launch_tnb_k<WB, false, true>(c, g, blocks); else launch_tnb_k<WB, false, false>(c, g, blocks); }
 }
 
-bool gemm_tnb(spa3d_ctx* c, TnArgs g) {
-  const bool wb = g.Ki % 384 == 0 && g.N % 256 == 0, wa = g.Ki % 256 == 0 && g.N % 384 == 0;
-  if (!wb && !wa) return false;
-  if (g.M < 256 || g.lda % 8 || g.ldb % 8) return false;
-  if (g.seg_n > 0 && g.seg_n % 32) return false;
-  if (g.lda > (1 << 24) || g.ldb > (1 << 24)) return false;                        // 32-bit lane offsets
-  if (g.brow_group > 0) {                                                           // the skips a lane accumulates over a split stay in 32 bits
-    if (g.brow_group < 16 || (g.M / g.brow_group + 2) * (int64_t)g.brow_skip * g.ldb * 2 >= (int64_t(1) << 31)) return false;
-  }
+void gemm_tnb(spa3d_ctx* c, TnArgs g) {
+  const bool wb = g.Ki % 384 == 0 && g.N % 256 == 0;   // else Ki % 256 == 0 and N % 384 == 0 (tnb_takes)
   const int64_t Mmain = g.M / 32 * 32;
   const int TI = wb ? 384 : 256, TNN = wb ? 256 : 384;
   TnArgs gm = g; gm.M = Mmain;
@@ -321,6 +314,5 @@ bool gemm_tnb(spa3d_ctx* c, TnArgs g) {
     const int64_t el = (int64_t)g.Ki * g.N;
     gemm_tn_tail_kernel<<<(unsigned)((el + 255) / 256), 256, 0, c->stream>>>(g, Mmain, (int)(g.M - Mmain));
   }
-  return true;
 }
 }  // namespace SPA_NS

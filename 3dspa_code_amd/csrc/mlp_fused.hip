@@ -398,29 +398,23 @@ template void mlp_fused_pack<bf16_t>(spa3d_ctx*, const bf16_t*, const bf16_t*, b
 
 int64_t mlp_fused_pack_elems() { return (int64_t)MF_NSEG * 48 * 512; }
 
-// y[M,384] = a + MLP(na);  h, hpre [M,1536] for the backward.  Returns false when the shape is not the fused kernel's.
-bool mlp_fused_fwd(spa3d_ctx* c, const bf16_t* na, const bf16_t* a, bf16_t* y, bf16_t* h, bf16_t* hpre, int64_t M, int d, int mlp,
-                   const bf16_t* wpk, const float* b_in, const float* b_out) {
-  if (d != MF_D || mlp != MF_H || M < 1 || !wpk || !b_in || !b_out) return false;
-  if (c->dry) return true;
-  // 16-byte vector loads / stores and LDS-DMA on every operand: a misaligned pointer from a C-ABI caller is refused, not faulted on (gemm_rs / gemm_nt_bf16 do the same)
-  for (const void* p : {(const void*)na, (const void*)a, (const void*)y, (const void*)h, (const void*)hpre, (const void*)wpk})
-    if (((uintptr_t)p) & 15) return false;
+// y[M,384] = a + MLP(na);  h, hpre [M,1536] for the backward, for operands gemm_plan.hpp's plan_mlp accepted
+void mlp_fused_fwd(spa3d_ctx* c, const bf16_t* na, const bf16_t* a, bf16_t* y, bf16_t* h, bf16_t* hpre, int64_t M, const bf16_t* wpk,
+                   const float* b_in, const float* b_out) {
   MlpFusedArgs g{};
   g.na = na; g.a = a; g.y = y; g.h = h; g.hpre = hpre; g.wpk = (const char*)wpk; g.b_in = b_in; g.b_out = b_out; g.M = M;
   g.tiles = (int)((M + 127) / 128);
   g.dbg = nullptr;
   if (MF_ABL & 32) { const char* e = getenv("SPA3D_MF_DBG"); if (e) g.dbg = (unsigned long long*)strtoull(e, nullptr, 0); }
-  g.nt_store = (c->nt_stream && (double)M * MF_H * 2.0 >= 512.0 * 1024 * 1024) ? 1 : 0;
+  g.nt_store = ((double)M * MF_H * 2.0 >= 512.0 * 1024 * 1024) ? 1 : 0;   // non-temporal stores for h / hpre >= 512 MB
   if (MF_ABL & 64) g.nt_store = 0;
   static bool attr = false;
   if (!attr) { (void)hipFuncSetAttribute((const void*)mlp_fused_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MF_LDS); attr = true; }
   ProfScope ps(c, PROF_GEMM_NT, 2.0 * 2.0 * (double)M * MF_D * MF_H, ((double)M * (3.0 * MF_D + 2.0 * MF_H) + 2.0 * MF_D * MF_H) * 2.0);
-  ps.tag(M, MF_D, MF_H, 256);
+  ps.tag(M, MF_D, MF_H, gemm_prof_flags(GemmKernel::MlpFused, GemmDesc{}, 0));
   const int grid = g.tiles < 256 ? g.tiles : 256;
   mlp_fused_fwd_kernel<<<grid, 256, MF_LDS, c->stream>>>(g);
   SPA_LAUNCH_CHECK(c);
-  return true;
 }
 
 }  // namespace SPA_NS

@@ -110,18 +110,17 @@ template <typename T> struct Net {
     for (int s = 0; s < l.nseg; ++s)
       k_pack<T>(c, l.src[s], segw, K, segw, l.wn + (int64_t)s * segw, l.N, l.wt + (int64_t)s * segw * K, K);
     if constexpr (sizeof(T) == 2) {
-      if (c->rs_gemm && c->gemm_impl != 1 && gemm_rs_ok(K, l.N) && segw % 64 == 0) {
+      const LinStreams ps = plan_lin_streams(c->gemm, K, l.N, segw, l.nseg, G != nullptr);
+      if (ps.rs) {
         l.wpk = alloc<T>(gemm_rs_pack_elems(l.N));
         for (int s = 0; s < l.nseg; ++s) gemm_rs_pack<float>(c, l.src[s], segw, 1, segw, l.wpk + gemm_rs_pack_elems(segw) * s);
       }
-      if (c->rs_gemm && c->gemm_impl != 1 && G && l.nseg == 1 && gemm_rs_ok(l.N, K)) {  // training only: element (k' = n, n' = k) of W^T is src[k * N + n]
+      if (ps.rs_t) {  // element (k' = n, n' = k) of W^T is src[k * N + n]
         l.wpk_t = alloc<T>(gemm_rs_pack_elems(K));
         gemm_rs_pack<float>(c, l.src[0], 1, l.N, K, l.wpk_t);
       }
-      if (c->nt_big && c->gemm_impl != 1) {  // large-register-tile NT kernel: the shapes it was measured ahead on (profiles/r05_gemm_ntb_*.log) -- contraction >= 768
-        if (K >= 768 && gemm_ntb_ok(K, l.N)) { l.wnb = alloc<T>(gemm_ntb_pack_elems(K, l.N)); gemm_ntb_pack<T>(c, l.wn, l.ldn, 1, K, l.N, l.wnb); }
-        if (G && l.N >= 768 && gemm_ntb_ok(l.N, K)) { l.wnb_t = alloc<T>(gemm_ntb_pack_elems(l.N, K)); gemm_ntb_pack<T>(c, l.wn, 1, l.ldn, l.N, K, l.wnb_t); }
-      }
+      if (ps.ntb) { l.wnb = alloc<T>(gemm_ntb_pack_elems(K, l.N)); gemm_ntb_pack<T>(c, l.wn, l.ldn, 1, K, l.N, l.wnb); }
+      if (ps.ntb_t) { l.wnb_t = alloc<T>(gemm_ntb_pack_elems(l.N, K)); gemm_ntb_pack<T>(c, l.wn, 1, l.ldn, l.N, K, l.wnb_t); }
     }
     return l;
   }
@@ -156,11 +155,11 @@ template <typename T> struct Net {
       w.mlp_in = make_lin({b + "/MLP_in/kernel"}, b + "/MLP_in/bias", d, mlp);
       w.mlp_out = make_lin({b + "/MLP_out/kernel"}, b + "/MLP_out/bias", mlp, d);
       if constexpr (sizeof(T) == 2) {
-        if (c->mlp_fused && !w.cross && d == 384 && mlp == 1536) {
+        if (plan_mlp_pack(c->gemm, w.cross, d, mlp)) {
           w.mlp_pk = alloc<T>(mlp_fused_pack_elems());
           mlp_fused_pack<float>(c, w.mlp_in.src[0], w.mlp_out.src[0], w.mlp_pk);
         }
-        if (c->qkv_attn && c->gemm_impl != 1 && c->attn_impl != 1 && !w.cross && d == 384 && Dh == 96) {
+        if (c->qkv_attn && !c->gemm.generic && c->attn_impl != 1 && !w.cross && d == 384 && Dh == 96) {
           w.qkv_pk = alloc<T>(qkv_attn_pack_elems(H));
           qkv_attn_pack<float>(c, w.qkv.src[0], w.qkv.src[1], w.qkv.src[2], E, H, w.qkv_pk);
         }
@@ -181,7 +180,7 @@ template <typename T> struct Net {
     if (g.dino_feature_dim > 0) dino = make_lin({"dino_projection/kernel"}, "dino_projection/bias", g.dino_feature_dim, d);
     if (g.depth_feature_dim > 0) depth = make_lin({"depth_projection/kernel"}, "depth_projection/bias", g.depth_feature_dim, d);
     if constexpr (sizeof(T) == 2) {
-      if (c->embed_fused && !twoD && d == 384 && tok.K % 64 == 0 && (g.dino_feature_dim == 0 || g.dino_feature_dim % 64 == 0) && g.depth_feature_dim <= 1) {
+      if (plan_embed_pack(c->gemm, twoD, d, tok.K, g.dino_feature_dim, g.depth_feature_dim)) {
         emb_K = tok.K + (g.dino_feature_dim > 0 ? dino.K : 0);
         emb_wt = alloc<T>((int64_t)d * emb_K); emb_bias = alloc<float>(d);
         k_pack<T>(c, tok.src[0], d, tok.K, d, nullptr, 0, emb_wt, emb_K);
@@ -199,43 +198,26 @@ template <typename T> struct Net {
     pred = make_lin({"track_predictor/kernel"}, "track_predictor/bias", dd, 4 * g.num_output_frames);
   }
 
-  // ------------------------------------------------------------------ GEMM front ends
-  void gemm(const GemmDesc& d) {
-    if constexpr (sizeof(T) == 2) {
-      if (c->gemm_impl != 1) {
-        if (gemm_nt_bf16(c, d)) return;
-        if (gemm_tn_bf16(c, d)) return;
-      }
-    }
-    gemm_generic<T>(c, d);
-  }
+  // ------------------------------------------------------------------ GEMM front ends: plan (gemm_plan.hpp), then launch (nothing when dry)
+  GemmKernel plan(const GemmDesc& d) const { return sizeof(T) == 2 ? plan_gemm(d, c->gemm) : GemmKernel::Generic; }
+  void gemm(const GemmDesc& d) { gemm_launch<T>(c, d, plan(d)); }
   // Y[M,N] = epi(X[M,K] W + b) (+ residual)
   void lin_fwd(const Lin<T>& l, const T* X, void* Y, int64_t M, int epi = EPI_NONE, const T* residual = nullptr, int out_f32 = 0,
                int accumulate = 0, int64_t ldx = 0, int64_t ldy = 0, int crow_group = 0, int crow_skip = 0, T* pre_out = nullptr) {
-    if constexpr (sizeof(T) == 2) {
-      if (l.wpk && epi == EPI_NONE && !residual && !out_f32 && !accumulate && !crow_group && !pre_out && M >= 512 &&
-          gemm_rs(c, X, ldx ? ldx : l.K, l.wpk, l.bias, (T*)Y, ldy ? ldy : l.N, M, l.N)) return;
-      if (l.wnb && epi == EPI_NONE && !residual && !out_f32 && !accumulate && !crow_group && !pre_out && (M >= 65536 || c->nt_big == 2) &&
-          gemm_ntb(c, X, ldx ? ldx : l.K, l.wnb, l.bias, (T*)Y, ldy ? ldy : l.N, M, l.N, l.K)) return;
-    }
     GemmDesc d{};
     d.A = X; d.B = l.wn; d.C = Y; d.M = M; d.N = l.N; d.K = l.K;
     d.sAm = ldx ? ldx : l.K; d.sAk = 1; d.sBk = l.ldn; d.sBn = 1; d.sCm = ldy ? ldy : l.N;
-    d.Bt = l.wt; d.ldBt = l.K;
+    d.Bt = l.wt; d.ldBt = l.K; d.rs_pk = l.wpk; d.ntb_pk = l.wnb;
     d.crow_group = crow_group; d.crow_skip = crow_skip; d.pre_out = pre_out;
     d.bias = l.bias; d.epi = epi; d.aux = residual; d.out_f32 = out_f32; d.accumulate = accumulate;
     gemm(d);
   }
   // dX[M,K] (op)= dY[M,N] W^T, optionally * gelu'(pre)
   void lin_bwd_x(const Lin<T>& l, const T* dY, T* dX, int64_t M, const T* gelu_pre = nullptr, int accumulate = 0, int64_t lddx = 0) {
-    if constexpr (sizeof(T) == 2) {
-      if (l.wpk_t && !accumulate && M >= 512 && gemm_rs(c, dY, l.N, l.wpk_t, nullptr, dX, lddx ? lddx : l.K, M, l.K, gelu_pre, l.K)) return;
-      if (l.wnb_t && !accumulate && !gelu_pre && (M >= 65536 || c->nt_big == 2) && gemm_ntb(c, dY, l.N, l.wnb_t, nullptr, dX, lddx ? lddx : l.K, M, l.K, l.N)) return;
-    }
     GemmDesc d{};
     d.A = dY; d.B = l.wn; d.C = dX; d.M = M; d.N = l.K; d.K = l.N;
     d.sAm = l.N; d.sAk = 1; d.sBk = 1; d.sBn = l.ldn; d.sCm = lddx ? lddx : l.K;
-    d.Bt = l.wn; d.ldBt = l.ldn;
+    d.Bt = l.wn; d.ldBt = l.ldn; d.rs_pk = l.wpk_t; d.ntb_pk = l.wnb_t;
     if (gelu_pre) { d.epi = EPI_MUL_GELU_GRAD; d.aux = gelu_pre; }
     d.accumulate = accumulate;
     gemm(d);
@@ -245,13 +227,14 @@ template <typename T> struct Net {
     if constexpr (sizeof(T) == 2) {
       // fused projections (q | k | v): ONE dW GEMM over all segments -- X is read once instead of once per segment, a third of the launches --
       // with the output tiles routed to the segments' separate leaves (8-phase TN kernels; else the per-segment loop below)
-      if (l.nseg > 1 && !l.gb && c->gemm_impl != 1 && l.gw[0]) {
+      if (l.nseg > 1 && !l.gb && l.gw[0]) {
         GemmDesc d{};
         d.A = X; d.B = dY; d.C = l.gw[0]; d.M = l.K; d.N = l.N; d.K = M;
         d.sAm = 1; d.sAk = ldx ? ldx : l.K; d.sBk = l.N; d.sBn = 1; d.sCm = l.segw;
         d.out_f32 = 1; d.accumulate = 1; d.zero_page = zero_page; d.brow_group = brow_group; d.brow_skip = brow_skip;
         d.seg_n = l.segw; d.C_seg[0] = l.gw[1]; d.C_seg[1] = l.nseg > 2 ? l.gw[2] : nullptr;
-        if (gemm_tn_bf16(c, d)) return;
+        const GemmKernel k = plan_tn(d, c->gemm);
+        if (k != GemmKernel::Refuse) { gemm_launch<T>(c, d, k); return; }
       }
     }
     for (int s = 0; s < l.nseg; ++s) {
@@ -259,10 +242,10 @@ template <typename T> struct Net {
       d.A = X; d.B = dY + (int64_t)s * l.segw; d.C = l.gw[s]; d.M = l.K; d.N = l.segw; d.K = M;
       d.sAm = 1; d.sAk = ldx ? ldx : l.K; d.sBk = l.N; d.sBn = 1; d.sCm = l.segw;
       d.out_f32 = 1; d.accumulate = 1; d.zero_page = zero_page; d.brow_group = brow_group; d.brow_skip = brow_skip;
-      d.colsum_out = l.gb ? l.gb + (int64_t)s * l.segw : nullptr;  // bias gradient rides along in the 8-phase dW kernel
-      c->tn_colsum_fused = false;
-      gemm(d);
-      if (l.gb && !c->tn_colsum_fused) k_colsum<T>(c, dY + (int64_t)s * l.segw, M, l.segw, l.N, l.gb + (int64_t)s * l.segw, brow_group, brow_skip);
+      d.colsum_out = l.gb ? l.gb + (int64_t)s * l.segw : nullptr;  // bias gradient rides along in the 8-phase and large-tile dW kernels
+      const GemmKernel k = plan(d);
+      gemm_launch<T>(c, d, k);
+      if (l.gb && !gemm_tn_fuses_colsum(k, d)) k_colsum<T>(c, dY + (int64_t)s * l.segw, M, l.segw, l.N, l.gb + (int64_t)s * l.segw, brow_group, brow_skip);
     }
   }
 
@@ -324,7 +307,8 @@ template <typename T> struct Net {
     T* hpre = alloc<T>(Mg * w.mlp); T* h = alloc<T>(Mg * w.mlp);
     bool fused = false;
     if constexpr (sizeof(T) == 2) {  // :103-108 as one sequence-resident kernel (track encoder widths): h is never read back from HBM
-      if (w.mlp_pk && c->gemm_impl != 1) fused = mlp_fused_fwd(c, na, a, y, h, hpre, Mg, d, w.mlp, w.mlp_pk, w.mlp_in.bias, w.mlp_out.bias);
+      fused = plan_mlp(c->gemm, Mg, d, w.mlp, w.mlp_pk, w.mlp_in.bias, w.mlp_out.bias, na, a, y, h, hpre) == GemmKernel::MlpFused;
+      if (fused && !c->dry) mlp_fused_fwd(c, na, a, y, h, hpre, Mg, w.mlp_pk, w.mlp_in.bias, w.mlp_out.bias);
     }
     if (!fused) {
       lin_fwd(w.mlp_in, na, h, Mg, EPI_GELU, nullptr, 0, 0, 0, 0, 0, 0, hpre);           // :106  h = gelu(hpre), both kept for the backward
@@ -527,7 +511,7 @@ template <typename T> struct Net {
       // K1: the three Denses are ONE Dense on the concatenated row (repair R4) -- one GEMM over K = 256 sin features + 768 DINO columns
       // (two A sources, no concatenated copy), depth as a rank-1 term and the summed biases in the f32 epilogue, every kept token row written
       // ONCE, straight into the compact (pruned) order; dropped frame tokens are neither computed nor gathered, readout rows come from k_embed_maps
-      if (emb_wt && c->gemm_impl != 1 && (g.dino_feature_dim > 0) == (k.dino != nullptr) && (g.depth_feature_dim > 0) == (k.depthf != nullptr) &&
+      if (emb_wt && (g.dino_feature_dim > 0) == (k.dino != nullptr) && (g.depth_feature_dim > 0) == (k.depthf != nullptr) &&
           nseq * (int64_t)T_ < 0x7fffffffLL && rows < 0x7fffffffLL) {
         const int64_t mk_emb = c->ar.mark();
         T* out = alloc<T>(rows_g * d);
@@ -538,7 +522,8 @@ template <typename T> struct Net {
         e.M = rows; e.N = d; e.K = emb_K; e.bias = emb_bias; e.arow_idx = arow; e.crow_idx = crow;
         if (k.dino) { e.A2 = k.dino; e.sA2m = g.dino_feature_dim; e.K1 = tok.K; }
         if (k.depthf) { e.r1_x = k.depthf; e.r1_w = depth.src[0]; }
-        emb_done = gemm_nt_bf16(c, e);
+        emb_done = plan_nt(e, c->gemm) == GemmKernel::NtEmbed;
+        if (emb_done) gemm_launch<T>(c, e, GemmKernel::NtEmbed);
         if (emb_done) k.tok0 = out;   // (the maps stay allocated for the chunk: the launch is asynchronous)
         else c->ar.release(mk_emb);   // refused: the multi-pass path below allocates its own buffers; k_embed_maps wrote only into what is released here
       }
@@ -1081,6 +1066,9 @@ static int64_t dry_need(spa3d_ctx* c, const RunArgs& a, int Bc) {
   return need;
 }
 
+// "gemm_impl" of a handle: 7 and 10 are spa3d_op_linear's one-kernel hooks; on a handle they mean 2, the product dispatch
+static void set_gemm_impl(spa3d_ctx* c, int v) { c->gemm = GemmPolicy::from_impl(v == 7 || v == 10 ? 2 : v); }
+
 static int check_batch(spa3d_ctx* c, const spa3d_batch* b, int mode) {
   if (!b || b->B <= 0 || b->Q <= 0) { c->err = "batch: B,Q must be positive"; return SPA3D_ERR_ARG; }
   if (mode != MODE_DECODE && (b->N <= 0 || b->T <= 0 || !b->support_tracks || !b->support_tracks_visible || !b->boundary_frame)) {
@@ -1144,7 +1132,7 @@ int spa3d_create(const spa3d_config* cfg, spa3d_handle* out) {
   // at the end (exact for powers of two)
   if (cfg->precision == SPA3D_F16) c->loss_scale = -16.f;
   // the nine switches (include/spa3d.h, spa3d_set_option) may be preset from the environment; nothing else is read from it
-  const char* e = getenv("SPA3D_GEMM_IMPL"); if (e) apply_gemm_impl(c, atoi(e));
+  const char* e = getenv("SPA3D_GEMM_IMPL"); if (e) set_gemm_impl(c, atoi(e));
   e = getenv("SPA3D_ATTN_IMPL"); if (e) apply_attn_impl(c, atoi(e));
   e = getenv("SPA3D_LOSS_SCALE"); if (e && cfg->precision == SPA3D_F16) c->loss_scale = (float)atof(e);
   e = getenv("SPA3D_PRUNE"); if (e) c->prune = atoi(e);
@@ -1232,7 +1220,7 @@ int spa3d_set_option(spa3d_handle h, const char* name, double value) {
   else if (n == "ro_share") h->ro_share = value != 0;
   else if (n == "loss_scale") { if (h->cfg.precision != SPA3D_F16) { h->err = "loss_scale applies to SPA3D_F16 handles only"; return SPA3D_ERR_ARG; } h->loss_scale = (float)value; }
   else if (n == "attn_impl") apply_attn_impl(h, (int)value);
-  else if (n == "gemm_impl") apply_gemm_impl(h, (int)value);
+  else if (n == "gemm_impl") set_gemm_impl(h, (int)value);
   else if (n == "chunk") {
     if (value > 1 && (h->query_chunk > 0 || h->track_chunk > 0)) { h->err = "\"chunk\" > 1 cannot be combined with \"query_chunk\" / \"track_chunk\""; return SPA3D_ERR_ARG; }
     h->chunk = value > 0 ? (int)value : 0;

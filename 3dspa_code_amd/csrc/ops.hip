@@ -20,21 +20,20 @@ int op_linear(OpCtx& c, const T* A, const T* B, const float* bias, const T* res,
   GemmDesc d{};
   d.A = A; d.B = B; d.C = C; d.M = M; d.N = N; d.K = K; d.sAm = K; d.sAk = 1; d.sBk = N; d.sBn = 1; d.sCm = N;
   d.bias = bias; d.epi = act == 1 ? EPI_GELU : (act == 2 ? EPI_MUL_GELU_GRAD : EPI_NONE); d.aux = res;  // act 2: C = (A.B + bias) o gelu'(residual)
-  apply_gemm_impl(&c, impl & 15);
+  const GemmPolicy p = GemmPolicy::from_impl(impl & 15);
   if constexpr (sizeof(T) == 2) {
-    if ((impl & 15) == 7) {  // the row-stationary K = 384 kernel (gemm_rs.hip) or an error
-      if (act == 1 || (act == 0 && res) || (act == 2 && !res) || !gemm_rs_ok(K, N)) return SPA3D_ERR_ARG;
-      T* pk = c.alloc<T>(gemm_rs_pack_elems(N));
+    if (p.only != GemmKernel::Refuse) {  // 7 / 10: the row-stationary K = 384 kernel (gemm_rs.hip) / the large-register-tile NT kernel (gemm_ntb.hip) or an error
+      const bool rs = p.only == GemmKernel::Rs;
+      const void*& pk = rs ? d.rs_pk : d.ntb_pk;
+      pk = A;   // stand-in for the packed stream (A must be 16-byte aligned too): a wrong shape is an argument error whatever the workspace
+      if (plan_nt(d, p) != p.only) return SPA3D_ERR_ARG;
+      T* w = c.alloc<T>(rs ? gemm_rs_pack_elems(N) : gemm_ntb_pack_elems(K, N));
       if (c.ar.overflow) return SPA3D_ERR_WORKSPACE;
-      gemm_rs_pack<T>(&c, B, N, 1, N, pk);
-      return gemm_rs(&c, A, K, pk, bias, C, N, M, N, act == 2 ? res : nullptr, N) ? c.status() : SPA3D_ERR_ARG;
-    }
-    if ((impl & 15) == 10) {  // the large-register-tile NT kernel (gemm_ntb.hip) or an error
-      if (act != 0 || res || !gemm_ntb_ok(K, N)) return SPA3D_ERR_ARG;
-      T* pk = c.alloc<T>(gemm_ntb_pack_elems(K, N));
-      if (c.ar.overflow) return SPA3D_ERR_WORKSPACE;
-      gemm_ntb_pack<T>(&c, B, N, 1, K, N, pk);
-      return gemm_ntb(&c, A, K, pk, bias, C, N, M, N, K) ? c.status() : SPA3D_ERR_ARG;
+      if (rs) gemm_rs_pack<T>(&c, B, N, 1, N, w); else gemm_ntb_pack<T>(&c, B, N, 1, K, N, w);
+      pk = w;
+      if (plan_nt(d, p) != p.only) return SPA3D_ERR_ARG;   // (a misaligned workspace)
+      gemm_launch<T>(&c, d, p.only);
+      return c.status();
     }
     if (impl != 1) {
       // impl | 16 (benchmarks): the MLP-in form of the step -- a second output stream (the pre-activation) from the same epilogue
@@ -43,33 +42,37 @@ int op_linear(OpCtx& c, const T* A, const T* B, const float* bias, const T* res,
       if (c.ar.overflow) return SPA3D_ERR_WORKSPACE;
       k_transpose<T>(&c, B, K, N, Bt);
       d.Bt = Bt; d.ldBt = K;
-      if (gemm_nt_bf16(&c, d)) return c.status();
-      if ((impl & 15) >= 2) return SPA3D_ERR_ARG;
+      const GemmKernel k = plan_nt(d, GemmPolicy::from_impl((impl & 15) == 1 ? 0 : impl & 15));   // (17, 33 ...: the product dispatch, as always)
+      if (k != GemmKernel::Refuse) { gemm_launch<T>(&c, d, k); return c.status(); }
     }
-  } else if ((impl & 15) >= 2) return SPA3D_ERR_ARG;
-  gemm_generic<T>(&c, d);
+  }
+  if ((impl & 15) >= 2) return SPA3D_ERR_ARG;   // tiled (or one kernel) or an error
+  gemm_launch<T>(&c, d, GemmKernel::Generic);
   return c.status();
 }
 
 template <typename T>
 int op_linear_bwd(OpCtx& c, const T* A, const T* B, const T* dC, T* dA, float* dB, float* dbias, int64_t M, int N, int K, int impl) {
-  apply_gemm_impl(&c, impl);
+  // 10: dA on the large-register-tile NT kernel or an error; 7 names no dA kernel here and is a tiled request like 2
+  const GemmPolicy p = GemmPolicy::from_impl(impl == 7 ? 2 : impl);
   if (dA) {  // dA[M,K] = dC[M,N] . B[K,N]^T
     GemmDesc d{};
     d.A = dC; d.B = B; d.C = dA; d.M = M; d.N = K; d.K = N; d.sAm = N; d.sAk = 1; d.sBk = 1; d.sBn = N; d.sCm = K;
     d.Bt = B; d.ldBt = N;
-    bool done = false;
+    GemmKernel k = GemmKernel::Refuse;
     if constexpr (sizeof(T) == 2) {
-      if (impl == 10) {  // dA on the large-register-tile NT kernel (gemm_ntb.hip) or an error: element (k' = n, n' = k) of B^T is B[k * N + n]
-        if (!gemm_ntb_ok(N, K)) return SPA3D_ERR_ARG;
+      if (p.only == GemmKernel::Ntb) {  // element (k' = n, n' = k) of B^T is B[k * N + n]
+        d.ntb_pk = dC;   // stand-in for the packed stream, as in op_linear
+        if (plan_nt(d, p) != GemmKernel::Ntb) return SPA3D_ERR_ARG;
         T* pk = c.alloc<T>(gemm_ntb_pack_elems(N, K));
         if (c.ar.overflow) return SPA3D_ERR_WORKSPACE;
         gemm_ntb_pack<T>(&c, B, 1, N, N, K, pk);
-        if (!gemm_ntb(&c, dC, N, pk, nullptr, dA, K, M, K, N)) return SPA3D_ERR_ARG;
-        done = true;
-      } else if (impl != 1) done = gemm_nt_bf16(&c, d);
+        d.ntb_pk = pk;
+      }
+      k = plan_nt(d, p);
     }
-    if (!done) { if (impl >= 2) return SPA3D_ERR_ARG; gemm_generic<T>(&c, d); }
+    if (k == GemmKernel::Refuse) { if (impl >= 2) return SPA3D_ERR_ARG; k = GemmKernel::Generic; }
+    gemm_launch<T>(&c, d, k);
   }
   if (dB) {  // dB[K,N] = A[M,K]^T . dC[M,N]
     k_zero(&c, dB, (int64_t)K * N * 4);
@@ -77,9 +80,10 @@ int op_linear_bwd(OpCtx& c, const T* A, const T* B, const T* dC, T* dA, float* d
     d.A = A; d.B = dC; d.C = dB; d.M = K; d.N = N; d.K = M; d.sAm = 1; d.sAk = K; d.sBk = N; d.sBn = 1; d.sCm = N;
     d.out_f32 = 1; d.accumulate = 1;
     void* zp = c.alloc<char>(256); k_zero(&c, zp, 256); d.zero_page = zp;
-    bool done = false;
-    if constexpr (sizeof(T) == 2) { if (impl != 1) done = gemm_tn_bf16(&c, d); }
-    if (!done) { if (impl >= 2) return SPA3D_ERR_ARG; gemm_generic<T>(&c, d); }
+    GemmKernel k = GemmKernel::Refuse;
+    if constexpr (sizeof(T) == 2) k = plan_tn(d, p);
+    if (k == GemmKernel::Refuse) { if (impl >= 2) return SPA3D_ERR_ARG; k = GemmKernel::Generic; }
+    gemm_launch<T>(&c, d, k);
   }
   if (dbias) { k_zero(&c, dbias, (int64_t)N * 4); k_colsum<T>(&c, dC, M, N, N, dbias); }
   return c.status();
@@ -177,7 +181,8 @@ int spa3d_op_mlp_fused(const void* na, const void* a, const void* w_in, const fl
   bf16_t* wpk = c.alloc<bf16_t>(mlp_fused_pack_elems());
   if (c.ar.overflow) return SPA3D_ERR_WORKSPACE;
   mlp_fused_pack<bf16_t>(&c, (const bf16_t*)w_in, (const bf16_t*)w_out, wpk);
-  if (!mlp_fused_fwd(&c, (const bf16_t*)na, (const bf16_t*)a, (bf16_t*)y, (bf16_t*)h, (bf16_t*)hpre, M, d, mlp, wpk, b_in, b_out)) return SPA3D_ERR_ARG;
+  if (plan_mlp(GemmPolicy(), M, d, mlp, wpk, b_in, b_out, na, a, y, h, hpre) != GemmKernel::MlpFused) return SPA3D_ERR_ARG;
+  mlp_fused_fwd(&c, (const bf16_t*)na, (const bf16_t*)a, (bf16_t*)y, (bf16_t*)h, (bf16_t*)hpre, M, wpk, b_in, b_out);
   return c.status();
 }
 

@@ -17,8 +17,8 @@ struct TnArgs {
   const DetCfg* det;   // the call's deterministic-gradient mode (common.hpp)
 };
 
-// large-register-tile kernel (gemm_tnb.hip): true when the shape is covered (Ki % 384 == 0 and N % 256 == 0, or Ki % 256 == 0 and N % 384 == 0;
-// M >= 256) and the launches were issued.  Handles M % 32 rows with a small tail launch.
-bool gemm_tnb(spa3d_ctx* c, TnArgs g);
+// large-register-tile kernel (gemm_tnb.hip) for a shape gemm_plan.hpp's tnb_takes accepted (Ki % 384 == 0 and N % 256 == 0, or Ki % 256 == 0 and
+// N % 384 == 0; M >= 256).  Handles M % 32 rows with a small tail launch.
+void gemm_tnb(spa3d_ctx* c, TnArgs g);
 
 }  // namespace SPA_NS

@@ -171,7 +171,8 @@ int spa3d_adamw_step(float* params, const float* grads, float* m, float* v, int6
  *                     single-buffer short-K kernel, 6 tiled GEMMs without the round-4 / round-5 kernels (MLP forward as two GEMMs, multi-pass input embedding, no row-stationary K = 384 kernel,
  *                     no large-register-tile kernels), 8 the product dispatch without the round-5 large-register-tile kernels (dW: csrc/gemm_tnb.hip; NT: csrc/gemm_ntb.hip), 9 = 3 with every
  *                     eligible dW / NT GEMM on those kernels whatever its row count.  (The `impl` argument of spa3d_op_linear* takes
- *                     the same values; spa3d_op_linear: | 16 = also write the pre-activation, the MLP-in form of the step.)
+ *                     the same values; spa3d_op_linear: | 16 = also write the pre-activation, the MLP-in form of the step.)  Decoded by
+ *                     GemmPolicy::from_impl, and every kernel choice is made by the planner in csrc/gemm_plan.hpp.
  *   "attn_impl"       0 product dispatch | 1 generic composition | 2 fused kernels | 3, 4 fused with the split-pass backward on 4 / 8 waves (tests) |
  *                     6 fused kernels with the track encoder's QKV projection + attention forward as one launch (built in round 5, slower than the pair: opt-in)
  *   "det_grads"  0/1  order-independent parameter gradients: every reduction into the gradient buffer (split-M dW tiles, bias / scale column sums, broadcast

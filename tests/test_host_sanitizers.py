@@ -19,7 +19,7 @@ def _build():
   os.makedirs(out, exist_ok=True)
   san = ['-fsanitize=address,undefined', '-fno-gpu-sanitize', '-fno-sanitize-recover=undefined', '-fno-omit-frame-pointer', '-g']
   flags = [f for f in b.FLAGS if f != '-O3'] + ['-O1'] + san
-  hdrs = [os.path.join(b.CSRC, 'common.hpp'), os.path.join(ROOT, 'include', 'spa3d.h')]
+  hdrs = [os.path.join(b.CSRC, 'common.hpp'), os.path.join(b.CSRC, 'gemm_plan.hpp'), os.path.join(ROOT, 'include', 'spa3d.h')]
   jobs = []
   for src in ('model.hip', 'ops.hip'):
     for suffix, extra in (('', []), ('_f16', ['-DSPA_F16=1'])):
