@@ -60,6 +60,7 @@ _SIGS = {
                                    C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     'spa3d_set_option': (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
     'spa3d_set_loss_scale_state': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'spa3d_set_counts': (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     'spa3d_grad_segments': (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     'spa3d_set_grad_events': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     'spa3d_grad_events_recorded': (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),

@@ -15,7 +15,10 @@ bool attn_fused_fwd_bf16(spa3d_ctx* c, const bf16_t* q, const bf16_t* k, const b
 bool attn_fused_bwd_bf16(spa3d_ctx* c, const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ldq, int64_t ldk, int64_t ldv,
                          const float* sq, const float* sk, const float* km, int64_t nseq, int Sq, int Sk, int H, int Dh, const bf16_t* o,
                          const float* lse, const bf16_t* d_o, bf16_t* dq, bf16_t* dk, bf16_t* dv, float* dsq, float* dsk,
-                         const int32_t* seq_off, int64_t total_rows);
+                         const int32_t* seq_off, int64_t total_rows, const int32_t* koff = nullptr, int64_t total_keys = 0);
+bool xattn_varlen_fwd_bf16(spa3d_ctx* c, const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq,
+                           const float* sk, int64_t nseq, int Sq, int Skmax, int H, int Dh, bf16_t* o, float* lse, const int32_t* koff,
+                           int64_t total_keys);
 
 template <typename T> static T* aalloc(spa3d_ctx* c, int64_t n) { return (T*)c->ar.alloc(n * (int64_t)sizeof(T)); }
 
@@ -125,13 +128,55 @@ void attention_bwd(spa3d_ctx* c, const T* q, const T* k, const T* v, int64_t ldq
   c->ar.release(mk);
 }
 
+// Cross attention of nseq sequences of Sq queries against RAGGED key sets (tracks_to_latents on a batch with per-sample support counts): the
+// keys of sequence i are rows [koff[i], koff[i + 1]) of the packed k / v.  koff_host and koff_dev hold the same nseq + 1 offsets.  16-bit modes:
+// one launch of the chunked-key kernels with per-sequence offsets (attention_fused.hip); the generic composition (fp32 parity mode, attn_impl 1,
+// shapes outside the fused kernel) runs the sequences one by one.
+template <typename T>
+void attention_varlen_fwd(spa3d_ctx* c, const T* q, const T* k, const T* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq, const float* sk,
+                          int64_t nseq, int Sq, const int32_t* koff_host, const int32_t* koff_dev, int H, int Dh, T* o, float* lse, int impl) {
+  const int E = H * Dh;
+  int Skmax = 0;
+  for (int64_t i = 0; i < nseq; ++i) Skmax = std::max(Skmax, koff_host[i + 1] - koff_host[i]);
+  if constexpr (sizeof(T) == 2) {
+    if (impl != 1 && xattn_varlen_fwd_bf16(c, q, k, v, ldq, ldk, ldv, sq, sk, nseq, Sq, Skmax, H, Dh, o, lse, koff_dev, koff_host[nseq])) return;
+  }
+  for (int64_t i = 0; i < nseq; ++i)
+    attention_fwd<T>(c, q + i * Sq * ldq, k + koff_host[i] * ldk, v + koff_host[i] * ldv, ldq, ldk, ldv, sq, sk, nullptr, 1, Sq,
+                     koff_host[i + 1] - koff_host[i], H, Dh, o + i * Sq * E, lse ? lse + i * H * Sq * 2 : nullptr, impl, nullptr, 0);
+}
+template <typename T>
+void attention_varlen_bwd(spa3d_ctx* c, const T* q, const T* k, const T* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq, const float* sk,
+                          int64_t nseq, int Sq, const int32_t* koff_host, const int32_t* koff_dev, int H, int Dh, const T* o, const float* lse,
+                          const T* d_o, T* dq, T* dk, T* dv, float* dsq, float* dsk, int impl) {
+  const int E = H * Dh;
+  int Skmax = 0;
+  for (int64_t i = 0; i < nseq; ++i) Skmax = std::max(Skmax, koff_host[i + 1] - koff_host[i]);
+  if constexpr (sizeof(T) == 2) {
+    if (impl != 1 && o && lse &&
+        attn_fused_bwd_bf16(c, q, k, v, ldq, ldk, ldv, sq, sk, nullptr, nseq, Sq, Skmax, H, Dh, o, lse, d_o, dq, dk, dv, dsq, dsk, nullptr, 0, koff_dev,
+                            koff_host[nseq]))
+      return;
+  }
+  for (int64_t i = 0; i < nseq; ++i) {
+    const int64_t k0 = koff_host[i];
+    attention_bwd<T>(c, q + i * Sq * ldq, k + k0 * ldk, v + k0 * ldv, ldq, ldk, ldv, sq, sk, nullptr, 1, Sq, koff_host[i + 1] - koff_host[i], H, Dh,
+                     o + i * Sq * E, lse ? lse + i * H * Sq * 2 : nullptr, d_o + i * Sq * E, dq + i * Sq * ldq, dk + k0 * ldk, dv + k0 * ldv, dsq, dsk,
+                     impl, nullptr, 0);
+  }
+}
 
 #define INST_ATTN(T)                                                                                                                  \
   template void attention_fwd<T>(spa3d_ctx*, const T*, const T*, const T*, int64_t, int64_t, int64_t, const float*, const float*,     \
                                  const float*, int64_t, int, int, int, int, T*, float*, int, const int32_t*, int64_t);                       \
   template void attention_bwd<T>(spa3d_ctx*, const T*, const T*, const T*, int64_t, int64_t, int64_t, const float*, const float*,     \
                                  const float*, int64_t, int, int, int, int, const T*, const float*, const T*, T*, T*, T*, float*, float*, int, \
-                                 const int32_t*, int64_t);
+                                 const int32_t*, int64_t);                                                                             \
+  template void attention_varlen_fwd<T>(spa3d_ctx*, const T*, const T*, const T*, int64_t, int64_t, int64_t, const float*, const float*, \
+                                        int64_t, int, const int32_t*, const int32_t*, int, int, T*, float*, int);                        \
+  template void attention_varlen_bwd<T>(spa3d_ctx*, const T*, const T*, const T*, int64_t, int64_t, int64_t, const float*, const float*, \
+                                        int64_t, int, const int32_t*, const int32_t*, int, int, const T*, const float*, const T*, T*, T*, T*,  \
+                                        float*, float*, int);
 INST_ATTN(float)
 INST_ATTN(bf16_t)
 }  // namespace SPA_NS

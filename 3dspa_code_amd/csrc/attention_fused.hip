@@ -252,6 +252,9 @@ struct XAttnArgs {
   const bf16_t *q, *k, *v; int64_t ldq, ldk, ldv;
   const float *sq, *sk, *km;
   int Sq, Sk, H, nsplit; int64_t nprob;
+  // ragged batches: key rows of sequence i are [koff[i], koff[i + 1]) (device, [nseq + 1]); Sk is then the longest sequence's key count and sizes
+  // nsplit; a chunk past its sequence's keys leaves the neutral partial (m = -inf, l = 0, zeros).  nullptr: Sk keys per sequence
+  const int32_t* koff;
   float* opart;   // [nprob][nsplit][Sq][96]
   float* mlpart;  // [nprob][nsplit][Sq][2]
 };
@@ -263,9 +266,15 @@ __global__ __launch_bounds__(256, 2) void xattn_fwd_kernel(XAttnArgs g) {
   const unsigned pi_u = blockIdx.x, prob_u = pi_u / (unsigned)g.nsplit, seq_u = prob_u / (unsigned)g.H;   // 32-bit: nprob * nsplit < 2^31 (xattn_fwd)
   const int64_t pi = pi_u, prob = prob_u; const int sp = (int)(pi_u - prob_u * (unsigned)g.nsplit);
   const int64_t seq = seq_u; const int h = (int)(prob_u - seq_u * (unsigned)g.H);
-  const int64_t qrow0 = seq * g.Sq, krow0 = seq * g.Sk + (int64_t)sp * S_pad;
-  const int Sq = g.Sq, kn = min(S_pad, g.Sk - sp * S_pad), QT = (Sq + 15) / 16;
+  const int64_t qrow0 = seq * g.Sq, krow0 = (g.koff ? (int64_t)g.koff[seq] : seq * g.Sk) + (int64_t)sp * S_pad;
+  const int Skseq = g.koff ? g.koff[seq + 1] - g.koff[seq] : g.Sk;
+  const int Sq = g.Sq, kn = min(S_pad, Skseq - sp * S_pad), QT = (Sq + 15) / 16;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, fr = lane & 15, fq = lane >> 4;
+  if (kn <= 0) {  // (ragged batches only) no key of this sequence in this chunk: the partial that the combine step weighs with exp(-inf) = 0
+    for (int t = tid; t < Sq * DH; t += NW * 64) g.opart[pi * Sq * DH + t] = 0.f;
+    for (int t = tid; t < Sq; t += NW * 64) { float* mp = g.mlpart + (pi * Sq + t) * 2; mp[0] = -__builtin_inff(); mp[1] = 0.f; }
+    return;
+  }
   RawRows<NP> rk, rv;
   rows_load<NP, RPP>(rk, g.k + krow0 * g.ldk + h * DH, g.ldk, kn);
   rows_load<NP, RPP>(rv, g.v + krow0 * g.ldv + h * DH, g.ldv, kn);
@@ -417,18 +426,20 @@ __global__ __launch_bounds__(256) void xattn_dq_finish_kernel(const float* __res
 static bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 static bool xattn_fwd(spa3d_ctx* c, const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq,
-                      const float* sk, const float* km, int64_t nseq, int Sq, int Sk, int H, bf16_t* o, float* lse, const int32_t* seq_off) {
+                      const float* sk, const float* km, int64_t nseq, int Sq, int Sk, int H, bf16_t* o, float* lse, const int32_t* seq_off,
+                      const int32_t* koff = nullptr, int64_t total_keys = 0) {
   const int nsplit = (Sk + XCHUNK - 1) / XCHUNK;
   const int64_t nprob = nseq * H;
   if (seq_off || Sq < 1 || Sq > XCHUNK || Sk < 1 || nprob * nsplit > 0x7fffffffLL) return false;
   if (ldq % 8 || ldk % 8 || ldv % 8 || !al16(q) || !al16(k) || !al16(v) || !al16(o)) return false;
   const int64_t mk = c->ar.mark();
   XAttnArgs a; a.q = q; a.k = k; a.v = v; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.sq = sq; a.sk = sk; a.km = km;
-  a.Sq = Sq; a.Sk = Sk; a.H = H; a.nsplit = nsplit; a.nprob = nprob;
+  a.Sq = Sq; a.Sk = Sk; a.H = H; a.nsplit = nsplit; a.nprob = nprob; a.koff = koff;
   a.opart = (float*)c->ar.alloc(nprob * nsplit * Sq * DH * (int64_t)sizeof(float));
   a.mlpart = (float*)c->ar.alloc(nprob * nsplit * Sq * 2 * (int64_t)sizeof(float));
   if (!c->dry) {
-    ProfScope ps(c, PROF_ATTN_FWD, 4.0 * (double)nprob * Sq * Sk * DH, (double)nprob * (2.0 * Sq + 2.0 * Sk) * DH * 2.0);
+    const double keys = koff ? (double)total_keys / (double)nseq : (double)Sk;  // keys per sequence actually present
+    ProfScope ps(c, PROF_ATTN_FWD, 4.0 * (double)nprob * Sq * keys * DH, (double)nprob * (2.0 * Sq + 2.0 * keys) * DH * 2.0);
     ps.tag(nseq, Sk, H, Sq);
     const int lds = 2 * img_bytes(XCHUNK) + XCHUNK * 4;
     xattn_fwd_kernel<<<(unsigned)(nprob * nsplit), 256, lds, c->stream>>>(a);
@@ -438,6 +449,15 @@ static bool xattn_fwd(spa3d_ctx* c, const bf16_t* q, const bf16_t* k, const bf16
   }
   c->ar.release(mk);  // stream-ordered: whatever reuses the space is launched behind the two kernels
   return true;
+}
+
+// cross attention over ragged key sets (tracks_to_latents on a batch with per-sample support counts): koff (device, [nseq + 1]) cuts the packed
+// key rows into sequences, Skmax = the longest.  false: shape outside the kernel (the caller then runs the sequences one by one)
+bool xattn_varlen_fwd_bf16(spa3d_ctx* c, const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq,
+                           const float* sk, int64_t nseq, int Sq, int Skmax, int H, int Dh, bf16_t* o, float* lse, const int32_t* koff,
+                           int64_t total_keys) {
+  if (Dh != DH || !koff) return false;
+  return xattn_fwd(c, q, k, v, ldq, ldk, ldv, sq, sk, nullptr, nseq, Sq, Skmax, H, o, lse, nullptr, koff, total_keys);
 }
 
 constexpr int ATTN_MAX_S = 320;  // K^ and V of one head resident: 2 x 320 x 192 B = 120 KiB of the CU's 160 KiB
@@ -506,6 +526,8 @@ struct AttnBwdArgs {
   // cross attention (attn_bwd8_kernel<8, true>): S = query rows per sequence (<= 128); the Sk keys of a sequence are cut into nsplit chunks
   // of 128, one workgroup pass per (sequence, head, chunk); dq^ (before the RMSNorm backward) leaves as fp32 partials per chunk
   int Sk, nsplit; float* dqpart;  // [nprob][nsplit][S][96]
+  // ... over ragged key sets (attn_bwd8_kernel<8, true, false, true>): seq_off (unused by the cross form otherwise) holds the key offsets
+  // [nseq + 1] of the packed key rows, Sk the longest sequence's key count; a chunk past its sequence's keys writes nothing (dqpart is zeroed)
   const DetCfg* det;  // the call's deterministic-gradient mode (common.hpp): the scale gradients
 #if SPA3D_ABL_ATTN  // tools/ablate_attn.py builds a separate diagnostic library with this; never defined for libspa3d_hip.so
   int ablate;          // 1: no tile work, 2: no staging (garbage operands), 4: no dq/dk/dv stores
@@ -809,8 +831,10 @@ __device__ __forceinline__ void flush_scale_grads(const AttnBwdArgs& g, float* s
 // problem: two waves per SIMD to overlap LDS/exp latency with the other's MFMAs, compute = max(a, b) instead of a + b.
 // X: cross attention -- a "problem" is (sequence, head, 128-key chunk): query-side rows (q, dO, O, lse: g.S per sequence) and key-side rows
 // (k, v: the chunk) come from different places, role (a) emits dq^ partials instead of dq (see bwd_query_tile).
-template <int KT, bool X = false, bool FAST = false>  // FAST: no key mask (g.km == nullptr), self attention -- see bwd_query_tile
+// V (with X): ragged key sets, an instance of its own so that the uniform form keeps its registers -- g.seq_off = key offsets, see AttnBwdArgs
+template <int KT, bool X = false, bool FAST = false, bool V = false>  // FAST: no key mask (g.km == nullptr), self attention -- see bwd_query_tile
 __global__ __launch_bounds__(512, 2) void attn_bwd8_kernel(AttnBwdArgs g) {
+  static_assert(!V || X, "ragged key sets are a form of the cross attention");
   static_assert(!(X && FAST), "the cross-attention form keeps the masked arithmetic");
   constexpr int S_pad = KT * 16;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -839,8 +863,15 @@ __global__ __launch_bounds__(512, 2) void attn_bwd8_kernel(AttnBwdArgs g) {
     const int64_t prob = prob_u, seq = seq_u; const int h = (int)h_u;
     const int64_t row0 = X ? seq * g.S : g.seq_off ? (int64_t)g.seq_off[seq] : seq * g.S;   // first query-side row
     const int S = (!X && g.seq_off) ? g.seq_off[seq + 1] - (int)row0 : g.S;               // query-side rows
-    const int64_t krow0 = X ? seq * g.Sk + (int64_t)sp * S_pad : row0;                   // first key-side row
-    const int Sk = X ? min(S_pad, g.Sk - sp * S_pad) : S;                                 // key-side rows
+    int64_t krow0; int Sk;  // first key-side row, key-side rows
+    if constexpr (V) {
+      const int k_lo = g.seq_off[seq] + sp * S_pad;
+      krow0 = k_lo; Sk = min(S_pad, g.seq_off[seq + 1] - k_lo);
+      if (Sk <= 0) continue;  // (uniform over the workgroup) no key of this sequence in this chunk: its dq^ partial stays at the launcher's zeros
+    } else {
+      krow0 = X ? seq * g.Sk + (int64_t)sp * S_pad : row0;
+      Sk = X ? min(S_pad, g.Sk - sp * S_pad) : S;
+    }
     const int QT = (S + 15) / 16, QTk = (Sk + 15) / 16;
     constexpr int NP = (S_pad + 127) / 128;
     // all five matrices of the problem are requested before the first is used: one memory latency per problem
@@ -1109,8 +1140,9 @@ static void launch_bwd(spa3d_ctx* c, const AttnBwdArgs& a) {
 bool attn_fused_bwd_bf16(spa3d_ctx* c, const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ldq, int64_t ldk, int64_t ldv,
                          const float* sq, const float* sk, const float* km, int64_t nseq, int Sq, int Sk, int H, int Dh, const bf16_t* o,
                          const float* lse, const bf16_t* d_o, bf16_t* dq, bf16_t* dk, bf16_t* dv, float* dsq, float* dsk,
-                         const int32_t* seq_off, int64_t total_rows) {
-  if (Dh == DH && Sq != Sk) {  // cross attention: chunked keys, see xattn_fwd_kernel
+                         const int32_t* seq_off, int64_t total_rows, const int32_t* koff, int64_t total_keys) {
+  if (koff && Dh != DH) return false;
+  if (koff || (Dh == DH && Sq != Sk)) {  // cross attention: chunked keys, see xattn_fwd_kernel (koff: ragged key sets, Sk = the longest)
     const int nsplit = (Sk + XCHUNK - 1) / XCHUNK;
     const int64_t nprob = nseq * H;
     if (seq_off || !o || !lse || Sq < 1 || Sq > XCHUNK || Sk < 1 || nprob * nsplit > 0x7fffffffLL) return false;
@@ -1121,18 +1153,27 @@ bool attn_fused_bwd_bf16(spa3d_ctx* c, const bf16_t* q, const bf16_t* k, const b
     float* dqpart = (float*)c->ar.alloc(nprob * nsplit * Sq * DH * (int64_t)sizeof(float));
     if (!c->dry) {
       AttnBwdArgs a; a.q = q; a.k = k; a.v = v; a.o = o; a.d_o = d_o; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.sq = sq; a.sk = sk; a.km = km;
-      a.lse = lse; a.S = Sq; a.H = H; a.nprob = nprob; a.dq = dq; a.dk = dk; a.dv = dv; a.dsq = dsq; a.dsk = dsk; a.seq_off = nullptr;
+      a.lse = lse; a.S = Sq; a.H = H; a.nprob = nprob; a.dq = dq; a.dk = dk; a.dv = dv; a.dsq = dsq; a.dsk = dsk; a.seq_off = koff;
       a.Sk = Sk; a.nsplit = nsplit; a.dqpart = dqpart; a.det = c->det;
 #if SPA3D_ABL_ATTN
       a.ablate = 0;
 #endif
-      ProfScope ps(c, PROF_ATTN_BWD, 14.0 * (double)nprob * Sq * Sk * DH, (double)nprob * (4.0 * Sq + 4.0 * Sk) * DH * 2.0);
+      const double keys = koff ? (double)total_keys / (double)nseq : (double)Sk;
+      ProfScope ps(c, PROF_ATTN_BWD, 14.0 * (double)nprob * Sq * keys * DH, (double)nprob * (4.0 * Sq + 4.0 * keys) * DH * 2.0);
       ps.tag(nseq, Sk, H, Sq);
       constexpr int KT = XCHUNK / 16;
       const int lds4 = 4 * img_bytes(XCHUNK) + 4 * XCHUNK * 4 + 4 * DH * 4 + 8 * WTILE;
       static bool attr_set = false;
-      if (!attr_set) { (void)hipFuncSetAttribute((const void*)attn_bwd8_kernel<KT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds4); attr_set = true; }
-      attn_bwd8_kernel<KT, true><<<(unsigned)std::min<int64_t>(nprob * nsplit, 1024), 512, lds4, c->stream>>>(a);
+      if (!attr_set) {
+        (void)hipFuncSetAttribute((const void*)attn_bwd8_kernel<KT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds4);
+        (void)hipFuncSetAttribute((const void*)attn_bwd8_kernel<KT, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds4);
+        attr_set = true;
+      }
+      if (koff) {  // chunks past a sequence's keys write nothing: their dq^ partials are these zeros
+        (void)hipMemsetAsync(dqpart, 0, (size_t)(nprob * nsplit * Sq * DH) * sizeof(float), c->stream);
+        attn_bwd8_kernel<KT, true, false, true><<<(unsigned)std::min<int64_t>(nprob * nsplit, 1024), 512, lds4, c->stream>>>(a);
+      }
+      else attn_bwd8_kernel<KT, true><<<(unsigned)std::min<int64_t>(nprob * nsplit, 1024), 512, lds4, c->stream>>>(a);
       const int64_t nrows = nprob * Sq;
       xattn_dq_finish_kernel<<<(unsigned)std::min<int64_t>((nrows + 3) / 4, 512), 256, 0, c->stream>>>(dqpart, nsplit, Sq, H, nrows, q, ldq, sq, dq, dsq, c->det);
       SPA_LAUNCH_CHECK(c);

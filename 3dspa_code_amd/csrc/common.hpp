@@ -218,6 +218,8 @@ struct spa3d_ctx {
                           // projection GEMM + attention kernel pair (profiles/r05_qkv_attn_fused.log), so opt-in only: attn_impl 6
   int det_grads = 0;      // spa3d_set_option "det_grads": order-independent parameter gradients (fixed-point shadow accumulation, DetCfg above); costs a few %
   const DetCfg* det = nullptr;  // the running det_grads train call's mode, in its workspace, passed to every kernel that adds into G; nullptr = float atomics
+  // spa3d_set_counts: per-sample live support tracks / live queries of the next calls' batch (host copies; cnt_B entries each)
+  std::vector<int32_t> cnt_n, cnt_q; bool has_cnt_n = false, has_cnt_q = false; int cnt_B = 0;
   int poison = 0;         // spa3d_set_option "poison": NaN-fill the workspace before every chunk and every op output before its launch (tests)
   Prof prof;
 };
@@ -309,6 +311,7 @@ template <typename T> void k_gelu(spa3d_ctx*, const T* x, T* y, int64_t n);
 template <typename T> void k_add(spa3d_ctx*, T* dst, const T* src, int64_t n);
 void k_fill(spa3d_ctx*, float* p, float v, int64_t n);
 void k_zero(spa3d_ctx*, void* p, int64_t bytes);
+void k_set_i32(spa3d_ctx*, int32_t* dst, const int32_t* host, int64_t n);  // n host ints -> device, by value in the launch arguments
 void k_mul(spa3d_ctx*, float* a, const float* b, int64_t n);
 void k_set_loss_scale(spa3d_ctx*, const float* denom_dev, float l1w, float setting, float* scale_dev);
 void k_unscale(spa3d_ctx*, float* a, const float* scale_dev, int64_t n);

@@ -759,6 +759,22 @@ void k_fill(spa3d_ctx* c, float* p, float v, int64_t n) {
   if (c->dry || n == 0) return;
   fill_kernel<<<GRID1D(n, 256), 256, 0, c->stream>>>(p, v, n); SPA_LAUNCH_CHECK(c);
 }
+// dst[0..n) = host values, passed BY VALUE in the launch arguments (32 per launch): no host-to-device copy, nothing borrowed from the caller
+struct I32x32 { int32_t v[32]; };
+__global__ void set_i32_kernel(int32_t* __restrict__ dst, I32x32 a, int n) {
+  const int t = threadIdx.x;
+#pragma unroll
+  for (int i = 0; i < 32; ++i) if (t == i && i < n) dst[i] = a.v[i];
+}
+void k_set_i32(spa3d_ctx* c, int32_t* dst, const int32_t* host, int64_t n) {
+  if (c->dry) return;
+  for (int64_t i0 = 0; i0 < n; i0 += 32) {
+    I32x32 a; const int m = (int)std::min<int64_t>(32, n - i0);
+    for (int i = 0; i < 32; ++i) a.v[i] = i < m ? host[i0 + i] : 0;
+    set_i32_kernel<<<1, 64, 0, c->stream>>>(dst + i0, a, m);
+  }
+  SPA_LAUNCH_CHECK(c);
+}
 void k_zero(spa3d_ctx* c, void* p, int64_t bytes) {
   if (c->dry || bytes == 0) return;
   hipError_t e = hipMemsetAsync(p, 0, (size_t)bytes, c->stream);

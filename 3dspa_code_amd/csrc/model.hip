@@ -19,6 +19,7 @@ enum { MODE_FORWARD = 0, MODE_TRAIN = 1, MODE_ENCODE = 2, MODE_DECODE = 3 };
 struct RunArgs {
   int mode; const float* P; const spa3d_batch* b; float denom; float* G; int accumulate; float* loss3; spa3d_outputs* out;
   const float* latents_in; float* latents_out; int chunk;  // chunk: fixed Bc (>0) or 0 = as large as fits
+  const int32_t* cn; const int32_t* cq;  // ragged batch (spa3d_set_counts): host arrays [B] of live support tracks / live queries per sample; null = all N / all Q
 };
 
 namespace SPA_NS {
@@ -30,6 +31,14 @@ template <typename T>
 void attention_bwd(spa3d_ctx* c, const T* q, const T* k, const T* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq,
                    const float* sk, const float* km, int64_t nseq, int Sq, int Sk, int H, int Dh, const T* o, const float* lse, const T* d_o,
                    T* dq, T* dk, T* dv, float* dsq, float* dsk, int impl, const int32_t* seq_off = nullptr, int64_t total_rows = 0);
+
+template <typename T>
+void attention_varlen_fwd(spa3d_ctx* c, const T* q, const T* k, const T* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq, const float* sk,
+                          int64_t nseq, int Sq, const int32_t* koff_host, const int32_t* koff_dev, int H, int Dh, T* o, float* lse, int impl);
+template <typename T>
+void attention_varlen_bwd(spa3d_ctx* c, const T* q, const T* k, const T* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq, const float* sk,
+                          int64_t nseq, int Sq, const int32_t* koff_host, const int32_t* koff_dev, int H, int Dh, const T* o, const float* lse,
+                          const T* d_o, T* dq, T* dk, T* dv, float* dsq, float* dsk, int impl);
 
 static const float L1_WEIGHT = 5000.0f, BCE_WEIGHT = 1e-8f;  // train.py:96
 
@@ -98,6 +107,10 @@ template <typename T> struct Net {
     twoD = g.model_kind == 1; NC = twoD ? 2 : 3;
   }
   template <typename U> U* alloc(int64_t n) { return (U*)c->ar.alloc(n * (int64_t)sizeof(U)); }
+  void copy_dd(void* dst, const void* src, int64_t bytes) {  // device-to-device on the launch stream
+    if (c->dry || bytes <= 0) return;
+    if (hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToDevice, c->stream) != hipSuccess && !c->hip_err) { c->hip_err = -7; c->err = "packing a ragged chunk: device copy failed"; }
+  }
   const float* p(const std::string& n) { return P + off.at(n); }
   float* gr(const std::string& n) { return G ? G + off.at(n) : nullptr; }
 
@@ -261,8 +274,9 @@ template <typename T> struct Net {
   }
 
   // ------------------------------------------------------------------ ImprovedTransformerBlock (attention.py:67-108)
+  // koff_h / koff_d (host / device, [nseq + 1]): cross attention against RAGGED key sets -- sequence i attends rows [koff[i], koff[i + 1]) of kv
   void block_fwd(const BlockW<T>& w, const T* x, T* y, int64_t nseq, int S, const float* km, const T* kv, int Skv, BlockStash<T>* st,
-                 const Rag& rg = Rag(), const Share<T>* sh = nullptr) {
+                 const Rag& rg = Rag(), const Share<T>* sh = nullptr, const int32_t* koff_h = nullptr, const int32_t* koff_d = nullptr) {
     const int64_t M = rg.off ? rg.rows : nseq * S, Mg = rg.off ? (M + 7) & ~int64_t(7) : M; const int d = w.d;  // Mg: NT-GEMM rows (see Rag)
     int64_t mk = c->ar.mark();
     T *nq, *qkv; float* st1;
@@ -297,9 +311,11 @@ template <typename T> struct Net {
     T *cq = nullptr, *ckv = nullptr, *co = nullptr; float* clse = nullptr;
     if (w.cross) {                                                                      // :92-100
       cq = alloc<T>(M * E); lin_fwd(w.cq, nq, cq, M);
-      ckv = alloc<T>(nseq * Skv * 2 * E); lin_fwd(w.ckv, kv, ckv, nseq * Skv);
+      const int64_t nkv = koff_h ? koff_h[nseq] : nseq * Skv;
+      ckv = alloc<T>(nkv * 2 * E); lin_fwd(w.ckv, kv, ckv, nkv);
       co = alloc<T>(M * E); clse = alloc<float>(M * H * 2);
-      attn_fwd(cq, ckv, ckv + E, E, 2 * E, 2 * E, w.csq, w.csk, nullptr, nseq, S, Skv, co, clse);
+      if (koff_h) attention_varlen_fwd<T>(c, cq, ckv, ckv + E, E, 2 * E, 2 * E, w.csq, w.csk, nseq, S, koff_h, koff_d, H, Dh, co, clse, c->attn_impl);
+      else attn_fwd(cq, ckv, ckv + E, E, 2 * E, 2 * E, w.csq, w.csk, nullptr, nseq, S, Skv, co, clse);
       lin_fwd(w.cout, co, a, M, EPI_NONE, a);
     }
     T* na = alloc<T>(Mg * d); float* st2 = alloc<float>(Mg * 2);
@@ -320,7 +336,7 @@ template <typename T> struct Net {
   }
   // dy -> dx (dx may alias dy); dkv accumulated (T) if cross
   void block_bwd(const BlockW<T>& w, const BlockStash<T>& s, const T* dy, T* dx, int64_t nseq, int S, const float* km, const T* kv,
-                 int Skv, T* dkv, const Rag& rg = Rag(), const Share<T>* sh = nullptr) {
+                 int Skv, T* dkv, const Rag& rg = Rag(), const Share<T>* sh = nullptr, const int32_t* koff_h = nullptr, const int32_t* koff_d = nullptr) {
     const int64_t M = rg.off ? rg.rows : nseq * S, Mg = rg.off ? (M + 7) & ~int64_t(7) : M; const int d = w.d;
     int64_t mk = c->ar.mark();
     lin_bwd_w(w.mlp_out, s.h, dy, M);
@@ -364,14 +380,17 @@ template <typename T> struct Net {
       lin_bwd_w(w.cout, s.co, da, M);
       lin_bwd_x(w.cout, da, d_o, M);  // d_o := d co
       T* dcq = dqkv;                  // reuse [M,E]
-      T* dckv = alloc<T>(nseq * Skv * 2 * E);
-      attn_bwd(s.cq, s.ckv, s.ckv + E, E, 2 * E, 2 * E, w.csq, w.csk, nullptr, nseq, S, Skv, s.co, s.clse, d_o, dcq, dckv, dckv + E,
+      const int64_t nkv = koff_h ? koff_h[nseq] : nseq * Skv;
+      T* dckv = alloc<T>(nkv * 2 * E);
+      if (koff_h) attention_varlen_bwd<T>(c, s.cq, s.ckv, s.ckv + E, E, 2 * E, 2 * E, w.csq, w.csk, nseq, S, koff_h, koff_d, H, Dh, s.co, s.clse, d_o,
+                                          dcq, dckv, dckv + E, w.g_csq, w.g_csk, c->attn_impl);
+      else attn_bwd(s.cq, s.ckv, s.ckv + E, E, 2 * E, 2 * E, w.csq, w.csk, nullptr, nseq, S, Skv, s.co, s.clse, d_o, dcq, dckv, dckv + E,
                w.g_csq, w.g_csk);
       // attn_bwd writes dq with stride ldq = E into dcq: dense [M,E]
       lin_bwd_w(w.cq, s.nq, dcq, M);
       lin_bwd_x(w.cq, dcq, dnq, M, nullptr, 1);
-      lin_bwd_w(w.ckv, kv, dckv, nseq * Skv);
-      lin_bwd_x(w.ckv, dckv, dkv, nseq * Skv, nullptr, 1);
+      lin_bwd_w(w.ckv, kv, dckv, nkv);
+      lin_bwd_x(w.ckv, dckv, dkv, nkv, nullptr, 1);
     }
     k_layernorm_bwd<T>(c, s.x, w.norm_q, s.st1, dnq, dx, w.g_norm_q, M, d, da);  // dx = da + LNbwd
     c->ar.release(mk);
@@ -455,6 +474,12 @@ template <typename T> struct Net {
     int64_t Bc, nseq; int N, Q, T_, S;
     // intra-sample slices (run_body: "track_chunk" / "query_chunk", one sample per chunk): the track encoder runs on tracks [n_off, n_off + Nc) of the
     // sample (nseq = Bc * Nc; the cross attention of tracks_to_latents still sees all N), the readout on queries [q_off, q_off + Qc)
+    bool ragged = false;  // sample(s) of a batch with per-sample counts (spa3d_set_counts)
+    // packed: a chunk of SEVERAL samples of such a batch.  Their live tracks / queries are packed back to back -- the track encoder runs on
+    // nseq = noff[Bc] sequences, the readout on qoff[Bc] -- and only the cheap per-sample kernels (key mask, sequence assembly, loss) loop over the samples
+    bool packed = false; std::vector<int32_t> noff, qoff; int32_t* koff_dev = nullptr;
+    int64_t nq() const { return packed ? (int64_t)qoff.back() : Bc * Qc; }
+    int Nk = 0;  // keys of the tracks_to_latents cross attention per sample: N, or the sample's live support tracks in a ragged batch
     int64_t n_off = 0, q_off = 0; int Nc = 0, Qc = 0; bool count_plan = true;  // count_plan: false for the backward's recompute (spa3d_plan_stats counts pass A only)
     // encoder
     T* sinbuf; const void* dino; const void* depthf; float* km; T* tok0; std::vector<BlockStash<T>> enc_st; T* enc_last; T* r0; float* st_r0;
@@ -479,6 +504,21 @@ template <typename T> struct Net {
     const int64_t nseq = k.nseq, trk0 = b0 * k.N + k.n_off;  // first track row of the slice (tracks of a sample chunk are contiguous when Nc < N: Bc = 1)
     const float* tracks = b->support_tracks + trk0 * T_ * NC;
     k.sup_vis = b->support_tracks_visible + trk0 * T_;
+    const bool want_dino = !twoD && g.dino_feature_dim > 0 && b->dino_features, want_depth = !twoD && g.depth_feature_dim > 0 && b->depth_features;
+    const T* dino_in = want_dino ? (const T*)b->dino_features + trk0 * T_ * g.dino_feature_dim : nullptr;
+    const T* depth_in = want_depth ? (const T*)b->depth_features + trk0 * T_ * g.depth_feature_dim : nullptr;
+    if (k.packed) {  // the live tracks of the chunk's samples, back to back (each sample's are the first rows of its slice: one copy per sample and tensor)
+      float* pt = alloc<float>(nseq * T_ * NC); float* pv = alloc<float>(nseq * T_);
+      T* pd = want_dino ? alloc<T>(nseq * T_ * g.dino_feature_dim) : nullptr; T* pz = want_depth ? alloc<T>(nseq * T_ * g.depth_feature_dim) : nullptr;
+      for (int64_t s = 0; s < k.Bc; ++s) {
+        const int64_t src = (b0 + s) * k.N * T_, dst = (int64_t)k.noff[s] * T_, n = (int64_t)(k.noff[s + 1] - k.noff[s]) * T_;
+        copy_dd(pt + dst * NC, b->support_tracks + src * NC, n * NC * 4);
+        copy_dd(pv + dst, b->support_tracks_visible + src, n * 4);
+        if (pd) copy_dd(pd + dst * g.dino_feature_dim, (const T*)b->dino_features + src * g.dino_feature_dim, n * g.dino_feature_dim * (int64_t)sizeof(T));
+        if (pz) copy_dd(pz + dst * g.depth_feature_dim, (const T*)b->depth_features + src * g.depth_feature_dim, n * g.depth_feature_dim * (int64_t)sizeof(T));
+      }
+      tracks = pt; k.sup_vis = pv; dino_in = pd; depth_in = pz;
+    }
     // embed stage (3d:123-165) as one profile class: algorithmic bytes = what a single pass would move (xyz f32 + visibility + the 16-bit
     // dino / depth planes in, the kept token rows out); FLOPs of its projections
     ProfScope* eps = nullptr;
@@ -490,7 +530,13 @@ template <typename T> struct Net {
     k.sinbuf = alloc<T>(nseq * T_ * (NC + 1) * 2 * nf);
     k_embed_tokens<T>(c, tracks, nseq * T_, T_, nf, g.track_scale_factor, k.sinbuf, NC);             // 3d:126-134 / ta:186-199
     k.km = alloc<float>(nseq * S);
-    if (twoD) k_keymask2d(c, k.sup_vis, b->boundary_frame + b0, nseq, k.Nc, T_, k.km);               // ta:213-223
+    if (k.packed) {  // boundary_frame is per sample
+      for (int64_t s = 0; s < k.Bc; ++s) {
+        const int n = k.noff[s + 1] - k.noff[s];
+        k_keymask(c, k.sup_vis + (int64_t)k.noff[s] * T_, b->boundary_frame + b0 + s, n, n, T_, k.km + (int64_t)k.noff[s] * S);
+      }
+    }
+    else if (twoD) k_keymask2d(c, k.sup_vis, b->boundary_frame + b0, nseq, k.Nc, T_, k.km);          // ta:213-223
     else k_keymask(c, k.sup_vis, b->boundary_frame + b0, nseq, k.Nc, T_, k.km);                      // 3d:167-180 (R2,R3)
     // Token pruning (3DSPA, fused 16-bit attention): a frame token whose key is masked is attended to by nobody, and only token 0 leaves
     // the stack (3d:187-188), so its row influences neither the output nor any gradient: the encoder runs on the kept rows only.
@@ -504,8 +550,7 @@ template <typename T> struct Net {
     }
     const Rag& rg = k.enc_rg;
     const int64_t rows = rg.off ? rg.rows : nseq * S, rows_g = rg.off ? (rows + 7) & ~int64_t(7) : rows;
-    k.dino = (!twoD && g.dino_feature_dim > 0 && b->dino_features) ? (const T*)b->dino_features + trk0 * T_ * g.dino_feature_dim : nullptr;
-    k.depthf = (!twoD && g.depth_feature_dim > 0 && b->depth_features) ? (const T*)b->depth_features + trk0 * T_ * g.depth_feature_dim : nullptr;
+    k.dino = dino_in; k.depthf = depth_in;
     bool emb_done = false;
     if constexpr (sizeof(T) == 2) {
       // K1: the three Denses are ONE Dense on the concatenated row (repair R4) -- one GEMM over K = 256 sin features + 768 DINO columns
@@ -576,17 +621,19 @@ template <typename T> struct Net {
       k_layernorm<T>(c, k.r0, enc.norm_enc, k.enc_out, k.st_r0, nseq, d);                            // attention.py:49-51 (row 0 only)
     }
   }
-  // L1-L3: k.enc_out holds all k.Bc * k.N encoder outputs
+  // L1-L3: k.enc_out holds all k.Bc * k.Nk encoder outputs
   void encode_latents(Chunk& k, bool train) {
     const int L = g.num_latent_tokens, dl = g.encoder_latent_dim;
     const T* x;
+    if (k.packed) { k.koff_dev = alloc<int32_t>(k.Bc + 1); k_set_i32(c, k.koff_dev, k.noff.data(), k.Bc + 1); }
+    const int32_t* koff_h = k.packed ? k.noff.data() : nullptr;
     k.lat_in = alloc<T>(k.Bc * L * dl);
     k_broadcast_rows<T>(c, lat0, L, dl, k.lat_in, k.Bc);                                             // 3d:200
     x = k.lat_in;
     k.t2l_st.resize(t2l.blocks.size());
     for (size_t i = 0; i < t2l.blocks.size(); ++i) {
       T* y = alloc<T>(k.Bc * L * dl);
-      block_fwd(t2l.blocks[i], x, y, k.Bc, L, nullptr, k.enc_out, k.N, train ? &k.t2l_st[i] : nullptr);  // 3d:201
+      block_fwd(t2l.blocks[i], x, y, k.Bc, L, nullptr, k.enc_out, k.Nk, train ? &k.t2l_st[i] : nullptr, Rag(), nullptr, koff_h, k.koff_dev);  // 3d:201
       x = y;
     }
     k.t2l_last = const_cast<T*>(x);
@@ -624,12 +671,19 @@ template <typename T> struct Net {
   // query tokens, readout stack and head of queries [k.q_off, k.q_off + k.Qc) of samples [b0, b0 + k.Bc) against k.latd
   void decode_queries(Chunk& k, const spa3d_batch* b, int64_t b0, bool train) {
     const int L = g.num_latent_tokens, dd = g.decoder_num_channels, Cl = dd - 128, nf = g.num_frequencies;
-    const int64_t nq = k.Bc * k.Qc;
+    const int64_t nq = k.nq();
     const T* x;
     // query tokens                                                                                     3d:209-233,265-275
     const int F = NC * 2 * nf + 1;
     k.feat = alloc<float>(nq * F); k.qframe = alloc<int32_t>(nq);
-    k_query_embed1(c, b->query_points + (b0 * k.Q + k.q_off) * (NC + 1), nq, nf, g.track_scale_factor, g.time_scale_factor, k.feat, k.qframe, NC);
+    const float* qp = b->query_points + (b0 * k.Q + k.q_off) * (NC + 1);
+    if (k.packed) {  // the live query points of the chunk's samples, back to back
+      float* pq = alloc<float>(nq * (NC + 1));
+      for (int64_t s = 0; s < k.Bc; ++s)
+        copy_dd(pq + (int64_t)k.qoff[s] * (NC + 1), b->query_points + (b0 + s) * k.Q * (NC + 1), (int64_t)(k.qoff[s + 1] - k.qoff[s]) * (NC + 1) * 4);
+      qp = pq;
+    }
+    k_query_embed1(c, qp, nq, nf, g.track_scale_factor, g.time_scale_factor, k.feat, k.qframe, NC);
     k.sin2 = alloc<T>(nq * F * 2 * nf);
     k_sin_embed<T>(c, k.feat, nq, F, nf, g.track_scale_factor, k.sin2);
     k.qtok = alloc<T>(nq * dd);
@@ -637,13 +691,23 @@ template <typename T> struct Net {
     // readout sequences                                                                                3d:276-285
     const int S = L + 1;
     k.seq0 = alloc<T>(nq * S * dd);
-    k_assemble_readout<T>(c, k.qtok, k.latd, k.qframe, k.Bc, k.Qc, L, Cl, dd, k.seq0);
+    if (k.packed) {  // a query's sample decides which latents it reads
+      for (int64_t s = 0; s < k.Bc; ++s) {
+        const int64_t q0 = k.qoff[s]; const int qs = k.qoff[s + 1] - k.qoff[s];
+        if (qs > 0) k_assemble_readout<T>(c, k.qtok + q0 * dd, k.latd + s * L * Cl, k.qframe + q0, 1, qs, L, Cl, dd, k.seq0 + q0 * S * dd);
+      }
+    }
+    else k_assemble_readout<T>(c, k.qtok, k.latd, k.qframe, k.Bc, k.Qc, L, Cl, dd, k.seq0);
     x = k.seq0;
     const int nro = (int)ro.blocks.size();
     k.ro_st.resize(nro);
     // first block: LN1 / QKV once per distinct (sample, query frame) -- see Share.  One stream sync reads the slot count.
     k.ro_sh = Share<T>(); k.ro_share = false;
-    if (sizeof(T) == 2 && c->ro_share && nro >= 2 && dd % 8 == 0 && Cl % 8 == 0 && k.Qc >= 8) {
+    const bool share_ok = sizeof(T) == 2 && c->ro_share && nro >= 2 && dd % 8 == 0 && Cl % 8 == 0;
+    // a ragged sample too narrow for the slot plan still counts its queries; a packed chunk runs without the slot plan (its slots would have to be
+    // planned per sample: not carried over yet) and counts them too
+    if (share_ok && (k.packed || k.Qc < 8) && k.ragged && !c->dry) c->plan_stats[3] += (double)nq;
+    if (share_ok && !k.packed && k.Qc >= 8) {
       int32_t* slot = alloc<int32_t>(nq); int32_t* slot_b = alloc<int32_t>(nq); int32_t* slot_f = alloc<int32_t>(nq);
       int32_t* slot_q0 = alloc<int32_t>(nq); int32_t* scratch = alloc<int32_t>(nq + k.Bc + 1);
       Share<T>& sh = k.ro_sh;
@@ -708,12 +772,19 @@ template <typename T> struct Net {
   // head, readout transformer, assembly, query encoder of queries [k.q_off, k.q_off + k.Qc): dlatd32 [Bc,L,Cl] = (accumulate ? += : =) the latent-side gradient
   void backward_queries(Chunk& k, const spa3d_batch* b, int64_t b0, const float* denom_dev, float* dlatd32, bool accumulate) {
     const int L = g.num_latent_tokens, dd = g.decoder_num_channels, Cl = dd - 128, To = g.num_output_frames;
-    const int64_t nq = k.Bc * k.Qc, qrow = b0 * k.Q + k.q_off;
+    const int64_t nq = k.nq(), qrow = b0 * k.Q + k.q_off;
     {
       const int S = L + 1;
       const int64_t mk = c->ar.mark();
       T* dhead = alloc<T>(nq * 4 * To);
-      k_loss_bwd<T>(c, k.head, nq, To, b->query_tracks + qrow * To * NC, b->query_tracks_visible + qrow * To, denom_dev,
+      if (k.packed) {  // targets stay in the padded layout: sample by sample
+        for (int64_t s = 0; s < k.Bc; ++s) {
+          const int64_t q0 = k.qoff[s], tr = (b0 + s) * k.Q;
+          k_loss_bwd<T>(c, k.head + q0 * 4 * To, k.qoff[s + 1] - k.qoff[s], To, b->query_tracks + tr * To * NC, b->query_tracks_visible + tr * To, denom_dev,
+                        L1_WEIGHT, BCE_WEIGHT, dhead + q0 * 4 * To, NC, c->loss_scale != 1.f ? denom_dev + 1 : nullptr);
+        }
+      }
+      else k_loss_bwd<T>(c, k.head, nq, To, b->query_tracks + qrow * To * NC, b->query_tracks_visible + qrow * To, denom_dev,
                     L1_WEIGHT, BCE_WEIGHT, dhead, NC, c->loss_scale != 1.f ? denom_dev + 1 : nullptr);  // + loss scale in fp16 mode
       lin_bwd_w(pred, k.q0n, dhead, nq);
       T* dq0n = alloc<T>(nq * dd);
@@ -726,7 +797,14 @@ template <typename T> struct Net {
       block_bwd_last(ro.blocks[nro - 1], k.ro_lst, dq0, dseq, nq, S, nullptr);
       for (int i = nro - 2; i >= 0; --i)
         block_bwd(ro.blocks[i], k.ro_st[i], dseq, dseq, nq, S, nullptr, nullptr, 0, nullptr, Rag(), (i == 0 && k.ro_share) ? &k.ro_sh : nullptr);
-      k_assemble_readout_bwd<T>(c, dseq, k.qframe, k.Bc, k.Qc, L, Cl, dd, dqtok, dlatd32, accumulate);
+      if (k.packed) {
+        for (int64_t s = 0; s < k.Bc; ++s) {
+          const int64_t q0 = k.qoff[s]; const int qs = k.qoff[s + 1] - k.qoff[s];
+          if (qs > 0) k_assemble_readout_bwd<T>(c, dseq + q0 * S * dd, k.qframe + q0, 1, qs, L, Cl, dd, dqtok + q0 * dd, dlatd32 + s * L * Cl, accumulate);
+          else if (!accumulate) k_zero(c, dlatd32 + s * L * Cl, (int64_t)L * Cl * 4);  // a sample without live queries sends no gradient to its latents
+        }
+      }
+      else k_assemble_readout_bwd<T>(c, dseq, k.qframe, k.Bc, k.Qc, L, Cl, dd, dqtok, dlatd32, accumulate);
       lin_bwd_w(qenc, k.sin2, dqtok, nq);
       c->ar.release(mk);
     }
@@ -756,10 +834,11 @@ template <typename T> struct Net {
     lin_bwd_x(comp, dlq, dt2ln, nl);
     T* dt2l = alloc<T>(nl * dl);
     k_layernorm_bwd<T>(c, k.t2l_last, t2l.norm_enc, k.st_t2l, dt2ln, dt2l, t2l.g_norm_enc, nl, dl, nullptr);
-    T* denc_out = alloc<T>(k.Bc * k.N * d);
-    k_zero(c, denc_out, k.Bc * k.N * d * (int64_t)sizeof(T));
+    const int64_t nkeys = k.packed ? (int64_t)k.noff.back() : k.Bc * k.Nk;
+    T* denc_out = alloc<T>(nkeys * d);
+    k_zero(c, denc_out, nkeys * d * (int64_t)sizeof(T));
     for (int i = (int)t2l.blocks.size() - 1; i >= 0; --i)
-      block_bwd(t2l.blocks[i], k.t2l_st[i], dt2l, dt2l, k.Bc, L, nullptr, k.enc_out, k.N, denc_out);
+      block_bwd(t2l.blocks[i], k.t2l_st[i], dt2l, dt2l, k.Bc, L, nullptr, k.enc_out, k.Nk, denc_out, Rag(), nullptr, k.packed ? k.noff.data() : nullptr, k.koff_dev);
     grad_segment_done(1);  // tracks_to_latents, compressor, decompressor, decompress_attn
     k_bcast_grad<T>(c, dt2l, (int64_t)L * dl, k.Bc, (int64_t)L * dl, g_lat0);
     return denc_out;
@@ -824,6 +903,20 @@ template <typename T>
 static void emit_outputs(spa3d_ctx* c, const RunArgs& a, Net<T>& net, typename Net<T>::Chunk& k, int64_t b0, float* sums, unsigned* poison) {
   const spa3d_batch* b = a.b; const int To = c->cfg.num_output_frames, NC = net.NC;
   const bool train = a.mode == MODE_TRAIN;
+  if (k.packed) {  // outputs and targets stay in the padded layout: sample by sample, and the padded query rows read as 0
+    for (int64_t s = 0; s < k.Bc; ++s) {
+      const int64_t r = (b0 + s) * b->Q, q0 = k.qoff[s], qs = k.qoff[s + 1] - k.qoff[s], pad = b->Q - qs;
+      float* tr = a.out && a.out->tracks ? a.out->tracks + r * To * NC : nullptr;
+      float* vl = a.out && a.out->visible_logits ? a.out->visible_logits + r * To : nullptr;
+      float* cl = a.out && a.out->certain_logits ? a.out->certain_logits + r * To : nullptr;
+      k_loss_fwd(c, k.head + q0 * 4 * To, qs, To, train ? b->query_tracks + r * To * NC : nullptr, train ? b->query_tracks_visible + r * To : nullptr,
+                 tr, vl, cl, sums, poison, NC);
+      if (tr && pad > 0) k_zero(c, tr + qs * To * NC, pad * To * NC * 4);
+      if (vl && pad > 0) k_zero(c, vl + qs * To, pad * To * 4);
+      if (cl && pad > 0) k_zero(c, cl + qs * To, pad * To * 4);
+    }
+    return;
+  }
   const int64_t nq = k.Bc * k.Qc, qrow = b0 * b->Q + k.q_off;
   float* tr = a.out && a.out->tracks ? a.out->tracks + qrow * To * NC : nullptr;
   float* vl = a.out && a.out->visible_logits ? a.out->visible_logits + qrow * To : nullptr;
@@ -840,25 +933,28 @@ static void emit_outputs(spa3d_ctx* c, const RunArgs& a, Net<T>& net, typename N
 //  query_chunk: readout rows depend on their query and the sample's latents only, and the loss denominator is batch-global and known up front,
 //    so each chunk of queries runs embed -> readout -> head -> loss -> readout backward and releases its arena; the latent-side gradient
 //    dlatd32 is written by the first chunk and accumulated (fp32, fixed order, no atomics) by the others.
+// A sample of a ragged batch (spa3d_set_counts) takes the same route with nlive <= N support tracks and qlive <= Q queries: its live rows are the
+// first rows of its slice of the padded tensors, so the sample runs as a sample of its own size on offset pointers -- nothing at or beyond a count
+// is read -- and the padded output rows are zeroed.  qlive == 0: the sample is encoded and contributes no loss and no gradient.
 template <typename T>
 static void run_sample_intra(spa3d_ctx* c, const RunArgs& a, Net<T>& net, typename Net<T>::Chunk& k, int64_t b0, const float* noise, float* sums,
-                             unsigned* poison, const float* denom_dev) {
+                             unsigned* poison, const float* denom_dev, int nlive, int qlive) {
   const spa3d_batch* b = a.b; const spa3d_config& g = c->cfg;
   const int L = g.num_latent_tokens, Ld = g.latent_token_dim, Cl = g.decoder_num_channels - 128, d = g.track_token_dim;
   const bool train = a.mode == MODE_TRAIN;
-  const int tc = c->track_chunk > 0 ? std::min(c->track_chunk, b->N) : b->N, qc = c->query_chunk > 0 ? std::min(c->query_chunk, b->Q) : b->Q;
-  auto track_slice = [&](int64_t n0) { k.n_off = n0; k.Nc = (int)std::min<int64_t>(tc, b->N - n0); k.nseq = k.Nc; };
+  const int tc = c->track_chunk > 0 ? std::min(c->track_chunk, nlive) : nlive, qc = c->query_chunk > 0 ? std::min(c->query_chunk, qlive) : qlive;
+  auto track_slice = [&](int64_t n0) { k.n_off = n0; k.Nc = (int)std::min<int64_t>(tc, nlive - n0); k.nseq = k.Nc; };
   if (a.mode != MODE_DECODE) {
     if (c->track_chunk > 0) {  // pass A
-      T* enc_all = net.template alloc<T>((int64_t)b->N * d);
-      for (int64_t n0 = 0; n0 < b->N; n0 += tc) {
+      T* enc_all = net.template alloc<T>((int64_t)nlive * d);
+      for (int64_t n0 = 0; n0 < nlive; n0 += tc) {
         track_slice(n0);
         const int64_t mk = c->ar.mark();
         poison_from(c, mk);
         net.encode_tracks(k, b, b0, false, enc_all + n0 * d);
         c->ar.release(mk);
       }
-      k.enc_out = enc_all; k.n_off = 0; k.Nc = b->N; k.nseq = b->N;
+      k.enc_out = enc_all; k.n_off = 0; k.Nc = nlive; k.nseq = nlive;
     } else {
       net.encode_tracks(k, b, b0, train);
     }
@@ -867,10 +963,20 @@ static void run_sample_intra(spa3d_ctx* c, const RunArgs& a, Net<T>& net, typena
     if (lo && !c->dry) (void)hipMemcpyAsync(lo + b0 * L * Ld, k.latents, (size_t)L * Ld * 4, hipMemcpyDeviceToDevice, c->stream);
   }
   if (a.mode == MODE_ENCODE) return;
+  if (qlive < b->Q && !c->dry) {  // padded query rows of the outputs read as 0
+    const int To = g.num_output_frames; const int64_t r0 = b0 * b->Q + qlive, nr = b->Q - qlive;
+    if (a.out && a.out->tracks) (void)hipMemsetAsync(a.out->tracks + r0 * To * net.NC, 0, (size_t)(nr * To * net.NC) * 4, c->stream);
+    if (a.out && a.out->visible_logits) (void)hipMemsetAsync(a.out->visible_logits + r0 * To, 0, (size_t)(nr * To) * 4, c->stream);
+    if (a.out && a.out->certain_logits) (void)hipMemsetAsync(a.out->certain_logits + r0 * To, 0, (size_t)(nr * To) * 4, c->stream);
+  }
+  if (qlive == 0) {  // no live query: no readout, no loss term, no gradient; the call's gradient segments may still end with this sample
+    if (train) { net.grad_segment_done(0); net.grad_segment_done(1); }
+    return;
+  }
   net.decode_latents(k, b, a.mode == MODE_DECODE ? a.latents_in + b0 * L * Ld : k.latents, noise, b0, train);
   float* dlatd32 = train ? net.template alloc<float>((int64_t)L * Cl) : nullptr;
-  for (int64_t q0 = 0; q0 < b->Q; q0 += qc) {
-    k.q_off = q0; k.Qc = (int)std::min<int64_t>(qc, b->Q - q0);
+  for (int64_t q0 = 0; q0 < qlive; q0 += qc) {
+    k.q_off = q0; k.Qc = (int)std::min<int64_t>(qc, qlive - q0);
     const int64_t mk = c->ar.mark();
     poison_from(c, mk);
     net.decode_queries(k, b, b0, train);
@@ -883,7 +989,7 @@ static void run_sample_intra(spa3d_ctx* c, const RunArgs& a, Net<T>& net, typena
   const T* denc_out = net.backward_latents(k, dlatd32);
   if (c->track_chunk <= 0) { net.backward_tracks(k, denc_out); return; }
   k.count_plan = false;  // pass B: recompute + backward per track chunk
-  for (int64_t n0 = 0; n0 < b->N; n0 += tc) {
+  for (int64_t n0 = 0; n0 < nlive; n0 += tc) {
     track_slice(n0);
     const int64_t mk = c->ar.mark();
     poison_from(c, mk);
@@ -911,7 +1017,11 @@ void run_body(spa3d_ctx* c, const RunArgs& a, int Bc) {
     noise = nb;
   }
   if (train) {
-    k_vis_count(c, b->query_tracks_visible, (int64_t)b->B * b->Q * To, sums + 4, poison);
+    if (a.cq) {  // live queries only: whatever sits in the padded target rows is never read
+      for (int64_t s = 0; s < b->B; ++s) k_vis_count(c, b->query_tracks_visible + s * b->Q * To, (int64_t)a.cq[s] * To, sums + 4, poison);
+    } else {
+      k_vis_count(c, b->query_tracks_visible, (int64_t)b->B * b->Q * To, sums + 4, poison);
+    }
     k_set_denom(c, sums, poison, a.denom, denom_dev);
     if (c->loss_scale != 1.f) k_set_loss_scale(c, denom_dev, L1_WEIGHT, c->loss_scale, denom_dev + 1);  // sums[7]
     if (!a.accumulate) k_zero(c, a.G, c->nparams * 4);
@@ -930,6 +1040,7 @@ void run_body(spa3d_ctx* c, const RunArgs& a, int Bc) {
     k_det_unit(c, sums, poison, denom_dev, c->loss_scale != 1.f ? denom_dev + 1 : nullptr, DetCfg{a.G, sh, (long long)c->nparams, fl, 0.f}, dc);
     c->det = dc;
   }
+  const bool ragged = a.cn || a.cq;  // per-sample counts (spa3d_set_counts; run() has validated them)
   const bool intra = c->query_chunk > 0 || c->track_chunk > 0;  // run() has made Bc = 1
   // The ragged chunk (B % Bc samples) runs FIRST, so the last chunk -- the one under whose track-encoder backward the gradient segments are all-reduced -- is a
   // full one (B = 64, Bc = 9: 9 samples of encoder backward to hide behind instead of 1)
@@ -938,10 +1049,20 @@ void run_body(spa3d_ctx* c, const RunArgs& a, int Bc) {
     cur = (b0 == 0 && b->B % Bc) ? b->B % Bc : std::min<int64_t>(Bc, b->B - b0);
     c->last_chunk = b0 + cur >= b->B;
     k.Bc = cur; k.N = b->N; k.Q = b->Q; k.T_ = b->T; k.S = b->T + (g.model_kind == 1 ? 0 : 1); k.nseq = k.Bc * b->N;
-    k.Nc = b->N; k.Qc = b->Q;
+    k.Nc = b->N; k.Qc = b->Q; k.Nk = b->N;
+    const int nlive = a.cn ? a.cn[b0] : b->N, qlive = a.cq ? a.cq[b0] : b->Q;
+    if (ragged && cur == 1) { k.ragged = true; k.Nc = k.Nk = nlive; k.nseq = nlive; k.Qc = qlive; }  // one sample: addressed in place, at its own size
+    else if (ragged) {  // several samples: their live rows packed back to back
+      k.ragged = k.packed = true; k.noff.assign(1, 0); k.qoff.assign(1, 0);
+      for (int64_t s = 0; s < cur; ++s) {
+        k.noff.push_back(k.noff.back() + (a.cn ? a.cn[b0 + s] : b->N));
+        k.qoff.push_back(k.qoff.back() + (a.cq ? a.cq[b0 + s] : b->Q));
+      }
+      k.nseq = k.noff.back();
+    }
     const int64_t mk = c->ar.mark();
     poison_from(c, mk);
-    if (intra) { run_sample_intra<T>(c, a, net, k, b0, noise, sums, poison, denom_dev); c->ar.release(mk); continue; }
+    if (intra || (ragged && cur == 1)) { run_sample_intra<T>(c, a, net, k, b0, noise, sums, poison, denom_dev, nlive, qlive); c->ar.release(mk); continue; }
     const float* lat = nullptr;
     if (a.mode != MODE_DECODE) {
       net.encode_chunk(k, b, b0, train);
@@ -952,9 +1073,11 @@ void run_body(spa3d_ctx* c, const RunArgs& a, int Bc) {
       lat = a.latents_in + b0 * L * Ld;
     }
     if (a.mode != MODE_ENCODE) {
-      net.decode_chunk(k, b, b0, lat, noise, train);
+      const bool no_query = k.packed && k.nq() == 0;  // a packed chunk without a single live query: outputs 0, no loss term, no gradient
+      if (!no_query) net.decode_chunk(k, b, b0, lat, noise, train);
       emit_outputs<T>(c, a, net, k, b0, sums, poison);
-      if (train) net.backward_chunk(k, b, b0, denom_dev);
+      if (train && !no_query) net.backward_chunk(k, b, b0, denom_dev);
+      if (train && no_query) { net.grad_segment_done(0); net.grad_segment_done(1); }
     }
     c->ar.release(mk);
   }
@@ -1091,6 +1214,28 @@ static int run(spa3d_ctx* c, RunArgs a, void* ws, int64_t ws_bytes, void* stream
     if (a.chunk > 1) { c->err = "\"chunk\" > 1 cannot be combined with \"query_chunk\" / \"track_chunk\" (they imply one sample per chunk)"; return SPA3D_ERR_ARG; }
     a.chunk = 1;
   }
+  // per-sample counts (spa3d_set_counts): validated here, before the first launch; the sizing dry runs below walk the live counts
+  a.cn = nullptr; a.cq = nullptr;
+  if (c->has_cnt_n || c->has_cnt_q) {
+    const spa3d_batch* b = a.b;
+    if (c->cnt_B != b->B) { c->err = "counts were set for B = " + std::to_string(c->cnt_B) + ", this batch has B = " + std::to_string(b->B); return SPA3D_ERR_ARG; }
+    if (c->cfg.model_kind == 1) { c->err = "per-sample counts are not supported by the 2-D model (model_kind 1)"; return SPA3D_ERR_ARG; }
+    if (c->query_chunk > 0 || c->track_chunk > 0) { c->err = "per-sample counts cannot be combined with \"query_chunk\" / \"track_chunk\""; return SPA3D_ERR_ARG; }
+    if (c->has_cnt_n && a.mode != MODE_DECODE) {  // spa3d_decode has no support tracks: it reads the query counts only
+      for (int i = 0; i < b->B; ++i)
+        if (c->cnt_n[i] < 1 || c->cnt_n[i] > b->N) { c->err = "support_count[" + std::to_string(i) + "] = " + std::to_string(c->cnt_n[i]) + " is outside [1, N = " + std::to_string(b->N) + "]"; return SPA3D_ERR_ARG; }
+      a.cn = c->cnt_n.data();
+    }
+    if (c->has_cnt_q && a.mode != MODE_ENCODE) {
+      for (int i = 0; i < b->B; ++i)
+        if (c->cnt_q[i] < 0 || c->cnt_q[i] > b->Q) { c->err = "query_count[" + std::to_string(i) + "] = " + std::to_string(c->cnt_q[i]) + " is outside [0, Q = " + std::to_string(b->Q) + "]"; return SPA3D_ERR_ARG; }
+      a.cq = c->cnt_q.data();
+    }
+    // counts that leave nothing out describe a uniform batch: it takes the batched path, bit for bit the call without counts
+    bool full = true;
+    for (int i = 0; i < b->B && full; ++i) full = (!a.cn || a.cn[i] == b->N) && (!a.cq || a.cq[i] == b->Q);
+    if (full) { a.cn = nullptr; a.cq = nullptr; }
+  }
   if (a.chunk > 0) { lo = hi = std::min(a.chunk, a.b->B); }
   if (dry_need(c, a, lo) > ws_bytes) {
     c->err = "workspace too small: need " + std::to_string(dry_need(c, a, lo)) + " bytes for chunk " + std::to_string(lo);
@@ -1204,11 +1349,27 @@ int spa3d_loss(spa3d_handle h, const spa3d_batch* b, const spa3d_outputs* preds,
   if (((uintptr_t)loss3) & 7) { h->err = "loss3 must be 8-byte aligned"; return SPA3D_ERR_ARG; }
   float* scratch = loss3 + 4;  // loss3 points at 12 floats: [0..2] results, [3] sticky non-finite flag, [4..9] three 64-bit fixed-point accumulators, [10] denominator
   unsigned* poison = (unsigned*)(loss3 + 3);
-  const int64_t n = (int64_t)b->B * b->Q * h->cfg.num_output_frames;
+  const int To = h->cfg.num_output_frames, NC = h->cfg.model_kind == 1 ? 2 : 3;
+  const int64_t n = (int64_t)b->B * b->Q * To;
+  if (h->has_cnt_q) {
+    if (h->cnt_B != b->B) { h->err = "counts were set for B = " + std::to_string(h->cnt_B) + ", this batch has B = " + std::to_string(b->B); return SPA3D_ERR_ARG; }
+    for (int i = 0; i < b->B; ++i)
+      if (h->cnt_q[i] < 0 || h->cnt_q[i] > b->Q) { h->err = "query_count[" + std::to_string(i) + "] is outside [0, Q]"; return SPA3D_ERR_ARG; }
+  }
   k_zero(h, loss3 + 3, 36);
+  if (h->has_cnt_q) {  // live queries only, sample by sample (the sums are order-independent fixed-point sums)
+    for (int64_t s = 0; s < b->B; ++s) k_vis_count(h, b->query_tracks_visible + s * b->Q * To, (int64_t)h->cnt_q[s] * To, scratch + 4, poison);
+    k_set_denom(h, scratch, poison, denom, scratch + 6);
+    for (int64_t s = 0; s < b->B; ++s) {
+      const int64_t r = s * b->Q * To;
+      k_loss_from_preds(h, preds->tracks + r * NC, preds->visible_logits + r, (int64_t)h->cnt_q[s] * To, b->query_tracks + r * NC, b->query_tracks_visible + r, scratch, poison, NC);
+    }
+    k_loss_finalize(h, scratch, poison, scratch + 6, L1_WEIGHT, BCE_WEIGHT, loss3);
+    return h->hip_err ? SPA3D_ERR_HIP : SPA3D_OK;
+  }
   k_vis_count(h, b->query_tracks_visible, n, scratch + 4, poison);
   k_set_denom(h, scratch, poison, denom, scratch + 6);
-  k_loss_from_preds(h, preds->tracks, preds->visible_logits, n, b->query_tracks, b->query_tracks_visible, scratch, poison, h->cfg.model_kind == 1 ? 2 : 3);
+  k_loss_from_preds(h, preds->tracks, preds->visible_logits, n, b->query_tracks, b->query_tracks_visible, scratch, poison, NC);
   k_loss_finalize(h, scratch, poison, scratch + 6, L1_WEIGHT, BCE_WEIGHT, loss3);
   return h->hip_err ? SPA3D_ERR_HIP : SPA3D_OK;
 }
@@ -1238,6 +1399,16 @@ int spa3d_set_option(spa3d_handle h, const char* name, double value) {
 int spa3d_set_loss_scale_state(spa3d_handle h, const float* state) {
   if (!h) return SPA3D_ERR_ARG;
   h->loss_scale_state = state;
+  return SPA3D_OK;
+}
+int spa3d_set_counts(spa3d_handle h, int32_t B, const int32_t* support_count, const int32_t* query_count) {
+  if (!h) return SPA3D_ERR_ARG;
+  h->has_cnt_n = h->has_cnt_q = false; h->cnt_n.clear(); h->cnt_q.clear(); h->cnt_B = 0;
+  if (!support_count && !query_count) return SPA3D_OK;  // detach
+  if (B <= 0) { h->err = "spa3d_set_counts: B must be positive"; return SPA3D_ERR_ARG; }
+  h->cnt_B = B;
+  if (support_count) { h->cnt_n.assign(support_count, support_count + B); h->has_cnt_n = true; }
+  if (query_count) { h->cnt_q.assign(query_count, query_count + B); h->has_cnt_q = true; }
   return SPA3D_OK;
 }
 int spa3d_grad_segments(spa3d_handle h, int64_t* bounds4) {

@@ -2,6 +2,7 @@
 
   prepare_3d_batch                         data_loader.py:56-110   support/query split + query-point sampling
   convert_predictions_to_tapvid3d_format   evaluate_tapvid3d.py:39-59
+  collate_ragged / split_ragged            evaluate_tapvid3d.py:318-348 as batches of clips with differing track / query counts
   load_checkpoint / save_checkpoint        inference.py:450-508, evaluate_tapvid3d.py:247-285 / train.py:389-393 (a stub upstream)
 
 Plain NumPy / torch glue: no arithmetic worth a kernel.  The metric arithmetic of TAPVid-3D stays in the un-vendored
@@ -56,6 +57,84 @@ def convert_predictions_to_tapvid3d_format(predictions, query_points=None):
   pred_tracks = predictions.tracks.detach().float().cpu().numpy()[0]
   logits = predictions.visible_logits.detach().float().cpu().numpy()[0, :, :, 0]
   return np.transpose(pred_tracks, (1, 0, 2)), np.transpose(logits <= 0.0, (1, 0))
+
+
+# ------------------------------------------------------------------------------------------------ ragged batches
+# keys whose second dimension is the support-track axis / the query axis of a [B, ...] batch
+SUPPORT_KEYS = ('support_tracks', 'support_tracks_visible', 'dino_features', 'depth_features')
+QUERY_KEYS = ('query_points', 'query_tracks', 'query_tracks_visible')
+
+
+def validate_counts(counts, B: int, limit: int, name: str, minimum: int):
+  """Per-sample counts of a ragged batch (include/spa3d.h, spa3d_set_counts) as a list of B ints in [minimum, limit]; None stays None.
+  ValueError otherwise -- the library would refuse the same values with SPA3D_ERR_ARG."""
+  if counts is None:
+    return None
+  vals = counts.detach().cpu().reshape(-1).tolist() if isinstance(counts, torch.Tensor) else list(np.asarray(counts).reshape(-1).tolist())
+  if len(vals) != B:
+    raise ValueError(f'{name} must have one entry per sample (B = {B}), got {len(vals)}')
+  out = []
+  for i, v in enumerate(vals):
+    if int(v) != v:
+      raise ValueError(f'{name}[{i}] = {v!r} is not an integer')
+    v = int(v)
+    if v < minimum or v > limit:
+      raise ValueError(f'{name}[{i}] = {v} is outside [{minimum}, {limit}]')
+    out.append(v)
+  return out
+
+
+def collate_ragged(samples, pad_value: float = 0.0):
+  """A list of per-clip dicts (support keys [n_b, T, ...], query keys [q_b, ...], `boundary_frame` a scalar or [1]; no batch axis) -> one
+  padded batch ([B, max n_b, T, ...], [B, max q_b, ...]) with `support_count` / `query_count` (int32 [B]).  Rows at or beyond a count are
+  padding (`pad_value`): the library never reads them.  Every clip carries the same keys and the same T; tensors stay on their device."""
+  if not samples:
+    raise ValueError('collate_ragged needs at least one sample')
+  keys = [k for k in samples[0] if k not in ('support_count', 'query_count')]
+  for s in samples:
+    if sorted(k for k in s if k not in ('support_count', 'query_count')) != sorted(keys):
+      raise ValueError('every sample of a ragged batch must carry the same keys')
+  ns = [int(torch.as_tensor(s['support_tracks']).shape[0]) for s in samples] if 'support_tracks' in keys else None
+  qs = [int(torch.as_tensor(s['query_points']).shape[0]) for s in samples] if 'query_points' in keys else None
+  if ns is not None and min(ns) < 1:
+    raise ValueError('every sample needs at least one support track')
+  batch = {}
+  for k in keys:
+    ts = [torch.as_tensor(s[k]) for s in samples]
+    if k == 'boundary_frame':
+      batch[k] = torch.stack([t.reshape(()).to(torch.int32) for t in ts])
+      continue
+    counts = ns if k in SUPPORT_KEYS else (qs if k in QUERY_KEYS else None)
+    if counts is None:
+      batch[k] = torch.stack(ts)
+      continue
+    if any(int(t.shape[0]) != c for t, c in zip(ts, counts)) or any(t.shape[1:] != ts[0].shape[1:] for t in ts):
+      raise ValueError(f'{k}: leading dimension must be the clip\'s own count and the remaining shape equal across clips')
+    out = torch.full((len(ts), max(max(counts), 1)) + tuple(ts[0].shape[1:]), pad_value, dtype=ts[0].dtype, device=ts[0].device)
+    for i, (t, c) in enumerate(zip(ts, counts)):
+      out[i, :c] = t
+    batch[k] = out
+  dev = batch['support_tracks'].device if 'support_tracks' in batch else batch['query_points'].device
+  if 'boundary_frame' in batch:
+    batch['boundary_frame'] = batch['boundary_frame'].to(dev)  # per-clip scalars are often host values; the batch lives on one device
+  if ns is not None:
+    batch['support_count'] = torch.tensor(ns, dtype=torch.int32, device=dev)
+  if qs is not None:
+    batch['query_count'] = torch.tensor(qs, dtype=torch.int32, device=dev)
+  return batch
+
+
+def split_ragged(results, batch):
+  """Back to per-clip views: `results` is a TrackAutoEncoderResults-like object (tensor attributes with leading [B, Q]) or a dict of
+  such tensors; returns a list of B dicts whose tensors are the views [q_b, ...] of the live rows."""
+  if isinstance(results, dict):
+    fields = {k: v for k, v in results.items() if isinstance(v, torch.Tensor)}
+  else:
+    fields = {k: v for k, v in vars(results).items() if isinstance(v, torch.Tensor)}
+  B = next(iter(fields.values())).shape[0]
+  Q = next(iter(fields.values())).shape[1]
+  qc = validate_counts(batch.get('query_count'), B, Q, 'query_count', 0) or [Q] * B
+  return [{k: v[i, :qc[i]] for k, v in fields.items()} for i in range(B)]
 
 
 # ------------------------------------------------------------------------------------------------ checkpoints

@@ -14,6 +14,7 @@ include/spa3d.h; PyTorch only owns device memory and the stream.  There is no CP
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import dataclasses
 import math
@@ -22,6 +23,7 @@ from typing import Any, Dict, Optional
 import torch
 
 from . import _lib
+from .data import validate_counts
 
 
 # ------------------------------------------------------------------------------------------------
@@ -53,6 +55,7 @@ class TrackAutoEncoderDecoderContext:
   query_points: torch.Tensor  # [B,Q,4] (t,x,y,z)
   query_frame: torch.Tensor  # int32 [B,Q] = round(t)
   boundary_frame: Optional[torch.Tensor]
+  query_count: Any = None  # ragged batch: live queries per sample ([B] ints), None = all Q
 
   @property
   def decoder_query(self):  # [B,Q,192] -- materialised on demand (ta:28-37)
@@ -77,6 +80,23 @@ def sinusoidal_embedding(x: torch.Tensor, num_frequencies: int = 32) -> torch.Te
 
 def _stream(t: torch.Tensor):
   return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+
+
+@contextlib.contextmanager
+def _counts_on(h, b):
+  """States the per-sample counts that _marshal found in the batch (b.counts) on the handle for the calls inside the block and detaches
+  them afterwards, so that a later plain batch on the same handle is not affected."""
+  cn, cq = getattr(b, 'counts', (None, None))
+  if cn is None and cq is None:
+    yield
+    return
+  lib = _lib.load()
+  arr = lambda v: (C.c_int32 * len(v))(*v) if v is not None else None
+  _lib.check(lib.spa3d_set_counts(h, b.B, arr(cn), arr(cq)), h, 'spa3d_set_counts')  # (the library copies the entries)
+  try:
+    yield
+  finally:
+    lib.spa3d_set_counts(h, 0, None, None)
 
 
 def _require_cuda(t: torch.Tensor, name: str):
@@ -243,7 +263,7 @@ class TrackAutoEncoder3D:
     return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.to(torch.float32).contiguous()
 
   def _marshal(self, inputs, dino_dim, depth_dim, need_support=True, need_query=True, targets=False, discretize=True,
-               noise=None, query_points=None):
+               noise=None, query_points=None, query_count=None):
     keep = []  # keeps converted tensors alive until the call was enqueued
     b = _lib.Batch()
     st = inputs.get('support_tracks')
@@ -304,6 +324,12 @@ class TrackAutoEncoder3D:
         raise ValueError(f'query_tracks must be {(b.B, b.Q, To, self._nc)} and query_tracks_visible {(b.B, b.Q, To, 1)}')
       keep += [qt, qv]
       b.query_tracks, b.query_tracks_visible = qt.data_ptr(), qv.data_ptr()
+    # ragged batch: optional per-sample counts (rows at or beyond a count are padding the library never reads); _counts_on states them
+    cn = validate_counts(inputs.get('support_count'), b.B, b.N, 'support_count', 1) if need_support else None
+    cq = validate_counts(query_count if query_count is not None else inputs.get('query_count'), b.B, b.Q, 'query_count', 0) if need_query else None
+    if (cn is not None or cq is not None) and self._kind == 1:
+      raise ValueError('support_count / query_count are not supported by the 2-D model')
+    b.counts = (cn, cq)
     return b, keep
 
   def default_query_grid(self, support_tracks):
@@ -361,8 +387,9 @@ class TrackAutoEncoder3D:
     lat = torch.empty(b.B, self.num_latent_tokens, self.latent_token_dim, dtype=torch.float32, device=dev)
     self._chunk_options(h, None)
     ws = self._workspace(h, b.B, b.N, 1, b.T, False, dev)
-    _lib.check(_lib.load().spa3d_encode(h, flat.data_ptr(), C.byref(b), lat.data_ptr(), ws.data_ptr(), ws.numel(), _stream(flat)),
-               h, 'spa3d_encode')
+    with _counts_on(h, b):
+      _lib.check(_lib.load().spa3d_encode(h, flat.data_ptr(), C.byref(b), lat.data_ptr(), ws.data_ptr(), ws.numel(), _stream(flat)),
+                 h, 'spa3d_encode')
     return lat
 
   def get_decoder_context(self, inputs):
@@ -371,7 +398,7 @@ class TrackAutoEncoder3D:
     if qp is None:
       qp = self.default_query_grid(inputs['support_tracks'])
     qp = qp.to(torch.float32)
-    return TrackAutoEncoderDecoderContext(qp, torch.round(qp[..., 0]).to(torch.int32), inputs.get('boundary_frame'))
+    return TrackAutoEncoderDecoderContext(qp, torch.round(qp[..., 0]).to(torch.int32), inputs.get('boundary_frame'), inputs.get('query_count'))
 
   def decode(self, variables, latents, decoder_context, discretize: bool = True, noise=None):
     """TrackAutoEncoder3D.decode (3d:248-307)."""
@@ -381,15 +408,16 @@ class TrackAutoEncoder3D:
     flat = self.flat_from_tree(params)
     dev = flat.device
     b, keep = self._marshal({}, dino, depth, need_support=False, discretize=discretize, noise=noise,
-                            query_points=decoder_context.query_points)
+                            query_points=decoder_context.query_points, query_count=getattr(decoder_context, 'query_count', None))
     lat = self._f32(latents, 'latents')
     if tuple(lat.shape) != (b.B, self.num_latent_tokens, self.latent_token_dim):
       raise ValueError('latents must be [B, num_latent_tokens, latent_token_dim]')
     self._chunk_options(h, b.Q)
     res, out = self._alloc_outputs(b.B, b.Q, dev)
     ws = self._workspace(h, b.B, 1, b.Q, 1, False, dev)
-    _lib.check(_lib.load().spa3d_decode(h, flat.data_ptr(), C.byref(b), lat.data_ptr(), C.byref(out), ws.data_ptr(), ws.numel(),
-                                        _stream(flat)), h, 'spa3d_decode')
+    with _counts_on(h, b):
+      _lib.check(_lib.load().spa3d_decode(h, flat.data_ptr(), C.byref(b), lat.data_ptr(), C.byref(out), ws.data_ptr(), ws.numel(),
+                                          _stream(flat)), h, 'spa3d_decode')
     return res
 
   def _alloc_outputs(self, B, Q, dev):
@@ -410,8 +438,9 @@ class TrackAutoEncoder3D:
     self._chunk_options(h, b.Q)
     res, out = self._alloc_outputs(b.B, b.Q, dev)
     ws = self._workspace(h, b.B, b.N, b.Q, b.T, False, dev)
-    _lib.check(_lib.load().spa3d_forward(h, flat.data_ptr(), C.byref(b), C.byref(out), ws.data_ptr(), ws.numel(), _stream(flat)),
-               h, 'spa3d_forward')
+    with _counts_on(h, b):
+      _lib.check(_lib.load().spa3d_forward(h, flat.data_ptr(), C.byref(b), C.byref(out), ws.data_ptr(), ws.numel(), _stream(flat)),
+                 h, 'spa3d_forward')
     return res
 
   def apply(self, variables, *args, rngs=None, method=None, **kw):
@@ -445,9 +474,10 @@ class TrackAutoEncoder3D:
       res, out = self._alloc_outputs(b.B, b.Q, dev)
       outp = C.byref(out)
     ws = self._workspace(h, b.B, b.N, b.Q, b.T, True, dev)
-    _lib.check(_lib.load().spa3d_loss_and_grads(h, flat.data_ptr(), C.byref(b), float(denom), grads_flat.data_ptr(),
-                                                1 if accumulate else 0, loss3.data_ptr(), outp, ws.data_ptr(), ws.numel(),
-                                                _stream(flat)), h, 'spa3d_loss_and_grads')
+    with _counts_on(h, b):
+      _lib.check(_lib.load().spa3d_loss_and_grads(h, flat.data_ptr(), C.byref(b), float(denom), grads_flat.data_ptr(),
+                                                  1 if accumulate else 0, loss3.data_ptr(), outp, ws.data_ptr(), ws.numel(),
+                                                  _stream(flat)), h, 'spa3d_loss_and_grads')
     ld = {'total_loss': loss3[0], 'position_loss': loss3[1], 'visible_loss': loss3[2]}
     return ld, self.tree_from_flat(grads_flat, dino, depth), res
 
@@ -471,7 +501,9 @@ def compute_loss_3d(predictions: TrackAutoEncoderResults, targets, l1_weight: fl
   vl = predictions.visible_logits.to(torch.float32).contiguous()
   out = _lib.Outputs(t32.data_ptr(), vl.data_ptr(), None, None)
   loss = torch.empty(12, dtype=torch.float32, device=tr.device)
-  _lib.check(lib.spa3d_loss(h, C.byref(b), C.byref(out), float(denom), loss.data_ptr(), _stream(tr)), h, 'spa3d_loss')
+  b.counts = (None, validate_counts(targets.get('query_count'), B, Q, 'query_count', 0))  # ragged batch: live queries only
+  with _counts_on(h, b):
+    _lib.check(lib.spa3d_loss(h, C.byref(b), C.byref(out), float(denom), loss.data_ptr(), _stream(tr)), h, 'spa3d_loss')
   pos, vis = loss[1], loss[2]
   return {'total_loss': l1_weight * pos + bce_weight * vis, 'position_loss': pos, 'visible_loss': vis}
 

@@ -38,14 +38,21 @@ def _collectives_on(group=None, force=False) -> bool:
   return force or dist.get_world_size(group) > 1
 
 
-def global_visible_count(visible: torch.Tensor, group=None, force=False, check_equal_batches: bool = False) -> float:
+def global_visible_count(visible: torch.Tensor, group=None, force=False, check_equal_batches: bool = False, query_count=None) -> float:
   """max(sum(query_tracks_visible) over ALL ranks, 1): both loss terms divide by the batch-global visible count
   (train.py:111-113,119-121), so under data parallelism it is one scalar all-reduce BEFORE the backward.  The C-ABI takes the
   denominator by value, so this is one 4-byte device->host read per step (the only host sync of the multi-GPU step).
   `check_equal_batches`: the same collective also carries (B_local, B_local^2), so EVERY rank checks EVERY step that all ranks hold the same
   local batch (world * sum(B^2) == (sum B)^2) and all of them raise together -- a check issued by only some ranks (e.g. on a cache miss)
-  would leave the others in the next collective and hang the job instead."""
+  would leave the others in the next collective and hang the job instead.
+  `query_count` (ragged batch, [B]): only the first query_count[b] queries of sample b are counted; the padded rows are not read as
+  numbers (they may hold NaN)."""
   b = float(visible.shape[0])
+  if query_count is not None:
+    from .data import validate_counts
+    qc = validate_counts(query_count, visible.shape[0], visible.shape[1], 'query_count', 0)
+    live = torch.arange(visible.shape[1], device=visible.device)[None, :] < torch.tensor(qc, device=visible.device)[:, None]
+    visible = torch.where(live.reshape(live.shape + (1,) * (visible.dim() - 2)), visible, torch.zeros((), dtype=visible.dtype, device=visible.device))
   s = torch.stack([visible.to(torch.float32).sum(), visible.new_tensor(b, dtype=torch.float32), visible.new_tensor(b * b, dtype=torch.float32)])
   if _collectives_on(group, force):
     dist.all_reduce(s, op=dist.ReduceOp.SUM, group=group)
@@ -245,7 +252,8 @@ class TrainState:
 
   def train_step(self, batch, discretize: bool = True, noise=None):
     multi = self.world > 1 or self.force
-    denom = global_visible_count(batch['query_tracks_visible'], self.pg, self.force, check_equal_batches=True) if multi else 0.0
+    denom = global_visible_count(batch['query_tracks_visible'], self.pg, self.force, check_equal_batches=True,
+                                 query_count=batch.get('query_count')) if multi else 0.0
     if multi and discretize and noise is None:
       noise = self.rank_noise(batch['query_tracks_visible'].shape[0])
     ld = self._compute(self.params, batch, self.grads, denom, discretize, noise)
@@ -290,7 +298,8 @@ class TrainState:
     loss terms are normalised by the GLOBAL visible count and summed over ranks, exactly as the training loss is, and the rank
     takes its slice of the global discretisation noise; predictions are the rank's own."""
     multi = self.world > 1 or self.force
-    denom = global_visible_count(batch['query_tracks_visible'], self.pg, self.force, check_equal_batches=True) if multi else 0.0
+    denom = global_visible_count(batch['query_tracks_visible'], self.pg, self.force, check_equal_batches=True,
+                                 query_count=batch.get('query_count')) if multi else 0.0
     if multi and discretize and noise is None:
       noise = self.rank_noise(batch['query_tracks_visible'].shape[0])
     ld, preds = self._evaluate(self.params, batch, denom, discretize, noise)

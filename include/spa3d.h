@@ -197,6 +197,32 @@ int spa3d_set_option(spa3d_handle h, const char* name, double value);
  * after 200 finite steps. */
 int spa3d_set_loss_scale_state(spa3d_handle h, const float* state);
 
+/* Ragged batches: per-sample counts of live support tracks and live queries.  The tensors keep their padded layouts ([B,N,T,..], [B,Q,..]);
+ * rows at or beyond a sample's count are padding: never read (they may hold NaN) and never contributing, in any entry point.
+ * support_count / query_count: HOST arrays of B entries (they size launches: no device read-back, no extra synchronisation), copied into the
+ * handle by this call (the caller may free them at once) and read by every later call on the handle; NULL = all N / all Q; both NULL detaches
+ * (B is then ignored).  A call whose batch has another B than the stored one, 1 <= support_count[b] <= N or 0 <= query_count[b] <= Q violated,
+ * counts together with "track_chunk" / "query_chunk", or counts on a model_kind 1 handle: SPA3D_ERR_ARG before the first launch, with a
+ * message in spa3d_last_error.  spa3d_decode reads the query counts only, spa3d_encode the support counts only, spa3d_loss the query counts.
+ *   Results: the live rows of every output and the latents are what the same handle gives for the sample alone, cropped to its counts (same
+ * noise[b], boundary_frame[b]; bit for bit when the sample is alone in its chunk, up to the order of summation in a packed chunk, see below); output rows of padded queries are written as 0; loss and gradients are those of the live rows
+ * (denom <= 0: max(sum of query_tracks_visible over the live queries, 1)) -- the sum over the samples of single-sample
+ * spa3d_loss_and_grads(denom = D, accumulate = 1) calls.  A sample with query_count 0 is encoded and adds no loss and no gradient.
+ *   Work follows the live counts, not B x N.  The samples of a sample chunk are PACKED: the track encoder runs once over the chunk's
+ * sum n_b live tracks, the K/V projection of tracks_to_latents over those sum n_b rows and its cross attention over each sample's own n_b keys
+ * (one launch of the chunked-key kernels with per-sample key offsets; the fp32 parity mode and attn_impl 1 run that attention sample by
+ * sample), the latent stacks over the chunk's samples, the readout over the sum q_b live queries; only cheap per-row kernels (key mask,
+ * sequence assembly, head / loss) are issued per sample.  The live rows of a chunk of several samples are copied once into packed buffers
+ * in the workspace (tracks, visibility, DINO / depth planes, query points); a chunk of ONE sample addresses its rows in place.
+ * spa3d_plan_stats reports the sums: out4[1] = sum n_b x (T + 1), out4[3] = sum q_b.  "chunk", "prune", "det_grads", "poison" and the fp16
+ * loss scale work as in a uniform call (the chunk size that fits is found with the live counts); "ro_share" applies to chunks of one sample
+ * only -- a packed chunk runs the first readout block densely (its slot plan is per (sample, frame) and is not carried over to packed
+ * queries yet).  Counts that all equal (N, Q) are the uniform call, bit for bit.  Results of a packed chunk equal the single-sample ones up to
+ * the order of summation (GEMM kernels are picked by row count).
+ * spa3d_workspace_bytes of the padded shape (any chunk >= 1) stays a sufficient bound: the sizing pass of a ragged call walks the live
+ * counts and takes the largest chunk that fits; a single sample needs no packed copy. */
+int spa3d_set_counts(spa3d_handle h, int32_t B, const int32_t* support_count, const int32_t* query_count);
+
 /* Overlapping the data-parallel gradient all-reduce with the backward (no reference counterpart: the reference is single-device, SURVEY 2;
  * the split is SURVEY 8(e)'s).  Parameter gradients accumulate over the call's sample chunks, so a leaf is final only in the LAST chunk's
  * backward, in reverse graph order.  spa3d_grad_segments: bounds4 = {0, b1, b2, n} (floats) cut the flat gradient buffer into
