@@ -38,6 +38,12 @@ class Outputs(C.Structure):
               ('latents', C.c_void_p)]
 
 
+class Scores(C.Structure):
+  """spa3d_scores (include/spa3d.h): thresholds by value, device pointers for the optional sample scale and the three result tensors."""
+  _fields_ = [('num_thresholds', C.c_int32), ('thresholds', C.c_float * 8), ('sample_scale', C.c_void_p), ('query_stats', C.c_void_p),
+              ('sample_stats', C.c_void_p), ('frame_err', C.c_void_p)]
+
+
 _SIGS = {
     'spa3d_version': (C.c_char_p, []),
     'spa3d_create': (C.c_int, [C.POINTER(Config), C.POINTER(C.c_void_p)]),
@@ -54,6 +60,9 @@ _SIGS = {
     'spa3d_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Batch), C.POINTER(Outputs), C.c_void_p, C.c_int64,
                                 C.c_void_p]),
     'spa3d_loss': (C.c_int, [C.c_void_p, C.POINTER(Batch), C.POINTER(Outputs), C.c_float, C.c_void_p, C.c_void_p]),
+    'spa3d_score': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Batch), C.POINTER(Scores), C.POINTER(Outputs), C.c_void_p, C.c_int64,
+                              C.c_void_p]),
+    'spa3d_score_from_preds': (C.c_int, [C.c_void_p, C.POINTER(Batch), C.POINTER(Outputs), C.POINTER(Scores), C.c_void_p]),
     'spa3d_loss_and_grads': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Batch), C.c_float, C.c_void_p, C.c_int32,
                                        C.c_void_p, C.POINTER(Outputs), C.c_void_p, C.c_int64, C.c_void_p]),
     'spa3d_adamw_step': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_int64,

@@ -31,7 +31,7 @@ def _stale(out, deps):
 
 def build(force: bool = False, verbose: bool = True) -> str:
   hipcc = _hipcc()
-  hdrs = [os.path.join(CSRC, 'common.hpp'), os.path.join(CSRC, 'gemm_plan.hpp'), os.path.join(CSRC, 'tn_args.hpp'), os.path.join(CSRC, 'ablate.inc'), os.path.join(CSRC, 'attn_common.hpp'), os.path.join(HERE, '..', 'include', 'spa3d.h')]
+  hdrs = [os.path.join(CSRC, 'common.hpp'), os.path.join(CSRC, 'gemm_plan.hpp'), os.path.join(CSRC, 'tn_args.hpp'), os.path.join(CSRC, 'ablate.inc'), os.path.join(CSRC, 'attn_common.hpp'), os.path.join(CSRC, 'score_row.hpp'), os.path.join(HERE, '..', 'include', 'spa3d.h')]
   objdir = os.path.join(HERE, 'build')
   os.makedirs(objdir, exist_ok=True)
   srcs = [s for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]

@@ -8,6 +8,7 @@
 #include "../../include/spa3d.h"
 #include "ablate.inc"  // every work-skipping diagnostic mask, all 0 in libspa3d_hip.so
 #include "gemm_plan.hpp"  // GemmDesc and the kernel choice (host-only)
+#include "score_row.hpp"  // per-track score arithmetic (host- and device-callable)
 
 // One translation unit is compiled for exactly ONE 16-bit activation type: bf16 (default) or IEEE fp16 (-DSPA_F16=1, BASELINE
 // cfg#5).  The raw 16-bit storage type is `bf16_t` (unsigned short) in both builds; what differs -- the two conversions, the MFMA
@@ -151,6 +152,16 @@ __device__ __forceinline__ void grad_add_q(const DetCfg& dc, float* p, long long
 // ------------------------------------------------------------------------------------------
 // host-side context
 // ------------------------------------------------------------------------------------------
+// One launch of score_rows_kernel (kernels.hip): rows [row0, row0 + nq) of the [B * Q] query rows.  Targets, sample scale, query_stats and frame_err are the
+// caller's whole tensors, indexed by the global row; the predictions come either from this launch's head rows (head != null: [nq][4 * T], coordinate-major,
+// row 0 = global row row0) or from the caller's split tensors (tracks [B * Q][T][NC], vlog [B * Q][T]).  The thresholds travel by value.
+struct ScoreArgs {
+  const float* head; const float* tracks; const float* vlog;
+  const float* tgt; const float* tvis; const float* scale;  // scale: device [B] or null
+  float* qstats; float* frame_err;                          // frame_err: [B * Q][T] or null
+  int64_t nq, row0; int Q, T, NC; ScoreThr thr;
+};
+
 struct Leaf {
   std::string name;
   int ndim;
@@ -355,6 +366,8 @@ void k_loss_fwd(spa3d_ctx*, const float* head, int64_t nq, int T_, const float* 
                 float* clog, float* sums, unsigned* poison, int NC = 3);
 void k_loss_from_preds(spa3d_ctx*, const float* tracks, const float* vlog, int64_t n, const float* tgt, const float* tvis, float* sums,
                        unsigned* poison, int NC = 3);
+void k_score_rows(spa3d_ctx*, const ScoreArgs& a);
+void k_score_reduce(spa3d_ctx*, const float* qstats, int64_t B, int Q, int K, double* out /*[B][8 + 4K]*/);
 template <typename T> void k_loss_bwd(spa3d_ctx*, const float* head, int64_t nq, int T_, const float* tgt, const float* tvis,
                                       const float* denom_dev, float l1w, float bcew, T* dhead, int NC = 3, const float* scale_dev = nullptr);
 void k_vis_count(spa3d_ctx*, const float* tvis, int64_t n, float* out, unsigned* poison);

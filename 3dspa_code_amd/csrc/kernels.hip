@@ -1613,6 +1613,85 @@ void k_loss_from_preds(spa3d_ctx* c, const float* tracks, const float* vlog, int
   loss_from_preds_kernel<<<g, 256, 0, c->stream>>>(tracks, vlog, n, tgt, tvis, sums, poison, NC);
   SPA_LAUNCH_CHECK(c);
 }
+// ---------------------------------------------------------------------------------------------
+// Per-track scores (spa3d_score / spa3d_score_from_preds; arithmetic and summation order: score_row.hpp)
+// One wave per query row, four rows per workgroup.  Lanes stride over the frames: in the head form every coordinate block of the row is read
+// coalesced, in the split form a wave reads the row's contiguous [T][NC] span.  The row's sums are merged by the xor butterfly, so every lane
+// ends with the same bits, and lanes 0 .. S-1 store one stat each.  No atomics: the same inputs give the same bits on every run, and the two
+// input forms run the same instructions on the same values.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ void score_acc_xor(ScoreAcc& a, int o, int K) {
+  ScoreAcc b;
+  b.n_vis = __shfl_xor(a.n_vis, o, 64); b.s_e1 = __shfl_xor(a.s_e1, o, 64); b.s_e2 = __shfl_xor(a.s_e2, o, 64); b.mx = __shfl_xor(a.mx, o, 64);
+  b.bce = __shfl_xor(a.bce, o, 64); b.occ = __shfl_xor(a.occ, o, 64); b.n_pv = __shfl_xor(a.n_pv, o, 64);
+#pragma unroll
+  for (int k = 0; k < SCORE_MAX_K; ++k) {
+    if (k < K) {  // wave-uniform
+      b.w[k] = __shfl_xor(a.w[k], o, 64); b.tp[k] = __shfl_xor(a.tp[k], o, 64); b.fp[k] = __shfl_xor(a.fp[k], o, 64); b.fn[k] = __shfl_xor(a.fn[k], o, 64);
+    } else {
+      b.w[k] = b.tp[k] = b.fp[k] = b.fn[k] = 0.f;
+    }
+  }
+  score_acc_merge(a, b, K);
+}
+__global__ __launch_bounds__(256) void score_rows_kernel(const ScoreArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= a.nq) return;  // whole waves leave: no shuffle partner is lost
+  const int64_t gr = a.row0 + r;
+  const int T = a.T, NC = a.NC;
+  const ScoreThr thr = score_thr_scaled(a.thr, a.scale ? a.scale[gr / a.Q] : 1.f);
+  const float *p, *lg; long sp, st;  // sp: stride between the coordinates of a frame, st: between frames
+  if (a.head) { p = a.head + r * 4 * T; lg = p + (int64_t)NC * T; sp = T; st = 1; }
+  else { p = a.tracks + gr * T * NC; lg = a.vlog + gr * T; sp = 1; st = NC; }
+  const float* g = a.tgt + gr * T * NC;
+  const float* y = a.tvis + gr * T;
+  ScoreAcc acc;
+  score_acc_init(acc);
+  for (int t = lane; t < T; t += 64) {
+    const float e2 = score_acc_frame(acc, p + (long)t * st, sp, g + (long)t * NC, 1, NC, lg[t], y[t], thr);
+    if (a.frame_err) a.frame_err[gr * T + t] = e2;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) score_acc_xor(acc, o, thr.K);
+  const int S = score_row_len(thr.K);
+  if (lane < S) a.qstats[gr * S + lane] = score_acc_slot(acc, lane, T);
+}
+void k_score_rows(spa3d_ctx* c, const ScoreArgs& a) {
+  if (c->dry || a.nq <= 0) return;
+  score_rows_kernel<<<(unsigned)cdiv(a.nq, 4), 256, 0, c->stream>>>(a);
+  SPA_LAUNCH_CHECK(c);
+}
+// sample_stats[b][s] (double) = the sample's Q rows of query_stats reduced in a fixed order: thread i takes rows i, i + 256, ..., then a tree
+// over the 256 partials.  Slot 3 is a max; padded rows hold zeros and add nothing.  One workgroup per (sample, stat).
+__global__ __launch_bounds__(256) void score_reduce_kernel(const float* __restrict__ qstats, int Q, int S, double* __restrict__ out) {
+  __shared__ double red[256];
+  const int64_t b = blockIdx.x / S; const int s = (int)(blockIdx.x - b * S);
+  const float* base = qstats + b * Q * S + s;
+  const bool is_max = s == 3;
+  double v = 0.0;
+  for (int q = threadIdx.x; q < Q; q += 256) {
+    const double x = (double)base[(int64_t)q * S];
+    v = is_max ? (x > v ? x : v) : v + x;
+  }
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) {
+      const double x = red[threadIdx.x + o], w = red[threadIdx.x];
+      red[threadIdx.x] = is_max ? (x > w ? x : w) : w + x;
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[blockIdx.x] = red[0];
+}
+void k_score_reduce(spa3d_ctx* c, const float* qstats, int64_t B, int Q, int K, double* out) {
+  if (c->dry || B <= 0) return;
+  const int S = score_row_len(K);
+  score_reduce_kernel<<<(unsigned)(B * S), 256, 0, c->stream>>>(qstats, Q, S, out);
+  SPA_LAUNCH_CHECK(c);
+}
+
 __global__ __launch_bounds__(256) void vis_count_kernel(const float* __restrict__ v, int64_t n, float* out, unsigned* poison) {
   __shared__ float red[4];
   float s = 0.f;

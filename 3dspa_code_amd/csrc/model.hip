@@ -20,6 +20,7 @@ struct RunArgs {
   int mode; const float* P; const spa3d_batch* b; float denom; float* G; int accumulate; float* loss3; spa3d_outputs* out;
   const float* latents_in; float* latents_out; int chunk;  // chunk: fixed Bc (>0) or 0 = as large as fits
   const int32_t* cn; const int32_t* cq;  // ragged batch (spa3d_set_counts): host arrays [B] of live support tracks / live queries per sample; null = all N / all Q
+  const spa3d_scores* score;  // spa3d_score: per-track scores of every emitted query row, straight from the head (emit_scores); null everywhere else
 };
 
 namespace SPA_NS {
@@ -898,9 +899,43 @@ static void poison_from(spa3d_ctx* c, int64_t mark) {
   if (o < c->ar.cap) (void)hipMemsetAsync(c->ar.base + o, 0xFF, (size_t)(c->ar.cap - o), c->stream);
 }
 
+// the launch arguments every score launch of a call shares (the caller's whole tensors; the thresholds by value)
+static ScoreArgs score_args(const spa3d_batch* b, const spa3d_scores* sc, int To, int NC) {
+  ScoreArgs s{};
+  s.tgt = b->query_tracks; s.tvis = b->query_tracks_visible; s.scale = sc->sample_scale; s.qstats = sc->query_stats; s.frame_err = sc->frame_err;
+  s.Q = b->Q; s.T = To; s.NC = NC; s.thr.K = sc->num_thresholds;
+  for (int i = 0; i < SCORE_MAX_K; ++i) s.thr.t[i] = i < sc->num_thresholds ? sc->thresholds[i] : 0.f;
+  return s;
+}
+// query_stats / frame_err rows [r0, r0 + nr) of the padded queries of a ragged batch read as 0
+static void score_zero_rows(spa3d_ctx* c, const spa3d_scores* sc, int64_t r0, int64_t nr, int To) {
+  if (c->dry || nr <= 0) return;
+  const int64_t S = score_row_len(sc->num_thresholds);
+  (void)hipMemsetAsync(sc->query_stats + r0 * S, 0, (size_t)(nr * S) * 4, c->stream);
+  if (sc->frame_err) (void)hipMemsetAsync(sc->frame_err + r0 * To, 0, (size_t)(nr * To) * 4, c->stream);
+}
+// per-track scores of the queries [k.q_off, k.q_off + k.Qc) of samples [b0, b0 + k.Bc) from k.head (spa3d_score): one launch next to the output kernel
+template <typename T>
+static void emit_scores(spa3d_ctx* c, const RunArgs& a, Net<T>& net, typename Net<T>::Chunk& k, int64_t b0) {
+  const spa3d_batch* b = a.b; const int To = c->cfg.num_output_frames;
+  ScoreArgs s = score_args(b, a.score, To, net.NC);
+  if (k.packed) {  // targets and results stay in the padded layout: sample by sample, padded rows zeroed
+    for (int64_t i = 0; i < k.Bc; ++i) {
+      const int64_t r = (b0 + i) * b->Q, q0 = k.qoff[i], qs = k.qoff[i + 1] - k.qoff[i];
+      s.head = k.head + q0 * 4 * To; s.nq = qs; s.row0 = r;
+      k_score_rows(c, s);
+      score_zero_rows(c, a.score, r + qs, b->Q - qs, To);
+    }
+    return;
+  }
+  s.head = k.head; s.nq = k.Bc * k.Qc; s.row0 = b0 * b->Q + k.q_off;
+  k_score_rows(c, s);
+}
+
 // outputs and loss sums of the queries [k.q_off, k.q_off + k.Qc) of samples [b0, b0 + k.Bc) from k.head
 template <typename T>
 static void emit_outputs(spa3d_ctx* c, const RunArgs& a, Net<T>& net, typename Net<T>::Chunk& k, int64_t b0, float* sums, unsigned* poison) {
+  if (a.score) { emit_scores<T>(c, a, net, k, b0); if (!a.out) return; }  // spa3d_score(out = NULL) writes no prediction tensor at all
   const spa3d_batch* b = a.b; const int To = c->cfg.num_output_frames, NC = net.NC;
   const bool train = a.mode == MODE_TRAIN;
   if (k.packed) {  // outputs and targets stay in the padded layout: sample by sample, and the padded query rows read as 0
@@ -968,6 +1003,7 @@ static void run_sample_intra(spa3d_ctx* c, const RunArgs& a, Net<T>& net, typena
     if (a.out && a.out->tracks) (void)hipMemsetAsync(a.out->tracks + r0 * To * net.NC, 0, (size_t)(nr * To * net.NC) * 4, c->stream);
     if (a.out && a.out->visible_logits) (void)hipMemsetAsync(a.out->visible_logits + r0 * To, 0, (size_t)(nr * To) * 4, c->stream);
     if (a.out && a.out->certain_logits) (void)hipMemsetAsync(a.out->certain_logits + r0 * To, 0, (size_t)(nr * To) * 4, c->stream);
+    if (a.score) score_zero_rows(c, a.score, r0, nr, To);
   }
   if (qlive == 0) {  // no live query: no readout, no loss term, no gradient; the call's gradient segments may still end with this sample
     if (train) { net.grad_segment_done(0); net.grad_segment_done(1); }
@@ -1095,6 +1131,8 @@ void run_body(spa3d_ctx* c, const RunArgs& a, int Bc) {
     }
   }
   if (train && a.loss3) k_loss_finalize(c, sums, poison, denom_dev, L1_WEIGHT, BCE_WEIGHT, a.loss3);
+  // spa3d_score: the per-sample pooled stats, ONE launch once every (sample / query / track) chunk has written its rows of query_stats
+  if (a.score && a.score->sample_stats) k_score_reduce(c, a.score->query_stats, b->B, b->Q, a.score->num_thresholds, a.score->sample_stats);
 }
 
 // entry points of this build's 16-bit type (and of the fp32 parity path, which lives in the bf16 build only)
@@ -1334,6 +1372,53 @@ int spa3d_forward(spa3d_handle h, const float* params, const spa3d_batch* b, spa
   RunArgs a{}; a.mode = MODE_FORWARD; a.P = params; a.b = b; a.out = out;
   return run(h, a, ws, ws_bytes, stream);
 }
+// refusals of a spa3d_scores block, before any launch
+static int check_scores(spa3d_ctx* c, const spa3d_batch* b, const spa3d_scores* sc) {
+  c->err.clear();
+  if (!b || !b->query_tracks || !b->query_tracks_visible) { c->err = "score: the batch needs its targets (query_tracks, query_tracks_visible)"; return SPA3D_ERR_ARG; }
+  if (!sc || !sc->query_stats) { c->err = "score: spa3d_scores::query_stats is required"; return SPA3D_ERR_ARG; }
+  if (sc->num_thresholds < 0 || sc->num_thresholds > SCORE_MAX_K) { c->err = "score: num_thresholds = " + std::to_string(sc->num_thresholds) + " is outside [0, 8]"; return SPA3D_ERR_ARG; }
+  for (int i = 0; i < sc->num_thresholds; ++i)
+    if (!(std::isfinite(sc->thresholds[i]) && sc->thresholds[i] > 0.f)) { c->err = "score: thresholds[" + std::to_string(i) + "] must be finite and positive"; return SPA3D_ERR_ARG; }
+  return SPA3D_OK;
+}
+int spa3d_score(spa3d_handle h, const float* params, const spa3d_batch* b, spa3d_scores* scores, spa3d_outputs* out, void* ws, int64_t ws_bytes, void* stream) {
+  if (!h || !params) return SPA3D_ERR_ARG;
+  const int rc = check_scores(h, b, scores);
+  if (rc) return rc;
+  RunArgs a{}; a.mode = MODE_FORWARD; a.P = params; a.b = b; a.out = out; a.score = scores;  // the forward pass: no stash, no backward
+  return run(h, a, ws, ws_bytes, stream);
+}
+int spa3d_score_from_preds(spa3d_handle h, const spa3d_batch* b, const spa3d_outputs* preds, spa3d_scores* scores, void* stream) {
+  if (!h) return SPA3D_ERR_ARG;
+  h->hip_err = 0;
+  const int rc = check_scores(h, b, scores);
+  if (rc) return rc;
+  if (!preds || !preds->tracks || !preds->visible_logits) { h->err = "score: predictions (tracks, visible_logits) are required"; return SPA3D_ERR_ARG; }
+  if (b->B <= 0 || b->Q <= 0) { h->err = "batch: B,Q must be positive"; return SPA3D_ERR_ARG; }
+  if (h->has_cnt_q) {
+    if (h->cnt_B != b->B) { h->err = "counts were set for B = " + std::to_string(h->cnt_B) + ", this batch has B = " + std::to_string(b->B); return SPA3D_ERR_ARG; }
+    for (int i = 0; i < b->B; ++i)
+      if (h->cnt_q[i] < 0 || h->cnt_q[i] > b->Q) { h->err = "query_count[" + std::to_string(i) + "] is outside [0, Q]"; return SPA3D_ERR_ARG; }
+  }
+  h->stream = (hipStream_t)stream; h->dry = false;
+  const int To = h->cfg.num_output_frames;
+  ScoreArgs s = score_args(b, scores, To, h->cfg.model_kind == 1 ? 2 : 3);
+  s.tracks = preds->tracks; s.vlog = preds->visible_logits;
+  if (h->has_cnt_q) {  // live queries only, sample by sample; padded rows read as 0
+    for (int64_t i = 0; i < b->B; ++i) {
+      s.nq = h->cnt_q[i]; s.row0 = i * b->Q;
+      k_score_rows(h, s);
+      score_zero_rows(h, scores, s.row0 + s.nq, b->Q - s.nq, To);
+    }
+  } else {
+    s.nq = (int64_t)b->B * b->Q; s.row0 = 0;
+    k_score_rows(h, s);
+  }
+  if (scores->sample_stats) k_score_reduce(h, scores->query_stats, b->B, b->Q, scores->num_thresholds, scores->sample_stats);
+  return h->hip_err ? SPA3D_ERR_HIP : SPA3D_OK;
+}
+
 int spa3d_loss_and_grads(spa3d_handle h, const float* params, const spa3d_batch* b, float denom, float* grads, int32_t accumulate,
                          float* loss3, spa3d_outputs* out, void* ws, int64_t ws_bytes, void* stream) {
   if (!h || !params || !grads) return SPA3D_ERR_ARG;

@@ -9,6 +9,7 @@ Plain NumPy / torch glue: no arithmetic worth a kernel.  The metric arithmetic o
 `tapnet` package, as upstream."""
 from __future__ import annotations
 
+import dataclasses
 import os
 from typing import Any, Dict, Optional
 
@@ -126,7 +127,16 @@ def collate_ragged(samples, pad_value: float = 0.0):
 
 def split_ragged(results, batch):
   """Back to per-clip views: `results` is a TrackAutoEncoderResults-like object (tensor attributes with leading [B, Q]) or a dict of
-  such tensors; returns a list of B dicts whose tensors are the views [q_b, ...] of the live rows."""
+  such tensors; returns a list of B dicts whose tensors are the views [q_b, ...] of the live rows.  A TrackScores comes back as a list of B
+  TrackScores (query_stats [q_b, S], sample_stats [S], frame_err [q_b, T])."""
+  if hasattr(results, 'query_stats') and hasattr(results, 'sample_stats'):  # TrackScores: one TrackScores per clip, cut to its live rows
+    B, Q = results.query_stats.shape[:2]
+    qc = validate_counts(batch.get('query_count'), B, Q, 'query_count', 0) or [Q] * B
+    cut = lambda t, i: None if t is None else t[i, :qc[i]]
+    preds = [None] * B if results.predictions is None else [
+        dataclasses.replace(results.predictions, **{k: v[i, :qc[i]] for k, v in vars(results.predictions).items() if isinstance(v, torch.Tensor)}) for i in range(B)]
+    return [dataclasses.replace(results, query_stats=cut(results.query_stats, i), sample_stats=None if results.sample_stats is None else results.sample_stats[i],
+                                frame_err=cut(results.frame_err, i), predictions=preds[i]) for i in range(B)]
   if isinstance(results, dict):
     fields = {k: v for k, v in results.items() if isinstance(v, torch.Tensor)}
   else:
@@ -135,6 +145,25 @@ def split_ragged(results, batch):
   Q = next(iter(fields.values())).shape[1]
   qc = validate_counts(batch.get('query_count'), B, Q, 'query_count', 0) or [Q] * B
   return [{k: v[i, :qc[i]] for k, v in fields.items()} for i in range(B)]
+
+
+def save_scores_npz(path: str, coords, frame_scores, visibs, **extra):
+  """Writes per-point scores in the layout upstream's visualiser reads: TIME-major `coords` [T, N, 3], `coords_score` [T, N], `visibs` [T, N]
+  (plus whatever the caller owns: video, intrinsics, extrinsics, ...).  Inputs are the library's track-major tensors of ONE clip: coords
+  [N, T, 3], frame_scores [N, T] (e.g. TrackScores.frame_err[b], or any score derived from it), visibs [N, T] or [N, T, 1]."""
+  to_np = lambda t: t.detach().float().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t, dtype=np.float32)
+  c, s, v = to_np(coords), to_np(frame_scores), to_np(visibs)
+  if v.ndim == 3 and v.shape[-1] == 1:
+    v = v[..., 0]
+  if s.ndim == 3 and s.shape[-1] == 1:
+    s = s[..., 0]
+  if c.ndim != 3 or s.shape != c.shape[:2] or v.shape != c.shape[:2]:
+    raise ValueError(f'coords must be [N, T, C] and frame_scores / visibs [N, T]; got {c.shape}, {s.shape}, {v.shape}')
+  for k in ('coords', 'coords_score', 'visibs'):
+    if k in extra:
+      raise ValueError(f'{k!r} is written from the positional arguments')
+  np.savez(path, coords=np.ascontiguousarray(c.transpose(1, 0, 2)), coords_score=np.ascontiguousarray(s.T), visibs=np.ascontiguousarray(v.T > 0.5),
+           **{k: (t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)) for k, t in extra.items()})
 
 
 # ------------------------------------------------------------------------------------------------ checkpoints

@@ -62,6 +62,138 @@ class TrackAutoEncoderDecoderContext:
     return sinusoidal_embedding(self.query_points[..., 1:].contiguous())
 
 
+# ------------------------------------------------------------------------------------------------
+# per-track reconstruction scores (include/spa3d.h, spa3d_scores)
+# ------------------------------------------------------------------------------------------------
+SCORE_BASE_SLOTS = 8  # stats row: [n_vis, sum y e1, sum y e2, max e2 (visible), sum bce, occlusion-correct frames, predicted-visible frames, frames] + 4 per threshold
+
+
+class _ScoreProperties:
+  """Ratios of a stats tensor [..., 8 + 4K]; every denominator is clamped at 1, so a row without visible frames (or a padded row) reads 0."""
+
+  def _stats(self) -> torch.Tensor:
+    raise NotImplementedError
+
+  def _ratio(self, num, den):
+    return num / torch.clamp(den, min=1.0)
+
+  def _per_threshold(self, offset):  # [..., K]
+    s = self._stats()
+    return s[..., SCORE_BASE_SLOTS + offset::4]
+
+  @property
+  def num_visible(self):
+    return self._stats()[..., 0]
+
+  @property
+  def position_l1(self):
+    """Mean over the visible frames of sum_c |p - g|: the training loss's L1 term of this row."""
+    s = self._stats()
+    return self._ratio(s[..., 1], s[..., 0])
+
+  @property
+  def distance_mean(self):
+    s = self._stats()
+    return self._ratio(s[..., 2], s[..., 0])
+
+  @property
+  def distance_max(self):
+    return self._stats()[..., 3]
+
+  @property
+  def visible_bce(self):
+    s = self._stats()
+    return self._ratio(s[..., 4], s[..., 7])
+
+  @property
+  def occlusion_accuracy(self):
+    s = self._stats()
+    return self._ratio(s[..., 5], s[..., 7])
+
+  @property
+  def pts_within(self):
+    """[..., K]: share of the visible frames whose distance is below thresholds[k] (x the sample scale)."""
+    return self._ratio(self._per_threshold(0), self._stats()[..., 0:1])
+
+  @property
+  def jaccard(self):
+    """[..., K]: TP / (TP + FP + FN), the TAP-Vid Jaccard counts at fixed metric thresholds (not tapnet's TAPVid-3D metric)."""
+    tp, fp, fn = self._per_threshold(1), self._per_threshold(2), self._per_threshold(3)
+    return self._ratio(tp, tp + fp + fn)
+
+  @property
+  def average_jaccard(self):
+    j = self.jaccard
+    return j.mean(-1) if j.shape[-1] else torch.zeros(j.shape[:-1], dtype=j.dtype, device=j.device)
+
+  @property
+  def average_pts_within(self):
+    w = self.pts_within
+    return w.mean(-1) if w.shape[-1] else torch.zeros(w.shape[:-1], dtype=w.dtype, device=w.device)
+
+
+@dataclasses.dataclass
+class SampleScores(_ScoreProperties):
+  """Per-sample scores from the pooled counts of the sample's live queries."""
+  stats: torch.Tensor  # [B, 8 + 4K] f64
+  thresholds: tuple = ()
+
+  def _stats(self):
+    return self.stats
+
+
+@dataclasses.dataclass
+class TrackScores(_ScoreProperties):
+  """What TrackAutoEncoder3D.score / score_predictions return: the raw tensors of spa3d_scores and, as properties, the per-query ratios
+  (position_l1, distance_mean, distance_max, occlusion_accuracy, pts_within[k], jaccard[k], average_jaccard); `.sample` gives the same per sample."""
+  query_stats: torch.Tensor  # [B, Q, 8 + 4K] f32; rows of padded queries are 0
+  sample_stats: Optional[torch.Tensor]  # [B, 8 + 4K] f64
+  frame_err: Optional[torch.Tensor]  # [B, Q, T] f32 Euclidean error of every frame, or None
+  thresholds: tuple = ()
+  predictions: Optional['TrackAutoEncoderResults'] = None  # score(return_predictions=True)
+
+  def _stats(self):
+    return self.query_stats
+
+  @property
+  def sample(self) -> SampleScores:
+    if self.sample_stats is None:
+      raise ValueError('these scores carry no sample_stats')
+    return SampleScores(self.sample_stats, self.thresholds)
+
+
+def _check_thresholds(thresholds):
+  thr = tuple(float(t) for t in thresholds)
+  if len(thr) > 8:
+    raise ValueError(f'at most 8 thresholds, got {len(thr)}')
+  for t in thr:
+    if not (math.isfinite(t) and t > 0):
+      raise ValueError(f'thresholds must be finite and positive, got {t!r}')
+  return thr
+
+
+def _alloc_scores(thr, B, Q, To, dev, sample_scale, frame_errors):
+  """Result tensors and the spa3d_scores block that points at them; the second value keeps what the block references alive."""
+  S = SCORE_BASE_SLOTS + 4 * len(thr)
+  res = TrackScores(torch.empty(B, Q, S, dtype=torch.float32, device=dev), torch.empty(B, S, dtype=torch.float64, device=dev),
+                    torch.empty(B, Q, To, dtype=torch.float32, device=dev) if frame_errors else None, thr)
+  sc = _lib.Scores()
+  sc.num_thresholds = len(thr)
+  for i, t in enumerate(thr):
+    sc.thresholds[i] = t
+  keep = None
+  if sample_scale is not None:
+    keep = sample_scale if isinstance(sample_scale, torch.Tensor) else torch.as_tensor(sample_scale, dtype=torch.float32, device=dev)
+    _require_cuda(keep, 'sample_scale')
+    keep = keep.to(torch.float32).contiguous()
+    if keep.numel() != B:
+      raise ValueError(f'sample_scale must have one entry per sample (B = {B}), got {keep.numel()}')
+    sc.sample_scale = keep.data_ptr()
+  sc.query_stats, sc.sample_stats = res.query_stats.data_ptr(), res.sample_stats.data_ptr()
+  sc.frame_err = res.frame_err.data_ptr() if frame_errors else None
+  return res, sc, keep
+
+
 class ParamTree(dict):
   """Nested dict of parameter views; the root carries the flat fp32 buffer the views alias."""
   flat: Optional[torch.Tensor] = None
@@ -443,6 +575,31 @@ class TrackAutoEncoder3D:
                  h, 'spa3d_forward')
     return res
 
+  def score(self, variables, batch, thresholds=(), sample_scale=None, return_predictions: bool = False, frame_errors: bool = False,
+            discretize: bool = True, noise=None) -> TrackScores:
+    """Forward pass + per-track reconstruction scores against the batch's targets in one call (spa3d_score): no [B,Q,T,.] prediction tensor is
+    written unless return_predictions.  thresholds: up to 8 distances (in the units of the tracks); sample_scale: [B] factors on every
+    threshold (scene-relative thresholds).  Fixed metric thresholds -- not tapnet's TAPVid-3D metric."""
+    thr = _check_thresholds(thresholds)
+    params = variables['params'] if 'params' in variables and isinstance(variables['params'], dict) else variables
+    dino, depth = self._dims_from_params(params)
+    h, _, _ = self._handle(dino, depth)
+    flat = self.flat_from_tree(params)
+    _require_cuda(flat, 'params')
+    dev = flat.device
+    b, keep = self._marshal(batch, dino, depth, targets=True, discretize=discretize, noise=noise)
+    self._chunk_options(h, b.Q)
+    res, sc, keep_scale = _alloc_scores(thr, b.B, b.Q, self.num_output_frames, dev, sample_scale, frame_errors)
+    outp = None
+    if return_predictions:
+      res.predictions, out = self._alloc_outputs(b.B, b.Q, dev)
+      outp = C.byref(out)
+    ws = self._workspace(h, b.B, b.N, b.Q, b.T, False, dev)
+    with _counts_on(h, b):
+      _lib.check(_lib.load().spa3d_score(h, flat.data_ptr(), C.byref(b), C.byref(sc), outp, ws.data_ptr(), ws.numel(), _stream(flat)),
+                 h, 'spa3d_score')
+    return res
+
   def apply(self, variables, *args, rngs=None, method=None, **kw):
     """Flax-style apply: model.apply({'params': p}, batch[, rngs=...][, method=model.encode])."""
     if method is None:
@@ -506,6 +663,34 @@ def compute_loss_3d(predictions: TrackAutoEncoderResults, targets, l1_weight: fl
     _lib.check(lib.spa3d_loss(h, C.byref(b), C.byref(out), float(denom), loss.data_ptr(), _stream(tr)), h, 'spa3d_loss')
   pos, vis = loss[1], loss[2]
   return {'total_loss': l1_weight * pos + bce_weight * vis, 'position_loss': pos, 'visible_loss': vis}
+
+
+def score_predictions(predictions: TrackAutoEncoderResults, targets, thresholds=(), sample_scale=None, frame_errors: bool = False) -> TrackScores:
+  """The scores of TrackAutoEncoder3D.score from predictions that already exist (spa3d_score_from_preds): on the predictions a score call
+  returned it gives that call's bits.  targets: query_tracks, query_tracks_visible and, for a ragged batch, query_count."""
+  thr = _check_thresholds(thresholds)
+  lib = _lib.load()
+  tr = predictions.tracks
+  _require_cuda(tr, 'predictions.tracks')
+  B, Q, To = tr.shape[:3]
+  h = _loss_handle(To, 1 if tr.shape[-1] == 2 else 0)
+  b = _lib.Batch()
+  b.B, b.Q = B, Q
+  qt = targets['query_tracks'].to(torch.float32).contiguous()
+  qv = targets['query_tracks_visible'].to(torch.float32).contiguous()
+  _require_cuda(qt, 'query_tracks')
+  _require_cuda(qv, 'query_tracks_visible')
+  if tuple(qt.shape) != tuple(tr.shape):
+    raise ValueError(f'query_tracks {tuple(qt.shape)} does not match predictions {tuple(tr.shape)}')
+  b.query_tracks, b.query_tracks_visible = qt.data_ptr(), qv.data_ptr()
+  t32 = tr.to(torch.float32).contiguous()
+  vl = predictions.visible_logits.to(torch.float32).contiguous()
+  out = _lib.Outputs(t32.data_ptr(), vl.data_ptr(), None, None)
+  res, sc, keep_scale = _alloc_scores(thr, B, Q, To, tr.device, sample_scale, frame_errors)
+  b.counts = (None, validate_counts(targets.get('query_count'), B, Q, 'query_count', 0))  # ragged batch: live queries only
+  with _counts_on(h, b):
+    _lib.check(lib.spa3d_score_from_preds(h, C.byref(b), C.byref(out), C.byref(sc), _stream(tr)), h, 'spa3d_score_from_preds')
+  return res
 
 
 _LOSS_HANDLES: Dict[Any, Any] = {}

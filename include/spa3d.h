@@ -131,6 +131,41 @@ int spa3d_forward(spa3d_handle h, const float* params, const spa3d_batch* b, spa
 int spa3d_loss(spa3d_handle h, const spa3d_batch* b, const spa3d_outputs* preds, float denom,
                float* loss3, void* stream);
 
+/* Per-track reconstruction scores (no reference counterpart in the model code: upstream's tooling consumes per-point scores, and this is
+ * what produces them).  For every query row, over its T_out frames, in fp32: e1 = sum_c |p - g| (the training loss's L1), e2 = the
+ * Euclidean distance sqrtf(sum_c (p - g)^2), pv = visible_logit > 0, vis = target visibility y > 0.5, bce as in spa3d_loss.
+ * query_stats row of S = 8 + 4K floats (K = num_thresholds):
+ *   [0] n_vis = sum vis   [1] sum y e1   [2] sum y e2   [3] max of e2 over vis frames (0 if none)   [4] sum bce
+ *   [5] sum [pv == vis] (occlusion-correct frames)   [6] sum pv   [7] T_out on a live row, 0 on a padded row
+ *   [8 + 4k] W_k  = sum [vis and e2 < thresholds[k] * scale_b]        [9 + 4k]  TP_k = sum [vis and pv and e2 < thresholds[k] * scale_b]
+ *   [10 + 4k] FP_k = sum [pv and not (vis and e2 < ...)]              [11 + 4k] FN_k = sum [vis and not (pv and e2 < ...)]
+ * (TP_k + FN_k = [0] and TP_k + FP_k = [6] on every row.)  These are the TAP-Vid Jaccard counts with FIXED metric thresholds.  This is NOT
+ * tapnet's TAPVid-3D metric: there is no depth-dependent threshold and no median rescaling; sample_scale (one factor per sample on every
+ * threshold, default 1) is the hook for scene-relative thresholds.
+ * sample_stats[b] = the sample's rows pooled in double (sums; [3] a max; [7] = T_out x live queries).  frame_err[q][t] = e2 of every frame,
+ * whatever y is.  One wave per row and fixed-order reductions, no atomics: the same inputs give the same bits on every run, and
+ * spa3d_score_from_preds on the predictions a spa3d_score call returned gives that call's bits.
+ * With per-sample counts (spa3d_set_counts) the rows of padded queries are written as 0 in query_stats and frame_err, and targets at or
+ * beyond a count are never read. */
+typedef struct {
+  int32_t num_thresholds;          /* 0..8 */
+  float   thresholds[8];           /* finite, > 0 */
+  const float* sample_scale;       /* device [B] or NULL */
+  float*  query_stats;             /* device [B,Q,8+4K] f32, required */
+  double* sample_stats;            /* device [B,8+4K] f64 or NULL */
+  float*  frame_err;               /* device [B,Q,T_out] f32 or NULL */
+} spa3d_scores;
+
+/* spa3d_forward with the scores of its predictions against the batch's targets (required) computed on the way out, from the same head
+ * buffer the outputs are split from.  No stash and no backward: spa3d_workspace_bytes(..., train = 0) is a sufficient workspace.  out may
+ * be NULL: no [B,Q,T_out,.] prediction tensor is written then.  Works with every precision, model_kind, option and with per-sample counts
+ * as spa3d_forward does (same refusals).  SPA3D_ERR_ARG with a message, before the first launch: missing targets, query_stats == NULL,
+ * num_thresholds outside 0..8, a threshold that is not finite and positive. */
+int spa3d_score(spa3d_handle h, const float* params, const spa3d_batch* b, spa3d_scores* scores, spa3d_outputs* out,
+                void* ws, int64_t ws_bytes, void* stream);
+/* The same scores from already-split predictions (as spa3d_loss): reads B, Q, the targets and the query counts only. */
+int spa3d_score_from_preds(spa3d_handle h, const spa3d_batch* b, const spa3d_outputs* preds, spa3d_scores* scores, void* stream);
+
 /* forward + loss + backward.  grads (flat f32, same layout as params) is OVERWRITTEN unless
  * accumulate!=0.  denom: global sum(query_tracks_visible) for data-parallel runs (the loss
  * normalisers are batch-global, train.py:111-113,119-121); <=0 = this batch's own.

@@ -1,0 +1,84 @@
+"""Per-track score arithmetic (3dspa_code_amd/csrc/score_row.hpp) on the CPU: the header is plain C++ shared by the fused kernel, the
+from-predictions kernel and this test, so a small driver (tests/host/score_row_check.cpp) is built with the host compiler and fed random rows --
+T in {8, 150, 300}, NC in {2, 3}, K in {0, 1, 5, 8}, rows without a visible frame and rows with every frame visible, with and without a
+sample scale -- and its stats rows and frame errors are compared with the NumPy float64 restatement in tests/score_util.py under the rules
+stated there.  No GPU needed."""
+import os
+import shutil
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+import score_util as SU
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+THRESHOLDS = {0: [], 1: [2.0], 5: [0.5, 1.0, 2.0, 4.0, 8.0], 8: [0.25, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 8.0]}
+
+
+@pytest.fixture(scope='module')
+def driver(tmp_path_factory):
+  cxx = shutil.which('g++') or shutil.which('c++')
+  if cxx is None:
+    pytest.fail('no host C++ compiler')
+  exe = str(tmp_path_factory.mktemp('score_row') / 'score_row_check')
+  r = subprocess.run([cxx, '-std=c++17', '-O1', '-ffp-contract=off', '-Wall', '-Wextra', '-Werror', os.path.join(ROOT, 'tests', 'host', 'score_row_check.cpp'), '-o', exe],
+                     capture_output=True, text=True)
+  assert r.returncode == 0, r.stderr[-3000:]
+  return exe
+
+
+def _rows(rng, R, T, NC):
+  p = rng.standard_normal((R, T, NC)).astype(np.float32)
+  g = rng.standard_normal((R, T, NC)).astype(np.float32)
+  l = (2.0 * rng.standard_normal((R, T))).astype(np.float32)
+  y = (rng.random((R, T)) < 0.5).astype(np.float32)
+  y[0] = 0.0  # no visible frame
+  y[1] = 1.0  # every frame visible
+  l[2] = np.abs(l[2]) + 0.1  # every frame predicted visible
+  l[3] = -np.abs(l[3]) - 0.1  # none
+  return p, l, g, y
+
+
+def _run(driver, p, l, g, y, thr, scale):
+  R, T, NC = p.shape
+  K = len(thr)
+  t8 = np.zeros(8, np.float32)
+  t8[:K] = thr
+  blob = [struct.pack('<i', R)]
+  for r in range(R):
+    blob += [struct.pack('<iii', T, NC, K), struct.pack('<f', float(scale[r])), t8.tobytes(), p[r].tobytes(), l[r].tobytes(), g[r].tobytes(), y[r].tobytes()]
+  out = subprocess.run([driver], input=b''.join(blob), capture_output=True, timeout=120)
+  assert out.returncode == 0, out.stderr[-2000:]
+  S = 8 + 4 * K
+  a = np.frombuffer(out.stdout, np.float32).reshape(R, S + T)
+  return a[:, :S], a[:, S:]
+
+
+@pytest.mark.parametrize('T', [8, 150, 300])
+@pytest.mark.parametrize('NC', [2, 3])
+@pytest.mark.parametrize('K', [0, 1, 5, 8])
+def test_score_rows_match_float64_restatement(driver, T, NC, K):
+  rng = np.random.default_rng(1000 * T + 10 * NC + K)
+  R = 256  # T = 8, K = 5: 10 240 (frame, threshold) pairs -- the 0.1 % allowance needs thousands of pairs before a single chance pair fits under it
+  p, l, g, y = _rows(rng, R, T, NC)
+  for scaled in (False, True):
+    scale = rng.choice(np.array([0.5, 1.0, 1.7], np.float32), R) if scaled else np.ones(R, np.float32)
+    stats, fe = _run(driver, p, l, g, y, THRESHOLDS[K], scale)
+    ref = SU.reference(p, l, g, y, THRESHOLDS[K], scale)
+    SU.check(stats, fe, ref, f'host T={T} NC={NC} K={K} scaled={scaled}')
+    assert (stats[0, 0] == 0) and (stats[0, 3] == 0) and (stats[1, 0] == T) and (stats[2, 6] == T) and (stats[3, 6] == 0)
+    if K:
+      assert (stats[0, 8::4] == 0).all() and (stats[0, 9::4] == 0).all() and (stats[0, 11::4] == 0).all()  # nothing visible: W = TP = FN = 0
+      assert (stats[0, 10::4] == stats[0, 6]).all()                                                        # and every predicted-visible frame is a false positive
+
+
+def test_thresholds_split_the_rows(driver):
+  """The thresholds are not vacuous: at T = 150 the middle one puts a real share of the visible frames on each side."""
+  rng = np.random.default_rng(7)
+  p, l, g, y = _rows(rng, 16, 150, 3)
+  stats, _ = _run(driver, p, l, g, y, THRESHOLDS[5], np.ones(16, np.float32))
+  w = stats[4:, 8::4] / np.maximum(stats[4:, 0:1], 1)
+  assert (np.diff(w, axis=1) >= 0).all() and w[:, 0].max() < 0.2 and 0.2 < w[:, 2].mean() < 0.8 and w[:, 4].min() > 0.95
