@@ -44,6 +44,12 @@ class Scores(C.Structure):
               ('sample_stats', C.c_void_p), ('frame_err', C.c_void_p)]
 
 
+class TapVid3D(C.Structure):
+  """spa3d_tapvid3d (include/spa3d.h): the scaling mode, the threshold table switch, then device pointers."""
+  _fields_ = [('scaling', C.c_int32), ('fixed_thresholds', C.c_int32), ('intrinsics', C.c_void_p), ('query_stats', C.c_void_p),
+              ('sample_stats', C.c_void_p), ('scale', C.c_void_p), ('row_scale', C.c_void_p), ('ratio', C.c_void_p)]
+
+
 _SIGS = {
     'spa3d_version': (C.c_char_p, []),
     'spa3d_create': (C.c_int, [C.POINTER(Config), C.POINTER(C.c_void_p)]),
@@ -63,6 +69,9 @@ _SIGS = {
     'spa3d_score': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Batch), C.POINTER(Scores), C.POINTER(Outputs), C.c_void_p, C.c_int64,
                               C.c_void_p]),
     'spa3d_score_from_preds': (C.c_int, [C.c_void_p, C.POINTER(Batch), C.POINTER(Outputs), C.POINTER(Scores), C.c_void_p]),
+    'spa3d_tapvid3d_workspace_bytes': (C.c_int64, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+    'spa3d_tapvid3d_from_preds': (C.c_int, [C.c_void_p, C.POINTER(Batch), C.POINTER(Outputs), C.POINTER(TapVid3D), C.c_void_p, C.c_int64, C.c_void_p]),
+    'spa3d_op_median_rows': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     'spa3d_loss_and_grads': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Batch), C.c_float, C.c_void_p, C.c_int32,
                                        C.c_void_p, C.POINTER(Outputs), C.c_void_p, C.c_int64, C.c_void_p]),
     'spa3d_adamw_step': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_int64,

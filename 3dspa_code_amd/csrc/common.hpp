@@ -9,6 +9,7 @@
 #include "ablate.inc"  // every work-skipping diagnostic mask, all 0 in libspa3d_hip.so
 #include "gemm_plan.hpp"  // GemmDesc and the kernel choice (host-only)
 #include "score_row.hpp"  // per-track score arithmetic (host- and device-callable)
+#include "tapvid3d_row.hpp"  // TAPVid-3D metric counts of a row and the exact median select (host- and device-callable)
 
 // One translation unit is compiled for exactly ONE 16-bit activation type: bf16 (default) or IEEE fp16 (-DSPA_F16=1, BASELINE
 // cfg#5).  The raw 16-bit storage type is `bf16_t` (unsigned short) in both builds; what differs -- the two conversions, the MFMA
@@ -160,6 +161,16 @@ struct ScoreArgs {
   const float* tgt; const float* tvis; const float* scale;  // scale: device [B] or null
   float* qstats; float* frame_err;                          // frame_err: [B * Q][T] or null
   int64_t nq, row0; int Q, T, NC; ScoreThr thr;
+};
+
+// The launches of spa3d_tapvid3d_from_preds (tapvid3d.hip) share this block: the caller's whole tensors, indexed by the global query row, and the
+// rows [row0, row0 + nq) a launch covers.  ratio / sel / row_scale / scale may be null (see each kernel).
+struct TvArgs {
+  const float* tracks; const float* vlog; const float* tgt; const float* tvis; const float* qpts; const float* intr;  // intr: device [B][4] or null
+  const float* scale;          // rows pass, median scaling: device [B]
+  float* ratio; float* sel;    // ratio pass: ratio [B * Q][T] of every frame; sel: the same with NaN outside {vis and ew} (the median's set)
+  float* row_scale; float* qstats;
+  int64_t nq, row0; int Q, T, scaling, fixed;
 };
 
 struct Leaf {
@@ -368,6 +379,11 @@ void k_loss_from_preds(spa3d_ctx*, const float* tracks, const float* vlog, int64
                        unsigned* poison, int NC = 3);
 void k_score_rows(spa3d_ctx*, const ScoreArgs& a);
 void k_score_reduce(spa3d_ctx*, const float* qstats, int64_t B, int Q, int K, double* out /*[B][8 + 4K]*/);
+void k_tv_ratio(spa3d_ctx*, const TvArgs& a);
+void k_tv_rows(spa3d_ctx*, const TvArgs& a);
+void k_tv_reduce(spa3d_ctx*, const float* qstats, int64_t B, int Q, double* out /*[B][24]*/);
+void k_tv_fill(spa3d_ctx*, float* p, int64_t n, float v);
+void k_median_rows(spa3d_ctx*, const float* x, int64_t rows, int64_t stride, int64_t n, float* out);
 template <typename T> void k_loss_bwd(spa3d_ctx*, const float* head, int64_t nq, int T_, const float* tgt, const float* tvis,
                                       const float* denom_dev, float l1w, float bcew, T* dhead, int NC = 3, const float* scale_dev = nullptr);
 void k_vis_count(spa3d_ctx*, const float* tvis, int64_t n, float* out, unsigned* poison);

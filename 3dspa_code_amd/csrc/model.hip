@@ -1419,6 +1419,81 @@ int spa3d_score_from_preds(spa3d_handle h, const spa3d_batch* b, const spa3d_out
   return h->hip_err ? SPA3D_ERR_HIP : SPA3D_OK;
 }
 
+// ---- TAPVid-3D metrics (tapvid3d.hip, tapvid3d_row.hpp) ----
+// The launches of one call.  Runs twice: dry (no launch, a counting arena: the workspace the call needs) and for real.  Workspace: the median's
+// set [B * Q][T_out] (median scaling only) and the per-sample factors [B] when the caller does not ask for them.
+static void tapvid3d_body(spa3d_ctx* c, const spa3d_batch* b, const spa3d_outputs* preds, const spa3d_tapvid3d* m, const int32_t* cq) {
+  const int To = c->cfg.num_output_frames;
+  const int64_t B = b->B, Q = b->Q;
+  const bool median = m->scaling == SPA3D_SCALE_MEDIAN;
+  TvArgs a{};
+  a.tracks = preds->tracks; a.vlog = preds->visible_logits; a.tgt = b->query_tracks; a.tvis = b->query_tracks_visible; a.qpts = b->query_points;
+  a.intr = m->intrinsics; a.ratio = m->ratio; a.row_scale = m->row_scale; a.qstats = m->query_stats;
+  a.Q = b->Q; a.T = To; a.scaling = m->scaling; a.fixed = m->fixed_thresholds != 0;
+  a.sel = median ? (float*)c->ar.alloc(B * Q * To * 4) : nullptr;
+  float* scale = m->scale ? m->scale : (median ? (float*)c->ar.alloc(B * 4) : nullptr);
+  a.scale = scale;
+  // rows of padded queries (spa3d_set_counts): every result reads 0, their inputs are never read and they are not part of the median
+  auto zero_padded = [&](int64_t r0, int64_t nr) {
+    if (c->dry || nr <= 0) return;
+    (void)hipMemsetAsync(m->query_stats + r0 * TV_S, 0, (size_t)(nr * TV_S) * 4, c->stream);
+    if (m->row_scale) (void)hipMemsetAsync(m->row_scale + r0, 0, (size_t)nr * 4, c->stream);
+    if (m->ratio) (void)hipMemsetAsync(m->ratio + r0 * To, 0, (size_t)(nr * To) * 4, c->stream);
+  };
+  auto each_span = [&](auto&& launch) {  // live rows: the whole batch at once, or sample by sample
+    if (!cq) { a.nq = B * Q; a.row0 = 0; launch(); return; }
+    for (int64_t i = 0; i < B; ++i) { a.nq = cq[i]; a.row0 = i * Q; launch(); }
+  };
+  if (a.ratio || a.sel) each_span([&] { k_tv_ratio(c, a); });
+  if (median) {
+    if (!cq) k_median_rows(c, a.sel, B, Q * To, Q * To, scale);
+    else for (int64_t i = 0; i < B; ++i) k_median_rows(c, a.sel + i * Q * To, 1, Q * To, (int64_t)cq[i] * To, scale + i);
+  } else if (scale) {
+    k_tv_fill(c, scale, B, 1.f);
+  }
+  each_span([&] { k_tv_rows(c, a); });
+  if (cq) for (int64_t i = 0; i < B; ++i) zero_padded(i * Q + cq[i], Q - cq[i]);
+  if (m->sample_stats) k_tv_reduce(c, m->query_stats, B, b->Q, m->sample_stats);
+}
+static int64_t tapvid3d_need(spa3d_ctx* c, const spa3d_batch* b, const spa3d_outputs* preds, const spa3d_tapvid3d* m, const int32_t* cq) {
+  Arena saved = c->ar; const bool sd = c->dry;
+  c->ar = Arena(); c->ar.dry = true; c->dry = true;
+  tapvid3d_body(c, b, preds, m, cq);
+  const int64_t need = c->ar.peak + 256;  // never 0: a call without a workspace is refused after the walk, whatever the scaling
+  c->ar = saved; c->dry = sd;
+  return need;
+}
+int64_t spa3d_tapvid3d_workspace_bytes(spa3d_handle h, int32_t B, int32_t Q, int32_t T) {
+  if (!h || B <= 0 || Q <= 0 || T <= 0) return -1;
+  const int64_t To = std::max(T, h->cfg.num_output_frames);  // the largest need of any scaling: the median's set and the factors, each 256-byte aligned
+  return (((int64_t)B * Q * To * 4 + 255) & ~int64_t(255)) + (((int64_t)B * 4 + 255) & ~int64_t(255)) + 256;
+}
+int spa3d_tapvid3d_from_preds(spa3d_handle h, const spa3d_batch* b, const spa3d_outputs* preds, spa3d_tapvid3d* m, void* ws, int64_t ws_bytes, void* stream) {
+  if (!h) return SPA3D_ERR_ARG;
+  h->err.clear(); h->hip_err = 0;
+  if (h->cfg.model_kind == 1) { h->err = "tapvid3d: the 2-D model (model_kind 1) has no depth coordinate"; return SPA3D_ERR_ARG; }
+  if (!b || !b->query_tracks || !b->query_tracks_visible) { h->err = "tapvid3d: the batch needs its targets (query_tracks, query_tracks_visible)"; return SPA3D_ERR_ARG; }
+  if (!b->query_points) { h->err = "tapvid3d: the batch needs query_points (the query frame is left out of every count)"; return SPA3D_ERR_ARG; }
+  if (!preds || !preds->tracks || !preds->visible_logits) { h->err = "tapvid3d: predictions (tracks, visible_logits) are required"; return SPA3D_ERR_ARG; }
+  if (!m || !m->query_stats) { h->err = "tapvid3d: spa3d_tapvid3d::query_stats is required"; return SPA3D_ERR_ARG; }
+  if (m->scaling < SPA3D_SCALE_NONE || m->scaling > SPA3D_SCALE_PER_TRAJECTORY) { h->err = "tapvid3d: scaling = " + std::to_string(m->scaling) + " is outside [0, 2]"; return SPA3D_ERR_ARG; }
+  if (b->B <= 0 || b->Q <= 0) { h->err = "batch: B,Q must be positive"; return SPA3D_ERR_ARG; }
+  const int32_t* cq = nullptr;
+  if (h->has_cnt_q) {
+    if (h->cnt_B != b->B) { h->err = "counts were set for B = " + std::to_string(h->cnt_B) + ", this batch has B = " + std::to_string(b->B); return SPA3D_ERR_ARG; }
+    for (int i = 0; i < b->B; ++i)
+      if (h->cnt_q[i] < 0 || h->cnt_q[i] > b->Q) { h->err = "query_count[" + std::to_string(i) + "] is outside [0, Q]"; return SPA3D_ERR_ARG; }
+    cq = h->cnt_q.data();
+  }
+  const int64_t need = tapvid3d_need(h, b, preds, m, cq);
+  if (!ws || ws_bytes < need) { h->err = "tapvid3d: workspace too small: need " + std::to_string(need) + " bytes"; return SPA3D_ERR_ARG; }
+  h->stream = (hipStream_t)stream; h->dry = false;
+  h->ar = Arena(); h->ar.base = (char*)ws; h->ar.cap = ws_bytes;
+  tapvid3d_body(h, b, preds, m, cq);
+  if (h->ar.overflow) { h->err = "internal: arena overflow"; return SPA3D_ERR_WORKSPACE; }
+  return h->hip_err ? SPA3D_ERR_HIP : SPA3D_OK;
+}
+
 int spa3d_loss_and_grads(spa3d_handle h, const float* params, const spa3d_batch* b, float denom, float* grads, int32_t accumulate,
                          float* loss3, spa3d_outputs* out, void* ws, int64_t ws_bytes, void* stream) {
   if (!h || !params || !grads) return SPA3D_ERR_ARG;

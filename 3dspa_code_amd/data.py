@@ -5,8 +5,8 @@
   collate_ragged / split_ragged            evaluate_tapvid3d.py:318-348 as batches of clips with differing track / query counts
   load_checkpoint / save_checkpoint        inference.py:450-508, evaluate_tapvid3d.py:247-285 / train.py:389-393 (a stub upstream)
 
-Plain NumPy / torch glue: no arithmetic worth a kernel.  The metric arithmetic of TAPVid-3D stays in the un-vendored
-`tapnet` package, as upstream."""
+Plain NumPy / torch glue: no arithmetic worth a kernel.  The metric arithmetic of TAPVid-3D is model.tapvid3d_predictions (upstream
+it is the un-vendored `tapnet` package)."""
 from __future__ import annotations
 
 import dataclasses
@@ -128,7 +128,12 @@ def collate_ragged(samples, pad_value: float = 0.0):
 def split_ragged(results, batch):
   """Back to per-clip views: `results` is a TrackAutoEncoderResults-like object (tensor attributes with leading [B, Q]) or a dict of
   such tensors; returns a list of B dicts whose tensors are the views [q_b, ...] of the live rows.  A TrackScores comes back as a list of B
-  TrackScores (query_stats [q_b, S], sample_stats [S], frame_err [q_b, T])."""
+  TrackScores (query_stats [q_b, S], sample_stats [S], frame_err [q_b, T]), a TapVid3DScores as a list of B TapVid3DScores."""
+  if hasattr(results, 'query_stats') and hasattr(results, 'row_scale'):  # TapVid3DScores: one per clip, cut to its live rows
+    B, Q = results.query_stats.shape[:2]
+    qc = validate_counts(batch.get('query_count'), B, Q, 'query_count', 0) or [Q] * B
+    return [dataclasses.replace(results, query_stats=results.query_stats[i, :qc[i]], sample_stats=results.sample_stats[i], scale=results.scale[i],
+                                row_scale=results.row_scale[i, :qc[i]], ratio=None if results.ratio is None else results.ratio[i, :qc[i]]) for i in range(B)]
   if hasattr(results, 'query_stats') and hasattr(results, 'sample_stats'):  # TrackScores: one TrackScores per clip, cut to its live rows
     B, Q = results.query_stats.shape[:2]
     qc = validate_counts(batch.get('query_count'), B, Q, 'query_count', 0) or [Q] * B

@@ -194,6 +194,98 @@ def _alloc_scores(thr, B, Q, To, dev, sample_scale, frame_errors):
   return res, sc, keep
 
 
+# ------------------------------------------------------------------------------------------------
+# TAPVid-3D metrics (include/spa3d.h, spa3d_tapvid3d): restated from the published definition, parity unpinned
+# ------------------------------------------------------------------------------------------------
+TAPVID3D_SLOTS = 24  # [evaluated frames, visible, occlusion-correct, predicted visible] + (W, TP, FP, FN) per pixel threshold
+TAPVID3D_PIXELS = (1, 2, 4, 8, 16)
+TAPVID3D_SCALINGS = {'none': 0, 'median': 1, 'per_trajectory': 2}
+
+
+class _TapVid3DProperties:
+  """Ratios of a stats tensor [..., 24]; a zero denominator gives 0, as _ScoreProperties does."""
+
+  def _stats(self) -> torch.Tensor:
+    raise NotImplementedError
+
+  def _ratio(self, num, den):
+    return num / torch.clamp(den, min=1.0)
+
+  @property
+  def occlusion_accuracy(self):
+    s = self._stats()
+    return self._ratio(s[..., 2], s[..., 0])
+
+  @property
+  def pts_within(self):
+    """[..., 5]: share of the evaluated visible frames within the 1, 2, 4, 8, 16 pixel thresholds."""
+    s = self._stats()
+    return self._ratio(s[..., 4::4], s[..., 1:2])
+
+  @property
+  def jaccard(self):
+    """[..., 5]: TP / (visible + FP) = TP / (TP + FN + FP)."""
+    s = self._stats()
+    return self._ratio(s[..., 5::4], s[..., 1:2] + s[..., 6::4])
+
+  @property
+  def average_jaccard(self):
+    return self.jaccard.mean(-1)
+
+  @property
+  def average_pts_within_thresh(self):
+    return self.pts_within.mean(-1)
+
+
+@dataclasses.dataclass
+class TapVid3DSampleScores(_TapVid3DProperties):
+  """Per-clip metrics from the pooled counts of the clip's live queries: what the reference's evaluation reports per video."""
+  stats: torch.Tensor  # [B, 24] f64 (or [24] after split_ragged)
+  scaling: str = 'median'
+
+  def _stats(self):
+    return self.stats
+
+
+@dataclasses.dataclass
+class TapVid3DScores(_TapVid3DProperties):
+  """What tapvid3d_predictions / TrackAutoEncoder3D.tapvid3d return: the raw tensors of spa3d_tapvid3d and, as properties, the per-query
+  ratios (occlusion_accuracy, pts_within[k], jaccard[k], average_jaccard, average_pts_within_thresh); `.sample` gives the same per clip."""
+  query_stats: torch.Tensor  # [B, Q, 24] f32; rows of padded queries are 0
+  sample_stats: torch.Tensor  # [B, 24] f64
+  scale: torch.Tensor  # [B] f32: the factor applied per sample (1 for none / per_trajectory)
+  row_scale: torch.Tensor  # [B, Q] f32: the factor each row's predictions were multiplied by
+  ratio: Optional[torch.Tensor] = None  # [B, Q, T] f32 |gt| / |pred| of every frame (ratios=True)
+  scaling: str = 'median'
+  fixed_thresholds: bool = False
+
+  def _stats(self):
+    return self.query_stats
+
+  @property
+  def sample(self) -> TapVid3DSampleScores:
+    return TapVid3DSampleScores(self.sample_stats, self.scaling)
+
+  def as_dict(self, b: int = 0) -> Dict[str, float]:
+    """The 13 keys compute_tapvid3d_metrics returns, for clip b (one host read of the clip's 24 pooled counts)."""
+    s = self.sample_stats if self.sample_stats.dim() == 1 else self.sample_stats[b]
+    one = TapVid3DSampleScores(s.detach().to('cpu', torch.float64), self.scaling)
+    out = {'occlusion_accuracy': float(one.occlusion_accuracy)}
+    w, j = one.pts_within.tolist(), one.jaccard.tolist()
+    for k, px in enumerate(TAPVID3D_PIXELS):
+      out[f'pts_within_{px}'] = w[k]
+      out[f'jaccard_{px}'] = j[k]
+    out['average_jaccard'] = float(one.average_jaccard)
+    out['average_pts_within_thresh'] = float(one.average_pts_within_thresh)
+    return out
+
+
+def _check_scaling(scaling) -> str:
+  if scaling not in TAPVID3D_SCALINGS:
+    raise ValueError(f"scaling must be one of {sorted(TAPVID3D_SCALINGS)} (tapnet's 'local_neighborhood' is not implemented), got {scaling!r}")
+  return scaling
+
+
 class ParamTree(dict):
   """Nested dict of parameter views; the root carries the flat fp32 buffer the views alias."""
   flat: Optional[torch.Tensor] = None
@@ -600,6 +692,14 @@ class TrackAutoEncoder3D:
                  h, 'spa3d_score')
     return res
 
+  def tapvid3d(self, variables, batch, scalings=('median',), fixed_thresholds: bool = False, ratios: bool = False, discretize: bool = True, noise=None):
+    """evaluate_tapvid3d.py:62-115 for one batch: ONE forward pass, then one TAPVid-3D metric call per scaling on that forward's
+    predictions (tapvid3d_predictions).  Returns {scaling: TapVid3DScores}.  The batch carries its targets, may carry `intrinsics` [B, 4]
+    (default (256, 256, 128, 128)) and, for a ragged batch, its counts (split_ragged cuts a TapVid3DScores per clip)."""
+    scalings = tuple(_check_scaling(s) for s in scalings)
+    preds = self(variables, batch, discretize=discretize, noise=noise)
+    return {s: tapvid3d_predictions(preds, batch, scaling=s, intrinsics=batch.get('intrinsics'), fixed_thresholds=fixed_thresholds, ratios=ratios) for s in scalings}
+
   def apply(self, variables, *args, rngs=None, method=None, **kw):
     """Flax-style apply: model.apply({'params': p}, batch[, rngs=...][, method=model.encode])."""
     if method is None:
@@ -691,6 +791,88 @@ def score_predictions(predictions: TrackAutoEncoderResults, targets, thresholds=
   with _counts_on(h, b):
     _lib.check(lib.spa3d_score_from_preds(h, C.byref(b), C.byref(out), C.byref(sc), _stream(tr)), h, 'spa3d_score_from_preds')
   return res
+
+
+def tapvid3d_predictions(predictions: TrackAutoEncoderResults, batch, scaling: str = 'median', intrinsics=None, fixed_thresholds: bool = False,
+                         ratios: bool = False) -> TapVid3DScores:
+  """TAPVid-3D metric counts of existing predictions (spa3d_tapvid3d_from_preds): the counterpart of
+  tapvid3d_metrics.compute_tapvid3d_metrics(..., scaling=scaling) in evaluate_tapvid3d.py:99-109, for every clip of the batch at once and
+  without a host copy.  batch: query_points, query_tracks, query_tracks_visible and, for a ragged batch, query_count.  intrinsics: [B, 4]
+  or [4] (fx, fy, cx, cy), default (256, 256, 128, 128).  Restated from the published definition; parity with tapnet is unpinned."""
+  _check_scaling(scaling)
+  lib = _lib.load()
+  tr = predictions.tracks
+  _require_cuda(tr, 'predictions.tracks')
+  if tr.dim() != 4 or tr.shape[-1] != 3:
+    raise ValueError(f'TAPVid-3D metrics need 3-D tracks [B, Q, T, 3], got {tuple(tr.shape)}')
+  B, Q, To = tr.shape[:3]
+  dev = tr.device
+  h = _loss_handle(To, 0)
+  b = _lib.Batch()
+  b.B, b.Q = B, Q
+  qt = batch['query_tracks'].to(torch.float32).contiguous()
+  qv = batch['query_tracks_visible'].to(torch.float32).contiguous()
+  qp = batch['query_points'].to(torch.float32).contiguous()
+  for t, name in ((qt, 'query_tracks'), (qv, 'query_tracks_visible'), (qp, 'query_points')):
+    _require_cuda(t, name)
+  if tuple(qt.shape) != tuple(tr.shape):
+    raise ValueError(f'query_tracks {tuple(qt.shape)} does not match predictions {tuple(tr.shape)}')
+  if qv.numel() != B * Q * To:
+    raise ValueError(f'query_tracks_visible {tuple(qv.shape)} does not match predictions {tuple(tr.shape)}')
+  if tuple(qp.shape) != (B, Q, 4):
+    raise ValueError(f'query_points must be [B, Q, 4] (t, x, y, z), got {tuple(qp.shape)}')
+  b.query_tracks, b.query_tracks_visible, b.query_points = qt.data_ptr(), qv.data_ptr(), qp.data_ptr()
+  t32 = tr.to(torch.float32).contiguous()
+  vl = predictions.visible_logits.to(torch.float32).contiguous()
+  out = _lib.Outputs(t32.data_ptr(), vl.data_ptr(), None, None)
+  res = TapVid3DScores(torch.empty(B, Q, TAPVID3D_SLOTS, dtype=torch.float32, device=dev), torch.empty(B, TAPVID3D_SLOTS, dtype=torch.float64, device=dev),
+                       torch.empty(B, dtype=torch.float32, device=dev), torch.empty(B, Q, dtype=torch.float32, device=dev),
+                       torch.empty(B, Q, To, dtype=torch.float32, device=dev) if ratios else None, scaling, bool(fixed_thresholds))
+  m = _lib.TapVid3D()
+  m.scaling, m.fixed_thresholds = TAPVID3D_SCALINGS[scaling], 1 if fixed_thresholds else 0
+  k = None
+  if intrinsics is not None:
+    k = intrinsics if isinstance(intrinsics, torch.Tensor) else torch.as_tensor(intrinsics, dtype=torch.float32)
+    k = k.to(device=dev, dtype=torch.float32)
+    if k.dim() == 1:
+      k = k.expand(B, -1)
+    if tuple(k.shape) != (B, 4):
+      raise ValueError(f'intrinsics must be [B, 4] or [4] (fx, fy, cx, cy), got {tuple(k.shape)}')
+    k = k.contiguous()
+    m.intrinsics = k.data_ptr()
+  m.query_stats, m.sample_stats, m.scale, m.row_scale = res.query_stats.data_ptr(), res.sample_stats.data_ptr(), res.scale.data_ptr(), res.row_scale.data_ptr()
+  m.ratio = res.ratio.data_ptr() if ratios else None
+  ws = torch.empty(max(int(lib.spa3d_tapvid3d_workspace_bytes(h, B, Q, To)), 256), dtype=torch.uint8, device=dev)
+  b.counts = (None, validate_counts(batch.get('query_count'), B, Q, 'query_count', 0))  # ragged batch: live queries only
+  with _counts_on(h, b):
+    _lib.check(lib.spa3d_tapvid3d_from_preds(h, C.byref(b), C.byref(out), C.byref(m), ws.data_ptr(), ws.numel(), _stream(tr)), h, 'spa3d_tapvid3d_from_preds')
+  return res
+
+
+def aggregate_tapvid3d(per_clip):
+  """evaluate_tapvid3d.py:233-243: per_clip = a list of metric dicts (one per video); returns {key: mean, key_std: population std}."""
+  out = {}
+  if not per_clip:
+    return out
+  for key in per_clip[0]:
+    vals = [float(c[key]) for c in per_clip]
+    mean = sum(vals) / len(vals)
+    out[key] = mean
+    out[f'{key}_std'] = math.sqrt(sum((v - mean) ** 2 for v in vals) / len(vals))
+  return out
+
+
+def evaluate_tapvid3d(model, variables, batches, depth_scalings=('median',), fixed_thresholds: bool = False):
+  """Counterpart of evaluate_model (evaluate_tapvid3d.py:144-244): every batch through model.tapvid3d (one forward, one metric call per
+  scaling), every clip of every batch one video; returns {scaling: {key: mean over videos, key_std: std over videos}} with the reference's
+  13 keys.  Batches may be ragged (collate_ragged) and may carry `intrinsics`."""
+  depth_scalings = tuple(_check_scaling(s) for s in depth_scalings)
+  per_clip = {s: [] for s in depth_scalings}
+  for batch in batches:
+    scores = model.tapvid3d(variables, batch, scalings=depth_scalings, fixed_thresholds=fixed_thresholds)
+    for s in depth_scalings:
+      per_clip[s] += [scores[s].as_dict(i) for i in range(scores[s].sample_stats.shape[0])]
+  return {s: aggregate_tapvid3d(per_clip[s]) for s in depth_scalings}
 
 
 _LOSS_HANDLES: Dict[Any, Any] = {}

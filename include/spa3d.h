@@ -13,6 +13,8 @@
  *   spa3d_loss_and_grads            jax.value_and_grad(loss_fn)(params)  train.py:134-162
  *   spa3d_adamw_step                optax.chain(clip_by_global_norm(1.0), adamw(lr, 0.01)) + apply_updates
  *                                   train.py:164-165,239-242 (intended semantics, repair R6)
+ *   spa3d_tapvid3d_from_preds       tapvid3d_metrics.compute_tapvid3d_metrics(...)  evaluate_tapvid3d.py:99-109,196-208
+ *                                   (third-party arithmetic upstream: restated from the published definition, parity unpinned)
  *   spa3d_uniform_noise             jax.random.uniform(PRNGKey(0), shape) track_autoencoder_3d.py:254-257
  *   spa3d_op_*                      single building blocks (attention.py, track_autoencoder.py:18-38),
  *                                   exported so tests can check each kernel against the oracle.
@@ -140,8 +142,8 @@ int spa3d_loss(spa3d_handle h, const spa3d_batch* b, const spa3d_outputs* preds,
  *   [8 + 4k] W_k  = sum [vis and e2 < thresholds[k] * scale_b]        [9 + 4k]  TP_k = sum [vis and pv and e2 < thresholds[k] * scale_b]
  *   [10 + 4k] FP_k = sum [pv and not (vis and e2 < ...)]              [11 + 4k] FN_k = sum [vis and not (pv and e2 < ...)]
  * (TP_k + FN_k = [0] and TP_k + FP_k = [6] on every row.)  These are the TAP-Vid Jaccard counts with FIXED metric thresholds.  This is NOT
- * tapnet's TAPVid-3D metric: there is no depth-dependent threshold and no median rescaling; sample_scale (one factor per sample on every
- * threshold, default 1) is the hook for scene-relative thresholds.
+ * tapnet's TAPVid-3D metric (that is spa3d_tapvid3d_from_preds below): there is no depth-dependent threshold and no median rescaling;
+ * sample_scale (one factor per sample on every threshold, default 1) is the hook for scene-relative thresholds.
  * sample_stats[b] = the sample's rows pooled in double (sums; [3] a max; [7] = T_out x live queries).  frame_err[q][t] = e2 of every frame,
  * whatever y is.  One wave per row and fixed-order reductions, no atomics: the same inputs give the same bits on every run, and
  * spa3d_score_from_preds on the predictions a spa3d_score call returned gives that call's bits.
@@ -165,6 +167,48 @@ int spa3d_score(spa3d_handle h, const float* params, const spa3d_batch* b, spa3d
                 void* ws, int64_t ws_bytes, void* stream);
 /* The same scores from already-split predictions (as spa3d_loss): reads B, Q, the targets and the query counts only. */
 int spa3d_score_from_preds(spa3d_handle h, const spa3d_batch* b, const spa3d_outputs* preds, spa3d_scores* scores, void* stream);
+
+/* TAPVid-3D metrics of existing predictions against the batch's targets: occlusion accuracy, points-within and Jaccard counts at the pixel
+ * thresholds 1, 2, 4, 8, 16, with the predictions rescaled first.  tapnet, whose compute_tapvid3d_metrics upstream calls, is not vendored by
+ * the reference: what follows is restated from the published definition, parity unpinned, and is the contract.
+ * fp32, per sample b, over the sample's live query rows; p, l = preds->tracks, preds->visible_logits, g, y = the batch's targets:
+ *   tq    = clamp(lrintf(query_points[b,q,0]), 0, T_out - 1); ew[q][t] = (t != tq): the query frame is left out of every count
+ *   gn    = sqrtf(fmaxf(1e-12f, sum_c g^2)), pn alike; ratio[q][t] = gn / pn, for every frame of a live row whatever y is
+ *   scaling SPA3D_SCALE_NONE: s = 1.  SPA3D_SCALE_MEDIAN: s_b = the exact median of ratio over the sample's {y > 0.5 and ew} (the middle
+ *   value; 0.5f a + 0.5f b of the two middle values for an even count; 1 for an empty set; a NaN ratio is not part of the set).
+ *   SPA3D_SCALE_PER_TRAJECTORY: s_q = ratio[q][tq].  Scaled prediction ps = p * s, rounded once per coordinate.
+ *   thr   = px * (g_z / f_b), f_b = sqrtf(fx fy + 1e-12f), px in {1, 2, 4, 8, 16}; intrinsics == NULL means (256, 256, 128, 128)
+ *           (evaluate_tapvid3d.py:97); fixed_thresholds != 0 uses the metric table 0.01, 0.04, 0.16, 0.64, 2.56 instead
+ *   within = sqrtf(sum_c (ps - g)^2) < thr (a non-positive threshold matches nothing); pv = l > 0; vis = y > 0.5
+ * query_stats row of 24 floats (exact counts):
+ *   [0] sum ew   [1] sum ew vis   [2] sum ew [pv == vis]   [3] sum ew pv
+ *   [4 + 4k] W = sum ew vis within   [5 + 4k] TP = sum ew vis pv within   [6 + 4k] FP = sum ew pv not (vis within)   [7 + 4k] FN = sum ew vis not (pv within)
+ * (TP + FN = [1] and TP + FP = [3] on every row.)  sample_stats[b] = the sample's rows summed in double in a fixed order.  The per-video
+ * metrics are ratios of the pooled counts, taken by the caller: occlusion_accuracy = [2] / [0], pts_within_px = W / [1],
+ * jaccard_px = TP / ([1] + FP), and the two averages over the five thresholds.
+ * The median is a radix select over the bit patterns with integer counts, the rows are one wave each with fixed-order reductions: no float
+ * atomics, the same inputs give the same bits on every run.  With per-sample counts (spa3d_set_counts) the rows of padded queries are written
+ * as 0 in query_stats, row_scale and ratio, their inputs are never read, and they are not part of the median.
+ * This differs from spa3d_scores, which has fixed per-sample thresholds, no rescaling, and counts the query frame. */
+#define SPA3D_SCALE_NONE 0
+#define SPA3D_SCALE_MEDIAN 1
+#define SPA3D_SCALE_PER_TRAJECTORY 2
+typedef struct {
+  int32_t scaling, fixed_thresholds;
+  const float* intrinsics;   /* device [B,4] (fx, fy, cx, cy) or NULL */
+  float*  query_stats;       /* device [B,Q,24], required */
+  double* sample_stats;      /* device [B,24] or NULL */
+  float*  scale;             /* device [B] or NULL: the factor applied per sample (1 for none / per_trajectory) */
+  float*  row_scale;         /* device [B,Q] or NULL: per_trajectory factors (else the sample's factor) */
+  float*  ratio;             /* device [B,Q,T_out] or NULL */
+} spa3d_tapvid3d;
+/* a sufficient workspace for any scaling; T = T_out of the predictions */
+int64_t spa3d_tapvid3d_workspace_bytes(spa3d_handle h, int32_t B, int32_t Q, int32_t T);
+/* Reads B, Q, query_points, the targets and the query counts of the batch.  Asynchronous, allocates nothing, reads nothing back to the host.
+ * SPA3D_ERR_ARG with a message, before the first launch: targets, query_points, predictions or query_stats missing; scaling outside 0..2;
+ * a model_kind 1 handle (no depth coordinate); a workspace that is too small (the message names the bytes needed). */
+int spa3d_tapvid3d_from_preds(spa3d_handle h, const spa3d_batch* b, const spa3d_outputs* preds, spa3d_tapvid3d* m, void* ws, int64_t ws_bytes,
+                              void* stream);
 
 /* forward + loss + backward.  grads (flat f32, same layout as params) is OVERWRITTEN unless
  * accumulate!=0.  denom: global sum(query_tracks_visible) for data-parallel runs (the loss
@@ -367,6 +411,9 @@ int spa3d_op_sample_depth_features(const float* depth, const float* tracks_2d, i
 /* lift_2d_to_3d (inference.py:287-336): intrinsics = host double[4] {fx,fy,cx,cy} or NULL (fx=fy=max(H,W), cx=W/2, cy=H/2) */
 int spa3d_op_lift_2d_to_3d(const float* tracks_2d, const float* depth, int32_t N, int32_t T, int32_t H, int32_t W,
                            const double* intrinsics, float* out, void* stream);
+/* test entry of the metric's exact median select: out[r] = median of the non-NaN entries of x[r][0..n) (1 if none); entries >= 0.  Two middle
+ * values of an even count are averaged as 0.5f a + 0.5f b.  ws is not used (the histograms live in LDS) and may be NULL. */
+int spa3d_op_median_rows(const float* x, int64_t rows, int64_t n, float* out, void* ws, int64_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
