@@ -50,6 +50,14 @@ class TapVid3D(C.Structure):
               ('sample_stats', C.c_void_p), ('scale', C.c_void_p), ('row_scale', C.c_void_p), ('ratio', C.c_void_p)]
 
 
+class Render(C.Structure):
+  """spa3d_render (include/spa3d.h): one clip's sizes, device pointers and drawing options."""
+  _fields_ = [('N', C.c_int32), ('T', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('video', C.c_void_p), ('out', C.c_void_p), ('tracks', C.c_void_p),
+              ('coords', C.c_int32), ('intrinsics', C.c_void_p), ('extrinsics', C.c_void_p), ('resize_h', C.c_int32), ('resize_w', C.c_int32),
+              ('scores', C.c_void_p), ('visible', C.c_void_p), ('normalize', C.c_int32), ('use_visibility', C.c_int32), ('colour_bgr', C.c_int32),
+              ('trail', C.c_int32), ('point_size', C.c_int32), ('pixels', C.c_void_p)]
+
+
 _SIGS = {
     'spa3d_version': (C.c_char_p, []),
     'spa3d_create': (C.c_int, [C.POINTER(Config), C.POINTER(C.c_void_p)]),
@@ -71,6 +79,8 @@ _SIGS = {
     'spa3d_score_from_preds': (C.c_int, [C.c_void_p, C.POINTER(Batch), C.POINTER(Outputs), C.POINTER(Scores), C.c_void_p]),
     'spa3d_tapvid3d_workspace_bytes': (C.c_int64, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     'spa3d_tapvid3d_from_preds': (C.c_int, [C.c_void_p, C.POINTER(Batch), C.POINTER(Outputs), C.POINTER(TapVid3D), C.c_void_p, C.c_int64, C.c_void_p]),
+    'spa3d_render_workspace_bytes': (C.c_int64, [C.c_void_p, C.c_int32, C.c_int32]),
+    'spa3d_render_tracks': (C.c_int, [C.c_void_p, C.POINTER(Render), C.c_void_p, C.c_int64, C.c_void_p]),
     'spa3d_op_median_rows': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     'spa3d_loss_and_grads': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Batch), C.c_float, C.c_void_p, C.c_int32,
                                        C.c_void_p, C.POINTER(Outputs), C.c_void_p, C.c_int64, C.c_void_p]),

@@ -10,6 +10,7 @@
 #include "gemm_plan.hpp"  // GemmDesc and the kernel choice (host-only)
 #include "score_row.hpp"  // per-track score arithmetic (host- and device-callable)
 #include "tapvid3d_row.hpp"  // TAPVid-3D metric counts of a row and the exact median select (host- and device-callable)
+#include "render_px.hpp"  // the arithmetic of spa3d_render_tracks: colour, projection, coverage, blend (host- and device-callable)
 
 // One translation unit is compiled for exactly ONE 16-bit activation type: bf16 (default) or IEEE fp16 (-DSPA_F16=1, BASELINE
 // cfg#5).  The raw 16-bit storage type is `bf16_t` (unsigned short) in both builds; what differs -- the two conversions, the MFMA
@@ -172,6 +173,20 @@ struct TvArgs {
   float* row_scale; float* qstats;
   int64_t nq, row0; int Q, T, scaling, fixed;
 };
+
+// The launches of spa3d_render_tracks (render.hip): the caller's tensors and the workspace arrays of the preparation.
+struct RenderArgs {
+  RpClip c;
+  const uint8_t* video; uint8_t* out; const float* tracks; const double* K; const double* E; const float* scores; const float* visible;
+  int32_t* pixels;     // caller's [N][T][2] or null
+  float* part;         // [RENDER_PARTS][2]: partial (min, max) of the finite scores
+  int32_t* pos;        // [N][T][2]
+  uint32_t* fl;        // [N][T]: flag words (render_px.hpp)
+  short* box;          // [T][N][4]: x0, y0, x1, y1 of everything point i draws in frame t (x0 > x1: nothing)
+  int nparts;
+};
+constexpr int RENDER_PARTS = 256;   // partial min / max pairs: one per workgroup of the reduction
+constexpr int RENDER_CHUNK = 256;   // points culled and compacted per round of the tile pass (= its workgroup size)
 
 struct Leaf {
   std::string name;
@@ -379,6 +394,10 @@ void k_loss_from_preds(spa3d_ctx*, const float* tracks, const float* vlog, int64
                        unsigned* poison, int NC = 3);
 void k_score_rows(spa3d_ctx*, const ScoreArgs& a);
 void k_score_reduce(spa3d_ctx*, const float* qstats, int64_t B, int Q, int K, double* out /*[B][8 + 4K]*/);
+void k_render_minmax(spa3d_ctx*, const RenderArgs& a);
+void k_render_points(spa3d_ctx*, const RenderArgs& a);
+void k_render_boxes(spa3d_ctx*, const RenderArgs& a);
+void k_render_tiles(spa3d_ctx*, const RenderArgs& a);
 void k_tv_ratio(spa3d_ctx*, const TvArgs& a);
 void k_tv_rows(spa3d_ctx*, const TvArgs& a);
 void k_tv_reduce(spa3d_ctx*, const float* qstats, int64_t B, int Q, double* out /*[B][24]*/);

@@ -1494,6 +1494,70 @@ int spa3d_tapvid3d_from_preds(spa3d_handle h, const spa3d_batch* b, const spa3d_
   return h->hip_err ? SPA3D_ERR_HIP : SPA3D_OK;
 }
 
+// ---- track overlays (render.hip, render_px.hpp) ----
+// The launches of one call.  Runs twice: dry (no launch, a counting arena: the workspace the call needs) and for real.  Workspace: the partial
+// min / max pairs, and -- when frames are drawn -- the positions, flag words and boxes of the N x T point-frames.
+static void render_body(spa3d_ctx* c, const spa3d_render* r) {
+  const int64_t n = (int64_t)r->N * r->T;
+  RenderArgs a{};
+  a.c = RpClip{r->N, r->T, r->H, r->W, r->coords, r->resize_h, r->resize_w, r->normalize != 0, r->use_visibility != 0, r->colour_bgr != 0, r->trail, r->point_size};
+  a.video = r->video; a.out = r->out; a.tracks = r->tracks; a.K = r->coords == 3 ? r->intrinsics : nullptr; a.E = r->coords == 3 ? r->extrinsics : nullptr;
+  a.scores = r->out ? r->scores : nullptr; a.visible = r->use_visibility ? r->visible : nullptr; a.pixels = r->pixels;
+  a.nparts = (int)std::min<int64_t>(RENDER_PARTS, (n + RENDER_CHUNK - 1) / RENDER_CHUNK);
+  const bool norm = a.scores && r->normalize;
+  if (norm) { a.part = (float*)c->ar.alloc(RENDER_PARTS * 2 * 4); k_render_minmax(c, a); }
+  if (r->out) {
+    a.pos = (int32_t*)c->ar.alloc(n * 8); a.fl = (uint32_t*)c->ar.alloc(n * 4); a.box = (short*)c->ar.alloc(n * 8);
+  }
+  k_render_points(c, a);
+  if (!r->out) return;
+  k_render_boxes(c, a);
+  k_render_tiles(c, a);
+}
+static int64_t render_need(spa3d_ctx* c, const spa3d_render* r) {
+  Arena saved = c->ar; const bool sd = c->dry;
+  c->ar = Arena(); c->ar.dry = true; c->dry = true;
+  render_body(c, r);
+  const int64_t need = c->ar.peak + 256;  // never 0: a call without a workspace is refused after the walk
+  c->ar = saved; c->dry = sd;
+  return need;
+}
+int64_t spa3d_render_workspace_bytes(spa3d_handle h, int32_t N, int32_t T) {
+  if (!h || N <= 0 || T <= 0) return -1;
+  const int64_t n = (int64_t)N * T;
+  auto up = [](int64_t b) { return (b + 255) & ~int64_t(255); };
+  return up(RENDER_PARTS * 2 * 4) + up(n * 8) + up(n * 4) + up(n * 8) + 256;
+}
+int spa3d_render_tracks(spa3d_handle h, const spa3d_render* r, void* ws, int64_t ws_bytes, void* stream) {
+  if (!h) return SPA3D_ERR_ARG;
+  h->err.clear(); h->hip_err = 0;
+  auto bad = [&](const std::string& m) { h->err = "render: " + m; return SPA3D_ERR_ARG; };
+  if (!r) return bad("spa3d_render is required");
+  if (r->N < 1 || r->T < 1) return bad("N = " + std::to_string(r->N) + ", T = " + std::to_string(r->T) + ": both must be positive");
+  if (r->H < 1 || r->H > RP_MAX_DIM || r->W < 1 || r->W > RP_MAX_DIM)
+    return bad("H = " + std::to_string(r->H) + ", W = " + std::to_string(r->W) + " are outside [1, " + std::to_string(RP_MAX_DIM) + "]");
+  if (!r->tracks) return bad("tracks is required");
+  if (r->coords != 2 && r->coords != 3) return bad("coords = " + std::to_string(r->coords) + " is neither 2 nor 3");
+  if (r->coords == 3 && (!r->intrinsics || !r->extrinsics)) return bad("coords == 3 needs the camera matrices (intrinsics, extrinsics)");
+  if (r->coords == 3 && (r->resize_h < 1 || r->resize_w < 1)) return bad("coords == 3 needs resize_h, resize_w >= 1");
+  if (!r->out && !r->pixels) return bad("nothing to do: out and pixels are both NULL");
+  if (r->out && (!r->video || !r->scores)) return bad("drawing needs video and scores");
+  if (r->use_visibility && !r->visible) return bad("use_visibility needs visible");
+  if (r->trail < 0 || r->trail > RP_MAX_TRAIL) return bad("trail = " + std::to_string(r->trail) + " is outside [0, " + std::to_string(RP_MAX_TRAIL) + "]");
+  if (r->point_size < 0 || r->point_size > RP_MAX_RADIUS)
+    return bad("point_size = " + std::to_string(r->point_size) + " is outside [0, " + std::to_string(RP_MAX_RADIUS) + "]");
+  // a launch holds fewer than 2^32 threads: one thread per point-frame, 256 per (frame, tile)
+  if ((int64_t)r->N * r->T > (int64_t)1 << 31) return bad("N x T = " + std::to_string((int64_t)r->N * r->T) + " point-frames exceed one launch (2^31)");
+  if (r->out && (int64_t)r->T * ((r->W + 63) / 64) * ((r->H + 15) / 16) >= (int64_t)1 << 24) return bad("T x tiles reaches 2^24 workgroups: more than one launch holds");
+  const int64_t need = render_need(h, r);
+  if (!ws || ws_bytes < need) return bad("workspace too small: need " + std::to_string(need) + " bytes");
+  h->stream = (hipStream_t)stream; h->dry = false;
+  h->ar = Arena(); h->ar.base = (char*)ws; h->ar.cap = ws_bytes;
+  render_body(h, r);
+  if (h->ar.overflow) { h->err = "internal: arena overflow"; return SPA3D_ERR_WORKSPACE; }
+  return h->hip_err ? SPA3D_ERR_HIP : SPA3D_OK;
+}
+
 int spa3d_loss_and_grads(spa3d_handle h, const float* params, const spa3d_batch* b, float denom, float* grads, int32_t accumulate,
                          float* loss3, spa3d_outputs* out, void* ws, int64_t ws_bytes, void* stream) {
   if (!h || !params || !grads) return SPA3D_ERR_ARG;

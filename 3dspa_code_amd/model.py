@@ -875,6 +875,148 @@ def evaluate_tapvid3d(model, variables, batches, depth_scalings=('median',), fix
   return {s: aggregate_tapvid3d(per_clip[s]) for s in depth_scalings}
 
 
+# ------------------------------------------------------------------------------------------------
+# track overlays (spa3d_render_tracks)
+# ------------------------------------------------------------------------------------------------
+def _video_u8(video: torch.Tensor) -> torch.Tensor:
+  """uint8 [T, H, W, 3] as it is; a float [T, 3, H, W] in [0, 1] as prepare_video_for_visualization (visualize.py:219-240) converts it: clip,
+  x 255, truncate."""
+  if video.dtype == torch.uint8:
+    if video.dim() != 4 or video.shape[-1] != 3:
+      raise ValueError(f'a uint8 video must be [T, H, W, 3], got {tuple(video.shape)}')
+    return video
+  if not video.is_floating_point() or video.dim() != 4 or video.shape[1] != 3:
+    raise ValueError(f'video must be uint8 [T, H, W, 3] or float [T, 3, H, W], got {video.dtype} {tuple(video.shape)}')
+  return (video.permute(0, 2, 3, 1).clamp(0, 1) * 255).to(torch.uint8).contiguous()
+
+
+def _camera(m, T, rows, name, dev):
+  m = m if isinstance(m, torch.Tensor) else torch.as_tensor(m, dtype=torch.float64)
+  m = m.to(device=dev, dtype=torch.float64)
+  if m.dim() == 2:
+    m = m.unsqueeze(0).expand(T, -1, -1)  # tiled over T, as project_all_tracks does
+  if tuple(m.shape) != (T, rows, rows):
+    raise ValueError(f'{name} must be [{rows}, {rows}] or [T, {rows}, {rows}], got {tuple(m.shape)}')
+  return m.contiguous()
+
+
+def _plane(t, N, T, name):
+  t = t if isinstance(t, torch.Tensor) else torch.as_tensor(t)
+  _require_cuda(t, name)
+  if t.dim() == 3 and t.shape[-1] == 1:
+    t = t[..., 0]
+  if tuple(t.shape) != (N, T):
+    raise ValueError(f'{name} must be [N, T] or [N, T, 1] = [{N}, {T}], got {tuple(t.shape)}')
+  return t.to(torch.float32).contiguous()
+
+
+def _render_call(r, tracks, intrinsics, extrinsics, resize):
+  """Fills the coordinate fields of a _lib.Render, sizes the workspace and calls spa3d_render_tracks on tracks' stream.  The converted tensors
+  and the workspace live until the call is enqueued; the caching allocator orders any reuse of their memory after it on that stream."""
+  lib = _lib.load()
+  N, T, nc = tracks.shape
+  dev = tracks.device
+  r.N, r.T, r.coords = N, T, nc
+  r.tracks = tracks.data_ptr()
+  if nc == 3:
+    if intrinsics is None or extrinsics is None:
+      raise ValueError('3-D tracks need intrinsics and extrinsics')
+    k, e = _camera(intrinsics, T, 3, 'intrinsics', dev), _camera(extrinsics, T, 4, 'extrinsics', dev)
+    r.intrinsics, r.extrinsics = k.data_ptr(), e.data_ptr()
+    r.resize_h, r.resize_w = int(resize[0]), int(resize[1])
+  h = _render_handle()
+  ws = torch.empty(max(int(lib.spa3d_render_workspace_bytes(h, N, T)), 256), dtype=torch.uint8, device=dev)
+  _lib.check(lib.spa3d_render_tracks(h, C.byref(r), ws.data_ptr(), ws.numel(), _stream(tracks)), h, 'spa3d_render_tracks')
+
+
+_RENDER_HANDLE = []
+
+
+def _render_handle():
+  """A handle of the render calls' own: spa3d_render_tracks uses its handle for the error message, the stream and the workspace arena only, and
+  must not reset those of a handle a model or the loss functions are using."""
+  if not _RENDER_HANDLE:
+    _RENDER_HANDLE.append(TrackAutoEncoder3D(num_output_frames=8, use_dino=False, use_depth=False, precision='fp32'))  # the model owns its handles
+  return _RENDER_HANDLE[0]._handle(0, 0)[0]
+
+
+def _tracks_f32(tracks):
+  _require_cuda(tracks, 'tracks')
+  if tracks.dim() != 3 or tracks.shape[-1] not in (2, 3):
+    raise ValueError(f'tracks must be [N, T, 3] points or [N, T, 2] pixel coordinates, got {tuple(tracks.shape)}')
+  return tracks.to(torch.float32).contiguous()
+
+
+def render_tracks(video, tracks, scores, visibs=None, intrinsics=None, extrinsics=None, trail: int = 5, point_size: int = 2, normalize: bool = True,
+                  resize=(1024, 1024), use_visibility: bool = False, colour_bgr: bool = False, out=None, return_pixels: bool = False):
+  """Score-coloured dots and trails drawn into a clip's frames on the GPU (spa3d_render_tracks): the counterpart of project_all_tracks +
+  normalize_scores + paint_point_track_with_colors (visualize.py:76-175, visualizer.py:23-45).  One clip, track-major: tracks [N, T, 3] with
+  intrinsics [3, 3] / [T, 3, 3] and extrinsics [4, 4] / [T, 4, 4], or [N, T, 2] pixel coordinates; scores, visibs [N, T] or [N, T, 1]; video
+  uint8 [T, H, W, 3] or float [T, 3, H, W] in [0, 1].  Returns uint8 [T, H, W, 3] (`out`, which may be the video itself, when given), and with
+  return_pixels also the int32 [N, T, 2] positions used.  The rasteriser is the library's own integer one (include/spa3d.h), not cv2's."""
+  _require_cuda(video, 'video')
+  vid = _video_u8(video).contiguous()
+  trk = _tracks_f32(tracks)
+  N, T = trk.shape[:2]
+  if vid.shape[0] != T:
+    raise ValueError(f'video has {vid.shape[0]} frames, tracks have {T}')
+  if out is None:
+    out = torch.empty_like(vid)
+  _require_cuda(out, 'out')
+  if out.dtype != torch.uint8 or tuple(out.shape) != tuple(vid.shape) or not out.is_contiguous():
+    raise ValueError(f'out must be a contiguous uint8 {tuple(vid.shape)} tensor')
+  r = _lib.Render()
+  r.H, r.W = vid.shape[1], vid.shape[2]
+  r.video, r.out = vid.data_ptr(), out.data_ptr()
+  sc = _plane(scores, N, T, 'scores')
+  r.scores = sc.data_ptr()
+  if visibs is not None:
+    vs = _plane(visibs, N, T, 'visibs')
+    r.visible = vs.data_ptr()
+  elif use_visibility:
+    raise ValueError('use_visibility needs visibs')
+  r.normalize, r.use_visibility, r.colour_bgr, r.trail, r.point_size = int(bool(normalize)), int(bool(use_visibility)), int(bool(colour_bgr)), int(trail), int(point_size)
+  pixels = torch.empty(N, T, 2, dtype=torch.int32, device=trk.device) if return_pixels else None
+  r.pixels = pixels.data_ptr() if return_pixels else None
+  _render_call(r, trk, intrinsics, extrinsics, resize)
+  return (out, pixels) if return_pixels else out
+
+
+def project_tracks(tracks_3d, intrinsics, extrinsics, H: int, W: int, resize=(1024, 1024)):
+  """project_all_tracks (visualize.py:125-175) followed by the painter's int(): int32 [N, T, 2] pixel positions (x, y) of [N, T, 3] points,
+  clipped to the image.  The same call as render_tracks with only the positions requested."""
+  trk = _tracks_f32(tracks_3d)
+  if trk.shape[-1] != 3:
+    raise ValueError(f'tracks_3d must be [N, T, 3], got {tuple(trk.shape)}')
+  r = _lib.Render()
+  r.H, r.W = int(H), int(W)
+  pixels = torch.empty(trk.shape[0], trk.shape[1], 2, dtype=torch.int32, device=trk.device)
+  r.pixels = pixels.data_ptr()
+  _render_call(r, trk, intrinsics, extrinsics, resize)
+  return pixels
+
+
+def visualize_npz(path: str, device='cuda', **options):
+  """Counterpart of visualizer.py's main (:149-203) up to the painted frames: reads the TIME-major file data.save_scores_npz writes (coords
+  [T, N, 3], coords_score [T, N] or [T, N, 1], video [T, 3, H, W] float or [T, H, W, 3] uint8, intrinsics, extrinsics, optional visibs),
+  transposes to track-major, renders on `device` and returns RGB uint8 [T, H, W, 3].  options: those of render_tracks.  Encoding a video
+  file is the caller's job."""
+  import numpy as np
+  d = np.load(path)
+  coords, score = np.asarray(d['coords']), np.asarray(d['coords_score'])
+  if score.ndim == 3:
+    score = score[..., 0]
+  to = lambda a, dt=None: torch.as_tensor(np.ascontiguousarray(a), dtype=dt).to(device)
+  visibs = None
+  if 'visibs' in d.files:
+    v = np.asarray(d['visibs'])
+    visibs = to((v[..., 0] if v.ndim == 3 else v).T.astype(np.float32))
+  cam = {}
+  if coords.shape[-1] == 3:
+    cam = dict(intrinsics=to(d['intrinsics'], torch.float64), extrinsics=to(d['extrinsics'], torch.float64))
+  return render_tracks(to(d['video']), to(coords.transpose(1, 0, 2), torch.float32), to(score.T, torch.float32), visibs, **cam, **options)
+
+
 _LOSS_HANDLES: Dict[Any, Any] = {}
 
 

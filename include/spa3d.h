@@ -15,6 +15,8 @@
  *                                   train.py:164-165,239-242 (intended semantics, repair R6)
  *   spa3d_tapvid3d_from_preds       tapvid3d_metrics.compute_tapvid3d_metrics(...)  evaluate_tapvid3d.py:99-109,196-208
  *                                   (third-party arithmetic upstream: restated from the published definition, parity unpinned)
+ *   spa3d_render_tracks             project_all_tracks + normalize_scores + paint_point_track_with_colors
+ *                                   visualize.py:15-175, visualizer.py:23-45,149-200 (own integer rasteriser, not cv2's)
  *   spa3d_uniform_noise             jax.random.uniform(PRNGKey(0), shape) track_autoencoder_3d.py:254-257
  *   spa3d_op_*                      single building blocks (attention.py, track_autoencoder.py:18-38),
  *                                   exported so tests can check each kernel against the oracle.
@@ -209,6 +211,64 @@ int64_t spa3d_tapvid3d_workspace_bytes(spa3d_handle h, int32_t B, int32_t Q, int
  * a model_kind 1 handle (no depth coordinate); a workspace that is too small (the message names the bytes needed). */
 int spa3d_tapvid3d_from_preds(spa3d_handle h, const spa3d_batch* b, const spa3d_outputs* preds, spa3d_tapvid3d* m, void* ws, int64_t ws_bytes,
                               void* stream);
+
+/* Score-coloured track overlays drawn on the device: the counterpart of upstream's visualiser (project_all_tracks, normalize_scores,
+ * score_to_color_bgr, paint_point_track_with_colors).  One clip per call; track-major layouts.  Kept from the reference: the primitives, their
+ * order, the colours, the projection and the integer pixel positions.  NOT kept: cv2's rasteriser -- LINE_AA and addWeighted are third-party
+ * arithmetic, parity with cv2 is not sought.  The rasteriser below is integer-only, so every output byte is defined and this comment is the
+ * contract (csrc/render_px.hpp is its only implementation; tests/render_util.py restates it in NumPy).
+ *
+ * Position of point i in frame t (pixels[i][t], a function of the coordinates alone):
+ *   coords == 3, in double, p = (x, y, z) of tracks[i][t] widened to double, K = intrinsics[t], E = extrinsics[t]:
+ *     sx = resize_w / W, sy = resize_h / H;  K00 *= sx, K02 *= sx, K11 *= sy, K12 *= sy (the other entries as given)
+ *     c_r = ((E[r][0] x + E[r][1] y) + E[r][2] z) + E[r][3]          r = 0..2, added left to right
+ *     h_r = (K[r][0] c_0 + K[r][1] c_1) + K[r][2] c_2                r = 0..2
+ *     u = h_0 / (h_2 + 1e-8), v = h_1 / (h_2 + 1e-8); NaN and +-inf become 0; u = u / sx, v = v / sy
+ *     u clipped to [0, W - 1], v to [0, H - 1], then truncated towards zero
+ *   coords == 2: each coordinate truncated towards zero (the reference's int()); a coordinate that is not finite or whose magnitude
+ *     exceeds 2^30 leaves the point-frame without a position: pixels reads (INT32_MIN, INT32_MIN) and nothing is drawn from or to it.
+ *   A position is in bounds when 0 <= x < W and 0 <= y < H.
+ * Colour of (t, i), s = scores[i][t]:
+ *   normalize != 0: min and max over the finite scores of the clip; fp32: s' = (s - min) / (max - min) if max > min, else s' = s - min.
+ *   normalize == 0: s' = s.  If s or s' is not finite, point i draws nothing in frame t.
+ *   score_to_color_bgr in double: q = s' clipped to [0, 1]; q < 0.5: ratio = q / 0.5, (b, g, r) = (int(255 ratio), int(255 ratio), 255);
+ *   else ratio = (q - 0.5) / 0.5, (b, g, r) = (255, int(255 (1 - ratio)), int(255 (1 - ratio))).  The three bytes written per pixel are
+ *   (b, g, r) when colour_bgr != 0, else (r, g, b).
+ * Drawing frame t: points in index order i = 0 .. N-1.  For each point first its segments for p = max(0, t - trail) .. t - 1 in that order,
+ *   segment p running from the position at frame p to the position at frame p + 1, each blended on its own; then its dot at the position of
+ *   frame t.  Everything of point i in frame t has the colour of (t, i).  A segment is drawn only if both ends are in bounds, a dot only if its
+ *   centre is.  visible is ignored unless use_visibility != 0 (upstream ignores it); then a dot needs visible[i][t] > 0.5 and a segment both
+ *   ends visible.  Later primitives go over earlier ones.
+ * Coverage, in units of 1/8 px: pixel (X, Y) has the 16 samples P = (8X + 2a + 1, 8Y + 2b + 1), a, b in 0..3; the integer position x is the
+ *   centre 8x + 4.  Dot of radius r = point_size around C: a sample is inside when |P - C|^2 <= (8r + 4)^2.  Segment A -> B: d = B - A,
+ *   L2 = d.d, u = (P - A).d;  u < 0 or L2 == 0: inside when |P - A|^2 <= 16;  u > L2: inside when |P - B|^2 <= 16;  otherwise, with
+ *   c = (P - A)_x d_y - (P - A)_y d_x: inside when |c| <= 4 (|d_x| + |d_y|) and c^2 <= 16 L2 (the first test is an exact reject that keeps c^2
+ *   within 64 bits at the size limit).  k = the number of inside samples, 0..16.
+ * Blend, per channel: w = k a, a = 179 for a segment (0.7 x 256) and 256 for a dot; out = (in (4096 - w) + col w + 2048) >> 12.  A pixel no
+ *   primitive touches keeps its input byte.
+ * Every pixel is read once and written once by the one thread that owns it (out == video is legal), no atomics on pixels, the min / max is an
+ * order-independent reduction: the same inputs give the same bytes on every run. */
+typedef struct {
+  int32_t N, T, H, W;              /* N, T >= 1; 1 <= H, W <= 16384 */
+  const uint8_t* video;            /* device [T,H,W,3], channel order = the caller's; colour_bgr says which */
+  uint8_t* out;                    /* device [T,H,W,3]; may be == video (in place).  NULL: only `pixels` is computed (video, scores not read) */
+  const float* tracks;             /* device [N,T,3] camera/world points, or [N,T,2] pixel coordinates when coords == 2 */
+  int32_t coords;                  /* 2 | 3 */
+  const double* intrinsics;        /* device [T,3,3], coords == 3 only */
+  const double* extrinsics;        /* device [T,4,4], coords == 3 only */
+  int32_t resize_h, resize_w;      /* project_all_tracks' resize_height / resize_width (1024, 1024); >= 1, coords == 3 only */
+  const float* scores;             /* device [N,T] */
+  const float* visible;            /* device [N,T] or NULL */
+  int32_t normalize, use_visibility, colour_bgr, trail, point_size;   /* trail 0..32, point_size 0..32 */
+  int32_t* pixels;                 /* device [N,T,2] or NULL: the integer positions used (x, y), INT32_MIN for "no position" */
+} spa3d_render;
+/* a sufficient workspace for any option */
+int64_t spa3d_render_workspace_bytes(spa3d_handle h, int32_t N, int32_t T);
+/* Asynchronous, allocates nothing, reads nothing back to the host.  SPA3D_ERR_ARG with a message, before the first launch: a missing pointer
+ * (tracks; video and scores when out is given; out and pixels both NULL; visible with use_visibility), coords outside {2, 3}, camera matrices
+ * or resize missing with coords == 3, a size, trail or point_size out of range, a workspace that is too small (the message names the bytes
+ * needed), more than 2^31 point-frames, or, when frames are drawn, 2^24 or more (frame, 64 x 16 tile) pairs: what one launch holds. */
+int spa3d_render_tracks(spa3d_handle h, const spa3d_render* r, void* ws, int64_t ws_bytes, void* stream);
 
 /* forward + loss + backward.  grads (flat f32, same layout as params) is OVERWRITTEN unless
  * accumulate!=0.  denom: global sum(query_tracks_visible) for data-parallel runs (the loss

@@ -1,0 +1,220 @@
+"""The arithmetic of spa3d_render_tracks (3dspa_code_amd/csrc/render_px.hpp) on the CPU: the header is plain C++ shared by the kernels of
+render.hip and this test, so a small driver (tests/host/render_px_check.cpp) is built with the host compiler and rasterises whole small scenes
+through it.  Every byte and every pixel position is compared with equality against the NumPy restatement of the contract
+(tests/render_util.py) and, for projection, normalisation and colours, against what the reference's own functions gave
+(tests/golden/visualize_golden.npz).  No GPU needed."""
+import os
+import shutil
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+import render_util as RU
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, 'tests', 'golden', 'visualize_golden.npz')
+
+
+@pytest.fixture(scope='module')
+def driver(tmp_path_factory):
+  cxx = shutil.which('g++') or shutil.which('c++')
+  if cxx is None:
+    pytest.fail('no host C++ compiler')
+  exe = str(tmp_path_factory.mktemp('render_px') / 'render_px_check')
+  r = subprocess.run([cxx, '-std=c++17', '-O1', '-ffp-contract=off', '-Wall', '-Wextra', '-Werror', os.path.join(ROOT, 'tests', 'host', 'render_px_check.cpp'), '-o', exe],
+                     capture_output=True, text=True)
+  assert r.returncode == 0, r.stderr[-3000:]
+  return exe
+
+
+@pytest.fixture(scope='module')
+def golden():
+  return dict(np.load(GOLDEN))
+
+
+def host_render(driver, video, tracks, scores, visible=None, K=None, E=None, resize=(1024, 1024), trail=5, point_size=2, normalize=True, use_visibility=False,
+                colour_bgr=False, windows=None, hw=None):
+  """The driver on one scene: (pixels int32 [N, T, 2], flags uint32 [N, T], painted video -- or, with windows [(t, y0, y1, x0, x1, bytes)] of
+  an hw = (H, W) clip, the painted windows)."""
+  N, T, C = tracks.shape
+  H, W = hw if hw is not None else video.shape[1:3]
+  blob = [struct.pack('<14i', N, T, H, W, C, resize[0], resize[1], int(normalize), int(use_visibility), int(colour_bgr), trail, point_size, int(visible is not None),
+                      len(windows) if windows else 0), np.ascontiguousarray(tracks, np.float32).tobytes()]
+  if C == 3:
+    blob += [np.ascontiguousarray(np.broadcast_to(K, (T, 3, 3)), np.float64).tobytes(), np.ascontiguousarray(np.broadcast_to(E, (T, 4, 4)), np.float64).tobytes()]
+  blob.append(np.ascontiguousarray(scores, np.float32).tobytes())
+  if visible is not None:
+    blob.append(np.ascontiguousarray(visible, np.float32).tobytes())
+  if windows:
+    for t, y0, y1, x0, x1, px in windows:
+      blob += [struct.pack('<5i', t, y0, y1, x0, x1), np.ascontiguousarray(px, np.uint8).tobytes()]
+  else:
+    blob.append(np.ascontiguousarray(video, np.uint8).tobytes())
+  out = subprocess.run([driver], input=b''.join(blob), capture_output=True, timeout=120)
+  assert out.returncode == 0, (out.returncode, out.stderr[-2000:])
+  n = N * T
+  pixels = np.frombuffer(out.stdout[:n * 8], np.int32).reshape(N, T, 2)
+  flags = np.frombuffer(out.stdout[n * 8:n * 12], np.uint32).reshape(N, T)
+  rest = np.frombuffer(out.stdout[n * 12:], np.uint8)
+  if not windows:
+    return pixels, flags, rest.reshape(video.shape)
+  res, o = [], 0
+  for t, y0, y1, x0, x1, px in windows:
+    res.append(rest[o:o + px.size].reshape(px.shape))
+    o += px.size
+  return pixels, flags, res
+
+
+def check_2d(driver, video, tracks, scores, visible=None, **opts):
+  pixels, _, out = host_render(driver, video, tracks, scores, visible, **opts)
+  pos = RU.pixels_2d(tracks)
+  assert np.array_equal(pixels, pos)
+  want = RU.render(video, pos, scores, visible, **opts)
+  assert np.array_equal(out, want), f'{int((out != want).sum())} bytes differ'
+  return out
+
+
+def test_golden_projection_normalisation_and_colours(driver, golden):
+  g = golden
+  H, W = (int(v) for v in g['hw'])
+  T = g['tracks'].shape[1]
+  for name in ('frames', 'single'):
+    K, E, rs = g['intrinsics_' + name], g['extrinsics_' + name], tuple(int(v) for v in g['resize_' + name])
+    pixels, flags, out = host_render(driver, g['video'], g['tracks'], g['scores'], K=K, E=E, resize=rs)
+    assert np.array_equal(pixels, g['pixels_' + name])   # the reference's int() of its own projection
+    Kt, Et = np.broadcast_to(K, (T, 3, 3)), np.broadcast_to(E, (T, 4, 4))
+    assert np.array_equal(RU.project(g['tracks'], Kt, Et, H, W, rs), g['pixels_' + name])
+    assert (flags & (1 << 24)).all()
+    col = np.stack([flags & 255, flags >> 8 & 255, flags >> 16 & 255], -1).astype(np.uint8)   # RGB in writing order
+    assert np.array_equal(col[..., ::-1], g['scores_bgr'])   # the reference's normalize_scores + score_to_color_bgr
+    want = RU.render(g['video'], g['pixels_' + name], g['scores'])
+    assert np.array_equal(out, want) and (out != g['video']).any()
+  # the restatement's normalisation is the reference's, bit for bit
+  mn, mx = g['scores'].min(), g['scores'].max()
+  assert np.array_equal(((g['scores'] - mn) / (mx - mn)).astype(np.float32), g['scores_norm']) and (g['const_norm'] == 0).all()
+
+
+def test_golden_colour_list(driver, golden):
+  """-0.3, 0, 0.5, 1, 1.7 and every k / 510 with their fp32 neighbours, unnormalised: the header, the restatement and the reference agree."""
+  cs, want = golden['colour_scores'], golden['colour_bgr']
+  n = cs.size
+  tracks = np.zeros((n, 1, 2), np.float32)
+  _, flags, _ = host_render(driver, np.zeros((1, 2, 2, 3), np.uint8), tracks, cs.reshape(n, 1), normalize=False, colour_bgr=True)
+  assert (flags & (1 << 24)).all()
+  got = np.stack([flags & 255, flags >> 8 & 255, flags >> 16 & 255], -1).astype(np.uint8).reshape(n, 3)   # BGR in writing order
+  assert np.array_equal(got, want)
+  assert np.array_equal(np.array([RU.colour_bgr(s) for s in cs], np.uint8), want)
+  col, ok = RU.colours(cs.reshape(n, 1), normalize=False, bgr=False)
+  assert ok.all() and np.array_equal(col.reshape(n, 3)[:, ::-1], want)
+
+
+@pytest.mark.parametrize('trail,radius', [(5, 2), (0, 0), (32, 7)])
+def test_scene_matches_restatement(driver, trail, radius):
+  video, tracks, scores, visible = RU.scene()   # 37 x 53, T = 7, N = 40
+  out = check_2d(driver, video, tracks, scores, trail=trail, point_size=radius)
+  assert (out != video).any()
+  assert np.array_equal(check_2d(driver, video, tracks, scores, visible, trail=trail, point_size=radius), out)   # visible is ignored unless asked for
+
+
+def test_use_visibility_and_bgr(driver):
+  video, tracks, scores, visible = RU.scene(seed=3)
+  a = check_2d(driver, video, tracks, scores, visible, use_visibility=True)
+  b = check_2d(driver, video, tracks, scores, visible)
+  assert (a != b).any()
+  c = check_2d(driver, video[..., ::-1], tracks, scores, visible, colour_bgr=True)
+  assert np.array_equal(c[..., ::-1], b)
+
+
+def test_order_zero_length_and_axis_segments(driver):
+  H, W, T = 24, 40, 3
+  video = np.full((T, H, W, 3), 90, np.uint8)
+  tracks = np.zeros((6, T, 2), np.float32)
+  tracks[0] = tracks[1] = (7.2, 9.9)                       # two points on one pixel, standing still: zero-length segments under the dots
+  tracks[2] = [(3, 3), (20, 3), (33, 3)]                    # horizontal
+  tracks[3] = [(5, 2), (5, 12), (5, 21)]                    # vertical
+  tracks[4] = [(10, 5), (20, 15), (28, 23)]                 # 45 degrees
+  tracks[5] = [(39, 0), (0, 23), (39, 23)]                  # corner to corner
+  scores = np.array([[0.0] * T, [1.0] * T, [0.2] * T, [0.4] * T, [0.6] * T, [0.8] * T], np.float32)
+  out = check_2d(driver, video, tracks, scores, normalize=False, trail=2, point_size=1)
+  assert tuple(out[2, 9, 7]) == (0, 0, 255)                # the higher index wins: score 1 is blue, score 0 red
+  swapped = check_2d(driver, video, tracks[[1, 0, 2, 3, 4, 5]], scores, normalize=False, trail=2, point_size=1)
+  assert np.array_equal(swapped, out)                       # same positions, colours by index: identical picture
+  out0 = check_2d(driver, video, tracks, scores[[1, 0, 2, 3, 4, 5]], normalize=False, trail=2, point_size=1)
+  assert tuple(out0[2, 9, 7]) == (255, 0, 0)
+  # radius 0: a dot is the centre pixel's disc of half a pixel, 12 of 16 samples
+  one = check_2d(driver, video, tracks[:1], scores[:1], normalize=False, trail=0, point_size=0)
+  assert (one[0] != video[0]).any(-1).sum() == 1 and tuple(one[0, 9, 7]) == tuple((90 * (4096 - 12 * 256) + np.array([255, 0, 0]) * 12 * 256 + 2048) >> 12)
+
+
+def test_truncation_and_bounds_of_2d_coordinates(driver):
+  H, W, T = 12, 20, 3
+  video = np.full((T, H, W, 3), 17, np.uint8)
+  tracks = np.array([[(-0.5, -0.99), (3.9, 2.2), (6.5, 4.0)],          # -0.5 truncates to 0 and is drawn
+                     [(5.0, 6.0), (float(W), 6.0), (9.0, 6.0)],        # x = W is out of bounds: both of its segments are skipped
+                     [(2.0, 9.0), (np.inf, 9.0), (4.0, 9.0)],
+                     [(2.0 ** 31, 3.0), (12.0, 3.0), (13.0, -1.0)]], np.float32)
+  scores = np.full((4, T), 0.1, np.float32)
+  pixels, _, out = host_render(driver, video, tracks, scores, normalize=False, trail=2, point_size=1)
+  assert pixels[0, 0].tolist() == [0, 0] and pixels[1, 1].tolist() == [W, 6] and pixels[2, 1].tolist() == [RU.NO_POS] * 2 and pixels[3, 0].tolist() == [RU.NO_POS] * 2
+  assert pixels[3, 2].tolist() == [13, -1]
+  out = check_2d(driver, video, tracks, scores, normalize=False, trail=2, point_size=1)
+  assert (out[0, 0, 0] != 17).any()                                   # the dot at (0, 0)
+  assert (out[2, 6, 4:8] == 17).all() and (out[2, 6, 9] != 17).any()  # frame 2 of point 1: only its dot, neither segment
+  assert (out[1, 6] == 17).all()                                      # frame 1 of point 1: nothing
+
+
+def test_scores_nan_inf_constant(driver):
+  video, tracks, scores, visible = RU.scene(T=4, N=12, H=20, W=30, seed=5)
+  s = scores.copy()
+  s[0, 1], s[1, 2], s[2, 0] = np.nan, np.inf, -np.inf
+  for normalize in (True, False):
+    out = check_2d(driver, video, tracks, s, normalize=normalize)
+    ref = check_2d(driver, video, np.delete(tracks, 0, 0), np.delete(s, 0, 0), normalize=normalize)
+    # point 0 draws nothing in frame 1 (NaN score), whatever its neighbours do; min / max come from the finite scores only
+    if normalize:
+      fin = s[np.isfinite(s)]
+      assert fin.min() == np.delete(s, 0, 0)[np.isfinite(np.delete(s, 0, 0))].min() and fin.max() == np.delete(s, 0, 0)[np.isfinite(np.delete(s, 0, 0))].max()
+      assert np.array_equal(out[1], ref[1])
+    const = np.full_like(s, 0.75)
+    c = check_2d(driver, video, tracks, const, normalize=normalize)
+    _, flags, _ = host_render(driver, video, tracks, const, normalize=normalize)
+    want = (255, 0, 0) if normalize else (127, 127, 255)   # max == min: s - min = 0 is red; raw 0.75 is half-way from white to blue
+    assert {(int(f) & 255, int(f) >> 8 & 255, int(f) >> 16 & 255) for f in flags.ravel()} == {want}
+    assert (c != video).any()
+  allnan = np.full_like(s, np.nan)
+  assert np.array_equal(check_2d(driver, video, tracks, allnan), video)
+
+
+def test_longest_segment_has_64_bit_headroom(driver):
+  """(0, 0) -> (W - 1, H - 1) at W = H = 16384: windows on and next to the line, the end caps included."""
+  S = 16384
+  tracks = np.array([[(0.0, 0.0), (S - 1.0, S - 1.0)], [(S - 1.0, 0.0), (0.0, S - 1.0)], [(0.0, 5000.0), (S - 1.0, 5003.0)]], np.float32)
+  scores = np.array([[0.0, 0.1], [0.0, 0.9], [0.0, 0.6]], np.float32)
+  rng = np.random.default_rng(1)
+  wins = []
+  for c in [0, 1, 2, 4097, 8191, 8192, 12345, S - 3, S - 2]:
+    for (x, y) in ((c, c), (S - 1 - c, c), (c, 5000 + (3 * c) // (S - 1))):
+      x0, y0 = max(0, min(x - 2, S - 6)), max(0, min(y - 2, S - 6))
+      wins.append((1, y0, y0 + 5, x0, x0 + 5, rng.integers(0, 256, (6, 6, 3), dtype=np.uint8)))
+  assert sum(w[5].size // 3 for w in wins) > 300
+  pixels, _, outs = host_render(driver, None, tracks, scores, normalize=False, trail=1, point_size=2, windows=wins, hw=(S, S))
+  pos = RU.pixels_2d(tracks)
+  assert np.array_equal(pixels, pos)
+  touched = 0
+  for (t, y0, y1, x0, x1, px), got in zip(wins, outs):
+    want = RU.render(px, pos, scores, normalize=False, trail=1, point_size=2, only=(t, y0, y1, x0, x1, S, S))
+    assert np.array_equal(got, want), (t, y0, x0)
+    touched += int((got != px).any(-1).sum())
+  assert touched > 200
+
+
+def test_long_segments(driver):
+  """Segments of about 512 px and one of 1280 px, steep and shallow, with radius-3 dots: products far beyond 32 bits, boxes spanning many pixels."""
+  T, H, W = 2, 140, 1300
+  video = np.random.default_rng(4).integers(0, 256, (T, H, W, 3), dtype=np.uint8)
+  tracks = np.array([[(2, 3), (513, 100)], [(2, 20), (514, 22)], [(2, 40), (515, 137)], [(700, 5), (189, 130)], [(3, 130), (3 + 512, 130 - 100)],
+                     [(10, 60), (1290, 75)], [(1295, 2), (1200, 139)]], np.float32)
+  scores = np.linspace(0, 1, tracks.shape[0] * T, dtype=np.float32).reshape(-1, T)
+  check_2d(driver, video, tracks, scores, normalize=False, trail=1, point_size=3)
