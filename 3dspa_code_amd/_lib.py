@@ -58,6 +58,14 @@ class Render(C.Structure):
               ('trail', C.c_int32), ('point_size', C.c_int32), ('pixels', C.c_void_p)]
 
 
+class Clip(C.Structure):
+  """spa3d_clip (include/spa3d.h): one clip of spa3d_build_batch -- device pointers, except `intrinsics` (host double[4] or NULL)."""
+  _fields_ = [('n_tracks', C.c_int32), ('T', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('tracks_2d', C.c_void_p), ('tracks_3d', C.c_void_p),
+              ('visible', C.c_void_p), ('depth_map', C.c_void_p), ('dino_map', C.c_void_p), ('Hp', C.c_int32), ('Wp', C.c_int32), ('dino_pool', C.c_void_p),
+              ('depth_pool', C.c_void_p), ('intrinsics', C.POINTER(C.c_double)), ('n_support', C.c_int32), ('n_query', C.c_int32),
+              ('support_index', C.c_void_p), ('query_index', C.c_void_p), ('query_frame', C.c_void_p)]
+
+
 _SIGS = {
     'spa3d_version': (C.c_char_p, []),
     'spa3d_create': (C.c_int, [C.POINTER(Config), C.POINTER(C.c_void_p)]),
@@ -81,6 +89,7 @@ _SIGS = {
     'spa3d_tapvid3d_from_preds': (C.c_int, [C.c_void_p, C.POINTER(Batch), C.POINTER(Outputs), C.POINTER(TapVid3D), C.c_void_p, C.c_int64, C.c_void_p]),
     'spa3d_render_workspace_bytes': (C.c_int64, [C.c_void_p, C.c_int32, C.c_int32]),
     'spa3d_render_tracks': (C.c_int, [C.c_void_p, C.POINTER(Render), C.c_void_p, C.c_int64, C.c_void_p]),
+    'spa3d_build_batch': (C.c_int, [C.c_void_p, C.POINTER(Clip), C.POINTER(Batch), C.c_void_p]),
     'spa3d_op_median_rows': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     'spa3d_loss_and_grads': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Batch), C.c_float, C.c_void_p, C.c_int32,
                                        C.c_void_p, C.POINTER(Outputs), C.c_void_p, C.c_int64, C.c_void_p]),

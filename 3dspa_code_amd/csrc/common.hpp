@@ -11,6 +11,7 @@
 #include "score_row.hpp"  // per-track score arithmetic (host- and device-callable)
 #include "tapvid3d_row.hpp"  // TAPVid-3D metric counts of a row and the exact median select (host- and device-callable)
 #include "render_px.hpp"  // the arithmetic of spa3d_render_tracks: colour, projection, coverage, blend (host- and device-callable)
+#include "build_row.hpp"  // the arithmetic of spa3d_build_batch: samplers, slot rule, the rounding to the feature type (host- and device-callable)
 
 // One translation unit is compiled for exactly ONE 16-bit activation type: bf16 (default) or IEEE fp16 (-DSPA_F16=1, BASELINE
 // cfg#5).  The raw 16-bit storage type is `bf16_t` (unsigned short) in both builds; what differs -- the two conversions, the MFMA
@@ -187,6 +188,24 @@ struct RenderArgs {
 };
 constexpr int RENDER_PARTS = 256;   // partial min / max pairs: one per workgroup of the reduction
 constexpr int RENDER_CHUNK = 256;   // points culled and compacted per round of the tile pass (= its workgroup size)
+
+// One launch of spa3d_build_batch (batch_build.hip): up to BB_CLIPS clips by value -- what fits in kernel arguments with room to spare -- and the
+// batch's buffers.  Clip g of the launch fills sample b0 + g.  Every pointer is a device pointer; the intrinsics and the map scales are already float32.
+constexpr int BB_CLIPS = 16;
+struct BbClip {
+  const float* tracks_2d; const float* tracks_3d; const float* visible; const float* depth; const float* dino_map;
+  const void* dino_pool; const void* depth_pool;   // rows in the feature type, copied
+  const int32_t* sidx; const int32_t* qidx; const int32_t* qframe;
+  int32_t n_tracks, T, H, W, Hp, Wp, n_support, n_query;
+  BrIntr k; float sw, sh;
+  int32_t depth_feat;   // the depth-feature channels come from the depth map (0: from depth_pool, or there are none)
+};
+struct BbArgs {
+  BbClip clip[BB_CLIPS];
+  float* st; float* sv; float* qp; float* qt; float* qv; int32_t* bf; void* dino; void* depthf;   // the batch: [B,N,T,3] [B,N,T] [B,Q,4] [B,Q,T,3] [B,Q,T] [B] [B,N,T,D] [B,N,T,DD]
+  int32_t b0, nclips, N, Q, T, D, DD;
+  int32_t vec;   // D % 4 == 0 and every DINO pointer 16-byte aligned: 16-byte accesses along the channel axis
+};
 
 struct Leaf {
   std::string name;
@@ -403,6 +422,7 @@ void k_tv_rows(spa3d_ctx*, const TvArgs& a);
 void k_tv_reduce(spa3d_ctx*, const float* qstats, int64_t B, int Q, double* out /*[B][24]*/);
 void k_tv_fill(spa3d_ctx*, float* p, int64_t n, float v);
 void k_median_rows(spa3d_ctx*, const float* x, int64_t rows, int64_t stride, int64_t n, float* out);
+void k_build_batch(spa3d_ctx*, const BbArgs& a, int out_type /* BR_F32 | BR_BF16 | BR_F16 */);
 template <typename T> void k_loss_bwd(spa3d_ctx*, const float* head, int64_t nq, int T_, const float* tgt, const float* tvis,
                                       const float* denom_dev, float l1w, float bcew, T* dhead, int NC = 3, const float* scale_dev = nullptr);
 void k_vis_count(spa3d_ctx*, const float* tvis, int64_t n, float* out, unsigned* poison);

@@ -1,20 +1,24 @@
 """Host-side steps either side of the hot path, with the reference's names:
 
   prepare_3d_batch                         data_loader.py:56-110   support/query split + query-point sampling
+  draw_split / build_batch                 data_loader.py:67-81, inference.py:541-590 for many clips in one device call (spa3d_build_batch)
   convert_predictions_to_tapvid3d_format   evaluate_tapvid3d.py:39-59
   collate_ragged / split_ragged            evaluate_tapvid3d.py:318-348 as batches of clips with differing track / query counts
   load_checkpoint / save_checkpoint        inference.py:450-508, evaluate_tapvid3d.py:247-285 / train.py:389-393 (a stub upstream)
 
-Plain NumPy / torch glue: no arithmetic worth a kernel.  The metric arithmetic of TAPVid-3D is model.tapvid3d_predictions (upstream
+Plain NumPy / torch glue: no arithmetic worth a kernel -- except build_batch, whose host side only validates and marshals.  The metric arithmetic of TAPVid-3D is model.tapvid3d_predictions (upstream
 it is the un-vendored `tapnet` package)."""
 from __future__ import annotations
 
+import ctypes as C
 import dataclasses
 import os
 from typing import Any, Dict, Optional
 
 import numpy as np
 import torch
+
+from . import _lib
 
 
 def prepare_3d_batch(example, num_support_tracks: int = 2048, num_query_tracks: int = 2048, num_frames: int = 150, use_dino: bool = True,
@@ -50,6 +54,223 @@ def prepare_3d_batch(example, num_support_tracks: int = 2048, num_query_tracks: 
     batch['dino_features'] = dev(np.asarray(example['dino_features'])[support_indices], feature_dtype)
   if use_depth and 'depth_features' in example:
     batch['depth_features'] = dev(np.asarray(example['depth_features'])[support_indices], feature_dtype)
+  return batch
+
+
+def draw_split(num_total: int, num_support: int, num_query: int, num_frames: int):
+  """The support / query split of one clip: (support indices, query indices, query frames).  The RNG call sequence of data_loader.py:67-81 and
+  inference.py:560-572 on NumPy's global generator -- one `permutation(num_total)`, then one `randint(0, num_frames)` per query -- so a seeded
+  run picks what a seeded prepare_3d_batch (or the reference) picks.  IndexError when the clip has too few tracks, as prepare_3d_batch."""
+  indices = np.random.permutation(num_total)
+  support = indices[:num_support]
+  query = indices[num_support:num_support + num_query]
+  if len(support) < num_support or len(query) < num_query:
+    raise IndexError(f'clip has {num_total} tracks, need {num_support} support + {num_query} query')
+  frames = np.array([np.random.randint(0, num_frames) for _ in range(num_query)], dtype=np.int64)
+  return support, query, frames
+
+
+def _shape(x):
+  return tuple(int(v) for v in (x.shape if hasattr(x, 'shape') else np.asarray(x).shape))
+
+
+def _index_array(x, name, lo, hi, what):
+  """A host int64 vector whose entries all lie in [lo, hi); ValueError otherwise (the device never sees an index that was not checked here)."""
+  a = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+  if a.ndim != 1:
+    raise ValueError(f'{name} must be one-dimensional, got shape {a.shape}')
+  if a.size and not np.issubdtype(a.dtype, np.integer):
+    if not np.all(np.asarray(a, dtype=np.float64) == np.floor(np.asarray(a, dtype=np.float64))):
+      raise ValueError(f'{name} must hold integers')
+  a = a.astype(np.int64)
+  if a.size and (a.min() < lo or a.max() >= hi):
+    raise ValueError(f'{name} has entries outside [{lo}, {hi}) ({what})')
+  return a
+
+
+def build_batch(clips, model=None, num_support_tracks: int = 2048, num_query_points: int = 512, num_frames: Optional[int] = None, splits=None,
+                device='cuda'):
+  """Clips -> the batch dict that model.apply / model.score / model.tapvid3d / TrainState.train_step take, in ONE device call (spa3d_build_batch,
+  include/spa3d.h): the split, the lift, the feature sampling and the padded ragged layout, only for the rows that were picked, the feature
+  planes written in the model's activation type.  What inference.py:541-590 does per clip over ALL of its tracks, and prepare_3d_batch on the host.
+
+  clips: a list of dicts (NumPy arrays or tensors).  Always `tracks_2d` [n,Tc,2] (pixels) and `visible` [n,Tc] or [n,Tc,1]; for the 3-D
+  positions `tracks_3d` [n,Tc,3] or `depth` [Tc,H,W(,1)] to lift with (optional `intrinsics` (fx, fy, cx, cy)); optional DINO as `dino_map`
+  [Tc,Hp,Wp,D] + `video_shape` (T,H,W,3) or as already-sampled `dino_features` [n,Tc,D]; optional `depth_features` [n,Tc,C] (without it, and
+  with model.use_depth, the depth features are sampled from `depth`, model.depth_feature_dim channels).  Tc <= num_frames (default:
+  model.num_output_frames); shorter clips are zero-padded and `boundary_frame` says where they end.
+  splits: None = draw_split per clip with min(count, what the clip has), or one (support_index, query_index, query_frame) triple per clip.
+  Everything is validated on the host first (ValueError; IndexError from the draw), the index arrays are uploaded once."""
+  if model is None:
+    raise ValueError('build_batch needs the model (precision and feature widths come from it)')
+  if getattr(model, '_kind', 0) == 1:
+    raise ValueError('build_batch is not available for the 2-D model')
+  if not clips:
+    raise ValueError('build_batch needs at least one clip')
+  B = len(clips)
+  if splits is not None and len(splits) != B:
+    raise ValueError(f'splits must have one entry per clip ({B}), got {len(splits)}')
+  T = int(num_frames) if num_frames is not None else int(model.num_output_frames)
+  if T < 1 or num_support_tracks < 1 or num_query_points < 0:
+    raise ValueError('num_frames and num_support_tracks must be positive, num_query_points non-negative')
+  # ---- host pass: shapes, sources, splits.  Nothing touches the device before every clip has passed.
+  plans, dino_dims, depth_dims = [], set(), set()
+  for i, clip in enumerate(clips):
+    bad = lambda m: ValueError(f'clip {i}: {m}')
+    if clip.get('tracks_2d') is None or clip.get('visible') is None:
+      raise bad('tracks_2d and visible are required')
+    s2 = _shape(clip['tracks_2d'])
+    if len(s2) != 3 or s2[2] != 2 or s2[0] < 1 or s2[1] < 1:
+      raise bad(f'tracks_2d must be [n,T,2], got {s2}')
+    n, Tc = s2[:2]
+    if Tc > T:
+      raise bad(f'has {Tc} frames, the batch has {T}')
+    sv = _shape(clip['visible'])
+    if sv not in ((n, Tc), (n, Tc, 1)):
+      raise bad(f'visible must be {(n, Tc)} or {(n, Tc, 1)}, got {sv}')
+    has3, depth = clip.get('tracks_3d') is not None, clip.get('depth')
+    if has3 and _shape(clip['tracks_3d']) != (n, Tc, 3):
+      raise bad(f'tracks_3d must be {(n, Tc, 3)}, got {_shape(clip["tracks_3d"])}')
+    H = W = 0
+    if depth is not None:
+      sd = _shape(depth)
+      if len(sd) == 4 and sd[3] == 1:
+        sd = sd[:3]
+      if len(sd) != 3 or sd[0] != Tc or sd[1] < 1 or sd[2] < 1:
+        raise bad(f'depth must be [T,H,W] or [T,H,W,1] with T = {Tc}, got {_shape(depth)}')
+      H, W = sd[1], sd[2]
+    if not has3 and depth is None:
+      raise bad('needs tracks_3d, or depth to lift tracks_2d with')
+    if clip.get('video_shape') is not None:
+      vs = tuple(int(v) for v in clip['video_shape'])
+      if len(vs) != 4 or vs[1] < 1 or vs[2] < 1:
+        raise bad(f'video_shape must be (T,H,W,3), got {vs}')
+      if depth is not None and (vs[1], vs[2]) != (H, W):
+        raise bad(f'video_shape {vs} and depth {(H, W)} disagree on the frame size')
+      H, W = vs[1], vs[2]
+    intr = None
+    if clip.get('intrinsics') is not None:
+      intr = [float(v) for v in np.asarray(clip['intrinsics'], dtype=np.float64).reshape(-1)]
+      if len(intr) != 4:
+        raise bad('intrinsics must be (fx, fy, cx, cy)')
+    dino = None
+    if model.use_dino and (clip.get('dino_map') is not None or clip.get('dino_features') is not None):
+      if clip.get('dino_map') is not None and clip.get('dino_features') is not None:
+        raise bad('dino_map and dino_features are both given')
+      if clip.get('dino_map') is not None:
+        sm = _shape(clip['dino_map'])
+        if len(sm) != 4 or sm[0] != Tc or min(sm) < 1:
+          raise bad(f'dino_map must be [T,Hp,Wp,D] with T = {Tc}, got {sm}')
+        if H < 1:
+          raise bad('dino_map needs video_shape (or depth) for the frame size')
+        dino = ('map', sm)
+      else:
+        sm = _shape(clip['dino_features'])
+        if len(sm) != 3 or sm[:2] != (n, Tc) or sm[2] < 1:
+          raise bad(f'dino_features must be [{n},{Tc},D], got {sm}')
+        dino = ('pool', sm)
+      dino_dims.add(sm[-1])
+    else:
+      dino_dims.add(0)
+    dfeat = None
+    if model.use_depth and (clip.get('depth_features') is not None or depth is not None):
+      if clip.get('depth_features') is not None:
+        sm = _shape(clip['depth_features'])
+        if len(sm) != 3 or sm[:2] != (n, Tc) or sm[2] < 1:
+          raise bad(f'depth_features must be [{n},{Tc},C], got {sm}')
+        if depth is not None and has3:
+          raise bad('depth and depth_features are both given (and tracks_3d needs no lift)')
+        dfeat = 'pool'
+        depth_dims.add(sm[2])
+      else:
+        dfeat = 'map'
+        depth_dims.add(int(model.depth_feature_dim))
+    else:
+      depth_dims.add(0)
+    if splits is None:
+      ns = min(int(num_support_tracks), n)
+      si, qi, qf = draw_split(n, ns, min(int(num_query_points), n - ns), Tc)
+    else:
+      if len(splits[i]) != 3:
+        raise bad('a split is (support_index, query_index, query_frame)')
+      si = _index_array(splits[i][0], f'clip {i}: support_index', 0, n, f'the clip has {n} tracks')
+      qi = _index_array(splits[i][1], f'clip {i}: query_index', 0, n, f'the clip has {n} tracks')
+      qf = _index_array(splits[i][2], f'clip {i}: query_frame', 0, Tc, f'the clip has {Tc} frames')
+      if len(qf) != len(qi):
+        raise bad(f'{len(qi)} query indices but {len(qf)} query frames')
+    if len(si) < 1:
+      raise bad('needs at least one support track')
+    plans.append(dict(n=n, Tc=Tc, H=H, W=W, has3=has3, dino=dino, dfeat=dfeat, intr=intr, si=si, qi=qi, qf=qf))
+  if len(dino_dims) != 1 or len(depth_dims) != 1:
+    raise ValueError('every clip of a batch must carry the same features with the same widths '
+                     f'(DINO widths {sorted(dino_dims)}, depth widths {sorted(depth_dims)}; 0 = none)')
+  D, DD = dino_dims.pop(), depth_dims.pop()
+  if D and D != model.dino_feature_dim:
+    raise ValueError(f'the clips carry {D} DINO channels, the model has dino_feature_dim = {model.dino_feature_dim}')
+  N, Q = max(len(p['si']) for p in plans), max(max(len(p['qi']) for p in plans), 1)
+  # ---- device pass
+  dev = torch.device(device)
+  if dev.type != 'cuda':
+    raise _lib.Spa3dError('build_batch runs on the GPU: the 3DSPA hot path is HIP-only (no CPU fallback)')
+  if dev.index is None:
+    dev = torch.device('cuda', torch.cuda.current_device())
+  h = model._handle(D, DD)[0]
+  act = model.act_dtype
+
+  def up(x, dtype=torch.float32):
+    t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
+    return t.to(device=dev, dtype=dtype).contiguous()
+
+  index = torch.from_numpy(np.concatenate([np.concatenate([p['si'], p['qi'], p['qf']]) for p in plans]).astype(np.int32)).to(dev)  # ONE upload
+  batch = {
+      'support_tracks': torch.empty(B, N, T, 3, dtype=torch.float32, device=dev), 'support_tracks_visible': torch.empty(B, N, T, 1, dtype=torch.float32, device=dev),
+      'query_points': torch.empty(B, Q, 4, dtype=torch.float32, device=dev), 'query_tracks': torch.empty(B, Q, T, 3, dtype=torch.float32, device=dev),
+      'query_tracks_visible': torch.empty(B, Q, T, 1, dtype=torch.float32, device=dev), 'boundary_frame': torch.empty(B, dtype=torch.int32, device=dev),
+  }
+  if D:
+    batch['dino_features'] = torch.empty(B, N, T, D, dtype=act, device=dev)
+  if DD:
+    batch['depth_features'] = torch.empty(B, N, T, DD, dtype=act, device=dev)
+  arr, keep, off = (_lib.Clip * B)(), [index], 0
+  for i, (clip, p) in enumerate(zip(clips, plans)):
+    c = arr[i]
+    c.n_tracks, c.T, c.H, c.W = p['n'], p['Tc'], p['H'], p['W']
+    tens = {'tracks_2d': up(clip['tracks_2d']), 'visible': up(clip['visible'])}
+    if p['has3']:
+      tens['tracks_3d'] = up(clip['tracks_3d'])
+    if clip.get('depth') is not None and (not p['has3'] or p['dfeat'] == 'map'):
+      tens['depth_map'] = up(clip['depth'])
+    if p['dino'] is not None and p['dino'][0] == 'map':
+      tens['dino_map'] = up(clip['dino_map'])
+      c.Hp, c.Wp = p['dino'][1][1], p['dino'][1][2]
+    elif p['dino'] is not None:
+      tens['dino_pool'] = up(clip['dino_features'], act)
+    if p['dfeat'] == 'pool':
+      tens['depth_pool'] = up(clip['depth_features'], act)
+    for k, t in tens.items():
+      setattr(c, k, t.data_ptr())
+      keep.append(t)
+    if p['intr'] is not None:
+      intr = (C.c_double * 4)(*p['intr'])
+      keep.append(intr)
+      c.intrinsics = C.cast(intr, C.POINTER(C.c_double))
+    ns, nq = len(p['si']), len(p['qi'])
+    c.n_support, c.n_query = ns, nq
+    c.support_index = index.data_ptr() + 4 * off
+    c.query_index = index.data_ptr() + 4 * (off + ns)
+    c.query_frame = index.data_ptr() + 4 * (off + ns + nq)
+    off += ns + 2 * nq
+  out = _lib.Batch()
+  out.B, out.N, out.Q, out.T = B, N, Q, T
+  for k in ('support_tracks', 'support_tracks_visible', 'query_points', 'query_tracks', 'query_tracks_visible', 'boundary_frame', 'dino_features', 'depth_features'):
+    if k in batch:
+      setattr(out, k, batch[k].data_ptr())
+  with torch.cuda.device(dev):
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(_lib.load().spa3d_build_batch(h, arr, C.byref(out), stream), h, 'spa3d_build_batch')
+  del keep  # the call is enqueued: the allocator recycles these on the same stream only
+  batch['support_count'] = torch.tensor([len(p['si']) for p in plans], dtype=torch.int32, device=dev)
+  batch['query_count'] = torch.tensor([len(p['qi']) for p in plans], dtype=torch.int32, device=dev)
   return batch
 
 

@@ -17,6 +17,8 @@
  *                                   (third-party arithmetic upstream: restated from the published definition, parity unpinned)
  *   spa3d_render_tracks             project_all_tracks + normalize_scores + paint_point_track_with_colors
  *                                   visualize.py:15-175, visualizer.py:23-45,149-200 (own integer rasteriser, not cv2's)
+ *   spa3d_build_batch               split + lift_2d_to_3d + sample_*_features_for_tracks + batch dict, for many clips at once
+ *                                   inference.py:541-590, data_loader.py:56-110
  *   spa3d_uniform_noise             jax.random.uniform(PRNGKey(0), shape) track_autoencoder_3d.py:254-257
  *   spa3d_op_*                      single building blocks (attention.py, track_autoencoder.py:18-38),
  *                                   exported so tests can check each kernel against the oracle.
@@ -269,6 +271,55 @@ int64_t spa3d_render_workspace_bytes(spa3d_handle h, int32_t N, int32_t T);
  * or resize missing with coords == 3, a size, trail or point_size out of range, a workspace that is too small (the message names the bytes
  * needed), more than 2^31 point-frames, or, when frames are drawn, 2^24 or more (frame, 64 x 16 tile) pairs: what one launch holds. */
 int spa3d_render_tracks(spa3d_handle h, const spa3d_render* r, void* ws, int64_t ws_bytes, void* stream);
+
+/* Clips to model batches in one call: the support / query split, the 2-D -> 3-D lift, the DINO and depth-feature sampling and the padded,
+ * ragged batch layout that spa3d_forward, spa3d_score, spa3d_loss_and_grads and spa3d_tapvid3d_from_preds read -- what inference.py:541-590 and
+ * data_loader.py:56-110 do on the host, clip by clip, for every track of a clip.  Only the picked rows are computed, and they are written
+ * straight into the batch, the feature planes in the handle's precision.
+ *
+ * A clip is a pool of n_tracks tracks over its own T frames (T <= the batch's T) and two index lists: batch slot i of the clip's sample reads
+ * pool track support_index[i] (i < n_support) resp. query_index[i] (i < n_query); query_frame[i] is the frame of query i's query point.
+ * Padding -- a slot at or beyond the clip's count, a frame at or beyond the clip's T, an index outside [0, n_tracks) -- is written as zeros,
+ * so every byte of every output is defined.  The indices are not checked on the host (they are device arrays): validate them before the call.
+ * Per live (slot, frame), with n the pool track and t the frame:
+ *   position (support_tracks / query_tracks)   tracks_3d[n][t] if the clip has tracks_3d, else what spa3d_op_lift_2d_to_3d gives for
+ *                                              tracks_2d[n][t] on depth_map with the clip's intrinsics
+ *   visibility (..._visible)                   visible[n][t]
+ *   dino_features (support slots)              the row dino_pool[n][t] copied, else what spa3d_op_sample_dino gives for the point on
+ *                                              dino_map (Hp x Wp texels over the H x W video), rounded ONCE to the feature type
+ *   depth_features (support slots)             the row depth_pool[n][t] copied, else the first depth_feature_dim channels of what
+ *                                              spa3d_op_sample_depth_features gives (d, d / 10, d - d_prev for t > 0, zeros), rounded once
+ *   query_points[q]                            (query_frame[q], x, y, z) of the query's position at that frame; zeros when query_frame[q] is
+ *                                              outside the clip's [0, T)
+ *   boundary_frame[b]                          the clip's T
+ * The values are bit for bit those of the three spa3d_op_ samplers (float32, the reference's operation order; csrc/build_row.hpp is the only
+ * implementation of the arithmetic and of the rounding: round to nearest even to bfloat16 or IEEE half).  One wave per (clip, frame, slot),
+ * walked frame-major; no atomics: two calls give the same bytes.
+ *
+ * out: B, N, Q, T and the device buffers to fill (the const of spa3d_batch's pointers is cast away): support_tracks, support_tracks_visible,
+ * boundary_frame always; query_points, query_tracks, query_tracks_visible when Q > 0.  dino_features == NULL: no clip may carry DINO (map or
+ * pool); given: every clip carries one of the two.  The same holds for depth_features, where depth_map alone counts as the source (it also
+ * serves the lift).  D = dino_feature_dim and the depth width = depth_feature_dim of the handle's config; noise and discretize are not touched.
+ * Asynchronous on `stream`, allocates nothing, takes no workspace, reads nothing back; clips[0 .. B) (host) and each clip's intrinsics are
+ * consumed before the call returns.  Up to 16 clips travel by value in one launch; a larger B takes several launches.
+ * SPA3D_ERR_ARG with a message, before the first launch: a missing pointer; n_support outside [1, N] or n_query outside [0, Q]; a clip T
+ * outside [1, out->T]; a map and a pool both given for one feature (for depth: depth_pool together with a depth_map that no lift needs); a
+ * feature the handle or the batch does not have; neither tracks_3d nor a depth_map to lift with; a map without tracks_2d or sizes; a
+ * model_kind 1 handle. */
+typedef struct {            /* one clip; device pointers except intrinsics */
+  int32_t n_tracks, T, H, W;               /* pool size, the clip's own frame count (<= batch T), video size */
+  const float* tracks_2d;                  /* [n_tracks,T,2] pixels; needed to lift or to sample */
+  const float* tracks_3d;                  /* [n_tracks,T,3] or NULL = lift from depth_map */
+  const float* visible;                    /* [n_tracks,T] */
+  const float* depth_map;                  /* [T,H,W] f32 or NULL */
+  const float* dino_map; int32_t Hp, Wp;   /* [T,Hp,Wp,D] f32 or NULL */
+  const void*  dino_pool;                  /* [n_tracks,T,D] in the output type, or NULL (prepare_3d_batch's layout) */
+  const void*  depth_pool;                 /* [n_tracks,T,depth_feature_dim] in the output type, or NULL */
+  const double* intrinsics;                /* host double[4] or NULL = lift_2d_to_3d's default */
+  int32_t n_support, n_query;
+  const int32_t *support_index, *query_index, *query_frame;   /* device */
+} spa3d_clip;
+int spa3d_build_batch(spa3d_handle h, const spa3d_clip* clips /* host [B] */, spa3d_batch* out, void* stream);
 
 /* forward + loss + backward.  grads (flat f32, same layout as params) is OVERWRITTEN unless
  * accumulate!=0.  denom: global sum(query_tracks_visible) for data-parallel runs (the loss
