@@ -11,6 +11,8 @@ CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libspa3d_hip.so')
 SOURCES = ['kernels.hip', 'gemm_generic.hip', 'gemm_fast.hip', 'gemm_tnb.hip', 'gemm_ntb.hip', 'gemm_rs.hip', 'mlp_fused.hip', 'attention.hip', 'attention_fused.hip', 'qkv_attn.hip', 'ops.hip', 'samplers.hip', 'tapvid3d.hip', 'render.hip', 'batch_build.hip', 'model.hip']
 F16_SOURCES = ['kernels.hip', 'gemm_generic.hip', 'gemm_fast.hip', 'gemm_tnb.hip', 'gemm_ntb.hip', 'gemm_rs.hip', 'mlp_fused.hip', 'attention.hip', 'attention_fused.hip', 'qkv_attn.hip', 'ops.hip', 'model.hip']
+HEADERS = [os.path.join(CSRC, h) for h in ('common.hpp', 'gemm_plan.hpp', 'tn_args.hpp', 'ablate.inc', 'attn_common.hpp', 'score_row.hpp', 'tapvid3d_row.hpp', 'render_px.hpp',
+                                            'build_row.hpp')] + [os.path.join(HERE, '..', 'include', 'spa3d.h')]
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off', '-Wall', '-Wno-unused-function', '-Wno-inline-asm',
          '-Wno-unused-variable', '-Wno-unused-but-set-variable']
 
@@ -31,7 +33,6 @@ def _stale(out, deps):
 
 def build(force: bool = False, verbose: bool = True) -> str:
   hipcc = _hipcc()
-  hdrs = [os.path.join(CSRC, 'common.hpp'), os.path.join(CSRC, 'gemm_plan.hpp'), os.path.join(CSRC, 'tn_args.hpp'), os.path.join(CSRC, 'ablate.inc'), os.path.join(CSRC, 'attn_common.hpp'), os.path.join(CSRC, 'score_row.hpp'), os.path.join(CSRC, 'tapvid3d_row.hpp'), os.path.join(CSRC, 'render_px.hpp'), os.path.join(CSRC, 'build_row.hpp'), os.path.join(HERE, '..', 'include', 'spa3d.h')]
   objdir = os.path.join(HERE, 'build')
   os.makedirs(objdir, exist_ok=True)
   srcs = [s for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
@@ -41,7 +42,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
   for s, o, extra in units:
     src = os.path.join(CSRC, s)
     obj = os.path.join(objdir, o)
-    if force or _stale(obj, [src] + hdrs):
+    if force or _stale(obj, [src] + HEADERS):
       jobs.append((src, obj, extra))
 
   def cc(job):

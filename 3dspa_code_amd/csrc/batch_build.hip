@@ -1,4 +1,4 @@
-// batch_build.hip -- the kernel of spa3d_build_batch (include/spa3d.h): clips -> the padded model batch, in one launch per BB_CLIPS clips.
+// batch_build.hip -- spa3d_build_batch (include/spa3d.h), the kernel first, the entry point below it: clips -> the padded model batch, in one launch per BB_CLIPS clips.
 // One wave per (clip, frame, slot); a clip's N support slots come first, then its Q query slots.  The arithmetic is build_row.hpp's (the
 // samplers' float32 operation order, the slot rule, one rounding to the feature type), which the g++ host test runs too.
 //
@@ -11,8 +11,27 @@
 // row by the wave of its query frame (or, for a padded slot, of frame 0).  No atomics: two runs give the same bytes.
 // The feature type is a template parameter and the 16-bit roundings are explicit (build_row.hpp): compiled once.
 #include "common.hpp"
+#include "build_row.hpp"  // samplers, slot rule, the rounding to the feature type (host- and device-callable)
 
 #include <algorithm>
+
+// One launch of spa3d_build_batch: up to BB_CLIPS clips by value -- what fits in kernel arguments with room to spare -- and the
+// batch's buffers.  Clip g of the launch fills sample b0 + g.  Every pointer is a device pointer; the intrinsics and the map scales are already float32.
+constexpr int BB_CLIPS = 16;
+struct BbClip {
+  const float* tracks_2d; const float* tracks_3d; const float* visible; const float* depth; const float* dino_map;
+  const void* dino_pool; const void* depth_pool;   // rows in the feature type, copied
+  const int32_t* sidx; const int32_t* qidx; const int32_t* qframe;
+  int32_t n_tracks, T, H, W, Hp, Wp, n_support, n_query;
+  BrIntr k; float sw, sh;
+  int32_t depth_feat;   // the depth-feature channels come from the depth map (0: from depth_pool, or there are none)
+};
+struct BbArgs {
+  BbClip clip[BB_CLIPS];
+  float* st; float* sv; float* qp; float* qt; float* qv; int32_t* bf; void* dino; void* depthf;   // the batch: [B,N,T,3] [B,N,T] [B,Q,4] [B,Q,T,3] [B,Q,T] [B] [B,N,T,D] [B,N,T,DD]
+  int32_t b0, nclips, N, Q, T, D, DD;
+  int32_t vec;   // D % 4 == 0 and every DINO pointer 16-byte aligned: 16-byte accesses along the channel axis
+};
 
 namespace SPA_NS {
 
@@ -146,3 +165,72 @@ void k_build_batch(spa3d_ctx* c, const BbArgs& a, int out_type) {
 }
 
 }  // namespace SPA_NS
+
+// ---- the entry point ----
+extern "C" {
+
+// Everything is checked for every clip before the first launch; then one launch per BB_CLIPS clips, their descriptors by value.
+int spa3d_build_batch(spa3d_handle h, const spa3d_clip* clips, spa3d_batch* out, void* stream) {
+  if (!h) return SPA3D_ERR_ARG;
+  h->err.clear(); h->hip_err = 0;
+  auto bad = [&](const std::string& m) { h->err = "build_batch: " + m; return SPA3D_ERR_ARG; };
+  if (h->cfg.model_kind == 1) return bad("the 2-D model (model_kind 1) has no depth coordinate");
+  if (!clips) return bad("clips is required");
+  if (!out) return bad("out is required");
+  if (out->B < 1 || out->N < 1 || out->Q < 0 || out->T < 1)
+    return bad("out: B = " + std::to_string(out->B) + ", N = " + std::to_string(out->N) + ", Q = " + std::to_string(out->Q) + ", T = " + std::to_string(out->T) + " (B, N, T >= 1 and Q >= 0)");
+  if (!out->support_tracks || !out->support_tracks_visible || !out->boundary_frame) return bad("out needs support_tracks, support_tracks_visible and boundary_frame");
+  if (out->Q > 0 && (!out->query_points || !out->query_tracks || !out->query_tracks_visible)) return bad("out needs query_points, query_tracks and query_tracks_visible when Q > 0");
+  const int D = h->cfg.dino_feature_dim, DD = h->cfg.depth_feature_dim;
+  if (out->dino_features && D <= 0) return bad("out carries dino_features but the handle has no DINO feature (dino_feature_dim = 0)");
+  if (out->depth_features && DD <= 0) return bad("out carries depth_features but the handle has no depth feature (depth_feature_dim = 0)");
+  auto aligned = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
+  bool vec_dino = (D & 3) == 0 && aligned(out->dino_features), vec_depth = (DD & 3) == 0 && aligned(out->depth_features);
+  for (int i = 0; i < out->B; ++i) {
+    const spa3d_clip& k = clips[i];
+    auto cbad = [&](const std::string& m) { return bad("clip " + std::to_string(i) + ": " + m); };
+    if (k.n_tracks < 1) return cbad("n_tracks = " + std::to_string(k.n_tracks) + " must be positive");
+    if (k.T < 1 || k.T > out->T) return cbad("T = " + std::to_string(k.T) + " is outside [1, " + std::to_string(out->T) + "] (the batch's T)");
+    if (k.n_support < 1 || k.n_support > out->N) return cbad("n_support = " + std::to_string(k.n_support) + " is outside [1, " + std::to_string(out->N) + "]");
+    if (k.n_query < 0 || k.n_query > out->Q) return cbad("n_query = " + std::to_string(k.n_query) + " is outside [0, " + std::to_string(out->Q) + "]");
+    if (!k.visible) return cbad("visible is required");
+    if (!k.support_index) return cbad("support_index is required");
+    if (k.n_query > 0 && (!k.query_index || !k.query_frame)) return cbad("query_index and query_frame are required when n_query > 0");
+    const bool depth_for_feature = out->depth_features && !k.depth_pool;
+    const bool need_2d = !k.tracks_3d || k.dino_map || depth_for_feature;
+    if (!k.tracks_3d && !k.depth_map) return cbad("a lift needs depth_map (or give tracks_3d)");
+    if (need_2d && !k.tracks_2d) return cbad("tracks_2d is required to lift or to sample a map");
+    if ((k.dino_map || !k.tracks_3d || depth_for_feature) && (k.H < 1 || k.W < 1)) return cbad("H = " + std::to_string(k.H) + ", W = " + std::to_string(k.W) + ": the video size must be positive");
+    if (k.dino_map && k.dino_pool) return cbad("dino_map and dino_pool are both given");
+    if (!out->dino_features && (k.dino_map || k.dino_pool)) return cbad("carries DINO but out->dino_features is NULL");
+    if (out->dino_features && !k.dino_map && !k.dino_pool) return cbad("out carries dino_features: dino_map or dino_pool is required");
+    if (k.dino_map && (k.Hp < 1 || k.Wp < 1)) return cbad("Hp = " + std::to_string(k.Hp) + ", Wp = " + std::to_string(k.Wp) + ": the map size must be positive");
+    if (k.depth_pool && k.depth_map && k.tracks_3d) return cbad("depth_map and depth_pool are both given (and no lift needs the map)");
+    if (!out->depth_features && k.depth_pool) return cbad("carries depth features but out->depth_features is NULL");
+    if (depth_for_feature && !k.depth_map) return cbad("out carries depth_features: depth_map or depth_pool is required");
+    vec_dino = vec_dino && aligned(k.dino_map) && aligned(k.dino_pool);
+    vec_depth = vec_depth && aligned(k.depth_pool);
+  }
+  h->stream = (hipStream_t)stream; h->dry = false;
+  for (int b0 = 0; b0 < out->B; b0 += BB_CLIPS) {
+    BbArgs a{};
+    a.b0 = b0; a.nclips = std::min(BB_CLIPS, out->B - b0); a.N = out->N; a.Q = out->Q; a.T = out->T; a.D = D; a.DD = DD;
+    a.st = (float*)out->support_tracks; a.sv = (float*)out->support_tracks_visible; a.qp = (float*)out->query_points; a.qt = (float*)out->query_tracks;
+    a.qv = (float*)out->query_tracks_visible; a.bf = (int32_t*)out->boundary_frame; a.dino = (void*)out->dino_features; a.depthf = (void*)out->depth_features;
+    a.vec = (vec_dino ? 1 : 0) | (vec_depth ? 2 : 0);
+    for (int g = 0; g < a.nclips; ++g) {
+      const spa3d_clip& k = clips[b0 + g];
+      BbClip& c = a.clip[g];
+      c.tracks_2d = k.tracks_2d; c.tracks_3d = k.tracks_3d; c.visible = k.visible; c.depth = k.depth_map; c.dino_map = k.dino_map;
+      c.dino_pool = k.dino_pool; c.depth_pool = k.depth_pool; c.sidx = k.support_index; c.qidx = k.query_index; c.qframe = k.query_frame;
+      c.n_tracks = k.n_tracks; c.T = k.T; c.H = k.H; c.W = k.W; c.Hp = k.Hp; c.Wp = k.Wp; c.n_support = k.n_support; c.n_query = k.n_query;
+      c.k = br_intrinsics(k.intrinsics, k.H, k.W);
+      c.sw = k.dino_map ? br_map_scale(k.Wp, k.W) : 0.f; c.sh = k.dino_map ? br_map_scale(k.Hp, k.H) : 0.f;
+      c.depth_feat = (out->depth_features && !k.depth_pool) ? 1 : 0;
+    }
+    k_build_batch(h, a, h->cfg.precision);
+  }
+  return h->hip_err ? SPA3D_ERR_HIP : SPA3D_OK;
+}
+
+}  // extern "C"

@@ -9,9 +9,6 @@
 #include "ablate.inc"  // every work-skipping diagnostic mask, all 0 in libspa3d_hip.so
 #include "gemm_plan.hpp"  // GemmDesc and the kernel choice (host-only)
 #include "score_row.hpp"  // per-track score arithmetic (host- and device-callable)
-#include "tapvid3d_row.hpp"  // TAPVid-3D metric counts of a row and the exact median select (host- and device-callable)
-#include "render_px.hpp"  // the arithmetic of spa3d_render_tracks: colour, projection, coverage, blend (host- and device-callable)
-#include "build_row.hpp"  // the arithmetic of spa3d_build_batch: samplers, slot rule, the rounding to the feature type (host- and device-callable)
 
 // One translation unit is compiled for exactly ONE 16-bit activation type: bf16 (default) or IEEE fp16 (-DSPA_F16=1, BASELINE
 // cfg#5).  The raw 16-bit storage type is `bf16_t` (unsigned short) in both builds; what differs -- the two conversions, the MFMA
@@ -165,47 +162,8 @@ struct ScoreArgs {
   int64_t nq, row0; int Q, T, NC; ScoreThr thr;
 };
 
-// The launches of spa3d_tapvid3d_from_preds (tapvid3d.hip) share this block: the caller's whole tensors, indexed by the global query row, and the
-// rows [row0, row0 + nq) a launch covers.  ratio / sel / row_scale / scale may be null (see each kernel).
-struct TvArgs {
-  const float* tracks; const float* vlog; const float* tgt; const float* tvis; const float* qpts; const float* intr;  // intr: device [B][4] or null
-  const float* scale;          // rows pass, median scaling: device [B]
-  float* ratio; float* sel;    // ratio pass: ratio [B * Q][T] of every frame; sel: the same with NaN outside {vis and ew} (the median's set)
-  float* row_scale; float* qstats;
-  int64_t nq, row0; int Q, T, scaling, fixed;
-};
-
-// The launches of spa3d_render_tracks (render.hip): the caller's tensors and the workspace arrays of the preparation.
-struct RenderArgs {
-  RpClip c;
-  const uint8_t* video; uint8_t* out; const float* tracks; const double* K; const double* E; const float* scores; const float* visible;
-  int32_t* pixels;     // caller's [N][T][2] or null
-  float* part;         // [RENDER_PARTS][2]: partial (min, max) of the finite scores
-  int32_t* pos;        // [N][T][2]
-  uint32_t* fl;        // [N][T]: flag words (render_px.hpp)
-  short* box;          // [T][N][4]: x0, y0, x1, y1 of everything point i draws in frame t (x0 > x1: nothing)
-  int nparts;
-};
-constexpr int RENDER_PARTS = 256;   // partial min / max pairs: one per workgroup of the reduction
+// render.hip's one constant that is read from outside it: tests/test_gpu_render.py sizes its compaction-order case by this line
 constexpr int RENDER_CHUNK = 256;   // points culled and compacted per round of the tile pass (= its workgroup size)
-
-// One launch of spa3d_build_batch (batch_build.hip): up to BB_CLIPS clips by value -- what fits in kernel arguments with room to spare -- and the
-// batch's buffers.  Clip g of the launch fills sample b0 + g.  Every pointer is a device pointer; the intrinsics and the map scales are already float32.
-constexpr int BB_CLIPS = 16;
-struct BbClip {
-  const float* tracks_2d; const float* tracks_3d; const float* visible; const float* depth; const float* dino_map;
-  const void* dino_pool; const void* depth_pool;   // rows in the feature type, copied
-  const int32_t* sidx; const int32_t* qidx; const int32_t* qframe;
-  int32_t n_tracks, T, H, W, Hp, Wp, n_support, n_query;
-  BrIntr k; float sw, sh;
-  int32_t depth_feat;   // the depth-feature channels come from the depth map (0: from depth_pool, or there are none)
-};
-struct BbArgs {
-  BbClip clip[BB_CLIPS];
-  float* st; float* sv; float* qp; float* qt; float* qv; int32_t* bf; void* dino; void* depthf;   // the batch: [B,N,T,3] [B,N,T] [B,Q,4] [B,Q,T,3] [B,Q,T] [B] [B,N,T,D] [B,N,T,DD]
-  int32_t b0, nclips, N, Q, T, D, DD;
-  int32_t vec;   // D % 4 == 0 and every DINO pointer 16-byte aligned: 16-byte accesses along the channel axis
-};
 
 struct Leaf {
   std::string name;
@@ -286,6 +244,51 @@ inline void apply_attn_impl(spa3d_ctx* c, int v) {
   c->attn_impl = v == 1 ? 1 : (v >= 2 ? 2 : 0);
   c->attn_bwd_mode = v == 3 ? 2 : (v == 4 ? 3 : 0);
   c->qkv_attn = v == 6;   // 6 = the fused kernels with the round-5 QKV projection + attention forward (opt-in: measured slower)
+}
+
+// ---- the scaffold of a call: sizing walk, sized call, query counts, live rows ----
+// Peak arena bytes of `body` walked with launches off (c->dry) against a counting arena; the arena and the mode come back as they were.
+// The caller adds its own slack.
+template <typename F> inline int64_t arena_peak(spa3d_ctx* c, F&& body) {
+  const Arena saved = c->ar; const bool sd = c->dry;
+  c->ar = Arena(); c->ar.dry = true; c->dry = true;
+  body();
+  const int64_t peak = c->ar.peak;
+  c->ar = saved; c->dry = sd;
+  return peak;
+}
+// A call whose need is known: refused (SPA3D_ERR_ARG, "<what>: workspace too small: need N bytes") without a workspace of `need` bytes;
+// else `body` runs on `stream` against the caller's workspace.
+template <typename F> inline int sized_call(spa3d_ctx* c, const char* what, int64_t need, void* ws, int64_t ws_bytes, void* stream, F&& body) {
+  if (!ws || ws_bytes < need) { c->err = std::string(what) + ": workspace too small: need " + std::to_string(need) + " bytes"; return SPA3D_ERR_ARG; }
+  c->stream = (hipStream_t)stream; c->dry = false;
+  c->ar = Arena(); c->ar.base = (char*)ws; c->ar.cap = ws_bytes;
+  body();
+  if (c->ar.overflow) { c->err = "internal: arena overflow"; return SPA3D_ERR_WORKSPACE; }
+  return c->hip_err ? SPA3D_ERR_HIP : SPA3D_OK;
+}
+// spa3d_set_counts against a batch of B samples: false with c->err set when the counts were set for another B
+inline bool counts_fit_batch(spa3d_ctx* c, int B) {
+  if (c->cnt_B == B) return true;
+  c->err = "counts were set for B = " + std::to_string(c->cnt_B) + ", this batch has B = " + std::to_string(B);
+  return false;
+}
+// The live-query counts [B] of a handle that has them (c->has_cnt_q), checked against a batch of B samples of Q queries; null with c->err
+// set when they do not fit it.
+inline const int32_t* checked_query_counts(spa3d_ctx* c, int B, int Q) {
+  if (!counts_fit_batch(c, B)) return nullptr;
+  for (int i = 0; i < B; ++i)
+    if (c->cnt_q[i] < 0 || c->cnt_q[i] > Q) {
+      c->err = "query_count[" + std::to_string(i) + "] = " + std::to_string(c->cnt_q[i]) + " is outside [0, Q = " + std::to_string(Q) + "]";
+      return nullptr;
+    }
+  return c->cnt_q.data();
+}
+// f(row0, nq) over the live rows of the [B * Q] query rows: the whole batch at once without counts, else sample by sample, rows
+// [i * Q, i * Q + cq[i]) -- the padded rows of sample i follow its span
+template <typename F> inline void for_each_live_span(const int32_t* cq, int64_t B, int64_t Q, F&& f) {
+  if (!cq) { f((int64_t)0, B * Q); return; }
+  for (int64_t i = 0; i < B; ++i) f(i * Q, (int64_t)cq[i]);
 }
 
 struct ProfScope {  // records an event pair around the launches issued in its lifetime
@@ -413,16 +416,6 @@ void k_loss_from_preds(spa3d_ctx*, const float* tracks, const float* vlog, int64
                        unsigned* poison, int NC = 3);
 void k_score_rows(spa3d_ctx*, const ScoreArgs& a);
 void k_score_reduce(spa3d_ctx*, const float* qstats, int64_t B, int Q, int K, double* out /*[B][8 + 4K]*/);
-void k_render_minmax(spa3d_ctx*, const RenderArgs& a);
-void k_render_points(spa3d_ctx*, const RenderArgs& a);
-void k_render_boxes(spa3d_ctx*, const RenderArgs& a);
-void k_render_tiles(spa3d_ctx*, const RenderArgs& a);
-void k_tv_ratio(spa3d_ctx*, const TvArgs& a);
-void k_tv_rows(spa3d_ctx*, const TvArgs& a);
-void k_tv_reduce(spa3d_ctx*, const float* qstats, int64_t B, int Q, double* out /*[B][24]*/);
-void k_tv_fill(spa3d_ctx*, float* p, int64_t n, float v);
-void k_median_rows(spa3d_ctx*, const float* x, int64_t rows, int64_t stride, int64_t n, float* out);
-void k_build_batch(spa3d_ctx*, const BbArgs& a, int out_type /* BR_F32 | BR_BF16 | BR_F16 */);
 template <typename T> void k_loss_bwd(spa3d_ctx*, const float* head, int64_t nq, int T_, const float* tgt, const float* tvis,
                                       const float* denom_dev, float l1w, float bcew, T* dhead, int NC = 3, const float* scale_dev = nullptr);
 void k_vis_count(spa3d_ctx*, const float* tvis, int64_t n, float* out, unsigned* poison);

@@ -1,5 +1,7 @@
 // model.hip -- host orchestration of the 3DSPA TrackAutoEncoder3D forward / loss / backward on gfx950
-// and the C-ABI of include/spa3d.h.  The graph follows SURVEY.md 0.1 (E1-E7, L1-L3, D1-D8, LOSS) with
+// and the C-ABI of include/spa3d.h that runs the network or reads its predictions (forward, score, loss,
+// options).  A stand-alone API lives whole in the file of its kernels -- tapvid3d.hip, render.hip,
+// batch_build.hip -- on the call scaffold of common.hpp.  The graph follows SURVEY.md 0.1 (E1-E7, L1-L3, D1-D8, LOSS) with
 // repairs R2-R5; file:line references are to /root/reference.
 //
 // Memory plan: the batch is processed in chunks of `Bc` samples (every op is per-sample; the only
@@ -1218,13 +1220,8 @@ static void run_dispatch(spa3d_ctx* c, const RunArgs& a, int Bc) {
 }
 
 static int64_t dry_need(spa3d_ctx* c, const RunArgs& a, int Bc) {
-  Arena saved = c->ar; bool sd = c->dry;
-  c->ar = Arena(); c->ar.dry = true; c->dry = true;
   RunArgs d = a; d.P = (const float*)0x100000; d.G = a.G ? (float*)0x100000 : nullptr;
-  run_dispatch(c, d, Bc);
-  int64_t need = c->ar.peak + 4096;
-  c->ar = saved; c->dry = sd;
-  return need;
+  return arena_peak(c, [&] { run_dispatch(c, d, Bc); }) + 4096;
 }
 
 // "gemm_impl" of a handle: 7 and 10 are spa3d_op_linear's one-kernel hooks; on a handle they mean 2, the product dispatch
@@ -1256,7 +1253,7 @@ static int run(spa3d_ctx* c, RunArgs a, void* ws, int64_t ws_bytes, void* stream
   a.cn = nullptr; a.cq = nullptr;
   if (c->has_cnt_n || c->has_cnt_q) {
     const spa3d_batch* b = a.b;
-    if (c->cnt_B != b->B) { c->err = "counts were set for B = " + std::to_string(c->cnt_B) + ", this batch has B = " + std::to_string(b->B); return SPA3D_ERR_ARG; }
+    if (!counts_fit_batch(c, b->B)) return SPA3D_ERR_ARG;  // first, and also when only support counts are set; checked_query_counts below repeats it, harmlessly
     if (c->cfg.model_kind == 1) { c->err = "per-sample counts are not supported by the 2-D model (model_kind 1)"; return SPA3D_ERR_ARG; }
     if (c->query_chunk > 0 || c->track_chunk > 0) { c->err = "per-sample counts cannot be combined with \"query_chunk\" / \"track_chunk\""; return SPA3D_ERR_ARG; }
     if (c->has_cnt_n && a.mode != MODE_DECODE) {  // spa3d_decode has no support tracks: it reads the query counts only
@@ -1264,11 +1261,7 @@ static int run(spa3d_ctx* c, RunArgs a, void* ws, int64_t ws_bytes, void* stream
         if (c->cnt_n[i] < 1 || c->cnt_n[i] > b->N) { c->err = "support_count[" + std::to_string(i) + "] = " + std::to_string(c->cnt_n[i]) + " is outside [1, N = " + std::to_string(b->N) + "]"; return SPA3D_ERR_ARG; }
       a.cn = c->cnt_n.data();
     }
-    if (c->has_cnt_q && a.mode != MODE_ENCODE) {
-      for (int i = 0; i < b->B; ++i)
-        if (c->cnt_q[i] < 0 || c->cnt_q[i] > b->Q) { c->err = "query_count[" + std::to_string(i) + "] = " + std::to_string(c->cnt_q[i]) + " is outside [0, Q = " + std::to_string(b->Q) + "]"; return SPA3D_ERR_ARG; }
-      a.cq = c->cnt_q.data();
-    }
+    if (c->has_cnt_q && a.mode != MODE_ENCODE && !(a.cq = checked_query_counts(c, b->B, b->Q))) return SPA3D_ERR_ARG;
     // counts that leave nothing out describe a uniform batch: it takes the batched path, bit for bit the call without counts
     bool full = true;
     for (int i = 0; i < b->B && full; ++i) full = (!a.cn || a.cn[i] == b->N) && (!a.cq || a.cq[i] == b->Q);
@@ -1396,230 +1389,18 @@ int spa3d_score_from_preds(spa3d_handle h, const spa3d_batch* b, const spa3d_out
   if (rc) return rc;
   if (!preds || !preds->tracks || !preds->visible_logits) { h->err = "score: predictions (tracks, visible_logits) are required"; return SPA3D_ERR_ARG; }
   if (b->B <= 0 || b->Q <= 0) { h->err = "batch: B,Q must be positive"; return SPA3D_ERR_ARG; }
-  if (h->has_cnt_q) {
-    if (h->cnt_B != b->B) { h->err = "counts were set for B = " + std::to_string(h->cnt_B) + ", this batch has B = " + std::to_string(b->B); return SPA3D_ERR_ARG; }
-    for (int i = 0; i < b->B; ++i)
-      if (h->cnt_q[i] < 0 || h->cnt_q[i] > b->Q) { h->err = "query_count[" + std::to_string(i) + "] is outside [0, Q]"; return SPA3D_ERR_ARG; }
-  }
+  const int32_t* cq = nullptr;
+  if (h->has_cnt_q && !(cq = checked_query_counts(h, b->B, b->Q))) return SPA3D_ERR_ARG;
   h->stream = (hipStream_t)stream; h->dry = false;
   const int To = h->cfg.num_output_frames;
   ScoreArgs s = score_args(b, scores, To, h->cfg.model_kind == 1 ? 2 : 3);
   s.tracks = preds->tracks; s.vlog = preds->visible_logits;
-  if (h->has_cnt_q) {  // live queries only, sample by sample; padded rows read as 0
-    for (int64_t i = 0; i < b->B; ++i) {
-      s.nq = h->cnt_q[i]; s.row0 = i * b->Q;
-      k_score_rows(h, s);
-      score_zero_rows(h, scores, s.row0 + s.nq, b->Q - s.nq, To);
-    }
-  } else {
-    s.nq = (int64_t)b->B * b->Q; s.row0 = 0;
+  for_each_live_span(cq, b->B, b->Q, [&](int64_t row0, int64_t nq) {  // live queries only; a sample's padded rows read as 0
+    s.nq = nq; s.row0 = row0;
     k_score_rows(h, s);
-  }
+    if (cq) score_zero_rows(h, scores, row0 + nq, b->Q - nq, To);
+  });
   if (scores->sample_stats) k_score_reduce(h, scores->query_stats, b->B, b->Q, scores->num_thresholds, scores->sample_stats);
-  return h->hip_err ? SPA3D_ERR_HIP : SPA3D_OK;
-}
-
-// ---- TAPVid-3D metrics (tapvid3d.hip, tapvid3d_row.hpp) ----
-// The launches of one call.  Runs twice: dry (no launch, a counting arena: the workspace the call needs) and for real.  Workspace: the median's
-// set [B * Q][T_out] (median scaling only) and the per-sample factors [B] when the caller does not ask for them.
-static void tapvid3d_body(spa3d_ctx* c, const spa3d_batch* b, const spa3d_outputs* preds, const spa3d_tapvid3d* m, const int32_t* cq) {
-  const int To = c->cfg.num_output_frames;
-  const int64_t B = b->B, Q = b->Q;
-  const bool median = m->scaling == SPA3D_SCALE_MEDIAN;
-  TvArgs a{};
-  a.tracks = preds->tracks; a.vlog = preds->visible_logits; a.tgt = b->query_tracks; a.tvis = b->query_tracks_visible; a.qpts = b->query_points;
-  a.intr = m->intrinsics; a.ratio = m->ratio; a.row_scale = m->row_scale; a.qstats = m->query_stats;
-  a.Q = b->Q; a.T = To; a.scaling = m->scaling; a.fixed = m->fixed_thresholds != 0;
-  a.sel = median ? (float*)c->ar.alloc(B * Q * To * 4) : nullptr;
-  float* scale = m->scale ? m->scale : (median ? (float*)c->ar.alloc(B * 4) : nullptr);
-  a.scale = scale;
-  // rows of padded queries (spa3d_set_counts): every result reads 0, their inputs are never read and they are not part of the median
-  auto zero_padded = [&](int64_t r0, int64_t nr) {
-    if (c->dry || nr <= 0) return;
-    (void)hipMemsetAsync(m->query_stats + r0 * TV_S, 0, (size_t)(nr * TV_S) * 4, c->stream);
-    if (m->row_scale) (void)hipMemsetAsync(m->row_scale + r0, 0, (size_t)nr * 4, c->stream);
-    if (m->ratio) (void)hipMemsetAsync(m->ratio + r0 * To, 0, (size_t)(nr * To) * 4, c->stream);
-  };
-  auto each_span = [&](auto&& launch) {  // live rows: the whole batch at once, or sample by sample
-    if (!cq) { a.nq = B * Q; a.row0 = 0; launch(); return; }
-    for (int64_t i = 0; i < B; ++i) { a.nq = cq[i]; a.row0 = i * Q; launch(); }
-  };
-  if (a.ratio || a.sel) each_span([&] { k_tv_ratio(c, a); });
-  if (median) {
-    if (!cq) k_median_rows(c, a.sel, B, Q * To, Q * To, scale);
-    else for (int64_t i = 0; i < B; ++i) k_median_rows(c, a.sel + i * Q * To, 1, Q * To, (int64_t)cq[i] * To, scale + i);
-  } else if (scale) {
-    k_tv_fill(c, scale, B, 1.f);
-  }
-  each_span([&] { k_tv_rows(c, a); });
-  if (cq) for (int64_t i = 0; i < B; ++i) zero_padded(i * Q + cq[i], Q - cq[i]);
-  if (m->sample_stats) k_tv_reduce(c, m->query_stats, B, b->Q, m->sample_stats);
-}
-static int64_t tapvid3d_need(spa3d_ctx* c, const spa3d_batch* b, const spa3d_outputs* preds, const spa3d_tapvid3d* m, const int32_t* cq) {
-  Arena saved = c->ar; const bool sd = c->dry;
-  c->ar = Arena(); c->ar.dry = true; c->dry = true;
-  tapvid3d_body(c, b, preds, m, cq);
-  const int64_t need = c->ar.peak + 256;  // never 0: a call without a workspace is refused after the walk, whatever the scaling
-  c->ar = saved; c->dry = sd;
-  return need;
-}
-int64_t spa3d_tapvid3d_workspace_bytes(spa3d_handle h, int32_t B, int32_t Q, int32_t T) {
-  if (!h || B <= 0 || Q <= 0 || T <= 0) return -1;
-  const int64_t To = std::max(T, h->cfg.num_output_frames);  // the largest need of any scaling: the median's set and the factors, each 256-byte aligned
-  return (((int64_t)B * Q * To * 4 + 255) & ~int64_t(255)) + (((int64_t)B * 4 + 255) & ~int64_t(255)) + 256;
-}
-int spa3d_tapvid3d_from_preds(spa3d_handle h, const spa3d_batch* b, const spa3d_outputs* preds, spa3d_tapvid3d* m, void* ws, int64_t ws_bytes, void* stream) {
-  if (!h) return SPA3D_ERR_ARG;
-  h->err.clear(); h->hip_err = 0;
-  if (h->cfg.model_kind == 1) { h->err = "tapvid3d: the 2-D model (model_kind 1) has no depth coordinate"; return SPA3D_ERR_ARG; }
-  if (!b || !b->query_tracks || !b->query_tracks_visible) { h->err = "tapvid3d: the batch needs its targets (query_tracks, query_tracks_visible)"; return SPA3D_ERR_ARG; }
-  if (!b->query_points) { h->err = "tapvid3d: the batch needs query_points (the query frame is left out of every count)"; return SPA3D_ERR_ARG; }
-  if (!preds || !preds->tracks || !preds->visible_logits) { h->err = "tapvid3d: predictions (tracks, visible_logits) are required"; return SPA3D_ERR_ARG; }
-  if (!m || !m->query_stats) { h->err = "tapvid3d: spa3d_tapvid3d::query_stats is required"; return SPA3D_ERR_ARG; }
-  if (m->scaling < SPA3D_SCALE_NONE || m->scaling > SPA3D_SCALE_PER_TRAJECTORY) { h->err = "tapvid3d: scaling = " + std::to_string(m->scaling) + " is outside [0, 2]"; return SPA3D_ERR_ARG; }
-  if (b->B <= 0 || b->Q <= 0) { h->err = "batch: B,Q must be positive"; return SPA3D_ERR_ARG; }
-  const int32_t* cq = nullptr;
-  if (h->has_cnt_q) {
-    if (h->cnt_B != b->B) { h->err = "counts were set for B = " + std::to_string(h->cnt_B) + ", this batch has B = " + std::to_string(b->B); return SPA3D_ERR_ARG; }
-    for (int i = 0; i < b->B; ++i)
-      if (h->cnt_q[i] < 0 || h->cnt_q[i] > b->Q) { h->err = "query_count[" + std::to_string(i) + "] is outside [0, Q]"; return SPA3D_ERR_ARG; }
-    cq = h->cnt_q.data();
-  }
-  const int64_t need = tapvid3d_need(h, b, preds, m, cq);
-  if (!ws || ws_bytes < need) { h->err = "tapvid3d: workspace too small: need " + std::to_string(need) + " bytes"; return SPA3D_ERR_ARG; }
-  h->stream = (hipStream_t)stream; h->dry = false;
-  h->ar = Arena(); h->ar.base = (char*)ws; h->ar.cap = ws_bytes;
-  tapvid3d_body(h, b, preds, m, cq);
-  if (h->ar.overflow) { h->err = "internal: arena overflow"; return SPA3D_ERR_WORKSPACE; }
-  return h->hip_err ? SPA3D_ERR_HIP : SPA3D_OK;
-}
-
-// ---- track overlays (render.hip, render_px.hpp) ----
-// The launches of one call.  Runs twice: dry (no launch, a counting arena: the workspace the call needs) and for real.  Workspace: the partial
-// min / max pairs, and -- when frames are drawn -- the positions, flag words and boxes of the N x T point-frames.
-static void render_body(spa3d_ctx* c, const spa3d_render* r) {
-  const int64_t n = (int64_t)r->N * r->T;
-  RenderArgs a{};
-  a.c = RpClip{r->N, r->T, r->H, r->W, r->coords, r->resize_h, r->resize_w, r->normalize != 0, r->use_visibility != 0, r->colour_bgr != 0, r->trail, r->point_size};
-  a.video = r->video; a.out = r->out; a.tracks = r->tracks; a.K = r->coords == 3 ? r->intrinsics : nullptr; a.E = r->coords == 3 ? r->extrinsics : nullptr;
-  a.scores = r->out ? r->scores : nullptr; a.visible = r->use_visibility ? r->visible : nullptr; a.pixels = r->pixels;
-  a.nparts = (int)std::min<int64_t>(RENDER_PARTS, (n + RENDER_CHUNK - 1) / RENDER_CHUNK);
-  const bool norm = a.scores && r->normalize;
-  if (norm) { a.part = (float*)c->ar.alloc(RENDER_PARTS * 2 * 4); k_render_minmax(c, a); }
-  if (r->out) {
-    a.pos = (int32_t*)c->ar.alloc(n * 8); a.fl = (uint32_t*)c->ar.alloc(n * 4); a.box = (short*)c->ar.alloc(n * 8);
-  }
-  k_render_points(c, a);
-  if (!r->out) return;
-  k_render_boxes(c, a);
-  k_render_tiles(c, a);
-}
-static int64_t render_need(spa3d_ctx* c, const spa3d_render* r) {
-  Arena saved = c->ar; const bool sd = c->dry;
-  c->ar = Arena(); c->ar.dry = true; c->dry = true;
-  render_body(c, r);
-  const int64_t need = c->ar.peak + 256;  // never 0: a call without a workspace is refused after the walk
-  c->ar = saved; c->dry = sd;
-  return need;
-}
-int64_t spa3d_render_workspace_bytes(spa3d_handle h, int32_t N, int32_t T) {
-  if (!h || N <= 0 || T <= 0) return -1;
-  const int64_t n = (int64_t)N * T;
-  auto up = [](int64_t b) { return (b + 255) & ~int64_t(255); };
-  return up(RENDER_PARTS * 2 * 4) + up(n * 8) + up(n * 4) + up(n * 8) + 256;
-}
-int spa3d_render_tracks(spa3d_handle h, const spa3d_render* r, void* ws, int64_t ws_bytes, void* stream) {
-  if (!h) return SPA3D_ERR_ARG;
-  h->err.clear(); h->hip_err = 0;
-  auto bad = [&](const std::string& m) { h->err = "render: " + m; return SPA3D_ERR_ARG; };
-  if (!r) return bad("spa3d_render is required");
-  if (r->N < 1 || r->T < 1) return bad("N = " + std::to_string(r->N) + ", T = " + std::to_string(r->T) + ": both must be positive");
-  if (r->H < 1 || r->H > RP_MAX_DIM || r->W < 1 || r->W > RP_MAX_DIM)
-    return bad("H = " + std::to_string(r->H) + ", W = " + std::to_string(r->W) + " are outside [1, " + std::to_string(RP_MAX_DIM) + "]");
-  if (!r->tracks) return bad("tracks is required");
-  if (r->coords != 2 && r->coords != 3) return bad("coords = " + std::to_string(r->coords) + " is neither 2 nor 3");
-  if (r->coords == 3 && (!r->intrinsics || !r->extrinsics)) return bad("coords == 3 needs the camera matrices (intrinsics, extrinsics)");
-  if (r->coords == 3 && (r->resize_h < 1 || r->resize_w < 1)) return bad("coords == 3 needs resize_h, resize_w >= 1");
-  if (!r->out && !r->pixels) return bad("nothing to do: out and pixels are both NULL");
-  if (r->out && (!r->video || !r->scores)) return bad("drawing needs video and scores");
-  if (r->use_visibility && !r->visible) return bad("use_visibility needs visible");
-  if (r->trail < 0 || r->trail > RP_MAX_TRAIL) return bad("trail = " + std::to_string(r->trail) + " is outside [0, " + std::to_string(RP_MAX_TRAIL) + "]");
-  if (r->point_size < 0 || r->point_size > RP_MAX_RADIUS)
-    return bad("point_size = " + std::to_string(r->point_size) + " is outside [0, " + std::to_string(RP_MAX_RADIUS) + "]");
-  // a launch holds fewer than 2^32 threads: one thread per point-frame, 256 per (frame, tile)
-  if ((int64_t)r->N * r->T > (int64_t)1 << 31) return bad("N x T = " + std::to_string((int64_t)r->N * r->T) + " point-frames exceed one launch (2^31)");
-  if (r->out && (int64_t)r->T * ((r->W + 63) / 64) * ((r->H + 15) / 16) >= (int64_t)1 << 24) return bad("T x tiles reaches 2^24 workgroups: more than one launch holds");
-  const int64_t need = render_need(h, r);
-  if (!ws || ws_bytes < need) return bad("workspace too small: need " + std::to_string(need) + " bytes");
-  h->stream = (hipStream_t)stream; h->dry = false;
-  h->ar = Arena(); h->ar.base = (char*)ws; h->ar.cap = ws_bytes;
-  render_body(h, r);
-  if (h->ar.overflow) { h->err = "internal: arena overflow"; return SPA3D_ERR_WORKSPACE; }
-  return h->hip_err ? SPA3D_ERR_HIP : SPA3D_OK;
-}
-
-// ---- clips to batches (batch_build.hip, build_row.hpp) ----
-// Everything is checked for every clip before the first launch; then one launch per BB_CLIPS clips, their descriptors by value.
-int spa3d_build_batch(spa3d_handle h, const spa3d_clip* clips, spa3d_batch* out, void* stream) {
-  if (!h) return SPA3D_ERR_ARG;
-  h->err.clear(); h->hip_err = 0;
-  auto bad = [&](const std::string& m) { h->err = "build_batch: " + m; return SPA3D_ERR_ARG; };
-  if (h->cfg.model_kind == 1) return bad("the 2-D model (model_kind 1) has no depth coordinate");
-  if (!clips) return bad("clips is required");
-  if (!out) return bad("out is required");
-  if (out->B < 1 || out->N < 1 || out->Q < 0 || out->T < 1)
-    return bad("out: B = " + std::to_string(out->B) + ", N = " + std::to_string(out->N) + ", Q = " + std::to_string(out->Q) + ", T = " + std::to_string(out->T) + " (B, N, T >= 1 and Q >= 0)");
-  if (!out->support_tracks || !out->support_tracks_visible || !out->boundary_frame) return bad("out needs support_tracks, support_tracks_visible and boundary_frame");
-  if (out->Q > 0 && (!out->query_points || !out->query_tracks || !out->query_tracks_visible)) return bad("out needs query_points, query_tracks and query_tracks_visible when Q > 0");
-  const int D = h->cfg.dino_feature_dim, DD = h->cfg.depth_feature_dim;
-  if (out->dino_features && D <= 0) return bad("out carries dino_features but the handle has no DINO feature (dino_feature_dim = 0)");
-  if (out->depth_features && DD <= 0) return bad("out carries depth_features but the handle has no depth feature (depth_feature_dim = 0)");
-  auto aligned = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
-  bool vec_dino = (D & 3) == 0 && aligned(out->dino_features), vec_depth = (DD & 3) == 0 && aligned(out->depth_features);
-  for (int i = 0; i < out->B; ++i) {
-    const spa3d_clip& k = clips[i];
-    auto cbad = [&](const std::string& m) { return bad("clip " + std::to_string(i) + ": " + m); };
-    if (k.n_tracks < 1) return cbad("n_tracks = " + std::to_string(k.n_tracks) + " must be positive");
-    if (k.T < 1 || k.T > out->T) return cbad("T = " + std::to_string(k.T) + " is outside [1, " + std::to_string(out->T) + "] (the batch's T)");
-    if (k.n_support < 1 || k.n_support > out->N) return cbad("n_support = " + std::to_string(k.n_support) + " is outside [1, " + std::to_string(out->N) + "]");
-    if (k.n_query < 0 || k.n_query > out->Q) return cbad("n_query = " + std::to_string(k.n_query) + " is outside [0, " + std::to_string(out->Q) + "]");
-    if (!k.visible) return cbad("visible is required");
-    if (!k.support_index) return cbad("support_index is required");
-    if (k.n_query > 0 && (!k.query_index || !k.query_frame)) return cbad("query_index and query_frame are required when n_query > 0");
-    const bool depth_for_feature = out->depth_features && !k.depth_pool;
-    const bool need_2d = !k.tracks_3d || k.dino_map || depth_for_feature;
-    if (!k.tracks_3d && !k.depth_map) return cbad("a lift needs depth_map (or give tracks_3d)");
-    if (need_2d && !k.tracks_2d) return cbad("tracks_2d is required to lift or to sample a map");
-    if ((k.dino_map || !k.tracks_3d || depth_for_feature) && (k.H < 1 || k.W < 1)) return cbad("H = " + std::to_string(k.H) + ", W = " + std::to_string(k.W) + ": the video size must be positive");
-    if (k.dino_map && k.dino_pool) return cbad("dino_map and dino_pool are both given");
-    if (!out->dino_features && (k.dino_map || k.dino_pool)) return cbad("carries DINO but out->dino_features is NULL");
-    if (out->dino_features && !k.dino_map && !k.dino_pool) return cbad("out carries dino_features: dino_map or dino_pool is required");
-    if (k.dino_map && (k.Hp < 1 || k.Wp < 1)) return cbad("Hp = " + std::to_string(k.Hp) + ", Wp = " + std::to_string(k.Wp) + ": the map size must be positive");
-    if (k.depth_pool && k.depth_map && k.tracks_3d) return cbad("depth_map and depth_pool are both given (and no lift needs the map)");
-    if (!out->depth_features && k.depth_pool) return cbad("carries depth features but out->depth_features is NULL");
-    if (depth_for_feature && !k.depth_map) return cbad("out carries depth_features: depth_map or depth_pool is required");
-    vec_dino = vec_dino && aligned(k.dino_map) && aligned(k.dino_pool);
-    vec_depth = vec_depth && aligned(k.depth_pool);
-  }
-  h->stream = (hipStream_t)stream; h->dry = false;
-  for (int b0 = 0; b0 < out->B; b0 += BB_CLIPS) {
-    BbArgs a{};
-    a.b0 = b0; a.nclips = std::min(BB_CLIPS, out->B - b0); a.N = out->N; a.Q = out->Q; a.T = out->T; a.D = D; a.DD = DD;
-    a.st = (float*)out->support_tracks; a.sv = (float*)out->support_tracks_visible; a.qp = (float*)out->query_points; a.qt = (float*)out->query_tracks;
-    a.qv = (float*)out->query_tracks_visible; a.bf = (int32_t*)out->boundary_frame; a.dino = (void*)out->dino_features; a.depthf = (void*)out->depth_features;
-    a.vec = (vec_dino ? 1 : 0) | (vec_depth ? 2 : 0);
-    for (int g = 0; g < a.nclips; ++g) {
-      const spa3d_clip& k = clips[b0 + g];
-      BbClip& c = a.clip[g];
-      c.tracks_2d = k.tracks_2d; c.tracks_3d = k.tracks_3d; c.visible = k.visible; c.depth = k.depth_map; c.dino_map = k.dino_map;
-      c.dino_pool = k.dino_pool; c.depth_pool = k.depth_pool; c.sidx = k.support_index; c.qidx = k.query_index; c.qframe = k.query_frame;
-      c.n_tracks = k.n_tracks; c.T = k.T; c.H = k.H; c.W = k.W; c.Hp = k.Hp; c.Wp = k.Wp; c.n_support = k.n_support; c.n_query = k.n_query;
-      c.k = br_intrinsics(k.intrinsics, k.H, k.W);
-      c.sw = k.dino_map ? br_map_scale(k.Wp, k.W) : 0.f; c.sh = k.dino_map ? br_map_scale(k.Hp, k.H) : 0.f;
-      c.depth_feat = (out->depth_features && !k.depth_pool) ? 1 : 0;
-    }
-    k_build_batch(h, a, h->cfg.precision);
-  }
   return h->hip_err ? SPA3D_ERR_HIP : SPA3D_OK;
 }
 
@@ -1639,26 +1420,16 @@ int spa3d_loss(spa3d_handle h, const spa3d_batch* b, const spa3d_outputs* preds,
   float* scratch = loss3 + 4;  // loss3 points at 12 floats: [0..2] results, [3] sticky non-finite flag, [4..9] three 64-bit fixed-point accumulators, [10] denominator
   unsigned* poison = (unsigned*)(loss3 + 3);
   const int To = h->cfg.num_output_frames, NC = h->cfg.model_kind == 1 ? 2 : 3;
-  const int64_t n = (int64_t)b->B * b->Q * To;
-  if (h->has_cnt_q) {
-    if (h->cnt_B != b->B) { h->err = "counts were set for B = " + std::to_string(h->cnt_B) + ", this batch has B = " + std::to_string(b->B); return SPA3D_ERR_ARG; }
-    for (int i = 0; i < b->B; ++i)
-      if (h->cnt_q[i] < 0 || h->cnt_q[i] > b->Q) { h->err = "query_count[" + std::to_string(i) + "] is outside [0, Q]"; return SPA3D_ERR_ARG; }
-  }
+  const int32_t* cq = nullptr;
+  if (h->has_cnt_q && !(cq = checked_query_counts(h, b->B, b->Q))) return SPA3D_ERR_ARG;
   k_zero(h, loss3 + 3, 36);
-  if (h->has_cnt_q) {  // live queries only, sample by sample (the sums are order-independent fixed-point sums)
-    for (int64_t s = 0; s < b->B; ++s) k_vis_count(h, b->query_tracks_visible + s * b->Q * To, (int64_t)h->cnt_q[s] * To, scratch + 4, poison);
-    k_set_denom(h, scratch, poison, denom, scratch + 6);
-    for (int64_t s = 0; s < b->B; ++s) {
-      const int64_t r = s * b->Q * To;
-      k_loss_from_preds(h, preds->tracks + r * NC, preds->visible_logits + r, (int64_t)h->cnt_q[s] * To, b->query_tracks + r * NC, b->query_tracks_visible + r, scratch, poison, NC);
-    }
-    k_loss_finalize(h, scratch, poison, scratch + 6, L1_WEIGHT, BCE_WEIGHT, loss3);
-    return h->hip_err ? SPA3D_ERR_HIP : SPA3D_OK;
-  }
-  k_vis_count(h, b->query_tracks_visible, n, scratch + 4, poison);
+  // live queries only: the whole batch at once, or sample by sample (the sums are order-independent fixed-point sums)
+  for_each_live_span(cq, b->B, b->Q, [&](int64_t row0, int64_t nq) { k_vis_count(h, b->query_tracks_visible + row0 * To, nq * To, scratch + 4, poison); });
   k_set_denom(h, scratch, poison, denom, scratch + 6);
-  k_loss_from_preds(h, preds->tracks, preds->visible_logits, n, b->query_tracks, b->query_tracks_visible, scratch, poison, NC);
+  for_each_live_span(cq, b->B, b->Q, [&](int64_t row0, int64_t nq) {
+    const int64_t r = row0 * To;
+    k_loss_from_preds(h, preds->tracks + r * NC, preds->visible_logits + r, nq * To, b->query_tracks + r * NC, b->query_tracks_visible + r, scratch, poison, NC);
+  });
   k_loss_finalize(h, scratch, poison, scratch + 6, L1_WEIGHT, BCE_WEIGHT, loss3);
   return h->hip_err ? SPA3D_ERR_HIP : SPA3D_OK;
 }

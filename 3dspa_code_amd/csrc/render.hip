@@ -1,4 +1,4 @@
-// render.hip -- kernels of spa3d_render_tracks (include/spa3d.h): score-coloured track overlays drawn into a clip's frames.
+// render.hip -- spa3d_render_tracks (include/spa3d.h), kernels first, entry points below them: score-coloured track overlays drawn into a clip's frames.
 // All arithmetic is render_px.hpp's (shared with the g++ host test); this file only decides which thread runs it on what.  No 16-bit code:
 // compiled once.
 //
@@ -12,7 +12,24 @@
 //                         the list is composited into the registers that hold the thread's pixels before the next chunk.  LDS: the list of
 //                         RENDER_CHUNK indices and four counters, whatever N is; no overflow case.  A pixel is loaded once and stored once by
 //                         its owner, so out == video is legal; no atomics, no hand-off between workgroups.
+#include <algorithm>
+
 #include "common.hpp"
+#include "render_px.hpp"  // colour, projection, coverage, blend (host- and device-callable)
+
+// The launches of spa3d_render_tracks: the caller's tensors and the workspace arrays of the preparation.
+struct RenderArgs {
+  RpClip c;
+  const uint8_t* video; uint8_t* out; const float* tracks; const double* K; const double* E; const float* scores; const float* visible;
+  int32_t* pixels;     // caller's [N][T][2] or null
+  float* part;         // [RENDER_PARTS][2]: partial (min, max) of the finite scores
+  int32_t* pos;        // [N][T][2]
+  uint32_t* fl;        // [N][T]: flag words (render_px.hpp)
+  short* box;          // [T][N][4]: x0, y0, x1, y1 of everything point i draws in frame t (x0 > x1: nothing)
+  int nparts;
+};
+constexpr int RENDER_PARTS = 256;   // partial min / max pairs: one per workgroup of the reduction
+// RENDER_CHUNK, the points culled and compacted per round of the tile pass, is in common.hpp: tests/test_gpu_render.py reads it there
 
 namespace SPA_NS {
 
@@ -171,3 +188,61 @@ void k_render_tiles(spa3d_ctx* c, const RenderArgs& a) {
 }
 
 }  // namespace SPA_NS
+
+// ---- the entry points ----
+// The launches of one call.  Runs twice: dry (no launch, a counting arena: the workspace the call needs) and for real.  Workspace: the partial
+// min / max pairs, and -- when frames are drawn -- the positions, flag words and boxes of the N x T point-frames.
+static void render_body(spa3d_ctx* c, const spa3d_render* r) {
+  const int64_t n = (int64_t)r->N * r->T;
+  RenderArgs a{};
+  a.c = RpClip{r->N, r->T, r->H, r->W, r->coords, r->resize_h, r->resize_w, r->normalize != 0, r->use_visibility != 0, r->colour_bgr != 0, r->trail, r->point_size};
+  a.video = r->video; a.out = r->out; a.tracks = r->tracks; a.K = r->coords == 3 ? r->intrinsics : nullptr; a.E = r->coords == 3 ? r->extrinsics : nullptr;
+  a.scores = r->out ? r->scores : nullptr; a.visible = r->use_visibility ? r->visible : nullptr; a.pixels = r->pixels;
+  a.nparts = (int)std::min<int64_t>(RENDER_PARTS, (n + RENDER_CHUNK - 1) / RENDER_CHUNK);
+  const bool norm = a.scores && r->normalize;
+  if (norm) { a.part = (float*)c->ar.alloc(RENDER_PARTS * 2 * 4); k_render_minmax(c, a); }
+  if (r->out) {
+    a.pos = (int32_t*)c->ar.alloc(n * 8); a.fl = (uint32_t*)c->ar.alloc(n * 4); a.box = (short*)c->ar.alloc(n * 8);
+  }
+  k_render_points(c, a);
+  if (!r->out) return;
+  k_render_boxes(c, a);
+  k_render_tiles(c, a);
+}
+static int64_t render_need(spa3d_ctx* c, const spa3d_render* r) {
+  return arena_peak(c, [&] { render_body(c, r); }) + 256;  // never 0: a call without a workspace is refused after the walk
+}
+
+extern "C" {
+
+int64_t spa3d_render_workspace_bytes(spa3d_handle h, int32_t N, int32_t T) {
+  if (!h || N <= 0 || T <= 0) return -1;
+  const int64_t n = (int64_t)N * T;
+  auto up = [](int64_t b) { return (b + 255) & ~int64_t(255); };
+  return up(RENDER_PARTS * 2 * 4) + up(n * 8) + up(n * 4) + up(n * 8) + 256;
+}
+int spa3d_render_tracks(spa3d_handle h, const spa3d_render* r, void* ws, int64_t ws_bytes, void* stream) {
+  if (!h) return SPA3D_ERR_ARG;
+  h->err.clear(); h->hip_err = 0;
+  auto bad = [&](const std::string& m) { h->err = "render: " + m; return SPA3D_ERR_ARG; };
+  if (!r) return bad("spa3d_render is required");
+  if (r->N < 1 || r->T < 1) return bad("N = " + std::to_string(r->N) + ", T = " + std::to_string(r->T) + ": both must be positive");
+  if (r->H < 1 || r->H > RP_MAX_DIM || r->W < 1 || r->W > RP_MAX_DIM)
+    return bad("H = " + std::to_string(r->H) + ", W = " + std::to_string(r->W) + " are outside [1, " + std::to_string(RP_MAX_DIM) + "]");
+  if (!r->tracks) return bad("tracks is required");
+  if (r->coords != 2 && r->coords != 3) return bad("coords = " + std::to_string(r->coords) + " is neither 2 nor 3");
+  if (r->coords == 3 && (!r->intrinsics || !r->extrinsics)) return bad("coords == 3 needs the camera matrices (intrinsics, extrinsics)");
+  if (r->coords == 3 && (r->resize_h < 1 || r->resize_w < 1)) return bad("coords == 3 needs resize_h, resize_w >= 1");
+  if (!r->out && !r->pixels) return bad("nothing to do: out and pixels are both NULL");
+  if (r->out && (!r->video || !r->scores)) return bad("drawing needs video and scores");
+  if (r->use_visibility && !r->visible) return bad("use_visibility needs visible");
+  if (r->trail < 0 || r->trail > RP_MAX_TRAIL) return bad("trail = " + std::to_string(r->trail) + " is outside [0, " + std::to_string(RP_MAX_TRAIL) + "]");
+  if (r->point_size < 0 || r->point_size > RP_MAX_RADIUS)
+    return bad("point_size = " + std::to_string(r->point_size) + " is outside [0, " + std::to_string(RP_MAX_RADIUS) + "]");
+  // a launch holds fewer than 2^32 threads: one thread per point-frame, 256 per (frame, tile)
+  if ((int64_t)r->N * r->T > (int64_t)1 << 31) return bad("N x T = " + std::to_string((int64_t)r->N * r->T) + " point-frames exceed one launch (2^31)");
+  if (r->out && (int64_t)r->T * ((r->W + 63) / 64) * ((r->H + 15) / 16) >= (int64_t)1 << 24) return bad("T x tiles reaches 2^24 workgroups: more than one launch holds");
+  return sized_call(h, "render", render_need(h, r), ws, ws_bytes, stream, [&] { render_body(h, r); });
+}
+
+}  // extern "C"

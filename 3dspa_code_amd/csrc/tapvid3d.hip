@@ -1,4 +1,4 @@
-// tapvid3d.hip -- kernels of spa3d_tapvid3d_from_preds and spa3d_op_median_rows (include/spa3d.h): the TAPVid-3D metric counts of every query
+// tapvid3d.hip -- spa3d_tapvid3d_from_preds and spa3d_op_median_rows (include/spa3d.h), kernels first, entry points below them: the TAPVid-3D metric counts of every query
 // row, with the predictions rescaled by the sample's exact median of |gt| / |pred| or by the row's ratio at its query frame.
 // The definitions are restated from the published definition (compute_tapvid3d_metrics of the tapnet package), parity unpinned; the frame
 // arithmetic and the digit walk of the select live in tapvid3d_row.hpp, which the g++ host test runs too.  fp32 only: compiled once.
@@ -8,7 +8,20 @@
 //   tv_rows_kernel      one wave per query row: the 24 counts, lanes striding over frames, xor butterfly, lanes 0..23 store
 //   tv_reduce_kernel    one workgroup per (sample, slot): the sample's rows pooled in double in a fixed order
 // No float atomics anywhere: the same inputs give the same bits on every run.
+#include <algorithm>
+
 #include "common.hpp"
+#include "tapvid3d_row.hpp"  // TAPVid-3D metric counts of a row and the exact median select (host- and device-callable)
+
+// The launches of spa3d_tapvid3d_from_preds share this block: the caller's whole tensors, indexed by the global query row, and the
+// rows [row0, row0 + nq) a launch covers.  ratio / sel / row_scale / scale may be null (see each kernel).
+struct TvArgs {
+  const float* tracks; const float* vlog; const float* tgt; const float* tvis; const float* qpts; const float* intr;  // intr: device [B][4] or null
+  const float* scale;          // rows pass, median scaling: device [B]
+  float* ratio; float* sel;    // ratio pass: ratio [B * Q][T] of every frame; sel: the same with NaN outside {vis and ew} (the median's set)
+  float* row_scale; float* qstats;
+  int64_t nq, row0; int Q, T, scaling, fixed;
+};
 
 namespace SPA_NS {
 
@@ -141,7 +154,63 @@ void k_tv_fill(spa3d_ctx* c, float* p, int64_t n, float v) {
 
 }  // namespace SPA_NS
 
+// ---- the entry points ----
+// The launches of one call.  Runs twice: dry (no launch, a counting arena: the workspace the call needs) and for real.  Workspace: the median's
+// set [B * Q][T_out] (median scaling only) and the per-sample factors [B] when the caller does not ask for them.
+static void tapvid3d_body(spa3d_ctx* c, const spa3d_batch* b, const spa3d_outputs* preds, const spa3d_tapvid3d* m, const int32_t* cq) {
+  const int To = c->cfg.num_output_frames;
+  const int64_t B = b->B, Q = b->Q;
+  const bool median = m->scaling == SPA3D_SCALE_MEDIAN;
+  TvArgs a{};
+  a.tracks = preds->tracks; a.vlog = preds->visible_logits; a.tgt = b->query_tracks; a.tvis = b->query_tracks_visible; a.qpts = b->query_points;
+  a.intr = m->intrinsics; a.ratio = m->ratio; a.row_scale = m->row_scale; a.qstats = m->query_stats;
+  a.Q = b->Q; a.T = To; a.scaling = m->scaling; a.fixed = m->fixed_thresholds != 0;
+  a.sel = median ? (float*)c->ar.alloc(B * Q * To * 4) : nullptr;
+  float* scale = m->scale ? m->scale : (median ? (float*)c->ar.alloc(B * 4) : nullptr);
+  a.scale = scale;
+  // rows of padded queries (spa3d_set_counts): every result reads 0, their inputs are never read and they are not part of the median
+  auto zero_padded = [&](int64_t r0, int64_t nr) {
+    if (c->dry || nr <= 0) return;
+    (void)hipMemsetAsync(m->query_stats + r0 * TV_S, 0, (size_t)(nr * TV_S) * 4, c->stream);
+    if (m->row_scale) (void)hipMemsetAsync(m->row_scale + r0, 0, (size_t)nr * 4, c->stream);
+    if (m->ratio) (void)hipMemsetAsync(m->ratio + r0 * To, 0, (size_t)(nr * To) * 4, c->stream);
+  };
+  if (a.ratio || a.sel) for_each_live_span(cq, B, Q, [&](int64_t row0, int64_t nq) { a.row0 = row0; a.nq = nq; k_tv_ratio(c, a); });
+  if (median) {
+    if (!cq) k_median_rows(c, a.sel, B, Q * To, Q * To, scale);
+    else for (int64_t i = 0; i < B; ++i) k_median_rows(c, a.sel + i * Q * To, 1, Q * To, (int64_t)cq[i] * To, scale + i);
+  } else if (scale) {
+    k_tv_fill(c, scale, B, 1.f);
+  }
+  for_each_live_span(cq, B, Q, [&](int64_t row0, int64_t nq) { a.row0 = row0; a.nq = nq; k_tv_rows(c, a); });
+  if (cq) for_each_live_span(cq, B, Q, [&](int64_t row0, int64_t nq) { zero_padded(row0 + nq, Q - nq); });
+  if (m->sample_stats) k_tv_reduce(c, m->query_stats, B, b->Q, m->sample_stats);
+}
+static int64_t tapvid3d_need(spa3d_ctx* c, const spa3d_batch* b, const spa3d_outputs* preds, const spa3d_tapvid3d* m, const int32_t* cq) {
+  return arena_peak(c, [&] { tapvid3d_body(c, b, preds, m, cq); }) + 256;  // never 0: a call without a workspace is refused after the walk, whatever the scaling
+}
+
 extern "C" {
+
+int64_t spa3d_tapvid3d_workspace_bytes(spa3d_handle h, int32_t B, int32_t Q, int32_t T) {
+  if (!h || B <= 0 || Q <= 0 || T <= 0) return -1;
+  const int64_t To = std::max(T, h->cfg.num_output_frames);  // the largest need of any scaling: the median's set and the factors, each 256-byte aligned
+  return (((int64_t)B * Q * To * 4 + 255) & ~int64_t(255)) + (((int64_t)B * 4 + 255) & ~int64_t(255)) + 256;
+}
+int spa3d_tapvid3d_from_preds(spa3d_handle h, const spa3d_batch* b, const spa3d_outputs* preds, spa3d_tapvid3d* m, void* ws, int64_t ws_bytes, void* stream) {
+  if (!h) return SPA3D_ERR_ARG;
+  h->err.clear(); h->hip_err = 0;
+  if (h->cfg.model_kind == 1) { h->err = "tapvid3d: the 2-D model (model_kind 1) has no depth coordinate"; return SPA3D_ERR_ARG; }
+  if (!b || !b->query_tracks || !b->query_tracks_visible) { h->err = "tapvid3d: the batch needs its targets (query_tracks, query_tracks_visible)"; return SPA3D_ERR_ARG; }
+  if (!b->query_points) { h->err = "tapvid3d: the batch needs query_points (the query frame is left out of every count)"; return SPA3D_ERR_ARG; }
+  if (!preds || !preds->tracks || !preds->visible_logits) { h->err = "tapvid3d: predictions (tracks, visible_logits) are required"; return SPA3D_ERR_ARG; }
+  if (!m || !m->query_stats) { h->err = "tapvid3d: spa3d_tapvid3d::query_stats is required"; return SPA3D_ERR_ARG; }
+  if (m->scaling < SPA3D_SCALE_NONE || m->scaling > SPA3D_SCALE_PER_TRAJECTORY) { h->err = "tapvid3d: scaling = " + std::to_string(m->scaling) + " is outside [0, 2]"; return SPA3D_ERR_ARG; }
+  if (b->B <= 0 || b->Q <= 0) { h->err = "batch: B,Q must be positive"; return SPA3D_ERR_ARG; }
+  const int32_t* cq = nullptr;
+  if (h->has_cnt_q && !(cq = checked_query_counts(h, b->B, b->Q))) return SPA3D_ERR_ARG;
+  return sized_call(h, "tapvid3d", tapvid3d_need(h, b, preds, m, cq), ws, ws_bytes, stream, [&] { tapvid3d_body(h, b, preds, m, cq); });
+}
 
 int spa3d_op_median_rows(const float* x, int64_t rows, int64_t n, float* out, void* ws, int64_t ws_bytes, void* stream) {
   (void)ws; (void)ws_bytes;  // the select needs no scratch: its histograms live in LDS

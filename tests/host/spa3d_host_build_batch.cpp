@@ -1,5 +1,5 @@
 // Host-side walk of spa3d_build_batch's refusals under AddressSanitizer + UndefinedBehaviorSanitizer, built like spa3d_host_tapvid3d.cpp
-// (tests/test_build_batch_host_dryrun.py).  No GPU is touched: the entry checks every clip before its first launch, so each call below returns
+// (tests/test_host_sanitizers.py).  No GPU is touched: the entry checks every clip before its first launch, so each call below returns
 // SPA3D_ERR_ARG with a message and launches nothing.  The pointers are fakes that are never dereferenced; a call that got past the checks would
 // try to launch and come back with another status, which fails the CHECK.
 #include <cstdio>

@@ -1,5 +1,5 @@
 // Host-side walk of RAGGED calls (spa3d_set_counts) under AddressSanitizer + UndefinedBehaviorSanitizer, built like spa3d_host_dryrun.cpp
-// (tests/test_ragged_host_dryrun.py).  No GPU is touched: every entry point validates the counts and sizes its workspace with a dry run of the
+// (tests/test_host_sanitizers.py).  No GPU is touched: every entry point validates the counts and sizes its workspace with a dry run of the
 // orchestration BEFORE its first launch, so a call with a zero-byte workspace walks the whole ragged orchestration -- packed chunks,
 // per-sample loops, samples without queries -- and returns SPA3D_ERR_WORKSPACE with the bytes one sample chunk needs.  Checked here:
 // that need never exceeds spa3d_workspace_bytes of the padded shape (include/spa3d.h promises the bound), and every refusal.
@@ -78,6 +78,17 @@ int main() {
       CHECK(spa3d_set_counts(h, r.B, r.n, r.q) == SPA3D_OK);
       CHECK(spa3d_forward(h, fake, &b, &out, fake, 0, nullptr) == SPA3D_ERR_ARG && strlen(spa3d_last_error(h)) > 0);
       CHECK(spa3d_loss_and_grads(h, fake, &b, 0.f, fake, 0, fake, &out, fake, 0, nullptr) == SPA3D_ERR_ARG);
+    }
+    // every entry that reads query_count refuses counts set for another B and a count above Q, by name, before a launch
+    spa3d_scores sc; memset(&sc, 0, sizeof sc); sc.query_stats = fake;
+    spa3d_tapvid3d tv; memset(&tv, 0, sizeof tv); tv.query_stats = fake;
+    struct { int B; const int32_t* q; const char* msg; } refused[] = {{B - 1, ok_q, "counts were set"}, {B, qbig, "query_count"}};
+    for (auto& r : refused) {
+      CHECK(spa3d_set_counts(h, r.B, nullptr, r.q) == SPA3D_OK);
+      CHECK(spa3d_forward(h, fake, &b, &out, fake, 0, nullptr) == SPA3D_ERR_ARG && strstr(spa3d_last_error(h), r.msg));
+      CHECK(spa3d_score_from_preds(h, &b, &out, &sc, nullptr) == SPA3D_ERR_ARG && strstr(spa3d_last_error(h), r.msg));
+      CHECK(spa3d_tapvid3d_from_preds(h, &b, &out, &tv, fake, 0, nullptr) == SPA3D_ERR_ARG && strstr(spa3d_last_error(h), r.msg));
+      CHECK(spa3d_loss(h, &b, &out, 0.f, fake, nullptr) == SPA3D_ERR_ARG && strstr(spa3d_last_error(h), r.msg));
     }
     CHECK(spa3d_set_counts(h, B, ok_n, ok_q) == SPA3D_OK);
     for (const char* o : {"track_chunk", "query_chunk"}) {

@@ -1,5 +1,5 @@
 // Host-side walk of spa3d_render_tracks under AddressSanitizer + UndefinedBehaviorSanitizer, built like spa3d_host_tapvid3d.cpp
-// (tests/test_render_host_dryrun.py).  No GPU is touched: the entry validates its arguments and sizes its workspace with a dry run of its
+// (tests/test_host_sanitizers.py).  No GPU is touched: the entry validates its arguments and sizes its workspace with a dry run of its
 // launches BEFORE the first real one, so a call with a zero-byte workspace walks every launch site -- small and large clips, both coordinate
 // forms, with and without normalisation, visibility, `pixels`, and the positions-only form -- and returns SPA3D_ERR_ARG with the bytes it
 // needs.  Checked here: that need never exceeds spa3d_render_workspace_bytes, and every refusal returns SPA3D_ERR_ARG with a message.

@@ -1,5 +1,5 @@
 // Host-side walk of spa3d_score / spa3d_score_from_preds under AddressSanitizer + UndefinedBehaviorSanitizer, built like spa3d_host_ragged.cpp
-// (tests/test_score_host_dryrun.py).  No GPU is touched: spa3d_score validates its arguments and sizes its workspace with a dry run of the
+// (tests/test_host_sanitizers.py).  No GPU is touched: spa3d_score validates its arguments and sizes its workspace with a dry run of the
 // orchestration BEFORE its first launch, so a call with a zero-byte workspace walks the whole score orchestration -- the BASELINE shapes, a
 // ragged batch with a sample without queries, query chunks, the 2-D twin -- and returns SPA3D_ERR_WORKSPACE with the bytes it needs.
 // Checked here: that need never exceeds spa3d_workspace_bytes(train = 0), and every refusal returns SPA3D_ERR_ARG with a message.

@@ -1,5 +1,5 @@
 // Host-side walk of spa3d_tapvid3d_from_preds under AddressSanitizer + UndefinedBehaviorSanitizer, built like spa3d_host_score.cpp
-// (tests/test_tapvid3d_host_dryrun.py).  No GPU is touched: the entry validates its arguments and sizes its workspace with a dry run of its
+// (tests/test_host_sanitizers.py).  No GPU is touched: the entry validates its arguments and sizes its workspace with a dry run of its
 // orchestration BEFORE its first launch, so a call with a zero-byte workspace walks every launch site -- the BASELINE shapes, the three
 // scalings, with and without the optional outputs, a ragged batch with a query-less sample -- and returns SPA3D_ERR_ARG with the bytes it
 // needs.  Checked here: that need never exceeds spa3d_tapvid3d_workspace_bytes, and every refusal returns SPA3D_ERR_ARG with a message.

@@ -3,13 +3,13 @@ test, so a small driver (tests/host/build_row_check.cpp) is built with the host 
 inputs of tests/golden/sampler_golden.npz.  Expected, bit for bit: the reference's own outputs stored there.  The two 16-bit roundings are
 compared with torch's, and the slot rule is probed at its edges.  No GPU needed."""
 import os
-import shutil
 import struct
 import subprocess
 
 import numpy as np
 import pytest
 import torch
+from util import host_check_driver
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 Z = np.load(os.path.join(ROOT, 'tests', 'golden', 'sampler_golden.npz'), allow_pickle=False)
@@ -17,14 +17,7 @@ Z = np.load(os.path.join(ROOT, 'tests', 'golden', 'sampler_golden.npz'), allow_p
 
 @pytest.fixture(scope='module')
 def driver(tmp_path_factory):
-  cxx = shutil.which('g++') or shutil.which('c++')
-  if cxx is None:
-    pytest.fail('no host C++ compiler')
-  exe = str(tmp_path_factory.mktemp('build_row') / 'build_row_check')
-  r = subprocess.run([cxx, '-std=c++17', '-O1', '-ffp-contract=off', '-Wall', '-Wextra', '-Werror', os.path.join(ROOT, 'tests', 'host', 'build_row_check.cpp'), '-o', exe],
-                     capture_output=True, text=True)
-  assert r.returncode == 0, r.stderr[-3000:]
-  return exe
+  return host_check_driver(tmp_path_factory, 'build_row')
 
 
 def _run(driver, mode, blob):

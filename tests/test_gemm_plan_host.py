@@ -3,13 +3,10 @@
 every `gemm_impl` value, every kernel of the catalogue and both sides of each threshold (rows 512 / 16 384 / 65 536, K <= 512, M.N < 128^2,
 8-phase dW tile waste <= 1.25, brow_group >= 16), the operand refusals and the fused column sums.  The planner has no dry mode: a row holds
 for the sizing pass and the real pass alike.  No GPU needed."""
-import os
-import shutil
 import subprocess
 
 import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from util import host_check_driver
 
 BT = 'Bt=0x500000'
 # dW descriptor: C[Ki = M][N] += A^T B over K rows
@@ -172,14 +169,7 @@ CASES = [
 
 @pytest.fixture(scope='module')
 def driver(tmp_path_factory):
-  cxx = shutil.which('g++') or shutil.which('c++')
-  if cxx is None:
-    pytest.fail('no host C++ compiler')
-  exe = str(tmp_path_factory.mktemp('gemm_plan') / 'gemm_plan_check')
-  r = subprocess.run([cxx, '-std=c++17', '-O1', '-Wall', '-Wextra', '-Werror', os.path.join(ROOT, 'tests', 'host', 'gemm_plan_check.cpp'), '-o', exe],
-                     capture_output=True, text=True)
-  assert r.returncode == 0, r.stderr[-3000:]
-  return exe
+  return host_check_driver(tmp_path_factory, 'gemm_plan', fp_contract_off=False)
 
 
 def test_gemm_plan_table(driver):

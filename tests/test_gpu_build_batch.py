@@ -21,7 +21,7 @@ pytestmark = pytest.mark.gpu
 
 Z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'sampler_golden.npz'), allow_pickle=False)
 DTYPES = {'fp32': torch.float32, 'bf16': torch.bfloat16, 'fp16': torch.float16}
-LAUNCH_CLIPS = 16  # BB_CLIPS of csrc/common.hpp: what one launch holds
+LAUNCH_CLIPS = 16  # BB_CLIPS of csrc/batch_build.hip: what one launch holds
 
 
 def _bits(t):

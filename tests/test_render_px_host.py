@@ -4,7 +4,6 @@ through it.  Every byte and every pixel position is compared with equality again
 (tests/render_util.py) and, for projection, normalisation and colours, against what the reference's own functions gave
 (tests/golden/visualize_golden.npz).  No GPU needed."""
 import os
-import shutil
 import struct
 import subprocess
 
@@ -12,6 +11,7 @@ import numpy as np
 import pytest
 
 import render_util as RU
+from util import host_check_driver
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, 'tests', 'golden', 'visualize_golden.npz')
@@ -19,14 +19,7 @@ GOLDEN = os.path.join(ROOT, 'tests', 'golden', 'visualize_golden.npz')
 
 @pytest.fixture(scope='module')
 def driver(tmp_path_factory):
-  cxx = shutil.which('g++') or shutil.which('c++')
-  if cxx is None:
-    pytest.fail('no host C++ compiler')
-  exe = str(tmp_path_factory.mktemp('render_px') / 'render_px_check')
-  r = subprocess.run([cxx, '-std=c++17', '-O1', '-ffp-contract=off', '-Wall', '-Wextra', '-Werror', os.path.join(ROOT, 'tests', 'host', 'render_px_check.cpp'), '-o', exe],
-                     capture_output=True, text=True)
-  assert r.returncode == 0, r.stderr[-3000:]
-  return exe
+  return host_check_driver(tmp_path_factory, 'render_px')
 
 
 @pytest.fixture(scope='module')

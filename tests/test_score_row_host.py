@@ -3,8 +3,6 @@ from-predictions kernel and this test, so a small driver (tests/host/score_row_c
 T in {8, 150, 300}, NC in {2, 3}, K in {0, 1, 5, 8}, rows without a visible frame and rows with every frame visible, with and without a
 sample scale -- and its stats rows and frame errors are compared with the NumPy float64 restatement in tests/score_util.py under the rules
 stated there.  No GPU needed."""
-import os
-import shutil
 import struct
 import subprocess
 
@@ -12,22 +10,14 @@ import numpy as np
 import pytest
 
 import score_util as SU
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from util import host_check_driver
 
 THRESHOLDS = {0: [], 1: [2.0], 5: [0.5, 1.0, 2.0, 4.0, 8.0], 8: [0.25, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 8.0]}
 
 
 @pytest.fixture(scope='module')
 def driver(tmp_path_factory):
-  cxx = shutil.which('g++') or shutil.which('c++')
-  if cxx is None:
-    pytest.fail('no host C++ compiler')
-  exe = str(tmp_path_factory.mktemp('score_row') / 'score_row_check')
-  r = subprocess.run([cxx, '-std=c++17', '-O1', '-ffp-contract=off', '-Wall', '-Wextra', '-Werror', os.path.join(ROOT, 'tests', 'host', 'score_row_check.cpp'), '-o', exe],
-                     capture_output=True, text=True)
-  assert r.returncode == 0, r.stderr[-3000:]
-  return exe
+  return host_check_driver(tmp_path_factory, 'score_row')
 
 
 def _rows(rng, R, T, NC):

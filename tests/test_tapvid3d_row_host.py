@@ -3,8 +3,6 @@ and this test, so a small driver (tests/host/tapvid3d_row_check.cpp) is built wi
 (3, 37, 70) and (2, 9, 150), the three scalings, depth-dependent and fixed thresholds, default and explicit intrinsics -- are compared with the
 NumPy float64 restatement in tests/tapvid3d_util.py under the rules stated there, and its median select is compared bit for bit with NumPy's
 on the cases a radix select can get wrong.  No GPU needed."""
-import os
-import shutil
 import struct
 import subprocess
 
@@ -12,20 +10,12 @@ import numpy as np
 import pytest
 
 import tapvid3d_util as TU
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from util import host_check_driver
 
 
 @pytest.fixture(scope='module')
 def driver(tmp_path_factory):
-  cxx = shutil.which('g++') or shutil.which('c++')
-  if cxx is None:
-    pytest.fail('no host C++ compiler')
-  exe = str(tmp_path_factory.mktemp('tapvid3d_row') / 'tapvid3d_row_check')
-  r = subprocess.run([cxx, '-std=c++17', '-O1', '-ffp-contract=off', '-Wall', '-Wextra', '-Werror', os.path.join(ROOT, 'tests', 'host', 'tapvid3d_row_check.cpp'), '-o', exe],
-                     capture_output=True, text=True)
-  assert r.returncode == 0, r.stderr[-3000:]
-  return exe
+  return host_check_driver(tmp_path_factory, 'tapvid3d_row')
 
 
 def host_rows(driver, d, b, scaling, s, intr, fixed):

@@ -1,8 +1,11 @@
 """Shared helpers for the parity tests: tiny configs, oracle<->product parameter exchange."""
 import os
+import shutil
+import subprocess
 import sys
 
 import numpy as np
+import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -14,6 +17,18 @@ from oracle import spa3d_oracle as O  # noqa: E402  (tests may use the oracle; t
 MINI = dict(num_output_frames=8, num_latent_tokens=8, latent_token_dim=16, num_frequencies=4, track_token_dim=32,
             encoder_latent_dim=48, decoder_num_channels=192, num_heads=2, qkv_size=32, enc_mlp=64, enc_layers=2, t2l_mlp=64,
             t2l_layers=2, dec_mlp=64, dec_layers=1, ro_mlp=64, ro_layers=2)
+
+
+def host_check_driver(tmp_path_factory, name, fp_contract_off=True):
+  """tests/host/<name>_check.cpp built with the host compiler (-ffp-contract=off, as the library, unless told otherwise): the program's path."""
+  cxx = shutil.which('g++') or shutil.which('c++')
+  if cxx is None:
+    pytest.fail('no host C++ compiler')
+  exe = str(tmp_path_factory.mktemp(name) / f'{name}_check')
+  flags = ['-std=c++17', '-O1'] + (['-ffp-contract=off'] if fp_contract_off else []) + ['-Wall', '-Wextra', '-Werror']
+  r = subprocess.run([cxx] + flags + [os.path.join(ROOT, 'tests', 'host', f'{name}_check.cpp'), '-o', exe], capture_output=True, text=True)
+  assert r.returncode == 0, r.stderr[-3000:]
+  return exe
 
 
 def oracle_cfg(**kw):
