@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+import parity_util as PU
 from util import MINI, O, batch_to, max_abs, product_model, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -33,9 +34,12 @@ def _ws(nbytes=256 << 20):
   return torch.empty(nbytes, dtype=torch.uint8, device='cuda')
 
 
+FP16_TILED = [(4133, 2304, 384, 0, False, False), (777, 1536, 384, 1, False, True), (2050, 384, 1536, 0, True, True), (300, 600, 1280, 0, False, True),
+              (70008, 512, 256, 0, True, True)]
+
+
 @pytest.mark.parametrize('force8p', [False, True])
-@pytest.mark.parametrize('M,N,K,act,res,bias', [(4133, 2304, 384, 0, False, False), (777, 1536, 384, 1, False, True), (2050, 384, 1536, 0, True, True),
-                                                (300, 600, 1280, 0, False, True), (70008, 512, 256, 0, True, True)])
+@pytest.mark.parametrize('M,N,K,act,res,bias', FP16_TILED)
 def test_fp16_linear_tiled(lib, force8p, M, N, K, act, res, bias):
   IMPL = 3 if force8p else 2  # 3: the 8-phase kernels for any M
   g = torch.Generator().manual_seed(11)
@@ -46,19 +50,22 @@ def test_fp16_linear_tiled(lib, force8p, M, N, K, act, res, bias):
   Ad, Bd = A.cuda(), B.cuda()
   bd = bs.cuda() if bias else None
   Rd = R.cuda() if res else None
-  Cd = torch.full((M, N), float('nan'), device='cuda', dtype=torch.float16)
-  ws = _ws()
+  Cd = PU.guarded(M, N, torch.float16)
+  ws = PU.poisoned_ws(PU.linear_ws_bytes(N, K))
   assert lib.spa3d_op_linear(Ad.data_ptr(), Bd.data_ptr(), bd.data_ptr() if bias else None, Rd.data_ptr() if res else None, Cd.data_ptr(),
                              M, N, K, act, F16, IMPL, ws.data_ptr(), ws.numel(), _s()) == 0
+  PU.check_guards()
   ref = A.double() @ B.double()
   if bias:
     ref = ref + bs.double()
+  pre = ref
   if act:
     ref = O.gelu_tanh(ref)
   if res:
     ref = ref + R.double()
   assert not torch.isnan(Cd.float()).any()
   assert rel_err(Cd.float(), ref) < 6e-4  # fp16 output rounding only (2^-12); accumulation is fp32
+  PU.assert_elementwise(Cd, ref, PU.linear_bound(A, B, bs, R, act, ref, pre, torch.float16), 'C')
 
 
 @pytest.mark.parametrize('M,N,K', [(5000, 384, 256), (3333, 2304, 384), (70001, 384, 768)])
@@ -69,27 +76,42 @@ def test_fp16_linear_bwd_tiled(lib, M, N, K):
   B = (torch.randn(K, N, generator=g) / math.sqrt(K)).half()
   dC = torch.randn(M, N, generator=g).half()
   Ad, Bd, dCd = A.cuda(), B.cuda(), dC.cuda()
-  dA = torch.full((M, K), float('nan'), device='cuda', dtype=torch.float16)
-  dB = torch.full((K, N), float('nan'), device='cuda')
-  db = torch.full((N,), float('nan'), device='cuda')
-  ws = _ws()
+  dA = PU.guarded(M, K, torch.float16, name='dA')
+  dB = PU.guarded(K, N, torch.float32, name='dB')
+  db = PU.guarded(1, N, torch.float32, name='dbias')[0]
+  ws = PU.poisoned_ws(PU.linear_ws_bytes(N, K))
   assert lib.spa3d_op_linear_bwd(Ad.data_ptr(), Bd.data_ptr(), dCd.data_ptr(), dA.data_ptr(), dB.data_ptr(), db.data_ptr(), M, N, K, F16, IMPL,
                                  ws.data_ptr(), ws.numel(), _s()) == 0
-  assert rel_err(dA.float(), dC.double() @ B.double().T) < 6e-4
-  assert rel_err(dB, A.double().T @ dC.double()) < 1e-5  # exact fp16 products, fp32 accumulate + fp32 atomics
-  assert rel_err(db, dC.double().sum(0)) < 1e-5
+  PU.check_guards()
+  rA, rB, rb = dC.double() @ B.double().T, A.double().T @ dC.double(), dC.double().sum(0)
+  assert rel_err(dA.float(), rA) < 6e-4
+  assert rel_err(dB, rB) < 1e-5  # exact fp16 products, fp32 accumulate + fp32 atomics
+  assert rel_err(db, rb) < 1e-5
+  PU.gate_linear_bwd(A, B, dC, dA, dB, db, rA, rB, rb, torch.float16)
 
 
-@pytest.mark.parametrize('d', [384, 1280])
+@pytest.mark.parametrize('d', [384, 1280, 512, 1152, 100])
 def test_fp16_layernorm(lib, d):
-  g = torch.Generator().manual_seed(5)
-  rows = 777
-  x = (torch.randn(rows, d, generator=g) * 3 + 1).half()
-  sc = 1 + 0.1 * torch.randn(d, generator=g)
-  xd, scd = x.cuda(), sc.cuda()
-  y = torch.empty_like(xd); st = torch.empty(rows, 2, device='cuda')
-  assert lib.spa3d_op_layernorm(xd.data_ptr(), scd.data_ptr(), y.data_ptr(), st.data_ptr(), rows, d, F16, _s()) == 0
-  assert rel_err(y.float(), O.layer_norm(x.double(), sc.double())) < 6e-4
+  """384 / 1280: the part kernels; 512 / 1152: the vectorised kernels in 1 / 3 steps; 100 (8 does not divide it): the plain kernels -- forward and backward, as
+  tests/test_gpu_ops.py::test_layernorm_fwd_bwd lists them; rows 1, 3, 257 beside the 777 the test had.  Element-wise gates on y, dx and dscale."""
+  for rows in (777, 1, 3, 257):
+    g = torch.Generator().manual_seed(5)
+    x = (torch.randn(rows, d, generator=g) * 3 + 1).half()
+    sc = 1 + 0.1 * torch.randn(d, generator=g)
+    dy = torch.randn(rows, d, generator=g).half()
+    xd, scd, dyd = x.cuda(), sc.cuda(), dy.cuda()
+    y = PU.guarded(rows, d, torch.float16, name='y'); st = PU.guarded(rows, 2, torch.float32, name='stats')
+    assert lib.spa3d_op_layernorm(xd.data_ptr(), scd.data_ptr(), y.data_ptr(), st.data_ptr(), rows, d, F16, _s()) == 0
+    PU.check_guards()
+    assert rel_err(y.float(), O.layer_norm(x.double(), sc.double())) < 6e-4
+    dx = PU.guarded(rows, d, torch.float16, name='dx'); ds = PU.guarded(1, d, torch.float32, name='dscale', fill=0.0)[0]
+    assert lib.spa3d_op_layernorm_bwd(xd.data_ptr(), scd.data_ptr(), st.data_ptr(), dyd.data_ptr(), dx.data_ptr(), ds.data_ptr(), rows, d, F16, _s()) == 0
+    PU.check_guards()
+    y64, dx64, ds64 = PU.layernorm_restated(x, sc, dy, torch.float64)
+    y32, dx32, ds32 = PU.layernorm_restated(x, sc, dy, torch.float32)
+    PU.assert_elementwise(y, y64, PU.restated_bound(y64, y32, torch.float16), 'y')
+    PU.assert_elementwise(dx, dx64, PU.restated_bound(dx64, dx32, torch.float16), 'dx')
+    PU.assert_elementwise(ds, ds64, PU.restated_bound(ds64, ds32, torch.float32), 'dscale')
 
 
 @pytest.mark.parametrize('bwd_mode', ['1', '3'])
@@ -107,14 +129,15 @@ def test_fp16_attention_fused(lib, nseq, S, H, masked, bwd_mode):
   if masked:
     km = (torch.rand(nseq, S, generator=g) < 0.8).float(); km[:, 0] = 1.0; km[0, 1:] = 0.0
   qkvd = qkv.cuda()
-  o = torch.full((nseq, S, E), float('nan'), device='cuda', dtype=torch.float16)
-  lse = torch.zeros(nseq, H, S, 2, device='cuda')
-  ws = _ws(64 << 20)
+  o = PU.guarded(nseq * S, E, torch.float16, name='o').view(nseq, S, E)
+  lse = PU.guarded(nseq * H * S, 2, torch.float32, name='lse', fill=0.0).view(nseq, H, S, 2)
+  ws = PU.poisoned_ws(1 << 20)   # the LDS-resident kernels carve nothing from it
   sqd, skd = sq.cuda(), sk.cuda()
   kmd = km.cuda() if masked else None
   assert lib.spa3d_op_attention(qkvd[..., :E].data_ptr(), qkvd[..., E:2 * E].data_ptr(), qkvd[..., 2 * E:].data_ptr(), 3 * E, 3 * E, 3 * E,
                                 sqd.data_ptr(), skd.data_ptr(), kmd.data_ptr() if masked else None, nseq, S, S, H, Dh, o.data_ptr(),
                                 lse.data_ptr(), F16, 2, ws.data_ptr(), ws.numel(), _s()) == 0
+  PU.check_guards()
   qr = qkv[..., :E].double().contiguous().requires_grad_(True)
   kr = qkv[..., E:2 * E].double().contiguous().requires_grad_(True)
   vr = qkv[..., 2 * E:].double().contiguous().requires_grad_(True)
@@ -123,19 +146,28 @@ def test_fp16_attention_fused(lib, nseq, S, H, masked, bwd_mode):
   e = rel_err(o.float(), ref.detach())
   print('fp16 fused attention fwd rel err', e)
   assert e < 3e-3  # bf16: 2e-2
+  from util import Gates
+  gt = Gates(f'fp16 fused self-attention forward, nseq {nseq} S {S} H {H} masked {masked}: kernel vs host emulation, both against the fp64 oracle')
+  PU.attention_row_gate(gt, 'o', o, PU.emulate_attention(qkv[..., :E], qkv[..., E:2 * E], qkv[..., 2 * E:], sq, sk, km, H, Dh), ref.detach(), H, Dh)
+  gt.check()
   d_o = torch.randn(nseq, S, E, generator=g).half()
   ref.backward(d_o.double())
   dod = d_o.cuda()
-  dqkv = torch.full((nseq, S, 3 * E), float('nan'), device='cuda', dtype=torch.float16)
-  dsq = torch.zeros(Dh, device='cuda'); dsk = torch.zeros(Dh, device='cuda')
+  dqkv = PU.guarded(nseq * S, 3 * E, torch.float16, name='dqkv').view(nseq, S, 3 * E)
+  dsq = PU.guarded(1, Dh, torch.float32, name='dsq', fill=0.0)[0]; dsk = PU.guarded(1, Dh, torch.float32, name='dsk', fill=0.0)[0]
   assert lib.spa3d_op_attention_bwd(qkvd[..., :E].data_ptr(), qkvd[..., E:2 * E].data_ptr(), qkvd[..., 2 * E:].data_ptr(), 3 * E, 3 * E, 3 * E,
                                     sqd.data_ptr(), skd.data_ptr(), kmd.data_ptr() if masked else None, nseq, S, S, H, Dh, o.data_ptr(),
                                     lse.data_ptr(), dod.data_ptr(), dqkv[..., :E].data_ptr(), dqkv[..., E:2 * E].data_ptr(),
                                     dqkv[..., 2 * E:].data_ptr(), dsq.data_ptr(), dsk.data_ptr(), F16, BWD_IMPL, ws.data_ptr(), ws.numel(), _s()) == 0
+  PU.check_guards()
   errs = [rel_err(dqkv[..., :E].float(), qr.grad), rel_err(dqkv[..., E:2 * E].float(), kr.grad), rel_err(dqkv[..., 2 * E:].float(), vr.grad),
           rel_err(dsq, sqr.grad), rel_err(dsk, skr.grad)]
   print('fp16 fused attention bwd rel errs dq dk dv dsq dsk', errs)
   assert max(errs) < 5e-3  # bf16: 3e-2
+  gb = Gates(f'fp16 fused self-attention backward, mode {bwd_mode} nseq {nseq} S {S} H {H} masked {masked}: kernel vs host emulation, both against the fp64 oracle')
+  emu = PU.emulate_attention_bwd(qkv[..., :E], qkv[..., E:2 * E], qkv[..., 2 * E:], sq, sk, km, H, Dh, d_o, fast=bwd_mode == '1' and not masked)
+  PU.attention_grad_gates(gb, (dqkv[..., :E], dqkv[..., E:2 * E], dqkv[..., 2 * E:], dsq, dsk), emu, (qr.grad, kr.grad, vr.grad, sqr.grad, skr.grad), H, Dh)
+  gb.check()
 
 
 def _params_to_oracle(params, dtype):

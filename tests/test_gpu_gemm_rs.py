@@ -7,6 +7,7 @@ import math
 import pytest
 import torch
 
+import parity_util as PU
 from util import rel_err
 
 pytestmark = pytest.mark.gpu
@@ -25,17 +26,22 @@ def _s():
 
 def _run(lib, A, B, bias, dtype, impl, pre=None):
   M, K = A.shape; N = B.shape[1]
-  out = torch.full((M, N), float('nan'), device='cuda', dtype=A.dtype)
-  ws = torch.empty(64 << 20, dtype=torch.uint8, device='cuda')
+  out = PU.guarded(M, N, A.dtype)
+  ws = PU.poisoned_ws(PU.linear_ws_bytes(N, K))
   rc = lib.spa3d_op_linear(A.data_ptr(), B.data_ptr(), bias.data_ptr() if bias is not None else None, pre.data_ptr() if pre is not None else None, out.data_ptr(), M, N, K,
                            2 if pre is not None else 0, dtype, impl,
                            ws.data_ptr(), ws.numel(), _s())
   torch.cuda.synchronize()
+  if rc == 0:
+    PU.check_guards()
   return rc, out
 
 
+RS_SHAPES = [(256, 256, True), (300, 768, False), (8, 2304, True), (5000, 2304, False), (256 * 260 + 77, 768, True), (70000, 1536, True)]
+
+
 @pytest.mark.parametrize('dtype', [BF16, F16])
-@pytest.mark.parametrize('M,N,with_bias', [(256, 256, True), (300, 768, False), (8, 2304, True), (5000, 2304, False), (256 * 260 + 77, 768, True), (70000, 1536, True)])
+@pytest.mark.parametrize('M,N,with_bias', RS_SHAPES)
 def test_gemm_rs_matches_fp64(lib, M, N, with_bias, dtype):
   g = torch.Generator().manual_seed(M + N)
   dt = torch.bfloat16 if dtype == BF16 else torch.float16
@@ -50,6 +56,7 @@ def test_gemm_rs_matches_fp64(lib, M, N, with_bias, dtype):
   eps = 2.0 ** -8 if dtype == BF16 else 2.0 ** -11
   assert rel_err(o.float(), ref) < (3e-3 if dtype == BF16 else 4e-4)
   assert bool(((o.double() - ref).abs() <= 1.01 * eps * ref.abs() + 1e-5).all())
+  PU.assert_elementwise(o, ref, PU.linear_bound(A, B, bias, None, 0, ref, ref, dt), 'C')
 
 
 def test_gemm_rs_equals_the_tiled_kernel(lib):
@@ -100,6 +107,11 @@ def test_gemm_rs_gelu_grad_epilogue_matches_fp64(lib, M, N, dtype):
   eps = 2.0 ** -8 if dtype == BF16 else 2.0 ** -11
   assert rel_err(o.float(), ref) < (3e-3 if dtype == BF16 else 4e-4)
   assert bool(((o.double() - ref).abs() <= 1.01 * eps * ref.abs() + 2e-5).all())
+  # (A . B) o gelu'(pre): the sum's error is scaled by |gelu'(pre)| (<= 1.13), and the factor itself carries 4 x the host's fp32 evaluation error
+  gg = _gelu_grad64(pre.double())
+  gerr = 4.0 * float((_gelu_grad64(pre.float()).double() - gg).abs().max())
+  ap = PU.abs_product(A, B)
+  PU.assert_elementwise(o, ref, PU.elementwise_bound(ref, ap * gg.abs(), 384, dt) + (1 + PU.unit_roundoff(dt)) * gerr * ap, 'dh')
   rc6, o6 = _run(lib, A.cuda(), B.cuda(), None, dtype, 6, pre=pre.cuda())   # the tiled kernel's epilogue
   if rc6 == 0:
     diff = (out != o6).float().mean().item()

@@ -8,6 +8,7 @@ import math
 import pytest
 import torch
 
+import parity_util as PU
 from util import O, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -40,14 +41,15 @@ def _case(M, dtype, seed=0):
 def _run(lib, M, dtype, t):
   na, a, w_in, w_out, b_in, b_out = [x.cuda() for x in t]
   dt = na.dtype
-  y = torch.full((M, 384), float('nan'), device='cuda', dtype=dt)
-  h = torch.full((M, 1536), float('nan'), device='cuda', dtype=dt)
-  hpre = torch.full((M, 1536), float('nan'), device='cuda', dtype=dt)
-  ws = torch.empty(8 << 20, dtype=torch.uint8, device='cuda')
+  y = PU.guarded(M, 384, dt, name='y')
+  h = PU.guarded(M, 1536, dt, name='h')
+  hpre = PU.guarded(M, 1536, dt, name='hpre')
+  ws = PU.poisoned_ws(4 << 20)   # include/spa3d.h: ws >= 4 MiB
   rc = lib.spa3d_op_mlp_fused(na.data_ptr(), a.data_ptr(), w_in.data_ptr(), b_in.data_ptr(), w_out.data_ptr(), b_out.data_ptr(),
                               y.data_ptr(), h.data_ptr(), hpre.data_ptr(), M, 384, 1536, dtype, ws.data_ptr(), ws.numel(), _s())
   assert rc == 0
   torch.cuda.synchronize()
+  PU.check_guards()
   return y.cpu(), h.cpu(), hpre.cpu()
 
 
@@ -70,6 +72,12 @@ def test_mlp_fused_matches_fp64(lib, M, dtype):
   yr = a.double() + h.double() @ w_out.double() + b_out.double()
   assert rel_err(y.float(), yr) < tol
   assert bool(((y.double() - yr).abs() <= 1.01 * eps * yr.abs() + 2e-5).all())
+  # element-wise gates (tests/parity_util.py): hpre is one rounding of the fp32 sum; h passes that sum through tanh-gelu; y is one rounding of an fp32 sum
+  # over the STORED h, so its bound is the plain GEMM bound with h as the left operand (tighter than carrying h's bound through |W_out|)
+  dt = na.dtype
+  PU.assert_elementwise(hpre, pre, PU.linear_bound(na, w_in, b_in, None, 0, pre, pre, dt), 'hpre')
+  PU.assert_elementwise(h, gl, PU.linear_bound(na, w_in, b_in, None, 1, gl, pre, dt), 'h')
+  PU.assert_elementwise(y, yr, PU.linear_bound(h, w_out, b_out, a, 0, yr, yr, dt), 'y')
 
 
 def test_mlp_fused_equals_the_two_gemms(lib):

@@ -1,0 +1,446 @@
+"""The gates of tests/parity_util.py, tested on the host: a correct result computed here (the fp64 value rounded once to 16 bits) passes every new gate, and
+each injected fault passes the assertion the kernel tests made before -- restated here -- and fails the new one.  This file is the evidence that the gates
+discriminate and that the reference alone stays inside them."""
+import math
+
+import pytest
+import torch
+
+import parity_util as PU
+from util import max_abs, rel_err
+
+
+def _old_nt_gate(C, ref):
+  """tests/test_gpu_ops.py::test_linear_tiled_nt before the element-wise gate"""
+  return (not torch.isnan(C.float()).any()) and rel_err(C.float(), ref) < 4e-3 and max_abs(C.float(), ref) < 0.05 * float(ref.abs().max())
+
+
+@pytest.fixture(scope='module')
+def gemm_case():
+  """(4133, 2304, 384), no bias: the shape of the issue's arithmetic, with a ragged last M-tile for every tile height in the tree"""
+  M, N, K = 4133, 2304, 384
+  g = torch.Generator().manual_seed(11)
+  A = torch.randn(M, K, generator=g).bfloat16()
+  B = (torch.randn(K, N, generator=g) / math.sqrt(K)).bfloat16()
+  ref = A.double() @ B.double()
+  return A, B, ref, PU.linear_bound(A, B, None, None, 0, ref, ref, torch.bfloat16)
+
+
+# ------------------------------------------------------------------------------------------------ element-wise gate
+def test_correctly_rounded_gemm_passes_the_elementwise_gate(gemm_case):
+  A, B, ref, bound = gemm_case
+  C = ref.bfloat16()
+  n, _, ratio = PU.elementwise_report(C, ref, bound)
+  assert n == 0 and ratio < 1.0
+  PU.assert_elementwise(C, ref, bound)
+  # an fp32 accumulation in another order, rounded once: still inside, and the bound is within about 3 x one output rounding where it matters
+  C32 = (A.float() @ B.float()).bfloat16()
+  PU.assert_elementwise(C32, ref, bound)
+  big = ref.abs() > 1.0
+  assert float((bound[big] / (PU.U_BF16 * ref.abs()[big])).max()) < 3.0
+
+
+@pytest.mark.parametrize('dt', [torch.bfloat16, torch.float16, torch.float32])
+@pytest.mark.parametrize('act,res', [(0, False), (1, False), (0, True), (1, True)])
+def test_correctly_rounded_linear_with_epilogues_passes(dt, act, res):
+  M, N, K = 130, 600, 1280
+  g = torch.Generator().manual_seed(1)
+  A = torch.randn(M, K, generator=g).to(dt)
+  B = (torch.randn(K, N, generator=g) / math.sqrt(K)).to(dt)
+  bias = torch.randn(N, generator=g)
+  R = torch.randn(M, N, generator=g).to(dt) if res else None
+  pre = A.double() @ B.double() + bias.double()
+  ref = PU.gelu_tanh(pre) if act else pre
+  if res:
+    ref = ref + R.double()
+  bound = PU.linear_bound(A, B, bias, R, act, ref, pre, dt)
+  PU.assert_elementwise(ref.to(dt), ref, bound)
+  # the same in fp32 arithmetic end to end, as a kernel computes it
+  c32 = A.float() @ B.float() + bias
+  c32 = PU.gelu_tanh(c32) if act else c32
+  PU.assert_elementwise((c32 + R.float() if res else c32).to(dt), ref, bound)
+
+
+def test_one_dropped_k_in_one_fragment_passes_the_old_gate_and_fails_the_new(gemm_case):
+  A, B, ref, bound = gemm_case
+  M, N = ref.shape
+  C = ref.clone()
+  r0, c0, k = 4128, 1024, 200   # a 16 x 16 fragment inside the ragged last tile (rows 4096 .. 4132), one contraction step lost
+  C[r0:r0 + 5, c0:c0 + 16] -= A[r0:r0 + 5, k:k + 1].double() * B[k:k + 1, c0:c0 + 16].double()
+  C = C.bfloat16()
+  assert _old_nt_gate(C, ref)
+  n, idx, ratio = PU.elementwise_report(C, ref, bound)
+  assert n > 0 and ratio > 1.0 and r0 <= idx[0] < r0 + 5 and c0 <= idx[1] < c0 + 16
+  with pytest.raises(AssertionError, match='over the bound'):
+    PU.assert_elementwise(C, ref, bound)
+
+
+def test_a_nan_fails_the_elementwise_gate(gemm_case):
+  _, _, ref, bound = gemm_case
+  C = ref.bfloat16()
+  C[7, 9] = float('nan')
+  assert PU.elementwise_report(C, ref, bound)[:2] == (1, (7, 9))
+
+
+def test_row_errs():
+  r = torch.arange(1.0, 13.0, dtype=torch.float64).view(3, 4)
+  g = r.clone()
+  g[1] *= 1.5
+  e = PU.row_errs(g, r, dim=1)
+  assert e.shape == (3,) and float(e[0]) == 0.0 and abs(float(e[1]) - 0.5) < 1e-12 and float(e[2]) == 0.0
+
+
+# ------------------------------------------------------------------------------------------------ exact-integer lane
+@pytest.mark.parametrize('K,N', [(64, 64), (384, 2304), (33, 50), (70, 130), (12352, 128), (192, 600)])
+def test_sparse_sign_matrix_covers_every_k_in_every_group_of_64_columns(K, N):
+  W, idx, sgn = PU.sparse_sign_matrix(K, N)
+  r = (K + 63) // 64
+  assert W.shape == (K, N) and idx.shape == (r, N)
+  assert torch.equal((W != 0).sum(0), torch.full((N,), r)) and torch.equal(W.abs().sum(0), torch.full((N,), float(r)))   # exactly r entries of +-1 per column
+  assert torch.equal(W[idx, torch.arange(N).expand(r, N)], sgn)
+  for c0 in range(0, N - 63, 64):
+    assert bool(((W[:, c0:c0 + 64] != 0).sum(1) >= 1).all()), c0
+  assert 0.2 < float((sgn > 0).float().mean()) < 0.8   # both signs occur
+
+
+@pytest.mark.parametrize('M,N,K,res,bias', [(133, 256, 384, True, True), (77, 50, 33, True, True), (5, 128, 12352, False, True), (300, 192, 1536, False, False)])
+def test_int_lane_nt_reference_is_the_matmul_and_is_exact_in_16_bits(M, N, K, res, bias):
+  A, W, b, R, ref = PU.int_lane_nt(M, N, K, seed=1, bias=bias, res=res)
+  full = A.double() @ W.double() + (b.double() if bias else 0.0) + (R.double() if res else 0.0)
+  assert torch.equal(full, ref.double())
+  for dt in (torch.bfloat16, torch.float16):
+    for t in (A, W, ref) + ((b,) if bias else ()) + ((R,) if res else ()):
+      assert torch.equal(t.to(dt).float(), t)   # operands and result are exact in both 16-bit types
+  # the worst partial sum of any order stays exact: sum of |terms| <= 256
+  assert float((A.abs() @ W.abs()).max()) + (3 if bias else 0) + (5 if res else 0) <= 256
+
+
+def test_int_lane_tn_reference_is_the_matmul():
+  for M, N, K in [(1000, 96, 64), (257, 50, 33), (100003, 8, 128)]:
+    A, dC, rW, rb = PU.int_lane_tn(M, N, K, seed=2)
+    assert torch.equal(A.double().t() @ dC.double(), rW.double()) and torch.equal(dC.double().sum(0), rb.double())
+    r = (K + 63) // 64
+    assert torch.equal((A != 0).sum(1), torch.full((M,), r))
+    assert float(A.abs().t().double().matmul(dC.abs().double()).max()) < 2 ** 24
+
+
+def test_two_swapped_k_slices_pass_the_old_gate_and_fail_the_integer_lane(gemm_case):
+  """a kernel that feeds k-slices k and k + 1 of A to each other's W rows, in the 5 live rows x 64 columns one wave owns in the ragged last tile (the
+  sparse operand touches every k once per aligned group of 64 columns; a single 16-column fragment touches a quarter of them).  On random operands the
+  elements move by (a_k - a_k+1)(w_k+1 - w_k), about 0.1 -- nothing to a relative Frobenius norm, and for some k also under the NT tests' 0.05 max|ref|;
+  on the integer operands EVERY k changes some integer."""
+  A, B, ref, _ = gemm_case
+  r0, c0, R, Cw = 4128, 512, 5, 64
+
+  def delta(A, B, k):
+    a0, a1 = A[r0:r0 + R, k:k + 1].double(), A[r0:r0 + R, k + 1:k + 2].double()
+    b0, b1 = B[k:k + 1, c0:c0 + Cw].double(), B[k + 1:k + 2, c0:c0 + Cw].double()
+    return (a0 * b1 + a1 * b0) - (a0 * b0 + a1 * b1)
+
+  def faulty(A, B, C, k):
+    C = C.clone()
+    C[r0:r0 + R, c0:c0 + Cw] += delta(A, B, k)
+    return C
+  # the dX tests and the fp16 twins asserted the relative Frobenius error alone (tests/test_gpu_ops.py::test_linear_bwd_tiled: < 4e-3): blind to every k
+  for k in (0, 128, 382):
+    assert rel_err(faulty(A, B, ref, k).bfloat16().float(), ref) < 4e-3
+  # the NT tests also had max_abs < 0.05 max|ref|: it sees the larger of these swaps and is blind to the rest
+  limit = 0.05 * float(ref.abs().max())
+  ks = [k for k in range(0, 383) if float(delta(A, B, k).abs().max()) < 0.8 * limit]
+  assert ks
+  assert _old_nt_gate(faulty(A, B, ref, ks[0]).bfloat16(), ref)
+  Ai, Wi, _, _, refi = PU.int_lane_nt(4133, 2304, 384, seed=3, bias=False, res=False)
+  assert torch.equal((Ai.double() @ Wi.double()).bfloat16().float(), refi)
+  for k in range(0, 383):
+    d = delta(Ai, Wi, k)
+    assert bool((d != 0).any()), k   # an integer changes, so torch.equal fails
+  bad = faulty(Ai, Wi, refi.double(), ks[0]).bfloat16().float()
+  assert not torch.equal(bad, refi) and int((bad != refi).sum()) == int((bad != refi)[r0:r0 + R, c0:c0 + Cw].sum())
+
+
+# ------------------------------------------------------------------------------------------------ guard bands, poisoned workspace
+@pytest.mark.parametrize('dt', [torch.bfloat16, torch.float16, torch.float32])
+def test_guarded_layout_and_canary(dt):
+  v = PU.guarded(37, 24, dt, ld=40, device='cpu')
+  assert v.shape == (37, 24) and v.stride() == (40, 1) and v.data_ptr() % 16 == 0 and bool(torch.isnan(v).all())
+  es = v.element_size()
+  raw = PU._guards[-1][3]
+  assert raw.numel() * 2 == PU.GUARD_FRONT_BYTES + (37 + PU.GUARD_TAIL_ROWS) * 40 * es
+  assert v.data_ptr() - raw.data_ptr() == PU.GUARD_FRONT_BYTES >= 4096
+  assert bool(torch.isnan(raw.view(dt)[:8]).all())   # the canary is a NaN in this type
+  v.copy_(torch.randn(37, 24).to(dt))                # a kernel writing every element of its view, and nothing else
+  PU.check_guards()
+  assert PU._guards == []
+
+
+@pytest.mark.parametrize('where', ['row past M', 'row gap', 'before', 'far tail'])
+def test_one_element_outside_the_view_passes_the_old_gate_and_fails_the_guards(where, gemm_case):
+  _, _, ref, _ = gemm_case
+  M, N = 100, 256
+  ref = ref[:M, :N]
+  ld = N + 8 if where == 'row gap' else N
+  v = PU.guarded(M, N, torch.bfloat16, ld=ld, device='cpu')
+  v.copy_(ref.bfloat16())
+  raw = PU._guards[-1][3].view(torch.bfloat16)
+  front = PU.GUARD_FRONT_BYTES // 2
+  at = {'row past M': front + M * ld + 5, 'row gap': front + 3 * ld + N, 'before': front - 1, 'far tail': front + (M + PU.GUARD_TAIL_ROWS) * ld - 1}[where]
+  raw[at] = 0.25   # one stray store
+  assert _old_nt_gate(v, ref)   # the view is untouched: nothing the tests asserted before sees it
+  with pytest.raises(AssertionError, match='stray stores'):
+    PU.check_guards()
+
+
+def test_a_failed_test_leaves_no_guards_behind(monkeypatch):
+  monkeypatch.setenv('PYTEST_CURRENT_TEST', 'some earlier test')
+  PU.guarded(4, 8, torch.float32, device='cpu')
+  PU._guards[-1][3][0] = 0   # damaged, and never checked: that test failed first
+  monkeypatch.setenv('PYTEST_CURRENT_TEST', 'this test')
+  PU.guarded(4, 8, torch.float32, device='cpu')
+  PU.check_guards()
+
+
+def test_poisoned_workspace_is_nan_in_every_type():
+  ws = PU.poisoned_ws(4096, device='cpu')
+  assert ws.numel() == 4096 and bool((ws == 0xFF).all())
+  for dt in (torch.float32, torch.bfloat16, torch.float16):
+    assert bool(torch.isnan(ws.view(dt)).all())
+
+
+# ------------------------------------------------------------------------------------------------ LayerNorm
+@pytest.mark.parametrize('dt', [torch.bfloat16, torch.float16, torch.float32])
+@pytest.mark.parametrize('rows,d', [(333, 384), (1, 48), (257, 2048), (3, 100)])
+def test_correctly_rounded_layernorm_passes_its_gates(dt, rows, d):
+  g = torch.Generator().manual_seed(3)
+  x = (torch.randn(rows, d, generator=g) * 2 + 0.5).to(dt)
+  scale = 1 + 0.1 * torch.randn(d, generator=g)
+  dy = torch.randn(rows, d, generator=g).to(dt)
+  y64, dx64, ds64 = PU.layernorm_restated(x, scale, dy, torch.float64)
+  y32, dx32, ds32 = PU.layernorm_restated(x, scale, dy, torch.float32)
+  PU.assert_elementwise(y64.to(dt), y64, PU.restated_bound(y64, y32, dt), 'y')
+  PU.assert_elementwise(dx64.to(dt), dx64, PU.restated_bound(dx64, dx32, dt), 'dx')
+  PU.assert_elementwise(ds64.float(), ds64, PU.restated_bound(ds64, ds32, torch.float32), 'dscale')
+  if dt != torch.float32 and rows > 1:   # one row of y off by 2 %: far inside the relative-Frobenius 1e-2 the test had, outside the element-wise gate
+    bad = y64.clone(); bad[rows // 2] *= 1.02
+    assert rel_err(bad.to(dt).float(), y64) < 1e-2 or rows < 5
+    assert PU.elementwise_report(bad.to(dt), y64, PU.restated_bound(y64, y32, dt))[0] > 0
+
+
+# ------------------------------------------------------------------------------------------------ fused attention forward: the row gate
+from util import Gates, O  # noqa: E402
+
+
+def _attn_ref(q, k, v, sq, sk, km, H, Dh):
+  """the fp64 oracle, as tests/test_gpu_ops.py::_attn_ref"""
+  nseq, Sq, _ = q.shape
+  Sk = k.shape[1]
+  qh = O.rms_norm(q.double().view(nseq, Sq, H, Dh), sq.double())
+  kh = O.rms_norm(k.double().view(nseq, Sk, H, Dh), sk.double())
+  mask = None if km is None else km[:, None, None, :].expand(nseq, H, Sq, Sk)
+  return O.dot_product_attention(qh, kh, v.double().view(nseq, Sk, H, Dh), mask).reshape(nseq, Sq, H * Dh)
+
+
+def _attn_case(nseq, Sq, Sk, H, masked, seed, dt=torch.bfloat16):
+  Dh, E = 96, H * 96
+  g = torch.Generator().manual_seed(seed)
+  q = torch.randn(nseq, Sq, E, generator=g).to(dt)
+  k = torch.randn(nseq, Sk, E, generator=g).to(dt)
+  v = torch.randn(nseq, Sk, E, generator=g).to(dt)
+  sq = 1 + 0.2 * torch.randn(Dh, generator=g)
+  sk = 1 + 0.2 * torch.randn(Dh, generator=g)
+  km = None
+  if masked:
+    km = (torch.rand(nseq, Sk, generator=g) < 0.8).float(); km[:, 0] = 1.0; km[0, 1:] = 0.0
+  return q, k, v, sq, sk, km
+
+
+def _row_gate_ok(got, emu, ref, H):
+  gt = Gates('host')
+  PU.attention_row_gate(gt, 'o', got, emu, ref, H, 96)
+  return gt.rows[0][4]
+
+
+@pytest.fixture(scope='module')
+def self_301():
+  q, k, v, sq, sk, km = _attn_case(3, 301, 301, 8, True, 21)
+  return q, k, v, sq, sk, km, _attn_ref(q, k, v, sq, sk, km, 8, 96), PU.emulate_attention(q, k, v, sq, sk, km, 8, 96)
+
+
+@pytest.mark.parametrize('dt', [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize('nseq,Sq,Sk,H,masked,chunk', [(3, 129, 129, 8, False, None), (5, 25, 25, 8, True, None), (2, 128, 300, 8, True, 128), (2, 37, 1000, 4, True, 128)])
+def test_attention_emulation_is_inside_its_own_gate_and_the_old_one(dt, nseq, Sq, Sk, H, masked, chunk):
+  q, k, v, sq, sk, km = _attn_case(nseq, Sq, Sk, H, masked, 4, dt)
+  if masked and chunk:
+    km[0, :] = 0.0   # every key masked: uniform attention over all keys, across the chunk merge
+  ref = _attn_ref(q, k, v, sq, sk, km, H, 96)
+  emu = PU.emulate_attention(q, k, v, sq, sk, km, H, 96, chunk)
+  assert rel_err(emu.float(), ref) < (2e-2 if dt == torch.bfloat16 else 3e-3)   # the limits the fused tests had
+  assert _row_gate_ok(emu, emu, ref, H)
+  # the single-chunk and the chunked contracts agree to within their roundings
+  other = PU.emulate_attention(q, k, v, sq, sk, km, H, 96, None if chunk else 128)
+  assert _row_gate_ok(other, emu, ref, H)
+
+
+def test_last_key_dropped_at_301_passes_the_old_gate_and_fails_the_row_gate(self_301):
+  q, k, v, sq, sk, km, ref, emu = self_301
+  km2 = torch.ones(3, 301) if km is None else km.clone()
+  km2[:, 300] = 0.0
+  km2[0, 0] = 1.0
+  bad = PU.emulate_attention(q, k, v, sq, sk, km2, 8, 96)   # a kernel that loses key 300
+  assert bool((km[1:, 300] == 1).any())                      # ... where it was visible
+  assert rel_err(bad.float(), ref) < 2e-2
+  assert not _row_gate_ok(bad, emu, ref, 8)
+
+
+def test_one_query_row_scaled_passes_the_old_gate_and_fails_the_row_gate(self_301):
+  q, k, v, sq, sk, km, ref, emu = self_301
+  bad = emu.clone().float()
+  bad[1, 200, 96 * 3:96 * 4] *= 1.5   # one (sequence, token, head) row 50 % wrong in (3, 301, 8)
+  assert rel_err(bad, ref) < 2e-2
+  assert not _row_gate_ok(bad.bfloat16(), emu, ref, 8)
+
+
+def test_first_key_of_the_second_chunk_dropped_passes_the_old_gate_and_fails_the_row_gate():
+  q, k, v, sq, sk, km = _attn_case(2, 128, 300, 8, False, 33)
+  ref = _attn_ref(q, k, v, sq, sk, None, 8, 96)
+  emu = PU.emulate_attention(q, k, v, sq, sk, None, 8, 96, 128)
+  km2 = torch.ones(2, 300); km2[:, 128] = 0.0
+  lost = PU.emulate_attention(q, k, v, sq, sk, km2, 8, 96, 128)
+  # lost in every head of every sequence, each row moves by about 1 / sqrt(Sk) = 5.8 % on these inputs, and the old 2 % limit does see that;
+  # lost by one workgroup -- one (sequence, head, chunk) -- it is 1.4 % of the tensor and passes
+  assert rel_err(lost.float(), ref) > 2e-2
+  bad = emu.clone()
+  bad[1, :, 96 * 5:96 * 6] = lost[1, :, 96 * 5:96 * 6]
+  assert rel_err(bad.float(), ref) < 2e-2
+  assert not _row_gate_ok(bad, emu, ref, 8)
+
+
+def test_probe_inputs_make_the_probed_key_dominant_and_its_loss_visible():
+  nseq, S, H = 3, 161, 8
+  ps = PU.probe_positions(S)
+  assert ps == [0, 1, 15, 16, 31, 32, 63, 64, 127, 128, 159, 160]
+  assert PU.probe_positions(300, cross=True) == [0, 1, 15, 16, 31, 32, 63, 64, 127, 128, 159, 160, 255, 256, 298, 299]
+  pos = [[ps[(s * H + h) % len(ps)] for h in range(H)] for s in range(nseq)]
+  q, k, v = PU.probe_inputs(nseq, S, S, H, 96, torch.bfloat16, pos, seed=5)
+  one = torch.ones(96)
+  ref = _attn_ref(q, k, v, one, one, None, H, 96)
+  emu = PU.emulate_attention(q, k, v, one, one, None, H, 96)
+  assert _row_gate_ok(emu, emu, ref, H)
+  qh = O.rms_norm(q.double().view(nseq, S, H, 96), one.double()); kh = O.rms_norm(k.double().view(nseq, S, H, 96), one.double())
+  p = torch.softmax(torch.einsum('nqhd,nkhd->nhqk', qh, kh) / math.sqrt(96), -1)
+  for s in range(nseq):
+    for h in range(H):
+      assert float(p[s, h, :, pos[s][h]].min()) > 0.9
+  km = torch.ones(nseq, S); km[1, pos[1][2]] = 0.0   # the probed key of one head lost
+  bad = PU.emulate_attention(q, k, v, one, one, km, H, 96)
+  e = PU.row_errs(bad.view(nseq, S, H, 96), ref.view(nseq, S, H, 96), -1)
+  assert float(e[1, :, 2].min()) > 0.5
+
+
+# ------------------------------------------------------------------------------------------------ fused attention backward: the gradient gates
+def _grads64(q, k, v, sq, sk, km, H, d_o):
+  nseq, Sq, _ = q.shape
+  Sk = k.shape[1]
+  qr, kr, vr = (t.double().requires_grad_(True) for t in (q, k, v))
+  sqr, skr = sq.double().requires_grad_(True), sk.double().requires_grad_(True)
+  qh = O.rms_norm(qr.view(nseq, Sq, H, 96), sqr); kh = O.rms_norm(kr.view(nseq, Sk, H, 96), skr)
+  mask = None if km is None else km[:, None, None, :].expand(nseq, H, Sq, Sk)
+  O.dot_product_attention(qh, kh, vr.view(nseq, Sk, H, 96), mask).reshape(nseq, Sq, H * 96).backward(d_o.double())
+  return qr.grad, kr.grad, vr.grad, sqr.grad, skr.grad
+
+
+def _grad_gates(got, emu, ref, H):
+  gt = Gates('host')
+  PU.attention_grad_gates(gt, got, emu, ref, H, 96)
+  return {r[0].split(':')[0]: r[4] for r in gt.rows}
+
+
+@pytest.fixture(scope='module')
+def bwd_151():
+  q, k, v, sq, sk, km = _attn_case(4, 151, 151, 8, True, 21)
+  d_o = torch.randn(4, 151, 8 * 96, generator=torch.Generator().manual_seed(2)).bfloat16()
+  return q, k, v, sq, sk, km, d_o, _grads64(q, k, v, sq, sk, km, 8, d_o), PU.emulate_attention_bwd(q, k, v, sq, sk, km, 8, 96, d_o)
+
+
+@pytest.mark.parametrize('dt', [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize('nseq,Sq,Sk,H,masked,chunk,fast', [(3, 129, 129, 8, False, None, True), (3, 129, 129, 8, False, None, False), (5, 25, 25, 8, True, None, False),
+                                                            (2, 100, 300, 4, True, 128, False)])
+def test_backward_emulation_is_inside_its_own_gates_and_the_old_one(dt, nseq, Sq, Sk, H, masked, chunk, fast):
+  q, k, v, sq, sk, km = _attn_case(nseq, Sq, Sk, H, masked, 4, dt)
+  d_o = torch.randn(nseq, Sq, H * 96, generator=torch.Generator().manual_seed(9)).to(dt)
+  ref = _grads64(q, k, v, sq, sk, km, H, d_o)
+  emu = PU.emulate_attention_bwd(q, k, v, sq, sk, km, H, 96, d_o, chunk, fast)
+  assert max(rel_err(a.float(), b) for a, b in zip(emu, ref)) < (3e-2 if dt == torch.bfloat16 else 5e-3)   # the limits the fused tests had
+  assert all(_grad_gates(emu, emu, ref, H).values())
+  if masked:   # a sequence with one visible key: dq and dk are exact zeros there, in the oracle and in the emulation
+    assert float(ref[0][0].abs().max()) == 0.0 and float(emu[0][0].float().abs().max()) == 0.0
+  if not masked:   # the two score arithmetics of the four-image kernel agree within their roundings
+    other = PU.emulate_attention_bwd(q, k, v, sq, sk, km, H, 96, d_o, chunk, not fast)
+    assert all(_grad_gates(other, emu, ref, H).values())
+
+
+def test_a_key_lost_in_the_backward_passes_the_old_gate_and_fails_the_row_gates(bwd_151):
+  """one workgroup -- one (sequence, head) -- computes its gradients without key 150: dk and dv of that key are zero rows, dq of every query moves"""
+  q, k, v, sq, sk, km, d_o, ref, emu = bwd_151
+  sq_ = next(i for i in (1, 2, 3) if float(km[i, 150]) == 1.0)   # a sequence that sees its last key
+  km2 = km.clone(); km2[:, 150] = 0.0
+  lost = PU.emulate_attention_bwd(q, k, v, sq, sk, km2, 8, 96, d_o)
+  bad = [t.clone() for t in emu]
+  for i in range(3):
+    bad[i][sq_, :, 96 * 5:96 * 6] = lost[i][sq_, :, 96 * 5:96 * 6]
+  bad[2][sq_, 150, 96 * 5:96 * 6] = 0   # and dv of the lost key is not written
+  assert max(rel_err(a.float(), b) for a, b in zip(bad, ref)) < 3e-2
+  ok = _grad_gates(bad, emu, ref, 8)
+  assert not ok['dq'] and not ok['dk'] and not ok['dv']
+
+
+def test_one_gradient_row_scaled_passes_the_old_gate_and_fails_the_row_gate(bwd_151):
+  q, k, v, sq, sk, km, d_o, ref, emu = bwd_151
+  t = next(i for i in range(60, 151) if float(km[1, i]) == 1.0)   # a visible key: a masked key's dk row is zero
+  for i, name in enumerate(('dq', 'dk', 'dv')):
+    bad = [t_.clone() for t_ in emu]
+    bad[i][1, t, 96 * 3:96 * 4] = (bad[i][1, t, 96 * 3:96 * 4].float() * 1.5).bfloat16()
+    assert max(rel_err(a.float(), b) for a, b in zip(bad, ref)) < 3e-2
+    ok = _grad_gates(bad, emu, ref, 8)
+    assert not ok[name] and all(v_ for n, v_ in ok.items() if n != name)
+
+
+def test_scale_gradient_missing_one_sequence_passes_the_old_gate_and_fails_the_vector_gate(bwd_151):
+  """dsq without the contribution of two query rows of one (sequence, head) out of 4832: the whole-vector error moves from 0.4 % to about 2 %, under the
+  old 3 %.  (A whole lost (sequence, head) of the 32 moves the vector by about 1 / sqrt(32) = 18 % -- the old limit does see that.)"""
+  q, k, v, sq, sk, km, d_o, ref, emu = bwd_151
+  part = PU.emulate_attention_bwd(q[3:4, 60:62, :96].contiguous(), k[3:4, :, :96].contiguous(), v[3:4, :, :96].contiguous(), sq, sk, km[3:4], 1, 96, d_o[3:4, 60:62, :96].contiguous())
+  bad = [t.clone() for t in emu]
+  bad[3] = emu[3] - part[3]
+  assert rel_err(bad[3], ref[3]) < 3e-2
+  assert not _grad_gates(bad, emu, ref, 8)['dsq']
+
+
+def test_zero_reference_rows_are_judged_against_a_typical_row():
+  r = torch.zeros(4, 8, dtype=torch.float64); r[1:] = 1.0
+  g = r.clone(); g[0, 0] = 1e-6
+  e = PU.row_errs_floored(g, r, PU.grad_row_floor(torch.bfloat16, 96, 301))
+  assert abs(PU.grad_row_floor(torch.bfloat16, 96, 301) - 0.0147) < 1e-3 and abs(PU.grad_row_floor(torch.float16, 96, 301) - 0.117) < 1e-2
+  assert 0 < float(e[0]) < 1e-3 and float(PU.row_errs(g, r)[0]) > 1e20
+
+
+@pytest.mark.parametrize('nseq,Sq,Sk,H,Dh,masked', [(5, 25, 25, 8, 96, True), (2, 128, 200, 8, 96, False), (4, 9, 9, 2, 16, True)])
+def test_generic_composition_emulation_is_inside_its_own_gates_and_the_old_one(nseq, Sq, Sk, H, Dh, masked):
+  E = H * Dh
+  g = torch.Generator().manual_seed(4)
+  q, k, v, d_o = (torch.randn(nseq, S, E, generator=g).bfloat16() for S in (Sq, Sk, Sk, Sq))
+  sq = 1 + 0.2 * torch.randn(Dh, generator=g); sk = 1 + 0.2 * torch.randn(Dh, generator=g)
+  km = None
+  if masked:
+    km = (torch.rand(nseq, Sk, generator=g) < 0.8).float(); km[:, 0] = 1.0; km[0, 1:] = 0.0
+  qr, kr, vr = (t.double().requires_grad_(True) for t in (q, k, v))
+  sqr, skr = sq.double().requires_grad_(True), sk.double().requires_grad_(True)
+  mask = None if km is None else km[:, None, None, :].expand(nseq, H, Sq, Sk)
+  ref = O.dot_product_attention(O.rms_norm(qr.view(nseq, Sq, H, Dh), sqr), O.rms_norm(kr.view(nseq, Sk, H, Dh), skr), vr.view(nseq, Sk, H, Dh), mask).reshape(nseq, Sq, E)
+  ref.backward(d_o.double())
+  refs = (qr.grad, kr.grad, vr.grad, sqr.grad, skr.grad)
+  emu = PU.emulate_attention_generic(q, k, v, sq, sk, km, H, Dh, d_o)
+  assert rel_err(emu[0].float(), ref.detach()) < 2e-2 and max(rel_err(a.float(), b) for a, b in zip(emu[1:], refs)) < 3e-2
+  gt = Gates('host')
+  PU.attention_row_gate(gt, 'o', emu[0], emu[0], ref.detach(), H, Dh)
+  PU.attention_grad_gates(gt, emu[1:], emu[1:], refs, H, Dh)
+  gt.check()
