@@ -9,8 +9,8 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libspa3d_hip.so')
-SOURCES = ['kernels.hip', 'gemm_generic.hip', 'gemm_fast.hip', 'gemm_tnb.hip', 'gemm_ntb.hip', 'gemm_rs.hip', 'mlp_fused.hip', 'attention.hip', 'attention_fused.hip', 'qkv_attn.hip', 'ops.hip', 'samplers.hip', 'tapvid3d.hip', 'render.hip', 'batch_build.hip', 'model.hip']
-F16_SOURCES = ['kernels.hip', 'gemm_generic.hip', 'gemm_fast.hip', 'gemm_tnb.hip', 'gemm_ntb.hip', 'gemm_rs.hip', 'mlp_fused.hip', 'attention.hip', 'attention_fused.hip', 'qkv_attn.hip', 'ops.hip', 'model.hip']
+SOURCES = ['layernorm.hip', 'embed.hip', 'rows.hip', 'attn_q1.hip', 'loss.hip', 'gemm_generic.hip', 'gemm_fast.hip', 'gemm_tnb.hip', 'gemm_ntb.hip', 'gemm_rs.hip', 'mlp_fused.hip', 'attention.hip', 'attention_fused.hip', 'qkv_attn.hip', 'ops.hip', 'samplers.hip', 'tapvid3d.hip', 'render.hip', 'batch_build.hip', 'model.hip']
+F16_SOURCES = ['layernorm.hip', 'embed.hip', 'rows.hip', 'attn_q1.hip', 'loss.hip', 'gemm_generic.hip', 'gemm_fast.hip', 'gemm_tnb.hip', 'gemm_ntb.hip', 'gemm_rs.hip', 'mlp_fused.hip', 'attention.hip', 'attention_fused.hip', 'qkv_attn.hip', 'ops.hip', 'model.hip']
 HEADERS = [os.path.join(CSRC, h) for h in ('common.hpp', 'gemm_plan.hpp', 'tn_args.hpp', 'ablate.inc', 'attn_common.hpp', 'score_row.hpp', 'tapvid3d_row.hpp', 'render_px.hpp',
                                             'build_row.hpp')] + [os.path.join(HERE, '..', 'include', 'spa3d.h')]
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off', '-Wall', '-Wno-unused-function', '-Wno-inline-asm',
@@ -62,6 +62,10 @@ def build(force: bool = False, verbose: bool = True) -> str:
   with ThreadPoolExecutor(max_workers=6) as ex:
     list(ex.map(cc, jobs))
   objs = [os.path.join(objdir, o) for _, o, _ in units]
+  # an object of a source that no longer exists (a build of an earlier commit) must not reach whoever links build/*.o
+  for f in os.listdir(objdir):
+    if f.endswith('.o') and os.path.join(objdir, f) not in objs:
+      os.remove(os.path.join(objdir, f))
   if force or jobs or _stale(LIB, objs):
     cmd = [hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', LIB] + objs
     if verbose:

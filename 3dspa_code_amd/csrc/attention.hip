@@ -1,6 +1,6 @@
 // attention.hip -- attention core of ImprovedMHDPAttention (attention.py:166-175): per-head RMSNorm of q,k,
 // q/sqrt(Dh), key mask with finfo.min fill, softmax, PV -- forward and backward.
-// impl 1 ("generic"): composition of the strided batched MFMA GEMM with row-wise kernels; any Sq/Sk/Dh<=128,
+// impl 1 ("generic"): composition of the strided batched MFMA GEMM with the row-wise kernels below (RMSNorm, softmax); any Sq/Sk/Dh<=128,
 // both dtypes; the F32 parity path.  impl 2: fused LDS-resident kernels (attention_fused.hip) for bf16.
 #include <algorithm>
 #include <cmath>
@@ -19,6 +19,148 @@ bool attn_fused_bwd_bf16(spa3d_ctx* c, const bf16_t* q, const bf16_t* k, const b
 bool xattn_varlen_fwd_bf16(spa3d_ctx* c, const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq,
                            const float* sk, int64_t nseq, int Sq, int Skmax, int H, int Dh, bf16_t* o, float* lse, const int32_t* koff,
                            int64_t total_keys);
+
+// ---------------------------------------------------------------------------------------------
+// per-head RMSNorm over Dh (flax nn.RMSNorm eps 1e-6) attention.py:166-167.  one wave per (row, head)
+// ---------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void rms_heads_fwd_kernel(const T* __restrict__ x, int64_t ldx, const float* __restrict__ scale,
+                                                            T* __restrict__ y, int64_t ldy, int64_t rows, int H, int Dh) {
+  const int lane = threadIdx.x & 63;
+  int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t n = rows * H, stride = (int64_t)gridDim.x * 4;
+  for (; item < n; item += stride) {
+    int64_t row = item / H; int h = (int)(item - row * H);
+    const T* xr = x + row * ldx + h * Dh;
+    float v0 = lane < Dh ? ld(xr + lane) : 0.f;
+    float v1 = lane + 64 < Dh ? ld(xr + lane + 64) : 0.f;
+    float ms = wave_sum(v0 * v0 + v1 * v1) / Dh;
+    float r = rsqrtf(ms + 1e-6f);
+    T* yr = y + row * ldy + h * Dh;
+    if (lane < Dh) st(yr + lane, v0 * r * scale[lane]);
+    if (lane + 64 < Dh) st(yr + lane + 64, v1 * r * scale[lane + 64]);
+  }
+}
+template <typename T>
+void k_rmsnorm_heads(spa3d_ctx* c, const T* x, int64_t ldx, const float* scale, T* y, int64_t ldy, int64_t rows, int H, int Dh) {
+  if (c->dry || rows == 0) return;
+  unsigned g = (unsigned)std::min<int64_t>(cdiv(rows * H, 4), 65536);
+  rms_heads_fwd_kernel<T><<<g, 256, 0, c->stream>>>(x, ldx, scale, y, ldy, rows, H, Dh);
+  SPA_LAUNCH_CHECK(c);
+}
+// dx = r*(g - xhat*mean(g*xhat)), g=dy*scale ; dscale += sum dy*xhat
+template <typename T>
+__global__ __launch_bounds__(256) void rms_heads_bwd_kernel(const T* __restrict__ x, int64_t ldx, const float* __restrict__ scale,
+                                                            const T* __restrict__ dy, int64_t lddy, T* __restrict__ dx, int64_t lddx,
+                                                            float* __restrict__ dscale, int64_t rows, int H, int Dh, const DetCfg* det) {
+  __shared__ float red[4][128];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  float a0 = 0.f, a1 = 0.f;
+  int64_t item = (int64_t)blockIdx.x * 4 + w;
+  const int64_t n = rows * H, stride = (int64_t)gridDim.x * 4;
+  const float s0 = lane < Dh ? scale[lane] : 0.f, s1 = lane + 64 < Dh ? scale[lane + 64] : 0.f;
+  for (; item < n; item += stride) {
+    int64_t row = item / H; int h = (int)(item - row * H);
+    const T* xr = x + row * ldx + h * Dh;
+    const T* dyr = dy + row * lddy + h * Dh;
+    float v0 = lane < Dh ? ld(xr + lane) : 0.f, v1 = lane + 64 < Dh ? ld(xr + lane + 64) : 0.f;
+    float d0 = lane < Dh ? ld(dyr + lane) : 0.f, d1 = lane + 64 < Dh ? ld(dyr + lane + 64) : 0.f;
+    float r = rsqrtf(wave_sum(v0 * v0 + v1 * v1) / Dh + 1e-6f);
+    float xh0 = v0 * r, xh1 = v1 * r;
+    float g0 = d0 * s0, g1 = d1 * s1;
+    float mg = wave_sum(g0 * xh0 + g1 * xh1) / Dh;
+    a0 += d0 * xh0; a1 += d1 * xh1;
+    T* dxr = dx + row * lddx + h * Dh;
+    if (lane < Dh) st(dxr + lane, r * (g0 - xh0 * mg));
+    if (lane + 64 < Dh) st(dxr + lane + 64, r * (g1 - xh1 * mg));
+  }
+  red[w][lane] = a0; red[w][lane + 64] = a1;
+  __syncthreads();
+  if (w == 0) {
+    if (lane < Dh) grad_add(det_read(det), dscale + lane, red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane]);
+    if (lane + 64 < Dh) grad_add(det_read(det), dscale + lane + 64, red[0][lane + 64] + red[1][lane + 64] + red[2][lane + 64] + red[3][lane + 64]);
+  }
+}
+template <typename T>
+void k_rmsnorm_heads_bwd(spa3d_ctx* c, const T* x, int64_t ldx, const float* scale, const T* dy, int64_t lddy, T* dx, int64_t lddx,
+                         float* dscale, int64_t rows, int H, int Dh) {
+  if (c->dry || rows == 0) return;
+  unsigned g = (unsigned)std::min<int64_t>(cdiv(rows * H, 4), 2048);
+  rms_heads_bwd_kernel<T><<<g, 256, 0, c->stream>>>(x, ldx, scale, dy, lddy, dx, lddx, dscale, rows, H, Dh, c->det);
+  SPA_LAUNCH_CHECK(c);
+}
+
+// ---------------------------------------------------------------------------------------------
+// softmax over keys with key mask: where(mask, logit, finfo.min) -> softmax (flax dot_product_attention)
+// s: [nseq][H][Sq][Sk] in place.  one wave per row.
+// ---------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void softmax_kernel(T* __restrict__ s, const float* __restrict__ km, int64_t nseq, int H, int Sq, int Sk) {
+  const int lane = threadIdx.x & 63;
+  int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t nrows = nseq * H * Sq, stride = (int64_t)gridDim.x * 4;
+  for (; row < nrows; row += stride) {
+    int64_t seq = row / ((int64_t)H * Sq);
+    T* sr = s + row * Sk;
+    const float* kmr = km ? km + seq * Sk : nullptr;
+    float m = -3.4028234663852886e38f;
+    for (int k = lane; k < Sk; k += 64) {
+      float v = ld(sr + k);
+      if (kmr && kmr[k] == 0.f) v = -3.4028234663852886e38f;
+      m = fmaxf(m, v);
+    }
+    m = wave_max(m);
+    float sum = 0.f;
+    for (int k = lane; k < Sk; k += 64) {
+      float v = ld(sr + k);
+      if (kmr && kmr[k] == 0.f) v = -3.4028234663852886e38f;
+      sum += expf(v - m);
+    }
+    sum = wave_sum(sum);
+    float inv = 1.f / sum;
+    for (int k = lane; k < Sk; k += 64) {
+      float v = ld(sr + k);
+      if (kmr && kmr[k] == 0.f) v = -3.4028234663852886e38f;
+      st(sr + k, expf(v - m) * inv);
+    }
+  }
+}
+template <typename T>
+void k_softmax(spa3d_ctx* c, T* s, const float* keymask, int64_t nseq, int H, int Sq, int Sk) {
+  if (c->dry || nseq == 0) return;
+  unsigned g = (unsigned)std::min<int64_t>(cdiv(nseq * H * Sq, 4), 65536);
+  softmax_kernel<T><<<g, 256, 0, c->stream>>>(s, keymask, nseq, H, Sq, Sk);
+  SPA_LAUNCH_CHECK(c);
+}
+// dS = P o (dP - rowsum(dP o P)), in place on dp; masked keys get exactly 0: where(mask, logit, min) passes them no gradient
+// (this matters only for fully masked rows, where P is uniform instead of 0)
+template <typename T>
+__global__ __launch_bounds__(256) void softmax_bwd_kernel(const T* __restrict__ p, T* __restrict__ dp, int64_t rows, int Sk,
+                                                          const float* __restrict__ km, int64_t rows_per_seq) {
+  const int lane = threadIdx.x & 63;
+  int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  for (; row < rows; row += stride) {
+    const T* pr = p + row * Sk; T* dr = dp + row * Sk;
+    float s = 0.f;
+    for (int k = lane; k < Sk; k += 64) s += ld(pr + k) * ld(dr + k);
+    s = wave_sum(s);
+    const float* kmr = km ? km + (row / rows_per_seq) * Sk : nullptr;
+    for (int k = lane; k < Sk; k += 64) {
+      float pv = ld(pr + k);
+      float v = pv * (ld(dr + k) - s);
+      if (kmr && kmr[k] == 0.f) v = 0.f;
+      st(dr + k, v);
+    }
+  }
+}
+template <typename T>
+void k_softmax_bwd(spa3d_ctx* c, const T* p, T* dp, int64_t rows, int Sk, const float* km, int64_t rows_per_seq) {
+  if (c->dry || rows == 0) return;
+  unsigned g = (unsigned)std::min<int64_t>(cdiv(rows, 4), 65536);
+  softmax_bwd_kernel<T><<<g, 256, 0, c->stream>>>(p, dp, rows, Sk, km, rows_per_seq);
+  SPA_LAUNCH_CHECK(c);
+}
 
 template <typename T> static T* aalloc(spa3d_ctx* c, int64_t n) { return (T*)c->ar.alloc(n * (int64_t)sizeof(T)); }
 

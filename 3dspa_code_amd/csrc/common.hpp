@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -121,6 +122,26 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// 16 bytes per lane and access: 4 f32 or 8 values of the 16-bit type, as floats in registers
+template <typename T> struct VecOf;
+template <> struct VecOf<float> { static constexpr int N = 4; };
+template <> struct VecOf<bf16_t> { static constexpr int N = 8; };
+template <typename T, int NV>
+__device__ __forceinline__ void load_vec(const T* p, float (&f)[NV]) {
+  if constexpr (sizeof(T) == 4) { const float4 v = *(const float4*)p; f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w; }
+  else { const uint4 v = *(const uint4*)p; const unsigned u[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { f[2 * i] = unpack_lo(u[i]); f[2 * i + 1] = unpack_hi(u[i]); } }
+}
+template <typename T, int NV>
+__device__ __forceinline__ void store_vec(T* p, const float (&f)[NV]) {
+  if constexpr (sizeof(T) == 4) { *(float4*)p = make_float4(f[0], f[1], f[2], f[3]); }
+  else { unsigned u[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) u[i] = f2bf_pack2(f[2 * i], f[2 * i + 1]);
+    *(uint4*)p = make_uint4(u[0], u[1], u[2], u[3]); }
+}
+
 // A kernel with many additions reads the mode ONCE and passes it along; the cold sites (one addition per thread at a workgroup's end) read it at the addition.
 __device__ __forceinline__ DetCfg det_read(const DetCfg* d) { return d ? *d : DetCfg{nullptr, nullptr, 0, nullptr, 4294967296.f}; }
 __device__ __forceinline__ void grad_add(const DetCfg& dc, float* p, float v) {
@@ -152,7 +173,7 @@ __device__ __forceinline__ void grad_add_q(const DetCfg& dc, float* p, long long
 // ------------------------------------------------------------------------------------------
 // host-side context
 // ------------------------------------------------------------------------------------------
-// One launch of score_rows_kernel (kernels.hip): rows [row0, row0 + nq) of the [B * Q] query rows.  Targets, sample scale, query_stats and frame_err are the
+// One launch of score_rows_kernel (loss.hip): rows [row0, row0 + nq) of the [B * Q] query rows.  Targets, sample scale, query_stats and frame_err are the
 // caller's whole tensors, indexed by the global row; the predictions come either from this launch's head rows (head != null: [nq][4 * T], coordinate-major,
 // row 0 = global row row0) or from the caller's split tensors (tracks [B * Q][T][NC], vlog [B * Q][T]).  The thresholds travel by value.
 struct ScoreArgs {
@@ -313,6 +334,10 @@ struct ProfScope {  // records an event pair around the launches issued in its l
     }                                                                             \
   } while (0)
 
+// launch geometry of the element-wise kernels: a 1-D grid of at most 2^20 workgroups of bs threads over n items (the kernels stride)
+#define GRID1D(n, bs) dim3((unsigned)std::min<int64_t>(((n) + (bs)-1) / (bs), 1 << 20))
+static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
 namespace SPA_NS {
 template <typename T> void gemm_generic(spa3d_ctx* c, const GemmDesc& d);
 // The GEMM launchers: each launches the kernel gemm_plan.hpp chose for the descriptor (never a refused or dry-run plan: gemm_launch)
@@ -351,56 +376,59 @@ template <typename T> void gemm_launch(spa3d_ctx* c, const GemmDesc& d, GemmKern
 }
 
 // ------------------------------------------------------------------------------------------
-// elementwise / reduction kernels (kernels.hip), all asynchronous on c->stream; no-ops when c->dry
+// launchers of the kernel units, grouped by file in each file's order; all asynchronous on c->stream; no-ops when c->dry
 // ------------------------------------------------------------------------------------------
+// layernorm.hip
 template <typename T> void k_layernorm(spa3d_ctx*, const T* x, const float* scale, T* y, float* stats, int64_t rows, int d);
 template <typename T> void k_layernorm_bwd(spa3d_ctx*, const T* x, const float* scale, const float* stats, const T* dy, T* dx,
                                            float* dscale, int64_t rows, int d, const T* add);
-template <typename T> void k_rmsnorm_heads(spa3d_ctx*, const T* x, int64_t ldx, const float* scale, T* y, int64_t ldy, int64_t rows, int H, int Dh);
-template <typename T> void k_rmsnorm_heads_bwd(spa3d_ctx*, const T* x, int64_t ldx, const float* scale, const T* dy, int64_t lddy, T* dx,
-                                               int64_t lddx, float* dscale, int64_t rows, int H, int Dh);
-template <typename T> void k_softmax(spa3d_ctx*, T* s, const float* keymask, int64_t nseq, int H, int Sq, int Sk);
-template <typename T> void k_softmax_bwd(spa3d_ctx*, const T* p, T* dp, int64_t rows, int Sk, const float* keymask = nullptr,
-                                         int64_t rows_per_seq = 1);
+// attention.hip: the attention front ends (generic composition or the fused kernels of attention_fused.hip, by impl)
+template <typename T>
+void attention_fwd(spa3d_ctx* c, const T* q, const T* k, const T* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq,
+                   const float* sk, const float* km, int64_t nseq, int Sq, int Sk, int H, int Dh, T* o, float* lse, int impl,
+                   const int32_t* seq_off = nullptr, int64_t total_rows = 0);
+template <typename T>
+void attention_bwd(spa3d_ctx* c, const T* q, const T* k, const T* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq,
+                   const float* sk, const float* km, int64_t nseq, int Sq, int Sk, int H, int Dh, const T* o, const float* lse, const T* d_o,
+                   T* dq, T* dk, T* dv, float* dsq, float* dsk, int impl, const int32_t* seq_off = nullptr, int64_t total_rows = 0);
+template <typename T>
+void attention_varlen_fwd(spa3d_ctx* c, const T* q, const T* k, const T* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq, const float* sk,
+                          int64_t nseq, int Sq, const int32_t* koff_host, const int32_t* koff_dev, int H, int Dh, T* o, float* lse, int impl);
+template <typename T>
+void attention_varlen_bwd(spa3d_ctx* c, const T* q, const T* k, const T* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq, const float* sk,
+                          int64_t nseq, int Sq, const int32_t* koff_host, const int32_t* koff_dev, int H, int Dh, const T* o, const float* lse,
+                          const T* d_o, T* dq, T* dk, T* dv, float* dsq, float* dsk, int impl);
+// embed.hip
 template <typename T> void k_sin_embed(spa3d_ctx*, const float* x, int64_t rows, int C, int nf, float prescale, T* out);
 template <typename T> void k_embed_tokens(spa3d_ctx*, const float* tracks, int64_t nrows, int T_, int nf, float prescale, T* sinbuf, int NC = 3);
-template <typename T> void k_colsum(spa3d_ctx*, const T* x, int64_t rows, int n, int64_t ld, float* out /*accumulated*/, int rgroup = 0,
-                                    int rskip = 0);
-template <typename T> void k_gelu(spa3d_ctx*, const T* x, T* y, int64_t n);
-template <typename T> void k_add(spa3d_ctx*, T* dst, const T* src, int64_t n);
-void k_fill(spa3d_ctx*, float* p, float v, int64_t n);
-void k_zero(spa3d_ctx*, void* p, int64_t bytes);
-void k_set_i32(spa3d_ctx*, int32_t* dst, const int32_t* host, int64_t n);  // n host ints -> device, by value in the launch arguments
-void k_mul(spa3d_ctx*, float* a, const float* b, int64_t n);
-void k_set_loss_scale(spa3d_ctx*, const float* denom_dev, float l1w, float setting, float* scale_dev);
-void k_unscale(spa3d_ctx*, float* a, const float* scale_dev, int64_t n);
-template <typename T> void k_cast_from_f32(spa3d_ctx*, const float* src, T* dst, int64_t n);
-template <typename T> void k_cast_to_f32(spa3d_ctx*, const T* src, float* dst, int64_t n);
-template <typename T> void k_pack(spa3d_ctx*, const float* src, int64_t src_ld, int rows, int cols, T* dst_native, int64_t ldn, T* dst_T, int64_t ldt);
-template <typename T> void k_transpose(spa3d_ctx*, const T* src, int rows, int cols, T* dst);  // dst[c][r] = src[r][c]
-template <typename T> void k_set_readout_rows(spa3d_ctx*, T* tok, const float* readout, int64_t nseq, int S, int d);
+void k_query_embed1(spa3d_ctx*, const float* qp, int64_t nq, int nf, float track_scale, float time_scale, float* feat, int32_t* qframe,
+                    int NC = 3);
 template <typename T> void k_embed_maps(spa3d_ctx*, const int32_t* row_src, int64_t rows, int S, int T_, int32_t* arow, int32_t* crow, T* tok, const float* readout, int d);
-void k_sum3(spa3d_ctx*, const float* a, const float* b, const float* c3, float* out, int n);
+template <typename T> void k_set_readout_rows(spa3d_ctx*, T* tok, const float* readout, int64_t nseq, int S, int d);
 void k_keymask(spa3d_ctx*, const float* visible, const int32_t* boundary, int64_t nseq, int N, int T_, float* km);
-template <typename T> void k_gather_rows(spa3d_ctx*, const T* src, int64_t src_stride_rows, T* dst, int64_t n, int d);
-// token pruning of the track encoder (kernels.hip): plan (returns the kept-row count, one stream sync) and rows-by-index movers
-int64_t k_prune_plan(spa3d_ctx*, const float* km, int64_t nseq, int S, int32_t* cnt, int32_t* seq_off, int32_t* row_src);
-template <typename T> void k_rows_idx(spa3d_ctx*, int mode /*0 gather, 1 scatter, 2 scatter-add*/, const T* src, const int32_t* idx, T* dst, int64_t n, int d);
-template <typename T> void k_scatter_rows(spa3d_ctx*, const T* src, T* dst, int64_t dst_stride_rows, int64_t n, int d);
-template <typename T> void k_compact_tokens(spa3d_ctx*, const T* tok, T* dst, int64_t nseq, int S, int d);
-template <typename T> void k_broadcast_rows(spa3d_ctx*, const float* src, int rows, int d, T* dst, int64_t B);
-template <typename T> void k_bcast_grad(spa3d_ctx*, const T* dsrc, int64_t per, int64_t B, int64_t bstride, float* dparam);
+void k_keymask2d(spa3d_ctx*, const float* visible, const int32_t* boundary, int64_t nseq, int N, int T_, float* km);  // 2-D TRAJAN twin (track_autoencoder.py:117-390)
+void k_sum3(spa3d_ctx*, const float* a, const float* b, const float* c3, float* out, int n);
 // Dense with input width K <= 4 as streaming kernels (false: shape not covered, use the GEMM path)
 template <typename T> bool k_rank_fwd(spa3d_ctx*, const T* x, const T* w /*[K][N]*/, const float* bias, T* out /*+=*/, int64_t M, int N, int K, int64_t ldo,
                                       int rgroup, int rskip);
 template <typename T> bool k_rank_bwd(spa3d_ctx*, const T* x, const T* dy, int64_t M, int N, int K, int64_t ldy, int rgroup, int rskip, float* gw /*+=*/,
                                       float* gb /*+=, may be null*/);
-void k_discretize(spa3d_ctx*, const float* lat, const float* noise, int discretize, float* out, float* clipmask, int64_t n);
-void k_query_embed1(spa3d_ctx*, const float* qp, int64_t nq, int nf, float track_scale, float time_scale, float* feat, int32_t* qframe,
-                    int NC = 3);
-template <typename T> void k_assemble_readout(spa3d_ctx*, const T* qtok, const T* lat, const int32_t* qframe, int64_t B, int Q, int L, int Cl,
-                                              int D, T* seq);
-// shared latent rows of the readout stack's first block (kernels.hip "Shared latent rows"; model.hip Share)
+template <typename T> void k_pack(spa3d_ctx*, const float* src, int64_t src_ld, int rows, int cols, T* dst_native, int64_t ldn, T* dst_T, int64_t ldt);
+template <typename T> void k_transpose(spa3d_ctx*, const T* src, int rows, int cols, T* dst);  // dst[c][r] = src[r][c]
+// rows.hip
+void k_zero(spa3d_ctx*, void* p, int64_t bytes);
+void k_set_i32(spa3d_ctx*, int32_t* dst, const int32_t* host, int64_t n);  // n host ints -> device, by value in the launch arguments
+void k_mul(spa3d_ctx*, float* a, const float* b, int64_t n);
+template <typename T> void k_cast_from_f32(spa3d_ctx*, const float* src, T* dst, int64_t n);
+template <typename T> void k_cast_to_f32(spa3d_ctx*, const T* src, float* dst, int64_t n);
+template <typename T> void k_colsum(spa3d_ctx*, const T* x, int64_t rows, int n, int64_t ld, float* out /*accumulated*/, int rgroup = 0,
+                                    int rskip = 0);
+template <typename T> void k_gather_rows(spa3d_ctx*, const T* src, int64_t src_stride_rows, T* dst, int64_t n, int d);
+template <typename T> void k_rows_idx(spa3d_ctx*, int mode /*0 gather, 1 scatter, 2 scatter-add*/, const T* src, const int32_t* idx, T* dst, int64_t n, int d);
+template <typename T> void k_add_rows_strided(spa3d_ctx*, T* dst, const T* src, int64_t dst_stride_rows, int64_t n, int d);
+// token pruning of the track encoder: the plan (returns the kept-row count, one stream sync); k_rows_idx moves the rows
+int64_t k_prune_plan(spa3d_ctx*, const float* km, int64_t nseq, int S, int32_t* cnt, int32_t* seq_off, int32_t* row_src);
+// shared latent rows of the readout stack's first block (rows.hip "Shared latent rows"; model.hip Share)
 int64_t k_share_plan(spa3d_ctx*, const int32_t* qframe, int64_t B, int Q, int32_t* slot, int32_t* slot_b, int32_t* slot_f, int32_t* slot_q0, int32_t* scratch);
 template <typename T> void k_share_assemble(spa3d_ctx*, const T* qtok, const T* lat, const int32_t* slot_b, const int32_t* slot_f, int64_t nslot, int64_t BQ,
                                             int L, int Cl, int D, T* xU);
@@ -408,27 +436,16 @@ template <typename T> void k_share_expand(spa3d_ctx*, const T* srcU, const int32
                                           const T* add, T* dst);
 template <typename T> void k_share_reduce(spa3d_ctx*, const T* src, const int32_t* slot, const int32_t* slot_b, int64_t nslot, int64_t nseq, int Q, int S, int d,
                                           T* dstU);
+template <typename T> void k_assemble_readout(spa3d_ctx*, const T* qtok, const T* lat, const int32_t* qframe, int64_t B, int Q, int L, int Cl,
+                                              int D, T* seq);
 template <typename T> void k_assemble_readout_bwd(spa3d_ctx*, const T* dseq, const int32_t* qframe, int64_t B, int Q, int L, int Cl, int D,
                                                   T* dqtok, float* dlat, bool accumulate = false);
-void k_loss_fwd(spa3d_ctx*, const float* head, int64_t nq, int T_, const float* tgt, const float* tvis, float* tracks, float* vlog,
-                float* clog, float* sums, unsigned* poison, int NC = 3);
-void k_loss_from_preds(spa3d_ctx*, const float* tracks, const float* vlog, int64_t n, const float* tgt, const float* tvis, float* sums,
-                       unsigned* poison, int NC = 3);
-void k_score_rows(spa3d_ctx*, const ScoreArgs& a);
-void k_score_reduce(spa3d_ctx*, const float* qstats, int64_t B, int Q, int K, double* out /*[B][8 + 4K]*/);
-template <typename T> void k_loss_bwd(spa3d_ctx*, const float* head, int64_t nq, int T_, const float* tgt, const float* tvis,
-                                      const float* denom_dev, float l1w, float bcew, T* dhead, int NC = 3, const float* scale_dev = nullptr);
-void k_vis_count(spa3d_ctx*, const float* tvis, int64_t n, float* out, unsigned* poison);
-void k_set_denom(spa3d_ctx*, const float* sums, const unsigned* poison, float denom_host, float* denom_dev);
-void k_loss_finalize(spa3d_ctx*, const float* sums, const unsigned* poison, const float* denom_dev, float l1w, float bcew, float* loss3);
-void k_adamw(spa3d_ctx*, float* p, const float* g, float* m, float* v, int64_t n, float lr, int64_t step, float clip, float b1, float b2,
-             float eps, float wd, float* scratch);
-void k_uniform_noise(spa3d_ctx*, float* out, int64_t n, uint32_t k0, uint32_t k1);
-// over [lo, lo + n) of c->det: g[i] += shadow[i] / scale; shadow[i] = 0; NaN when *flag or |shadow[i]| >= 2^62
-void k_det_flush(spa3d_ctx* c, int64_t lo, int64_t n);
-// *out = d with the call's unit as its scale (DetCfg unit rule)
-void k_det_unit(spa3d_ctx*, const float* sums, const unsigned* poison, const float* denom_dev, const float* scale_dev, const DetCfg& d, DetCfg* out);
-// single-query attention of the pruned last block (kernels.hip)
+template <typename T> void k_broadcast_rows(spa3d_ctx*, const float* src, int rows, int d, T* dst, int64_t B);
+template <typename T> void k_bcast_grad(spa3d_ctx*, const T* dsrc, int64_t per, int64_t B, int64_t bstride, float* dparam);
+// 2-D TRAJAN twin (track_autoencoder.py:117-390)
+template <typename T> void k_vis_mean_pool(spa3d_ctx*, const T* tok, const float* vis, int64_t nseq, int T_, int d, T* out);
+template <typename T> void k_vis_mean_pool_bwd(spa3d_ctx*, const T* dout, const float* vis, int64_t nseq, int T_, int d, T* dtok);
+// attn_q1.hip: single-query attention of the pruned last block
 template <typename T> void k_attn_q1_fwd(spa3d_ctx*, const T* q0, int64_t ldq0, const T* k, const T* v, int64_t ldk, int64_t ldv,
                                          const float* sq, const float* sk, const float* km, int64_t nseq, int S, int H, int Dh, T* o0,
                                          float* p0, const int32_t* seq_off = nullptr);
@@ -436,10 +453,27 @@ template <typename T> void k_attn_q1_bwd(spa3d_ctx*, const T* q0, int64_t ldq0, 
                                          const float* sq, const float* sk, const float* km, int64_t nseq, int S, int H, int Dh,
                                          const float* p0, const T* d_o0, T* dq0, T* dk, T* dv, float* dsq, float* dsk,
                                          const int32_t* seq_off = nullptr);
-template <typename T> void k_add_rows_strided(spa3d_ctx*, T* dst, const T* src, int64_t dst_stride_rows, int64_t n, int d);
-// 2-D TRAJAN twin (track_autoencoder.py:117-390)
-template <typename T> void k_vis_mean_pool(spa3d_ctx*, const T* tok, const float* vis, int64_t nseq, int T_, int d, T* out);
-template <typename T> void k_vis_mean_pool_bwd(spa3d_ctx*, const T* dout, const float* vis, int64_t nseq, int T_, int d, T* dtok);
-void k_keymask2d(spa3d_ctx*, const float* visible, const int32_t* boundary, int64_t nseq, int N, int T_, float* km);
+// loss.hip
+void k_discretize(spa3d_ctx*, const float* lat, const float* noise, int discretize, float* out, float* clipmask, int64_t n);
+void k_loss_fwd(spa3d_ctx*, const float* head, int64_t nq, int T_, const float* tgt, const float* tvis, float* tracks, float* vlog,
+                float* clog, float* sums, unsigned* poison, int NC = 3);
+void k_loss_from_preds(spa3d_ctx*, const float* tracks, const float* vlog, int64_t n, const float* tgt, const float* tvis, float* sums,
+                       unsigned* poison, int NC = 3);
+void k_score_rows(spa3d_ctx*, const ScoreArgs& a);
+void k_score_reduce(spa3d_ctx*, const float* qstats, int64_t B, int Q, int K, double* out /*[B][8 + 4K]*/);
+void k_vis_count(spa3d_ctx*, const float* tvis, int64_t n, float* out, unsigned* poison);
+void k_set_denom(spa3d_ctx*, const float* sums, const unsigned* poison, float denom_host, float* denom_dev);
+void k_loss_finalize(spa3d_ctx*, const float* sums, const unsigned* poison, const float* denom_dev, float l1w, float bcew, float* loss3);
+template <typename T> void k_loss_bwd(spa3d_ctx*, const float* head, int64_t nq, int T_, const float* tgt, const float* tvis,
+                                      const float* denom_dev, float l1w, float bcew, T* dhead, int NC = 3, const float* scale_dev = nullptr);
+void k_set_loss_scale(spa3d_ctx*, const float* denom_dev, float l1w, float setting, float* scale_dev);
+void k_unscale(spa3d_ctx*, float* a, const float* scale_dev, int64_t n);
+void k_adamw(spa3d_ctx*, float* p, const float* g, float* m, float* v, int64_t n, float lr, int64_t step, float clip, float b1, float b2,
+             float eps, float wd, float* scratch);
+void k_uniform_noise(spa3d_ctx*, float* out, int64_t n, uint32_t k0, uint32_t k1);
+// over [lo, lo + n) of c->det: g[i] += shadow[i] / scale; shadow[i] = 0; NaN when *flag or |shadow[i]| >= 2^62
+void k_det_flush(spa3d_ctx* c, int64_t lo, int64_t n);
+// *out = d with the call's unit as its scale (DetCfg unit rule)
+void k_det_unit(spa3d_ctx*, const float* sums, const unsigned* poison, const float* denom_dev, const float* scale_dev, const DetCfg& d, DetCfg* out);
 }  // namespace SPA_NS
 using namespace SPA_NS;  // one 16-bit type per translation unit

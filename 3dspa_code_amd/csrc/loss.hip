@@ -1,0 +1,432 @@
+// loss.hip -- everything between the head and the parameter update (gfx950): latent discretisation, the loss (forward, backward, from
+// split predictions), per-track scores, the loss scale of the 16-bit backward, AdamW with its gradient-norm and skip guard, the
+// Threefry uniform noise, and the det_grads flush and unit.  Sums over the batch are fixed-order or fixed-point: no float atomics.
+// T in {float, bf16_t} storage, fp32 math.  References such as attention.py:49 are to the reference implementation's files.
+#include <algorithm>
+
+#include "common.hpp"
+
+namespace SPA_NS {
+
+// ---------------------------------------------------------------------------------------------
+// D1: clip, discretise, fixed noise, straight-through (track_autoencoder_3d.py:251-260)
+// out = l - (l - q)  (same op order as the reference);  clipmask = 1[-1<=raw<=1] for the backward
+// ---------------------------------------------------------------------------------------------
+__global__ void discretize_kernel(const float* __restrict__ lat, const float* __restrict__ noise, int disc, float* __restrict__ out,
+                                  float* __restrict__ clipmask, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    float raw = lat[i];
+    float l = raw != raw ? raw : fminf(fmaxf(raw, -1.f), 1.f);   // jnp.clip keeps a NaN a NaN (fmaxf / fminf would return the bound): a diverged latent must show
+    if (clipmask) clipmask[i] = raw != raw ? raw : ((raw >= -1.f && raw <= 1.f) ? 1.f : 0.f);   // ... in the backward as well (jnp.clip's gradient of NaN is NaN)
+    if (disc) {
+      float q = rintf(__fmul_rn(l, 128.f)) / 128.f;
+      q = __fsub_rn(__fadd_rn(q, noise[i] / 128.f), 1.0f / 256.0f);
+      l = __fsub_rn(l, __fsub_rn(l, q));
+    }
+    out[i] = l;
+  }
+}
+void k_discretize(spa3d_ctx* c, const float* lat, const float* noise, int discretize, float* out, float* clipmask, int64_t n) {
+  if (c->dry || n == 0) return;
+  discretize_kernel<<<GRID1D(n, 256), 256, 0, c->stream>>>(lat, noise, discretize, out, clipmask, n); SPA_LAUNCH_CHECK(c);
+}
+
+// ---------------------------------------------------------------------------------------------
+// D8 head split + compute_loss_3d (track_autoencoder_3d.py:289-301, train.py:96-129)
+// head[q][c*T+t], c<3 coords (coordinate-major), c==3 visibility logit
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ float log_sigmoid_f(float x) { return fminf(x, 0.f) - log1pf(expf(-fabsf(x))); }
+// The loss numerators and the visible count are summed over the whole batch by thousands of workgroups.  Float atomics make that sum depend
+// on arrival order (the same batch gave 14089.21875 and 14089.216796875 in round 3), so two data-parallel replicas could log different
+// losses and a test could not ask for bit-equal reruns.  Each workgroup reduces in a fixed order and adds its partial as a 64-bit FIXED-POINT
+// integer (2^-24 units: exact, order-independent integer addition; quantisation 6e-8 per workgroup, far below fp32 resolution of the sums).
+// Layout of the 10-float `sums` block: three 64-bit accumulators {position numerator, bce numerator, visible count} | denominator | loss scale | flag word.
+// A partial that is not finite or beyond the fixed-point range sets a STICKY flag word (atomicOr) next to the accumulators and adds nothing; the sums then read as
+// NaN.  (Round 4 added a marker value to the accumulator itself: k marked workgroups sum to k * 2^62 mod 2^64 = 0 for 4 | k, so a fully diverged forward reported loss 0.)
+constexpr float LOSS_FIX = 16777216.f;                 // 2^24
+__device__ __forceinline__ void loss_acc_add(unsigned long long* acc, unsigned* poison, float partial) {
+  const float f = partial * LOSS_FIX;
+  if (fabsf(f) < 1.0e15f) atomicAdd(acc, (unsigned long long)__float2ll_rn(f));   // NaN fails the comparison too
+  else atomicOr(poison, 1u);
+}
+__device__ __forceinline__ float loss_acc_read(const unsigned long long* acc, const unsigned* poison) {
+  if (*poison) return __int_as_float(0x7fc00000);
+  return (float)((double)(long long)*acc * (1.0 / 16777216.0));
+}
+__global__ __launch_bounds__(256) void head_loss_fwd_kernel(const float* __restrict__ head, int64_t nq, int T_, const float* __restrict__ tgt,
+                                                            const float* __restrict__ tvis, float* __restrict__ tracks,
+                                                            float* __restrict__ vlog, float* __restrict__ clog, float* __restrict__ sums, unsigned* poison, int NC) {
+  // head row: NC coordinate blocks of T, then the visibility logits; the 2-D model (NC == 2) has a 4th block: certainty logits
+  __shared__ float red[3][4];
+  float pn = 0.f, bn = 0.f;
+  const int64_t n = nq * T_;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    int64_t q = i / T_; int t = (int)(i - q * T_);
+    const float* hr = head + q * 4 * T_;
+    const float lg = hr[NC * T_ + t];
+    float perr = 0.f;
+    for (int cdx = 0; cdx < NC; ++cdx) {
+      const float pv = hr[cdx * T_ + t];
+      if (tracks) tracks[i * NC + cdx] = pv;
+      if (tgt) perr += fabsf(pv - tgt[i * NC + cdx]);
+    }
+    if (vlog) vlog[i] = lg;
+    if (clog) clog[i] = NC == 2 ? hr[3 * T_ + t] : 0.f;  // 3DSPA: certain_logits = zeros (3d:301); TRAJAN: real head (ta:344)
+    if (tgt) {
+      float y = tvis[i];
+      pn += perr * y;
+      bn += -y * log_sigmoid_f(lg) - (1.f - y) * log_sigmoid_f(-lg);
+    }
+  }
+  if (!tgt) return;
+  pn = wave_sum(pn); bn = wave_sum(bn);
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { red[0][w] = pn; red[1][w] = bn; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    loss_acc_add((unsigned long long*)sums + 0, poison, red[0][0] + red[0][1] + red[0][2] + red[0][3]);
+    loss_acc_add((unsigned long long*)sums + 1, poison, red[1][0] + red[1][1] + red[1][2] + red[1][3]);
+  }
+}
+void k_loss_fwd(spa3d_ctx* c, const float* head, int64_t nq, int T_, const float* tgt, const float* tvis, float* tracks, float* vlog,
+                float* clog, float* sums, unsigned* poison, int NC) {
+  if (c->dry || nq == 0) return;
+  unsigned g = (unsigned)std::min<int64_t>(cdiv(nq * T_, 256), 4096);
+  head_loss_fwd_kernel<<<g, 256, 0, c->stream>>>(head, nq, T_, tgt, tvis, tracks, vlog, clog, sums, poison, NC);
+  SPA_LAUNCH_CHECK(c);
+}
+// same numerators from already-split predictions (spa3d_loss entry point)
+__global__ __launch_bounds__(256) void loss_from_preds_kernel(const float* __restrict__ tracks, const float* __restrict__ vlog, int64_t n,
+                                                              const float* __restrict__ tgt, const float* __restrict__ tvis, float* sums, unsigned* poison, int NC) {
+  __shared__ float red[2][4];
+  float pn = 0.f, bn = 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    float y = tvis[i], lg = vlog[i];
+    float perr = 0.f;
+    for (int cdx = 0; cdx < NC; ++cdx) perr += fabsf(tracks[i * NC + cdx] - tgt[i * NC + cdx]);
+    pn += perr * y;
+    bn += -y * log_sigmoid_f(lg) - (1.f - y) * log_sigmoid_f(-lg);
+  }
+  pn = wave_sum(pn); bn = wave_sum(bn);
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { red[0][w] = pn; red[1][w] = bn; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    loss_acc_add((unsigned long long*)sums + 0, poison, red[0][0] + red[0][1] + red[0][2] + red[0][3]);
+    loss_acc_add((unsigned long long*)sums + 1, poison, red[1][0] + red[1][1] + red[1][2] + red[1][3]);
+  }
+}
+void k_loss_from_preds(spa3d_ctx* c, const float* tracks, const float* vlog, int64_t n, const float* tgt, const float* tvis, float* sums,
+                       unsigned* poison, int NC) {
+  if (c->dry || n == 0) return;
+  unsigned g = (unsigned)std::min<int64_t>(cdiv(n, 256), 4096);
+  loss_from_preds_kernel<<<g, 256, 0, c->stream>>>(tracks, vlog, n, tgt, tvis, sums, poison, NC);
+  SPA_LAUNCH_CHECK(c);
+}
+// ---------------------------------------------------------------------------------------------
+// Per-track scores (spa3d_score / spa3d_score_from_preds; arithmetic and summation order: score_row.hpp)
+// One wave per query row, four rows per workgroup.  Lanes stride over the frames: in the head form every coordinate block of the row is read
+// coalesced, in the split form a wave reads the row's contiguous [T][NC] span.  The row's sums are merged by the xor butterfly, so every lane
+// ends with the same bits, and lanes 0 .. S-1 store one stat each.  No atomics: the same inputs give the same bits on every run, and the two
+// input forms run the same instructions on the same values.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ void score_acc_xor(ScoreAcc& a, int o, int K) {
+  ScoreAcc b;
+  b.n_vis = __shfl_xor(a.n_vis, o, 64); b.s_e1 = __shfl_xor(a.s_e1, o, 64); b.s_e2 = __shfl_xor(a.s_e2, o, 64); b.mx = __shfl_xor(a.mx, o, 64);
+  b.bce = __shfl_xor(a.bce, o, 64); b.occ = __shfl_xor(a.occ, o, 64); b.n_pv = __shfl_xor(a.n_pv, o, 64);
+#pragma unroll
+  for (int k = 0; k < SCORE_MAX_K; ++k) {
+    if (k < K) {  // wave-uniform
+      b.w[k] = __shfl_xor(a.w[k], o, 64); b.tp[k] = __shfl_xor(a.tp[k], o, 64); b.fp[k] = __shfl_xor(a.fp[k], o, 64); b.fn[k] = __shfl_xor(a.fn[k], o, 64);
+    } else {
+      b.w[k] = b.tp[k] = b.fp[k] = b.fn[k] = 0.f;
+    }
+  }
+  score_acc_merge(a, b, K);
+}
+__global__ __launch_bounds__(256) void score_rows_kernel(const ScoreArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= a.nq) return;  // whole waves leave: no shuffle partner is lost
+  const int64_t gr = a.row0 + r;
+  const int T = a.T, NC = a.NC;
+  const ScoreThr thr = score_thr_scaled(a.thr, a.scale ? a.scale[gr / a.Q] : 1.f);
+  const float *p, *lg; long sp, st;  // sp: stride between the coordinates of a frame, st: between frames
+  if (a.head) { p = a.head + r * 4 * T; lg = p + (int64_t)NC * T; sp = T; st = 1; }
+  else { p = a.tracks + gr * T * NC; lg = a.vlog + gr * T; sp = 1; st = NC; }
+  const float* g = a.tgt + gr * T * NC;
+  const float* y = a.tvis + gr * T;
+  ScoreAcc acc;
+  score_acc_init(acc);
+  for (int t = lane; t < T; t += 64) {
+    const float e2 = score_acc_frame(acc, p + (long)t * st, sp, g + (long)t * NC, 1, NC, lg[t], y[t], thr);
+    if (a.frame_err) a.frame_err[gr * T + t] = e2;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) score_acc_xor(acc, o, thr.K);
+  const int S = score_row_len(thr.K);
+  if (lane < S) a.qstats[gr * S + lane] = score_acc_slot(acc, lane, T);
+}
+void k_score_rows(spa3d_ctx* c, const ScoreArgs& a) {
+  if (c->dry || a.nq <= 0) return;
+  score_rows_kernel<<<(unsigned)cdiv(a.nq, 4), 256, 0, c->stream>>>(a);
+  SPA_LAUNCH_CHECK(c);
+}
+// sample_stats[b][s] (double) = the sample's Q rows of query_stats reduced in a fixed order: thread i takes rows i, i + 256, ..., then a tree
+// over the 256 partials.  Slot 3 is a max; padded rows hold zeros and add nothing.  One workgroup per (sample, stat).
+__global__ __launch_bounds__(256) void score_reduce_kernel(const float* __restrict__ qstats, int Q, int S, double* __restrict__ out) {
+  __shared__ double red[256];
+  const int64_t b = blockIdx.x / S; const int s = (int)(blockIdx.x - b * S);
+  const float* base = qstats + b * Q * S + s;
+  const bool is_max = s == 3;
+  double v = 0.0;
+  for (int q = threadIdx.x; q < Q; q += 256) {
+    const double x = (double)base[(int64_t)q * S];
+    v = is_max ? (x > v ? x : v) : v + x;
+  }
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) {
+      const double x = red[threadIdx.x + o], w = red[threadIdx.x];
+      red[threadIdx.x] = is_max ? (x > w ? x : w) : w + x;
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[blockIdx.x] = red[0];
+}
+void k_score_reduce(spa3d_ctx* c, const float* qstats, int64_t B, int Q, int K, double* out) {
+  if (c->dry || B <= 0) return;
+  const int S = score_row_len(K);
+  score_reduce_kernel<<<(unsigned)(B * S), 256, 0, c->stream>>>(qstats, Q, S, out);
+  SPA_LAUNCH_CHECK(c);
+}
+
+__global__ __launch_bounds__(256) void vis_count_kernel(const float* __restrict__ v, int64_t n, float* out, unsigned* poison) {
+  __shared__ float red[4];
+  float s = 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) s += v[i];
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) loss_acc_add((unsigned long long*)out, poison, red[0] + red[1] + red[2] + red[3]);
+}
+void k_vis_count(spa3d_ctx* c, const float* tvis, int64_t n, float* out, unsigned* poison) {
+  if (c->dry || n == 0) return;
+  unsigned g = (unsigned)std::min<int64_t>(cdiv(n, 256), 1024);
+  vis_count_kernel<<<g, 256, 0, c->stream>>>(tvis, n, out, poison); SPA_LAUNCH_CHECK(c);
+}
+// sums = {pos_num, bce_num, vis_cnt} (fixed-point accumulators, see loss_acc_add); denom_dev = denom_host>0 ? denom_host : max(vis_cnt,1)
+__global__ void set_denom_kernel(const float* sums, const unsigned* poison, float denom_host, float* denom_dev) {
+  *denom_dev = denom_host > 0.f ? denom_host : fmaxf(loss_acc_read((const unsigned long long*)sums + 2, poison), 1.f);  // fmaxf(NaN, 1) = 1: the numerators carry the NaN
+}
+void k_set_denom(spa3d_ctx* c, const float* sums, const unsigned* poison, float denom_host, float* denom_dev) {
+  if (c->dry) return;
+  set_denom_kernel<<<1, 1, 0, c->stream>>>(sums, poison, denom_host, denom_dev); SPA_LAUNCH_CHECK(c);
+}
+__global__ void loss_finalize_kernel(const float* sums, const unsigned* poison, const float* denom_dev, float l1w, float bcew, float* loss3) {
+  float d = *denom_dev;
+  float pos = loss_acc_read((const unsigned long long*)sums + 0, poison) / d, vis = loss_acc_read((const unsigned long long*)sums + 1, poison) / d;
+  loss3[0] = l1w * pos + bcew * vis; loss3[1] = pos; loss3[2] = vis;
+}
+void k_loss_finalize(spa3d_ctx* c, const float* sums, const unsigned* poison, const float* denom_dev, float l1w, float bcew, float* loss3) {
+  if (c->dry) return;
+  loss_finalize_kernel<<<1, 1, 0, c->stream>>>(sums, poison, denom_dev, l1w, bcew, loss3); SPA_LAUNCH_CHECK(c);
+}
+// d head: l1w*sign(pred-tgt)*vis/denom ; bcew*(sigmoid(l)-y)/denom ; sign(0)=0
+template <typename T>
+__global__ void loss_bwd_kernel(const float* __restrict__ head, int64_t nq, int T_, const float* __restrict__ tgt,
+                                const float* __restrict__ tvis, const float* __restrict__ denom_dev, float l1w, float bcew, T* __restrict__ dhead,
+                                int NC, const float* __restrict__ scale_dev) {
+  const float inv = (scale_dev ? *scale_dev : 1.f) / *denom_dev;  // scale_dev: the fp16 mode's loss scale (a power of two)
+  const int64_t n = nq * 4 * T_;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    int64_t q = i / (4 * T_); int j = (int)(i - q * 4 * T_);
+    int cc = j / T_, t = j - cc * T_;
+    float y = tvis[q * T_ + t], g;
+    if (cc < NC) {
+      float df = head[i] - tgt[(q * T_ + t) * NC + cc];
+      g = l1w * (df > 0.f ? 1.f : (df < 0.f ? -1.f : 0.f)) * y * inv;
+    } else if (cc == NC) {
+      float l = head[i];
+      g = bcew * (1.f / (1.f + expf(-l)) - y) * inv;
+    } else {
+      g = 0.f;  // TRAJAN's certainty head carries no loss term in compute_loss_2d (train.py:60-93)
+    }
+    st(dhead + i, g);
+  }
+}
+template <typename T>
+void k_loss_bwd(spa3d_ctx* c, const float* head, int64_t nq, int T_, const float* tgt, const float* tvis, const float* denom_dev, float l1w,
+                float bcew, T* dhead, int NC, const float* scale_dev) {
+  if (c->dry || nq == 0) return;
+  loss_bwd_kernel<T><<<GRID1D(nq * 4 * T_, 256), 256, 0, c->stream>>>(head, nq, T_, tgt, tvis, denom_dev, l1w, bcew, dhead, NC, scale_dev);
+  SPA_LAUNCH_CHECK(c);
+}
+// Loss scale of the 16-bit backward (fp16 mode).  setting > 0: that value.  setting < 0: automatic -- the largest power of two that keeps
+// the head gradient's magnitude l1w / denom at or below |setting| (16): activations' gradients then sit mid-range in fp16 for any batch
+// size (at BASELINE cfg#3, denom = 4.4 M: 8192; a 100-element toy batch: 1).
+// `state` (may be null): the caller's dynamic-scale state, state[0] = a power-of-two multiplier in (0, 1] that spa3d_adamw_step halves after
+// a step with a non-finite gradient norm and grows back after 200 finite ones (0 or garbage-free zero memory = 1).
+__global__ void set_loss_scale_kernel(const float* __restrict__ denom_dev, float l1w, float setting, const float* __restrict__ state,
+                                      float* __restrict__ scale_dev) {
+  float s = setting;
+  if (setting < 0.f) s = fminf(fmaxf(exp2f(floorf(log2f(*denom_dev * (-setting) / l1w))), 1.f), 16777216.f);
+  if (state) { const float m = state[0]; if (m > 0.f && m < 1.f) s = fmaxf(s * m, 5.9604645e-8f); }
+  *scale_dev = s;
+}
+void k_set_loss_scale(spa3d_ctx* c, const float* denom_dev, float l1w, float setting, float* scale_dev) {
+  if (c->dry) return;
+  set_loss_scale_kernel<<<1, 1, 0, c->stream>>>(denom_dev, l1w, setting, c->loss_scale_state, scale_dev); SPA_LAUNCH_CHECK(c);
+}
+__global__ void unscale_kernel(float* __restrict__ a, const float* __restrict__ scale_dev, int64_t n) {
+  const float s = 1.f / *scale_dev;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) a[i] *= s;
+}
+void k_unscale(spa3d_ctx* c, float* a, const float* scale_dev, int64_t n) {
+  if (c->dry || n == 0) return;
+  unscale_kernel<<<GRID1D(n, 256), 256, 0, c->stream>>>(a, scale_dev, n); SPA_LAUNCH_CHECK(c);
+}
+
+// ---------------------------------------------------------------------------------------------
+// optimizer: clip_by_global_norm -> adamw -> apply_updates on flat buffers (train.py:239-242)
+// ---------------------------------------------------------------------------------------------
+// Global gradient norm, reproducible: every workgroup writes ITS partial sum of squares to scratch[SUMSQ_OFF + block] (fixed thread -> element
+// map, fixed reduction tree) and adamw_guard_kernel adds the partials in index order.  A float atomicAdd here made the clip factor -- and so the
+// whole AdamW update -- depend on arrival order: two data-parallel replicas holding bit-identical reduced gradients could drift apart.
+constexpr int SUMSQ_MAXB = 512, SUMSQ_OFF = 256;  // partials live in floats [256, 768) of the >= 4 KiB scratch block
+__global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g, int64_t n, float* partial) {
+  __shared__ float red[4];
+  float s = 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) s += g[i] * g[i];
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                    float* __restrict__ v, int64_t n, float lr, float tstep, float clip, float b1,
+                                                    float b2, float eps, float wd, float* scratch) {
+  // bias correction at the number of updates actually APPLIED: calls so far (tstep = step + 1) minus the steps skipped before this one
+  // (scratch[3]; this kernel returns early when this step itself is skipped).  -expm1(t log b) keeps 1 - b^t accurate for b -> 1.
+  const float teff = fmaxf(tstep - scratch[3], 1.f);
+  const float bc1 = -expm1f(teff * logf(b1)), bc2 = -expm1f(teff * logf(b2));
+  const float gn = sqrtf(scratch[1]);
+  const float sc = gn < clip ? 1.f : clip / gn;
+  if (blockIdx.x == 0 && threadIdx.x == 0) scratch[0] = gn;
+  if (!(gn <= 3.0e38f)) return;  // inf / NaN gradient (an fp16 overflow): parameters and both moments stay as they are (adamw_guard_kernel reports it)
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    float gi = g[i] * sc;
+    float mi = b1 * m[i] + (1.f - b1) * gi;
+    float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+    m[i] = mi; v[i] = vi;
+    float mh = mi / bc1, vh = vi / bc2;
+    float pi = p[i];
+    p[i] = pi - lr * (mh / (sqrtf(vh) + eps) + wd * pi);
+  }
+}
+// scratch[2] := 1 if this step was skipped (non-finite gradient norm) else 0; scratch[3] += skipped steps; scratch[4] = dynamic loss-scale
+// multiplier (0 = 1; halved on a skip, doubled up to 1 after 200 finite steps counted in scratch[5]) -- read by set_loss_scale_kernel when the
+// caller registered it with spa3d_set_loss_scale_state.
+__global__ __launch_bounds__(256) void adamw_guard_kernel(float* scratch, int nblocks) {
+  __shared__ float red[256];
+  float s = 0.f;
+  for (int i = threadIdx.x; i < nblocks; i += 256) s += scratch[SUMSQ_OFF + i];  // fixed order: thread t takes partials t, t + 256
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
+  if (threadIdx.x != 0) return;
+  scratch[1] = red[0];
+  const bool bad = !(sqrtf(scratch[1]) <= 3.0e38f);
+  scratch[2] = bad ? 1.f : 0.f;
+  // the dynamic loss-scale multiplier must be a power of two in [2^-24, 1]; anything else (uninitialised scratch of a caller written against
+  // the old contract, a stray value in (0,1]) reads as 1
+  float m = scratch[4]; { int e; if (!(m >= 5.9604645e-8f && m <= 1.f && frexpf(m, &e) == 0.5f)) m = 1.f; }
+  if (bad) { scratch[3] += 1.f; m = fmaxf(m * 0.5f, 5.9604645e-8f); scratch[5] = 0.f; }
+  else if (m < 1.f) { scratch[5] += 1.f; if (scratch[5] >= 200.f) { m = fminf(2.f * m, 1.f); scratch[5] = 0.f; } }
+  scratch[4] = m;
+}
+void k_adamw(spa3d_ctx* c, float* p, const float* g, float* m, float* v, int64_t n, float lr, int64_t step, float clip, float b1, float b2,
+             float eps, float wd, float* scratch) {
+  (void)hipMemsetAsync(scratch, 0, 12, c->stream);
+  unsigned gr = (unsigned)std::min<int64_t>(cdiv(n, 256), 4096);
+  const unsigned gs = (unsigned)std::min<int64_t>(cdiv(n, 256), SUMSQ_MAXB);
+  sumsq_kernel<<<gs, 256, 0, c->stream>>>(g, n, scratch + SUMSQ_OFF);
+  adamw_guard_kernel<<<1, 256, 0, c->stream>>>(scratch, (int)gs);
+  adamw_kernel<<<gr, 256, 0, c->stream>>>(p, g, m, v, n, lr, (float)(step + 1), clip, b1, b2, eps, wd, scratch);
+  SPA_LAUNCH_CHECK(c);
+}
+
+// ---------------------------------------------------------------------------------------------
+// jax.random.uniform(PRNGKey(k0,k1), [n]) legacy threefry layout
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t rotl32(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
+__device__ void threefry2x32(uint32_t k0, uint32_t k1, uint32_t& x0, uint32_t& x1) {
+  const uint32_t ks[3] = {k0, k1, k0 ^ k1 ^ 0x1BD11BDAu};
+  const int R[2][4] = {{13, 15, 26, 6}, {17, 29, 16, 24}};
+  x0 += ks[0]; x1 += ks[1];
+#pragma unroll
+  for (int i = 0; i < 5; ++i) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { x0 += x1; x1 = rotl32(x1, R[i & 1][j]); x1 ^= x0; }
+    x0 += ks[(i + 1) % 3]; x1 += ks[(i + 2) % 3] + (uint32_t)(i + 1);
+  }
+}
+__global__ void uniform_noise_kernel(float* __restrict__ out, int64_t n, int64_t half, uint32_t k0, uint32_t k1) {
+  for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < half; j += (int64_t)gridDim.x * 256) {
+    uint32_t x0 = (uint32_t)j, x1 = (uint32_t)(half + j);
+    threefry2x32(k0, k1, x0, x1);
+    out[j] = __uint_as_float((x0 >> 9) | 0x3F800000u) - 1.0f;
+    if (half + j < n) out[half + j] = __uint_as_float((x1 >> 9) | 0x3F800000u) - 1.0f;
+  }
+}
+void k_uniform_noise(spa3d_ctx* c, float* out, int64_t n, uint32_t k0, uint32_t k1) {
+  if (c->dry || n == 0) return;
+  int64_t half = (n + (n & 1)) / 2;
+  uniform_noise_kernel<<<GRID1D(half, 256), 256, 0, c->stream>>>(out, n, half, k0, k1); SPA_LAUNCH_CHECK(c);
+}
+// deterministic mode: fold the fixed-point shadow of a range of the gradient buffer into it (and clear the shadow: a later flush of the same range adds nothing).
+// A sum of 2^62 units or more is overflow (common.hpp DetCfg): NaN, like the sticky flag -- a wrapped sum must never reach the buffer as a finite value.
+__global__ __launch_bounds__(256) void det_flush_kernel(const DetCfg* __restrict__ det, int64_t lo, int64_t n) {
+  const DetCfg d = *det;
+  float* __restrict__ g = d.gbase + lo;
+  long long* __restrict__ shadow = d.shadow + lo;
+  const bool bad = *d.flag != 0;
+  const double inv = 1.0 / (double)d.scale;   // a power of two: exact
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const long long q = shadow[i];
+    if (q != 0 || bad) {
+      const bool ovf = bad || q >= DET_SUM_MAX || q <= -DET_SUM_MAX;
+      g[i] = ovf ? __int_as_float(0x7fc00000) : g[i] + (float)((double)q * inv); shadow[i] = 0;
+    }
+  }
+}
+void k_det_flush(spa3d_ctx* c, int64_t lo, int64_t n) {
+  if (c->dry || n <= 0) return;
+  det_flush_kernel<<<(unsigned)std::min<int64_t>(cdiv(n, 256), 8192), 256, 0, c->stream>>>(c->det, lo, n); SPA_LAUNCH_CHECK(c);
+}
+// the fixed-point unit of a det_grads call (common.hpp DetCfg): 2^(32 + e), e = floor(log2(denom / (n_vis * loss scale))) clamped to [-24, 40].  Inputs are the call's
+// global denominator, its own visible count and its loss scale, so the unit is a function of the call's inputs alone (bit-equal run to run and whatever the
+// all-reduce schedule).  -24 covers the fp16 mode at BASELINE configs[2] (e ~ -14); below it the unit stops coarsening and the range guards take over.
+// Writes the call's DetCfg, with the unit as its scale, where the call's kernels read it.
+__global__ void det_unit_kernel(const float* sums, const unsigned* poison, const float* denom_dev, const float* scale_dev, DetCfg d, DetCfg* out) {
+  const float nvis = fmaxf(loss_acc_read((const unsigned long long*)sums + 2, poison), 1.f);   // fmaxf(NaN, 1) = 1
+  const float r = *denom_dev / (nvis * (scale_dev ? *scale_dev : 1.f));
+  int e = 0;
+  if (r > 0.f && r <= 3.0e38f) { (void)frexpf(r, &e); e = min(max(e - 1, DET_E_MIN), DET_E_MAX); }   // r = m 2^e', m in [0.5, 1): floor(log2 r) = e' - 1, exactly
+  d.scale = ldexpf(1.f, 32 + e);
+  *out = d;
+}
+void k_det_unit(spa3d_ctx* c, const float* sums, const unsigned* poison, const float* denom_dev, const float* scale_dev, const DetCfg& d, DetCfg* out) {
+  if (c->dry) return;
+  det_unit_kernel<<<1, 1, 0, c->stream>>>(sums, poison, denom_dev, scale_dev, d, out); SPA_LAUNCH_CHECK(c);
+}
+
+// ---------------------------------------------------------------------------------------------
+// explicit instantiations
+// ---------------------------------------------------------------------------------------------
+#define INST_LOSS(T) \
+  template void k_loss_bwd<T>(spa3d_ctx*, const float*, int64_t, int, const float*, const float*, const float*, float, float, T*, int, const float*);
+INST_LOSS(float)
+INST_LOSS(bf16_t)
+}  // namespace SPA_NS

@@ -26,23 +26,6 @@ struct RunArgs {
 };
 
 namespace SPA_NS {
-template <typename T>
-void attention_fwd(spa3d_ctx* c, const T* q, const T* k, const T* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq,
-                   const float* sk, const float* km, int64_t nseq, int Sq, int Sk, int H, int Dh, T* o, float* lse, int impl,
-                   const int32_t* seq_off = nullptr, int64_t total_rows = 0);
-template <typename T>
-void attention_bwd(spa3d_ctx* c, const T* q, const T* k, const T* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq,
-                   const float* sk, const float* km, int64_t nseq, int Sq, int Sk, int H, int Dh, const T* o, const float* lse, const T* d_o,
-                   T* dq, T* dk, T* dv, float* dsq, float* dsk, int impl, const int32_t* seq_off = nullptr, int64_t total_rows = 0);
-
-template <typename T>
-void attention_varlen_fwd(spa3d_ctx* c, const T* q, const T* k, const T* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq, const float* sk,
-                          int64_t nseq, int Sq, const int32_t* koff_host, const int32_t* koff_dev, int H, int Dh, T* o, float* lse, int impl);
-template <typename T>
-void attention_varlen_bwd(spa3d_ctx* c, const T* q, const T* k, const T* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq, const float* sk,
-                          int64_t nseq, int Sq, const int32_t* koff_host, const int32_t* koff_dev, int H, int Dh, const T* o, const float* lse,
-                          const T* d_o, T* dq, T* dk, T* dv, float* dsq, float* dsk, int impl);
-
 static const float L1_WEIGHT = 5000.0f, BCE_WEIGHT = 1e-8f;  // train.py:96
 
 // ---------------------------------------------------------------------------------------------
@@ -79,7 +62,7 @@ template <typename T> struct BlockStash {
 
 // Readout block 1 (track_autoencoder_3d.py:276-285): rows 1.. of the sequence of query (b, q) depend on (b, query frame) only, so LayerNorm 1 and
 // the QKV projection (forward, dW, dX, LN backward) run once per "slot" = distinct (sample, frame) pair and are expanded to / reduced
-// from the per-query rows through the slot index (kernels.hip "Shared latent rows"); the block's dx carries a slot's LN-backward term on
+// from the per-query rows through the slot index (rows.hip "Shared latent rows"); the block's dx carries a slot's LN-backward term on
 // the slot's first sequence only (consumers sum over the queries of a sample).  xU = [nslot * (S-1) latent rows | one row 0 per
 // sequence].  Same values as the dense computation up to summation order (dqkv rows of a slot are pre-summed in fp32).
 template <typename T> struct Share {
@@ -1045,7 +1028,7 @@ void run_body(spa3d_ctx* c, const RunArgs& a, int Bc) {
   Net<T> net(c, a.P, a.G);
   net.pack();
   float* sums = net.template alloc<float>(10);
-  float* denom_dev = sums + 6;  // [0..5] three 64-bit fixed-point accumulators (kernels.hip loss_acc_add), [6] denominator, [7] loss scale, [8] sticky non-finite flag
+  float* denom_dev = sums + 6;  // [0..5] three 64-bit fixed-point accumulators (loss.hip loss_acc_add), [6] denominator, [7] loss scale, [8] sticky non-finite flag
   unsigned* poison = (unsigned*)(sums + 8);
   k_zero(c, sums, 40);
   const float* noise = b->noise;

@@ -4,7 +4,7 @@
 //
 // One row = one query track of T frames: predictions p[t][c], visibility logit l[t], targets g[t][c], target visibility y[t] in {0, 1},
 // NC = 3 coordinates (2 for the 2-D model), K <= 8 distance thresholds tau_k, each multiplied by the row's sample scale.  Per frame, fp32:
-//   e1  = sum_c |p - g|            the training loss's L1, summed in the order of head_loss_fwd_kernel (kernels.hip)
+//   e1  = sum_c |p - g|            the training loss's L1, summed in the order of head_loss_fwd_kernel (loss.hip)
 //   e2  = sqrtf(sum_c (p - g)^2)   Euclidean distance
 //   pv  = l > 0, vis = y > 0.5
 //   bce = -y log_sigmoid(l) - (1 - y) log_sigmoid(-l), the expression of head_loss_fwd_kernel

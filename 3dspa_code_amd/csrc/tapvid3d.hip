@@ -25,8 +25,6 @@ struct TvArgs {
 
 namespace SPA_NS {
 
-static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
 __global__ __launch_bounds__(256) void tv_ratio_kernel(const TvArgs a) {
   const int lane = threadIdx.x & 63;
   const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);

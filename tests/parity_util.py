@@ -218,7 +218,7 @@ def linear_bound(A, B, bias, R, act, ref64, pre64, out_dtype):
 
 # ------------------------------------------------------------------------------------------------ LayerNorm
 def layernorm_restated(x, scale, dy, dtype):
-  """The LayerNorm kernels' arithmetic (csrc/kernels.hip: mean and E[x^2] - mean^2 clamped at 0, eps 1e-6, r = rsqrt; dx = r (g - mean(g) - xhat mean(g xhat)),
+  """The LayerNorm kernels' arithmetic (csrc/layernorm.hip: mean and E[x^2] - mean^2 clamped at 0, eps 1e-6, r = rsqrt; dx = r (g - mean(g) - xhat mean(g xhat)),
   g = dy scale; dscale = sum over rows of dy xhat) in `dtype` on the host: float32 restates the kernels, float64 is the reference.  -> (y, dx, dscale)"""
   x, scale, dy = x.to(dtype), scale.to(dtype), dy.to(dtype)
   d = x.shape[1]
@@ -445,14 +445,14 @@ def attention_grad_gates(gates, got, emu, ref, H, Dh):
 # ------------------------------------------------------------------------------------------------ generic 16-bit attention composition: host emulation
 def emulate_attention_generic(q, k, v, sq, sk, km, H, Dh, d_o):
   """The generic composition in a 16-bit type (csrc/attention.hip:42-129: GEMM + row kernels, every intermediate stored in 16 bits), sums exact and rounded once:
-    * q^, k^ = 16-bit(x r scale) (rms_heads_fwd_kernel, csrc/kernels.hip:426-432);
+    * q^, k^ = 16-bit(x r scale) (rms_heads_fwd_kernel, csrc/attention.hip);
     * S = 16-bit(alpha fp32 sum q^ k^) (scores(), attention.hip:31-40, alpha = 1 / sqrtf(Dh) in the GEMM epilogue);
-    * P = 16-bit(exp(S - max) / sum) in fp32 on the stored S, a masked key read as finfo.min (softmax_kernel, kernels.hip:497-515);
+    * P = 16-bit(exp(S - max) / sum) in fp32 on the stored S, a masked key read as finfo.min (softmax_kernel, attention.hip);
     * o = 16-bit(fp32 sum P v) (attention.hip:61-66);
     * dP = 16-bit(fp32 sum dO v) (attention.hip:96-102), dv = 16-bit(fp32 sum P dO) (103-109);
-    * dS = 16-bit(P (dP - fp32 sum(P dP))), 0 for a masked key (softmax_bwd_kernel, kernels.hip:536-544);
+    * dS = 16-bit(P (dP - fp32 sum(P dP))), 0 for a masked key (softmax_bwd_kernel, attention.hip);
     * dq^ = 16-bit(alpha fp32 sum dS k^), dk^ = 16-bit(alpha fp32 sum dS q^) (attention.hip:111-124);
-    * dq, dk = 16-bit(r (g - xh mean(g xh))), g = dq^ scale, and dscale += dq^ xh in fp32 (rms_heads_bwd_kernel, kernels.hip:457-472).
+    * dq, dk = 16-bit(r (g - xh mean(g xh))), g = dq^ scale, and dscale += dq^ xh in fp32 (rms_heads_bwd_kernel, attention.hip).
   -> (o, dq, dk, dv in the 16-bit type, dsq, dsk fp32 [Dh])"""
   dt = q.dtype
   nseq, Sq, _ = q.shape

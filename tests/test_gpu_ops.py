@@ -113,7 +113,7 @@ def test_linear_bwd_generic(lib, dtype, M, N, K):
 @pytest.mark.parametrize('dtype', [F32, BF16])
 @pytest.mark.parametrize('d', [384, 512, 1152, 1280, 48, 768, 1024, 2048, 100])
 def test_layernorm_fwd_bwd(lib, dtype, d):
-  """Which kernel a width reaches (k_layernorm / k_layernorm_bwd in csrc/kernels.hip; forward and backward dispatch alike; V = 4 elements per 16-byte load in
+  """Which kernel a width reaches (k_layernorm / k_layernorm_bwd in csrc/layernorm.hip; forward and backward dispatch alike; V = 4 elements per 16-byte load in
   fp32, 8 in the 16-bit types; the vectorised kernels take V | d <= 256 V with aligned pointers, in ceil(d / 64 V) steps):
     fp32    48, 100 -> vec, 1 step | 384, 512 -> vec, 2 steps | 768 -> vec, 3 steps | 1024 -> vec, 4 steps | 1152, 1280, 2048 -> plain
     16-bit  384 -> part<16, 3> | 1280 -> part<32, 5> | 48, 512 -> vec, 1 step | 768, 1024 -> vec, 2 steps | 1152 -> vec, 3 steps | 2048 -> vec, 4 steps |

@@ -297,7 +297,7 @@ def test_split_pass_attention_backward_in_model_ragged_and_bit_reproducible_loss
   (l1, g1), (l4, g4) = runs[2], runs[mode]
   worst = max((rel_err(g4[k], g1[k]), k) for k in g1 if float(g1[k].double().norm()) > 1e-12)
   print(f'attention impl {mode} (split-pass backward) vs 2 in-model (ragged, fp16): loss {l4} vs {l1}; worst gradient leaf {worst}')
-  assert l4 == l1  # the forward is the same code, and the loss sums are order-independent fixed-point accumulations (kernels.hip loss_acc_add)
+  assert l4 == l1  # the forward is the same code, and the loss sums are order-independent fixed-point accumulations (loss.hip loss_acc_add)
   assert all(bool(torch.isfinite(v).all()) for v in g4.values())
   assert worst[0] < 0.04
 
