@@ -44,6 +44,12 @@ class Scores(C.Structure):
               ('sample_stats', C.c_void_p), ('frame_err', C.c_void_p)]
 
 
+class LossConfig(C.Structure):
+  """spa3d_loss_config (include/spa3d.h): eight 4-byte fields, 32 bytes."""
+  _fields_ = [('l1_weight', C.c_float), ('bce_weight', C.c_float), ('position_kind', C.c_int32), ('huber_delta', C.c_float),
+              ('axis_weight', C.c_float * 3), ('bce_pos_weight', C.c_float)]
+
+
 class TapVid3D(C.Structure):
   """spa3d_tapvid3d (include/spa3d.h): the scaling mode, the threshold table switch, then device pointers."""
   _fields_ = [('scaling', C.c_int32), ('fixed_thresholds', C.c_int32), ('intrinsics', C.c_void_p), ('query_stats', C.c_void_p),
@@ -98,6 +104,9 @@ _SIGS = {
     'spa3d_set_option': (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
     'spa3d_set_loss_scale_state': (C.c_int, [C.c_void_p, C.c_void_p]),
     'spa3d_set_counts': (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    'spa3d_set_loss': (C.c_int, [C.c_void_p, C.POINTER(LossConfig)]),
+    'spa3d_get_loss': (C.c_int, [C.c_void_p, C.POINTER(LossConfig)]),
+    'spa3d_set_point_weights': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     'spa3d_grad_segments': (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     'spa3d_set_grad_events': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     'spa3d_grad_events_recorded': (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),

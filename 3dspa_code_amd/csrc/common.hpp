@@ -10,6 +10,7 @@
 #include "ablate.inc"  // every work-skipping diagnostic mask, all 0 in libspa3d_hip.so
 #include "gemm_plan.hpp"  // GemmDesc and the kernel choice (host-only)
 #include "score_row.hpp"  // per-track score arithmetic (host- and device-callable)
+#include "loss_point.hpp"  // the training objective at one point (host- and device-callable)
 
 // One translation unit is compiled for exactly ONE 16-bit activation type: bf16 (default) or IEEE fp16 (-DSPA_F16=1, BASELINE
 // cfg#5).  The raw 16-bit storage type is `bf16_t` (unsigned short) in both builds; what differs -- the two conversions, the MFMA
@@ -31,8 +32,9 @@ typedef unsigned short bf16_t;  // raw 16-bit pattern (bf16, or fp16 in the SPA_
 // det_grads train call writes its DetCfg into its own workspace (k_det_unit) and passes a pointer to it (spa3d_ctx::det) to every kernel that adds into the gradient
 // buffer; nullptr = float atomics.  (A pointer, not the struct by value: kernel arguments are loaded at kernel entry, so the fields would stay live in SGPRs
 // through the main loops -- SGPR spills in the LayerNorm backward, more VGPRs in the single-query attention backward; the struct is read where it is used.)
-// Unit: one integer step is 1 / scale of the buffer's value, scale = 2^(32 + e) with e = floor(log2(denom / (n_vis * loss scale))) clamped to [DET_E_MIN, DET_E_MAX]
-// (k_det_unit: a power of two, so the flush is exact; a gradient of this call scales as n_vis * loss scale / denom).  At a real batch n_vis ~ denom, so the unit is
+// Unit: one integer step is 1 / scale of the buffer's value, scale = 2^(32 + e) with e = floor(log2(denom / (n_vis * loss scale))) - floor(log2(gmax / 5000)) clamped to
+// [DET_E_MIN, DET_E_MAX] (k_det_unit: a power of two, so the flush is exact; a gradient of this call scales as gmax * n_vis * loss scale / denom, gmax = the objective's
+// largest head gradient per unit point weight, 5000 by default: the second term is then 0).  At a real batch n_vis ~ denom, so the unit is
 // 2^-32 as it always was (2^-(32 + log2 ranks) data-parallel); it only gets finer when the denominator exceeds the call's own visible count.  Range: an addend of
 // 2^55 units or more (or a NaN) sets the sticky flag instead of being added; a shadow sum of 2^62 units or more is taken as overflow by det_flush -- both flush NaN,
 // never a wrapped finite value.  2^62 / 2^55 = 128 addends at the bound fit; a sum can only wrap past the flush check with 384 or more addends all near the bound.
@@ -224,6 +226,13 @@ struct Prof {
   }
 };
 
+inline spa3d_loss_config loss_config_defaults() {  // train.py:96
+  spa3d_loss_config d;
+  d.l1_weight = 5000.0f; d.bce_weight = 1e-8f; d.position_kind = SPA3D_POS_L1; d.huber_delta = 1.f;
+  d.axis_weight[0] = d.axis_weight[1] = d.axis_weight[2] = 1.f; d.bce_pos_weight = 1.f;
+  return d;
+}
+
 struct spa3d_ctx {
   spa3d_config cfg;
   std::vector<Leaf> leaves;
@@ -255,6 +264,11 @@ struct spa3d_ctx {
   const DetCfg* det = nullptr;  // the running det_grads train call's mode, in its workspace, passed to every kernel that adds into G; nullptr = float atomics
   // spa3d_set_counts: per-sample live support tracks / live queries of the next calls' batch (host copies; cnt_B entries each)
   std::vector<int32_t> cnt_n, cnt_q; bool has_cnt_n = false, has_cnt_q = false; int cnt_B = 0;
+  // spa3d_set_loss: the objective of spa3d_loss_and_grads / spa3d_loss, with what follows from it -- gmax = max(l1_weight * max_c a_c, bce_weight * max(1, beta)),
+  // the head gradient's bound per unit point weight (fp16 automatic loss scale), and gshift = floor(log2(gmax / 5000)) (det_grads unit)
+  spa3d_loss_config loss = loss_config_defaults(); float loss_gmax = 5000.f; int loss_gshift = 0;
+  // spa3d_set_point_weights: caller-owned device plane [B,Q,T_out] of the next calls' batch (null = every weight 1) and the B, Q it was stated for
+  const float* pt_w = nullptr; int pt_B = 0, pt_Q = 0;
   int poison = 0;         // spa3d_set_option "poison": NaN-fill the workspace before every chunk and every op output before its launch (tests)
   Prof prof;
 };
@@ -292,6 +306,13 @@ template <typename F> inline int sized_call(spa3d_ctx* c, const char* what, int6
 inline bool counts_fit_batch(spa3d_ctx* c, int B) {
   if (c->cnt_B == B) return true;
   c->err = "counts were set for B = " + std::to_string(c->cnt_B) + ", this batch has B = " + std::to_string(B);
+  return false;
+}
+// spa3d_set_point_weights against a batch of B samples of Q queries: false with c->err set when the plane was stated for another shape
+inline bool weights_fit_batch(spa3d_ctx* c, int B, int Q) {
+  if (!c->pt_w || (c->pt_B == B && c->pt_Q == Q)) return true;
+  c->err = "point weights were set for B = " + std::to_string(c->pt_B) + ", Q = " + std::to_string(c->pt_Q) + ", this batch has B = " + std::to_string(B) +
+           ", Q = " + std::to_string(Q);
   return false;
 }
 // The live-query counts [B] of a handle that has them (c->has_cnt_q), checked against a batch of B samples of Q queries; null with c->err
@@ -456,17 +477,18 @@ template <typename T> void k_attn_q1_bwd(spa3d_ctx*, const T* q0, int64_t ldq0, 
 // loss.hip
 void k_discretize(spa3d_ctx*, const float* lat, const float* noise, int discretize, float* out, float* clipmask, int64_t n);
 void k_loss_fwd(spa3d_ctx*, const float* head, int64_t nq, int T_, const float* tgt, const float* tvis, float* tracks, float* vlog,
-                float* clog, float* sums, unsigned* poison, int NC = 3);
+                float* clog, float* sums, unsigned* poison, int NC, const spa3d_loss_config& lc, const float* wgt);
 void k_loss_from_preds(spa3d_ctx*, const float* tracks, const float* vlog, int64_t n, const float* tgt, const float* tvis, float* sums,
-                       unsigned* poison, int NC = 3);
+                       unsigned* poison, int NC, const spa3d_loss_config& lc, const float* wgt);
 void k_score_rows(spa3d_ctx*, const ScoreArgs& a);
 void k_score_reduce(spa3d_ctx*, const float* qstats, int64_t B, int Q, int K, double* out /*[B][8 + 4K]*/);
 void k_vis_count(spa3d_ctx*, const float* tvis, int64_t n, float* out, unsigned* poison);
 void k_set_denom(spa3d_ctx*, const float* sums, const unsigned* poison, float denom_host, float* denom_dev);
 void k_loss_finalize(spa3d_ctx*, const float* sums, const unsigned* poison, const float* denom_dev, float l1w, float bcew, float* loss3);
 template <typename T> void k_loss_bwd(spa3d_ctx*, const float* head, int64_t nq, int T_, const float* tgt, const float* tvis,
-                                      const float* denom_dev, float l1w, float bcew, T* dhead, int NC = 3, const float* scale_dev = nullptr);
-void k_set_loss_scale(spa3d_ctx*, const float* denom_dev, float l1w, float setting, float* scale_dev);
+                                      const float* denom_dev, const spa3d_loss_config& lc, const float* wgt, T* dhead, int NC = 3,
+                                      const float* scale_dev = nullptr);
+void k_set_loss_scale(spa3d_ctx*, const float* denom_dev, float gmax, float setting, float* scale_dev);
 void k_unscale(spa3d_ctx*, float* a, const float* scale_dev, int64_t n);
 void k_adamw(spa3d_ctx*, float* p, const float* g, float* m, float* v, int64_t n, float lr, int64_t step, float clip, float b1, float b2,
              float eps, float wd, float* scratch);
@@ -474,6 +496,6 @@ void k_uniform_noise(spa3d_ctx*, float* out, int64_t n, uint32_t k0, uint32_t k1
 // over [lo, lo + n) of c->det: g[i] += shadow[i] / scale; shadow[i] = 0; NaN when *flag or |shadow[i]| >= 2^62
 void k_det_flush(spa3d_ctx* c, int64_t lo, int64_t n);
 // *out = d with the call's unit as its scale (DetCfg unit rule)
-void k_det_unit(spa3d_ctx*, const float* sums, const unsigned* poison, const float* denom_dev, const float* scale_dev, const DetCfg& d, DetCfg* out);
+void k_det_unit(spa3d_ctx*, const float* sums, const unsigned* poison, const float* denom_dev, const float* scale_dev, int gshift, const DetCfg& d, DetCfg* out);
 }  // namespace SPA_NS
 using namespace SPA_NS;  // one 16-bit type per translation unit

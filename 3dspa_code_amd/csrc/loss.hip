@@ -35,7 +35,11 @@ void k_discretize(spa3d_ctx* c, const float* lat, const float* noise, int discre
 // D8 head split + compute_loss_3d (track_autoencoder_3d.py:289-301, train.py:96-129)
 // head[q][c*T+t], c<3 coords (coordinate-major), c==3 visibility logit
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float log_sigmoid_f(float x) { return fminf(x, 0.f) - log1pf(expf(-fabsf(x))); }
+// The objective is configurable per handle (spa3d_loss_config, include/spa3d.h): position term L1 or Huber with per-axis weights, BCE with a
+// positive-class weight, and an optional per-point weight plane w[q][t] addressed like the visibility targets (null = 1).  The arithmetic of
+// one point is loss_point.hpp; the numerators are P = sum w y e and V = sum w v, the denominator stays the unweighted visible count.
+// (The axis weight is picked by selects: indexing the by-value argument with a per-thread index would move it to scratch memory.)
+__device__ __forceinline__ float loss_axis(const spa3d_loss_config& lc, int c) { return c == 0 ? lc.axis_weight[0] : (c == 1 ? lc.axis_weight[1] : lc.axis_weight[2]); }
 // The loss numerators and the visible count are summed over the whole batch by thousands of workgroups.  Float atomics make that sum depend
 // on arrival order (the same batch gave 14089.21875 and 14089.216796875 in round 3), so two data-parallel replicas could log different
 // losses and a test could not ask for bit-equal reruns.  Each workgroup reduces in a fixed order and adds its partial as a 64-bit FIXED-POINT
@@ -55,7 +59,8 @@ __device__ __forceinline__ float loss_acc_read(const unsigned long long* acc, co
 }
 __global__ __launch_bounds__(256) void head_loss_fwd_kernel(const float* __restrict__ head, int64_t nq, int T_, const float* __restrict__ tgt,
                                                             const float* __restrict__ tvis, float* __restrict__ tracks,
-                                                            float* __restrict__ vlog, float* __restrict__ clog, float* __restrict__ sums, unsigned* poison, int NC) {
+                                                            float* __restrict__ vlog, float* __restrict__ clog, float* __restrict__ sums, unsigned* poison, int NC,
+                                                            const spa3d_loss_config lc, const float* __restrict__ wgt) {
   // head row: NC coordinate blocks of T, then the visibility logits; the 2-D model (NC == 2) has a 4th block: certainty logits
   __shared__ float red[3][4];
   float pn = 0.f, bn = 0.f;
@@ -68,14 +73,14 @@ __global__ __launch_bounds__(256) void head_loss_fwd_kernel(const float* __restr
     for (int cdx = 0; cdx < NC; ++cdx) {
       const float pv = hr[cdx * T_ + t];
       if (tracks) tracks[i * NC + cdx] = pv;
-      if (tgt) perr += fabsf(pv - tgt[i * NC + cdx]);
+      if (tgt) perr += loss_axis(lc, cdx) * loss_pos_value(lc.position_kind, lc.huber_delta, pv - tgt[i * NC + cdx]);
     }
     if (vlog) vlog[i] = lg;
     if (clog) clog[i] = NC == 2 ? hr[3 * T_ + t] : 0.f;  // 3DSPA: certain_logits = zeros (3d:301); TRAJAN: real head (ta:344)
     if (tgt) {
-      float y = tvis[i];
-      pn += perr * y;
-      bn += -y * log_sigmoid_f(lg) - (1.f - y) * log_sigmoid_f(-lg);
+      const float y = tvis[i], w = wgt ? wgt[i] : 1.f;
+      pn += perr * y * w;
+      bn += loss_vis_value(lc.bce_pos_weight, y, lg) * w;
     }
   }
   if (!tgt) return;
@@ -89,23 +94,24 @@ __global__ __launch_bounds__(256) void head_loss_fwd_kernel(const float* __restr
   }
 }
 void k_loss_fwd(spa3d_ctx* c, const float* head, int64_t nq, int T_, const float* tgt, const float* tvis, float* tracks, float* vlog,
-                float* clog, float* sums, unsigned* poison, int NC) {
+                float* clog, float* sums, unsigned* poison, int NC, const spa3d_loss_config& lc, const float* wgt) {
   if (c->dry || nq == 0) return;
   unsigned g = (unsigned)std::min<int64_t>(cdiv(nq * T_, 256), 4096);
-  head_loss_fwd_kernel<<<g, 256, 0, c->stream>>>(head, nq, T_, tgt, tvis, tracks, vlog, clog, sums, poison, NC);
+  head_loss_fwd_kernel<<<g, 256, 0, c->stream>>>(head, nq, T_, tgt, tvis, tracks, vlog, clog, sums, poison, NC, lc, wgt);
   SPA_LAUNCH_CHECK(c);
 }
 // same numerators from already-split predictions (spa3d_loss entry point)
 __global__ __launch_bounds__(256) void loss_from_preds_kernel(const float* __restrict__ tracks, const float* __restrict__ vlog, int64_t n,
-                                                              const float* __restrict__ tgt, const float* __restrict__ tvis, float* sums, unsigned* poison, int NC) {
+                                                              const float* __restrict__ tgt, const float* __restrict__ tvis, float* sums, unsigned* poison, int NC,
+                                                              const spa3d_loss_config lc, const float* __restrict__ wgt) {
   __shared__ float red[2][4];
   float pn = 0.f, bn = 0.f;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    float y = tvis[i], lg = vlog[i];
+    const float y = tvis[i], lg = vlog[i], w = wgt ? wgt[i] : 1.f;
     float perr = 0.f;
-    for (int cdx = 0; cdx < NC; ++cdx) perr += fabsf(tracks[i * NC + cdx] - tgt[i * NC + cdx]);
-    pn += perr * y;
-    bn += -y * log_sigmoid_f(lg) - (1.f - y) * log_sigmoid_f(-lg);
+    for (int cdx = 0; cdx < NC; ++cdx) perr += loss_axis(lc, cdx) * loss_pos_value(lc.position_kind, lc.huber_delta, tracks[i * NC + cdx] - tgt[i * NC + cdx]);
+    pn += perr * y * w;
+    bn += loss_vis_value(lc.bce_pos_weight, y, lg) * w;
   }
   pn = wave_sum(pn); bn = wave_sum(bn);
   const int w = threadIdx.x >> 6;
@@ -117,10 +123,10 @@ __global__ __launch_bounds__(256) void loss_from_preds_kernel(const float* __res
   }
 }
 void k_loss_from_preds(spa3d_ctx* c, const float* tracks, const float* vlog, int64_t n, const float* tgt, const float* tvis, float* sums,
-                       unsigned* poison, int NC) {
+                       unsigned* poison, int NC, const spa3d_loss_config& lc, const float* wgt) {
   if (c->dry || n == 0) return;
   unsigned g = (unsigned)std::min<int64_t>(cdiv(n, 256), 4096);
-  loss_from_preds_kernel<<<g, 256, 0, c->stream>>>(tracks, vlog, n, tgt, tvis, sums, poison, NC);
+  loss_from_preds_kernel<<<g, 256, 0, c->stream>>>(tracks, vlog, n, tgt, tvis, sums, poison, NC, lc, wgt);
   SPA_LAUNCH_CHECK(c);
 }
 // ---------------------------------------------------------------------------------------------
@@ -233,23 +239,25 @@ void k_loss_finalize(spa3d_ctx* c, const float* sums, const unsigned* poison, co
   if (c->dry) return;
   loss_finalize_kernel<<<1, 1, 0, c->stream>>>(sums, poison, denom_dev, l1w, bcew, loss3); SPA_LAUNCH_CHECK(c);
 }
-// d head: l1w*sign(pred-tgt)*vis/denom ; bcew*(sigmoid(l)-y)/denom ; sign(0)=0
+// d head (include/spa3d.h "Head cotangent"): l1w * w * y * a_c * rho'(pred - tgt) / denom ; bcew * w * v'(l) / denom.
+// Default configuration, no weight plane: l1w*sign(pred-tgt)*vis/denom ; bcew*(sigmoid(l)-y)/denom ; sign(0)=0, in that order of operations.
 template <typename T>
 __global__ void loss_bwd_kernel(const float* __restrict__ head, int64_t nq, int T_, const float* __restrict__ tgt,
-                                const float* __restrict__ tvis, const float* __restrict__ denom_dev, float l1w, float bcew, T* __restrict__ dhead,
-                                int NC, const float* __restrict__ scale_dev) {
+                                const float* __restrict__ tvis, const float* __restrict__ denom_dev, const spa3d_loss_config lc,
+                                const float* __restrict__ wgt, T* __restrict__ dhead, int NC, const float* __restrict__ scale_dev) {
   const float inv = (scale_dev ? *scale_dev : 1.f) / *denom_dev;  // scale_dev: the fp16 mode's loss scale (a power of two)
   const int64_t n = nq * 4 * T_;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     int64_t q = i / (4 * T_); int j = (int)(i - q * 4 * T_);
     int cc = j / T_, t = j - cc * T_;
     float y = tvis[q * T_ + t], g;
+    const float w = (wgt && cc <= NC) ? wgt[q * T_ + t] : 1.f;
     if (cc < NC) {
       float df = head[i] - tgt[(q * T_ + t) * NC + cc];
-      g = l1w * (df > 0.f ? 1.f : (df < 0.f ? -1.f : 0.f)) * y * inv;
+      g = lc.l1_weight * (loss_axis(lc, cc) * loss_pos_deriv(lc.position_kind, lc.huber_delta, df)) * y * w * inv;
     } else if (cc == NC) {
       float l = head[i];
-      g = bcew * (1.f / (1.f + expf(-l)) - y) * inv;
+      g = lc.bce_weight * loss_vis_deriv(lc.bce_pos_weight, y, l) * w * inv;
     } else {
       g = 0.f;  // TRAJAN's certainty head carries no loss term in compute_loss_2d (train.py:60-93)
     }
@@ -257,27 +265,28 @@ __global__ void loss_bwd_kernel(const float* __restrict__ head, int64_t nq, int 
   }
 }
 template <typename T>
-void k_loss_bwd(spa3d_ctx* c, const float* head, int64_t nq, int T_, const float* tgt, const float* tvis, const float* denom_dev, float l1w,
-                float bcew, T* dhead, int NC, const float* scale_dev) {
+void k_loss_bwd(spa3d_ctx* c, const float* head, int64_t nq, int T_, const float* tgt, const float* tvis, const float* denom_dev,
+                const spa3d_loss_config& lc, const float* wgt, T* dhead, int NC, const float* scale_dev) {
   if (c->dry || nq == 0) return;
-  loss_bwd_kernel<T><<<GRID1D(nq * 4 * T_, 256), 256, 0, c->stream>>>(head, nq, T_, tgt, tvis, denom_dev, l1w, bcew, dhead, NC, scale_dev);
+  loss_bwd_kernel<T><<<GRID1D(nq * 4 * T_, 256), 256, 0, c->stream>>>(head, nq, T_, tgt, tvis, denom_dev, lc, wgt, dhead, NC, scale_dev);
   SPA_LAUNCH_CHECK(c);
 }
 // Loss scale of the 16-bit backward (fp16 mode).  setting > 0: that value.  setting < 0: automatic -- the largest power of two that keeps
-// the head gradient's magnitude l1w / denom at or below |setting| (16): activations' gradients then sit mid-range in fp16 for any batch
+// the head gradient's magnitude gmax / denom at or below |setting| (16; gmax = the configured objective's largest head gradient per unit
+// point weight, spa3d_loss_config: 5000 by default): activations' gradients then sit mid-range in fp16 for any batch
 // size (at BASELINE cfg#3, denom = 4.4 M: 8192; a 100-element toy batch: 1).
 // `state` (may be null): the caller's dynamic-scale state, state[0] = a power-of-two multiplier in (0, 1] that spa3d_adamw_step halves after
 // a step with a non-finite gradient norm and grows back after 200 finite ones (0 or garbage-free zero memory = 1).
-__global__ void set_loss_scale_kernel(const float* __restrict__ denom_dev, float l1w, float setting, const float* __restrict__ state,
+__global__ void set_loss_scale_kernel(const float* __restrict__ denom_dev, float gmax, float setting, const float* __restrict__ state,
                                       float* __restrict__ scale_dev) {
   float s = setting;
-  if (setting < 0.f) s = fminf(fmaxf(exp2f(floorf(log2f(*denom_dev * (-setting) / l1w))), 1.f), 16777216.f);
+  if (setting < 0.f) s = fminf(fmaxf(exp2f(floorf(log2f(*denom_dev * (-setting) / gmax))), 1.f), 16777216.f);
   if (state) { const float m = state[0]; if (m > 0.f && m < 1.f) s = fmaxf(s * m, 5.9604645e-8f); }
   *scale_dev = s;
 }
-void k_set_loss_scale(spa3d_ctx* c, const float* denom_dev, float l1w, float setting, float* scale_dev) {
+void k_set_loss_scale(spa3d_ctx* c, const float* denom_dev, float gmax, float setting, float* scale_dev) {
   if (c->dry) return;
-  set_loss_scale_kernel<<<1, 1, 0, c->stream>>>(denom_dev, l1w, setting, c->loss_scale_state, scale_dev); SPA_LAUNCH_CHECK(c);
+  set_loss_scale_kernel<<<1, 1, 0, c->stream>>>(denom_dev, gmax, setting, c->loss_scale_state, scale_dev); SPA_LAUNCH_CHECK(c);
 }
 __global__ void unscale_kernel(float* __restrict__ a, const float* __restrict__ scale_dev, int64_t n) {
   const float s = 1.f / *scale_dev;
@@ -408,25 +417,27 @@ void k_det_flush(spa3d_ctx* c, int64_t lo, int64_t n) {
 // the fixed-point unit of a det_grads call (common.hpp DetCfg): 2^(32 + e), e = floor(log2(denom / (n_vis * loss scale))) clamped to [-24, 40].  Inputs are the call's
 // global denominator, its own visible count and its loss scale, so the unit is a function of the call's inputs alone (bit-equal run to run and whatever the
 // all-reduce schedule).  -24 covers the fp16 mode at BASELINE configs[2] (e ~ -14); below it the unit stops coarsening and the range guards take over.
+// gshift = floor(log2(gmax / 5000)) (host; 0 for the default objective): a gradient of the call also scales as the objective's largest head gradient gmax, so the
+// unit follows it by that power of two -- e - gshift is what is clamped -- and a visibility-only objective is resolved as finely, relative to its size, as the default.
 // Writes the call's DetCfg, with the unit as its scale, where the call's kernels read it.
-__global__ void det_unit_kernel(const float* sums, const unsigned* poison, const float* denom_dev, const float* scale_dev, DetCfg d, DetCfg* out) {
+__global__ void det_unit_kernel(const float* sums, const unsigned* poison, const float* denom_dev, const float* scale_dev, int gshift, DetCfg d, DetCfg* out) {
   const float nvis = fmaxf(loss_acc_read((const unsigned long long*)sums + 2, poison), 1.f);   // fmaxf(NaN, 1) = 1
   const float r = *denom_dev / (nvis * (scale_dev ? *scale_dev : 1.f));
   int e = 0;
-  if (r > 0.f && r <= 3.0e38f) { (void)frexpf(r, &e); e = min(max(e - 1, DET_E_MIN), DET_E_MAX); }   // r = m 2^e', m in [0.5, 1): floor(log2 r) = e' - 1, exactly
+  if (r > 0.f && r <= 3.0e38f) { (void)frexpf(r, &e); e = min(max(e - 1 - gshift, DET_E_MIN), DET_E_MAX); }   // r = m 2^e', m in [0.5, 1): floor(log2 r) = e' - 1, exactly
   d.scale = ldexpf(1.f, 32 + e);
   *out = d;
 }
-void k_det_unit(spa3d_ctx* c, const float* sums, const unsigned* poison, const float* denom_dev, const float* scale_dev, const DetCfg& d, DetCfg* out) {
+void k_det_unit(spa3d_ctx* c, const float* sums, const unsigned* poison, const float* denom_dev, const float* scale_dev, int gshift, const DetCfg& d, DetCfg* out) {
   if (c->dry) return;
-  det_unit_kernel<<<1, 1, 0, c->stream>>>(sums, poison, denom_dev, scale_dev, d, out); SPA_LAUNCH_CHECK(c);
+  det_unit_kernel<<<1, 1, 0, c->stream>>>(sums, poison, denom_dev, scale_dev, gshift, d, out); SPA_LAUNCH_CHECK(c);
 }
 
 // ---------------------------------------------------------------------------------------------
 // explicit instantiations
 // ---------------------------------------------------------------------------------------------
 #define INST_LOSS(T) \
-  template void k_loss_bwd<T>(spa3d_ctx*, const float*, int64_t, int, const float*, const float*, const float*, float, float, T*, int, const float*);
+  template void k_loss_bwd<T>(spa3d_ctx*, const float*, int64_t, int, const float*, const float*, const float*, const spa3d_loss_config&, const float*, T*, int, const float*);
 INST_LOSS(float)
 INST_LOSS(bf16_t)
 }  // namespace SPA_NS

@@ -23,10 +23,12 @@ struct RunArgs {
   const float* latents_in; float* latents_out; int chunk;  // chunk: fixed Bc (>0) or 0 = as large as fits
   const int32_t* cn; const int32_t* cq;  // ragged batch (spa3d_set_counts): host arrays [B] of live support tracks / live queries per sample; null = all N / all Q
   const spa3d_scores* score;  // spa3d_score: per-track scores of every emitted query row, straight from the head (emit_scores); null everywhere else
+  const float* w;  // train: the point weights [B,Q,T_out] (spa3d_set_point_weights; run() has checked their shape), addressed with the visibility targets' offsets; null = 1
 };
 
 namespace SPA_NS {
-static const float L1_WEIGHT = 5000.0f, BCE_WEIGHT = 1e-8f;  // train.py:96
+// the point-weight plane at a row offset (null stays null: no arithmetic on a null pointer)
+static inline const float* at_rows(const float* w, int64_t off) { return w ? w + off : nullptr; }
 
 // ---------------------------------------------------------------------------------------------
 // weights as the kernels want them
@@ -732,6 +734,7 @@ template <typename T> struct Net {
   // finished segment is unscaled right before its event; the rest of the buffer at the end of the call.
   int64_t seg_lo[2] = {0, 0}, seg_hi[2] = {0, 0};  // flat ranges of segment 0 ([b2, n): readout side) and 1 ([b1, b2): latent stacks), spa3d_grad_segments
   const float* scale_dev = nullptr;                  // fp16 mode: the call's loss scale (device)
+  const float* ptw = nullptr;                        // the call's point weights (RunArgs::w)
   bool seg_unscaled[2] = {false, false};
   void grad_segment_done(int i) {
     if (c->dry || !c->last_chunk || !c->grad_ev[i]) return;
@@ -767,11 +770,11 @@ template <typename T> struct Net {
         for (int64_t s = 0; s < k.Bc; ++s) {
           const int64_t q0 = k.qoff[s], tr = (b0 + s) * k.Q;
           k_loss_bwd<T>(c, k.head + q0 * 4 * To, k.qoff[s + 1] - k.qoff[s], To, b->query_tracks + tr * To * NC, b->query_tracks_visible + tr * To, denom_dev,
-                        L1_WEIGHT, BCE_WEIGHT, dhead + q0 * 4 * To, NC, c->loss_scale != 1.f ? denom_dev + 1 : nullptr);
+                        c->loss, at_rows(ptw, tr * To), dhead + q0 * 4 * To, NC, c->loss_scale != 1.f ? denom_dev + 1 : nullptr);
         }
       }
       else k_loss_bwd<T>(c, k.head, nq, To, b->query_tracks + qrow * To * NC, b->query_tracks_visible + qrow * To, denom_dev,
-                    L1_WEIGHT, BCE_WEIGHT, dhead, NC, c->loss_scale != 1.f ? denom_dev + 1 : nullptr);  // + loss scale in fp16 mode
+                    c->loss, at_rows(ptw, qrow * To), dhead, NC, c->loss_scale != 1.f ? denom_dev + 1 : nullptr);  // + loss scale in fp16 mode
       lin_bwd_w(pred, k.q0n, dhead, nq);
       T* dq0n = alloc<T>(nq * dd);
       lin_bwd_x(pred, dhead, dq0n, nq);
@@ -930,7 +933,7 @@ static void emit_outputs(spa3d_ctx* c, const RunArgs& a, Net<T>& net, typename N
       float* vl = a.out && a.out->visible_logits ? a.out->visible_logits + r * To : nullptr;
       float* cl = a.out && a.out->certain_logits ? a.out->certain_logits + r * To : nullptr;
       k_loss_fwd(c, k.head + q0 * 4 * To, qs, To, train ? b->query_tracks + r * To * NC : nullptr, train ? b->query_tracks_visible + r * To : nullptr,
-                 tr, vl, cl, sums, poison, NC);
+                 tr, vl, cl, sums, poison, NC, c->loss, train ? at_rows(a.w, r * To) : nullptr);
       if (tr && pad > 0) k_zero(c, tr + qs * To * NC, pad * To * NC * 4);
       if (vl && pad > 0) k_zero(c, vl + qs * To, pad * To * 4);
       if (cl && pad > 0) k_zero(c, cl + qs * To, pad * To * 4);
@@ -942,7 +945,7 @@ static void emit_outputs(spa3d_ctx* c, const RunArgs& a, Net<T>& net, typename N
   float* vl = a.out && a.out->visible_logits ? a.out->visible_logits + qrow * To : nullptr;
   float* cl = a.out && a.out->certain_logits ? a.out->certain_logits + qrow * To : nullptr;
   k_loss_fwd(c, k.head, nq, To, train ? b->query_tracks + qrow * To * NC : nullptr, train ? b->query_tracks_visible + qrow * To : nullptr,
-             tr, vl, cl, sums, poison, NC);
+             tr, vl, cl, sums, poison, NC, c->loss, train ? at_rows(a.w, qrow * To) : nullptr);
 }
 
 // One sample with intra-sample chunks (spa3d_set_option "track_chunk" / "query_chunk"; k.Bc == 1).
@@ -1027,6 +1030,7 @@ void run_body(spa3d_ctx* c, const RunArgs& a, int Bc) {
   const bool train = a.mode == MODE_TRAIN;
   Net<T> net(c, a.P, a.G);
   net.pack();
+  net.ptw = train ? a.w : nullptr;
   float* sums = net.template alloc<float>(10);
   float* denom_dev = sums + 6;  // [0..5] three 64-bit fixed-point accumulators (loss.hip loss_acc_add), [6] denominator, [7] loss scale, [8] sticky non-finite flag
   unsigned* poison = (unsigned*)(sums + 8);
@@ -1044,7 +1048,7 @@ void run_body(spa3d_ctx* c, const RunArgs& a, int Bc) {
       k_vis_count(c, b->query_tracks_visible, (int64_t)b->B * b->Q * To, sums + 4, poison);
     }
     k_set_denom(c, sums, poison, a.denom, denom_dev);
-    if (c->loss_scale != 1.f) k_set_loss_scale(c, denom_dev, L1_WEIGHT, c->loss_scale, denom_dev + 1);  // sums[7]
+    if (c->loss_scale != 1.f) k_set_loss_scale(c, denom_dev, c->loss_gmax, c->loss_scale, denom_dev + 1);  // sums[7]
     if (!a.accumulate) k_zero(c, a.G, c->nparams * 4);
   }
   if (train && (c->loss_scale != 1.f || c->det_grads)) {
@@ -1058,7 +1062,7 @@ void run_body(spa3d_ctx* c, const RunArgs& a, int Bc) {
     long long* sh = net.template alloc<long long>(c->nparams); unsigned* fl = net.template alloc<unsigned>(64);
     k_zero(c, sh, c->nparams * 8); k_zero(c, fl, 256);
     DetCfg* dc = (DetCfg*)(fl + 2);   // fl[0]: the sticky overflow flag, fl[2...]: the DetCfg of this call, with its fixed-point unit
-    k_det_unit(c, sums, poison, denom_dev, c->loss_scale != 1.f ? denom_dev + 1 : nullptr, DetCfg{a.G, sh, (long long)c->nparams, fl, 0.f}, dc);
+    k_det_unit(c, sums, poison, denom_dev, c->loss_scale != 1.f ? denom_dev + 1 : nullptr, c->loss_gshift, DetCfg{a.G, sh, (long long)c->nparams, fl, 0.f}, dc);
     c->det = dc;
   }
   const bool ragged = a.cn || a.cq;  // per-sample counts (spa3d_set_counts; run() has validated them)
@@ -1115,7 +1119,7 @@ void run_body(spa3d_ctx* c, const RunArgs& a, int Bc) {
       if (!net.seg_unscaled[0]) k_unscale(c, a.G + lo0, denom_dev + 1, c->nparams - lo0);
     }
   }
-  if (train && a.loss3) k_loss_finalize(c, sums, poison, denom_dev, L1_WEIGHT, BCE_WEIGHT, a.loss3);
+  if (train && a.loss3) k_loss_finalize(c, sums, poison, denom_dev, c->loss.l1_weight, c->loss.bce_weight, a.loss3);
   // spa3d_score: the per-sample pooled stats, ONE launch once every (sample / query / track) chunk has written its rows of query_stats
   if (a.score && a.score->sample_stats) k_score_reduce(c, a.score->query_stats, b->B, b->Q, a.score->num_thresholds, a.score->sample_stats);
 }
@@ -1231,6 +1235,12 @@ static int run(spa3d_ctx* c, RunArgs a, void* ws, int64_t ws_bytes, void* stream
   if (c->query_chunk > 0 || c->track_chunk > 0) {  // intra-sample chunks: one sample per sample chunk
     if (a.chunk > 1) { c->err = "\"chunk\" > 1 cannot be combined with \"query_chunk\" / \"track_chunk\" (they imply one sample per chunk)"; return SPA3D_ERR_ARG; }
     a.chunk = 1;
+  }
+  // point weights (spa3d_set_point_weights): read by the train call only, refused for another batch shape before the first launch
+  a.w = nullptr;
+  if (a.mode == MODE_TRAIN) {
+    if (!weights_fit_batch(c, a.b->B, a.b->Q)) return SPA3D_ERR_ARG;
+    a.w = c->pt_w;
   }
   // per-sample counts (spa3d_set_counts): validated here, before the first launch; the sizing dry runs below walk the live counts
   a.cn = nullptr; a.cq = nullptr;
@@ -1405,15 +1415,17 @@ int spa3d_loss(spa3d_handle h, const spa3d_batch* b, const spa3d_outputs* preds,
   const int To = h->cfg.num_output_frames, NC = h->cfg.model_kind == 1 ? 2 : 3;
   const int32_t* cq = nullptr;
   if (h->has_cnt_q && !(cq = checked_query_counts(h, b->B, b->Q))) return SPA3D_ERR_ARG;
+  if (!weights_fit_batch(h, b->B, b->Q)) return SPA3D_ERR_ARG;
   k_zero(h, loss3 + 3, 36);
   // live queries only: the whole batch at once, or sample by sample (the sums are order-independent fixed-point sums)
   for_each_live_span(cq, b->B, b->Q, [&](int64_t row0, int64_t nq) { k_vis_count(h, b->query_tracks_visible + row0 * To, nq * To, scratch + 4, poison); });
   k_set_denom(h, scratch, poison, denom, scratch + 6);
   for_each_live_span(cq, b->B, b->Q, [&](int64_t row0, int64_t nq) {
     const int64_t r = row0 * To;
-    k_loss_from_preds(h, preds->tracks + r * NC, preds->visible_logits + r, nq * To, b->query_tracks + r * NC, b->query_tracks_visible + r, scratch, poison, NC);
+    k_loss_from_preds(h, preds->tracks + r * NC, preds->visible_logits + r, nq * To, b->query_tracks + r * NC, b->query_tracks_visible + r, scratch, poison, NC,
+                      h->loss, at_rows(h->pt_w, r));
   });
-  k_loss_finalize(h, scratch, poison, scratch + 6, L1_WEIGHT, BCE_WEIGHT, loss3);
+  k_loss_finalize(h, scratch, poison, scratch + 6, h->loss.l1_weight, h->loss.bce_weight, loss3);
   return h->hip_err ? SPA3D_ERR_HIP : SPA3D_OK;
 }
 
@@ -1452,6 +1464,43 @@ int spa3d_set_counts(spa3d_handle h, int32_t B, const int32_t* support_count, co
   h->cnt_B = B;
   if (support_count) { h->cnt_n.assign(support_count, support_count + B); h->has_cnt_n = true; }
   if (query_count) { h->cnt_q.assign(query_count, query_count + B); h->has_cnt_q = true; }
+  return SPA3D_OK;
+}
+// the objective (include/spa3d.h "The training objective"): every refusal leaves the stored configuration as it was
+int spa3d_set_loss(spa3d_handle h, const spa3d_loss_config* cfg) {
+  if (!h) return SPA3D_ERR_ARG;
+  const spa3d_loss_config d = cfg ? *cfg : loss_config_defaults();
+  const int NC = h->cfg.model_kind == 1 ? 2 : 3;
+  auto refuse = [&](const std::string& m) { h->err = "spa3d_set_loss: " + m; return SPA3D_ERR_ARG; };
+  if (d.position_kind != SPA3D_POS_L1 && d.position_kind != SPA3D_POS_HUBER) return refuse("position_kind = " + std::to_string(d.position_kind) + " is neither SPA3D_POS_L1 nor SPA3D_POS_HUBER");
+  const bool huber = d.position_kind == SPA3D_POS_HUBER;
+  bool finite = std::isfinite(d.l1_weight) && std::isfinite(d.bce_weight) && std::isfinite(d.bce_pos_weight) && (!huber || std::isfinite(d.huber_delta));
+  for (int i = 0; i < NC; ++i) finite = finite && std::isfinite(d.axis_weight[i]);
+  if (!finite) return refuse("every field must be finite");
+  bool negative = d.l1_weight < 0.f || d.bce_weight < 0.f || d.bce_pos_weight < 0.f;
+  float amax = 0.f;
+  for (int i = 0; i < NC; ++i) { negative = negative || d.axis_weight[i] < 0.f; amax = std::max(amax, d.axis_weight[i]); }
+  if (negative) return refuse("l1_weight, bce_weight, axis_weight and bce_pos_weight must not be negative");
+  if (huber && !(d.huber_delta > 0.f)) return refuse("huber_delta must be positive with SPA3D_POS_HUBER");
+  if (d.l1_weight > 0.f && !(amax > 0.f)) return refuse("l1_weight > 0 needs a positive axis_weight among the model's " + std::to_string(NC) + " coordinates");
+  const float gmax = std::max(d.l1_weight * amax, d.bce_weight * std::max(1.f, d.bce_pos_weight));
+  if (!(gmax > 0.f && gmax <= 1073741824.f)) return refuse("the largest head gradient max(l1_weight * max axis_weight, bce_weight * max(1, bce_pos_weight)) must lie in (0, 2^30]");
+  int e = 0;
+  (void)frexp((double)gmax / 5000.0, &e);  // gmax / 5000 = m 2^e, m in [0.5, 1): floor(log2) = e - 1
+  h->loss = d; h->loss_gmax = gmax; h->loss_gshift = e - 1;
+  return SPA3D_OK;
+}
+int spa3d_get_loss(spa3d_handle h, spa3d_loss_config* out) {
+  if (!h || !out) return SPA3D_ERR_ARG;
+  *out = h->loss;
+  return SPA3D_OK;
+}
+int spa3d_set_point_weights(spa3d_handle h, int32_t B, int32_t Q, const float* w) {
+  if (!h) return SPA3D_ERR_ARG;
+  h->pt_w = nullptr; h->pt_B = h->pt_Q = 0;
+  if (!w) return SPA3D_OK;  // detach (B and Q are then ignored)
+  if (B <= 0 || Q <= 0) { h->err = "spa3d_set_point_weights: B and Q must be positive"; return SPA3D_ERR_ARG; }
+  h->pt_w = w; h->pt_B = B; h->pt_Q = Q;
   return SPA3D_OK;
 }
 int spa3d_grad_segments(spa3d_handle h, int64_t* bounds4) {

@@ -284,7 +284,7 @@ def convert_predictions_to_tapvid3d_format(predictions, query_points=None):
 # ------------------------------------------------------------------------------------------------ ragged batches
 # keys whose second dimension is the support-track axis / the query axis of a [B, ...] batch
 SUPPORT_KEYS = ('support_tracks', 'support_tracks_visible', 'dino_features', 'depth_features')
-QUERY_KEYS = ('query_points', 'query_tracks', 'query_tracks_visible')
+QUERY_KEYS = ('query_points', 'query_tracks', 'query_tracks_visible', 'query_weight')
 
 
 def validate_counts(counts, B: int, limit: int, name: str, minimum: int):

@@ -323,6 +323,94 @@ def _counts_on(h, b):
     lib.spa3d_set_counts(h, 0, None, None)
 
 
+# ------------------------------------------------------------------------------------------------
+# the training objective (include/spa3d.h, spa3d_loss_config)
+# ------------------------------------------------------------------------------------------------
+POS_L1, POS_HUBER = 0, 1
+
+
+@dataclasses.dataclass(frozen=True)
+class LossConfig:
+  """spa3d_loss_config: the objective of loss_and_grads / TrainState / compute_loss_3d(loss=...).  The defaults are the reference's
+  (train.py:96).  position_kind POS_L1 or POS_HUBER (delta = huber_delta, L1's slope in the tails); axis_weight per coordinate (the 2-D model
+  reads two); bce_pos_weight as torch's pos_weight.  Validated with the library's rules (ValueError here, SPA3D_ERR_ARG there)."""
+  l1_weight: float = 5000.0
+  bce_weight: float = 1e-8
+  position_kind: int = POS_L1
+  huber_delta: float = 1.0
+  axis_weight: tuple = (1.0, 1.0, 1.0)
+  bce_pos_weight: float = 1.0
+
+  def __post_init__(self):
+    self.validate(3)
+
+  def validate(self, nc: int = 3):
+    """The refusals of spa3d_set_loss for a model of `nc` coordinates, on the values as the library sees them (float32)."""
+    f32 = lambda v: C.c_float(float(v)).value
+    if isinstance(self.position_kind, bool) or self.position_kind not in (POS_L1, POS_HUBER):
+      raise ValueError(f'position_kind must be POS_L1 (0) or POS_HUBER (1), got {self.position_kind!r}')
+    ax = tuple(self.axis_weight)
+    if len(ax) != 3:
+      raise ValueError(f'axis_weight must have 3 entries (the 2-D model reads the first two), got {len(ax)}')
+    huber = self.position_kind == POS_HUBER
+    l1, bce, beta, delta = f32(self.l1_weight), f32(self.bce_weight), f32(self.bce_pos_weight), f32(self.huber_delta)
+    ax = tuple(f32(a) for a in ax)
+    if not all(math.isfinite(v) for v in (l1, bce, beta) + ax[:nc] + ((delta,) if huber else ())):
+      raise ValueError('every field of a LossConfig must be finite')
+    if l1 < 0 or bce < 0 or beta < 0 or any(a < 0 for a in ax[:nc]):
+      raise ValueError('l1_weight, bce_weight, axis_weight and bce_pos_weight must not be negative')
+    if huber and not delta > 0:
+      raise ValueError(f'huber_delta must be positive with POS_HUBER, got {self.huber_delta!r}')
+    amax = max(ax[:nc])
+    if l1 > 0 and not amax > 0:
+      raise ValueError(f"l1_weight > 0 needs a positive axis_weight among the model's {nc} coordinates")
+    gmax = max(f32(l1 * amax), f32(bce * max(1.0, beta)))
+    if not (0 < gmax <= 2.0 ** 30):
+      raise ValueError(f'the largest head gradient max(l1_weight * max axis_weight, bce_weight * max(1, bce_pos_weight)) = {gmax!r} must lie in (0, 2^30]')
+    return self
+
+  def as_struct(self):
+    s = _lib.LossConfig()
+    s.l1_weight, s.bce_weight, s.position_kind, s.huber_delta, s.bce_pos_weight = self.l1_weight, self.bce_weight, int(self.position_kind), self.huber_delta, self.bce_pos_weight
+    for i, a in enumerate(self.axis_weight):
+      s.axis_weight[i] = a
+    return s
+
+
+def _point_weights(w, B, Q, To):
+  """batch['query_weight'] ([B,Q,T] or [B,Q,T,1]) as the contiguous float32 plane the library reads; None stays None."""
+  if w is None:
+    return None
+  _require_cuda(w, 'query_weight')
+  if tuple(w.shape) not in ((B, Q, To), (B, Q, To, 1)):
+    raise ValueError(f'query_weight must be {(B, Q, To)} or {(B, Q, To, 1)}, got {tuple(w.shape)}')
+  return w if (w.dtype == torch.float32 and w.is_contiguous()) else w.to(torch.float32).contiguous()
+
+
+@contextlib.contextmanager
+def _loss_on(h, loss, weights, B, Q, nc):
+  """States the objective and the point weights on the handle for the calls inside the block and takes both off afterwards (as _counts_on
+  does with the counts): a handle shared by several owners never carries one owner's objective into another's call."""
+  if loss is None and weights is None:
+    yield
+    return
+  lib = _lib.load()
+  if loss is not None:
+    if not isinstance(loss, LossConfig):
+      raise TypeError(f'loss must be a LossConfig or None, got {type(loss).__name__}')
+    loss.validate(nc)
+    cfg = loss.as_struct()
+    _lib.check(lib.spa3d_set_loss(h, C.byref(cfg)), h, 'spa3d_set_loss')
+  try:
+    if weights is not None:
+      _lib.check(lib.spa3d_set_point_weights(h, B, Q, weights.data_ptr()), h, 'spa3d_set_point_weights')
+    yield
+  finally:
+    lib.spa3d_set_point_weights(h, 0, 0, None)
+    if loss is not None:
+      lib.spa3d_set_loss(h, None)
+
+
 def _require_cuda(t: torch.Tensor, name: str):
   if not t.is_cuda:
     raise _lib.Spa3dError(f'{name} must live on the GPU: the 3DSPA hot path is HIP-only (no CPU fallback)')
@@ -548,6 +636,7 @@ class TrackAutoEncoder3D:
         raise ValueError(f'query_tracks must be {(b.B, b.Q, To, self._nc)} and query_tracks_visible {(b.B, b.Q, To, 1)}')
       keep += [qt, qv]
       b.query_tracks, b.query_tracks_visible = qt.data_ptr(), qv.data_ptr()
+      b.weights = _point_weights(inputs.get('query_weight'), b.B, b.Q, To)  # optional per-point loss weights; _loss_on states them
     # ragged batch: optional per-sample counts (rows at or beyond a count are padding the library never reads); _counts_on states them
     cn = validate_counts(inputs.get('support_count'), b.B, b.N, 'support_count', 1) if need_support else None
     cq = validate_counts(query_count if query_count is not None else inputs.get('query_count'), b.B, b.Q, 'query_count', 0) if need_query else None
@@ -712,9 +801,10 @@ class TrackAutoEncoder3D:
 
   # -------------------------------------------------------------------------------- value_and_grad
   def loss_and_grads(self, variables, batch, grads_flat: Optional[torch.Tensor] = None, accumulate: bool = False,
-                     denom: float = 0.0, discretize: bool = True, noise=None, return_predictions: bool = False):
+                     denom: float = 0.0, discretize: bool = True, noise=None, return_predictions: bool = False, loss: Optional[LossConfig] = None):
     """jax.value_and_grad(loss_fn)(params) of train.py:134-162 in one call.  Returns (loss_dict, grads_tree, preds|None).
-    `denom`: the batch-GLOBAL sum(query_tracks_visible) under data parallelism (train.py:111-113)."""
+    `denom`: the batch-GLOBAL sum(query_tracks_visible) under data parallelism (train.py:111-113).
+    `loss`: the objective (LossConfig; None = the reference's); batch['query_weight'] ([B,Q,T] or [B,Q,T,1], in [0, 1]) weights single points."""
     params = variables['params'] if 'params' in variables and isinstance(variables['params'], dict) else variables
     dino, depth = self._dims_from_params(params)
     h, _, n = self._handle(dino, depth)
@@ -731,7 +821,7 @@ class TrackAutoEncoder3D:
       res, out = self._alloc_outputs(b.B, b.Q, dev)
       outp = C.byref(out)
     ws = self._workspace(h, b.B, b.N, b.Q, b.T, True, dev)
-    with _counts_on(h, b):
+    with _counts_on(h, b), _loss_on(h, loss, b.weights, b.B, b.Q, self._nc):
       _lib.check(_lib.load().spa3d_loss_and_grads(h, flat.data_ptr(), C.byref(b), float(denom), grads_flat.data_ptr(),
                                                   1 if accumulate else 0, loss3.data_ptr(), outp, ws.data_ptr(), ws.numel(),
                                                   _stream(flat)), h, 'spa3d_loss_and_grads')
@@ -740,8 +830,10 @@ class TrackAutoEncoder3D:
 
 
 def compute_loss_3d(predictions: TrackAutoEncoderResults, targets, l1_weight: float = 5000.0, bce_weight: float = 1e-8,
-                    denom: float = 0.0):
-  """train.py:96-129 on the GPU kernels.  Needs any model handle only for its output-frame count."""
+                    denom: float = 0.0, loss: Optional[LossConfig] = None):
+  """train.py:96-129 on the GPU kernels.  Needs any model handle only for its output-frame count.
+  targets['query_weight'], when present, weights single points.  With `loss` (a LossConfig) the three numbers are what loss_and_grads reports
+  under that objective for these predictions (l1_weight / bce_weight are then the configuration's, not the arguments)."""
   lib = _lib.load()
   tr = predictions.tracks
   _require_cuda(tr, 'predictions.tracks')
@@ -757,11 +849,14 @@ def compute_loss_3d(predictions: TrackAutoEncoderResults, targets, l1_weight: fl
   t32 = tr.to(torch.float32).contiguous()
   vl = predictions.visible_logits.to(torch.float32).contiguous()
   out = _lib.Outputs(t32.data_ptr(), vl.data_ptr(), None, None)
-  loss = torch.empty(12, dtype=torch.float32, device=tr.device)
   b.counts = (None, validate_counts(targets.get('query_count'), B, Q, 'query_count', 0))  # ragged batch: live queries only
-  with _counts_on(h, b):
-    _lib.check(lib.spa3d_loss(h, C.byref(b), C.byref(out), float(denom), loss.data_ptr(), _stream(tr)), h, 'spa3d_loss')
-  pos, vis = loss[1], loss[2]
+  qw = _point_weights(targets.get('query_weight'), B, Q, To)
+  loss3 = torch.empty(12, dtype=torch.float32, device=tr.device)
+  with _counts_on(h, b), _loss_on(h, loss, qw, B, Q, tr.shape[-1]):
+    _lib.check(lib.spa3d_loss(h, C.byref(b), C.byref(out), float(denom), loss3.data_ptr(), _stream(tr)), h, 'spa3d_loss')
+  pos, vis = loss3[1], loss3[2]
+  if loss is not None:
+    return {'total_loss': loss3[0], 'position_loss': pos, 'visible_loss': vis}
   return {'total_loss': l1_weight * pos + bce_weight * vis, 'position_loss': pos, 'visible_loss': vis}
 
 
@@ -1029,9 +1124,10 @@ def _loss_handle(num_output_frames, kind=0):
   return _LOSS_HANDLES[(num_output_frames, kind)]
 
 
-def compute_loss_2d(predictions: TrackAutoEncoderResults, targets, l1_weight: float = 5000.0, bce_weight: float = 1e-8, denom: float = 0.0):
+def compute_loss_2d(predictions: TrackAutoEncoderResults, targets, l1_weight: float = 5000.0, bce_weight: float = 1e-8, denom: float = 0.0,
+                    loss: Optional[LossConfig] = None):
   """train.py:60-93 (same arithmetic as compute_loss_3d on 2 coordinates)."""
-  return compute_loss_3d(predictions, targets, l1_weight, bce_weight, denom)
+  return compute_loss_3d(predictions, targets, l1_weight, bce_weight, denom, loss)
 
 
 class TrackAutoEncoder(TrackAutoEncoder3D):

@@ -136,8 +136,11 @@ class TrainState:
                total_steps: int = 1000000, weight_decay: float = 0.01, clip_norm: float = 1.0, b1: float = 0.9,
                b2: float = 0.999, eps: float = 1e-8, process_group: Optional[dist.ProcessGroup] = None,
                grad_bucket_bytes: int = 128 << 20, compute=None, adamw=None, noise_fn=None, force_collectives: bool = False,
-               evaluate=None, overlap_allreduce: bool = True):
+               evaluate=None, overlap_allreduce: bool = True, loss=None):
     self.model = model
+    # the objective of this state's steps (a LossConfig; None = the reference's): stated on the model's handle for each call and taken off after
+    # it, so two states with different objectives on one model never see each other's
+    self.loss = loss
     self.params = params if hasattr(params, 'flat') and params.flat is not None else None
     flat = model.flat_from_tree(params)
     if self.params is None:
@@ -227,7 +230,7 @@ class TrainState:
   # ---- default (HIP) compute and optimizer
   def _hip_compute(self, params, batch, grads_flat, denom, discretize, noise):
     ld, _, _ = self.model.loss_and_grads(params, batch, grads_flat=grads_flat, accumulate=False, denom=denom,
-                                         discretize=discretize, noise=noise)
+                                         discretize=discretize, noise=noise, loss=self.loss)
     return ld
 
   def _hip_adamw(self, flat, grads, m, v, lr, step, clip, b1, b2, eps, wd, scratch):
@@ -238,7 +241,7 @@ class TrainState:
     from .model import compute_loss_2d, compute_loss_3d
     preds = self.model.apply({'params': params}, batch, discretize=discretize, noise=noise)
     loss_fn = compute_loss_2d if preds.tracks.shape[-1] == 2 else compute_loss_3d
-    return loss_fn(preds, batch, denom=denom), preds
+    return loss_fn(preds, batch, denom=denom, loss=self.loss), preds
 
   def rank_noise(self, b_local: int):
     """The reference draws uniform(PRNGKey(0), [B_global, L, Ld]) over the GLOBAL batch (3d:254-258); rank r owns rows

@@ -324,10 +324,54 @@ int spa3d_build_batch(spa3d_handle h, const spa3d_clip* clips /* host [B] */, sp
 /* forward + loss + backward.  grads (flat f32, same layout as params) is OVERWRITTEN unless
  * accumulate!=0.  denom: global sum(query_tracks_visible) for data-parallel runs (the loss
  * normalisers are batch-global, train.py:111-113,119-121); <=0 = this batch's own.
- * loss3 (device): {total, position, visible} with that denominator.  out may be NULL. */
+ * loss3 (device): {total, position, visible} with that denominator.  out may be NULL.
+ * The objective is the handle's (spa3d_set_loss, spa3d_set_point_weights below; the reference's by default). */
 int spa3d_loss_and_grads(spa3d_handle h, const float* params, const spa3d_batch* b, float denom,
                          float* grads, int32_t accumulate, float* loss3, spa3d_outputs* out,
                          void* ws, int64_t ws_bytes, void* stream);
+
+/* The training objective.  The reference trains one objective, L1 positions and BCE visibility with the weights 5000 and 1e-8 (train.py:96);
+ * that is the default here, and a handle may be given another member of a small family.  Per live point (q, t) of a live query row, in fp32:
+ *   p_c, g_c prediction and target, d_c = p_c - g_c, c < NC (3; 2 on the 2-D twin); l the visibility logit, y the target visibility;
+ *   w the point weight (1 when no plane is attached); a_c = axis_weight[c]; beta = bce_pos_weight (the semantics of torch's pos_weight).
+ *   position term   e = sum_c a_c rho(d_c)
+ *     SPA3D_POS_L1     rho(d) = |d|,  rho' = sign(d) with sign(0) = 0
+ *     SPA3D_POS_HUBER  rho(d) = d d / (2 delta) for |d| <= delta, else |d| - delta / 2;  rho' = d / delta, respectively sign(d)
+ *                      (L1's slope in the tails, so l1_weight keeps its meaning)
+ *   visibility term v = -beta y logsig(l) - (1 - y) logsig(-l)
+ *   numerators      P = sum w y e,  V = sum w v  over the live points
+ *   denominator     D = denom when denom > 0, else max(sum of y over the live rows, 1).  It is NOT weighted: a caller who wants a weighted
+ *                   denominator passes it.
+ *   loss3           {l1_weight P / D + bce_weight V / D,  P / D,  V / D}
+ *   head cotangent  d/dp_c = l1_weight w y a_c rho'(d_c) / D
+ *                   d/dl   = bce_weight w (beta y (sigmoid(l) - 1) + (1 - y) sigmoid(l)) / D;  with beta == 1 this is evaluated as
+ *                            bce_weight w (sigmoid(l) - y) / D
+ * With the default configuration and no weight plane every result is what the fixed objective gave, bit for bit, in all three precisions (the
+ * extra multiplications are by exactly 1, in an order that leaves the old operations as they were).
+ *   The configuration is per handle, like the options: spa3d_loss_and_grads and spa3d_loss read it; spa3d_score and the metrics do not.
+ * spa3d_set_loss(h, NULL) restores the defaults.  It returns SPA3D_ERR_ARG with a message in spa3d_last_error, and leaves the stored
+ * configuration untouched, for: a field that is not finite; a negative weight; position_kind outside {0, 1}; huber_delta <= 0 with HUBER;
+ * l1_weight > 0 with no positive axis weight among the model's NC; g_max outside (0, 2^30], where
+ *   g_max = max(l1_weight max_c a_c, bce_weight max(1, beta))
+ * bounds the head gradient per unit point weight (and excludes the all-zero objective).  The fp16 automatic loss scale keeps g_max / D at or
+ * below its target, and the det_grads unit follows g_max (see "det_grads" below); the defaults give g_max = 5000.
+ *   Point weights: a caller-owned DEVICE plane [B,Q,T_out] of floats, one per point, addressed like query_tracks_visible; the handle keeps
+ * the pointer (not a copy) until it is detached with w = NULL, and spa3d_loss_and_grads and spa3d_loss read it.  As with spa3d_set_counts a
+ * later call whose batch has another B or Q is refused (SPA3D_ERR_ARG) before its first launch.  Rows at or beyond a sample's query_count are
+ * never read (they may hold NaN).  Weights are expected in [0, 1]: the fp16 automatic loss scale and the det_grads unit are sized for that;
+ * larger weights want a fixed "loss_scale". */
+#define SPA3D_POS_L1 0
+#define SPA3D_POS_HUBER 1
+typedef struct {
+  float l1_weight, bce_weight;   /* 5000, 1e-8 */
+  int32_t position_kind;         /* SPA3D_POS_L1 */
+  float huber_delta;             /* read with HUBER only; > 0 (default 1) */
+  float axis_weight[3];          /* 1, 1, 1; the 2-D twin reads two */
+  float bce_pos_weight;          /* 1 */
+} spa3d_loss_config;
+int spa3d_set_loss(spa3d_handle h, const spa3d_loss_config* cfg /* NULL = defaults */);
+int spa3d_get_loss(spa3d_handle h, spa3d_loss_config* out);
+int spa3d_set_point_weights(spa3d_handle h, int32_t B, int32_t Q, const float* w /* device [B,Q,T_out] or NULL = detach */);
 
 /* clip_by_global_norm(clip) -> adamw(b1,b2,eps,wd) -> apply_updates on flat buffers, in place.
  * step = number of spa3d_adamw_step calls BEFORE this one; the bias correction uses step + 1 - scratch[3] (updates actually applied:
@@ -368,9 +412,13 @@ int spa3d_adamw_step(float* params, const float* grads, float* m, float* v, int6
  *   "det_grads"  0/1  order-independent parameter gradients: every reduction into the gradient buffer (split-M dW tiles, bias / scale column sums, broadcast
  *                     gradients) adds 64-bit fixed-point integers into a shadow of the buffer instead of float atomics, so two runs -- and two
  *                     data-parallel schedules -- give the same bits.  Unit: 2^-(32 + e) of the buffer's value with e = floor(log2(denom / (n_vis *
- *                     loss scale))), n_vis = this call's visible query points, clamped to [-24, 40]: a power of two chosen per call from its inputs alone.
- *                     With a real batch n_vis ~ denom, so the unit is 2^-32 as before (2^-(32 + log2 ranks) data-parallel; fp16: follows the loss
- *                     scale); it is finer only when the denominator exceeds the call's own visible count.  Range: an addend of 2^55 units or more, or a
+ *                     loss scale))) - floor(log2(g_max / 5000)), n_vis = this call's visible query points and g_max the objective's head-gradient
+ *                     bound (spa3d_set_loss), clamped to [-24, 40]: a power of two chosen per call from its inputs and the handle's objective alone.
+ *                     With the default objective the second term is 0, and with a real batch n_vis ~ denom, so the unit is 2^-32 as before
+ *                     (2^-(32 + log2 ranks) data-parallel; fp16: follows the loss scale); it is finer when the denominator exceeds the call's own
+ *                     visible count or the objective's gradients are smaller (g_max = 1, a visibility-only objective: 2^-45), and coarser by the
+ *                     power of two below g_max / 5000 when they are larger -- gradients are resolved as finely, relative to their size, whatever
+ *                     the objective.  Point weights are expected in [0, 1] and do not move the unit.  Range: an addend of 2^55 units or more, or a
  *                     shadow sum of 2^62 units or more, turns the whole gradient buffer of the call into NaN -- never a wrapped finite value.  The mode is
  *                     per handle and per train call: it travels with each launch of that call, so handles on other streams and the spa3d_op_*_bwd
  *                     entry points (always float atomics) never see it.
