@@ -90,6 +90,9 @@ _SIGS = {
     'spa3d_loss': (C.c_int, [C.c_void_p, C.POINTER(Batch), C.POINTER(Outputs), C.c_float, C.c_void_p, C.c_void_p]),
     'spa3d_score': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Batch), C.POINTER(Scores), C.POINTER(Outputs), C.c_void_p, C.c_int64,
                               C.c_void_p]),
+    'spa3d_score_folds_workspace_bytes': (C.c_int64, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+    'spa3d_score_folds': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Batch), C.c_int32, C.POINTER(C.c_int32), C.POINTER(Scores), C.POINTER(Outputs),
+                                    C.c_void_p, C.c_int64, C.c_void_p]),
     'spa3d_score_from_preds': (C.c_int, [C.c_void_p, C.POINTER(Batch), C.POINTER(Outputs), C.POINTER(Scores), C.c_void_p]),
     'spa3d_tapvid3d_workspace_bytes': (C.c_int64, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     'spa3d_tapvid3d_from_preds': (C.c_int, [C.c_void_p, C.POINTER(Batch), C.POINTER(Outputs), C.POINTER(TapVid3D), C.c_void_p, C.c_int64, C.c_void_p]),
@@ -130,6 +133,8 @@ _SIGS = {
                                + [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     'spa3d_op_attention': (C.c_int, [C.c_void_p] * 3 + [C.c_int64] * 3 + [C.c_void_p] * 3 + [C.c_int64] + [C.c_int32] * 4
                            + [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    'spa3d_op_attention_holdout': (C.c_int, [C.c_void_p] * 3 + [C.c_int64] * 3 + [C.c_void_p] * 2 + [C.c_int64] + [C.c_int32] * 4
+                                   + [C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     'spa3d_op_attention_bwd': (C.c_int, [C.c_void_p] * 3 + [C.c_int64] * 3 + [C.c_void_p] * 3 + [C.c_int64]
                                + [C.c_int32] * 4 + [C.c_void_p] * 8 + [C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
                                                                        C.c_void_p]),

@@ -20,6 +20,10 @@ bool xattn_varlen_fwd_bf16(spa3d_ctx* c, const bf16_t* q, const bf16_t* k, const
                            const float* sk, int64_t nseq, int Sq, int Skmax, int H, int Dh, bf16_t* o, float* lse, const int32_t* koff,
                            int64_t total_keys);
 
+bool xattn_holdout_fwd_bf16(spa3d_ctx* c, const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq,
+                            const float* sk, int64_t nseq, int Sq, int Nk, int nmax, int H, int Dh, bf16_t* o, float* lse, const int32_t* hole,
+                            int64_t total_keys);
+
 // ---------------------------------------------------------------------------------------------
 // per-head RMSNorm over Dh (flax nn.RMSNorm eps 1e-6) attention.py:166-167.  one wave per (row, head)
 // ---------------------------------------------------------------------------------------------
@@ -308,6 +312,37 @@ void attention_varlen_bwd(spa3d_ctx* c, const T* q, const T* k, const T* v, int6
   }
 }
 
+// Cross attention of nseq sequences of Sq queries over ONE shared key set, rows [0, Nk) of k / v, sequence i leaving out the rows [lo_i, hi_i) =
+// holes[2i], holes[2i + 1] (leave-fold-out scoring, spa3d_score_folds): its keys are the rows outside the hole, in row order.  holes_host and holes_dev
+// hold the same 2 nseq values; the caller has checked 0 <= lo <= hi <= Nk and hi - lo < Nk.  16-bit modes: one launch of the chunked-key kernel, which
+// addresses the keys by logical position (attention_fused.hip).  The generic composition (fp32 parity mode, attn_impl 1, shapes outside the fused kernel)
+// runs the sequences one by one on a compact copy of the two key segments.  Either way sequence i gets the bits of attention_fwd on a compacted copy.
+template <typename T>
+void attention_holdout_fwd(spa3d_ctx* c, const T* q, const T* k, const T* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq, const float* sk,
+                           int64_t nseq, int Sq, int Nk, const int32_t* holes_host, const int32_t* holes_dev, int H, int Dh, T* o, float* lse, int impl) {
+  const int E = H * Dh;
+  int nmax = 0; int64_t total = 0;
+  for (int64_t i = 0; i < nseq; ++i) { const int n = Nk - (holes_host[2 * i + 1] - holes_host[2 * i]); nmax = std::max(nmax, n); total += n; }
+  if constexpr (sizeof(T) == 2) {
+    if (impl != 1 && xattn_holdout_fwd_bf16(c, q, k, v, ldq, ldk, ldv, sq, sk, nseq, Sq, Nk, nmax, H, Dh, o, lse, holes_dev, total)) return;
+  }
+  const int64_t mk = c->ar.mark();
+  T* kc = aalloc<T>(c, (int64_t)nmax * E); T* vc = aalloc<T>(c, (int64_t)nmax * E);
+  auto seg = [&](T* dst, const T* src, int64_t ld_, int64_t r0, int64_t r1) {  // rows [r0, r1) of a strided [*, E] plane -> dense rows at dst
+    if (c->dry || r1 <= r0) return;
+    if (hipMemcpy2DAsync(dst, (size_t)E * sizeof(T), src + r0 * ld_, (size_t)ld_ * sizeof(T), (size_t)E * sizeof(T), (size_t)(r1 - r0), hipMemcpyDeviceToDevice,
+                         c->stream) != hipSuccess && !c->hip_err) { c->hip_err = -8; c->err = "hold-out attention: compacting the keys failed"; }
+  };
+  for (int64_t i = 0; i < nseq; ++i) {
+    const int lo = holes_host[2 * i], hi = holes_host[2 * i + 1], n = Nk - (hi - lo);
+    seg(kc, k, ldk, 0, lo); seg(kc + (int64_t)lo * E, k, ldk, hi, Nk);
+    seg(vc, v, ldv, 0, lo); seg(vc + (int64_t)lo * E, v, ldv, hi, Nk);
+    attention_fwd<T>(c, q + i * Sq * ldq, kc, vc, ldq, E, E, sq, sk, nullptr, 1, Sq, n, H, Dh, o + i * Sq * E, lse ? lse + i * H * Sq * 2 : nullptr, impl,
+                     nullptr, 0);
+  }
+  c->ar.release(mk);
+}
+
 #define INST_ATTN(T)                                                                                                                  \
   template void attention_fwd<T>(spa3d_ctx*, const T*, const T*, const T*, int64_t, int64_t, int64_t, const float*, const float*,     \
                                  const float*, int64_t, int, int, int, int, T*, float*, int, const int32_t*, int64_t);                       \
@@ -318,7 +353,9 @@ void attention_varlen_bwd(spa3d_ctx* c, const T* q, const T* k, const T* v, int6
                                         int64_t, int, const int32_t*, const int32_t*, int, int, T*, float*, int);                        \
   template void attention_varlen_bwd<T>(spa3d_ctx*, const T*, const T*, const T*, int64_t, int64_t, int64_t, const float*, const float*, \
                                         int64_t, int, const int32_t*, const int32_t*, int, int, const T*, const float*, const T*, T*, T*, T*,  \
-                                        float*, float*, int);
+                                        float*, float*, int);                                                                              \
+  template void attention_holdout_fwd<T>(spa3d_ctx*, const T*, const T*, const T*, int64_t, int64_t, int64_t, const float*, const float*, \
+                                         int64_t, int, int, const int32_t*, const int32_t*, int, int, T*, float*, int);
 INST_ATTN(float)
 INST_ATTN(bf16_t)
 }  // namespace SPA_NS

@@ -59,6 +59,26 @@ __device__ __forceinline__ void rows_load(RawRows<NP>& r, const bf16_t* __restri
     }
   }
 }
+// rows_load over a key set with a HOLE (xattn_fwd_kernel<true>): chunk row r is logical key j0 + r of the sequence, which is physical row j + (j >= lo ? gap : 0)
+// of src -- a chunk that straddles the seam takes its rows from both sides of the hole.  S: live rows of the chunk (logical keys below the sequence's count)
+template <int NP, int RPP>
+__device__ __forceinline__ void rows_load_hole(RawRows<NP>& r, const bf16_t* __restrict__ src, int64_t ld_, int S, int j0, int lo, int gap) {
+  const int part = threadIdx.x & 3, r0 = threadIdx.x >> 2;
+#pragma unroll
+  for (int ps = 0; ps < NP; ++ps) {
+    const int row = r0 + RPP * ps;
+    if (row < S) {
+      const int j = j0 + row;
+      const u16x8* p = (const u16x8*)(src + (int64_t)(j + (j >= lo ? gap : 0)) * ld_) + part;
+      r.x[ps][0] = p[0]; r.x[ps][1] = p[4]; r.x[ps][2] = p[8];
+    } else {
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) r.x[ps][c][j] = 0;
+    }
+  }
+}
 // into LDS rows of 192 B.  NORM: per-row RMSNorm * scale (attention.py:167) before the 16-bit round, as the unfused path stores it.
 template <bool NORM, int NP, int RPP>
 __device__ __forceinline__ void rows_store(RawRows<NP>& r, int S_pad, const float* __restrict__ scale, char* lds) {
@@ -257,8 +277,13 @@ struct XAttnArgs {
   const int32_t* koff;
   float* opart;   // [nprob][nsplit][Sq][96]
   float* mlpart;  // [nprob][nsplit][Sq][2]
+  // shared keys with a per-sequence hole (xattn_fwd_kernel<true>; spa3d_score_folds): every sequence reads the SAME Sk rows of k / v and leaves out rows
+  // [hole[2i], hole[2i + 1]) (device, [nseq][2]); its keys are the rows outside, in row order, addressed by LOGICAL position (rows_load_hole), so the chunks
+  // are cut exactly where a call on a compacted copy cuts them and the result is that call's, bit for bit.  nsplit covers the longest sequence.  No key mask.
+  const int32_t* hole;
 };
 
+template <bool HOLE>
 __global__ __launch_bounds__(256, 2) void xattn_fwd_kernel(XAttnArgs g) {
   constexpr int KT = XCHUNK / 16, NW = 4, S_pad = XCHUNK, RPP = NW * 16, NP = S_pad / RPP, NT = KT / NW;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -266,8 +291,10 @@ __global__ __launch_bounds__(256, 2) void xattn_fwd_kernel(XAttnArgs g) {
   const unsigned pi_u = blockIdx.x, prob_u = pi_u / (unsigned)g.nsplit, seq_u = prob_u / (unsigned)g.H;   // 32-bit: nprob * nsplit < 2^31 (xattn_fwd)
   const int64_t pi = pi_u, prob = prob_u; const int sp = (int)(pi_u - prob_u * (unsigned)g.nsplit);
   const int64_t seq = seq_u; const int h = (int)(prob_u - seq_u * (unsigned)g.H);
-  const int64_t qrow0 = seq * g.Sq, krow0 = (g.koff ? (int64_t)g.koff[seq] : seq * g.Sk) + (int64_t)sp * S_pad;
-  const int Skseq = g.koff ? g.koff[seq + 1] - g.koff[seq] : g.Sk;
+  int hlo = 0, hgap = 0;
+  if constexpr (HOLE) { hlo = g.hole[2 * seq]; hgap = g.hole[2 * seq + 1] - hlo; }
+  const int64_t qrow0 = seq * g.Sq, krow0 = HOLE ? 0 : (g.koff ? (int64_t)g.koff[seq] : seq * g.Sk) + (int64_t)sp * S_pad;
+  const int Skseq = HOLE ? g.Sk - hgap : (g.koff ? g.koff[seq + 1] - g.koff[seq] : g.Sk);
   const int Sq = g.Sq, kn = min(S_pad, Skseq - sp * S_pad), QT = (Sq + 15) / 16;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, fr = lane & 15, fq = lane >> 4;
   if (kn <= 0) {  // (ragged batches only) no key of this sequence in this chunk: the partial that the combine step weighs with exp(-inf) = 0
@@ -276,8 +303,13 @@ __global__ __launch_bounds__(256, 2) void xattn_fwd_kernel(XAttnArgs g) {
     return;
   }
   RawRows<NP> rk, rv;
-  rows_load<NP, RPP>(rk, g.k + krow0 * g.ldk + h * DH, g.ldk, kn);
-  rows_load<NP, RPP>(rv, g.v + krow0 * g.ldv + h * DH, g.ldv, kn);
+  if constexpr (HOLE) {
+    rows_load_hole<NP, RPP>(rk, g.k + h * DH, g.ldk, kn, sp * S_pad, hlo, hgap);
+    rows_load_hole<NP, RPP>(rv, g.v + h * DH, g.ldv, kn, sp * S_pad, hlo, hgap);
+  } else {
+    rows_load<NP, RPP>(rk, g.k + krow0 * g.ldk + h * DH, g.ldk, kn);
+    rows_load<NP, RPP>(rv, g.v + krow0 * g.ldv + h * DH, g.ldv, kn);
+  }
   u16x8 qx[NT][3];
 #pragma unroll
   for (int it = 0; it < NT; ++it) {
@@ -291,7 +323,7 @@ __global__ __launch_bounds__(256, 2) void xattn_fwd_kernel(XAttnArgs g) {
   for (int t = tid; t < S_pad; t += NW * 64) {
     float b = 0.f;
     if (t >= kn) b = -__builtin_inff();
-    else if (g.km && g.km[krow0 + t] == 0.f) b = NEG_BIG;
+    else if (!HOLE && g.km && g.km[krow0 + t] == 0.f) b = NEG_BIG;
     kbias[t] = b;
   }
   __syncthreads();
@@ -427,22 +459,23 @@ static bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 static bool xattn_fwd(spa3d_ctx* c, const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq,
                       const float* sk, const float* km, int64_t nseq, int Sq, int Sk, int H, bf16_t* o, float* lse, const int32_t* seq_off,
-                      const int32_t* koff = nullptr, int64_t total_keys = 0) {
-  const int nsplit = (Sk + XCHUNK - 1) / XCHUNK;
+                      const int32_t* koff = nullptr, int64_t total_keys = 0, const int32_t* hole = nullptr, int Nk = 0) {
+  const int nsplit = (Sk + XCHUNK - 1) / XCHUNK;  // (hole: Sk is the longest sequence's key count, Nk the shared rows)
   const int64_t nprob = nseq * H;
   if (seq_off || Sq < 1 || Sq > XCHUNK || Sk < 1 || nprob * nsplit > 0x7fffffffLL) return false;
   if (ldq % 8 || ldk % 8 || ldv % 8 || !al16(q) || !al16(k) || !al16(v) || !al16(o)) return false;
   const int64_t mk = c->ar.mark();
   XAttnArgs a; a.q = q; a.k = k; a.v = v; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.sq = sq; a.sk = sk; a.km = km;
-  a.Sq = Sq; a.Sk = Sk; a.H = H; a.nsplit = nsplit; a.nprob = nprob; a.koff = koff;
+  a.Sq = Sq; a.Sk = hole ? Nk : Sk; a.H = H; a.nsplit = nsplit; a.nprob = nprob; a.koff = koff; a.hole = hole;
   a.opart = (float*)c->ar.alloc(nprob * nsplit * Sq * DH * (int64_t)sizeof(float));
   a.mlpart = (float*)c->ar.alloc(nprob * nsplit * Sq * 2 * (int64_t)sizeof(float));
   if (!c->dry) {
-    const double keys = koff ? (double)total_keys / (double)nseq : (double)Sk;  // keys per sequence actually present
+    const double keys = koff || hole ? (double)total_keys / (double)nseq : (double)Sk;  // keys per sequence actually present
     ProfScope ps(c, PROF_ATTN_FWD, 4.0 * (double)nprob * Sq * keys * DH, (double)nprob * (2.0 * Sq + 2.0 * keys) * DH * 2.0);
     ps.tag(nseq, Sk, H, Sq);
     const int lds = 2 * img_bytes(XCHUNK) + XCHUNK * 4;
-    xattn_fwd_kernel<<<(unsigned)(nprob * nsplit), 256, lds, c->stream>>>(a);
+    if (hole) xattn_fwd_kernel<true><<<(unsigned)(nprob * nsplit), 256, lds, c->stream>>>(a);
+    else xattn_fwd_kernel<false><<<(unsigned)(nprob * nsplit), 256, lds, c->stream>>>(a);
     const int64_t nrows = nprob * Sq;
     xattn_combine_kernel<<<(unsigned)((nrows + 3) / 4), 256, 0, c->stream>>>(a.opart, a.mlpart, nsplit, Sq, H, nrows, o, lse);
     SPA_LAUNCH_CHECK(c);
@@ -458,6 +491,15 @@ bool xattn_varlen_fwd_bf16(spa3d_ctx* c, const bf16_t* q, const bf16_t* k, const
                            int64_t total_keys) {
   if (Dh != DH || !koff) return false;
   return xattn_fwd(c, q, k, v, ldq, ldk, ldv, sq, sk, nullptr, nseq, Sq, Skmax, H, o, lse, nullptr, koff, total_keys);
+}
+
+// cross attention of nseq sequences over ONE shared key set [0, Nk), sequence i leaving out rows [hole[2i], hole[2i + 1]) (device, [nseq][2]); nmax = the
+// longest sequence's key count, total_keys their sum (profiling).  false: shape outside the kernel (the caller then runs the sequences one by one)
+bool xattn_holdout_fwd_bf16(spa3d_ctx* c, const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq,
+                            const float* sk, int64_t nseq, int Sq, int Nk, int nmax, int H, int Dh, bf16_t* o, float* lse, const int32_t* hole,
+                            int64_t total_keys) {
+  if (Dh != DH || !hole || nmax < 1 || nmax > Nk) return false;
+  return xattn_fwd(c, q, k, v, ldq, ldk, ldv, sq, sk, nullptr, nseq, Sq, nmax, H, o, lse, nullptr, nullptr, total_keys, hole, Nk);
 }
 
 constexpr int ATTN_MAX_S = 320;  // K^ and V of one head resident: 2 x 320 x 192 B = 120 KiB of the CU's 160 KiB

@@ -419,6 +419,9 @@ template <typename T>
 void attention_varlen_bwd(spa3d_ctx* c, const T* q, const T* k, const T* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq, const float* sk,
                           int64_t nseq, int Sq, const int32_t* koff_host, const int32_t* koff_dev, int H, int Dh, const T* o, const float* lse,
                           const T* d_o, T* dq, T* dk, T* dv, float* dsq, float* dsk, int impl);
+template <typename T>
+void attention_holdout_fwd(spa3d_ctx* c, const T* q, const T* k, const T* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq, const float* sk,
+                           int64_t nseq, int Sq, int Nk, const int32_t* holes_host, const int32_t* holes_dev, int H, int Dh, T* o, float* lse, int impl);
 // embed.hip
 template <typename T> void k_sin_embed(spa3d_ctx*, const float* x, int64_t rows, int C, int nf, float prescale, T* out);
 template <typename T> void k_embed_tokens(spa3d_ctx*, const float* tracks, int64_t nrows, int T_, int nf, float prescale, T* sinbuf, int NC = 3);

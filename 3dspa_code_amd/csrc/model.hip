@@ -24,6 +24,7 @@ struct RunArgs {
   const int32_t* cn; const int32_t* cq;  // ragged batch (spa3d_set_counts): host arrays [B] of live support tracks / live queries per sample; null = all N / all Q
   const spa3d_scores* score;  // spa3d_score: per-track scores of every emitted query row, straight from the head (emit_scores); null everywhere else
   const float* w;  // train: the point weights [B,Q,T_out] (spa3d_set_point_weights; run() has checked their shape), addressed with the visibility targets' offsets; null = 1
+  int nfold; const int32_t* fold_off;  // spa3d_score_folds: the F folds of every clip (host, [nfold + 1]; validated by the entry point); 0 / null everywhere else
 };
 
 namespace SPA_NS {
@@ -78,6 +79,9 @@ constexpr double SHARE_MAX_FRAC = 0.45;  // Share is used when slots <= 45 % of 
 // NT GEMMs run on the row count rounded up to 8 (the persistent kernels want M % 8 == 0; rows are independent there and every compact
 // buffer carries the slack); reductions over rows (dW, LayerNorm, attention) use the exact count.
 struct Rag { const int32_t* off = nullptr; int64_t rows = 0; };
+// Cross attention of a leave-fold-out round (spa3d_score_folds): the nseq sequences share ONE key set of Nk rows and sequence i leaves out the rows
+// [lo_i, hi_i) = entries 2i, 2i + 1 of host / dev (the same 2 nseq values on both sides)
+struct Holes { const int32_t* host = nullptr; const int32_t* dev = nullptr; int Nk = 0; };
 
 template <typename T> struct Net {
   spa3d_ctx* c; const spa3d_config& g; const float* P; float* G;
@@ -264,7 +268,8 @@ template <typename T> struct Net {
   // ------------------------------------------------------------------ ImprovedTransformerBlock (attention.py:67-108)
   // koff_h / koff_d (host / device, [nseq + 1]): cross attention against RAGGED key sets -- sequence i attends rows [koff[i], koff[i + 1]) of kv
   void block_fwd(const BlockW<T>& w, const T* x, T* y, int64_t nseq, int S, const float* km, const T* kv, int Skv, BlockStash<T>* st,
-                 const Rag& rg = Rag(), const Share<T>* sh = nullptr, const int32_t* koff_h = nullptr, const int32_t* koff_d = nullptr) {
+                 const Rag& rg = Rag(), const Share<T>* sh = nullptr, const int32_t* koff_h = nullptr, const int32_t* koff_d = nullptr,
+                 const Holes* hl = nullptr) {  // hl: cross attention against ONE shared key set of hl->Nk rows of kv, a hole per sequence (forward only)
     const int64_t M = rg.off ? rg.rows : nseq * S, Mg = rg.off ? (M + 7) & ~int64_t(7) : M; const int d = w.d;  // Mg: NT-GEMM rows (see Rag)
     int64_t mk = c->ar.mark();
     T *nq, *qkv; float* st1;
@@ -299,10 +304,11 @@ template <typename T> struct Net {
     T *cq = nullptr, *ckv = nullptr, *co = nullptr; float* clse = nullptr;
     if (w.cross) {                                                                      // :92-100
       cq = alloc<T>(M * E); lin_fwd(w.cq, nq, cq, M);
-      const int64_t nkv = koff_h ? koff_h[nseq] : nseq * Skv;
+      const int64_t nkv = hl ? hl->Nk : (koff_h ? koff_h[nseq] : nseq * Skv);  // (shared keys: projected ONCE, not per sequence)
       ckv = alloc<T>(nkv * 2 * E); lin_fwd(w.ckv, kv, ckv, nkv);
       co = alloc<T>(M * E); clse = alloc<float>(M * H * 2);
-      if (koff_h) attention_varlen_fwd<T>(c, cq, ckv, ckv + E, E, 2 * E, 2 * E, w.csq, w.csk, nseq, S, koff_h, koff_d, H, Dh, co, clse, c->attn_impl);
+      if (hl) attention_holdout_fwd<T>(c, cq, ckv, ckv + E, E, 2 * E, 2 * E, w.csq, w.csk, nseq, S, hl->Nk, hl->host, hl->dev, H, Dh, co, clse, c->attn_impl);
+      else if (koff_h) attention_varlen_fwd<T>(c, cq, ckv, ckv + E, E, 2 * E, 2 * E, w.csq, w.csk, nseq, S, koff_h, koff_d, H, Dh, co, clse, c->attn_impl);
       else attn_fwd(cq, ckv, ckv + E, E, 2 * E, 2 * E, w.csq, w.csk, nullptr, nseq, S, Skv, co, clse);
       lin_fwd(w.cout, co, a, M, EPI_NONE, a);
     }
@@ -466,6 +472,10 @@ template <typename T> struct Net {
     // packed: a chunk of SEVERAL samples of such a batch.  Their live tracks / queries are packed back to back -- the track encoder runs on
     // nseq = noff[Bc] sequences, the readout on qoff[Bc] -- and only the cheap per-sample kernels (key mask, sequence assembly, loss) loop over the samples
     bool packed = false; std::vector<int32_t> noff, qoff; int32_t* koff_dev = nullptr;
+    // folds: ONE clip as F pseudo-samples (run_folds, spa3d_score_folds).  The track encoder runs once over the clip in place (Bc = 1); the latent stacks run
+    // with Bc = F on the shared encoder rows, sequence f leaving out the rows holes_h[2f], holes_h[2f + 1]; the readout runs over a group of consecutive folds
+    // as a packed chunk whose queries are rows [q_off, q_off + qoff[Bc]) of the clip IN PLACE (no packed copy) and read the latents of folds lat_f0, lat_f0 + 1, ..
+    bool folds = false; std::vector<int32_t> holes_h; int32_t* holes_dev = nullptr; int lat_f0 = 0;
     int64_t nq() const { return packed ? (int64_t)qoff.back() : Bc * Qc; }
     int Nk = 0;  // keys of the tracks_to_latents cross attention per sample: N, or the sample's live support tracks in a ragged batch
     int64_t n_off = 0, q_off = 0; int Nc = 0, Qc = 0; bool count_plan = true;  // count_plan: false for the backward's recompute (spa3d_plan_stats counts pass A only)
@@ -615,13 +625,16 @@ template <typename T> struct Net {
     const T* x;
     if (k.packed) { k.koff_dev = alloc<int32_t>(k.Bc + 1); k_set_i32(c, k.koff_dev, k.noff.data(), k.Bc + 1); }
     const int32_t* koff_h = k.packed ? k.noff.data() : nullptr;
+    Holes hl;
+    if (k.folds) { k.holes_dev = alloc<int32_t>(2 * k.Bc); k_set_i32(c, k.holes_dev, k.holes_h.data(), 2 * k.Bc); hl.host = k.holes_h.data(); hl.dev = k.holes_dev; hl.Nk = k.Nk; }
     k.lat_in = alloc<T>(k.Bc * L * dl);
     k_broadcast_rows<T>(c, lat0, L, dl, k.lat_in, k.Bc);                                             // 3d:200
     x = k.lat_in;
     k.t2l_st.resize(t2l.blocks.size());
     for (size_t i = 0; i < t2l.blocks.size(); ++i) {
       T* y = alloc<T>(k.Bc * L * dl);
-      block_fwd(t2l.blocks[i], x, y, k.Bc, L, nullptr, k.enc_out, k.Nk, train ? &k.t2l_st[i] : nullptr, Rag(), nullptr, koff_h, k.koff_dev);  // 3d:201
+      block_fwd(t2l.blocks[i], x, y, k.Bc, L, nullptr, k.enc_out, k.Nk, train ? &k.t2l_st[i] : nullptr, Rag(), nullptr, koff_h, k.koff_dev,
+                k.folds ? &hl : nullptr);  // 3d:201
       x = y;
     }
     k.t2l_last = const_cast<T*>(x);
@@ -665,7 +678,7 @@ template <typename T> struct Net {
     const int F = NC * 2 * nf + 1;
     k.feat = alloc<float>(nq * F); k.qframe = alloc<int32_t>(nq);
     const float* qp = b->query_points + (b0 * k.Q + k.q_off) * (NC + 1);
-    if (k.packed) {  // the live query points of the chunk's samples, back to back
+    if (k.packed && !k.folds) {  // the live query points of the chunk's samples, back to back (folds: consecutive rows of the clip already)
       float* pq = alloc<float>(nq * (NC + 1));
       for (int64_t s = 0; s < k.Bc; ++s)
         copy_dd(pq + (int64_t)k.qoff[s] * (NC + 1), b->query_points + (b0 + s) * k.Q * (NC + 1), (int64_t)(k.qoff[s + 1] - k.qoff[s]) * (NC + 1) * 4);
@@ -682,7 +695,7 @@ template <typename T> struct Net {
     if (k.packed) {  // a query's sample decides which latents it reads
       for (int64_t s = 0; s < k.Bc; ++s) {
         const int64_t q0 = k.qoff[s]; const int qs = k.qoff[s + 1] - k.qoff[s];
-        if (qs > 0) k_assemble_readout<T>(c, k.qtok + q0 * dd, k.latd + s * L * Cl, k.qframe + q0, 1, qs, L, Cl, dd, k.seq0 + q0 * S * dd);
+        if (qs > 0) k_assemble_readout<T>(c, k.qtok + q0 * dd, k.latd + (k.lat_f0 + s) * L * Cl, k.qframe + q0, 1, qs, L, Cl, dd, k.seq0 + q0 * S * dd);
       }
     }
     else k_assemble_readout<T>(c, k.qtok, k.latd, k.qframe, k.Bc, k.Qc, L, Cl, dd, k.seq0);
@@ -907,7 +920,7 @@ template <typename T>
 static void emit_scores(spa3d_ctx* c, const RunArgs& a, Net<T>& net, typename Net<T>::Chunk& k, int64_t b0) {
   const spa3d_batch* b = a.b; const int To = c->cfg.num_output_frames;
   ScoreArgs s = score_args(b, a.score, To, net.NC);
-  if (k.packed) {  // targets and results stay in the padded layout: sample by sample, padded rows zeroed
+  if (k.packed && !k.folds) {  // targets and results stay in the padded layout: sample by sample, padded rows zeroed
     for (int64_t i = 0; i < k.Bc; ++i) {
       const int64_t r = (b0 + i) * b->Q, q0 = k.qoff[i], qs = k.qoff[i + 1] - k.qoff[i];
       s.head = k.head + q0 * 4 * To; s.nq = qs; s.row0 = r;
@@ -916,7 +929,7 @@ static void emit_scores(spa3d_ctx* c, const RunArgs& a, Net<T>& net, typename Ne
     }
     return;
   }
-  s.head = k.head; s.nq = k.Bc * k.Qc; s.row0 = b0 * b->Q + k.q_off;
+  s.head = k.head; s.nq = k.nq(); s.row0 = b0 * b->Q + k.q_off;  // (folds: the group's queries are consecutive rows of the clip, in batch row order)
   k_score_rows(c, s);
 }
 
@@ -926,7 +939,7 @@ static void emit_outputs(spa3d_ctx* c, const RunArgs& a, Net<T>& net, typename N
   if (a.score) { emit_scores<T>(c, a, net, k, b0); if (!a.out) return; }  // spa3d_score(out = NULL) writes no prediction tensor at all
   const spa3d_batch* b = a.b; const int To = c->cfg.num_output_frames, NC = net.NC;
   const bool train = a.mode == MODE_TRAIN;
-  if (k.packed) {  // outputs and targets stay in the padded layout: sample by sample, and the padded query rows read as 0
+  if (k.packed && !k.folds) {  // outputs and targets stay in the padded layout: sample by sample, and the padded query rows read as 0
     for (int64_t s = 0; s < k.Bc; ++s) {
       const int64_t r = (b0 + s) * b->Q, q0 = k.qoff[s], qs = k.qoff[s + 1] - k.qoff[s], pad = b->Q - qs;
       float* tr = a.out && a.out->tracks ? a.out->tracks + r * To * NC : nullptr;
@@ -940,7 +953,7 @@ static void emit_outputs(spa3d_ctx* c, const RunArgs& a, Net<T>& net, typename N
     }
     return;
   }
-  const int64_t nq = k.Bc * k.Qc, qrow = b0 * b->Q + k.q_off;
+  const int64_t nq = k.nq(), qrow = b0 * b->Q + k.q_off;
   float* tr = a.out && a.out->tracks ? a.out->tracks + qrow * To * NC : nullptr;
   float* vl = a.out && a.out->visible_logits ? a.out->visible_logits + qrow * To : nullptr;
   float* cl = a.out && a.out->certain_logits ? a.out->certain_logits + qrow * To : nullptr;
@@ -1023,6 +1036,48 @@ static void run_sample_intra(spa3d_ctx* c, const RunArgs& a, Net<T>& net, typena
   }
 }
 
+// spa3d_score_folds: a leave-fold-out round over every clip, one clip at a time.  The track encoder -- per track, and by far the largest stage -- runs ONCE
+// over the clip's N tracks; the latent stacks run on F sequences that share its output rows (the K / V projection of tracks_to_latents once over the N
+// rows, the cross attention with fold f's rows left out of sequence f: Holes); the readout decodes every track once, against the latents of its own fold,
+// over groups of G consecutive folds (G: the most that fit the workspace), released between groups.  Forward only; nothing but the prune count is read back.
+template <typename T>
+static void run_folds(spa3d_ctx* c, const RunArgs& a, Net<T>& net, const float* noise, float* sums, unsigned* poison, int G) {
+  const spa3d_batch* b = a.b; const spa3d_config& g = c->cfg;
+  const int F = a.nfold; const int64_t LL = (int64_t)g.num_latent_tokens * g.latent_token_dim;
+  for (int64_t b0 = 0; b0 < b->B; ++b0) {
+    typename Net<T>::Chunk k{};
+    c->last_chunk = b0 + 1 >= b->B;
+    k.Bc = 1; k.N = b->N; k.Q = b->Q; k.T_ = b->T; k.S = b->T + 1; k.nseq = b->N; k.Nc = b->N; k.Qc = b->Q; k.Nk = b->N;
+    k.folds = true;
+    const int64_t mk = c->ar.mark();
+    poison_from(c, mk);
+    net.encode_tracks(k, b, b0, false);  // the clip in place: no packed copy
+    k.Bc = F;
+    for (int f = 0; f < F; ++f) { k.holes_h.push_back(a.fold_off[f]); k.holes_h.push_back(a.fold_off[f + 1]); }
+    net.encode_latents(k, false);
+    const float* nz = nullptr;
+    if (noise) {  // every fold of the clip discretises with the clip's noise
+      float* nb = net.template alloc<float>(F * LL);
+      for (int f = 0; f < F; ++f) net.copy_dd(nb + f * LL, noise + b0 * LL, LL * 4);
+      nz = nb;
+    }
+    net.decode_latents(k, b, k.latents, nz, 0, false);
+    k.packed = k.ragged = true;
+    for (int f0 = 0; f0 < F; f0 += G) {
+      const int f1 = std::min(F, f0 + G);
+      k.Bc = f1 - f0; k.lat_f0 = f0; k.q_off = a.fold_off[f0];
+      k.qoff.clear();
+      for (int f = f0; f <= f1; ++f) k.qoff.push_back(a.fold_off[f] - a.fold_off[f0]);
+      const int64_t mq = c->ar.mark();
+      poison_from(c, mq);
+      net.decode_queries(k, b, b0, false);
+      emit_outputs<T>(c, a, net, k, b0, sums, poison);
+      c->ar.release(mq);
+    }
+    c->ar.release(mk);
+  }
+}
+
 template <typename T>
 void run_body(spa3d_ctx* c, const RunArgs& a, int Bc) {
   const spa3d_config& g = c->cfg; const spa3d_batch* b = a.b;
@@ -1069,7 +1124,8 @@ void run_body(spa3d_ctx* c, const RunArgs& a, int Bc) {
   const bool intra = c->query_chunk > 0 || c->track_chunk > 0;  // run() has made Bc = 1
   // The ragged chunk (B % Bc samples) runs FIRST, so the last chunk -- the one under whose track-encoder backward the gradient segments are all-reduced -- is a
   // full one (B = 64, Bc = 9: 9 samples of encoder backward to hide behind instead of 1)
-  for (int64_t b0 = 0, cur = 0; b0 < b->B; b0 += cur) {
+  if (a.nfold > 0) run_folds<T>(c, a, net, noise, sums, poison, Bc);  // (Bc: folds per readout group)
+  else for (int64_t b0 = 0, cur = 0; b0 < b->B; b0 += cur) {
     typename Net<T>::Chunk k{};
     cur = (b0 == 0 && b->B % Bc) ? b->B % Bc : std::min<int64_t>(Bc, b->B - b0);
     c->last_chunk = b0 + cur >= b->B;
@@ -1374,6 +1430,62 @@ int spa3d_score(spa3d_handle h, const float* params, const spa3d_batch* b, spa3d
   if (rc) return rc;
   RunArgs a{}; a.mode = MODE_FORWARD; a.P = params; a.b = b; a.out = out; a.score = scores;  // the forward pass: no stash, no backward
   return run(h, a, ws, ws_bytes, stream);
+}
+// the near-equal split of N tracks into F folds, larger folds first (what spa3d.fold_offsets gives): what the workspace function sizes for
+static std::vector<int32_t> equal_folds(int N, int F) {
+  std::vector<int32_t> off(1, 0);
+  for (int f = 0; f < F; ++f) off.push_back(off.back() + N / F + (f < N % F ? 1 : 0));
+  return off;
+}
+int64_t spa3d_score_folds_workspace_bytes(spa3d_handle h, int32_t N, int32_t T, int32_t num_folds) {
+  if (!h || h->cfg.model_kind != 0 || T <= 0 || num_folds < 2 || num_folds > 64 || N < num_folds) return -1;
+  const std::vector<int32_t> off = equal_folds(N, num_folds);
+  spa3d_batch b{}; b.B = 1; b.N = N; b.Q = N; b.T = T; b.discretize = 1;
+  const float* fake = (const float*)(uintptr_t)0x100000;  // never dereferenced (see spa3d_workspace_bytes)
+  b.support_tracks = fake; b.support_tracks_visible = fake; b.query_points = fake; b.boundary_frame = (const int32_t*)fake;
+  b.query_tracks = fake; b.query_tracks_visible = fake;
+  b.dino_features = h->cfg.dino_feature_dim > 0 ? (const void*)fake : nullptr;
+  b.depth_features = h->cfg.depth_feature_dim > 0 ? (const void*)fake : nullptr;
+  RunArgs a{}; a.mode = MODE_FORWARD; a.b = &b; a.nfold = num_folds; a.fold_off = off.data();
+  return dry_need(h, a, 1);  // the readout one fold at a time: the least a call with these folds can run in
+}
+int spa3d_score_folds(spa3d_handle h, const float* params, const spa3d_batch* b, int32_t num_folds, const int32_t* fold_off, spa3d_scores* scores,
+                      spa3d_outputs* out, void* ws, int64_t ws_bytes, void* stream) {
+  if (!h || !params) return SPA3D_ERR_ARG;
+  h->err.clear(); h->hip_err = 0;
+  auto refuse = [&](const std::string& m) { h->err = "score_folds: " + m; return SPA3D_ERR_ARG; };
+  int rc = check_batch(h, b, MODE_FORWARD);
+  if (rc) return rc;
+  if (b->Q != b->N) return refuse("the batch must have Q == N (query row q of a clip is its track q), got Q = " + std::to_string(b->Q) + ", N = " + std::to_string(b->N));
+  if (num_folds < 2 || num_folds > 64) return refuse("num_folds = " + std::to_string(num_folds) + " is outside [2, 64]");
+  if (!fold_off) return refuse("fold_off is required");
+  if (fold_off[0] != 0 || fold_off[num_folds] != b->N) return refuse("fold_off must start at 0 and end at N = " + std::to_string(b->N));
+  for (int f = 0; f < num_folds; ++f)
+    if (fold_off[f + 1] <= fold_off[f]) return refuse("fold_off must be strictly increasing (fold_off[" + std::to_string(f + 1) + "] = " + std::to_string(fold_off[f + 1]) + ")");
+  spa3d_batch bb = *b;
+  if (!bb.query_tracks && !bb.query_tracks_visible) {  // the targets are the support tensors themselves: no copy
+    if (b->T != h->cfg.num_output_frames) return refuse("targets left NULL need T == num_output_frames, got T = " + std::to_string(b->T) + ", num_output_frames = " + std::to_string(h->cfg.num_output_frames));
+    bb.query_tracks = b->support_tracks; bb.query_tracks_visible = b->support_tracks_visible;
+  }
+  if (h->cfg.model_kind != 0) return refuse("not supported by the 2-D model (model_kind 1)");
+  if (h->has_cnt_n || h->has_cnt_q) return refuse("per-sample counts (spa3d_set_counts) cannot be combined with folds");
+  if (h->track_chunk > 0 || h->query_chunk > 0) return refuse("\"track_chunk\" / \"query_chunk\" cannot be combined with folds");
+  rc = check_scores(h, &bb, scores);
+  if (rc) return rc;
+  RunArgs a{}; a.mode = MODE_FORWARD; a.P = params; a.b = &bb; a.out = out; a.score = scores; a.nfold = num_folds; a.fold_off = fold_off;
+  const int64_t need = std::max(spa3d_score_folds_workspace_bytes(h, b->N, b->T, num_folds), dry_need(h, a, 1));
+  if (!ws || ws_bytes < need) return refuse("workspace too small: need " + std::to_string(need) + " bytes");
+  int lo = 1, hi = num_folds;  // folds per readout group: the most that fit
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) / 2;
+    if (dry_need(h, a, mid) <= ws_bytes) lo = mid; else hi = mid - 1;
+  }
+  h->stream = (hipStream_t)stream;
+  h->ar = Arena(); h->ar.base = (char*)ws; h->ar.cap = ws_bytes; h->dry = false;
+  for (double& v : h->plan_stats) v = 0;
+  run_dispatch(h, a, lo);
+  if (h->ar.overflow) { h->err = "internal: arena overflow"; return SPA3D_ERR_WORKSPACE; }
+  return h->hip_err ? SPA3D_ERR_HIP : SPA3D_OK;
 }
 int spa3d_score_from_preds(spa3d_handle h, const spa3d_batch* b, const spa3d_outputs* preds, spa3d_scores* scores, void* stream) {
   if (!h) return SPA3D_ERR_ARG;

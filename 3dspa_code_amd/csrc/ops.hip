@@ -111,6 +111,9 @@ int spa3d_op_layernorm_bwd_f16(const void* x, const float* scale, const float* s
 int spa3d_op_attention_f16(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* scale_q,
                            const float* scale_k, const float* keymask, int64_t nseq, int32_t Sq, int32_t Sk, int32_t H, int32_t Dh, void* o,
                            float* lse, int32_t dtype, int32_t impl, void* ws, int64_t ws_bytes, void* stream);
+int spa3d_op_attention_holdout_f16(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* scale_q,
+                                   const float* scale_k, int64_t nseq, int32_t Sq, int32_t Nk, int32_t H, int32_t Dh, const int32_t* holes, void* o,
+                                   float* lse, int32_t dtype, int32_t impl, void* ws, int64_t ws_bytes, void* stream);
 int spa3d_op_attention_bwd_f16(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* scale_q,
                                const float* scale_k, const float* keymask, int64_t nseq, int32_t Sq, int32_t Sk, int32_t H, int32_t Dh,
                                const void* o, const float* lse, const void* d_o, void* dq, void* dk, void* dv, float* dscale_q,
@@ -127,6 +130,7 @@ int spa3d_op_attention_bwd_f16(const void* q, const void* k, const void* v, int6
 #define spa3d_op_layernorm_bwd spa3d_op_layernorm_bwd_f16
 #define spa3d_op_attention spa3d_op_attention_f16
 #define spa3d_op_attention_bwd spa3d_op_attention_bwd_f16
+#define spa3d_op_attention_holdout spa3d_op_attention_holdout_f16
 #define FWD16(call)
 #else
 #define FWD16(call) if (dtype == SPA3D_F16) return call;
@@ -220,6 +224,28 @@ int spa3d_op_attention(const void* q, const void* k, const void* v, int64_t ldq,
   else
     attention_fwd<bf16_t>(&c, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv, scale_q, scale_k, keymask, nseq, Sq, Sk, H,
                           Dh, (bf16_t*)o, lse, c.attn_impl);
+  return c.status();
+}
+int spa3d_op_attention_holdout(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* scale_q,
+                               const float* scale_k, int64_t nseq, int32_t Sq, int32_t Nk, int32_t H, int32_t Dh, const int32_t* holes, void* o,
+                               float* lse, int32_t dtype, int32_t impl, void* ws, int64_t ws_bytes, void* stream) {
+  FWD16(spa3d_op_attention_holdout_f16(q, k, v, ldq, ldk, ldv, scale_q, scale_k, nseq, Sq, Nk, H, Dh, holes, o, lse, dtype, impl, ws, ws_bytes, stream))
+  if (!q || !k || !v || !o || !scale_q || !scale_k || !holes || Dh < 1 || Dh > 128 || nseq < 1 || nseq > (1 << 20) || Sq < 1 || Nk < 1 || H < 1) return SPA3D_ERR_ARG;
+  for (int64_t i = 0; i < nseq; ++i) {  // a hole outside [0, Nk], lo > hi, a sequence left without a key
+    const int64_t lo = holes[2 * i], hi = holes[2 * i + 1];
+    if (lo < 0 || hi > Nk || lo > hi || hi - lo >= Nk) return SPA3D_ERR_ARG;
+  }
+  OpCtx c(stream, ws, ws_bytes);
+  apply_attn_impl(&c, impl);
+  int32_t* hd = c.alloc<int32_t>(2 * nseq);
+  if (c.ar.overflow) return SPA3D_ERR_WORKSPACE;
+  k_set_i32(&c, hd, holes, 2 * nseq);
+  if (dtype == SPA3D_F32)
+    attention_holdout_fwd<float>(&c, (const float*)q, (const float*)k, (const float*)v, ldq, ldk, ldv, scale_q, scale_k, nseq, Sq, Nk, holes, hd, H, Dh,
+                                 (float*)o, lse, c.attn_impl);
+  else
+    attention_holdout_fwd<bf16_t>(&c, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv, scale_q, scale_k, nseq, Sq, Nk, holes, hd, H,
+                                  Dh, (bf16_t*)o, lse, c.attn_impl);
   return c.status();
 }
 int spa3d_op_attention_bwd(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* scale_q,

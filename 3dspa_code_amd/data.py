@@ -306,6 +306,20 @@ def validate_counts(counts, B: int, limit: int, name: str, minimum: int):
   return out
 
 
+def fold_offsets(num_tracks: int, folds: int) -> np.ndarray:
+  """The offsets [folds + 1] (int32) that cut num_tracks tracks into `folds` contiguous folds of near-equal size, the larger folds first: what
+  model.score_all(folds=int) uses and spa3d_score_folds_workspace_bytes sizes for.  Contiguous folds of a shuffled clip are random folds."""
+  if isinstance(folds, bool) or not isinstance(folds, (int, np.integer)) or isinstance(num_tracks, bool) or not isinstance(num_tracks, (int, np.integer)):
+    raise ValueError(f'num_tracks and folds must be ints, got {num_tracks!r}, {folds!r}')
+  if folds < 2 or folds > 64:
+    raise ValueError(f'folds must lie in [2, 64], got {folds}')
+  if folds > num_tracks:
+    raise ValueError(f'{folds} folds need at least as many tracks, got {num_tracks}')
+  sizes = np.full(folds, num_tracks // folds, dtype=np.int64)
+  sizes[:num_tracks % folds] += 1
+  return np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+
+
 def collate_ragged(samples, pad_value: float = 0.0):
   """A list of per-clip dicts (support keys [n_b, T, ...], query keys [q_b, ...], `boundary_frame` a scalar or [1]; no batch axis) -> one
   padded batch ([B, max n_b, T, ...], [B, max q_b, ...]) with `support_count` / `query_count` (int32 [B]).  Rows at or beyond a count are

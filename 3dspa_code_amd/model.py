@@ -23,7 +23,7 @@ from typing import Any, Dict, Optional
 import torch
 
 from . import _lib
-from .data import validate_counts
+from .data import fold_offsets, validate_counts
 
 
 # ------------------------------------------------------------------------------------------------
@@ -779,6 +779,118 @@ class TrackAutoEncoder3D:
     with _counts_on(h, b):
       _lib.check(_lib.load().spa3d_score(h, flat.data_ptr(), C.byref(b), C.byref(sc), outp, ws.data_ptr(), ws.numel(), _stream(flat)),
                  h, 'spa3d_score')
+    return res
+
+  def score_all(self, variables, batch, folds=8, thresholds=(), sample_scale=None, frame_errors: bool = False, return_predictions: bool = False,
+                discretize: bool = True, noise=None) -> TrackScores:
+    """Scores for EVERY track of every clip in one call (spa3d_score_folds): the tracks of each of `folds` contiguous folds are reconstructed from
+    the clip's other tracks, and the result has [B, N, ..] shapes -- row n is track n.  The track encoder runs once per clip, not once per fold.
+    folds: an int (fold_offsets(N, folds): near-equal sizes) or an offsets array [F + 1] from 0 to N, strictly increasing, 2 <= F <= 64; the same
+    for every clip.  Contiguous folds are random folds when the tracks were shuffled beforehand.
+    batch: the support keys (support_tracks [B,N,T,3], support_tracks_visible, boundary_frame, dino_features / depth_features as the parameters
+    want) and either `query_frame` [B,N] ints -- track n is queried at its position in that frame -- or `query_points` [B,N,4].  The targets are
+    `query_tracks` / `query_tracks_visible` when the batch carries them as [B,N,..]; otherwise (absent, or the [B,1,..] placeholders of a
+    build_batch without queries) the support tensors themselves, which needs T == num_output_frames.  Everything is validated on the host
+    (ValueError) before any device work.  Other arguments as `score`.
+
+    One clip, every track coloured by its own reconstruction error:
+      perm = np.random.permutation(n)                                                     # random folds = contiguous folds of a shuffled clip
+      batch = spa3d.build_batch([clip], model, num_support_tracks=n, num_query_points=0, splits=[(perm, [], [])])
+      batch['query_frame'] = torch.zeros(1, n, dtype=torch.int32, device='cuda')          # every track queried at frame 0
+      sc = model.score_all(variables, batch, folds=8, frame_errors=True)
+      err = torch.empty_like(sc.frame_err[0]); err[torch.as_tensor(perm, device=err.device)] = sc.frame_err[0]   # back to the clip's own track order
+      spa3d.save_scores_npz('scores.npz', clip['tracks_3d'], err, clip['visible'], video=video, intrinsics=K, extrinsics=E)
+      frames = spa3d.visualize_npz('scores.npz')                                          # RGB uint8 [T, H, W, 3]"""
+    thr = _check_thresholds(thresholds)
+    if self._kind == 1:
+      raise ValueError('score_all is not available for the 2-D model')
+    if self.decoder_scan_chunk_size is not None or self.track_chunk_size is not None:
+      raise ValueError('score_all cannot be combined with decoder_scan_chunk_size / track_chunk_size')
+    for key in ('support_tracks', 'support_tracks_visible', 'boundary_frame'):
+      if batch.get(key) is None:
+        raise ValueError(f'score_all needs support_tracks, support_tracks_visible and boundary_frame (no {key!r})')
+    st = batch['support_tracks']
+    if not isinstance(st, torch.Tensor) or st.dim() != 4 or st.shape[-1] != 3:
+      raise ValueError(f'support_tracks must be a [B,N,T,3] tensor, got {tuple(getattr(st, "shape", ()))}')
+    B, N, T = (int(v) for v in st.shape[:3])
+    To = self.num_output_frames
+    import numpy as np
+    if isinstance(folds, (int, np.integer)) and not isinstance(folds, bool):
+      off = fold_offsets(N, int(folds))
+    else:
+      off = folds.detach().cpu().numpy() if isinstance(folds, torch.Tensor) else np.asarray(folds)
+      if off.ndim != 1 or off.size < 3 or off.size > 65 or off.dtype.kind not in 'iu':
+        raise ValueError('folds must be an int or an integer offsets array [F + 1] with 2 <= F <= 64')
+      off = off.astype('int64')
+      if off[0] != 0 or off[-1] != N or (off[1:] <= off[:-1]).any():
+        raise ValueError(f'fold offsets must start at 0, increase strictly and end at N = {N}, got {off.tolist()}')
+    F = len(off) - 1
+    cn = validate_counts(batch.get('support_count'), B, N, 'support_count', 1)
+    if cn is not None and any(c != N for c in cn):
+      raise ValueError('score_all does not take ragged batches: every support_count must equal N')
+    qf, qp = batch.get('query_frame'), batch.get('query_points')
+    if qf is not None:
+      qf = torch.as_tensor(qf)
+      if tuple(qf.shape) != (B, N) or qf.dtype.is_floating_point or qf.dtype == torch.bool:
+        raise ValueError(f'query_frame must be [B,N] = {(B, N)} ints, got {tuple(qf.shape)} {qf.dtype}')
+      if qf.numel() and (int(qf.min()) < 0 or int(qf.max()) >= T):
+        raise ValueError(f'query_frame has entries outside [0, T = {T})')
+    elif qp is None or not isinstance(qp, torch.Tensor) or tuple(qp.shape) != (B, N, 4):
+      raise ValueError(f'score_all needs query_frame [B,N] or query_points [B,N,4] = {(B, N, 4)}; got query_points {tuple(getattr(qp, "shape", ()))}')
+    qt, qv = batch.get('query_tracks'), batch.get('query_tracks_visible')
+    explicit = qt is not None and qv is not None and int(qt.shape[1]) == N
+    if qt is not None and not explicit and int(qt.shape[1]) != 1:
+      raise ValueError(f'query_tracks must be [B,N,T,3] targets (or absent), got {tuple(qt.shape)}')
+    if explicit and (tuple(qt.shape) != (B, N, To, 3) or tuple(qv.shape[:3]) != (B, N, To)):
+      raise ValueError(f'query_tracks must be {(B, N, To, 3)} and query_tracks_visible {(B, N, To, 1)}')
+    if not explicit and T != To:
+      raise ValueError(f'targets that default to the support tensors need T == num_output_frames, got T = {T}, num_output_frames = {To}')
+    # ---- device work from here on
+    params = variables['params'] if 'params' in variables and isinstance(variables['params'], dict) else variables
+    dino, depth = self._dims_from_params(params)
+    h, _, _ = self._handle(dino, depth)
+    flat = self.flat_from_tree(params)
+    _require_cuda(flat, 'params')
+    dev = flat.device
+    if qf is not None:  # the query point of track n: (frame, its position in that frame)
+      _require_cuda(st, 'support_tracks')
+      idx = qf.to(device=st.device, dtype=torch.int64)
+      pos = torch.gather(st.to(torch.float32), 2, idx[:, :, None, None].expand(B, N, 1, 3))[:, :, 0]
+      qp = torch.cat([idx[..., None].to(torch.float32), pos], dim=-1)
+    inputs = {k: v for k, v in batch.items() if k not in ('support_count', 'query_count', 'query_points')}
+    lib = _lib.load()
+    if noise is None and discretize:  # the library's own draw, made here: the workspace need then does not depend on B
+      noise = torch.empty(B, self.num_latent_tokens, self.latent_token_dim, dtype=torch.float32, device=dev)
+      _lib.check(lib.spa3d_uniform_noise(noise.data_ptr(), noise.numel(), 0, 0, _stream(flat)), what='spa3d_uniform_noise')
+    b, keep = self._marshal(inputs, dino, depth, discretize=discretize, noise=noise, query_points=qp)
+    if explicit:
+      qt, qv = self._f32(qt, 'query_tracks'), self._f32(qv, 'query_tracks_visible')
+      keep += [qt, qv]
+      b.query_tracks, b.query_tracks_visible = qt.data_ptr(), qv.data_ptr()
+    self._chunk_options(h, None)
+    res, sc, keep_scale = _alloc_scores(thr, B, N, To, dev, sample_scale, frame_errors)
+    outp = None
+    if return_predictions:
+      res.predictions, out = self._alloc_outputs(B, N, dev)
+      outp = C.byref(out)
+    # workspace: at least what the call needs with the readout one fold at a time; up to one sample's forward more lets it take every fold at once
+    floor = lib.spa3d_score_folds_workspace_bytes(h, N, T, F)
+    if floor < 0:
+      raise _lib.Spa3dError(f'spa3d_score_folds_workspace_bytes refused N = {N}, T = {T}, folds = {F}')
+    want = floor + lib.spa3d_workspace_bytes(h, 1, N, N, T, 1, 0)
+    have = self._ws.numel() if (self._ws is not None and self._ws.device == torch.device(dev)) else 0
+    if have < want and not (self._ws_cap > 0 and have >= max(floor, self._ws_cap)):
+      free, _total = torch.cuda.mem_get_info(dev)
+      size = min(want, max(int((free + have) * self.workspace_fraction), floor))
+      if size > have:
+        self._ws = None
+        torch.cuda.empty_cache()
+        self._ws = torch.empty(size, dtype=torch.uint8, device=dev)
+        self._ws_cap = size if size < want else 0
+    ws = self._ws
+    offs = (C.c_int32 * (F + 1))(*[int(v) for v in off])
+    _lib.check(lib.spa3d_score_folds(h, flat.data_ptr(), C.byref(b), F, offs, C.byref(sc), outp, ws.data_ptr(), ws.numel(), _stream(flat)),
+               h, 'spa3d_score_folds')
     return res
 
   def tapvid3d(self, variables, batch, scalings=('median',), fixed_thresholds: bool = False, ratios: bool = False, discretize: bool = True, noise=None):

@@ -172,6 +172,38 @@ int spa3d_score(spa3d_handle h, const float* params, const spa3d_batch* b, spa3d
 /* The same scores from already-split predictions (as spa3d_loss): reads B, Q, the targets and the query counts only. */
 int spa3d_score_from_preds(spa3d_handle h, const spa3d_batch* b, const spa3d_outputs* preds, spa3d_scores* scores, void* stream);
 
+/* Scores for EVERY track of a clip in one call: a leave-fold-out round.  The clip's N tracks are cut into num_folds contiguous folds
+ * [fold_off[f], fold_off[f + 1]); the tracks of fold f are reconstructed from the tracks outside it, and the per-point error is their score (what
+ * upstream's visualiser paints as coords_score).  A caller who wants random folds shuffles the tracks beforehand (spa3d_build_batch with index
+ * lists does that); the same fold_off (HOST, num_folds + 1 entries) applies to every clip of the batch.
+ *   Batch: Q == N -- query row q of a clip IS its track q; query_points [B,N,4] required.  query_tracks and query_tracks_visible may both be
+ * NULL: the targets are then support_tracks / support_tracks_visible themselves (no copy), which needs T == num_output_frames.
+ *   Results: rows [fold_off[f], fold_off[f + 1]) of every output and of query_stats / frame_err are what spa3d_score gives on the batch whose
+ * support tracks are the clip's tracks outside that range, in their order, and whose queries are the rows of that range (same noise[b],
+ * boundary_frame[b] and options), up to the order of summation.  sample_stats[b] pools all N rows of the clip.  out may be NULL as in spa3d_score;
+ * out->latents is not written (a clip has num_folds latent sets).  Two runs give the same bits: no float atomics.
+ *   Work: the track encoder is per track, so it runs ONCE per clip over all N tracks, addressed in place (token pruning as usual) -- not num_folds
+ * times over N (1 - 1 / num_folds).  The latent stacks run on num_folds sequences that share the encoder's output rows: the K / V projection of each
+ * tracks_to_latents block runs once over the N rows, and its cross attention lets sequence f skip the rows of fold f (one launch of the chunked-key
+ * kernel, keys addressed by logical position, so a sequence's result is bit for bit that of the kernel on a compacted copy of its keys; the
+ * fp32 parity mode and attn_impl 1 run the sequences one by one on such a copy).  The readout decodes every track once against the latents of its
+ * own fold, the first block dense as in a packed chunk, over groups of consecutive folds: as many folds per group as fit the workspace, released
+ * between groups; the latent stages always run all folds at once.  spa3d_plan_stats reports out4[1] = sum over clips of N x (T + 1),
+ * out4[3] = sum over clips of N.  "chunk" is ignored (clips are processed one at a time); "prune", "poison", "attn_impl", "gemm_impl" and the three
+ * precisions work as elsewhere.  Asynchronous, allocates nothing, reads back nothing but the prune count.
+ *   spa3d_score_folds_workspace_bytes: the bytes for the near-equal split of N into num_folds (sizes N / num_folds, the first N % num_folds one larger)
+ * with the readout one fold at a time; -1 for arguments the call would refuse.  A larger workspace lets the readout take more folds per group.
+ * (A call that leaves noise NULL with discretize set draws the noise of all B clips into the workspace first: B x L x latent_token_dim x 4 bytes more.)
+ *   SPA3D_ERR_ARG with a message, before the first launch: Q != N; num_folds outside [2, 64], fold_off[0] != 0, fold_off not strictly increasing,
+ * fold_off[num_folds] != N; NULL targets with T != num_output_frames; a model_kind 1 handle; stored per-sample counts (spa3d_set_counts);
+ * "track_chunk" or "query_chunk" set; a workspace below what the workspace function returns, or below what this call's own folds need (the
+ * message names the bytes); the spa3d_scores refusals of spa3d_score. */
+int64_t spa3d_score_folds_workspace_bytes(spa3d_handle h, int32_t N, int32_t T, int32_t num_folds);
+int spa3d_score_folds(spa3d_handle h, const float* params, const spa3d_batch* b,
+                      int32_t num_folds, const int32_t* fold_off /* HOST [num_folds + 1] */,
+                      spa3d_scores* scores, spa3d_outputs* out /* may be NULL */,
+                      void* ws, int64_t ws_bytes, void* stream);
+
 /* TAPVid-3D metrics of existing predictions against the batch's targets: occlusion accuracy, points-within and Jaccard counts at the pixel
  * thresholds 1, 2, 4, 8, 16, with the predictions rescaled first.  tapnet, whose compute_tapvid3d_metrics upstream calls, is not vendored by
  * the reference: what follows is restated from the published definition, parity unpinned, and is the contract.
@@ -549,6 +581,16 @@ int spa3d_op_attention(const void* q, const void* k, const void* v, int64_t ldq,
                        int64_t nseq, int32_t Sq, int32_t Sk, int32_t H, int32_t Dh, void* o,
                        float* lse /* [nseq,H,Sq,2] = (row max, log row sum); written by the fused kernel only; may be NULL */,
                        int32_t dtype, int32_t impl, void* ws, int64_t ws_bytes, void* stream);
+/* The cross attention of a leave-fold-out round (spa3d_score_folds) on its own: nseq sequences of Sq queries, q [nseq,Sq,H*Dh], over ONE shared key
+ * set k, v [Nk,H*Dh]; sequence i leaves out the rows [lo_i, hi_i) = holes[2i], holes[2i + 1] and attends the rows outside, in row order.  No key
+ * mask.  o, lse and impl as spa3d_op_attention; the result of sequence i is bit for bit spa3d_op_attention's on a compacted copy of its keys
+ * (Sq queries against n_i = Nk - (hi_i - lo_i) keys, n_i != Sq).  ws holds the device copy of the holes, the fused kernel's partials or, on the
+ * generic path, the compact copy.  SPA3D_ERR_ARG: a hole outside [0, Nk], lo > hi, a sequence left without a key. */
+int spa3d_op_attention_holdout(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldk, int64_t ldv,
+                               const float* scale_q, const float* scale_k, int64_t nseq, int32_t Sq, int32_t Nk,
+                               int32_t H, int32_t Dh, const int32_t* holes /* HOST [nseq][2] = lo, hi */,
+                               void* o, float* lse, int32_t dtype, int32_t impl,
+                               void* ws, int64_t ws_bytes, void* stream);
 /* gradients of the above: dq,dk,dv dense-strided like q,k,v (same ld*); dscale_q/k f32[Dh] accumulated into */
 int spa3d_op_attention_bwd(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldk, int64_t ldv,
                            const float* scale_q, const float* scale_k, const float* keymask,
