@@ -432,7 +432,7 @@ template <typename T> void k_set_readout_rows(spa3d_ctx*, T* tok, const float* r
 void k_keymask(spa3d_ctx*, const float* visible, const int32_t* boundary, int64_t nseq, int N, int T_, float* km);
 void k_keymask2d(spa3d_ctx*, const float* visible, const int32_t* boundary, int64_t nseq, int N, int T_, float* km);  // 2-D TRAJAN twin (track_autoencoder.py:117-390)
 void k_sum3(spa3d_ctx*, const float* a, const float* b, const float* c3, float* out, int n);
-// Dense with input width K <= 4 as streaming kernels (false: shape not covered, use the GEMM path)
+// Dense with input width K <= 4 as streaming kernels (false: shape not covered, use the GEMM path); instantiated for the 16-bit type only
 template <typename T> bool k_rank_fwd(spa3d_ctx*, const T* x, const T* w /*[K][N]*/, const float* bias, T* out /*+=*/, int64_t M, int N, int K, int64_t ldo,
                                       int rgroup, int rskip);
 template <typename T> bool k_rank_bwd(spa3d_ctx*, const T* x, const T* dy, int64_t M, int N, int K, int64_t ldy, int rgroup, int rskip, float* gw /*+=*/,

@@ -200,7 +200,7 @@ void k_sum3(spa3d_ctx* c, const float* a, const float* b, const float* c3, float
 // 3.4 M x 384 tensor: pure streaming.  out[crow(m)][:] += x[m][:K] . w[K][N] + bias, crow(m) = m + (m / G + 1) * S (token rows
 // 1..T of each sequence).  8 columns (16 B) per thread.
 // ---------------------------------------------------------------------------------------------
-template <typename T, int K>
+template <typename T, int K>   // T: the 16-bit type only (see the instantiations)
 __global__ void rank_fwd_kernel(const T* __restrict__ x, const T* __restrict__ w, const float* __restrict__ bias, T* __restrict__ out,
                                 int64_t M, int N, int64_t ldo, int rgroup, int rskip) {
   constexpr int NV = 8;
@@ -384,10 +384,11 @@ template <typename T> void k_transpose(spa3d_ctx* c, const T* src, int rows, int
   template void k_embed_tokens<T>(spa3d_ctx*, const float*, int64_t, int, int, float, T*, int);                             \
   template void k_embed_maps<T>(spa3d_ctx*, const int32_t*, int64_t, int, int, int32_t*, int32_t*, T*, const float*, int);  \
   template void k_set_readout_rows<T>(spa3d_ctx*, T*, const float*, int64_t, int, int);                                     \
-  template bool k_rank_fwd<T>(spa3d_ctx*, const T*, const T*, const float*, T*, int64_t, int, int, int64_t, int, int);      \
-  template bool k_rank_bwd<T>(spa3d_ctx*, const T*, const T*, int64_t, int, int, int64_t, int, int, float*, float*);        \
   template void k_pack<T>(spa3d_ctx*, const float*, int64_t, int, int, T*, int64_t, T*, int64_t);                           \
   template void k_transpose<T>(spa3d_ctx*, const T*, int, int, T*);
 INST_EMBED(float)
 INST_EMBED(bf16_t)
+// the rank-K kernels move 8 columns per thread in ONE 16-byte access: the 16-bit types only (in float that access is 4 columns wide; no caller ever had a float use)
+template bool k_rank_fwd<bf16_t>(spa3d_ctx*, const bf16_t*, const bf16_t*, const float*, bf16_t*, int64_t, int, int, int64_t, int, int);
+template bool k_rank_bwd<bf16_t>(spa3d_ctx*, const bf16_t*, const bf16_t*, int64_t, int, int, int64_t, int, int, float*, float*);
 }  // namespace SPA_NS

@@ -581,7 +581,9 @@ template <typename T> struct Net {
     if (k.dino) lin_fwd(dino, (const T*)k.dino, k.tok0, nseq * T_, EPI_NONE, nullptr, 0, 1, 0, 0, T_, 1);
     if (k.depthf) {
       // 1-channel input: a rank-1 update of the token tensor, streamed (as a K=1 GEMM it ran at 1 TB/s); bf16 path only
-      if (!(sizeof(T) == 2 && depth.ldn == depth.N && k_rank_fwd<T>(c, (const T*)k.depthf, depth.wn, depth.bias, k.tok0, nseq * T_, depth.N, depth.K, d, T_, 1)))
+      bool streamed = false;
+      if constexpr (sizeof(T) == 2) streamed = depth.ldn == depth.N && k_rank_fwd<T>(c, (const T*)k.depthf, depth.wn, depth.bias, k.tok0, nseq * T_, depth.N, depth.K, d, T_, 1);
+      if (!streamed)
         lin_fwd(depth, (const T*)k.depthf, k.tok0, nseq * T_, EPI_NONE, nullptr, 0, 1, 0, 0, T_, 1);
     }
     if (!twoD) k_set_readout_rows<T>(c, k.tok0, readout, nseq, S, d);                                // 3d:161-165
@@ -883,7 +885,10 @@ template <typename T> struct Net {
       // token rows 1..T of every sequence (row remap on the reduction index: no compaction copy)
       lin_bwd_w(tok, k.sinbuf, dtok_dense, nseq * T_, 0, T_, 1);
       if (k.dino) lin_bwd_w(dino, (const T*)k.dino, dtok_dense, nseq * T_, 0, T_, 1);
-      if (k.depthf && !(sizeof(T) == 2 && depth.nseg == 1 && k_rank_bwd<T>(c, (const T*)k.depthf, dtok_dense, nseq * T_, depth.N, depth.K, d, T_, 1, depth.gw[0], depth.gb)))
+      bool streamed = false;
+      if constexpr (sizeof(T) == 2)
+        streamed = k.depthf && depth.nseg == 1 && k_rank_bwd<T>(c, (const T*)k.depthf, dtok_dense, nseq * T_, depth.N, depth.K, d, T_, 1, depth.gw[0], depth.gb);
+      if (k.depthf && !streamed)
         lin_bwd_w(depth, (const T*)k.depthf, dtok_dense, nseq * T_, 0, T_, 1);
     }
   }
@@ -1344,6 +1349,10 @@ int spa3d_create(const spa3d_config* cfg, spa3d_handle* out) {
   if (!cfg || !out) return SPA3D_ERR_ARG;
   if (cfg->num_heads <= 0 || cfg->qkv_size % cfg->num_heads) return SPA3D_ERR_ARG;  // attention.py:147-150
   if (cfg->qkv_size / cfg->num_heads > 128 || cfg->num_frequencies > 64 || cfg->num_frequencies <= 0) return SPA3D_ERR_ARG;
+  // the readout stack's last block (block_fwd_last) runs the single-query attention in every precision, model kind and attn_impl: only the head widths
+  // csrc/attn_q1.hip instantiates make a usable model (any other used to fail at the first forward, as a HIP-class error)
+  { const int Dh = cfg->qkv_size / cfg->num_heads;
+    if (Dh != 8 && Dh != 16 && Dh != 32 && Dh != 64 && Dh != 96 && Dh != 128) return SPA3D_ERR_ARG; }
   if (cfg->precision != SPA3D_F32 && cfg->precision != SPA3D_BF16 && cfg->precision != SPA3D_F16) return SPA3D_ERR_ARG;
   if (cfg->model_kind != 0 && cfg->model_kind != 1) return SPA3D_ERR_ARG;
   if (cfg->model_kind == 1 && (cfg->dino_feature_dim != 0 || cfg->depth_feature_dim != 0)) return SPA3D_ERR_ARG;

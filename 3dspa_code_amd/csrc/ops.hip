@@ -118,6 +118,17 @@ int spa3d_op_attention_bwd_f16(const void* q, const void* k, const void* v, int6
                                const float* scale_k, const float* keymask, int64_t nseq, int32_t Sq, int32_t Sk, int32_t H, int32_t Dh,
                                const void* o, const float* lse, const void* d_o, void* dq, void* dk, void* dv, float* dscale_q,
                                float* dscale_k, int32_t dtype, int32_t impl, void* ws, int64_t ws_bytes, void* stream);
+int spa3d_op_attention_q1_f16(const void* q0, int64_t ldq0, const void* k, const void* v, int64_t ldk, int64_t ldv, const float* scale_q,
+                              const float* scale_k, const float* keymask, const int32_t* seq_off, int64_t nseq, int32_t S, int32_t H, int32_t Dh,
+                              void* o0, float* p0, int32_t dtype, void* stream);
+int spa3d_op_attention_q1_bwd_f16(const void* q0, int64_t ldq0, const void* k, const void* v, int64_t ldk, int64_t ldv, const float* scale_q,
+                                  const float* scale_k, const float* keymask, const int32_t* seq_off, int64_t nseq, int32_t S, int32_t H, int32_t Dh,
+                                  const float* p0, const void* d_o0, void* dq0, void* dk, void* dv, float* dscale_q, float* dscale_k, int32_t dtype,
+                                  void* stream);
+int spa3d_op_rank_linear_f16(const void* x, const void* w, const float* bias, void* out, int64_t M, int32_t N, int32_t K, int64_t ldo, int32_t rgroup,
+                             int32_t rskip, int32_t dtype, void* stream);
+int spa3d_op_rank_linear_bwd_f16(const void* x, const void* dy, int64_t M, int32_t N, int32_t K, int64_t ldy, int32_t rgroup, int32_t rskip, float* gw,
+                                 float* gb, int32_t dtype, void* stream);
 #pragma GCC visibility pop
 }
 #if SPA_F16
@@ -131,6 +142,10 @@ int spa3d_op_attention_bwd_f16(const void* q, const void* k, const void* v, int6
 #define spa3d_op_attention spa3d_op_attention_f16
 #define spa3d_op_attention_bwd spa3d_op_attention_bwd_f16
 #define spa3d_op_attention_holdout spa3d_op_attention_holdout_f16
+#define spa3d_op_attention_q1 spa3d_op_attention_q1_f16
+#define spa3d_op_attention_q1_bwd spa3d_op_attention_q1_bwd_f16
+#define spa3d_op_rank_linear spa3d_op_rank_linear_f16
+#define spa3d_op_rank_linear_bwd spa3d_op_rank_linear_bwd_f16
 #define FWD16(call)
 #else
 #define FWD16(call) if (dtype == SPA3D_F16) return call;
@@ -265,6 +280,61 @@ int spa3d_op_attention_bwd(const void* q, const void* k, const void* v, int64_t 
     attention_bwd<bf16_t>(&c, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv, scale_q, scale_k, keymask, nseq, Sq, Sk, H,
                           Dh, (const bf16_t*)o, lse, (const bf16_t*)d_o, (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, dscale_q, dscale_k, c.attn_impl);
   return c.status();
+}
+
+// Single-query attention and the rank-K projection: every shape their launchers would record as a HIP-class error (or decline) is an argument error here
+static bool q1_shape_ok(int64_t nseq, int32_t S, int32_t H, int32_t Dh) {
+  const bool width = Dh == 8 || Dh == 16 || Dh == 32 || Dh == 64 || Dh == 96 || Dh == 128;   // the instantiations of csrc/attn_q1.hip
+  return width && S >= 1 && S <= 320 && H >= 1 && nseq >= 0;
+}
+int spa3d_op_attention_q1(const void* q0, int64_t ldq0, const void* k, const void* v, int64_t ldk, int64_t ldv, const float* scale_q,
+                          const float* scale_k, const float* keymask, const int32_t* seq_off, int64_t nseq, int32_t S, int32_t H, int32_t Dh,
+                          void* o0, float* p0, int32_t dtype, void* stream) {
+  FWD16(spa3d_op_attention_q1_f16(q0, ldq0, k, v, ldk, ldv, scale_q, scale_k, keymask, seq_off, nseq, S, H, Dh, o0, p0, dtype, stream))
+  if (!q0 || !k || !v || !scale_q || !scale_k || !o0 || !p0 || !q1_shape_ok(nseq, S, H, Dh)) return SPA3D_ERR_ARG;
+  OpCtx c(stream, nullptr, 0);
+  if (dtype == SPA3D_F32)
+    k_attn_q1_fwd<float>(&c, (const float*)q0, ldq0, (const float*)k, (const float*)v, ldk, ldv, scale_q, scale_k, keymask, nseq, S, H, Dh, (float*)o0, p0,
+                         seq_off);
+  else
+    k_attn_q1_fwd<bf16_t>(&c, (const bf16_t*)q0, ldq0, (const bf16_t*)k, (const bf16_t*)v, ldk, ldv, scale_q, scale_k, keymask, nseq, S, H, Dh, (bf16_t*)o0,
+                          p0, seq_off);
+  return c.hip_err == -3 ? SPA3D_ERR_ARG : c.status();
+}
+int spa3d_op_attention_q1_bwd(const void* q0, int64_t ldq0, const void* k, const void* v, int64_t ldk, int64_t ldv, const float* scale_q,
+                              const float* scale_k, const float* keymask, const int32_t* seq_off, int64_t nseq, int32_t S, int32_t H, int32_t Dh,
+                              const float* p0, const void* d_o0, void* dq0, void* dk, void* dv, float* dscale_q, float* dscale_k, int32_t dtype,
+                              void* stream) {
+  FWD16(spa3d_op_attention_q1_bwd_f16(q0, ldq0, k, v, ldk, ldv, scale_q, scale_k, keymask, seq_off, nseq, S, H, Dh, p0, d_o0, dq0, dk, dv, dscale_q,
+                                      dscale_k, dtype, stream))
+  if (!q0 || !k || !v || !scale_q || !scale_k || !p0 || !d_o0 || !dq0 || !dk || !dv || !dscale_q || !dscale_k || !q1_shape_ok(nseq, S, H, Dh))
+    return SPA3D_ERR_ARG;
+  OpCtx c(stream, nullptr, 0);   // c.det stays null: float atomics
+  if (dtype == SPA3D_F32)
+    k_attn_q1_bwd<float>(&c, (const float*)q0, ldq0, (const float*)k, (const float*)v, ldk, ldv, scale_q, scale_k, keymask, nseq, S, H, Dh, p0,
+                         (const float*)d_o0, (float*)dq0, (float*)dk, (float*)dv, dscale_q, dscale_k, seq_off);
+  else
+    k_attn_q1_bwd<bf16_t>(&c, (const bf16_t*)q0, ldq0, (const bf16_t*)k, (const bf16_t*)v, ldk, ldv, scale_q, scale_k, keymask, nseq, S, H, Dh, p0,
+                          (const bf16_t*)d_o0, (bf16_t*)dq0, (bf16_t*)dk, (bf16_t*)dv, dscale_q, dscale_k, seq_off);
+  return c.hip_err == -3 ? SPA3D_ERR_ARG : c.status();
+}
+
+int spa3d_op_rank_linear(const void* x, const void* w, const float* bias, void* out, int64_t M, int32_t N, int32_t K, int64_t ldo, int32_t rgroup,
+                         int32_t rskip, int32_t dtype, void* stream) {
+  FWD16(spa3d_op_rank_linear_f16(x, w, bias, out, M, N, K, ldo, rgroup, rskip, dtype, stream))
+  if (!x || !w || !out || M < 0 || N < 8 || ldo < N || rgroup < 0 || rskip < 0 || dtype == SPA3D_F32) return SPA3D_ERR_ARG;   // (no float instantiation: embed.hip)
+  OpCtx c(stream, nullptr, 0);
+  // false: K outside 1..4, N % 8, N > 2048, ldo % 8, a misaligned out, M >= 2^31 (k_rank_fwd launches nothing then)
+  const bool ok = k_rank_fwd<bf16_t>(&c, (const bf16_t*)x, (const bf16_t*)w, bias, (bf16_t*)out, M, N, K, ldo, rgroup, rskip);
+  return ok ? c.status() : SPA3D_ERR_ARG;
+}
+int spa3d_op_rank_linear_bwd(const void* x, const void* dy, int64_t M, int32_t N, int32_t K, int64_t ldy, int32_t rgroup, int32_t rskip, float* gw,
+                             float* gb, int32_t dtype, void* stream) {
+  FWD16(spa3d_op_rank_linear_bwd_f16(x, dy, M, N, K, ldy, rgroup, rskip, gw, gb, dtype, stream))
+  if (!x || !dy || !gw || M < 0 || N < 8 || ldy < N || rgroup < 0 || rskip < 0 || dtype == SPA3D_F32) return SPA3D_ERR_ARG;
+  OpCtx c(stream, nullptr, 0);
+  const bool ok = k_rank_bwd<bf16_t>(&c, (const bf16_t*)x, (const bf16_t*)dy, M, N, K, ldy, rgroup, rskip, gw, gb);
+  return ok ? c.status() : SPA3D_ERR_ARG;
 }
 
 }  // extern "C"

@@ -476,6 +476,9 @@ class TrackAutoEncoder3D:
   def _handle(self, dino_dim: int, depth_dim: int):
     key = (dino_dim, depth_dim)
     if key not in self._handles:
+      # the last block of the readout stack runs the single-query attention kernels, which exist for these head widths only (SPA3D_ERR_ARG in spa3d_create)
+      if self.num_heads > 0 and self.qkv_size % self.num_heads == 0 and self.qkv_size // self.num_heads not in (8, 16, 32, 64, 96, 128):
+        raise ValueError(f'head width qkv_size / num_heads = {self.qkv_size // self.num_heads} must be one of 8, 16, 32, 64, 96, 128')
       lib = _lib.load()
       cfg = _lib.Config(self.num_output_frames, self.num_latent_tokens, self.latent_token_dim, self.num_frequencies,
                         self.track_scale_factor, self.time_scale_factor, self.track_token_dim, self.encoder_latent_dim,

@@ -71,7 +71,7 @@ typedef struct {
   int32_t dino_feature_dim;    /* 768; 0 = no dino_projection leaf (use_dino False / key absent) */
   int32_t depth_feature_dim;   /* channels of depth_features actually fed; 0 = no depth_projection */
   int32_t num_heads;           /* 8 */
-  int32_t qkv_size;            /* 768 */
+  int32_t qkv_size;            /* 768; qkv_size / num_heads must be one of 8, 16, 32, 64, 96, 128 (spa3d_create: SPA3D_ERR_ARG otherwise) */
   int32_t enc_mlp, enc_layers; /* 1536, 3 */
   int32_t t2l_mlp, t2l_layers; /* 2048, 4 */
   int32_t dec_mlp, dec_layers; /* 2048, 4 */
@@ -598,6 +598,35 @@ int spa3d_op_attention_bwd(const void* q, const void* k, const void* v, int64_t 
                            const void* o, const float* lse /* forward outputs: needed by the fused kernel, NULL -> generic */,
                            const void* d_o, void* dq, void* dk, void* dv, float* dscale_q, float* dscale_k,
                            int32_t dtype, int32_t impl, void* ws, int64_t ws_bytes, void* stream);
+
+/* Single-query attention of a stack's last block (csrc/attn_q1.hip; track_autoencoder_3d.py:187-188, 286): only token 0 of each sequence
+ * queries, every token is a key.  q0 [nseq,H*Dh] with row stride ldq0; k, v [rows,H*Dh] with row strides ldk / ldv; o0 [nseq,H*Dh] dense;
+ * p0 [nseq*H,S] f32 = the softmax row of every (sequence, head), kept for the backward.  Scales, key mask and arithmetic as
+ * spa3d_op_attention (fp32 between load and store); keymask f32 [rows] or NULL.  seq_off (int32 [nseq + 1], device) = ragged sequences:
+ * sequence i is rows [seq_off[i], seq_off[i + 1]) of k, v and keymask, 1 <= its length <= S, and only that many entries of its p0 rows
+ * are written; NULL = nseq dense sequences of S rows.  Dh in {8, 16, 32, 64, 96, 128}, 1 <= S <= 320; anything else, or a NULL
+ * required pointer, returns SPA3D_ERR_ARG and launches nothing. */
+int spa3d_op_attention_q1(const void* q0, int64_t ldq0, const void* k, const void* v, int64_t ldk, int64_t ldv,
+                          const float* scale_q, const float* scale_k, const float* keymask, const int32_t* seq_off,
+                          int64_t nseq, int32_t S, int32_t H, int32_t Dh, void* o0, float* p0, int32_t dtype, void* stream);
+/* gradients of the above from the forward's p0: dq0 [nseq,H*Dh] dense; dk, dv strided like k, v, every row of every sequence overwritten
+ * (a masked key's rows with zeros); dscale_q / dscale_k f32[Dh] accumulated into.  Float atomics (the deterministic-gradient variant
+ * runs inside spa3d_loss_and_grads only). */
+int spa3d_op_attention_q1_bwd(const void* q0, int64_t ldq0, const void* k, const void* v, int64_t ldk, int64_t ldv,
+                              const float* scale_q, const float* scale_k, const float* keymask, const int32_t* seq_off,
+                              int64_t nseq, int32_t S, int32_t H, int32_t Dh, const float* p0, const void* d_o0,
+                              void* dq0, void* dk, void* dv, float* dscale_q, float* dscale_k, int32_t dtype, void* stream);
+
+/* Dense with an input width K <= 4 as a streaming kernel (csrc/embed.hip; the depth projection, track_autoencoder_3d.py:143-147):
+ * out[crow(m)][0..N) += x[m][0..K) . w[K][N] + bias, m < M, crow(m) = m + (m / rgroup + 1) * rskip (rgroup > 0) or m (rgroup == 0).
+ * x [M,K], w [K,N] and out (row stride ldo) in `dtype`; bias f32[N] or NULL.  16-bit dtypes only; 1 <= K <= 4, N a multiple of 8 up to
+ * 2048, ldo a multiple of 8, out 16-byte aligned, M < 2^31; anything else returns SPA3D_ERR_ARG and launches nothing. */
+int spa3d_op_rank_linear(const void* x, const void* w, const float* bias, void* out, int64_t M, int32_t N, int32_t K, int64_t ldo,
+                         int32_t rgroup, int32_t rskip, int32_t dtype, void* stream);
+/* gradients of the above: gw f32[K,N] += x^T . dy (rows of dy mapped by crow), gb f32[N] += column sums of those rows (NULL: skipped).
+ * dy with row stride ldy; the same shape rules on N, K, ldy and dy's alignment. */
+int spa3d_op_rank_linear_bwd(const void* x, const void* dy, int64_t M, int32_t N, int32_t K, int64_t ldy, int32_t rgroup, int32_t rskip,
+                             float* gw, float* gb, int32_t dtype, void* stream);
 
 /* ---- feature producers that build the hot path's inputs.  Host pointers: `intrinsics` only. ----
  * Float32 arithmetic in the reference's operation order: bit-identical to the reference functions under NumPy >= 2. */

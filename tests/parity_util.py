@@ -479,3 +479,64 @@ def emulate_attention_generic(q, k, v, sq, sk, km, H, Dh, d_o):
   E = H * Dh
   back = lambda t, S: t.permute(0, 2, 1, 3).reshape(nseq, S, E)
   return back(o, Sq), dq.reshape(nseq, Sq, E), dk.reshape(nseq, Sk, E), back(dv, Sk), dsq, dsk
+
+
+# ------------------------------------------------------------------------------------------------ single-query attention and sums by float atomics
+def sequential_sum(first, addends, dtype):
+  """first + addends[0] + addends[1] + ... taken one addend after the other in `dtype` (float32: what a chain of float atomics does, in one of its possible
+  orders; numpy's accumulate neither widens nor sums pairwise, torch's cumsum would accumulate float32 in double).  first [d], addends [n, d] -> [d]"""
+  import numpy as np
+  npdt = {torch.float32: np.float32, torch.float64: np.float64}[dtype]
+  a = np.concatenate([first.detach().cpu().numpy().astype(npdt)[None], addends.detach().cpu().numpy().astype(npdt)], 0)
+  return torch.from_numpy(np.add.accumulate(a, axis=0)[-1].copy())
+
+
+def arrival_orders(n, d, samples=128):
+  """Row orders in which to restate a sum of n addends that a kernel takes by float atomics, for a result of d elements: the given order, its reverse, then
+  seeded random permutations -- ceil(samples / d) orders in all.  The atomics' arrival order is not fixed, so every order is as much the restatement as any
+  other, and "the restatement's own worst error" (the gate is 4 x that) is the worst over the elements of all of them.  One order is enough for a wide result;
+  for a narrow one (8 columns) the worst of 8 rounding-noise samples is itself noise -- it falls below a quarter of the typical worst about once in a hundred
+  draws, and a correct kernel then fails -- so narrow results take more orders until at least `samples` = 128 elements enter the maximum."""
+  count = max(1, -(-samples // d))
+  yield torch.arange(n)
+  if count > 1:
+    yield torch.arange(n - 1, -1, -1)
+  for i in range(2, count):
+    yield torch.randperm(n, generator=torch.Generator().manual_seed(i))
+
+
+def attn_q1_restated(q0, k, v, sq, sk, km, H, Dh, d_o, dtype):
+  """Single-query attention (track_autoencoder_3d.py:187-188, 286: token 0 of each sequence queries, every token is a key) and its gradients, written out in
+  `dtype` on the host: float32 is the restatement that sets the 16-bit gates, float64 must equal the oracle's autograd (tests/test_parity_gates_host.py).
+  x^ = x rsqrt(mean x^2 + 1e-6); q^ = x^_q s_q; logit_j = q^ . (x^_j s_k) / sqrt(Dh), finfo.min for a masked key; p = softmax; o = sum p_j v_j.
+  Backward: dp_j = dO . v_j; ds_j = p_j (dp_j - sum p dp) / sqrt(Dh), 0 for a masked key; dv_j = p_j dO; dk^_j = ds_j q^ and u = sum ds_j x^_j give
+  dq^ = u s_k, ds_k = q^ u, ds_q = dq^ x^_q; a row's gradient through the RMSNorm is r (g - x^ mean(g x^)) with g = d(normalised row) x scale.
+  q0, d_o [n, H Dh]; k, v [n, S, H Dh]; km [n, S] or None.  -> o [n, H Dh], p [n, H, S], dq [n, H Dh], dk, dv [n, S, H Dh] and the scale gradients of every
+  (sequence, head) problem, csq, csk [n H, Dh] in problem order (to be summed as the kernel's atomics sum them: sequential_sum)."""
+  n, S = k.shape[0], k.shape[1]
+  x = q0.to(dtype).reshape(n, H, Dh)
+  kk, vv = k.to(dtype).reshape(n, S, H, Dh), v.to(dtype).reshape(n, S, H, Dh)
+  do = d_o.to(dtype).reshape(n, H, Dh)
+  sq, sk = sq.to(dtype), sk.to(dtype)
+  alpha = torch.tensor(1.0 / math.sqrt(Dh), dtype=dtype)
+  rq = torch.rsqrt((x * x).sum(-1, keepdim=True) / Dh + 1e-6)
+  xq = x * rq
+  qh = xq * sq
+  rk = torch.rsqrt((kk * kk).sum(-1, keepdim=True) / Dh + 1e-6)
+  xk = kk * rk
+  lg = torch.einsum('nhd,nshd->nhs', qh, xk * sk) * alpha
+  keep = torch.ones(n, 1, S, dtype=torch.bool) if km is None else (km != 0)[:, None, :]
+  lg = torch.where(keep, lg, torch.full_like(lg, torch.finfo(dtype).min))
+  p = torch.softmax(lg, -1)
+  o = torch.einsum('nhs,nshd->nhd', p, vv)
+  dp = torch.einsum('nhd,nshd->nhs', do, vv)
+  ds = torch.where(keep, p * (dp - (p * dp).sum(-1, keepdim=True)) * alpha, torch.zeros((), dtype=dtype))
+  dv = torch.einsum('nhs,nhd->nshd', p, do)
+  u = torch.einsum('nhs,nshd->nhd', ds, xk)
+  gk = torch.einsum('nhs,nhd->nshd', ds, qh) * sk
+  dk = rk * (gk - xk * ((gk * xk).sum(-1, keepdim=True) / Dh))
+  dqh = u * sk
+  gq = dqh * sq
+  dq = rq * (gq - xq * ((gq * xq).sum(-1, keepdim=True) / Dh))
+  E = H * Dh
+  return o.reshape(n, E), p, dq.reshape(n, E), dk.reshape(n, S, E), dv.reshape(n, S, E), (dqh * xq).reshape(n * H, Dh), (qh * u).reshape(n * H, Dh)

@@ -52,9 +52,9 @@ def _noise(B, cfg, seed=3):
 
 
 # ---------------------------------------------------------------------------------------------- mini config, all features
-@pytest.mark.parametrize('dino,depth', [(0, 0), (24, 1), (16, 5)])
-def test_mini_forward_loss_grads_fp32(spa3d, dino, depth):
-  cfg = O.Config(**MINI, use_dino=dino > 0, use_depth=depth > 0, dino_feature_dim=max(dino, 1), depth_feature_dim=max(depth, 1))
+def _mini_fp32(spa3d, dino, depth, **over):
+  """forward, losses and every gradient leaf of the mini config (with `over` replacing some of its sizes) in fp32 against the fp64 oracle"""
+  cfg = O.Config(**{**MINI, **over}, use_dino=dino > 0, use_depth=depth > 0, dino_feature_dim=max(dino, 1), depth_feature_dim=max(depth, 1))
   B, N, Q, T = 3, 10, 6, 8
   model, params, batch, gb = _setup(spa3d, cfg, B, N, Q, T, 'fp32', dino, depth)
   batch['boundary_frame'] = torch.tensor([8, 5, 3], dtype=torch.int32)
@@ -83,6 +83,18 @@ def test_mini_forward_loss_grads_fp32(spa3d, dino, depth):
     worst = max(worst, e)
     assert e < 2e-3, (k, e)
   print('mini fp32 worst grad rel err', worst)
+
+
+@pytest.mark.parametrize('dino,depth', [(0, 0), (24, 1), (16, 5)])
+def test_mini_forward_loss_grads_fp32(spa3d, dino, depth):
+  _mini_fp32(spa3d, dino, depth)
+
+
+@pytest.mark.parametrize('heads,qkv,dino,depth', [(2, 16, 0, 0), (2, 64, 24, 3), (2, 128, 0, 0), (1, 128, 16, 1)])
+def test_mini_head_widths_fp32(spa3d, heads, qkv, dino, depth):
+  """the same recipe and tolerances at head widths 8, 32, 64 and 128 (MINI has 16, the default model 96): the other instantiations of the single-query attention
+  of the last blocks (csrc/attn_q1.hip) inside the model, one of them with a 3-channel depth feature"""
+  _mini_fp32(spa3d, dino, depth, num_heads=heads, qkv_size=qkv)
 
 
 def test_mini_chunking_and_api_equivalences(spa3d, monkeypatch):
@@ -119,10 +131,11 @@ def test_mini_chunking_and_api_equivalences(spa3d, monkeypatch):
   assert pg.tracks.shape == (B, 1024, T, 3) and max_abs(pg.tracks, rg.tracks) < 1e-4
 
 
-def test_mini_bf16_mode(spa3d):
-  cfg = O.Config(**MINI, use_dino=True, use_depth=True, dino_feature_dim=24, depth_feature_dim=1)
+def _mini_bf16(spa3d, depth=1, **over):
+  """the bf16 mode of the mini config (with `over` replacing some of its sizes) against the fp64 oracle on the 16-bit feature planes"""
+  cfg = O.Config(**{**MINI, **over}, use_dino=True, use_depth=True, dino_feature_dim=24, depth_feature_dim=depth)
   B, N, Q, T = 2, 12, 6, 8
-  model, params, batch, gb = _setup(spa3d, cfg, B, N, Q, T, 'bf16', 24, 1)
+  model, params, batch, gb = _setup(spa3d, cfg, B, N, Q, T, 'bf16', 24, depth)
   noise = _noise(B, cfg)
   om = O.TrackAutoEncoder3D(cfg)
   p64 = _params_to_oracle(params, torch.float64)
@@ -140,6 +153,17 @@ def test_mini_bf16_mode(spa3d):
   cos = float((a @ b) / (a.norm() * b.norm()))
   print('bf16 mini grad cosine', cos)
   assert cos > 0.98
+
+
+def test_mini_bf16_mode(spa3d):
+  _mini_bf16(spa3d)
+
+
+@pytest.mark.parametrize('heads,qkv,depth', [(2, 64, 3), (2, 64, 4), (1, 128, 3), (1, 128, 4)])
+def test_mini_head_widths_bf16(spa3d, heads, qkv, depth):
+  """test_mini_bf16_mode's gates at head widths 32 and 128 with a 3- and a 4-channel depth feature: the model's dispatch into the rank-K projection kernels
+  (csrc/embed.hip) at K > 1"""
+  _mini_bf16(spa3d, depth, num_heads=heads, qkv_size=qkv)
 
 
 # ---------------------------------------------------------------------------------------------- BASELINE cfg#1 (full-size model)

@@ -444,3 +444,35 @@ def test_generic_composition_emulation_is_inside_its_own_gates_and_the_old_one(n
   PU.attention_row_gate(gt, 'o', emu[0], emu[0], ref.detach(), H, Dh)
   PU.attention_grad_gates(gt, emu[1:], emu[1:], refs, H, Dh)
   gt.check()
+
+
+# ------------------------------------------------------------------------------------------------ single-query attention: the restatement and its gates
+@pytest.mark.parametrize('n,S,H,Dh,masked', [(3, 17, 3, 8, True), (2, 151, 1, 96, False), (4, 33, 2, 32, True)])
+def test_single_query_restatement_is_the_oracle_in_fp64_and_inside_its_gates_in_fp32(n, S, H, Dh, masked):
+  """parity_util.attn_q1_restated in float64 equals the oracle's autograd (O.rms_norm, O.dot_product_attention, query row 0 only) to rounding, its scale
+  gradients included; in float32, rounded once to 16 bits, it passes the gate tests/test_gpu_attn_q1.py applies to the kernels; a result that ignores the key
+  mask does not."""
+  E = H * Dh
+  g = torch.Generator().manual_seed(S)
+  q0, d_o = torch.randn(n, E, generator=g).bfloat16(), torch.randn(n, E, generator=g).bfloat16()
+  k, v = torch.randn(n, S, E, generator=g).bfloat16(), torch.randn(n, S, E, generator=g).bfloat16()
+  sq = 1 + 0.2 * torch.randn(Dh, generator=g); sk = 1 + 0.2 * torch.randn(Dh, generator=g)
+  km = None
+  if masked:
+    km = (torch.rand(n, S, generator=g) < 0.8).float(); km[:, 0] = 1.0; km[0, 1:] = 0.0
+  qr, kr, vr = (t.double().requires_grad_(True) for t in (q0, k, v))
+  sqr, skr = sq.double().requires_grad_(True), sk.double().requires_grad_(True)
+  mask = None if km is None else km[:, None, None, :].expand(n, H, 1, S)
+  ref = O.dot_product_attention(O.rms_norm(qr.view(n, 1, H, Dh), sqr), O.rms_norm(kr.view(n, S, H, Dh), skr), vr.view(n, S, H, Dh), mask).reshape(n, E)
+  ref.backward(d_o.double())
+  r64 = PU.attn_q1_restated(q0, k, v, sq, sk, km, H, Dh, d_o, torch.float64)
+  for name, a, b in zip(('o', 'dq', 'dk', 'dv'), (r64[0], r64[2], r64[3], r64[4]), (ref.detach(), qr.grad, kr.grad, vr.grad)):
+    assert max_abs(a, b) < 1e-12, name
+  zero = torch.zeros(Dh, dtype=torch.float64)
+  assert max_abs(PU.sequential_sum(zero, r64[5], torch.float64), sqr.grad) < 1e-12 and max_abs(PU.sequential_sum(zero, r64[6], torch.float64), skr.grad) < 1e-12
+  r32 = PU.attn_q1_restated(q0, k, v, sq, sk, km, H, Dh, d_o, torch.float32)
+  for i, b in ((0, ref.detach()), (2, qr.grad), (3, kr.grad), (4, vr.grad)):
+    PU.assert_elementwise(r32[i].bfloat16(), b, PU.restated_bound(b, r32[i], torch.bfloat16))
+  if masked:   # gradients that ignore the key mask (keep = true for every key): masked keys get a dk, and the gate sees it
+    bad = PU.attn_q1_restated(q0, k, v, sq, sk, None, H, Dh, d_o, torch.float32)
+    assert PU.elementwise_report(bad[3].bfloat16(), kr.grad, PU.restated_bound(kr.grad, r32[3], torch.bfloat16))[0] > 0
