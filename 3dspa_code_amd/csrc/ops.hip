@@ -129,6 +129,18 @@ int spa3d_op_rank_linear_f16(const void* x, const void* w, const float* bias, vo
                              int32_t rskip, int32_t dtype, void* stream);
 int spa3d_op_rank_linear_bwd_f16(const void* x, const void* dy, int64_t M, int32_t N, int32_t K, int64_t ldy, int32_t rgroup, int32_t rskip, float* gw,
                                  float* gb, int32_t dtype, void* stream);
+int spa3d_op_colsum_f16(const void* x, int64_t rows, int32_t n, int64_t ld, int32_t rgroup, int32_t rskip, float* out, int32_t dtype, void* stream);
+int spa3d_op_rows_f16(int32_t mode, const void* src, const int32_t* idx, int64_t stride_rows, void* dst, int64_t n, int32_t d, int32_t dtype, void* stream);
+int spa3d_op_share_rows_f16(int32_t which, const void* a, const void* b, const int32_t* slot, const int32_t* slot_b, const int32_t* slot_f,
+                            const int32_t* slot_q0, int64_t nslot, int64_t B, int32_t Q, int32_t L, int32_t Cl, int32_t d, void* out, int32_t dtype, void* stream);
+int spa3d_op_assemble_readout_f16(const void* qtok, const void* lat, const int32_t* qframe, int64_t B, int32_t Q, int32_t L, int32_t Cl, int32_t D, void* seq,
+                                  int32_t dtype, void* stream);
+int spa3d_op_assemble_readout_bwd_f16(const void* dseq, const int32_t* qframe, int64_t B, int32_t Q, int32_t L, int32_t Cl, int32_t D, void* dqtok,
+                                      float* dlat, int32_t accumulate, int32_t dtype, void* stream);
+int spa3d_op_broadcast_rows_f16(const float* src, int32_t rows, int32_t d, void* dst, int64_t B, int32_t dtype, void* stream);
+int spa3d_op_bcast_grad_f16(const void* dsrc, int64_t per, int64_t B, int64_t bstride, float* dparam, int32_t dtype, void* stream);
+int spa3d_op_vis_mean_pool_f16(const void* tok, const float* vis, int64_t nseq, int32_t T, int32_t d, void* out, int32_t dtype, void* stream);
+int spa3d_op_vis_mean_pool_bwd_f16(const void* dout, const float* vis, int64_t nseq, int32_t T, int32_t d, void* dtok, int32_t dtype, void* stream);
 #pragma GCC visibility pop
 }
 #if SPA_F16
@@ -146,6 +158,15 @@ int spa3d_op_rank_linear_bwd_f16(const void* x, const void* dy, int64_t M, int32
 #define spa3d_op_attention_q1_bwd spa3d_op_attention_q1_bwd_f16
 #define spa3d_op_rank_linear spa3d_op_rank_linear_f16
 #define spa3d_op_rank_linear_bwd spa3d_op_rank_linear_bwd_f16
+#define spa3d_op_colsum spa3d_op_colsum_f16
+#define spa3d_op_rows spa3d_op_rows_f16
+#define spa3d_op_share_rows spa3d_op_share_rows_f16
+#define spa3d_op_assemble_readout spa3d_op_assemble_readout_f16
+#define spa3d_op_assemble_readout_bwd spa3d_op_assemble_readout_bwd_f16
+#define spa3d_op_broadcast_rows spa3d_op_broadcast_rows_f16
+#define spa3d_op_bcast_grad spa3d_op_bcast_grad_f16
+#define spa3d_op_vis_mean_pool spa3d_op_vis_mean_pool_f16
+#define spa3d_op_vis_mean_pool_bwd spa3d_op_vis_mean_pool_bwd_f16
 #define FWD16(call)
 #else
 #define FWD16(call) if (dtype == SPA3D_F16) return call;
@@ -335,6 +356,134 @@ int spa3d_op_rank_linear_bwd(const void* x, const void* dy, int64_t M, int32_t N
   OpCtx c(stream, nullptr, 0);
   const bool ok = k_rank_bwd<bf16_t>(&c, (const bf16_t*)x, (const bf16_t*)dy, M, N, K, ldy, rgroup, rskip, gw, gb);
   return ok ? c.status() : SPA3D_ERR_ARG;
+}
+
+// ---- The row plumbing of csrc/rows.hip on its own (tests/test_gpu_rows.py).  Thin wrappers: every input a launcher would record as a HIP-class error
+// (an empty grid, a row width that is not a multiple of 16 bytes) or mis-handle without a word (a 16-byte access through a pointer that is not 16-byte
+// aligned, a negative count) is an argument error here and launches nothing.  c.det stays null: sums use float atomics.
+#if SPA_F16
+#define ROWS_DT16 SPA3D_F16
+#else
+#define ROWS_DT16 SPA3D_BF16
+#endif
+#define ROWS_DTYPE_OK(dtype) ((dtype) == SPA3D_F32 || (dtype) == ROWS_DT16)
+// f(T*) with T the storage type of `dtype`
+#define ROWS_BY_DTYPE(dtype, body)                                          \
+  do {                                                                      \
+    if ((dtype) == SPA3D_F32) { using T = float; body; }                    \
+    else { using T = bf16_t; body; }                                        \
+  } while (0)
+static bool rows_al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+static int rows_nv(int32_t dtype) { return dtype == SPA3D_F32 ? 4 : 8; }   // elements per 16 bytes (VecOf<T>::N)
+
+int spa3d_op_colsum(const void* x, int64_t rows, int32_t n, int64_t ld, int32_t rgroup, int32_t rskip, float* out, int32_t dtype, void* stream) {
+  FWD16(spa3d_op_colsum_f16(x, rows, n, ld, rgroup, rskip, out, dtype, stream))
+  if (!x || !out || !ROWS_DTYPE_OK(dtype) || rows < 0 || n < 1 || ld < n || rgroup < 0 || rskip < 0) return SPA3D_ERR_ARG;
+  OpCtx c(stream, nullptr, 0);
+  ROWS_BY_DTYPE(dtype, k_colsum<T>(&c, (const T*)x, rows, n, ld, out, rgroup, rskip));
+  return c.status();
+}
+
+int spa3d_op_rows(int32_t mode, const void* src, const int32_t* idx, int64_t stride_rows, void* dst, int64_t n, int32_t d, int32_t dtype, void* stream) {
+  FWD16(spa3d_op_rows_f16(mode, src, idx, stride_rows, dst, n, d, dtype, stream))
+  if (!src || !dst || !ROWS_DTYPE_OK(dtype) || n < 0 || d < 1 || mode < SPA3D_ROWS_GATHER_STRIDED || mode > SPA3D_ROWS_ADD_STRIDED) return SPA3D_ERR_ARG;
+  const bool by_idx = mode == SPA3D_ROWS_GATHER_IDX || mode == SPA3D_ROWS_SCATTER_IDX || mode == SPA3D_ROWS_SCATTER_ADD_IDX;
+  if (by_idx && (!idx || d % rows_nv(dtype) || !rows_al16(src) || !rows_al16(dst))) return SPA3D_ERR_ARG;   // 16-byte accesses: the launcher checks d only
+  if (!by_idx && stride_rows < 1) return SPA3D_ERR_ARG;
+  OpCtx c(stream, nullptr, 0);
+  ROWS_BY_DTYPE(dtype, {
+    if (mode == SPA3D_ROWS_GATHER_STRIDED) k_gather_rows<T>(&c, (const T*)src, stride_rows, (T*)dst, n, d);
+    else if (mode == SPA3D_ROWS_ADD_STRIDED) k_add_rows_strided<T>(&c, (T*)dst, (const T*)src, stride_rows, n, d);
+    else k_rows_idx<T>(&c, mode - SPA3D_ROWS_GATHER_IDX, (const T*)src, idx, (T*)dst, n, d);
+  });
+  return c.status();
+}
+
+#if !SPA_F16   // the two plans have no storage type: one copy
+int spa3d_op_prune_plan(const float* km, int64_t nseq, int32_t S, int32_t* cnt, int32_t* seq_off, int32_t* row_src, int64_t* kept, void* stream) {
+  if (!km || !cnt || !seq_off || !row_src || !kept || nseq < 0 || S < 1 || nseq * (int64_t)S > 0x7fffffffLL) return SPA3D_ERR_ARG;   // row_src holds int32 rows
+  OpCtx c(stream, nullptr, 0);
+  *kept = k_prune_plan(&c, km, nseq, S, cnt, seq_off, row_src);
+  return c.status();
+}
+int spa3d_op_share_plan(const int32_t* qframe, int64_t B, int32_t Q, int32_t* slot, int32_t* slot_b, int32_t* slot_f, int32_t* slot_q0, int32_t* scratch,
+                        int64_t* nslot, void* stream) {
+  if (!qframe || !slot || !slot_b || !slot_f || !slot_q0 || !scratch || !nslot || B < 0 || Q < 0 || B * (int64_t)Q > 0x7fffffffLL) return SPA3D_ERR_ARG;
+  if (B == 0 || Q == 0) { *nslot = 0; return SPA3D_OK; }   // (k_share_plan would launch an empty grid)
+  OpCtx c(stream, nullptr, 0);
+  *nslot = k_share_plan(&c, qframe, B, Q, slot, slot_b, slot_f, slot_q0, scratch);
+  return c.status();
+}
+#endif
+
+int spa3d_op_share_rows(int32_t which, const void* a, const void* b, const int32_t* slot, const int32_t* slot_b, const int32_t* slot_f, const int32_t* slot_q0,
+                        int64_t nslot, int64_t B, int32_t Q, int32_t L, int32_t Cl, int32_t d, void* out, int32_t dtype, void* stream) {
+  FWD16(spa3d_op_share_rows_f16(which, a, b, slot, slot_b, slot_f, slot_q0, nslot, B, Q, L, Cl, d, out, dtype, stream))
+  if (!a || !out || !ROWS_DTYPE_OK(dtype) || nslot < 0 || B < 0 || Q < 1 || L < 0 || d < 1 || which < SPA3D_SHARE_ASSEMBLE || which > SPA3D_SHARE_REDUCE)
+    return SPA3D_ERR_ARG;
+  const int nv = rows_nv(dtype);
+  if (d % nv || !rows_al16(a) || !rows_al16(out) || nslot > B * Q) return SPA3D_ERR_ARG;   // vector-only kernels
+  const int64_t nseq = B * Q;
+  OpCtx c(stream, nullptr, 0);
+  if (which == SPA3D_SHARE_ASSEMBLE) {
+    if (!b || !slot_b || !slot_f || Cl < 1 || Cl > d || Cl % nv || !rows_al16(b)) return SPA3D_ERR_ARG;
+    ROWS_BY_DTYPE(dtype, k_share_assemble<T>(&c, (const T*)a, (const T*)b, slot_b, slot_f, nslot, nseq, L, Cl, d, (T*)out));
+  } else if (which == SPA3D_SHARE_EXPAND) {
+    if (!slot || !slot_q0 || !rows_al16(b)) return SPA3D_ERR_ARG;   // b = add, may be NULL
+    ROWS_BY_DTYPE(dtype, k_share_expand<T>(&c, (const T*)a, slot, slot_q0, nslot, nseq, L + 1, d, (const T*)b, (T*)out));
+  } else {
+    if (!slot || !slot_b || Q > 12288) return SPA3D_ERR_ARG;         // the member list [Q] lives in LDS, as the plan's table
+    ROWS_BY_DTYPE(dtype, k_share_reduce<T>(&c, (const T*)a, slot, slot_b, nslot, nseq, Q, L + 1, d, (T*)out));
+  }
+  return c.status();
+}
+
+int spa3d_op_assemble_readout(const void* qtok, const void* lat, const int32_t* qframe, int64_t B, int32_t Q, int32_t L, int32_t Cl, int32_t D, void* seq,
+                              int32_t dtype, void* stream) {
+  FWD16(spa3d_op_assemble_readout_f16(qtok, lat, qframe, B, Q, L, Cl, D, seq, dtype, stream))
+  if (!qtok || !lat || !qframe || !seq || !ROWS_DTYPE_OK(dtype) || B < 0 || Q < 1 || L < 0 || Cl < 1 || D < Cl) return SPA3D_ERR_ARG;
+  OpCtx c(stream, nullptr, 0);
+  ROWS_BY_DTYPE(dtype, k_assemble_readout<T>(&c, (const T*)qtok, (const T*)lat, qframe, B, Q, L, Cl, D, (T*)seq));
+  return c.status();
+}
+int spa3d_op_assemble_readout_bwd(const void* dseq, const int32_t* qframe, int64_t B, int32_t Q, int32_t L, int32_t Cl, int32_t D, void* dqtok, float* dlat,
+                                  int32_t accumulate, int32_t dtype, void* stream) {
+  FWD16(spa3d_op_assemble_readout_bwd_f16(dseq, qframe, B, Q, L, Cl, D, dqtok, dlat, accumulate, dtype, stream))
+  if (!dseq || !qframe || !dqtok || !dlat || !ROWS_DTYPE_OK(dtype) || B < 0 || Q < 1 || L < 1 || Cl < 1 || D < Cl || (accumulate != 0 && accumulate != 1))
+    return SPA3D_ERR_ARG;   // (L = 0: dlat is empty and its launch would have no workgroup)
+  OpCtx c(stream, nullptr, 0);
+  ROWS_BY_DTYPE(dtype, k_assemble_readout_bwd<T>(&c, (const T*)dseq, qframe, B, Q, L, Cl, D, (T*)dqtok, dlat, accumulate != 0));
+  return c.status();
+}
+
+int spa3d_op_broadcast_rows(const float* src, int32_t rows, int32_t d, void* dst, int64_t B, int32_t dtype, void* stream) {
+  FWD16(spa3d_op_broadcast_rows_f16(src, rows, d, dst, B, dtype, stream))
+  if (!src || !dst || !ROWS_DTYPE_OK(dtype) || rows < 1 || d < 1 || B < 0) return SPA3D_ERR_ARG;
+  OpCtx c(stream, nullptr, 0);
+  ROWS_BY_DTYPE(dtype, k_broadcast_rows<T>(&c, src, rows, d, (T*)dst, B));
+  return c.status();
+}
+int spa3d_op_bcast_grad(const void* dsrc, int64_t per, int64_t B, int64_t bstride, float* dparam, int32_t dtype, void* stream) {
+  FWD16(spa3d_op_bcast_grad_f16(dsrc, per, B, bstride, dparam, dtype, stream))
+  if (!dsrc || !dparam || !ROWS_DTYPE_OK(dtype) || per < 1 || per > 0x7fffffffLL || B < 0 || bstride < per) return SPA3D_ERR_ARG;
+  OpCtx c(stream, nullptr, 0);
+  ROWS_BY_DTYPE(dtype, k_bcast_grad<T>(&c, (const T*)dsrc, per, B, bstride, dparam));
+  return c.status();
+}
+
+int spa3d_op_vis_mean_pool(const void* tok, const float* vis, int64_t nseq, int32_t T_, int32_t d, void* out, int32_t dtype, void* stream) {
+  FWD16(spa3d_op_vis_mean_pool_f16(tok, vis, nseq, T_, d, out, dtype, stream))
+  if (!tok || !vis || !out || !ROWS_DTYPE_OK(dtype) || nseq < 0 || T_ < 1 || d < 1) return SPA3D_ERR_ARG;
+  OpCtx c(stream, nullptr, 0);
+  ROWS_BY_DTYPE(dtype, k_vis_mean_pool<T>(&c, (const T*)tok, vis, nseq, T_, d, (T*)out));
+  return c.status();
+}
+int spa3d_op_vis_mean_pool_bwd(const void* dout, const float* vis, int64_t nseq, int32_t T_, int32_t d, void* dtok, int32_t dtype, void* stream) {
+  FWD16(spa3d_op_vis_mean_pool_bwd_f16(dout, vis, nseq, T_, d, dtok, dtype, stream))
+  if (!dout || !vis || !dtok || !ROWS_DTYPE_OK(dtype) || nseq < 0 || T_ < 1 || d < 1) return SPA3D_ERR_ARG;
+  OpCtx c(stream, nullptr, 0);
+  ROWS_BY_DTYPE(dtype, k_vis_mean_pool_bwd<T>(&c, (const T*)dout, vis, nseq, T_, d, (T*)dtok));
+  return c.status();
 }
 
 }  // extern "C"

@@ -2,6 +2,11 @@
 // the shared latent rows of the readout stack's first block, readout sequence assembly, the parameter-row broadcast and its gradient, and
 // TRAJAN's visible-frame pooling.  Element-wise, HBM-bound kernels, 16 bytes per thread where the shape allows.
 // T in {float, bf16_t} storage, fp32 math.  References such as attention.py:49 are to the reference implementation's files.
+// Each launcher (fills and casts apart) is callable on its own -- spa3d_op_colsum, spa3d_op_rows, spa3d_op_prune_plan, spa3d_op_share_plan,
+// spa3d_op_share_rows, spa3d_op_assemble_readout(_bwd), spa3d_op_broadcast_rows, spa3d_op_bcast_grad, spa3d_op_vis_mean_pool(_bwd) in ops.hip -- and
+// tests/test_gpu_rows.py pins every branch below against tests/rows_util.py: copies bit for bit, plans integer for integer, sums element by element.
+// Not reached there: the second grid-stride pass of the 1-D kernels (GRID1D caps a grid at 2^20 workgroups, 2^28 items a pass) and the
+// nchunk >= 2^31 fallback of k_assemble_readout.  rows_idx mode 2 (scatter-add) is a plain read-modify-write: it is specified for UNIQUE indices only.
 #include <algorithm>
 
 #include "common.hpp"
@@ -236,6 +241,7 @@ __global__ __launch_bounds__(256) void prune_fill_kernel(const float* __restrict
 // returns the number of kept rows (ONE stream synchronisation: the row count sizes every launch that follows); dense count when dry
 int64_t k_prune_plan(spa3d_ctx* c, const float* km, int64_t nseq, int S, int32_t* cnt, int32_t* seq_off, int32_t* row_src) {
   if (c->dry) return nseq * S;
+  if (nseq == 0) return 0;   // a grid of no workgroups is a launch error; no model call gets here (nseq = samples x tracks, both >= 1), spa3d_op_prune_plan does
   prune_count_kernel<<<(unsigned)std::min<int64_t>(cdiv(nseq, 4), 8192), 256, 0, c->stream>>>(km, nseq, S, cnt); SPA_LAUNCH_CHECK(c);
   prune_scan_kernel<<<1, 1024, 0, c->stream>>>(cnt, nseq, seq_off); SPA_LAUNCH_CHECK(c);
   prune_fill_kernel<<<(unsigned)std::min<int64_t>(cdiv(nseq, 4), 8192), 256, 0, c->stream>>>(km, nseq, S, seq_off, row_src); SPA_LAUNCH_CHECK(c);

@@ -628,6 +628,70 @@ int spa3d_op_rank_linear(const void* x, const void* w, const float* bias, void* 
 int spa3d_op_rank_linear_bwd(const void* x, const void* dy, int64_t M, int32_t N, int32_t K, int64_t ldy, int32_t rgroup, int32_t rskip,
                              float* gw, float* gb, int32_t dtype, void* stream);
 
+/* ---- The row plumbing of csrc/rows.hip on its own (tests/test_gpu_rows.py).  `dtype` in {SPA3D_F32, SPA3D_BF16, SPA3D_F16} is the storage type of
+ * every `void*` tensor; sums are fp32 (float atomics where a sum is split).  "16 bytes" below is 4 fp32 or 8 16-bit elements.  An empty input
+ * (0 rows, 0 samples) returns SPA3D_OK and launches nothing; a NULL required pointer, a negative count or a shape outside what is stated
+ * returns SPA3D_ERR_ARG and launches nothing. ---- */
+
+/* out[j] += sum over r < rows of x[crow(r) * ld + j], j < n; crow as spa3d_op_rank_linear.  1 <= n <= ld.  16 bytes per thread when n and ld are
+ * multiples of 16 bytes and x is 16-byte aligned, else element by element. */
+int spa3d_op_colsum(const void* x, int64_t rows, int32_t n, int64_t ld, int32_t rgroup, int32_t rskip, float* out /* f32[n], accumulated into */,
+                    int32_t dtype, void* stream);
+
+/* Row movers, n rows of d elements:
+ *   SPA3D_ROWS_GATHER_STRIDED   dst[i] = src[i * stride_rows]          SPA3D_ROWS_ADD_STRIDED      dst[i * stride_rows] += src[i]
+ *   SPA3D_ROWS_GATHER_IDX       dst[i] = src[idx[i]]                   SPA3D_ROWS_SCATTER_IDX      dst[idx[i]] = src[i]
+ *   SPA3D_ROWS_SCATTER_ADD_IDX  dst[idx[i]] += src[i]  -- for UNIQUE indices only (a plain read-modify-write: two rows with one index race)
+ * The strided modes take any d >= 1 and stride_rows >= 1 (idx is not read); the index modes (idx int32 [n], device; stride_rows not read) move 16 bytes
+ * per thread: d a multiple of 16 bytes, src and dst 16-byte aligned.  Copies are bit-exact; an add is one fp32 addition and one rounding to `dtype`. */
+enum { SPA3D_ROWS_GATHER_STRIDED = 0, SPA3D_ROWS_GATHER_IDX = 1, SPA3D_ROWS_SCATTER_IDX = 2, SPA3D_ROWS_SCATTER_ADD_IDX = 3, SPA3D_ROWS_ADD_STRIDED = 4 };
+int spa3d_op_rows(int32_t mode, const void* src, const int32_t* idx, int64_t stride_rows, void* dst, int64_t n, int32_t d, int32_t dtype, void* stream);
+
+/* Token-pruning plan of the track encoder: km f32 [nseq, S] (non-zero = keep; -0.0 is dropped, NaN kept) -> cnt [nseq] kept tokens per sequence,
+ * seq_off [nseq + 1] their exclusive prefix, row_src [*kept] the dense row seq * S + t behind every kept row, in order; *kept (host) = seq_off[nseq].
+ * Synchronises the stream once.  S >= 1, nseq * S < 2^31; nseq = 0: *kept = 0, nothing written. */
+int spa3d_op_prune_plan(const float* km, int64_t nseq, int32_t S, int32_t* cnt, int32_t* seq_off, int32_t* row_src, int64_t* kept, void* stream);
+
+/* Shared-latent-row plan of the readout stack's first block: qframe int32 [B, Q] -> slot [B * Q] = the slot of every query, a slot being a distinct
+ * (sample, frame) pair numbered sample by sample in order of first occurrence; slot_b / slot_f / slot_q0 [*nslot] = sample, frame and first member
+ * query (b * Q + q) of every slot; *nslot (host) their number.  scratch int32 [B * Q + B + 1].  Synchronises the stream once.  B > 1024 or Q > 12288
+ * is outside the plan's tables: *nslot = B * Q and nothing is written (the caller keeps the dense path). */
+int spa3d_op_share_plan(const int32_t* qframe, int64_t B, int32_t Q, int32_t* slot, int32_t* slot_b, int32_t* slot_f, int32_t* slot_q0, int32_t* scratch,
+                        int64_t* nslot, void* stream);
+
+/* The rows behind that plan; S = L + 1 tokens per query sequence, nseq = B * Q, U = nslot * L + nseq rows:
+ *   SPA3D_SHARE_ASSEMBLE  a = qtok [nseq, d], b = lat [B, L, Cl] -> out [U, d]: row (s, n) = [lat[slot_b[s]][n] | its window at frame slot_f[s]] (as
+ *                         spa3d_op_assemble_readout), then the nseq query-token rows.  Reads slot_b, slot_f.  Cl <= d, a multiple of 16 bytes.
+ *   SPA3D_SHARE_EXPAND    a = srcU [U, d] -> out [nseq, S, d]: token 0 = row nslot * L + seq, token 1 + n = row slot[seq] * L + n.  With b = add
+ *                         [nseq, S, d] (the backward form): out = add, plus the source row at every token 0 and at the tokens of each slot's FIRST
+ *                         member slot_q0 only.  Reads slot, slot_q0; Cl is not read.
+ *   SPA3D_SHARE_REDUCE    a = src [nseq, S, d] -> out [U, d], the transpose of the expansion: row (s, n) = fp32 sum over the slot's members, in
+ *                         ascending query order, of their token 1 + n; row nslot * L + seq = token 0 of seq.  Reads slot, slot_b; Q <= 12288.
+ * Vector kernels only: d a multiple of 16 bytes and a, b, out 16-byte aligned.  Pointers a mode does not read may be NULL. */
+enum { SPA3D_SHARE_ASSEMBLE = 0, SPA3D_SHARE_EXPAND = 1, SPA3D_SHARE_REDUCE = 2 };
+int spa3d_op_share_rows(int32_t which, const void* a, const void* b, const int32_t* slot, const int32_t* slot_b, const int32_t* slot_f,
+                        const int32_t* slot_q0, int64_t nslot, int64_t B, int32_t Q, int32_t L, int32_t Cl, int32_t d, void* out, int32_t dtype, void* stream);
+
+/* Readout sequence assembly (track_autoencoder_3d.py:235-246, 276-284): seq [B, Q, 1 + L, D]; token 0 = qtok [B, Q, D]; token 1 + n =
+ * [lat[b][n][0..Cl) | lat[b][n][dd + 5 qframe[b][q]] for dd < D - Cl, 0 outside [0, Cl)].  1 <= Cl <= D.  16 bytes per thread when Cl and D are multiples
+ * of 16 bytes and the three tensors are 16-byte aligned, else element by element; both are copies, bit for bit. */
+int spa3d_op_assemble_readout(const void* qtok, const void* lat, const int32_t* qframe, int64_t B, int32_t Q, int32_t L, int32_t Cl, int32_t D, void* seq,
+                              int32_t dtype, void* stream);
+/* its backward: dqtok [B, Q, D] = token 0 of dseq (a copy); dlat f32 [B, L, Cl] = (accumulate ? dlat : 0) + the sum over the sample's queries of
+ * both parts, in a fixed order (no atomics).  L >= 1. */
+int spa3d_op_assemble_readout_bwd(const void* dseq, const int32_t* qframe, int64_t B, int32_t Q, int32_t L, int32_t Cl, int32_t D, void* dqtok, float* dlat,
+                                  int32_t accumulate, int32_t dtype, void* stream);
+
+/* dst [B, rows, d] = src f32 [rows, d] rounded once to `dtype` (ParamStateInit, track_autoencoder.py:41-53) ... */
+int spa3d_op_broadcast_rows(const float* src, int32_t rows, int32_t d, void* dst, int64_t B, int32_t dtype, void* stream);
+/* ... and its gradient: dparam f32 [per] += sum over b < B of dsrc[b * bstride + 0..per).  1 <= per <= bstride. */
+int spa3d_op_bcast_grad(const void* dsrc, int64_t per, int64_t B, int64_t bstride, float* dparam, int32_t dtype, void* stream);
+
+/* TRAJAN's track pooling (track_autoencoder.py:230-232): out [nseq, d] = mean of tok [nseq, T, d] over the frames with vis f32 [nseq, T] != 0 (0 when
+ * there is none); backward dtok [nseq, T, d] = dout [nseq, d] / max(1, visible frames) at the visible frames, 0 elsewhere.  T, d >= 1. */
+int spa3d_op_vis_mean_pool(const void* tok, const float* vis, int64_t nseq, int32_t T, int32_t d, void* out, int32_t dtype, void* stream);
+int spa3d_op_vis_mean_pool_bwd(const void* dout, const float* vis, int64_t nseq, int32_t T, int32_t d, void* dtok, int32_t dtype, void* stream);
+
 /* ---- feature producers that build the hot path's inputs.  Host pointers: `intrinsics` only. ----
  * Float32 arithmetic in the reference's operation order: bit-identical to the reference functions under NumPy >= 2. */
 
