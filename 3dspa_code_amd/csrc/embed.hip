@@ -126,7 +126,7 @@ void k_query_embed1(spa3d_ctx* c, const float* qp, int64_t nq, int nf, float tra
 // ---------------------------------------------------------------------------------------------
 // token bookkeeping
 // ---------------------------------------------------------------------------------------------
-// One-pass embedding (model.hip encode_chunk): row maps of the token rows the encoder keeps.  Row j of the (compact or dense) token buffer is dense
+// One-pass embedding (model.hip encode_tracks): row maps of the token rows the encoder keeps.  Row j of the (compact or dense) token buffer is dense
 // token q = row_src[j] (or j) = (seq, s): a frame token (s >= 1) reads input row seq * T + s - 1 and is written to row j; the readout token (s == 0)
 // has no input -- its GEMM row is dropped (crow = -1, arow = any valid row) and row j receives the readout parameter here (3d:161-165).
 template <typename T>

@@ -8,6 +8,12 @@
 // batch-global quantity, the loss denominator, is computed from the targets up front).  Within a chunk
 // all block intermediates needed by the backward are stashed in the caller's workspace (bump arena);
 // parameter gradients accumulate in fp32 across chunks.
+//
+// Sequencing: run_body owns what belongs to the call (weight shadows, denominator, noise, det_grads, unscaling, the loss, the score reduction) and cuts
+// the batch into chunks; run_chunk is the ONE route a chunk takes through the stages of Net -- encode_tracks, encode_latents, decode_latents,
+// decode_queries, emit_outputs, backward_queries, backward_latents, backward_tracks -- whatever it is: uniform, one sample of a ragged batch, several
+// packed, sliced by "track_chunk" / "query_chunk".  Only run_folds (spa3d_score_folds), whose chunk changes shape between the stages, sequences them itself.
+// Every entry point that runs the network ends in sized_run: need at the least count, largest count that fits, run, status.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -466,7 +472,7 @@ template <typename T> struct Net {
   // ------------------------------------------------------------------ per-chunk state
   struct Chunk {
     int64_t Bc, nseq; int N, Q, T_, S;
-    // intra-sample slices (run_body: "track_chunk" / "query_chunk", one sample per chunk): the track encoder runs on tracks [n_off, n_off + Nc) of the
+    // intra-sample slices (run_chunk: "track_chunk" / "query_chunk", one sample per chunk): the track encoder runs on tracks [n_off, n_off + Nc) of the
     // sample (nseq = Bc * Nc; the cross attention of tracks_to_latents still sees all N), the readout on queries [q_off, q_off + Qc)
     bool ragged = false;  // sample(s) of a batch with per-sample counts (spa3d_set_counts)
     // packed: a chunk of SEVERAL samples of such a batch.  Their live tracks / queries are packed back to back -- the track encoder runs on
@@ -477,12 +483,19 @@ template <typename T> struct Net {
     // as a packed chunk whose queries are rows [q_off, q_off + qoff[Bc]) of the clip IN PLACE (no packed copy) and read the latents of folds lat_f0, lat_f0 + 1, ..
     bool folds = false; std::vector<int32_t> holes_h; int32_t* holes_dev = nullptr; int lat_f0 = 0;
     int64_t nq() const { return packed ? (int64_t)qoff.back() : Bc * Qc; }
+    // Which rows of the batch's [B * Q] query rows are the chunk's nq() query rows: f(chunk_row0, batch_row0, n, sample) once for the whole chunk
+    // when its rows are consecutive in the batch (a uniform chunk, one ragged sample in place, a group of folds), else once per sample of the packed
+    // chunk -- its live rows are the first of its Q (a sample without live queries gets its call too, with n = 0).  b0: the chunk's first sample.
+    template <typename F> void for_each_query_span(int64_t b0, F&& f) const {
+      if (!packed || folds) { f((int64_t)0, b0 * Q + q_off, nq(), (int64_t)0); return; }
+      for (int64_t s = 0; s < Bc; ++s) f((int64_t)qoff[s], (b0 + s) * Q, (int64_t)(qoff[s + 1] - qoff[s]), s);
+    }
     int Nk = 0;  // keys of the tracks_to_latents cross attention per sample: N, or the sample's live support tracks in a ragged batch
     int64_t n_off = 0, q_off = 0; int Nc = 0, Qc = 0; bool count_plan = true;  // count_plan: false for the backward's recompute (spa3d_plan_stats counts pass A only)
     // encoder
     T* sinbuf; const void* dino; const void* depthf; float* km; T* tok0; std::vector<BlockStash<T>> enc_st; T* enc_last; T* r0; float* st_r0;
     T* enc_out; LastStash enc_lst, ro_lst; T* enc_ln_all = nullptr; float* st_all = nullptr; const float* sup_vis = nullptr;
-    Rag enc_rg; int32_t* row_src = nullptr;  // token pruning of the track encoder (encode_chunk)
+    Rag enc_rg; int32_t* row_src = nullptr;  // token pruning of the track encoder (encode_tracks)
     // t2l
     T* lat_in; std::vector<BlockStash<T>> t2l_st; T* t2l_last; float* st_t2l; T* t2l_n; float* latents;  // [Bc,L,Ld] f32
     // decode
@@ -491,12 +504,7 @@ template <typename T> struct Net {
     float* head;
   };
 
-  // E1-E7 + L1-L3 (track_autoencoder_3d.py:123-204)
-  void encode_chunk(Chunk& k, const spa3d_batch* b, int64_t b0, bool train) {
-    encode_tracks(k, b, b0, train);
-    encode_latents(k, train);
-  }
-  // E1-E7 on tracks [k.n_off, k.n_off + k.Nc) of samples [b0, b0 + k.Bc) -> k.enc_out [nseq, d] (written to enc_dst when given, else allocated here)
+  // E1-E7 (track_autoencoder_3d.py:123-188; with encode_latents: -204) on tracks [k.n_off, k.n_off + k.Nc) of samples [b0, b0 + k.Bc) -> k.enc_out [nseq, d] (written to enc_dst when given, else allocated here)
   void encode_tracks(Chunk& k, const spa3d_batch* b, int64_t b0, bool train, T* enc_dst = nullptr) {
     const int d = g.track_token_dim, nf = g.num_frequencies, T_ = k.T_, S = k.S;
     const int64_t nseq = k.nseq, trk0 = b0 * k.N + k.n_off;  // first track row of the slice (tracks of a sample chunk are contiguous when Nc < N: Bc = 1)
@@ -646,7 +654,7 @@ template <typename T> struct Net {
     lin_fwd(comp, k.t2l_n, k.latents, k.Bc * L, EPI_NONE, nullptr, 1);                               // 3d:203
   }
 
-  // D1-D7: discretise, decompressor, decoder stack -> k.latd [Bc,L,Cl] (once per sample chunk)
+  // D1-D7 (track_autoencoder_3d.py:206-263; with decode_queries, D8: -307): discretise, decompressor, decoder stack -> k.latd [Bc,L,Cl] (once per sample chunk).  latents_in: [Bc,L,Ld] f32
   void decode_latents(Chunk& k, const spa3d_batch* b, const float* latents_in, const float* noise, int64_t b0, bool train) {
     const int L = g.num_latent_tokens, Ld = g.latent_token_dim, dd = g.decoder_num_channels, Cl = dd - 128;
     const int64_t nl = k.Bc * L;
@@ -666,12 +674,7 @@ template <typename T> struct Net {
     k.st_dec = alloc<float>(nl * 2); k.latd = alloc<T>(nl * Cl);
     k_layernorm<T>(c, x, dec.norm_enc, k.latd, k.st_dec, nl, Cl);
   }
-  // D1-D8 (track_autoencoder_3d.py:206-307).  latents_in: [Bc,L,Ld] f32
-  void decode_chunk(Chunk& k, const spa3d_batch* b, int64_t b0, const float* latents_in, const float* noise, bool train) {
-    decode_latents(k, b, latents_in, noise, b0, train);
-    decode_queries(k, b, b0, train);
-  }
-  // query tokens, readout stack and head of queries [k.q_off, k.q_off + k.Qc) of samples [b0, b0 + k.Bc) against k.latd
+  // D8: query tokens, readout stack and head of queries [k.q_off, k.q_off + k.Qc) of samples [b0, b0 + k.Bc) against k.latd
   void decode_queries(Chunk& k, const spa3d_batch* b, int64_t b0, bool train) {
     const int L = g.num_latent_tokens, dd = g.decoder_num_channels, Cl = dd - 128, nf = g.num_frequencies;
     const int64_t nq = k.nq();
@@ -679,13 +682,13 @@ template <typename T> struct Net {
     // query tokens                                                                                     3d:209-233,265-275
     const int F = NC * 2 * nf + 1;
     k.feat = alloc<float>(nq * F); k.qframe = alloc<int32_t>(nq);
-    const float* qp = b->query_points + (b0 * k.Q + k.q_off) * (NC + 1);
-    if (k.packed && !k.folds) {  // the live query points of the chunk's samples, back to back (folds: consecutive rows of the clip already)
-      float* pq = alloc<float>(nq * (NC + 1));
-      for (int64_t s = 0; s < k.Bc; ++s)
-        copy_dd(pq + (int64_t)k.qoff[s] * (NC + 1), b->query_points + (b0 + s) * k.Q * (NC + 1), (int64_t)(k.qoff[s + 1] - k.qoff[s]) * (NC + 1) * 4);
-      qp = pq;
-    }
+    // the chunk's query points where they lie in the batch, or -- a packed chunk -- the live ones of its samples copied back to back
+    float* pq = k.packed && !k.folds ? alloc<float>(nq * (NC + 1)) : nullptr;
+    const float* qp = pq;
+    k.for_each_query_span(b0, [&](int64_t r, int64_t br, int64_t n, int64_t) {
+      const float* src = b->query_points + br * (NC + 1);
+      if (pq) copy_dd(pq + r * (NC + 1), src, n * (NC + 1) * 4); else qp = src;
+    });
     k_query_embed1(c, qp, nq, nf, g.track_scale_factor, g.time_scale_factor, k.feat, k.qframe, NC);
     k.sin2 = alloc<T>(nq * F * 2 * nf);
     k_sin_embed<T>(c, k.feat, nq, F, nf, g.track_scale_factor, k.sin2);
@@ -762,34 +765,19 @@ template <typename T> struct Net {
     if (hipEventRecord((hipEvent_t)c->grad_ev[i], c->stream) != hipSuccess && !c->hip_err) { c->hip_err = -6; c->err = "recording a gradient-segment event failed"; }
     else c->grad_ev_gen[i] += 1;
   }
-  // full backward of one chunk; parameter gradients accumulate into G
-  void backward_chunk(Chunk& k, const spa3d_batch* b, int64_t b0, const float* denom_dev) {
-    const int L = g.num_latent_tokens, Cl = g.decoder_num_channels - 128;
-    const int64_t mk0 = c->ar.mark();
-    float* dlatd32 = alloc<float>(k.Bc * L * Cl);
-    backward_queries(k, b, b0, denom_dev, dlatd32, false);
-    grad_segment_done(0);  // track_readout_attn, query_encoder, track_predictor: final once the LAST chunk has come this far
-    T* denc_out = backward_latents(k, dlatd32);
-    backward_tracks(k, denc_out);
-    c->ar.release(mk0);
-  }
+  // The backward of a chunk in three stages; parameter gradients accumulate into G.
   // head, readout transformer, assembly, query encoder of queries [k.q_off, k.q_off + k.Qc): dlatd32 [Bc,L,Cl] = (accumulate ? += : =) the latent-side gradient
   void backward_queries(Chunk& k, const spa3d_batch* b, int64_t b0, const float* denom_dev, float* dlatd32, bool accumulate) {
     const int L = g.num_latent_tokens, dd = g.decoder_num_channels, Cl = dd - 128, To = g.num_output_frames;
-    const int64_t nq = k.nq(), qrow = b0 * k.Q + k.q_off;
+    const int64_t nq = k.nq();
     {
       const int S = L + 1;
       const int64_t mk = c->ar.mark();
       T* dhead = alloc<T>(nq * 4 * To);
-      if (k.packed) {  // targets stay in the padded layout: sample by sample
-        for (int64_t s = 0; s < k.Bc; ++s) {
-          const int64_t q0 = k.qoff[s], tr = (b0 + s) * k.Q;
-          k_loss_bwd<T>(c, k.head + q0 * 4 * To, k.qoff[s + 1] - k.qoff[s], To, b->query_tracks + tr * To * NC, b->query_tracks_visible + tr * To, denom_dev,
-                        c->loss, at_rows(ptw, tr * To), dhead + q0 * 4 * To, NC, c->loss_scale != 1.f ? denom_dev + 1 : nullptr);
-        }
-      }
-      else k_loss_bwd<T>(c, k.head, nq, To, b->query_tracks + qrow * To * NC, b->query_tracks_visible + qrow * To, denom_dev,
-                    c->loss, at_rows(ptw, qrow * To), dhead, NC, c->loss_scale != 1.f ? denom_dev + 1 : nullptr);  // + loss scale in fp16 mode
+      k.for_each_query_span(b0, [&](int64_t r, int64_t br, int64_t n, int64_t) {  // targets stay in the batch's padded layout
+        k_loss_bwd<T>(c, k.head + r * 4 * To, n, To, b->query_tracks + br * To * NC, b->query_tracks_visible + br * To, denom_dev,
+                      c->loss, at_rows(ptw, br * To), dhead + r * 4 * To, NC, c->loss_scale != 1.f ? denom_dev + 1 : nullptr);  // + loss scale in fp16 mode
+      });
       lin_bwd_w(pred, k.q0n, dhead, nq);
       T* dq0n = alloc<T>(nq * dd);
       lin_bwd_x(pred, dhead, dq0n, nq);
@@ -920,118 +908,101 @@ static void score_zero_rows(spa3d_ctx* c, const spa3d_scores* sc, int64_t r0, in
   (void)hipMemsetAsync(sc->query_stats + r0 * S, 0, (size_t)(nr * S) * 4, c->stream);
   if (sc->frame_err) (void)hipMemsetAsync(sc->frame_err + r0 * To, 0, (size_t)(nr * To) * 4, c->stream);
 }
-// per-track scores of the queries [k.q_off, k.q_off + k.Qc) of samples [b0, b0 + k.Bc) from k.head (spa3d_score): one launch next to the output kernel
-template <typename T>
-static void emit_scores(spa3d_ctx* c, const RunArgs& a, Net<T>& net, typename Net<T>::Chunk& k, int64_t b0) {
-  const spa3d_batch* b = a.b; const int To = c->cfg.num_output_frames;
-  ScoreArgs s = score_args(b, a.score, To, net.NC);
-  if (k.packed && !k.folds) {  // targets and results stay in the padded layout: sample by sample, padded rows zeroed
-    for (int64_t i = 0; i < k.Bc; ++i) {
-      const int64_t r = (b0 + i) * b->Q, q0 = k.qoff[i], qs = k.qoff[i + 1] - k.qoff[i];
-      s.head = k.head + q0 * 4 * To; s.nq = qs; s.row0 = r;
-      k_score_rows(c, s);
-      score_zero_rows(c, a.score, r + qs, b->Q - qs, To);
-    }
-    return;
-  }
-  s.head = k.head; s.nq = k.nq(); s.row0 = b0 * b->Q + k.q_off;  // (folds: the group's queries are consecutive rows of the clip, in batch row order)
-  k_score_rows(c, s);
+// The query rows [r0, r0 + nr) of the batch -- the padded queries of a sample of a ragged batch -- read as 0 in every tensor the call writes per query
+static void zero_padded_rows(spa3d_ctx* c, const RunArgs& a, int NC, int64_t r0, int64_t nr) {
+  if (c->dry || nr <= 0) return;
+  const int To = c->cfg.num_output_frames;
+  if (a.out && a.out->tracks) (void)hipMemsetAsync(a.out->tracks + r0 * To * NC, 0, (size_t)(nr * To * NC) * 4, c->stream);
+  if (a.out && a.out->visible_logits) (void)hipMemsetAsync(a.out->visible_logits + r0 * To, 0, (size_t)(nr * To) * 4, c->stream);
+  if (a.out && a.out->certain_logits) (void)hipMemsetAsync(a.out->certain_logits + r0 * To, 0, (size_t)(nr * To) * 4, c->stream);
+  if (a.score) score_zero_rows(c, a.score, r0, nr, To);
 }
 
-// outputs and loss sums of the queries [k.q_off, k.q_off + k.Qc) of samples [b0, b0 + k.Bc) from k.head
+// Per-track scores (spa3d_score), then outputs and loss sums, of the chunk's queries from k.head: one launch each per span of batch rows
+// (Chunk::for_each_query_span).  Targets and results stay in the batch's padded layout.
 template <typename T>
 static void emit_outputs(spa3d_ctx* c, const RunArgs& a, Net<T>& net, typename Net<T>::Chunk& k, int64_t b0, float* sums, unsigned* poison) {
-  if (a.score) { emit_scores<T>(c, a, net, k, b0); if (!a.out) return; }  // spa3d_score(out = NULL) writes no prediction tensor at all
   const spa3d_batch* b = a.b; const int To = c->cfg.num_output_frames, NC = net.NC;
   const bool train = a.mode == MODE_TRAIN;
-  if (k.packed && !k.folds) {  // outputs and targets stay in the padded layout: sample by sample, and the padded query rows read as 0
-    for (int64_t s = 0; s < k.Bc; ++s) {
-      const int64_t r = (b0 + s) * b->Q, q0 = k.qoff[s], qs = k.qoff[s + 1] - k.qoff[s], pad = b->Q - qs;
-      float* tr = a.out && a.out->tracks ? a.out->tracks + r * To * NC : nullptr;
-      float* vl = a.out && a.out->visible_logits ? a.out->visible_logits + r * To : nullptr;
-      float* cl = a.out && a.out->certain_logits ? a.out->certain_logits + r * To : nullptr;
-      k_loss_fwd(c, k.head + q0 * 4 * To, qs, To, train ? b->query_tracks + r * To * NC : nullptr, train ? b->query_tracks_visible + r * To : nullptr,
-                 tr, vl, cl, sums, poison, NC, c->loss, train ? at_rows(a.w, r * To) : nullptr);
-      if (tr && pad > 0) k_zero(c, tr + qs * To * NC, pad * To * NC * 4);
-      if (vl && pad > 0) k_zero(c, vl + qs * To, pad * To * 4);
-      if (cl && pad > 0) k_zero(c, cl + qs * To, pad * To * 4);
-    }
-    return;
+  if (a.score) {
+    ScoreArgs s = score_args(b, a.score, To, NC);
+    k.for_each_query_span(b0, [&](int64_t r, int64_t br, int64_t n, int64_t) { s.head = k.head + r * 4 * To; s.nq = n; s.row0 = br; k_score_rows(c, s); });
+    if (!a.out) return;  // spa3d_score(out = NULL) writes no prediction tensor at all
   }
-  const int64_t nq = k.nq(), qrow = b0 * b->Q + k.q_off;
-  float* tr = a.out && a.out->tracks ? a.out->tracks + qrow * To * NC : nullptr;
-  float* vl = a.out && a.out->visible_logits ? a.out->visible_logits + qrow * To : nullptr;
-  float* cl = a.out && a.out->certain_logits ? a.out->certain_logits + qrow * To : nullptr;
-  k_loss_fwd(c, k.head, nq, To, train ? b->query_tracks + qrow * To * NC : nullptr, train ? b->query_tracks_visible + qrow * To : nullptr,
-             tr, vl, cl, sums, poison, NC, c->loss, train ? at_rows(a.w, qrow * To) : nullptr);
+  k.for_each_query_span(b0, [&](int64_t r, int64_t br, int64_t n, int64_t) {
+    float* tr = a.out && a.out->tracks ? a.out->tracks + br * To * NC : nullptr;
+    float* vl = a.out && a.out->visible_logits ? a.out->visible_logits + br * To : nullptr;
+    float* cl = a.out && a.out->certain_logits ? a.out->certain_logits + br * To : nullptr;
+    k_loss_fwd(c, k.head + r * 4 * To, n, To, train ? b->query_tracks + br * To * NC : nullptr, train ? b->query_tracks_visible + br * To : nullptr,
+               tr, vl, cl, sums, poison, NC, c->loss, train ? at_rows(a.w, br * To) : nullptr);
+  });
 }
 
-// One sample with intra-sample chunks (spa3d_set_option "track_chunk" / "query_chunk"; k.Bc == 1).
+// One chunk of k.Bc >= 1 samples [b0, b0 + k.Bc), in every mode: the one route a sample takes through the network, whether the chunk is uniform, one
+// sample of a ragged batch (spa3d_set_counts) addressed in place at its own size -- its live rows are the first rows of its slice of the padded
+// tensors, nothing at or beyond a count is read -- or several such samples packed back to back (Chunk::packed).
+// Intra-sample chunks (spa3d_set_option "track_chunk" / "query_chunk"; run() has made k.Bc == 1):
 //  track_chunk: pass A runs the track encoder over chunks of tracks without a stash (the no-stash ping-pong path) into one persistent
 //    [N, d] enc_out; tracks_to_latents sees all N keys as before.  Pass B, after the latent-side backward has produced d enc_out for all N
 //    tracks, re-runs each chunk's encoder forward WITH its stash and its backward against its rows (the reference's nn.remat idea, applied to
 //    the largest stash).  Parameter gradients accumulate as they do across sample chunks.
 //  query_chunk: readout rows depend on their query and the sample's latents only, and the loss denominator is batch-global and known up front,
-//    so each chunk of queries runs embed -> readout -> head -> loss -> readout backward and releases its arena; the latent-side gradient
-//    dlatd32 is written by the first chunk and accumulated (fp32, fixed order, no atomics) by the others.
-// A sample of a ragged batch (spa3d_set_counts) takes the same route with nlive <= N support tracks and qlive <= Q queries: its live rows are the
-// first rows of its slice of the padded tensors, so the sample runs as a sample of its own size on offset pointers -- nothing at or beyond a count
-// is read -- and the padded output rows are zeroed.  qlive == 0: the sample is encoded and contributes no loss and no gradient.
+//    so each chunk of queries runs embed -> readout -> head -> loss -> readout backward; the latent-side gradient dlatd32 is written by the
+//    first chunk and accumulated (fp32, fixed order, no atomics) by the others.  Without query_chunk the loop below has one iteration.
 template <typename T>
-static void run_sample_intra(spa3d_ctx* c, const RunArgs& a, Net<T>& net, typename Net<T>::Chunk& k, int64_t b0, const float* noise, float* sums,
-                             unsigned* poison, const float* denom_dev, int nlive, int qlive) {
+static void run_chunk(spa3d_ctx* c, const RunArgs& a, Net<T>& net, typename Net<T>::Chunk& k, int64_t b0, const float* noise, float* sums,
+                      unsigned* poison, const float* denom_dev) {
   const spa3d_batch* b = a.b; const spa3d_config& g = c->cfg;
   const int L = g.num_latent_tokens, Ld = g.latent_token_dim, Cl = g.decoder_num_channels - 128, d = g.track_token_dim;
   const bool train = a.mode == MODE_TRAIN;
-  const int tc = c->track_chunk > 0 ? std::min(c->track_chunk, nlive) : nlive, qc = c->query_chunk > 0 ? std::min(c->query_chunk, qlive) : qlive;
-  auto track_slice = [&](int64_t n0) { k.n_off = n0; k.Nc = (int)std::min<int64_t>(tc, nlive - n0); k.nseq = k.Nc; };
+  // The readout stash of a query chunk is released when the chunk is done -- before backward_latents -- on the calls that have always done so:
+  // intra-sample chunks, and a ragged sample alone in its chunk.  Every other chunk keeps it to its end, as it always has.  Releasing it everywhere
+  // would lower the training need (and so raise the chunk size a workspace gives, and change the step time): a follow-up with a benchmark of its own.
+  const bool release_each = c->query_chunk > 0 || c->track_chunk > 0 || (k.ragged && !k.packed);
+  const int64_t ntrk = k.nseq, Qall = k.Qc;  // (track_chunk / query_chunk: k.Bc == 1)
+  const int64_t tc = c->track_chunk > 0 ? std::min<int64_t>(c->track_chunk, ntrk) : ntrk, qc = c->query_chunk > 0 ? std::min<int64_t>(c->query_chunk, Qall) : Qall;
+  auto track_slice = [&](int64_t n0) { k.n_off = n0; k.Nc = (int)std::min(tc, ntrk - n0); k.nseq = k.Nc; };
   if (a.mode != MODE_DECODE) {
     if (c->track_chunk > 0) {  // pass A
-      T* enc_all = net.template alloc<T>((int64_t)nlive * d);
-      for (int64_t n0 = 0; n0 < nlive; n0 += tc) {
+      T* enc_all = net.template alloc<T>(ntrk * d);
+      for (int64_t n0 = 0; n0 < ntrk; n0 += tc) {
         track_slice(n0);
         const int64_t mk = c->ar.mark();
         poison_from(c, mk);
         net.encode_tracks(k, b, b0, false, enc_all + n0 * d);
         c->ar.release(mk);
       }
-      k.enc_out = enc_all; k.n_off = 0; k.Nc = nlive; k.nseq = nlive;
+      k.enc_out = enc_all; k.n_off = 0; k.Nc = (int)ntrk; k.nseq = ntrk;
     } else {
       net.encode_tracks(k, b, b0, train);
     }
     net.encode_latents(k, train);
     float* lo = a.latents_out ? a.latents_out : (a.out && a.out->latents ? a.out->latents : nullptr);
-    if (lo && !c->dry) (void)hipMemcpyAsync(lo + b0 * L * Ld, k.latents, (size_t)L * Ld * 4, hipMemcpyDeviceToDevice, c->stream);
+    if (lo && !c->dry) (void)hipMemcpyAsync(lo + b0 * L * Ld, k.latents, (size_t)(k.Bc * L * Ld) * 4, hipMemcpyDeviceToDevice, c->stream);
   }
   if (a.mode == MODE_ENCODE) return;
-  if (qlive < b->Q && !c->dry) {  // padded query rows of the outputs read as 0
-    const int To = g.num_output_frames; const int64_t r0 = b0 * b->Q + qlive, nr = b->Q - qlive;
-    if (a.out && a.out->tracks) (void)hipMemsetAsync(a.out->tracks + r0 * To * net.NC, 0, (size_t)(nr * To * net.NC) * 4, c->stream);
-    if (a.out && a.out->visible_logits) (void)hipMemsetAsync(a.out->visible_logits + r0 * To, 0, (size_t)(nr * To) * 4, c->stream);
-    if (a.out && a.out->certain_logits) (void)hipMemsetAsync(a.out->certain_logits + r0 * To, 0, (size_t)(nr * To) * 4, c->stream);
-    if (a.score) score_zero_rows(c, a.score, r0, nr, To);
-  }
-  if (qlive == 0) {  // no live query: no readout, no loss term, no gradient; the call's gradient segments may still end with this sample
+  if (a.cq) for (int64_t s = 0; s < k.Bc; ++s) zero_padded_rows(c, a, net.NC, (b0 + s) * b->Q + a.cq[b0 + s], b->Q - a.cq[b0 + s]);
+  if (k.nq() == 0) {  // no live query: no readout, no loss term, no gradient; the call's gradient segments may still end with this chunk
     if (train) { net.grad_segment_done(0); net.grad_segment_done(1); }
     return;
   }
   net.decode_latents(k, b, a.mode == MODE_DECODE ? a.latents_in + b0 * L * Ld : k.latents, noise, b0, train);
-  float* dlatd32 = train ? net.template alloc<float>((int64_t)L * Cl) : nullptr;
-  for (int64_t q0 = 0; q0 < qlive; q0 += qc) {
-    k.q_off = q0; k.Qc = (int)std::min<int64_t>(qc, qlive - q0);
+  float* dlatd32 = train ? net.template alloc<float>(k.Bc * L * Cl) : nullptr;
+  for (int64_t q0 = 0; q0 < Qall; q0 += qc) {
+    k.q_off = q0; k.Qc = (int)std::min(qc, Qall - q0);
     const int64_t mk = c->ar.mark();
-    poison_from(c, mk);
+    if (release_each) poison_from(c, mk);
     net.decode_queries(k, b, b0, train);
     emit_outputs<T>(c, a, net, k, b0, sums, poison);
     if (train) net.backward_queries(k, b, b0, denom_dev, dlatd32, q0 > 0);
-    c->ar.release(mk);
+    if (release_each) c->ar.release(mk);
   }
   if (!train) return;
-  net.grad_segment_done(0);  // after the last query chunk (of the last sample chunk: grad_segment_done checks)
+  net.grad_segment_done(0);  // track_readout_attn, query_encoder, track_predictor: final after the last query chunk of the LAST sample chunk (grad_segment_done checks)
   const T* denc_out = net.backward_latents(k, dlatd32);
   if (c->track_chunk <= 0) { net.backward_tracks(k, denc_out); return; }
   k.count_plan = false;  // pass B: recompute + backward per track chunk
-  for (int64_t n0 = 0; n0 < nlive; n0 += tc) {
+  for (int64_t n0 = 0; n0 < ntrk; n0 += tc) {
     track_slice(n0);
     const int64_t mk = c->ar.mark();
     poison_from(c, mk);
@@ -1126,7 +1097,6 @@ void run_body(spa3d_ctx* c, const RunArgs& a, int Bc) {
     c->det = dc;
   }
   const bool ragged = a.cn || a.cq;  // per-sample counts (spa3d_set_counts; run() has validated them)
-  const bool intra = c->query_chunk > 0 || c->track_chunk > 0;  // run() has made Bc = 1
   // The ragged chunk (B % Bc samples) runs FIRST, so the last chunk -- the one under whose track-encoder backward the gradient segments are all-reduced -- is a
   // full one (B = 64, Bc = 9: 9 samples of encoder backward to hide behind instead of 1)
   if (a.nfold > 0) run_folds<T>(c, a, net, noise, sums, poison, Bc);  // (Bc: folds per readout group)
@@ -1136,9 +1106,9 @@ void run_body(spa3d_ctx* c, const RunArgs& a, int Bc) {
     c->last_chunk = b0 + cur >= b->B;
     k.Bc = cur; k.N = b->N; k.Q = b->Q; k.T_ = b->T; k.S = b->T + (g.model_kind == 1 ? 0 : 1); k.nseq = k.Bc * b->N;
     k.Nc = b->N; k.Qc = b->Q; k.Nk = b->N;
-    const int nlive = a.cn ? a.cn[b0] : b->N, qlive = a.cq ? a.cq[b0] : b->Q;
-    if (ragged && cur == 1) { k.ragged = true; k.Nc = k.Nk = nlive; k.nseq = nlive; k.Qc = qlive; }  // one sample: addressed in place, at its own size
-    else if (ragged) {  // several samples: their live rows packed back to back
+    if (ragged && cur == 1) {  // one sample: addressed in place, at its own size
+      k.ragged = true; k.Nc = k.Nk = a.cn ? a.cn[b0] : b->N; k.nseq = k.Nc; k.Qc = a.cq ? a.cq[b0] : b->Q;
+    } else if (ragged) {  // several samples: their live rows packed back to back
       k.ragged = k.packed = true; k.noff.assign(1, 0); k.qoff.assign(1, 0);
       for (int64_t s = 0; s < cur; ++s) {
         k.noff.push_back(k.noff.back() + (a.cn ? a.cn[b0 + s] : b->N));
@@ -1148,23 +1118,7 @@ void run_body(spa3d_ctx* c, const RunArgs& a, int Bc) {
     }
     const int64_t mk = c->ar.mark();
     poison_from(c, mk);
-    if (intra || (ragged && cur == 1)) { run_sample_intra<T>(c, a, net, k, b0, noise, sums, poison, denom_dev, nlive, qlive); c->ar.release(mk); continue; }
-    const float* lat = nullptr;
-    if (a.mode != MODE_DECODE) {
-      net.encode_chunk(k, b, b0, train);
-      lat = k.latents;
-      float* lo = a.latents_out ? a.latents_out : (a.out && a.out->latents ? a.out->latents : nullptr);
-      if (lo && !c->dry) (void)hipMemcpyAsync(lo + b0 * L * Ld, k.latents, k.Bc * L * Ld * 4, hipMemcpyDeviceToDevice, c->stream);
-    } else {
-      lat = a.latents_in + b0 * L * Ld;
-    }
-    if (a.mode != MODE_ENCODE) {
-      const bool no_query = k.packed && k.nq() == 0;  // a packed chunk without a single live query: outputs 0, no loss term, no gradient
-      if (!no_query) net.decode_chunk(k, b, b0, lat, noise, train);
-      emit_outputs<T>(c, a, net, k, b0, sums, poison);
-      if (train && !no_query) net.backward_chunk(k, b, b0, denom_dev);
-      if (train && no_query) { net.grad_segment_done(0); net.grad_segment_done(1); }
-    }
+    run_chunk<T>(c, a, net, k, b0, noise, sums, poison, denom_dev);
     c->ar.release(mk);
   }
   if (c->det) {
@@ -1271,6 +1225,34 @@ static int64_t dry_need(spa3d_ctx* c, const RunArgs& a, int Bc) {
   RunArgs d = a; d.P = (const float*)0x100000; d.G = a.G ? (float*)0x100000 : nullptr;
   return arena_peak(c, [&] { run_dispatch(c, d, Bc); }) + 4096;
 }
+// The batch of a sizing walk: sizes only.  Its pointers are never dereferenced (the dry run launches nothing), but the orchestration offsets them per
+// chunk and arithmetic on a null pointer is undefined behaviour (UBSan, tests/test_host_sanitizers.py): they point at a fake non-null base
+static spa3d_batch sizing_batch(const spa3d_ctx* c, int B, int N, int Q, int T) {
+  spa3d_batch b{}; b.B = B; b.N = N; b.Q = Q; b.T = T; b.discretize = 1;
+  const float* fake = (const float*)(uintptr_t)0x100000;
+  b.support_tracks = fake; b.support_tracks_visible = fake; b.query_points = fake; b.boundary_frame = (const int32_t*)fake;
+  b.query_tracks = fake; b.query_tracks_visible = fake;
+  b.dino_features = c->cfg.dino_feature_dim > 0 ? (const void*)fake : nullptr;
+  b.depth_features = c->cfg.depth_feature_dim > 0 ? (const void*)fake : nullptr;
+  return b;
+}
+// The tail of every call that runs the network.  [lo, hi]: the counts the call may run with (samples per chunk, or folds per readout group).  The need at
+// `lo` (at least `floor`) is checked first -- `refuse(need)` words the entry's message and gives its status (sized_call has one wording, the entries
+// here two) --, then the largest count that fits is found by bisection over dry runs and the call runs in the caller's workspace.
+template <typename R> static int sized_run(spa3d_ctx* c, const RunArgs& a, int lo, int hi, int64_t floor, void* ws, int64_t ws_bytes, void* stream, R&& refuse) {
+  const int64_t need = std::max(floor, dry_need(c, a, lo));
+  if (ws_bytes < need) return refuse(need);
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) / 2;
+    if (dry_need(c, a, mid) <= ws_bytes) lo = mid; else hi = mid - 1;
+  }
+  c->stream = (hipStream_t)stream; c->dry = false;
+  c->ar = Arena(); c->ar.base = (char*)ws; c->ar.cap = ws_bytes;
+  for (double& v : c->plan_stats) v = 0;
+  run_dispatch(c, a, lo);
+  if (c->ar.overflow) { c->err = "internal: arena overflow"; return SPA3D_ERR_WORKSPACE; }
+  return c->hip_err ? SPA3D_ERR_HIP : SPA3D_OK;
+}
 
 // "gemm_impl" of a handle: 7 and 10 are spa3d_op_linear's one-kernel hooks; on a handle they mean 2, the product dispatch
 static void set_gemm_impl(spa3d_ctx* c, int v) { c->gemm = GemmPolicy::from_impl(v == 7 || v == 10 ? 2 : v); }
@@ -1290,7 +1272,6 @@ static int run(spa3d_ctx* c, RunArgs a, void* ws, int64_t ws_bytes, void* stream
   c->err.clear(); c->hip_err = 0;
   int rc = check_batch(c, a.b, a.mode);
   if (rc) return rc;
-  c->stream = (hipStream_t)stream;
   int lo = 1, hi = a.b->B;
   if (a.chunk <= 0) a.chunk = c->chunk;  // spa3d_set_option "chunk" / SPA3D_CHUNK: fixed samples per chunk (tests: chunk-to-chunk reuse of the arena)
   if (c->query_chunk > 0 || c->track_chunk > 0) {  // intra-sample chunks: one sample per sample chunk
@@ -1322,20 +1303,10 @@ static int run(spa3d_ctx* c, RunArgs a, void* ws, int64_t ws_bytes, void* stream
     if (full) { a.cn = nullptr; a.cq = nullptr; }
   }
   if (a.chunk > 0) { lo = hi = std::min(a.chunk, a.b->B); }
-  if (dry_need(c, a, lo) > ws_bytes) {
-    c->err = "workspace too small: need " + std::to_string(dry_need(c, a, lo)) + " bytes for chunk " + std::to_string(lo);
+  return sized_run(c, a, lo, hi, 0, ws, ws_bytes, stream, [&](int64_t need) {
+    c->err = "workspace too small: need " + std::to_string(need) + " bytes for chunk " + std::to_string(lo);
     return SPA3D_ERR_WORKSPACE;
-  }
-  while (lo < hi) {  // largest chunk that fits
-    int mid = (lo + hi + 1) / 2;
-    if (dry_need(c, a, mid) <= ws_bytes) lo = mid; else hi = mid - 1;
-  }
-  c->ar = Arena(); c->ar.base = (char*)ws; c->ar.cap = ws_bytes; c->dry = false;
-  for (double& v : c->plan_stats) v = 0;
-  run_dispatch(c, a, lo);
-  if (c->ar.overflow) { c->err = "internal: arena overflow"; return SPA3D_ERR_WORKSPACE; }
-  if (c->hip_err) return SPA3D_ERR_HIP;
-  return SPA3D_OK;
+  });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1394,14 +1365,7 @@ int spa3d_leaf_info(spa3d_handle h, int32_t i, char* name, int32_t* ndim, int64_
 
 int64_t spa3d_workspace_bytes(spa3d_handle h, int32_t B, int32_t N, int32_t Q, int32_t T, int32_t chunk, int32_t train) {
   if (!h || B <= 0 || N <= 0 || Q <= 0 || T <= 0) return -1;
-  spa3d_batch b{}; b.B = B; b.N = N; b.Q = Q; b.T = T; b.discretize = 1;
-  // never dereferenced (the dry run launches nothing), but the orchestration offsets them per chunk: arithmetic on a null pointer is undefined
-  // behaviour (UBSan, tests/test_host_sanitizers.py), so the dummy batch points at a fake non-null base
-  const float* fake = (const float*)(uintptr_t)0x100000;
-  b.support_tracks = fake; b.support_tracks_visible = fake; b.query_points = fake; b.boundary_frame = (const int32_t*)fake;
-  b.query_tracks = fake; b.query_tracks_visible = fake;
-  b.dino_features = h->cfg.dino_feature_dim > 0 ? (const void*)fake : nullptr;
-  b.depth_features = h->cfg.depth_feature_dim > 0 ? (const void*)fake : nullptr;
+  const spa3d_batch b = sizing_batch(h, B, N, Q, T);
   RunArgs a{}; a.mode = train ? MODE_TRAIN : MODE_FORWARD; a.b = &b; a.G = train ? (float*)0x100000 : nullptr;
   if (h->query_chunk > 0 || h->track_chunk > 0) chunk = 1;  // intra-sample chunks process one sample at a time
   return dry_need(h, a, std::max(1, std::min(chunk, B)));
@@ -1449,12 +1413,7 @@ static std::vector<int32_t> equal_folds(int N, int F) {
 int64_t spa3d_score_folds_workspace_bytes(spa3d_handle h, int32_t N, int32_t T, int32_t num_folds) {
   if (!h || h->cfg.model_kind != 0 || T <= 0 || num_folds < 2 || num_folds > 64 || N < num_folds) return -1;
   const std::vector<int32_t> off = equal_folds(N, num_folds);
-  spa3d_batch b{}; b.B = 1; b.N = N; b.Q = N; b.T = T; b.discretize = 1;
-  const float* fake = (const float*)(uintptr_t)0x100000;  // never dereferenced (see spa3d_workspace_bytes)
-  b.support_tracks = fake; b.support_tracks_visible = fake; b.query_points = fake; b.boundary_frame = (const int32_t*)fake;
-  b.query_tracks = fake; b.query_tracks_visible = fake;
-  b.dino_features = h->cfg.dino_feature_dim > 0 ? (const void*)fake : nullptr;
-  b.depth_features = h->cfg.depth_feature_dim > 0 ? (const void*)fake : nullptr;
+  const spa3d_batch b = sizing_batch(h, 1, N, N, T);
   RunArgs a{}; a.mode = MODE_FORWARD; a.b = &b; a.nfold = num_folds; a.fold_off = off.data();
   return dry_need(h, a, 1);  // the readout one fold at a time: the least a call with these folds can run in
 }
@@ -1482,19 +1441,9 @@ int spa3d_score_folds(spa3d_handle h, const float* params, const spa3d_batch* b,
   rc = check_scores(h, &bb, scores);
   if (rc) return rc;
   RunArgs a{}; a.mode = MODE_FORWARD; a.P = params; a.b = &bb; a.out = out; a.score = scores; a.nfold = num_folds; a.fold_off = fold_off;
-  const int64_t need = std::max(spa3d_score_folds_workspace_bytes(h, b->N, b->T, num_folds), dry_need(h, a, 1));
-  if (!ws || ws_bytes < need) return refuse("workspace too small: need " + std::to_string(need) + " bytes");
-  int lo = 1, hi = num_folds;  // folds per readout group: the most that fit
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) / 2;
-    if (dry_need(h, a, mid) <= ws_bytes) lo = mid; else hi = mid - 1;
-  }
-  h->stream = (hipStream_t)stream;
-  h->ar = Arena(); h->ar.base = (char*)ws; h->ar.cap = ws_bytes; h->dry = false;
-  for (double& v : h->plan_stats) v = 0;
-  run_dispatch(h, a, lo);
-  if (h->ar.overflow) { h->err = "internal: arena overflow"; return SPA3D_ERR_WORKSPACE; }
-  return h->hip_err ? SPA3D_ERR_HIP : SPA3D_OK;
+  // folds per readout group: the most that fit, at least one; never less than the workspace function promises for an even split (no workspace: 0 bytes)
+  return sized_run(h, a, 1, num_folds, spa3d_score_folds_workspace_bytes(h, b->N, b->T, num_folds), ws, ws ? ws_bytes : 0, stream,
+                   [&](int64_t need) { return refuse("workspace too small: need " + std::to_string(need) + " bytes"); });
 }
 int spa3d_score_from_preds(spa3d_handle h, const spa3d_batch* b, const spa3d_outputs* preds, spa3d_scores* scores, void* stream) {
   if (!h) return SPA3D_ERR_ARG;

@@ -69,6 +69,23 @@ int main() {
     CHECK(spa3d_set_counts(h, B, sets[0][0], sets[0][1]) == SPA3D_OK && spa3d_set_option(h, "chunk", 3) == SPA3D_OK);
     CHECK(spa3d_loss_and_grads(h, fake, &b, 0.f, fake, 0, fake, &out, fake, 0, nullptr) == SPA3D_ERR_WORKSPACE && need_of(h) > 0);
     CHECK(need_of(h) <= spa3d_workspace_bytes(h, B, N, Q, T, 3, 1));
+    // One sample alone in the first chunk and three packed in the second (B = 4, chunk = 3: B % chunk = 1) go through the same chunk driver.  The
+    // sample without live queries sits alone in its chunk, then inside the packed chunk; training and forward.  The sizing walk decides the call:
+    // one byte below the need it reports the call is refused with that same need (at the need it would go on to launch, which needs a device), and
+    // the need of samples at their own size stays within the padded bound.
+    const int32_t alone[2][4] = {{100, 512, 64, 300}, {0, 128, 1, 50}}, inside[2][4] = {{512, 100, 64, 300}, {128, 0, 1, 50}};
+    for (auto s : {alone, inside}) {
+      CHECK(spa3d_set_counts(h, B, s[0], s[1]) == SPA3D_OK);
+      CHECK(spa3d_loss_and_grads(h, fake, &b, 0.f, fake, 0, fake, &out, fake, 0, nullptr) == SPA3D_ERR_WORKSPACE && strstr(spa3d_last_error(h), "for chunk 3"));
+      const long long need_t = need_of(h);
+      CHECK(need_t > 0 && need_t <= spa3d_workspace_bytes(h, B, N, Q, T, 3, 1));
+      CHECK(spa3d_loss_and_grads(h, fake, &b, 0.f, fake, 0, fake, &out, fake, need_t - 1, nullptr) == SPA3D_ERR_WORKSPACE && need_of(h) == need_t);
+      CHECK(spa3d_forward(h, fake, &b, &out, fake, 0, nullptr) == SPA3D_ERR_WORKSPACE && strstr(spa3d_last_error(h), "for chunk 3"));
+      const long long need_f = need_of(h);
+      CHECK(need_f > 0 && need_f <= need_t && need_f <= spa3d_workspace_bytes(h, B, N, Q, T, 3, 0));
+      CHECK(spa3d_forward(h, fake, &b, &out, fake, need_f - 1, nullptr) == SPA3D_ERR_WORKSPACE && need_of(h) == need_f);
+      printf("precision %d chunk 3 of 4, query-less sample %s: need train %.3f GB, forward %.3f GB\n", prec, s == alone ? "alone" : "packed", need_t / 1e9, need_f / 1e9);
+    }
     CHECK(spa3d_set_option(h, "chunk", 0) == SPA3D_OK);
     // refusals: SPA3D_ERR_ARG with a message, before anything else happens
     const int32_t ok_n[4] = {512, 100, 64, 300}, ok_q[4] = {128, 0, 1, 50};
