@@ -141,6 +141,13 @@ int spa3d_op_broadcast_rows_f16(const float* src, int32_t rows, int32_t d, void*
 int spa3d_op_bcast_grad_f16(const void* dsrc, int64_t per, int64_t B, int64_t bstride, float* dparam, int32_t dtype, void* stream);
 int spa3d_op_vis_mean_pool_f16(const void* tok, const float* vis, int64_t nseq, int32_t T, int32_t d, void* out, int32_t dtype, void* stream);
 int spa3d_op_vis_mean_pool_bwd_f16(const void* dout, const float* vis, int64_t nseq, int32_t T, int32_t d, void* dtok, int32_t dtype, void* stream);
+int spa3d_op_sin_embed_scaled_f16(const float* x, int64_t rows, int32_t C, int32_t nf, float prescale, void* out, int32_t dtype, void* stream);
+int spa3d_op_embed_tokens_f16(const float* tracks, int64_t nrows, int32_t T, int32_t NC, int32_t nf, float prescale, void* out, int32_t dtype, void* stream);
+int spa3d_op_embed_maps_f16(const int32_t* row_src, int64_t rows, int32_t S, int32_t T, int32_t* arow, int32_t* crow, void* tok, const float* readout, int32_t d,
+                            int32_t dtype, void* stream);
+int spa3d_op_set_readout_rows_f16(void* tok, const float* readout, int64_t nseq, int32_t S, int32_t d, int32_t dtype, void* stream);
+int spa3d_op_pack_f16(const float* src, int64_t src_ld, int32_t rows, int32_t cols, void* dn, int64_t ldn, void* dt, int64_t ldt, int32_t dtype, void* stream);
+int spa3d_op_transpose_f16(const void* src, int32_t rows, int32_t cols, void* dst, int32_t dtype, void* stream);
 #pragma GCC visibility pop
 }
 #if SPA_F16
@@ -167,6 +174,12 @@ int spa3d_op_vis_mean_pool_bwd_f16(const void* dout, const float* vis, int64_t n
 #define spa3d_op_bcast_grad spa3d_op_bcast_grad_f16
 #define spa3d_op_vis_mean_pool spa3d_op_vis_mean_pool_f16
 #define spa3d_op_vis_mean_pool_bwd spa3d_op_vis_mean_pool_bwd_f16
+#define spa3d_op_sin_embed_scaled spa3d_op_sin_embed_scaled_f16
+#define spa3d_op_embed_tokens spa3d_op_embed_tokens_f16
+#define spa3d_op_embed_maps spa3d_op_embed_maps_f16
+#define spa3d_op_set_readout_rows spa3d_op_set_readout_rows_f16
+#define spa3d_op_pack spa3d_op_pack_f16
+#define spa3d_op_transpose spa3d_op_transpose_f16
 #define FWD16(call)
 #else
 #define FWD16(call) if (dtype == SPA3D_F16) return call;
@@ -485,5 +498,88 @@ int spa3d_op_vis_mean_pool_bwd(const void* dout, const float* vis, int64_t nseq,
   ROWS_BY_DTYPE(dtype, k_vis_mean_pool_bwd<T>(&c, (const T*)dout, vis, nseq, T_, d, (T*)dtok));
   return c.status();
 }
+
+// ---- The first mile of the model on its own (tests/test_gpu_embed.py): the embeddings, row maps, readout rows, key masks and weight shadows of csrc/embed.hip
+// and the latent quantiser of csrc/loss.hip.  Same rules as the row plumbing above.  SinScales holds 64 entries and is indexed by the feature number: a width
+// above 64 would read past the by-value kernel argument, so nf is checked here (spa3d_create checks num_frequencies; the launchers trust their caller).
+static bool embed_nf_ok(int32_t nf) { return nf >= 1 && nf <= 64; }
+static bool embed_scale_ok(float s) { return s != 0.f && s == s; }
+static const int32_t kTileRowsMax = 65535 * 32;   // pack / transpose put the row tiles on gridDim.y
+
+int spa3d_op_sin_embed_scaled(const float* x, int64_t rows, int32_t C, int32_t nf, float prescale, void* out, int32_t dtype, void* stream) {
+  FWD16(spa3d_op_sin_embed_scaled_f16(x, rows, C, nf, prescale, out, dtype, stream))
+  if (!x || !out || !ROWS_DTYPE_OK(dtype) || rows < 0 || C < 1 || C > 65536 || !embed_nf_ok(nf) || !embed_scale_ok(prescale)) return SPA3D_ERR_ARG;
+  OpCtx c(stream, nullptr, 0);
+  ROWS_BY_DTYPE(dtype, k_sin_embed<T>(&c, x, rows, C, nf, prescale, (T*)out));
+  return c.status();
+}
+int spa3d_op_embed_tokens(const float* tracks, int64_t nrows, int32_t T_, int32_t NC, int32_t nf, float prescale, void* out, int32_t dtype, void* stream) {
+  FWD16(spa3d_op_embed_tokens_f16(tracks, nrows, T_, NC, nf, prescale, out, dtype, stream))
+  if (!tracks || !out || !ROWS_DTYPE_OK(dtype) || nrows < 0 || T_ < 1 || (NC != 2 && NC != 3) || !embed_nf_ok(nf) || !embed_scale_ok(prescale)) return SPA3D_ERR_ARG;
+  OpCtx c(stream, nullptr, 0);
+  ROWS_BY_DTYPE(dtype, k_embed_tokens<T>(&c, tracks, nrows, T_, nf, prescale, (T*)out, NC));
+  return c.status();
+}
+int spa3d_op_embed_maps(const int32_t* row_src, int64_t rows, int32_t S, int32_t T_, int32_t* arow, int32_t* crow, void* tok, const float* readout, int32_t d,
+                        int32_t dtype, void* stream) {
+  FWD16(spa3d_op_embed_maps_f16(row_src, rows, S, T_, arow, crow, tok, readout, d, dtype, stream))
+  if (!arow || !crow || !tok || !readout || !ROWS_DTYPE_OK(dtype) || rows < 0 || rows > 0x7fffffffLL || T_ < 1 || S != T_ + 1 || d < 1) return SPA3D_ERR_ARG;
+  OpCtx c(stream, nullptr, 0);
+  ROWS_BY_DTYPE(dtype, k_embed_maps<T>(&c, row_src, rows, S, T_, arow, crow, (T*)tok, readout, d));
+  return c.status();
+}
+int spa3d_op_set_readout_rows(void* tok, const float* readout, int64_t nseq, int32_t S, int32_t d, int32_t dtype, void* stream) {
+  FWD16(spa3d_op_set_readout_rows_f16(tok, readout, nseq, S, d, dtype, stream))
+  if (!tok || !readout || !ROWS_DTYPE_OK(dtype) || nseq < 0 || S < 1 || d < 1) return SPA3D_ERR_ARG;
+  OpCtx c(stream, nullptr, 0);
+  ROWS_BY_DTYPE(dtype, k_set_readout_rows<T>(&c, (T*)tok, readout, nseq, S, d));
+  return c.status();
+}
+int spa3d_op_pack(const float* src, int64_t src_ld, int32_t rows, int32_t cols, void* dn, int64_t ldn, void* dt, int64_t ldt, int32_t dtype, void* stream) {
+  FWD16(spa3d_op_pack_f16(src, src_ld, rows, cols, dn, ldn, dt, ldt, dtype, stream))
+  if (!src || (!dn && !dt) || !ROWS_DTYPE_OK(dtype) || rows < 0 || rows > kTileRowsMax || cols < 0 || src_ld < cols || (dn && ldn < cols) || (dt && ldt < rows))
+    return SPA3D_ERR_ARG;
+  if (rows == 0 || cols == 0) return SPA3D_OK;   // (k_pack would launch an empty grid)
+  OpCtx c(stream, nullptr, 0);
+  ROWS_BY_DTYPE(dtype, k_pack<T>(&c, src, src_ld, rows, cols, (T*)dn, ldn, (T*)dt, ldt));
+  return c.status();
+}
+int spa3d_op_transpose(const void* src, int32_t rows, int32_t cols, void* dst, int32_t dtype, void* stream) {
+  FWD16(spa3d_op_transpose_f16(src, rows, cols, dst, dtype, stream))
+  if (!src || !dst || !ROWS_DTYPE_OK(dtype) || rows < 0 || rows > kTileRowsMax || cols < 0) return SPA3D_ERR_ARG;
+  if (rows == 0 || cols == 0) return SPA3D_OK;
+  OpCtx c(stream, nullptr, 0);
+  ROWS_BY_DTYPE(dtype, k_transpose<T>(&c, (const T*)src, rows, cols, (T*)dst));
+  return c.status();
+}
+
+#if !SPA_F16   // fp32 and int32 tensors only: one copy
+int spa3d_op_query_embed(const float* qp, int64_t nq, int32_t NC, int32_t nf, float track_scale, float time_scale, float* feat, int32_t* qframe, void* stream) {
+  if (!qp || !feat || !qframe || nq < 0 || (NC != 2 && NC != 3) || !embed_nf_ok(nf) || !embed_scale_ok(track_scale) || !embed_scale_ok(time_scale)) return SPA3D_ERR_ARG;
+  OpCtx c(stream, nullptr, 0);
+  k_query_embed1(&c, qp, nq, nf, track_scale, time_scale, feat, qframe, NC);
+  return c.status();
+}
+int spa3d_op_keymask(const float* visible, const int32_t* boundary, int64_t nseq, int32_t N, int32_t T_, int32_t with_readout, float* km, void* stream) {
+  if (!visible || !boundary || !km || nseq < 0 || N < 1 || nseq % N || T_ < 1 || (with_readout != 0 && with_readout != 1)) return SPA3D_ERR_ARG;
+  OpCtx c(stream, nullptr, 0);
+  if (with_readout) k_keymask(&c, visible, boundary, nseq, N, T_, km);
+  else k_keymask2d(&c, visible, boundary, nseq, N, T_, km);
+  return c.status();
+}
+int spa3d_op_sum3(const float* a, const float* b, const float* c3, float* out, int32_t n, void* stream) {
+  if (!out || (!a && !b && !c3) || n < 0) return SPA3D_ERR_ARG;
+  if (n == 0) return SPA3D_OK;   // (k_sum3 would launch an empty grid)
+  OpCtx c(stream, nullptr, 0);
+  k_sum3(&c, a, b, c3, out, n);
+  return c.status();
+}
+int spa3d_op_discretize(const float* lat, const float* noise, int32_t discretize, float* out, float* clipmask, int64_t n, void* stream) {
+  if (!lat || !out || n < 0 || (discretize != 0 && discretize != 1) || (discretize && !noise)) return SPA3D_ERR_ARG;
+  OpCtx c(stream, nullptr, 0);
+  k_discretize(&c, lat, noise, discretize, out, clipmask, n);
+  return c.status();
+}
+#endif
 
 }  // extern "C"

@@ -692,6 +692,44 @@ int spa3d_op_bcast_grad(const void* dsrc, int64_t per, int64_t B, int64_t bstrid
 int spa3d_op_vis_mean_pool(const void* tok, const float* vis, int64_t nseq, int32_t T, int32_t d, void* out, int32_t dtype, void* stream);
 int spa3d_op_vis_mean_pool_bwd(const void* dout, const float* vis, int64_t nseq, int32_t T, int32_t d, void* dtok, int32_t dtype, void* stream);
 
+/* ---- The first mile of the model on its own (tests/test_gpu_embed.py): the embeddings, row maps, readout rows, key masks and weight shadows of
+ * csrc/embed.hip and the latent quantiser of csrc/loss.hip.  Rules as for the row plumbing: `dtype` in {SPA3D_F32, SPA3D_BF16, SPA3D_F16} is the storage
+ * type of every `void*` tensor; an empty input returns SPA3D_OK and launches nothing; a NULL required pointer, a negative count or a shape outside what
+ * is stated returns SPA3D_ERR_ARG and launches nothing.  Everywhere 1 <= nf <= 64 (the scale table of the kernels holds 64 entries), and a scale
+ * that divides is neither 0 nor NaN. ---- */
+
+/* spa3d_op_sin_embed with the division the model applies first: out[rows, C*2*nf] = SinusoidalEmbedding(x / prescale).  1 <= C <= 65536. */
+int spa3d_op_sin_embed_scaled(const float* x, int64_t rows, int32_t C, int32_t nf, float prescale, void* out, int32_t dtype, void* stream);
+/* Track tokens (track_autoencoder_3d.py:126-134): out[nrows, (NC+1)*2*nf] = SinusoidalEmbedding([tracks[r][0..NC), fl32(r % T) / fl32(T)] / prescale),
+ * tracks f32 [nrows, NC], NC in {2, 3}, T >= 1.  16 bytes per thread when nf is a multiple of 16 bytes and out is 16-byte aligned, else element by
+ * element (out need only be element-aligned); both give the same bits. */
+int spa3d_op_embed_tokens(const float* tracks, int64_t nrows, int32_t T, int32_t NC, int32_t nf, float prescale, void* out, int32_t dtype, void* stream);
+/* Decoder context (track_autoencoder_3d.py:209-233, 265-272): qp f32 [nq, NC+1] = (t, coordinates); qframe[q] = round-half-even(t);
+ * feat f32 [nq, NC*2*nf + 1] = [SinusoidalEmbedding(coordinates / track_scale) | floor(fl32(qframe) / time_scale)].  NC in {2, 3}. */
+int spa3d_op_query_embed(const float* qp, int64_t nq, int32_t NC, int32_t nf, float track_scale, float time_scale, float* feat, int32_t* qframe, void* stream);
+/* Row maps of the one-pass embedding: row j of the token buffer is dense token q = row_src[j] (row_src NULL: j) = (seq, s) of nseq sequences of
+ * S = T + 1 tokens.  s >= 1: arow[j] = seq * T + s - 1 (its input row), crow[j] = j, tok row j untouched.  s == 0: arow[j] = seq * T, crow[j] = -1,
+ * tok[j][0..d) = readout f32 [d] rounded once.  rows < 2^31, T >= 1, S == T + 1, d >= 1. */
+int spa3d_op_embed_maps(const int32_t* row_src, int64_t rows, int32_t S, int32_t T, int32_t* arow, int32_t* crow, void* tok, const float* readout, int32_t d,
+                        int32_t dtype, void* stream);
+/* tok [nseq, S, d]: row 0 of every sequence = readout f32 [d] rounded once (track_autoencoder_3d.py:161-165); the other rows untouched.  S, d >= 1. */
+int spa3d_op_set_readout_rows(void* tok, const float* readout, int64_t nseq, int32_t S, int32_t d, int32_t dtype, void* stream);
+/* Key masks: visible f32 [nseq, T], boundary int32 [nseq / N] (sequence s belongs to sample s / N); key t is kept when visible != 0 (-0.0 dropped,
+ * NaN kept) and t < boundary.  with_readout = 1: km f32 [nseq, T + 1], key 0 (the readout token) always 1; with_readout = 0: km f32 [nseq, T], the 2-D
+ * model's form.  N >= 1 divides nseq, T >= 1. */
+int spa3d_op_keymask(const float* visible, const int32_t* boundary, int64_t nseq, int32_t N, int32_t T, int32_t with_readout, float* km, void* stream);
+/* out[i] = fl32(fl32(a[i] + b[i]) + c[i]), i < n; a NULL operand counts as 0.f, at least one is given (the fused embedding bias). */
+int spa3d_op_sum3(const float* a, const float* b, const float* c, float* out, int32_t n, void* stream);
+/* Weight shadows: src f32 [rows, cols] with row stride src_ld -> dn [rows, cols] with row stride ldn and dt [cols, rows] with row stride ldt (the
+ * transpose), both rounded once to `dtype`; either may be NULL, not both.  src_ld >= cols, ldn >= cols, ldt >= rows, rows <= 65535 * 32. */
+int spa3d_op_pack(const float* src, int64_t src_ld, int32_t rows, int32_t cols, void* dn, int64_t ldn, void* dt, int64_t ldt, int32_t dtype, void* stream);
+/* dst [cols, rows] = src [rows, cols] transposed, both dense, a copy.  rows <= 65535 * 32. */
+int spa3d_op_transpose(const void* src, int32_t rows, int32_t cols, void* dst, int32_t dtype, void* stream);
+/* Latent clip / quantise / straight-through (track_autoencoder_3d.py:251-260), f32 [n]: l = clip(lat, -1, 1); discretize = 1:
+ * q = round-half-even(l * 128) / 128 + noise / 128 - 1 / 256 and out = l - (l - q), else out = l.  clipmask (may be NULL) = 1 where -1 <= lat <= 1,
+ * else 0.  A NaN latent is a NaN in out and in clipmask.  noise may be NULL when discretize = 0. */
+int spa3d_op_discretize(const float* lat, const float* noise, int32_t discretize, float* out, float* clipmask, int64_t n, void* stream);
+
 /* ---- feature producers that build the hot path's inputs.  Host pointers: `intrinsics` only. ----
  * Float32 arithmetic in the reference's operation order: bit-identical to the reference functions under NumPy >= 2. */
 
