@@ -91,135 +91,62 @@ int op_linear_bwd(OpCtx& c, const T* A, const T* B, const T* dC, T* dA, float* d
 }  // namespace
 }  // namespace SPA_NS
 
-// The entry points below are compiled twice: as declared in include/spa3d.h (this build's 16-bit type is bf16) and, with
-// -DSPA_F16=1, under a hidden `_f16` suffix with fp16 as the 16-bit type; the public functions forward dtype == SPA3D_F16 there.
-extern "C" {
-#pragma GCC visibility push(hidden)
-int spa3d_op_sin_embed_f16(const float* x, int64_t rows, int32_t C, int32_t nf, void* out, int32_t dtype, void* stream);
-int spa3d_op_linear_f16(const void* A, const void* B, const float* bias, const void* residual, void* C, int64_t M, int32_t N, int32_t K,
-                        int32_t act, int32_t dtype, int32_t impl, void* ws, int64_t ws_bytes, void* stream);
-int spa3d_op_linear_bwd_f16(const void* A, const void* B, const void* dC, void* dA, float* dB, float* dbias, int64_t M, int32_t N, int32_t K,
-                            int32_t dtype, int32_t impl, void* ws, int64_t ws_bytes, void* stream);
-int spa3d_op_mlp_fused_f16(const void* na, const void* a, const void* w_in, const float* b_in, const void* w_out, const float* b_out, void* y,
-                           void* h, void* hpre, int64_t M, int32_t d, int32_t mlp, int32_t dtype, void* ws, int64_t ws_bytes, void* stream);
-int spa3d_op_qkv_attention_f16(const void* nq, int64_t ldn, const void* wq, const void* wk, const void* wv, const float* scale_q, const float* scale_k,
-                               const float* keymask, const int32_t* seq_off, int64_t nseq, int32_t S, int32_t H, void* qkv, void* o, float* lse,
-                               int32_t dtype, void* ws, int64_t ws_bytes, void* stream);
-int spa3d_op_layernorm_f16(const void* x, const float* scale, void* y, float* stats, int64_t rows, int32_t d, int32_t dtype, void* stream);
-int spa3d_op_layernorm_bwd_f16(const void* x, const float* scale, const float* stats, const void* dy, void* dx, float* dscale, int64_t rows,
-                               int32_t d, int32_t dtype, void* stream);
-int spa3d_op_attention_f16(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* scale_q,
-                           const float* scale_k, const float* keymask, int64_t nseq, int32_t Sq, int32_t Sk, int32_t H, int32_t Dh, void* o,
-                           float* lse, int32_t dtype, int32_t impl, void* ws, int64_t ws_bytes, void* stream);
-int spa3d_op_attention_holdout_f16(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* scale_q,
-                                   const float* scale_k, int64_t nseq, int32_t Sq, int32_t Nk, int32_t H, int32_t Dh, const int32_t* holes, void* o,
-                                   float* lse, int32_t dtype, int32_t impl, void* ws, int64_t ws_bytes, void* stream);
-int spa3d_op_attention_bwd_f16(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* scale_q,
-                               const float* scale_k, const float* keymask, int64_t nseq, int32_t Sq, int32_t Sk, int32_t H, int32_t Dh,
-                               const void* o, const float* lse, const void* d_o, void* dq, void* dk, void* dv, float* dscale_q,
-                               float* dscale_k, int32_t dtype, int32_t impl, void* ws, int64_t ws_bytes, void* stream);
-int spa3d_op_attention_q1_f16(const void* q0, int64_t ldq0, const void* k, const void* v, int64_t ldk, int64_t ldv, const float* scale_q,
-                              const float* scale_k, const float* keymask, const int32_t* seq_off, int64_t nseq, int32_t S, int32_t H, int32_t Dh,
-                              void* o0, float* p0, int32_t dtype, void* stream);
-int spa3d_op_attention_q1_bwd_f16(const void* q0, int64_t ldq0, const void* k, const void* v, int64_t ldk, int64_t ldv, const float* scale_q,
-                                  const float* scale_k, const float* keymask, const int32_t* seq_off, int64_t nseq, int32_t S, int32_t H, int32_t Dh,
-                                  const float* p0, const void* d_o0, void* dq0, void* dk, void* dv, float* dscale_q, float* dscale_k, int32_t dtype,
-                                  void* stream);
-int spa3d_op_rank_linear_f16(const void* x, const void* w, const float* bias, void* out, int64_t M, int32_t N, int32_t K, int64_t ldo, int32_t rgroup,
-                             int32_t rskip, int32_t dtype, void* stream);
-int spa3d_op_rank_linear_bwd_f16(const void* x, const void* dy, int64_t M, int32_t N, int32_t K, int64_t ldy, int32_t rgroup, int32_t rskip, float* gw,
-                                 float* gb, int32_t dtype, void* stream);
-int spa3d_op_colsum_f16(const void* x, int64_t rows, int32_t n, int64_t ld, int32_t rgroup, int32_t rskip, float* out, int32_t dtype, void* stream);
-int spa3d_op_rows_f16(int32_t mode, const void* src, const int32_t* idx, int64_t stride_rows, void* dst, int64_t n, int32_t d, int32_t dtype, void* stream);
-int spa3d_op_share_rows_f16(int32_t which, const void* a, const void* b, const int32_t* slot, const int32_t* slot_b, const int32_t* slot_f,
-                            const int32_t* slot_q0, int64_t nslot, int64_t B, int32_t Q, int32_t L, int32_t Cl, int32_t d, void* out, int32_t dtype, void* stream);
-int spa3d_op_assemble_readout_f16(const void* qtok, const void* lat, const int32_t* qframe, int64_t B, int32_t Q, int32_t L, int32_t Cl, int32_t D, void* seq,
-                                  int32_t dtype, void* stream);
-int spa3d_op_assemble_readout_bwd_f16(const void* dseq, const int32_t* qframe, int64_t B, int32_t Q, int32_t L, int32_t Cl, int32_t D, void* dqtok,
-                                      float* dlat, int32_t accumulate, int32_t dtype, void* stream);
-int spa3d_op_broadcast_rows_f16(const float* src, int32_t rows, int32_t d, void* dst, int64_t B, int32_t dtype, void* stream);
-int spa3d_op_bcast_grad_f16(const void* dsrc, int64_t per, int64_t B, int64_t bstride, float* dparam, int32_t dtype, void* stream);
-int spa3d_op_vis_mean_pool_f16(const void* tok, const float* vis, int64_t nseq, int32_t T, int32_t d, void* out, int32_t dtype, void* stream);
-int spa3d_op_vis_mean_pool_bwd_f16(const void* dout, const float* vis, int64_t nseq, int32_t T, int32_t d, void* dtok, int32_t dtype, void* stream);
-int spa3d_op_sin_embed_scaled_f16(const float* x, int64_t rows, int32_t C, int32_t nf, float prescale, void* out, int32_t dtype, void* stream);
-int spa3d_op_embed_tokens_f16(const float* tracks, int64_t nrows, int32_t T, int32_t NC, int32_t nf, float prescale, void* out, int32_t dtype, void* stream);
-int spa3d_op_embed_maps_f16(const int32_t* row_src, int64_t rows, int32_t S, int32_t T, int32_t* arow, int32_t* crow, void* tok, const float* readout, int32_t d,
-                            int32_t dtype, void* stream);
-int spa3d_op_set_readout_rows_f16(void* tok, const float* readout, int64_t nseq, int32_t S, int32_t d, int32_t dtype, void* stream);
-int spa3d_op_pack_f16(const float* src, int64_t src_ld, int32_t rows, int32_t cols, void* dn, int64_t ldn, void* dt, int64_t ldt, int32_t dtype, void* stream);
-int spa3d_op_transpose_f16(const void* src, int32_t rows, int32_t cols, void* dst, int32_t dtype, void* stream);
-#pragma GCC visibility pop
-}
+// An entry point with a `dtype` argument is compiled twice: as declared in include/spa3d.h (this build's 16-bit type is bf16) and, with -DSPA_F16=1,
+// under a hidden `_f16` suffix with fp16 as the 16-bit type; the public function forwards dtype == SPA3D_F16 there (FWD16, its first statement).
+// SPA3D_OP(name)(parameters) { ... } defines this build's one of the two.  The twin's type is the header's declaration of `name`, and the names have C
+// linkage, so a parameter list that differs from the header does not compile in either build.
+#define SPA3D_TWIN(name) __attribute__((visibility("hidden"))) decltype(name) name##_f16
 #if SPA_F16
-#define spa3d_op_sin_embed spa3d_op_sin_embed_f16
-#define spa3d_op_linear spa3d_op_linear_f16
-#define spa3d_op_linear_bwd spa3d_op_linear_bwd_f16
-#define spa3d_op_layernorm spa3d_op_layernorm_f16
-#define spa3d_op_mlp_fused spa3d_op_mlp_fused_f16
-#define spa3d_op_qkv_attention spa3d_op_qkv_attention_f16
-#define spa3d_op_layernorm_bwd spa3d_op_layernorm_bwd_f16
-#define spa3d_op_attention spa3d_op_attention_f16
-#define spa3d_op_attention_bwd spa3d_op_attention_bwd_f16
-#define spa3d_op_attention_holdout spa3d_op_attention_holdout_f16
-#define spa3d_op_attention_q1 spa3d_op_attention_q1_f16
-#define spa3d_op_attention_q1_bwd spa3d_op_attention_q1_bwd_f16
-#define spa3d_op_rank_linear spa3d_op_rank_linear_f16
-#define spa3d_op_rank_linear_bwd spa3d_op_rank_linear_bwd_f16
-#define spa3d_op_colsum spa3d_op_colsum_f16
-#define spa3d_op_rows spa3d_op_rows_f16
-#define spa3d_op_share_rows spa3d_op_share_rows_f16
-#define spa3d_op_assemble_readout spa3d_op_assemble_readout_f16
-#define spa3d_op_assemble_readout_bwd spa3d_op_assemble_readout_bwd_f16
-#define spa3d_op_broadcast_rows spa3d_op_broadcast_rows_f16
-#define spa3d_op_bcast_grad spa3d_op_bcast_grad_f16
-#define spa3d_op_vis_mean_pool spa3d_op_vis_mean_pool_f16
-#define spa3d_op_vis_mean_pool_bwd spa3d_op_vis_mean_pool_bwd_f16
-#define spa3d_op_sin_embed_scaled spa3d_op_sin_embed_scaled_f16
-#define spa3d_op_embed_tokens spa3d_op_embed_tokens_f16
-#define spa3d_op_embed_maps spa3d_op_embed_maps_f16
-#define spa3d_op_set_readout_rows spa3d_op_set_readout_rows_f16
-#define spa3d_op_pack spa3d_op_pack_f16
-#define spa3d_op_transpose spa3d_op_transpose_f16
-#define FWD16(call)
+#define SPA3D_OP(name) SPA3D_TWIN(name); int name##_f16
+#define FWD16(name, ...)
+#define OP_DT16 SPA3D_F16
 #else
-#define FWD16(call) if (dtype == SPA3D_F16) return call;
+#define SPA3D_OP(name) SPA3D_TWIN(name); int name
+#define FWD16(name, ...) if (dtype == SPA3D_F16) return name##_f16(__VA_ARGS__);
+#define OP_DT16 SPA3D_BF16
 #endif
+#define OP_DTYPE_OK(dtype) ((dtype) == SPA3D_F32 || (dtype) == OP_DT16)
+// `body` with T the storage type of `dtype`: float for SPA3D_F32, this build's 16-bit type for every other value
+#define OP_BY_DTYPE(dtype, body)                                            \
+  do {                                                                      \
+    if ((dtype) == SPA3D_F32) { using T = float; body; }                    \
+    else { using T = bf16_t; body; }                                        \
+  } while (0)
+static bool op_al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+static int op_nv(int32_t dtype) { return dtype == SPA3D_F32 ? 4 : 8; }   // elements per 16 bytes (VecOf<T>::N)
 
 extern "C" {
 
-int spa3d_op_sin_embed(const float* x, int64_t rows, int32_t C, int32_t nf, void* out, int32_t dtype, void* stream) {
-  FWD16(spa3d_op_sin_embed_f16(x, rows, C, nf, out, dtype, stream))
+SPA3D_OP(spa3d_op_sin_embed)(const float* x, int64_t rows, int32_t C, int32_t nf, void* out, int32_t dtype, void* stream) {
+  FWD16(spa3d_op_sin_embed, x, rows, C, nf, out, dtype, stream)
   if (!x || !out || nf <= 0 || nf > 64) return SPA3D_ERR_ARG;
   OpCtx c(stream, nullptr, 0);
-  if (dtype == SPA3D_F32) k_sin_embed<float>(&c, x, rows, C, nf, 1.0f, (float*)out);
-  else k_sin_embed<bf16_t>(&c, x, rows, C, nf, 1.0f, (bf16_t*)out);
+  OP_BY_DTYPE(dtype, k_sin_embed<T>(&c, x, rows, C, nf, 1.0f, (T*)out));
   return c.status();
 }
 
-int spa3d_op_linear(const void* A, const void* B, const float* bias, const void* residual, void* C, int64_t M, int32_t N, int32_t K,
-                    int32_t act, int32_t dtype, int32_t impl, void* ws, int64_t ws_bytes, void* stream) {
-  FWD16(spa3d_op_linear_f16(A, B, bias, residual, C, M, N, K, act, dtype, impl, ws, ws_bytes, stream))
+SPA3D_OP(spa3d_op_linear)(const void* A, const void* B, const float* bias, const void* residual, void* C, int64_t M, int32_t N, int32_t K,
+                          int32_t act, int32_t dtype, int32_t impl, void* ws, int64_t ws_bytes, void* stream) {
+  FWD16(spa3d_op_linear, A, B, bias, residual, C, M, N, K, act, dtype, impl, ws, ws_bytes, stream)
   if (!A || !B || !C) return SPA3D_ERR_ARG;
   OpCtx c(stream, ws, ws_bytes);
-  if (dtype == SPA3D_F32) return op_linear<float>(c, (const float*)A, (const float*)B, bias, (const float*)residual, (float*)C, M, N, K, act, impl);
-  return op_linear<bf16_t>(c, (const bf16_t*)A, (const bf16_t*)B, bias, (const bf16_t*)residual, (bf16_t*)C, M, N, K, act, impl);
+  OP_BY_DTYPE(dtype, return op_linear<T>(c, (const T*)A, (const T*)B, bias, (const T*)residual, (T*)C, M, N, K, act, impl));
 }
-int spa3d_op_linear_bwd(const void* A, const void* B, const void* dC, void* dA, float* dB, float* dbias, int64_t M, int32_t N, int32_t K,
-                        int32_t dtype, int32_t impl, void* ws, int64_t ws_bytes, void* stream) {
-  FWD16(spa3d_op_linear_bwd_f16(A, B, dC, dA, dB, dbias, M, N, K, dtype, impl, ws, ws_bytes, stream))
+SPA3D_OP(spa3d_op_linear_bwd)(const void* A, const void* B, const void* dC, void* dA, float* dB, float* dbias, int64_t M, int32_t N, int32_t K,
+                              int32_t dtype, int32_t impl, void* ws, int64_t ws_bytes, void* stream) {
+  FWD16(spa3d_op_linear_bwd, A, B, dC, dA, dB, dbias, M, N, K, dtype, impl, ws, ws_bytes, stream)
   if (!A || !B || !dC) return SPA3D_ERR_ARG;
   OpCtx c(stream, ws, ws_bytes);
-  if (dtype == SPA3D_F32) return op_linear_bwd<float>(c, (const float*)A, (const float*)B, (const float*)dC, (float*)dA, dB, dbias, M, N, K, impl);
-  return op_linear_bwd<bf16_t>(c, (const bf16_t*)A, (const bf16_t*)B, (const bf16_t*)dC, (bf16_t*)dA, dB, dbias, M, N, K, impl);
+  OP_BY_DTYPE(dtype, return op_linear_bwd<T>(c, (const T*)A, (const T*)B, (const T*)dC, (T*)dA, dB, dbias, M, N, K, impl));
 }
 
-int spa3d_op_mlp_fused(const void* na, const void* a, const void* w_in, const float* b_in, const void* w_out, const float* b_out, void* y,
-                       void* h, void* hpre, int64_t M, int32_t d, int32_t mlp, int32_t dtype, void* ws, int64_t ws_bytes, void* stream) {
-  FWD16(spa3d_op_mlp_fused_f16(na, a, w_in, b_in, w_out, b_out, y, h, hpre, M, d, mlp, dtype, ws, ws_bytes, stream))
+SPA3D_OP(spa3d_op_mlp_fused)(const void* na, const void* a, const void* w_in, const float* b_in, const void* w_out, const float* b_out, void* y,
+                             void* h, void* hpre, int64_t M, int32_t d, int32_t mlp, int32_t dtype, void* ws, int64_t ws_bytes, void* stream) {
+  FWD16(spa3d_op_mlp_fused, na, a, w_in, b_in, w_out, b_out, y, h, hpre, M, d, mlp, dtype, ws, ws_bytes, stream)
   if (!na || !a || !w_in || !b_in || !w_out || !b_out || !y || !h || !hpre || dtype == SPA3D_F32) return SPA3D_ERR_ARG;
   if (d != 384 || mlp != 1536 || M < 1) return SPA3D_ERR_ARG;   // shape first: a wrong shape is an argument error whatever the workspace
   for (const void* p : {na, a, (const void*)y, (const void*)h, (const void*)hpre, w_in, w_out})
-    if (((uintptr_t)p) & 15) return SPA3D_ERR_ARG;               // 16-byte vector / LDS-DMA accesses on every operand
+    if (!op_al16(p)) return SPA3D_ERR_ARG;                       // 16-byte vector / LDS-DMA accesses on every operand
   OpCtx c(stream, ws, ws_bytes);
   bf16_t* wpk = c.alloc<bf16_t>(mlp_fused_pack_elems());
   if (c.ar.overflow) return SPA3D_ERR_WORKSPACE;
@@ -229,10 +156,10 @@ int spa3d_op_mlp_fused(const void* na, const void* a, const void* w_in, const fl
   return c.status();
 }
 
-int spa3d_op_qkv_attention(const void* nq, int64_t ldn, const void* wq, const void* wk, const void* wv, const float* scale_q, const float* scale_k,
-                           const float* keymask, const int32_t* seq_off, int64_t nseq, int32_t S, int32_t H, void* qkv, void* o, float* lse,
-                           int32_t dtype, void* ws, int64_t ws_bytes, void* stream) {
-  FWD16(spa3d_op_qkv_attention_f16(nq, ldn, wq, wk, wv, scale_q, scale_k, keymask, seq_off, nseq, S, H, qkv, o, lse, dtype, ws, ws_bytes, stream))
+SPA3D_OP(spa3d_op_qkv_attention)(const void* nq, int64_t ldn, const void* wq, const void* wk, const void* wv, const float* scale_q, const float* scale_k,
+                                 const float* keymask, const int32_t* seq_off, int64_t nseq, int32_t S, int32_t H, void* qkv, void* o, float* lse,
+                                 int32_t dtype, void* ws, int64_t ws_bytes, void* stream) {
+  FWD16(spa3d_op_qkv_attention, nq, ldn, wq, wk, wv, scale_q, scale_k, keymask, seq_off, nseq, S, H, qkv, o, lse, dtype, ws, ws_bytes, stream)
   if (!nq || !wq || !wk || !wv || !scale_q || !scale_k || !qkv || !o || dtype == SPA3D_F32 || H < 1 || H > 64) return SPA3D_ERR_ARG;
   OpCtx c(stream, ws, ws_bytes);
   bf16_t* wpk = c.alloc<bf16_t>(qkv_attn_pack_elems(H));
@@ -242,43 +169,37 @@ int spa3d_op_qkv_attention(const void* nq, int64_t ldn, const void* wq, const vo
   return c.status();
 }
 
-int spa3d_op_layernorm(const void* x, const float* scale, void* y, float* stats, int64_t rows, int32_t d, int32_t dtype, void* stream) {
-  FWD16(spa3d_op_layernorm_f16(x, scale, y, stats, rows, d, dtype, stream))
+SPA3D_OP(spa3d_op_layernorm)(const void* x, const float* scale, void* y, float* stats, int64_t rows, int32_t d, int32_t dtype, void* stream) {
+  FWD16(spa3d_op_layernorm, x, scale, y, stats, rows, d, dtype, stream)
   if (!x || !scale || !y || d <= 0 || d > 2048) return SPA3D_ERR_ARG;
   OpCtx c(stream, nullptr, 0);
-  if (dtype == SPA3D_F32) k_layernorm<float>(&c, (const float*)x, scale, (float*)y, stats, rows, d);
-  else k_layernorm<bf16_t>(&c, (const bf16_t*)x, scale, (bf16_t*)y, stats, rows, d);
+  OP_BY_DTYPE(dtype, k_layernorm<T>(&c, (const T*)x, scale, (T*)y, stats, rows, d));
   return c.status();
 }
-int spa3d_op_layernorm_bwd(const void* x, const float* scale, const float* stats, const void* dy, void* dx, float* dscale, int64_t rows,
-                           int32_t d, int32_t dtype, void* stream) {
-  FWD16(spa3d_op_layernorm_bwd_f16(x, scale, stats, dy, dx, dscale, rows, d, dtype, stream))
+SPA3D_OP(spa3d_op_layernorm_bwd)(const void* x, const float* scale, const float* stats, const void* dy, void* dx, float* dscale, int64_t rows,
+                                 int32_t d, int32_t dtype, void* stream) {
+  FWD16(spa3d_op_layernorm_bwd, x, scale, stats, dy, dx, dscale, rows, d, dtype, stream)
   if (!x || !scale || !stats || !dy || !dx || !dscale || d <= 0 || d > 2048) return SPA3D_ERR_ARG;
   OpCtx c(stream, nullptr, 0);
-  if (dtype == SPA3D_F32) k_layernorm_bwd<float>(&c, (const float*)x, scale, stats, (const float*)dy, (float*)dx, dscale, rows, d, nullptr);
-  else k_layernorm_bwd<bf16_t>(&c, (const bf16_t*)x, scale, stats, (const bf16_t*)dy, (bf16_t*)dx, dscale, rows, d, nullptr);
+  OP_BY_DTYPE(dtype, k_layernorm_bwd<T>(&c, (const T*)x, scale, stats, (const T*)dy, (T*)dx, dscale, rows, d, nullptr));
   return c.status();
 }
 
-int spa3d_op_attention(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* scale_q,
-                       const float* scale_k, const float* keymask, int64_t nseq, int32_t Sq, int32_t Sk, int32_t H, int32_t Dh, void* o,
-                       float* lse, int32_t dtype, int32_t impl, void* ws, int64_t ws_bytes, void* stream) {
-  FWD16(spa3d_op_attention_f16(q, k, v, ldq, ldk, ldv, scale_q, scale_k, keymask, nseq, Sq, Sk, H, Dh, o, lse, dtype, impl, ws, ws_bytes, stream))
+SPA3D_OP(spa3d_op_attention)(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* scale_q,
+                             const float* scale_k, const float* keymask, int64_t nseq, int32_t Sq, int32_t Sk, int32_t H, int32_t Dh, void* o,
+                             float* lse, int32_t dtype, int32_t impl, void* ws, int64_t ws_bytes, void* stream) {
+  FWD16(spa3d_op_attention, q, k, v, ldq, ldk, ldv, scale_q, scale_k, keymask, nseq, Sq, Sk, H, Dh, o, lse, dtype, impl, ws, ws_bytes, stream)
   if (!q || !k || !v || !o || !scale_q || !scale_k || Dh > 128) return SPA3D_ERR_ARG;
   OpCtx c(stream, ws, ws_bytes);
   apply_attn_impl(&c, impl);
-  if (dtype == SPA3D_F32)
-    attention_fwd<float>(&c, (const float*)q, (const float*)k, (const float*)v, ldq, ldk, ldv, scale_q, scale_k, keymask, nseq, Sq, Sk, H, Dh,
-                         (float*)o, lse, c.attn_impl);
-  else
-    attention_fwd<bf16_t>(&c, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv, scale_q, scale_k, keymask, nseq, Sq, Sk, H,
-                          Dh, (bf16_t*)o, lse, c.attn_impl);
+  OP_BY_DTYPE(dtype, attention_fwd<T>(&c, (const T*)q, (const T*)k, (const T*)v, ldq, ldk, ldv, scale_q, scale_k, keymask, nseq, Sq, Sk, H, Dh, (T*)o, lse,
+                                      c.attn_impl));
   return c.status();
 }
-int spa3d_op_attention_holdout(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* scale_q,
-                               const float* scale_k, int64_t nseq, int32_t Sq, int32_t Nk, int32_t H, int32_t Dh, const int32_t* holes, void* o,
-                               float* lse, int32_t dtype, int32_t impl, void* ws, int64_t ws_bytes, void* stream) {
-  FWD16(spa3d_op_attention_holdout_f16(q, k, v, ldq, ldk, ldv, scale_q, scale_k, nseq, Sq, Nk, H, Dh, holes, o, lse, dtype, impl, ws, ws_bytes, stream))
+SPA3D_OP(spa3d_op_attention_holdout)(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* scale_q,
+                                     const float* scale_k, int64_t nseq, int32_t Sq, int32_t Nk, int32_t H, int32_t Dh, const int32_t* holes, void* o,
+                                     float* lse, int32_t dtype, int32_t impl, void* ws, int64_t ws_bytes, void* stream) {
+  FWD16(spa3d_op_attention_holdout, q, k, v, ldq, ldk, ldv, scale_q, scale_k, nseq, Sq, Nk, H, Dh, holes, o, lse, dtype, impl, ws, ws_bytes, stream)
   if (!q || !k || !v || !o || !scale_q || !scale_k || !holes || Dh < 1 || Dh > 128 || nseq < 1 || nseq > (1 << 20) || Sq < 1 || Nk < 1 || H < 1) return SPA3D_ERR_ARG;
   for (int64_t i = 0; i < nseq; ++i) {  // a hole outside [0, Nk], lo > hi, a sequence left without a key
     const int64_t lo = holes[2 * i], hi = holes[2 * i + 1];
@@ -289,30 +210,21 @@ int spa3d_op_attention_holdout(const void* q, const void* k, const void* v, int6
   int32_t* hd = c.alloc<int32_t>(2 * nseq);
   if (c.ar.overflow) return SPA3D_ERR_WORKSPACE;
   k_set_i32(&c, hd, holes, 2 * nseq);
-  if (dtype == SPA3D_F32)
-    attention_holdout_fwd<float>(&c, (const float*)q, (const float*)k, (const float*)v, ldq, ldk, ldv, scale_q, scale_k, nseq, Sq, Nk, holes, hd, H, Dh,
-                                 (float*)o, lse, c.attn_impl);
-  else
-    attention_holdout_fwd<bf16_t>(&c, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv, scale_q, scale_k, nseq, Sq, Nk, holes, hd, H,
-                                  Dh, (bf16_t*)o, lse, c.attn_impl);
+  OP_BY_DTYPE(dtype, attention_holdout_fwd<T>(&c, (const T*)q, (const T*)k, (const T*)v, ldq, ldk, ldv, scale_q, scale_k, nseq, Sq, Nk, holes, hd, H, Dh,
+                                              (T*)o, lse, c.attn_impl));
   return c.status();
 }
-int spa3d_op_attention_bwd(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* scale_q,
-                           const float* scale_k, const float* keymask, int64_t nseq, int32_t Sq, int32_t Sk, int32_t H, int32_t Dh,
-                           const void* o, const float* lse, const void* d_o, void* dq, void* dk, void* dv, float* dscale_q,
-                           float* dscale_k, int32_t dtype, int32_t impl,
-                           void* ws, int64_t ws_bytes, void* stream) {
-  FWD16(spa3d_op_attention_bwd_f16(q, k, v, ldq, ldk, ldv, scale_q, scale_k, keymask, nseq, Sq, Sk, H, Dh, o, lse, d_o, dq, dk, dv, dscale_q,
-                                   dscale_k, dtype, impl, ws, ws_bytes, stream))
+SPA3D_OP(spa3d_op_attention_bwd)(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* scale_q,
+                                 const float* scale_k, const float* keymask, int64_t nseq, int32_t Sq, int32_t Sk, int32_t H, int32_t Dh,
+                                 const void* o, const float* lse, const void* d_o, void* dq, void* dk, void* dv, float* dscale_q,
+                                 float* dscale_k, int32_t dtype, int32_t impl, void* ws, int64_t ws_bytes, void* stream) {
+  FWD16(spa3d_op_attention_bwd, q, k, v, ldq, ldk, ldv, scale_q, scale_k, keymask, nseq, Sq, Sk, H, Dh, o, lse, d_o, dq, dk, dv, dscale_q, dscale_k, dtype,
+        impl, ws, ws_bytes, stream)
   if (!q || !k || !v || !d_o || !dq || !dk || !dv || !dscale_q || !dscale_k || Dh > 128) return SPA3D_ERR_ARG;
   OpCtx c(stream, ws, ws_bytes);
   apply_attn_impl(&c, impl);
-  if (dtype == SPA3D_F32)
-    attention_bwd<float>(&c, (const float*)q, (const float*)k, (const float*)v, ldq, ldk, ldv, scale_q, scale_k, keymask, nseq, Sq, Sk, H, Dh,
-                         (const float*)o, lse, (const float*)d_o, (float*)dq, (float*)dk, (float*)dv, dscale_q, dscale_k, c.attn_impl);
-  else
-    attention_bwd<bf16_t>(&c, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv, scale_q, scale_k, keymask, nseq, Sq, Sk, H,
-                          Dh, (const bf16_t*)o, lse, (const bf16_t*)d_o, (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, dscale_q, dscale_k, c.attn_impl);
+  OP_BY_DTYPE(dtype, attention_bwd<T>(&c, (const T*)q, (const T*)k, (const T*)v, ldq, ldk, ldv, scale_q, scale_k, keymask, nseq, Sq, Sk, H, Dh, (const T*)o, lse,
+                                      (const T*)d_o, (T*)dq, (T*)dk, (T*)dv, dscale_q, dscale_k, c.attn_impl));
   return c.status();
 }
 
@@ -321,50 +233,41 @@ static bool q1_shape_ok(int64_t nseq, int32_t S, int32_t H, int32_t Dh) {
   const bool width = Dh == 8 || Dh == 16 || Dh == 32 || Dh == 64 || Dh == 96 || Dh == 128;   // the instantiations of csrc/attn_q1.hip
   return width && S >= 1 && S <= 320 && H >= 1 && nseq >= 0;
 }
-int spa3d_op_attention_q1(const void* q0, int64_t ldq0, const void* k, const void* v, int64_t ldk, int64_t ldv, const float* scale_q,
-                          const float* scale_k, const float* keymask, const int32_t* seq_off, int64_t nseq, int32_t S, int32_t H, int32_t Dh,
-                          void* o0, float* p0, int32_t dtype, void* stream) {
-  FWD16(spa3d_op_attention_q1_f16(q0, ldq0, k, v, ldk, ldv, scale_q, scale_k, keymask, seq_off, nseq, S, H, Dh, o0, p0, dtype, stream))
+SPA3D_OP(spa3d_op_attention_q1)(const void* q0, int64_t ldq0, const void* k, const void* v, int64_t ldk, int64_t ldv, const float* scale_q,
+                                const float* scale_k, const float* keymask, const int32_t* seq_off, int64_t nseq, int32_t S, int32_t H, int32_t Dh,
+                                void* o0, float* p0, int32_t dtype, void* stream) {
+  FWD16(spa3d_op_attention_q1, q0, ldq0, k, v, ldk, ldv, scale_q, scale_k, keymask, seq_off, nseq, S, H, Dh, o0, p0, dtype, stream)
   if (!q0 || !k || !v || !scale_q || !scale_k || !o0 || !p0 || !q1_shape_ok(nseq, S, H, Dh)) return SPA3D_ERR_ARG;
   OpCtx c(stream, nullptr, 0);
-  if (dtype == SPA3D_F32)
-    k_attn_q1_fwd<float>(&c, (const float*)q0, ldq0, (const float*)k, (const float*)v, ldk, ldv, scale_q, scale_k, keymask, nseq, S, H, Dh, (float*)o0, p0,
-                         seq_off);
-  else
-    k_attn_q1_fwd<bf16_t>(&c, (const bf16_t*)q0, ldq0, (const bf16_t*)k, (const bf16_t*)v, ldk, ldv, scale_q, scale_k, keymask, nseq, S, H, Dh, (bf16_t*)o0,
-                          p0, seq_off);
+  OP_BY_DTYPE(dtype, k_attn_q1_fwd<T>(&c, (const T*)q0, ldq0, (const T*)k, (const T*)v, ldk, ldv, scale_q, scale_k, keymask, nseq, S, H, Dh, (T*)o0, p0, seq_off));
   return c.hip_err == -3 ? SPA3D_ERR_ARG : c.status();
 }
-int spa3d_op_attention_q1_bwd(const void* q0, int64_t ldq0, const void* k, const void* v, int64_t ldk, int64_t ldv, const float* scale_q,
-                              const float* scale_k, const float* keymask, const int32_t* seq_off, int64_t nseq, int32_t S, int32_t H, int32_t Dh,
-                              const float* p0, const void* d_o0, void* dq0, void* dk, void* dv, float* dscale_q, float* dscale_k, int32_t dtype,
-                              void* stream) {
-  FWD16(spa3d_op_attention_q1_bwd_f16(q0, ldq0, k, v, ldk, ldv, scale_q, scale_k, keymask, seq_off, nseq, S, H, Dh, p0, d_o0, dq0, dk, dv, dscale_q,
-                                      dscale_k, dtype, stream))
+SPA3D_OP(spa3d_op_attention_q1_bwd)(const void* q0, int64_t ldq0, const void* k, const void* v, int64_t ldk, int64_t ldv, const float* scale_q,
+                                    const float* scale_k, const float* keymask, const int32_t* seq_off, int64_t nseq, int32_t S, int32_t H, int32_t Dh,
+                                    const float* p0, const void* d_o0, void* dq0, void* dk, void* dv, float* dscale_q, float* dscale_k, int32_t dtype,
+                                    void* stream) {
+  FWD16(spa3d_op_attention_q1_bwd, q0, ldq0, k, v, ldk, ldv, scale_q, scale_k, keymask, seq_off, nseq, S, H, Dh, p0, d_o0, dq0, dk, dv, dscale_q, dscale_k,
+        dtype, stream)
   if (!q0 || !k || !v || !scale_q || !scale_k || !p0 || !d_o0 || !dq0 || !dk || !dv || !dscale_q || !dscale_k || !q1_shape_ok(nseq, S, H, Dh))
     return SPA3D_ERR_ARG;
   OpCtx c(stream, nullptr, 0);   // c.det stays null: float atomics
-  if (dtype == SPA3D_F32)
-    k_attn_q1_bwd<float>(&c, (const float*)q0, ldq0, (const float*)k, (const float*)v, ldk, ldv, scale_q, scale_k, keymask, nseq, S, H, Dh, p0,
-                         (const float*)d_o0, (float*)dq0, (float*)dk, (float*)dv, dscale_q, dscale_k, seq_off);
-  else
-    k_attn_q1_bwd<bf16_t>(&c, (const bf16_t*)q0, ldq0, (const bf16_t*)k, (const bf16_t*)v, ldk, ldv, scale_q, scale_k, keymask, nseq, S, H, Dh, p0,
-                          (const bf16_t*)d_o0, (bf16_t*)dq0, (bf16_t*)dk, (bf16_t*)dv, dscale_q, dscale_k, seq_off);
+  OP_BY_DTYPE(dtype, k_attn_q1_bwd<T>(&c, (const T*)q0, ldq0, (const T*)k, (const T*)v, ldk, ldv, scale_q, scale_k, keymask, nseq, S, H, Dh, p0, (const T*)d_o0,
+                                      (T*)dq0, (T*)dk, (T*)dv, dscale_q, dscale_k, seq_off));
   return c.hip_err == -3 ? SPA3D_ERR_ARG : c.status();
 }
 
-int spa3d_op_rank_linear(const void* x, const void* w, const float* bias, void* out, int64_t M, int32_t N, int32_t K, int64_t ldo, int32_t rgroup,
-                         int32_t rskip, int32_t dtype, void* stream) {
-  FWD16(spa3d_op_rank_linear_f16(x, w, bias, out, M, N, K, ldo, rgroup, rskip, dtype, stream))
+SPA3D_OP(spa3d_op_rank_linear)(const void* x, const void* w, const float* bias, void* out, int64_t M, int32_t N, int32_t K, int64_t ldo, int32_t rgroup,
+                               int32_t rskip, int32_t dtype, void* stream) {
+  FWD16(spa3d_op_rank_linear, x, w, bias, out, M, N, K, ldo, rgroup, rskip, dtype, stream)
   if (!x || !w || !out || M < 0 || N < 8 || ldo < N || rgroup < 0 || rskip < 0 || dtype == SPA3D_F32) return SPA3D_ERR_ARG;   // (no float instantiation: embed.hip)
   OpCtx c(stream, nullptr, 0);
   // false: K outside 1..4, N % 8, N > 2048, ldo % 8, a misaligned out, M >= 2^31 (k_rank_fwd launches nothing then)
   const bool ok = k_rank_fwd<bf16_t>(&c, (const bf16_t*)x, (const bf16_t*)w, bias, (bf16_t*)out, M, N, K, ldo, rgroup, rskip);
   return ok ? c.status() : SPA3D_ERR_ARG;
 }
-int spa3d_op_rank_linear_bwd(const void* x, const void* dy, int64_t M, int32_t N, int32_t K, int64_t ldy, int32_t rgroup, int32_t rskip, float* gw,
-                             float* gb, int32_t dtype, void* stream) {
-  FWD16(spa3d_op_rank_linear_bwd_f16(x, dy, M, N, K, ldy, rgroup, rskip, gw, gb, dtype, stream))
+SPA3D_OP(spa3d_op_rank_linear_bwd)(const void* x, const void* dy, int64_t M, int32_t N, int32_t K, int64_t ldy, int32_t rgroup, int32_t rskip, float* gw,
+                                   float* gb, int32_t dtype, void* stream) {
+  FWD16(spa3d_op_rank_linear_bwd, x, dy, M, N, K, ldy, rgroup, rskip, gw, gb, dtype, stream)
   if (!x || !dy || !gw || M < 0 || N < 8 || ldy < N || rgroup < 0 || rskip < 0 || dtype == SPA3D_F32) return SPA3D_ERR_ARG;
   OpCtx c(stream, nullptr, 0);
   const bool ok = k_rank_bwd<bf16_t>(&c, (const bf16_t*)x, (const bf16_t*)dy, M, N, K, ldy, rgroup, rskip, gw, gb);
@@ -374,37 +277,22 @@ int spa3d_op_rank_linear_bwd(const void* x, const void* dy, int64_t M, int32_t N
 // ---- The row plumbing of csrc/rows.hip on its own (tests/test_gpu_rows.py).  Thin wrappers: every input a launcher would record as a HIP-class error
 // (an empty grid, a row width that is not a multiple of 16 bytes) or mis-handle without a word (a 16-byte access through a pointer that is not 16-byte
 // aligned, a negative count) is an argument error here and launches nothing.  c.det stays null: sums use float atomics.
-#if SPA_F16
-#define ROWS_DT16 SPA3D_F16
-#else
-#define ROWS_DT16 SPA3D_BF16
-#endif
-#define ROWS_DTYPE_OK(dtype) ((dtype) == SPA3D_F32 || (dtype) == ROWS_DT16)
-// f(T*) with T the storage type of `dtype`
-#define ROWS_BY_DTYPE(dtype, body)                                          \
-  do {                                                                      \
-    if ((dtype) == SPA3D_F32) { using T = float; body; }                    \
-    else { using T = bf16_t; body; }                                        \
-  } while (0)
-static bool rows_al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-static int rows_nv(int32_t dtype) { return dtype == SPA3D_F32 ? 4 : 8; }   // elements per 16 bytes (VecOf<T>::N)
-
-int spa3d_op_colsum(const void* x, int64_t rows, int32_t n, int64_t ld, int32_t rgroup, int32_t rskip, float* out, int32_t dtype, void* stream) {
-  FWD16(spa3d_op_colsum_f16(x, rows, n, ld, rgroup, rskip, out, dtype, stream))
-  if (!x || !out || !ROWS_DTYPE_OK(dtype) || rows < 0 || n < 1 || ld < n || rgroup < 0 || rskip < 0) return SPA3D_ERR_ARG;
+SPA3D_OP(spa3d_op_colsum)(const void* x, int64_t rows, int32_t n, int64_t ld, int32_t rgroup, int32_t rskip, float* out, int32_t dtype, void* stream) {
+  FWD16(spa3d_op_colsum, x, rows, n, ld, rgroup, rskip, out, dtype, stream)
+  if (!x || !out || !OP_DTYPE_OK(dtype) || rows < 0 || n < 1 || ld < n || rgroup < 0 || rskip < 0) return SPA3D_ERR_ARG;
   OpCtx c(stream, nullptr, 0);
-  ROWS_BY_DTYPE(dtype, k_colsum<T>(&c, (const T*)x, rows, n, ld, out, rgroup, rskip));
+  OP_BY_DTYPE(dtype, k_colsum<T>(&c, (const T*)x, rows, n, ld, out, rgroup, rskip));
   return c.status();
 }
 
-int spa3d_op_rows(int32_t mode, const void* src, const int32_t* idx, int64_t stride_rows, void* dst, int64_t n, int32_t d, int32_t dtype, void* stream) {
-  FWD16(spa3d_op_rows_f16(mode, src, idx, stride_rows, dst, n, d, dtype, stream))
-  if (!src || !dst || !ROWS_DTYPE_OK(dtype) || n < 0 || d < 1 || mode < SPA3D_ROWS_GATHER_STRIDED || mode > SPA3D_ROWS_ADD_STRIDED) return SPA3D_ERR_ARG;
+SPA3D_OP(spa3d_op_rows)(int32_t mode, const void* src, const int32_t* idx, int64_t stride_rows, void* dst, int64_t n, int32_t d, int32_t dtype, void* stream) {
+  FWD16(spa3d_op_rows, mode, src, idx, stride_rows, dst, n, d, dtype, stream)
+  if (!src || !dst || !OP_DTYPE_OK(dtype) || n < 0 || d < 1 || mode < SPA3D_ROWS_GATHER_STRIDED || mode > SPA3D_ROWS_ADD_STRIDED) return SPA3D_ERR_ARG;
   const bool by_idx = mode == SPA3D_ROWS_GATHER_IDX || mode == SPA3D_ROWS_SCATTER_IDX || mode == SPA3D_ROWS_SCATTER_ADD_IDX;
-  if (by_idx && (!idx || d % rows_nv(dtype) || !rows_al16(src) || !rows_al16(dst))) return SPA3D_ERR_ARG;   // 16-byte accesses: the launcher checks d only
+  if (by_idx && (!idx || d % op_nv(dtype) || !op_al16(src) || !op_al16(dst))) return SPA3D_ERR_ARG;   // 16-byte accesses: the launcher checks d only
   if (!by_idx && stride_rows < 1) return SPA3D_ERR_ARG;
   OpCtx c(stream, nullptr, 0);
-  ROWS_BY_DTYPE(dtype, {
+  OP_BY_DTYPE(dtype, {
     if (mode == SPA3D_ROWS_GATHER_STRIDED) k_gather_rows<T>(&c, (const T*)src, stride_rows, (T*)dst, n, d);
     else if (mode == SPA3D_ROWS_ADD_STRIDED) k_add_rows_strided<T>(&c, (T*)dst, (const T*)src, stride_rows, n, d);
     else k_rows_idx<T>(&c, mode - SPA3D_ROWS_GATHER_IDX, (const T*)src, idx, (T*)dst, n, d);
@@ -429,73 +317,73 @@ int spa3d_op_share_plan(const int32_t* qframe, int64_t B, int32_t Q, int32_t* sl
 }
 #endif
 
-int spa3d_op_share_rows(int32_t which, const void* a, const void* b, const int32_t* slot, const int32_t* slot_b, const int32_t* slot_f, const int32_t* slot_q0,
-                        int64_t nslot, int64_t B, int32_t Q, int32_t L, int32_t Cl, int32_t d, void* out, int32_t dtype, void* stream) {
-  FWD16(spa3d_op_share_rows_f16(which, a, b, slot, slot_b, slot_f, slot_q0, nslot, B, Q, L, Cl, d, out, dtype, stream))
-  if (!a || !out || !ROWS_DTYPE_OK(dtype) || nslot < 0 || B < 0 || Q < 1 || L < 0 || d < 1 || which < SPA3D_SHARE_ASSEMBLE || which > SPA3D_SHARE_REDUCE)
+SPA3D_OP(spa3d_op_share_rows)(int32_t which, const void* a, const void* b, const int32_t* slot, const int32_t* slot_b, const int32_t* slot_f,
+                              const int32_t* slot_q0, int64_t nslot, int64_t B, int32_t Q, int32_t L, int32_t Cl, int32_t d, void* out, int32_t dtype, void* stream) {
+  FWD16(spa3d_op_share_rows, which, a, b, slot, slot_b, slot_f, slot_q0, nslot, B, Q, L, Cl, d, out, dtype, stream)
+  if (!a || !out || !OP_DTYPE_OK(dtype) || nslot < 0 || B < 0 || Q < 1 || L < 0 || d < 1 || which < SPA3D_SHARE_ASSEMBLE || which > SPA3D_SHARE_REDUCE)
     return SPA3D_ERR_ARG;
-  const int nv = rows_nv(dtype);
-  if (d % nv || !rows_al16(a) || !rows_al16(out) || nslot > B * Q) return SPA3D_ERR_ARG;   // vector-only kernels
+  const int nv = op_nv(dtype);
+  if (d % nv || !op_al16(a) || !op_al16(out) || nslot > B * Q) return SPA3D_ERR_ARG;   // vector-only kernels
   const int64_t nseq = B * Q;
   OpCtx c(stream, nullptr, 0);
   if (which == SPA3D_SHARE_ASSEMBLE) {
-    if (!b || !slot_b || !slot_f || Cl < 1 || Cl > d || Cl % nv || !rows_al16(b)) return SPA3D_ERR_ARG;
-    ROWS_BY_DTYPE(dtype, k_share_assemble<T>(&c, (const T*)a, (const T*)b, slot_b, slot_f, nslot, nseq, L, Cl, d, (T*)out));
+    if (!b || !slot_b || !slot_f || Cl < 1 || Cl > d || Cl % nv || !op_al16(b)) return SPA3D_ERR_ARG;
+    OP_BY_DTYPE(dtype, k_share_assemble<T>(&c, (const T*)a, (const T*)b, slot_b, slot_f, nslot, nseq, L, Cl, d, (T*)out));
   } else if (which == SPA3D_SHARE_EXPAND) {
-    if (!slot || !slot_q0 || !rows_al16(b)) return SPA3D_ERR_ARG;   // b = add, may be NULL
-    ROWS_BY_DTYPE(dtype, k_share_expand<T>(&c, (const T*)a, slot, slot_q0, nslot, nseq, L + 1, d, (const T*)b, (T*)out));
+    if (!slot || !slot_q0 || !op_al16(b)) return SPA3D_ERR_ARG;   // b = add, may be NULL
+    OP_BY_DTYPE(dtype, k_share_expand<T>(&c, (const T*)a, slot, slot_q0, nslot, nseq, L + 1, d, (const T*)b, (T*)out));
   } else {
     if (!slot || !slot_b || Q > 12288) return SPA3D_ERR_ARG;         // the member list [Q] lives in LDS, as the plan's table
-    ROWS_BY_DTYPE(dtype, k_share_reduce<T>(&c, (const T*)a, slot, slot_b, nslot, nseq, Q, L + 1, d, (T*)out));
+    OP_BY_DTYPE(dtype, k_share_reduce<T>(&c, (const T*)a, slot, slot_b, nslot, nseq, Q, L + 1, d, (T*)out));
   }
   return c.status();
 }
 
-int spa3d_op_assemble_readout(const void* qtok, const void* lat, const int32_t* qframe, int64_t B, int32_t Q, int32_t L, int32_t Cl, int32_t D, void* seq,
-                              int32_t dtype, void* stream) {
-  FWD16(spa3d_op_assemble_readout_f16(qtok, lat, qframe, B, Q, L, Cl, D, seq, dtype, stream))
-  if (!qtok || !lat || !qframe || !seq || !ROWS_DTYPE_OK(dtype) || B < 0 || Q < 1 || L < 0 || Cl < 1 || D < Cl) return SPA3D_ERR_ARG;
+SPA3D_OP(spa3d_op_assemble_readout)(const void* qtok, const void* lat, const int32_t* qframe, int64_t B, int32_t Q, int32_t L, int32_t Cl, int32_t D, void* seq,
+                                    int32_t dtype, void* stream) {
+  FWD16(spa3d_op_assemble_readout, qtok, lat, qframe, B, Q, L, Cl, D, seq, dtype, stream)
+  if (!qtok || !lat || !qframe || !seq || !OP_DTYPE_OK(dtype) || B < 0 || Q < 1 || L < 0 || Cl < 1 || D < Cl) return SPA3D_ERR_ARG;
   OpCtx c(stream, nullptr, 0);
-  ROWS_BY_DTYPE(dtype, k_assemble_readout<T>(&c, (const T*)qtok, (const T*)lat, qframe, B, Q, L, Cl, D, (T*)seq));
+  OP_BY_DTYPE(dtype, k_assemble_readout<T>(&c, (const T*)qtok, (const T*)lat, qframe, B, Q, L, Cl, D, (T*)seq));
   return c.status();
 }
-int spa3d_op_assemble_readout_bwd(const void* dseq, const int32_t* qframe, int64_t B, int32_t Q, int32_t L, int32_t Cl, int32_t D, void* dqtok, float* dlat,
-                                  int32_t accumulate, int32_t dtype, void* stream) {
-  FWD16(spa3d_op_assemble_readout_bwd_f16(dseq, qframe, B, Q, L, Cl, D, dqtok, dlat, accumulate, dtype, stream))
-  if (!dseq || !qframe || !dqtok || !dlat || !ROWS_DTYPE_OK(dtype) || B < 0 || Q < 1 || L < 1 || Cl < 1 || D < Cl || (accumulate != 0 && accumulate != 1))
+SPA3D_OP(spa3d_op_assemble_readout_bwd)(const void* dseq, const int32_t* qframe, int64_t B, int32_t Q, int32_t L, int32_t Cl, int32_t D, void* dqtok,
+                                        float* dlat, int32_t accumulate, int32_t dtype, void* stream) {
+  FWD16(spa3d_op_assemble_readout_bwd, dseq, qframe, B, Q, L, Cl, D, dqtok, dlat, accumulate, dtype, stream)
+  if (!dseq || !qframe || !dqtok || !dlat || !OP_DTYPE_OK(dtype) || B < 0 || Q < 1 || L < 1 || Cl < 1 || D < Cl || (accumulate != 0 && accumulate != 1))
     return SPA3D_ERR_ARG;   // (L = 0: dlat is empty and its launch would have no workgroup)
   OpCtx c(stream, nullptr, 0);
-  ROWS_BY_DTYPE(dtype, k_assemble_readout_bwd<T>(&c, (const T*)dseq, qframe, B, Q, L, Cl, D, (T*)dqtok, dlat, accumulate != 0));
+  OP_BY_DTYPE(dtype, k_assemble_readout_bwd<T>(&c, (const T*)dseq, qframe, B, Q, L, Cl, D, (T*)dqtok, dlat, accumulate != 0));
   return c.status();
 }
 
-int spa3d_op_broadcast_rows(const float* src, int32_t rows, int32_t d, void* dst, int64_t B, int32_t dtype, void* stream) {
-  FWD16(spa3d_op_broadcast_rows_f16(src, rows, d, dst, B, dtype, stream))
-  if (!src || !dst || !ROWS_DTYPE_OK(dtype) || rows < 1 || d < 1 || B < 0) return SPA3D_ERR_ARG;
+SPA3D_OP(spa3d_op_broadcast_rows)(const float* src, int32_t rows, int32_t d, void* dst, int64_t B, int32_t dtype, void* stream) {
+  FWD16(spa3d_op_broadcast_rows, src, rows, d, dst, B, dtype, stream)
+  if (!src || !dst || !OP_DTYPE_OK(dtype) || rows < 1 || d < 1 || B < 0) return SPA3D_ERR_ARG;
   OpCtx c(stream, nullptr, 0);
-  ROWS_BY_DTYPE(dtype, k_broadcast_rows<T>(&c, src, rows, d, (T*)dst, B));
+  OP_BY_DTYPE(dtype, k_broadcast_rows<T>(&c, src, rows, d, (T*)dst, B));
   return c.status();
 }
-int spa3d_op_bcast_grad(const void* dsrc, int64_t per, int64_t B, int64_t bstride, float* dparam, int32_t dtype, void* stream) {
-  FWD16(spa3d_op_bcast_grad_f16(dsrc, per, B, bstride, dparam, dtype, stream))
-  if (!dsrc || !dparam || !ROWS_DTYPE_OK(dtype) || per < 1 || per > 0x7fffffffLL || B < 0 || bstride < per) return SPA3D_ERR_ARG;
+SPA3D_OP(spa3d_op_bcast_grad)(const void* dsrc, int64_t per, int64_t B, int64_t bstride, float* dparam, int32_t dtype, void* stream) {
+  FWD16(spa3d_op_bcast_grad, dsrc, per, B, bstride, dparam, dtype, stream)
+  if (!dsrc || !dparam || !OP_DTYPE_OK(dtype) || per < 1 || per > 0x7fffffffLL || B < 0 || bstride < per) return SPA3D_ERR_ARG;
   OpCtx c(stream, nullptr, 0);
-  ROWS_BY_DTYPE(dtype, k_bcast_grad<T>(&c, (const T*)dsrc, per, B, bstride, dparam));
+  OP_BY_DTYPE(dtype, k_bcast_grad<T>(&c, (const T*)dsrc, per, B, bstride, dparam));
   return c.status();
 }
 
-int spa3d_op_vis_mean_pool(const void* tok, const float* vis, int64_t nseq, int32_t T_, int32_t d, void* out, int32_t dtype, void* stream) {
-  FWD16(spa3d_op_vis_mean_pool_f16(tok, vis, nseq, T_, d, out, dtype, stream))
-  if (!tok || !vis || !out || !ROWS_DTYPE_OK(dtype) || nseq < 0 || T_ < 1 || d < 1) return SPA3D_ERR_ARG;
+SPA3D_OP(spa3d_op_vis_mean_pool)(const void* tok, const float* vis, int64_t nseq, int32_t T_, int32_t d, void* out, int32_t dtype, void* stream) {
+  FWD16(spa3d_op_vis_mean_pool, tok, vis, nseq, T_, d, out, dtype, stream)
+  if (!tok || !vis || !out || !OP_DTYPE_OK(dtype) || nseq < 0 || T_ < 1 || d < 1) return SPA3D_ERR_ARG;
   OpCtx c(stream, nullptr, 0);
-  ROWS_BY_DTYPE(dtype, k_vis_mean_pool<T>(&c, (const T*)tok, vis, nseq, T_, d, (T*)out));
+  OP_BY_DTYPE(dtype, k_vis_mean_pool<T>(&c, (const T*)tok, vis, nseq, T_, d, (T*)out));
   return c.status();
 }
-int spa3d_op_vis_mean_pool_bwd(const void* dout, const float* vis, int64_t nseq, int32_t T_, int32_t d, void* dtok, int32_t dtype, void* stream) {
-  FWD16(spa3d_op_vis_mean_pool_bwd_f16(dout, vis, nseq, T_, d, dtok, dtype, stream))
-  if (!dout || !vis || !dtok || !ROWS_DTYPE_OK(dtype) || nseq < 0 || T_ < 1 || d < 1) return SPA3D_ERR_ARG;
+SPA3D_OP(spa3d_op_vis_mean_pool_bwd)(const void* dout, const float* vis, int64_t nseq, int32_t T_, int32_t d, void* dtok, int32_t dtype, void* stream) {
+  FWD16(spa3d_op_vis_mean_pool_bwd, dout, vis, nseq, T_, d, dtok, dtype, stream)
+  if (!dout || !vis || !dtok || !OP_DTYPE_OK(dtype) || nseq < 0 || T_ < 1 || d < 1) return SPA3D_ERR_ARG;
   OpCtx c(stream, nullptr, 0);
-  ROWS_BY_DTYPE(dtype, k_vis_mean_pool_bwd<T>(&c, (const T*)dout, vis, nseq, T_, d, (T*)dtok));
+  OP_BY_DTYPE(dtype, k_vis_mean_pool_bwd<T>(&c, (const T*)dout, vis, nseq, T_, d, (T*)dtok));
   return c.status();
 }
 
@@ -506,50 +394,50 @@ static bool embed_nf_ok(int32_t nf) { return nf >= 1 && nf <= 64; }
 static bool embed_scale_ok(float s) { return s != 0.f && s == s; }
 static const int32_t kTileRowsMax = 65535 * 32;   // pack / transpose put the row tiles on gridDim.y
 
-int spa3d_op_sin_embed_scaled(const float* x, int64_t rows, int32_t C, int32_t nf, float prescale, void* out, int32_t dtype, void* stream) {
-  FWD16(spa3d_op_sin_embed_scaled_f16(x, rows, C, nf, prescale, out, dtype, stream))
-  if (!x || !out || !ROWS_DTYPE_OK(dtype) || rows < 0 || C < 1 || C > 65536 || !embed_nf_ok(nf) || !embed_scale_ok(prescale)) return SPA3D_ERR_ARG;
+SPA3D_OP(spa3d_op_sin_embed_scaled)(const float* x, int64_t rows, int32_t C, int32_t nf, float prescale, void* out, int32_t dtype, void* stream) {
+  FWD16(spa3d_op_sin_embed_scaled, x, rows, C, nf, prescale, out, dtype, stream)
+  if (!x || !out || !OP_DTYPE_OK(dtype) || rows < 0 || C < 1 || C > 65536 || !embed_nf_ok(nf) || !embed_scale_ok(prescale)) return SPA3D_ERR_ARG;
   OpCtx c(stream, nullptr, 0);
-  ROWS_BY_DTYPE(dtype, k_sin_embed<T>(&c, x, rows, C, nf, prescale, (T*)out));
+  OP_BY_DTYPE(dtype, k_sin_embed<T>(&c, x, rows, C, nf, prescale, (T*)out));
   return c.status();
 }
-int spa3d_op_embed_tokens(const float* tracks, int64_t nrows, int32_t T_, int32_t NC, int32_t nf, float prescale, void* out, int32_t dtype, void* stream) {
-  FWD16(spa3d_op_embed_tokens_f16(tracks, nrows, T_, NC, nf, prescale, out, dtype, stream))
-  if (!tracks || !out || !ROWS_DTYPE_OK(dtype) || nrows < 0 || T_ < 1 || (NC != 2 && NC != 3) || !embed_nf_ok(nf) || !embed_scale_ok(prescale)) return SPA3D_ERR_ARG;
+SPA3D_OP(spa3d_op_embed_tokens)(const float* tracks, int64_t nrows, int32_t T_, int32_t NC, int32_t nf, float prescale, void* out, int32_t dtype, void* stream) {
+  FWD16(spa3d_op_embed_tokens, tracks, nrows, T_, NC, nf, prescale, out, dtype, stream)
+  if (!tracks || !out || !OP_DTYPE_OK(dtype) || nrows < 0 || T_ < 1 || (NC != 2 && NC != 3) || !embed_nf_ok(nf) || !embed_scale_ok(prescale)) return SPA3D_ERR_ARG;
   OpCtx c(stream, nullptr, 0);
-  ROWS_BY_DTYPE(dtype, k_embed_tokens<T>(&c, tracks, nrows, T_, nf, prescale, (T*)out, NC));
+  OP_BY_DTYPE(dtype, k_embed_tokens<T>(&c, tracks, nrows, T_, nf, prescale, (T*)out, NC));
   return c.status();
 }
-int spa3d_op_embed_maps(const int32_t* row_src, int64_t rows, int32_t S, int32_t T_, int32_t* arow, int32_t* crow, void* tok, const float* readout, int32_t d,
-                        int32_t dtype, void* stream) {
-  FWD16(spa3d_op_embed_maps_f16(row_src, rows, S, T_, arow, crow, tok, readout, d, dtype, stream))
-  if (!arow || !crow || !tok || !readout || !ROWS_DTYPE_OK(dtype) || rows < 0 || rows > 0x7fffffffLL || T_ < 1 || S != T_ + 1 || d < 1) return SPA3D_ERR_ARG;
+SPA3D_OP(spa3d_op_embed_maps)(const int32_t* row_src, int64_t rows, int32_t S, int32_t T_, int32_t* arow, int32_t* crow, void* tok, const float* readout,
+                              int32_t d, int32_t dtype, void* stream) {
+  FWD16(spa3d_op_embed_maps, row_src, rows, S, T_, arow, crow, tok, readout, d, dtype, stream)
+  if (!arow || !crow || !tok || !readout || !OP_DTYPE_OK(dtype) || rows < 0 || rows > 0x7fffffffLL || T_ < 1 || S != T_ + 1 || d < 1) return SPA3D_ERR_ARG;
   OpCtx c(stream, nullptr, 0);
-  ROWS_BY_DTYPE(dtype, k_embed_maps<T>(&c, row_src, rows, S, T_, arow, crow, (T*)tok, readout, d));
+  OP_BY_DTYPE(dtype, k_embed_maps<T>(&c, row_src, rows, S, T_, arow, crow, (T*)tok, readout, d));
   return c.status();
 }
-int spa3d_op_set_readout_rows(void* tok, const float* readout, int64_t nseq, int32_t S, int32_t d, int32_t dtype, void* stream) {
-  FWD16(spa3d_op_set_readout_rows_f16(tok, readout, nseq, S, d, dtype, stream))
-  if (!tok || !readout || !ROWS_DTYPE_OK(dtype) || nseq < 0 || S < 1 || d < 1) return SPA3D_ERR_ARG;
+SPA3D_OP(spa3d_op_set_readout_rows)(void* tok, const float* readout, int64_t nseq, int32_t S, int32_t d, int32_t dtype, void* stream) {
+  FWD16(spa3d_op_set_readout_rows, tok, readout, nseq, S, d, dtype, stream)
+  if (!tok || !readout || !OP_DTYPE_OK(dtype) || nseq < 0 || S < 1 || d < 1) return SPA3D_ERR_ARG;
   OpCtx c(stream, nullptr, 0);
-  ROWS_BY_DTYPE(dtype, k_set_readout_rows<T>(&c, (T*)tok, readout, nseq, S, d));
+  OP_BY_DTYPE(dtype, k_set_readout_rows<T>(&c, (T*)tok, readout, nseq, S, d));
   return c.status();
 }
-int spa3d_op_pack(const float* src, int64_t src_ld, int32_t rows, int32_t cols, void* dn, int64_t ldn, void* dt, int64_t ldt, int32_t dtype, void* stream) {
-  FWD16(spa3d_op_pack_f16(src, src_ld, rows, cols, dn, ldn, dt, ldt, dtype, stream))
-  if (!src || (!dn && !dt) || !ROWS_DTYPE_OK(dtype) || rows < 0 || rows > kTileRowsMax || cols < 0 || src_ld < cols || (dn && ldn < cols) || (dt && ldt < rows))
+SPA3D_OP(spa3d_op_pack)(const float* src, int64_t src_ld, int32_t rows, int32_t cols, void* dn, int64_t ldn, void* dt, int64_t ldt, int32_t dtype, void* stream) {
+  FWD16(spa3d_op_pack, src, src_ld, rows, cols, dn, ldn, dt, ldt, dtype, stream)
+  if (!src || (!dn && !dt) || !OP_DTYPE_OK(dtype) || rows < 0 || rows > kTileRowsMax || cols < 0 || src_ld < cols || (dn && ldn < cols) || (dt && ldt < rows))
     return SPA3D_ERR_ARG;
   if (rows == 0 || cols == 0) return SPA3D_OK;   // (k_pack would launch an empty grid)
   OpCtx c(stream, nullptr, 0);
-  ROWS_BY_DTYPE(dtype, k_pack<T>(&c, src, src_ld, rows, cols, (T*)dn, ldn, (T*)dt, ldt));
+  OP_BY_DTYPE(dtype, k_pack<T>(&c, src, src_ld, rows, cols, (T*)dn, ldn, (T*)dt, ldt));
   return c.status();
 }
-int spa3d_op_transpose(const void* src, int32_t rows, int32_t cols, void* dst, int32_t dtype, void* stream) {
-  FWD16(spa3d_op_transpose_f16(src, rows, cols, dst, dtype, stream))
-  if (!src || !dst || !ROWS_DTYPE_OK(dtype) || rows < 0 || rows > kTileRowsMax || cols < 0) return SPA3D_ERR_ARG;
+SPA3D_OP(spa3d_op_transpose)(const void* src, int32_t rows, int32_t cols, void* dst, int32_t dtype, void* stream) {
+  FWD16(spa3d_op_transpose, src, rows, cols, dst, dtype, stream)
+  if (!src || !dst || !OP_DTYPE_OK(dtype) || rows < 0 || rows > kTileRowsMax || cols < 0) return SPA3D_ERR_ARG;
   if (rows == 0 || cols == 0) return SPA3D_OK;
   OpCtx c(stream, nullptr, 0);
-  ROWS_BY_DTYPE(dtype, k_transpose<T>(&c, (const T*)src, rows, cols, (T*)dst));
+  OP_BY_DTYPE(dtype, k_transpose<T>(&c, (const T*)src, rows, cols, (T*)dst));
   return c.status();
 }
 

@@ -35,6 +35,69 @@ def test_library_exports_every_declared_symbol(spa3d):
   assert spa3d._lib.load().spa3d_version().startswith(b'spa3d-hip')
 
 
+def _c_kind(decl):
+  """pointer / int32 / int64 / uint32 / float / double of one C return or parameter type as include/spa3d.h writes it (the parameter's name may follow)"""
+  if '*' in decl or '[' in decl or re.search(r'\bspa3d_handle\b', decl):
+    return 'pointer'
+  for kind, pat in (('int64', r'\bint64_t\b'), ('uint32', r'\buint32_t\b'), ('int32', r'\b(int32_t|int)\b'), ('float', r'\bfloat\b'), ('double', r'\bdouble\b')):
+    if re.search(pat, decl):
+      return kind
+  raise AssertionError(f'unparsed C type: {decl!r}')
+
+
+def _ctypes_kind(t):
+  if t in (C.c_void_p, C.c_char_p) or issubclass(t, C._Pointer):
+    return 'pointer'
+  return {C.c_int32: 'int32', C.c_int64: 'int64', C.c_uint32: 'uint32', C.c_float: 'float', C.c_double: 'double'}[t]   # (c_int is c_int32)
+
+
+def _header_signatures():
+  """{name: (return kind, [argument kinds])} of every function include/spa3d.h declares"""
+  hdr = open(os.path.join(ROOT, 'include', 'spa3d.h')).read()
+  hdr = re.sub(r'/\*.*?\*/', ' ', hdr, flags=re.S)
+  hdr = re.sub(r'//[^\n]*', ' ', hdr)
+  hdr = re.sub(r'^\s*#[^\n]*', ' ', hdr, flags=re.M)
+  sigs = {}
+  for ret, name, args in re.findall(r'([^;{}()]*?)\b(spa3d_[a-z0-9_]+)\s*\(([^()]*)\)\s*;', hdr):
+    args = [a for a in (a.strip() for a in args.split(',')) if a and a != 'void']
+    assert name not in sigs, name
+    sigs[name] = (_c_kind(ret), [_c_kind(a) for a in args])
+  return sigs
+
+
+def _table_mismatches(header, table):
+  out = []
+  for name in sorted(set(header) | set(table)):
+    if name not in header or name not in table:
+      out.append(f'{name}: only in the {"table" if name in table else "header"}')
+      continue
+    (hret, hargs), (tret, targs) = header[name], table[name]
+    if _ctypes_kind(tret) != hret:
+      out.append(f'{name}: returns {hret}, table says {_ctypes_kind(tret)}')
+    if len(targs) != len(hargs):
+      out.append(f'{name}: {len(hargs)} arguments, table has {len(targs)}')
+      continue
+    out += [f'{name}: argument {i} is {h}, table says {_ctypes_kind(t)}' for i, (h, t) in enumerate(zip(hargs, targs)) if _ctypes_kind(t) != h]
+  return out
+
+
+def test_ctypes_table_matches_header_signatures(spa3d):
+  """_lib._SIGS against include/spa3d.h by return kind, argument count and each argument's kind (the export test above compares names only): a c_int32
+  where the header says int64_t, or a missing argument, would hand a kernel garbage without a word.  No library is loaded."""
+  lib = spa3d._lib
+  header = _header_signatures()
+  hdr = open(os.path.join(ROOT, 'include', 'spa3d.h')).read()
+  assert set(header) == set(re.findall(r'\b(spa3d_[a-z0-9_]+)\s*\(', hdr)) - {'spa3d_ctx'}, 'the parser missed a declaration'
+  assert len(header) >= 77
+  assert _table_mismatches(header, lib._SIGS) == []
+  # the comparison sees what it is for: one int64 narrowed, one argument dropped
+  bad = {k: (r, list(a)) for k, (r, a) in lib._SIGS.items()}
+  i = bad['spa3d_op_layernorm'][1].index(C.c_int64)
+  bad['spa3d_op_layernorm'][1][i] = C.c_int32
+  bad['spa3d_op_transpose'][1].pop()
+  assert _table_mismatches(header, bad) == [f'spa3d_op_layernorm: argument {i} is int64, table says int32', 'spa3d_op_transpose: 6 arguments, table has 5']
+
+
 def test_no_cpu_fallback_and_no_oracle_import_in_product():
   pkg = os.path.join(ROOT, '3dspa_code_amd')
   for fn in os.listdir(pkg):
