@@ -53,6 +53,19 @@ struct NtArgs {
   int nt_store;  // bf16 output with non-temporal stores: a streamed output far larger than the caches (+3-6 % measured at K = 384)
 };
 
+// opt KERNEL into LDS bytes of dynamic shared memory (more than the 64 KiB a kernel gets unasked), once per kernel
+template <auto KERNEL, int LDS>
+static void set_max_lds() {
+  static bool done = false;
+  if (!done) { (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); done = true; }
+}
+
+// 8 consecutive floats of a per-column vector (bias, rank-1 weights) as two 16-byte loads; gn % 4 == 0
+__device__ __forceinline__ void load_bias8(const float* bias, int gn, float (&b8)[8]) {
+  const float4 b0 = *(const float4*)(bias + gn), b1 = *(const float4*)(bias + gn + 4);
+  b8[0] = b0.x; b8[1] = b0.y; b8[2] = b0.z; b8[3] = b0.w; b8[4] = b1.x; b8[5] = b1.y; b8[6] = b1.z; b8[7] = b1.w;
+}
+
 __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(NtArgs g) {
   extern __shared__ __attribute__((aligned(16))) char smem[];  // [2][A 16 KiB | B 16 KiB]
   // XCD-aware id: blocks b, b+8, b+16.. share an XCD; give each XCD whole A panels (all N-tiles of an M-tile)
@@ -138,13 +151,13 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(NtArgs g) {
   float b8[8];
 #pragma unroll
   for (int r = 0; r < 8; ++r) b8[r] = 0.f;
-  if (g.bias) { const float4 b0 = *(const float4*)(g.bias + gn), b1 = *(const float4*)(g.bias + gn + 4);
-    b8[0] = b0.x; b8[1] = b0.y; b8[2] = b0.z; b8[3] = b0.w; b8[4] = b1.x; b8[5] = b1.y; b8[6] = b1.z; b8[7] = b1.w; }
+  if (g.bias) load_bias8(g.bias, gn, b8);
 #pragma unroll 2
   for (int it = 0; it < 8; ++it) {
     const int row = it * 16 + er;
     const int64_t gm = m0 + row;
     if (gm >= g.M) break;
+    // the rest mirrors nt_store8 (below) without its non-temporal arm; calling it instead costs 18 instructions
     int64_t crow = gm;
     if (g.crow_group > 0) crow = gm + (gm / g.crow_group + 1) * (int64_t)g.crow_skip;
     const f32x4 v0 = *(const f32x4*)(cs + row * 128 + (((2 * ec) ^ (row & 31)) << 2));
@@ -198,6 +211,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(NtArgs g) {
 // =================================================================================================================
 __global__ __launch_bounds__(256, 4) void gemm_nt_occ_kernel(NtArgs g) {
   extern __shared__ __attribute__((aligned(16))) char smem[];  // [A 16 KiB | B 16 KiB]
+  // tile id, staging addresses and accumulators as in gemm_nt_kernel (a shared inline helper changed both kernels' code: spelled out)
   const int bid = blockIdx.x;
   const int xcd = bid & 7, idx = bid >> 3;
   const int tm = (idx / g.tiles_n) * 8 + xcd, tn = idx % g.tiles_n;
@@ -300,24 +314,6 @@ __global__ __launch_bounds__(256, 4) void gemm_nt_occ_kernel(NtArgs g) {
 }
 
 
-// =================================================================================================================
-// 256x256x64, 8 waves, 8-phase schedule (cdna_hip_programming.md "The 256^2 8-phase template"), written for this
-// library's operand layout (A [M][K], Bt [N][K], XOR-swizzled 128-B LDS rows, swapped-operand MFMA).
-//   waves 2(M) x 4(N), 128x64 per wave; a K-tile is four half-tiles of 16 KiB, split by NEED, not by position:
-//     A-h0 / A-h1 = the first / second 64 rows of each wave-row's 128;  B-h0 / B-h1 = the first / second 32 columns of each
-//     wave-column's 64.  Phase p of K-tile t works on one quadrant of the wave's output:
-//       P0: read B-q0 (4 ds_read_b128, retired before the barrier), A-q0 (8);  16 MFMA  (rows 0-63,   cols 0-31)
-//       P1: read B-q1 (4);                                                      16 MFMA  (rows 0-63,   cols 32-63)
-//       P2: read A-q1 (8);                                                      16 MFMA  (rows 64-127, cols 32-63)
-//       P3: --                                                                  16 MFMA  (rows 64-127, cols 0-31)
-//     LDS: A in a 3-slot ring, B double-buffered (160 KiB / 144 KiB).  Everything issued during K-tile t is for K-tile t+2:
-//       P0: A-h0(t+2), A-h1(t+2) into the ring slot last read in K-tile t-1;  P1: B-h0(t+2) (its slot's last reads retired before
-//       P0's barrier);  P3: B-h1(t+2) (last read in P1).  The A panel is the operand streamed from HBM: it gets a full two
-//       K-tiles of lead; the weights come from L2.
-//   One counted wait per K-tile, in P3 before its first barrier: vmcnt(#LDS-DMA of one K-tile) leaves K-tile t+2 in flight and
-//   retires all of K-tile t+1, which is first read one phase later.  Two raw s_barrier per phase; the wave-row-1 waves run
-//   one barrier behind, so on every SIMD one wave is in its MFMA section while the other is in its read/stage section.
-// =================================================================================================================
 // 8 consecutive columns of one output row: alpha/bias, optional pre-activation copy, GELU, residual / GELU-gradient, store.
 template <bool AUXPRE = false, bool REMAP = true>
 __device__ __forceinline__ void nt_store8(const NtArgs& g, int64_t gm, int gn, float (&v)[8], const float (&b8)[8], uint4 auxpre = uint4{0, 0, 0, 0}) {
@@ -385,49 +381,6 @@ __device__ __forceinline__ uint4 nt_compute8_aux(const NtArgs& g, float (&v)[8],
   return o4;
 }
 
-__device__ __forceinline__ void nt_store4(const NtArgs& g, int64_t gm, int gn, const f32x4& a) {
-  if (gm >= g.M || gn >= g.N) return;
-  int64_t crow = gm;
-  if (g.crow_group > 0) crow = gm + (gm / g.crow_group + 1) * (int64_t)g.crow_skip;
-  float vv[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) vv[r] = g.alpha * a[r];
-  if (g.bias) { const float4 b4 = *(const float4*)(g.bias + gn); vv[0] += b4.x; vv[1] += b4.y; vv[2] += b4.z; vv[3] += b4.w; }
-  const int64_t ci = crow * g.ldc + gn;
-  if (g.pre_out) { u16x4 p4;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) p4[r] = f2bf(vv[r]);
-    *(u16x4*)(g.pre_out + ci) = p4; }
-  if (g.epi == EPI_GELU) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) vv[r] = gelu_tanh_fast_f(vv[r]);
-  }
-  if (g.aux) {
-    const u16x4 x4 = *(const u16x4*)(g.aux + ci);
-    if (g.epi == EPI_MUL_GELU_GRAD) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) vv[r] *= gelu_tanh_grad_fast_f(bf2f(x4[r]));
-    } else {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) vv[r] += bf2f(x4[r]);
-    }
-  }
-  if (g.out_f32) {
-    float4* cp = (float4*)((float*)g.C + ci);
-    if (g.accumulate) { const float4 o = *cp; vv[0] += o.x; vv[1] += o.y; vv[2] += o.z; vv[3] += o.w; }
-    *cp = make_float4(vv[0], vv[1], vv[2], vv[3]);
-  } else {
-    u16x4* cp = (u16x4*)((bf16_t*)g.C + ci);
-    if (g.accumulate) { const u16x4 o = *cp;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) vv[r] += bf2f(o[r]); }
-    u16x4 o4;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) o4[r] = f2bf(vv[r]);
-    *cp = o4;
-  }
-}
-
 // diagnostic library only (tools/ablate_gemm.py, -DSPA3D_ABLATION_BUILD -DSPA3D_ABL_NT=1: csrc/ablate.inc): the persistent kernel without its output stores = loop-only time
 #if SPA3D_ABL_NT
 #define NT_ABLATE_STORES && !g.ablate
@@ -438,16 +391,132 @@ __device__ __forceinline__ void nt_store4(const NtArgs& g, int64_t gm, int gn, c
 #define NT8P_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
 #define NT8P_WAIT_LGKM(n) asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(n) : "memory")
 
-// WMT x WNT = 16x16 output tiles per wave; waves 2(M) x 4(N); tile = (32 WMT) x (64 WNT): <8,4> = 256x256, <4,6> = 128x384
-// (N = 384 in ONE tile: the A panel is read from HBM exactly once).  64 KiB per LDS buffer in both.
-// <4,2> = 128x128 on 80 KiB of LDS and <= 128 registers: TWO workgroups per CU, so one's epilogue (the store drain that is purely additive at
-// K = 384) can run under the other's K-loop -- the round-3 measurement of that hypothesis (SPA3D_NT_8P=42)
-template <int WMT, int WNT, bool COARSE = false, bool EMB = false>  // EMB: the one-pass input-embedding operands of NtArgs are live
-__global__ __launch_bounds__(512, (WMT * WNT <= 8 ? 4 : 2)) void gemm_nt8p_kernel(NtArgs g) {
-  constexpr int BM = 32 * WMT, BN = 64 * WNT;
-  constexpr int NA = WMT / 4, NB = WNT / 2;   // LDS-DMA per thread per A / B half-tile
-  constexpr int HM = WMT / 2, HN = WNT / 2;   // tiles per quadrant side
-  constexpr int ASLOT = BM * 128, BBUF = BN * 128, BOFF = 3 * ASLOT;  // A ring of 3, then two B buffers
+// Geometry of the 8-phase NT kernels.  WMT x WNT = 16x16 output tiles per wave; waves 2(M) x 4(N); tile = (32 WMT) x (64 WNT):
+// <8,4> = 256x256, <4,6> = 128x384 (N = 384 in ONE tile: the A panel is read from HBM exactly once).  64 KiB per LDS buffer in both.
+template <int WMT, int WNT>
+struct Nt8pGeom {
+  static constexpr int BM = 32 * WMT, BN = 64 * WNT;
+  static constexpr int NA = WMT / 4, NB = WNT / 2;   // LDS-DMA per thread per A / B half-tile
+  static constexpr int HM = WMT / 2, HN = WNT / 2;   // tiles per quadrant side
+  static constexpr int ASLOT = BM * 128, BBUF = BN * 128, BOFF = 3 * ASLOT;  // A ring of 3, then two B buffers
+  static constexpr int NKT = 2 * NA + 2 * NB;        // LDS-DMA per thread per K-tile
+  static constexpr int LDS = 3 * ASLOT + 2 * BBUF;   // 160 KiB <8,4>, 144 KiB <4,6>
+};
+// staging: first row of the 8-row group that LDS-DMA i of wave w brings into half h of an operand tile whose waves own WT 16-row tiles
+// each (A: WMT, B: WNT).  It is group gi = 8i + w of the half-tile: wave-row / wave-column block gi / WT, group gi % WT of that block's half
+template <int WT>
+__device__ __forceinline__ int nt8p_row_group(int h, int i, int w) { const int gi = i * 8 + w; return (gi / WT) * (WT * 16) + h * (WT * 8) + (gi % WT) * 8; }
+
+// =================================================================================================================
+// 256x256x64, 8 waves, 8-phase schedule (cdna_hip_programming.md "The 256^2 8-phase template"), written for this
+// library's operand layout (A [M][K], Bt [N][K], XOR-swizzled 128-B LDS rows, swapped-operand MFMA).
+//   waves 2(M) x 4(N), 128x64 per wave; a K-tile is four half-tiles of 16 KiB, split by NEED, not by position:
+//     A-h0 / A-h1 = the first / second 64 rows of each wave-row's 128;  B-h0 / B-h1 = the first / second 32 columns of each
+//     wave-column's 64.  Phase p of K-tile t works on one quadrant of the wave's output:
+//       P0: read B-q0 (4 ds_read_b128, retired before the barrier), A-q0 (8);  16 MFMA  (rows 0-63,   cols 0-31)
+//       P1: read B-q1 (4);                                                      16 MFMA  (rows 0-63,   cols 32-63)
+//       P2: read A-q1 (8);                                                      16 MFMA  (rows 64-127, cols 32-63)
+//       P3: --                                                                  16 MFMA  (rows 64-127, cols 0-31)
+//     LDS: A in a 3-slot ring, B double-buffered (160 KiB / 144 KiB).  Everything issued during K-tile t is for K-tile t+2:
+//       P0: A-h0(t+2), A-h1(t+2) into the ring slot last read in K-tile t-1;  P1: B-h0(t+2) (its slot's last reads retired before
+//       P0's barrier);  P3: B-h1(t+2) (last read in P1).  The A panel is the operand streamed from HBM: it gets a full two
+//       K-tiles of lead; the weights come from L2.
+//   One counted wait per K-tile, in P3 before its first barrier: vmcnt(#LDS-DMA of one K-tile) leaves K-tile t+2 in flight and
+//   retires all of K-tile t+1, which is first read one phase later.  Two raw s_barrier per phase; the wave-row-1 waves run
+//   one barrier behind, so on every SIMD one wave is in its MFMA section while the other is in its read/stage section.
+// =================================================================================================================
+// The K-loop of both 8-phase NT kernels (gemm_nt8p_kernel, gemm_nt8pp_kernel).  On entry K-tile 0 is visible to every wave, K-tile 1
+// (if any) is in flight and wave-row 1 has taken its extra barrier; stageA(kt, slot) / stageB(h, kt) issue the caller's LDS-DMA.
+// COARSE: two phases per K-tile instead of four.  On return only wave-row 0's pairing barrier is left to the caller.
+template <int WMT, int WNT, bool COARSE, class StageA, class StageB>
+__device__ __forceinline__ void nt8p_kloop(f32x4 (&acc)[WMT][WNT], const char* smem, int nt, int a_off, int b_off, int x0, int x1,
+                                           StageA&& stageA, StageB&& stageB) {
+  using G = Nt8pGeom<WMT, WNT>;
+  constexpr int HM = G::HM, HN = G::HN, ASLOT = G::ASLOT, BBUF = G::BBUF, NKT = G::NKT;
+  bf16x8 aq[HM][2], bq0[HN][2], bq1[HN][2];
+#define NT8P_MFMA(AI, BJ, BQ)                                                                                                         \
+  __builtin_amdgcn_s_setprio(1);                                                                                                      \
+  _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) _Pragma("unroll") for (int i = 0; i < HM; ++i) _Pragma("unroll") for (int j = 0; j < HN; ++j) \
+      acc[(AI) + i][(BJ) + j] = MFMA16(BQ[j][ks], aq[i][ks], acc[(AI) + i][(BJ) + j]);       \
+  __builtin_amdgcn_s_setprio(0);
+  int aslot = 0, aslot2 = 2;  // ring slots of K-tiles t and t+2
+  for (int t = 0; t < nt; ++t) {
+    const char* sa = smem + aslot * ASLOT;
+    const char* sb = smem + (t & 1) * BBUF;
+    if constexpr (COARSE) {
+      // two phases per K-tile, 2 HM HN x 2 MFMAs (<8,4>: 32, 512 cycles) per barrier pair: one wave-row's MFMA section covers the
+      // other's reads and their LDS latency.  Every read is retired BEFORE its phase's first barrier, so a slot may be restaged one
+      // phase later.
+      // ---------------- PA: B-q0, B-q1 (retired first), A-q0 | stage A(t+2) | quadrants (0,0) (0,1)
+#pragma unroll
+      for (int j = 0; j < HN; ++j) { bq0[j][0] = *(const bf16x8*)(sb + b_off + j * 2048 + x0); bq0[j][1] = *(const bf16x8*)(sb + b_off + j * 2048 + x1); }
+#pragma unroll
+      for (int j = 0; j < HN; ++j) { bq1[j][0] = *(const bf16x8*)(sb + b_off + (HN + j) * 2048 + x0); bq1[j][1] = *(const bf16x8*)(sb + b_off + (HN + j) * 2048 + x1); }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int i = 0; i < HM; ++i) { aq[i][0] = *(const bf16x8*)(sa + a_off + i * 2048 + x0); aq[i][1] = *(const bf16x8*)(sa + a_off + i * 2048 + x1); }
+      if (t + 2 < nt) stageA(t + 2, aslot2);   // slot of K-tile t-1: its A-q1 reads were retired before the previous phase's barrier
+      NT8P_WAIT_LGKM(2 * HM);                  // the B reads have returned: both B halves may be restaged next phase
+      NT8P_BAR();
+      NT8P_WAIT_LGKM(0);
+      NT8P_MFMA(0, 0, bq0)
+      NT8P_MFMA(0, HN, bq1)
+      NT8P_BAR();
+      // ---------------- PB: A-q1 (retired before the barrier) | stage B-h0(t+2), B-h1(t+2) | wait K-tile t+1 | quadrants (1,1) (1,0)
+#pragma unroll
+      for (int i = 0; i < HM; ++i) { aq[i][0] = *(const bf16x8*)(sa + a_off + (HM + i) * 2048 + x0); aq[i][1] = *(const bf16x8*)(sa + a_off + (HM + i) * 2048 + x1); }
+      if (t + 2 < nt) { stageB(0, t + 2); stageB(1, t + 2); NT8P_WAIT_VM(NKT); }
+      else NT8P_WAIT_VM(0);
+      NT8P_WAIT_LGKM(0);
+      NT8P_BAR();
+      NT8P_MFMA(HM, HN, bq1)
+      NT8P_MFMA(HM, 0, bq0)
+      NT8P_BAR();
+    } else {
+      // ---------------- P0
+#pragma unroll
+      for (int j = 0; j < HN; ++j) { bq0[j][0] = *(const bf16x8*)(sb + b_off + j * 2048 + x0); bq0[j][1] = *(const bf16x8*)(sb + b_off + j * 2048 + x1); }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int i = 0; i < HM; ++i) { aq[i][0] = *(const bf16x8*)(sa + a_off + i * 2048 + x0); aq[i][1] = *(const bf16x8*)(sa + a_off + i * 2048 + x1); }
+      if (t + 2 < nt) stageA(t + 2, aslot2);
+      NT8P_WAIT_LGKM(2 * HM);  // the B-q0 reads have returned: B-h0 may be restaged one phase from now
+      NT8P_BAR();
+      NT8P_WAIT_LGKM(0);
+      NT8P_MFMA(0, 0, bq0)
+      NT8P_BAR();
+      // ---------------- P1
+#pragma unroll
+      for (int j = 0; j < HN; ++j) { bq1[j][0] = *(const bf16x8*)(sb + b_off + (HN + j) * 2048 + x0); bq1[j][1] = *(const bf16x8*)(sb + b_off + (HN + j) * 2048 + x1); }
+      if (t + 2 < nt) stageB(0, t + 2);
+      NT8P_BAR();
+      NT8P_WAIT_LGKM(0);
+      NT8P_MFMA(0, HN, bq1)
+      NT8P_BAR();
+      // ---------------- P2
+#pragma unroll
+      for (int i = 0; i < HM; ++i) { aq[i][0] = *(const bf16x8*)(sa + a_off + (HM + i) * 2048 + x0); aq[i][1] = *(const bf16x8*)(sa + a_off + (HM + i) * 2048 + x1); }
+      NT8P_BAR();
+      NT8P_WAIT_LGKM(0);
+      NT8P_MFMA(HM, HN, bq1)
+      NT8P_BAR();
+      // ---------------- P3
+      if (t + 2 < nt) { stageB(1, t + 2); NT8P_WAIT_VM(NKT); }  // K-tile t+1 has landed (this wave's part); t+2 stays in flight
+      else NT8P_WAIT_VM(0);
+      NT8P_BAR();
+      NT8P_MFMA(HM, 0, bq0)
+      NT8P_BAR();
+    }
+    aslot = aslot == 2 ? 0 : aslot + 1; aslot2 = aslot2 == 2 ? 0 : aslot2 + 1;
+  }
+#undef NT8P_MFMA
+}
+
+// Non-persistent form: one workgroup per output tile.  EMB: the one-pass input-embedding operands of NtArgs are live
+template <int WMT, int WNT, bool EMB = false>
+__global__ __launch_bounds__(512, 2) void gemm_nt8p_kernel(NtArgs g) {
+  using G = Nt8pGeom<WMT, WNT>;
+  constexpr int BM = G::BM, BN = G::BN, NA = G::NA, NB = G::NB, HM = G::HM, ASLOT = G::ASLOT, BBUF = G::BBUF, BOFF = G::BOFF, NKT = G::NKT;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int bid = blockIdx.x;
   const int xcd = bid & 7, idx = bid >> 3;
@@ -461,7 +530,7 @@ __global__ __launch_bounds__(512, (WMT * WNT <= 8 ? 4 : 2)) void gemm_nt8p_kerne
   const int fr = lane & 15, fq = lane >> 4;
   const int sr = lane >> 3, scp = lane & 7;
   const int sc = (scp ^ sr) * 8;
-  // staging: 8-row group gi = 8i + w of a half-tile.  A-h: wave-row block gi / WMT, group gi % WMT; B-h: wave-column block gi / WNT
+  // staging: per LDS-DMA a 64-bit source pointer (rows clamped on the edges) and the byte offset of its 8-row group in the LDS image
   const bf16_t* pa[2][NA]; const bf16_t* pb[2][NB];
   const bf16_t* pa2[2][NA];  // second A source (columns K1 .. K), same rows
   int la[2][NA], lb[2][NB];
@@ -469,7 +538,7 @@ __global__ __launch_bounds__(512, (WMT * WNT <= 8 ? 4 : 2)) void gemm_nt8p_kerne
   for (int h = 0; h < 2; ++h) {
 #pragma unroll
     for (int i = 0; i < NA; ++i) {
-      const int gi = i * 8 + w, ra = (gi / WMT) * (WMT * 16) + h * (WMT * 8) + (gi % WMT) * 8;
+      const int ra = nt8p_row_group<WMT>(h, i, w);
       int64_t am = m0 + ra + sr; if (am > g.M - 1) am = g.M - 1;
       if (EMB && g.arow_idx) am = g.arow_idx[am];  // gathered input rows (the rows of a tile are the same for every K-tile: one lookup per lane)
       pa[h][i] = g.A + am * g.lda + sc; la[h][i] = ra * 128;
@@ -477,7 +546,7 @@ __global__ __launch_bounds__(512, (WMT * WNT <= 8 ? 4 : 2)) void gemm_nt8p_kerne
     }
 #pragma unroll
     for (int i = 0; i < NB; ++i) {
-      const int gi = i * 8 + w, rb = (gi / WNT) * (WNT * 16) + h * (WNT * 8) + (gi % WNT) * 8;
+      const int rb = nt8p_row_group<WNT>(h, i, w);
       int bn = n0 + rb + sr; if (bn > g.N - 1) bn = g.N - 1;
       pb[h][i] = g.Bt + (int64_t)bn * g.ldb + sc; lb[h][i] = BOFF + rb * 128;
     }
@@ -505,7 +574,6 @@ __global__ __launch_bounds__(512, (WMT * WNT <= 8 ? 4 : 2)) void gemm_nt8p_kerne
 #pragma unroll
     for (int j = 0; j < WNT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int nt = g.K / 64;
-  constexpr int NKT = 2 * NA + 2 * NB;  // LDS-DMA per thread per K-tile
   stageA(0, 0); stageB(0, 0); stageB(1, 0);
   if (nt > 1) { stageA(1, 1); stageB(0, 1); stageB(1, 1); NT8P_WAIT_VM(NKT); }
   else NT8P_WAIT_VM(0);
@@ -513,82 +581,7 @@ __global__ __launch_bounds__(512, (WMT * WNT <= 8 ? 4 : 2)) void gemm_nt8p_kerne
   if (wr == 1) NT8P_BAR();    // the stagger: wave-row 1 runs one barrier behind
   const int a_off = (wr * WMT * 16 + fr) * 128, b_off = BOFF + (wc * WNT * 16 + fr) * 128;
   const int x0 = ((fq) ^ (fr & 7)) * 16, x1 = ((4 + fq) ^ (fr & 7)) * 16;
-  bf16x8 aq[HM][2], bq0[HN][2], bq1[HN][2];
-#define NT8P_MFMA(AI, BJ, BQ)                                                                                                         \
-  __builtin_amdgcn_s_setprio(1);                                                                                                      \
-  _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) _Pragma("unroll") for (int i = 0; i < HM; ++i) _Pragma("unroll") for (int j = 0; j < HN; ++j) \
-      acc[(AI) + i][(BJ) + j] = MFMA16(BQ[j][ks], aq[i][ks], acc[(AI) + i][(BJ) + j]);       \
-  __builtin_amdgcn_s_setprio(0);
-  int aslot = 0, aslot2 = 2;  // ring slots of K-tiles t and t+2
-  for (int t = 0; t < nt; ++t) {
-    const char* sa = smem + aslot * ASLOT;
-    const char* sb = smem + (t & 1) * BBUF;
-    if constexpr (COARSE) {
-      // two phases per K-tile (2 HM HN x 2 MFMAs per barrier pair): one wave-row's MFMA section covers the other's reads and their
-      // LDS latency.  Every read is retired BEFORE its phase's first barrier, so a slot may be restaged one phase later.
-      // ---------------- PA: B-q0, B-q1 (retired first), A-q0 | stage A(t+2) | quadrants (0,0) (0,1)
-#pragma unroll
-      for (int j = 0; j < HN; ++j) { bq0[j][0] = *(const bf16x8*)(sb + b_off + j * 2048 + x0); bq0[j][1] = *(const bf16x8*)(sb + b_off + j * 2048 + x1); }
-#pragma unroll
-      for (int j = 0; j < HN; ++j) { bq1[j][0] = *(const bf16x8*)(sb + b_off + (HN + j) * 2048 + x0); bq1[j][1] = *(const bf16x8*)(sb + b_off + (HN + j) * 2048 + x1); }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int i = 0; i < HM; ++i) { aq[i][0] = *(const bf16x8*)(sa + a_off + i * 2048 + x0); aq[i][1] = *(const bf16x8*)(sa + a_off + i * 2048 + x1); }
-      if (t + 2 < nt) stageA(t + 2, aslot2);
-      NT8P_WAIT_LGKM(2 * HM);
-      NT8P_BAR();
-      NT8P_WAIT_LGKM(0);
-      NT8P_MFMA(0, 0, bq0)
-      NT8P_MFMA(0, HN, bq1)
-      NT8P_BAR();
-      // ---------------- PB: A-q1 (retired before the barrier) | stage B-h0(t+2), B-h1(t+2) | wait K-tile t+1 | quadrants (1,1) (1,0)
-#pragma unroll
-      for (int i = 0; i < HM; ++i) { aq[i][0] = *(const bf16x8*)(sa + a_off + (HM + i) * 2048 + x0); aq[i][1] = *(const bf16x8*)(sa + a_off + (HM + i) * 2048 + x1); }
-      if (t + 2 < nt) { stageB(0, t + 2); stageB(1, t + 2); NT8P_WAIT_VM(NKT); }
-      else NT8P_WAIT_VM(0);
-      NT8P_WAIT_LGKM(0);
-      NT8P_BAR();
-      NT8P_MFMA(HM, HN, bq1)
-      NT8P_MFMA(HM, 0, bq0)
-      NT8P_BAR();
-    } else {
-    // ---------------- P0
-#pragma unroll
-    for (int j = 0; j < HN; ++j) { bq0[j][0] = *(const bf16x8*)(sb + b_off + j * 2048 + x0); bq0[j][1] = *(const bf16x8*)(sb + b_off + j * 2048 + x1); }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int i = 0; i < HM; ++i) { aq[i][0] = *(const bf16x8*)(sa + a_off + i * 2048 + x0); aq[i][1] = *(const bf16x8*)(sa + a_off + i * 2048 + x1); }
-    if (t + 2 < nt) stageA(t + 2, aslot2);
-    NT8P_WAIT_LGKM(2 * HM);  // the B-q0 reads have returned: B-h0 may be restaged one phase from now
-    NT8P_BAR();
-    NT8P_WAIT_LGKM(0);
-    NT8P_MFMA(0, 0, bq0)
-    NT8P_BAR();
-    // ---------------- P1
-#pragma unroll
-    for (int j = 0; j < HN; ++j) { bq1[j][0] = *(const bf16x8*)(sb + b_off + (HN + j) * 2048 + x0); bq1[j][1] = *(const bf16x8*)(sb + b_off + (HN + j) * 2048 + x1); }
-    if (t + 2 < nt) stageB(0, t + 2);
-    NT8P_BAR();
-    NT8P_WAIT_LGKM(0);
-    NT8P_MFMA(0, HN, bq1)
-    NT8P_BAR();
-    // ---------------- P2
-#pragma unroll
-    for (int i = 0; i < HM; ++i) { aq[i][0] = *(const bf16x8*)(sa + a_off + (HM + i) * 2048 + x0); aq[i][1] = *(const bf16x8*)(sa + a_off + (HM + i) * 2048 + x1); }
-    NT8P_BAR();
-    NT8P_WAIT_LGKM(0);
-    NT8P_MFMA(HM, HN, bq1)
-    NT8P_BAR();
-    // ---------------- P3
-    if (t + 2 < nt) { stageB(1, t + 2); NT8P_WAIT_VM(NKT); }  // K-tile t+1 has landed (this wave's part); t+2 stays in flight
-    else NT8P_WAIT_VM(0);
-    NT8P_BAR();
-    NT8P_MFMA(HM, 0, bq0)
-    NT8P_BAR();
-    }
-    aslot = aslot == 2 ? 0 : aslot + 1; aslot2 = aslot2 == 2 ? 0 : aslot2 + 1;
-  }
-#undef NT8P_MFMA
+  nt8p_kloop<WMT, WNT, false>(acc, smem, nt, a_off, b_off, x0, x1, stageA, stageB);
   if (wr == 0) NT8P_BAR();  // pairs with wave-row 1's extra barrier
   // ---- epilogue through wave-private LDS (the K-loop's buffers are dead: every wave has passed the final barrier).
   // Region per wave: [8 WMT rows][4 WNT chunks of 16 B] f32 (16 KiB / 12 KiB), chunk index swizzled with the row so that both the
@@ -647,8 +640,7 @@ __global__ __launch_bounds__(512, (WMT * WNT <= 8 ? 4 : 2)) void gemm_nt8p_kerne
     const int gn = n0 + wc * (WNT * 16) + c8 * 8;
 #pragma unroll
     for (int r = 0; r < 8; ++r) bv[it][r] = 0.f;
-    if (g.bias && gn < g.N) { const float4 b0 = *(const float4*)(g.bias + gn), b1 = *(const float4*)(g.bias + gn + 4);
-      bv[it][0] = b0.x; bv[it][1] = b0.y; bv[it][2] = b0.z; bv[it][3] = b0.w; bv[it][4] = b1.x; bv[it][5] = b1.y; bv[it][6] = b1.z; bv[it][7] = b1.w; }
+    if (g.bias && gn < g.N) load_bias8(g.bias, gn, bv[it]);
   }
   float wv[EMB ? NBV : 1][8];  // rank-1 column weights
   if constexpr (EMB)
@@ -658,8 +650,7 @@ __global__ __launch_bounds__(512, (WMT * WNT <= 8 ? 4 : 2)) void gemm_nt8p_kerne
     const int gn = n0 + wc * (WNT * 16) + c8 * 8;
 #pragma unroll
     for (int r = 0; r < 8; ++r) wv[it][r] = 0.f;
-    if (g.r1_x && gn < g.N) { const float4 b0 = *(const float4*)(g.r1_w + gn), b1 = *(const float4*)(g.r1_w + gn + 4);
-      wv[it][0] = b0.x; wv[it][1] = b0.y; wv[it][2] = b0.z; wv[it][3] = b0.w; wv[it][4] = b1.x; wv[it][5] = b1.y; wv[it][6] = b1.z; wv[it][7] = b1.w; }
+    if (g.r1_x && gn < g.N) load_bias8(g.r1_w, gn, wv[it]);
   }
 #pragma unroll
   for (int half = 0; half < 2; ++half) {
@@ -698,10 +689,9 @@ template <int WMT, int WNT, bool EMB = false>
 static void launch_nt8p(spa3d_ctx* c, const NtArgs& g) {
   NtArgs g2 = g; g2.tiles_m = (int)((g.M + 32 * WMT - 1) / (32 * WMT)); g2.tiles_n = g.N / (64 * WNT);
   const int64_t b2 = (int64_t)((g2.tiles_m + 7) / 8) * 8 * g2.tiles_n;
-  static bool attr = false;
-  constexpr int LDS = (3 * 32 * WMT + 2 * 64 * WNT) * 128;  // 160 KiB <8,4>, 144 KiB <4,6>
-  if (!attr) { (void)hipFuncSetAttribute((const void*)gemm_nt8p_kernel<WMT, WNT, false, EMB>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); attr = true; }
-  gemm_nt8p_kernel<WMT, WNT, false, EMB><<<(unsigned)b2, 512, LDS, c->stream>>>(g2);
+  constexpr int LDS = Nt8pGeom<WMT, WNT>::LDS;
+  set_max_lds<gemm_nt8p_kernel<WMT, WNT, EMB>, LDS>();
+  gemm_nt8p_kernel<WMT, WNT, EMB><<<(unsigned)b2, 512, LDS, c->stream>>>(g2);
 }
 
 // =================================================================================================================
@@ -714,8 +704,8 @@ static void launch_nt8p(spa3d_ctx* c, const NtArgs& g) {
 // =================================================================================================================
 template <int WMT, int WNT, bool COARSE, bool AUX>
 __global__ __launch_bounds__(512, 2) void gemm_nt8pp_kernel(NtArgs g) {
-  constexpr int BM = 32 * WMT, BN = 64 * WNT, NA = WMT / 4, NB = WNT / 2, HM = WMT / 2, HN = WNT / 2;  // <8,4>: 256x256, <4,6>: 128x384
-  constexpr int ASLOT = BM * 128, BBUF = BN * 128, BOFF = 3 * ASLOT, NKT = 2 * NA + 2 * NB;
+  using G = Nt8pGeom<WMT, WNT>;
+  constexpr int BM = G::BM, BN = G::BN, NA = G::NA, NB = G::NB, ASLOT = G::ASLOT, BBUF = G::BBUF, BOFF = G::BOFF, NKT = G::NKT;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int xcd = blockIdx.x & 7, cu_slot = blockIdx.x >> 3, nslot = gridDim.x >> 3;
   const int per_xcd = ((g.tiles_m + 7) / 8) * g.tiles_n;  // tile list of one XCD (entries with tm >= tiles_m are skipped)
@@ -732,17 +722,13 @@ __global__ __launch_bounds__(512, 2) void gemm_nt8pp_kernel(NtArgs g) {
   // One lane-offset VGPR per operand: (row-in-group * ld + swizzled column) * 2.  The 8-row group of each LDS-DMA is wave-uniform and
   // goes into the scalar base; on the M edge the GROUP is clamped (M % 8 == 0 on the host: a group is valid or invalid as a whole, and
   // an invalid one only feeds accumulator rows that are never stored).
-  int rga[1][2][NA], rgb[1][2][NB];  // row groups (uniform)
+  int rga[2][NA], rgb[2][NB];  // row groups (uniform)
 #pragma unroll
-  for (int v = 0; v < 1; ++v) {
-    const int vw = w;
+  for (int h = 0; h < 2; ++h) {
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
+    for (int i = 0; i < NA; ++i) rga[h][i] = nt8p_row_group<WMT>(h, i, w);
 #pragma unroll
-      for (int i = 0; i < NA; ++i) { const int gi = i * 8 + vw; rga[v][h][i] = (gi / WMT) * (WMT * 16) + h * (WMT * 8) + (gi % WMT) * 8; }
-#pragma unroll
-      for (int i = 0; i < NB; ++i) { const int gi = i * 8 + vw; rgb[v][h][i] = (gi / WNT) * (WNT * 16) + h * (WNT * 8) + (gi % WNT) * 8; }
-    }
+    for (int i = 0; i < NB; ++i) rgb[h][i] = nt8p_row_group<WNT>(h, i, w);
   }
   const unsigned oal = (unsigned)(sr * g.lda + sc) * 2u, obl = (unsigned)(sr * g.ldb + sc) * 2u;
   const int64_t lda2 = g.lda * 2, ldb2 = g.ldb * 2;
@@ -758,13 +744,13 @@ __global__ __launch_bounds__(512, 2) void gemm_nt8pp_kernel(NtArgs g) {
 #pragma unroll
     for (int h = 0; h < 2; ++h)
 #pragma unroll
-      for (int i = 0; i < NA; ++i) { const int rg = rga[0][h][i] < maxgrp ? rga[0][h][i] : maxgrp; glds16_s(src + rg * lda2, oal, base + rga[0][h][i] * 128); }
+      for (int i = 0; i < NA; ++i) { const int rg = rga[h][i] < maxgrp ? rga[h][i] : maxgrp; glds16_s(src + rg * lda2, oal, base + rga[h][i] * 128); }
   };
   auto stageB = [&](int h, int kt) {
     char* base = smem + (kt & 1) * BBUF + BOFF;
     const char* src = baseB + kt * 128;
 #pragma unroll
-    for (int i = 0; i < NB; ++i) glds16_s(src + rgb[0][h][i] * ldb2, obl, base + rgb[0][h][i] * 128);
+    for (int i = 0; i < NB; ++i) glds16_s(src + rgb[h][i] * ldb2, obl, base + rgb[h][i] * 128);
   };
   auto prologue = [&]() { stageA(0, 0); stageB(0, 0); stageB(1, 0); stageA(1, 1); stageB(0, 1); stageB(1, 1); };
 
@@ -786,78 +772,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt8pp_kernel(NtArgs g) {
     for (int i = 0; i < WMT; ++i)
 #pragma unroll
       for (int j = 0; j < WNT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    bf16x8 aq[HM][2], bq0[HN][2], bq1[HN][2];
-#define NT8P_MFMA(AI, BJ, BQ)                                                                                                         \
-  __builtin_amdgcn_s_setprio(1);                                                                                                      \
-  _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) _Pragma("unroll") for (int i = 0; i < HM; ++i) _Pragma("unroll") for (int j = 0; j < HN; ++j) \
-      acc[(AI) + i][(BJ) + j] = MFMA16(BQ[j][ks], aq[i][ks], acc[(AI) + i][(BJ) + j]);       \
-  __builtin_amdgcn_s_setprio(0);
-    int aslot = 0, aslot2 = 2;
-    for (int t = 0; t < nt; ++t) {
-      const char* sa = smem + aslot * ASLOT;
-      const char* sb = smem + (t & 1) * BBUF;
-      if constexpr (COARSE) {
-        // two phases per K-tile, 32 MFMAs (512 cycles) per barrier pair: one wave-row's MFMA section covers the other's 16 reads and
-        // their LDS latency.  Every read is retired BEFORE its phase's first barrier, so a slot may be restaged one phase later.
-        // ---------------- PA: B-q0, B-q1 (retired first), A-q0 | stage A(t+2) | quadrants (0,0) (0,1)
-#pragma unroll
-        for (int j = 0; j < HN; ++j) { bq0[j][0] = *(const bf16x8*)(sb + b_off + j * 2048 + x0); bq0[j][1] = *(const bf16x8*)(sb + b_off + j * 2048 + x1); }
-#pragma unroll
-        for (int j = 0; j < HN; ++j) { bq1[j][0] = *(const bf16x8*)(sb + b_off + (HN + j) * 2048 + x0); bq1[j][1] = *(const bf16x8*)(sb + b_off + (HN + j) * 2048 + x1); }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < HM; ++i) { aq[i][0] = *(const bf16x8*)(sa + a_off + i * 2048 + x0); aq[i][1] = *(const bf16x8*)(sa + a_off + i * 2048 + x1); }
-        if (t + 2 < nt) stageA(t + 2, aslot2);   // slot of K-tile t-1: its A-q1 reads were retired before the previous phase's barrier
-        NT8P_WAIT_LGKM(2 * HM);                  // the B reads have returned: both B halves may be restaged next phase
-        NT8P_BAR();
-        NT8P_WAIT_LGKM(0);
-        NT8P_MFMA(0, 0, bq0)
-        NT8P_MFMA(0, HN, bq1)
-        NT8P_BAR();
-        // ---------------- PB: A-q1 (retired before the barrier) | stage B-h0(t+2), B-h1(t+2) | wait K-tile t+1 | quadrants (1,1) (1,0)
-#pragma unroll
-        for (int i = 0; i < HM; ++i) { aq[i][0] = *(const bf16x8*)(sa + a_off + (HM + i) * 2048 + x0); aq[i][1] = *(const bf16x8*)(sa + a_off + (HM + i) * 2048 + x1); }
-        if (t + 2 < nt) { stageB(0, t + 2); stageB(1, t + 2); NT8P_WAIT_VM(NKT); }
-        else NT8P_WAIT_VM(0);
-        NT8P_WAIT_LGKM(0);
-        NT8P_BAR();
-        NT8P_MFMA(HM, HN, bq1)
-        NT8P_MFMA(HM, 0, bq0)
-        NT8P_BAR();
-      } else {
-#pragma unroll
-      for (int j = 0; j < HN; ++j) { bq0[j][0] = *(const bf16x8*)(sb + b_off + j * 2048 + x0); bq0[j][1] = *(const bf16x8*)(sb + b_off + j * 2048 + x1); }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int i = 0; i < HM; ++i) { aq[i][0] = *(const bf16x8*)(sa + a_off + i * 2048 + x0); aq[i][1] = *(const bf16x8*)(sa + a_off + i * 2048 + x1); }
-      if (t + 2 < nt) stageA(t + 2, aslot2);
-      NT8P_WAIT_LGKM(2 * HM);
-      NT8P_BAR();
-      NT8P_WAIT_LGKM(0);
-      NT8P_MFMA(0, 0, bq0)
-      NT8P_BAR();
-#pragma unroll
-      for (int j = 0; j < HN; ++j) { bq1[j][0] = *(const bf16x8*)(sb + b_off + (HN + j) * 2048 + x0); bq1[j][1] = *(const bf16x8*)(sb + b_off + (HN + j) * 2048 + x1); }
-      if (t + 2 < nt) stageB(0, t + 2);
-      NT8P_BAR();
-      NT8P_WAIT_LGKM(0);
-      NT8P_MFMA(0, HN, bq1)
-      NT8P_BAR();
-#pragma unroll
-      for (int i = 0; i < HM; ++i) { aq[i][0] = *(const bf16x8*)(sa + a_off + (HM + i) * 2048 + x0); aq[i][1] = *(const bf16x8*)(sa + a_off + (HM + i) * 2048 + x1); }
-      NT8P_BAR();
-      NT8P_WAIT_LGKM(0);
-      NT8P_MFMA(HM, HN, bq1)
-      NT8P_BAR();
-      if (t + 2 < nt) { stageB(1, t + 2); NT8P_WAIT_VM(NKT); }
-      else NT8P_WAIT_VM(0);
-      NT8P_BAR();
-      NT8P_MFMA(HM, 0, bq0)
-      NT8P_BAR();
-      }
-      aslot = aslot == 2 ? 0 : aslot + 1; aslot2 = aslot2 == 2 ? 0 : aslot2 + 1;
-    }
-#undef NT8P_MFMA
+    nt8p_kloop<WMT, WNT, COARSE>(acc, smem, nt, a_off, b_off, x0, x1, stageA, stageB);
     if (wr == 0) NT8P_BAR();  // pairs with wave-row 1's extra barrier: every LDS read of this tile is done
 
     // ---- residual / pre-activation operand of this tile first (its data is needed first), then the next tile's two K-tiles
@@ -886,9 +801,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt8pp_kernel(NtArgs g) {
       for (int it = 0; it < 2; ++it) {
 #pragma unroll
         for (int r = 0; r < 8; ++r) b8[cs][it][r] = 0.f;
-        if (g.bias) { const int gn = gn_of(cs, it); const float4 b0 = *(const float4*)(g.bias + gn), b1 = *(const float4*)(g.bias + gn + 4);
-          b8[cs][it][0] = b0.x; b8[cs][it][1] = b0.y; b8[cs][it][2] = b0.z; b8[cs][it][3] = b0.w;
-          b8[cs][it][4] = b1.x; b8[cs][it][5] = b1.y; b8[cs][it][6] = b1.z; b8[cs][it][7] = b1.w; }
+        if (g.bias) load_bias8(g.bias, gn_of(cs, it), b8[cs][it]);
 #pragma unroll
         for (int r = 0; r < 8; ++r) asm volatile("" ::"v"(b8[cs][it][r]));
       }
@@ -974,6 +887,14 @@ __global__ __launch_bounds__(512, 2) void gemm_nt8pp_kernel(NtArgs g) {
   }
 }
 
+template <int WMT, int WNT, bool COARSE>
+static void launch_nt8pp(spa3d_ctx* c, const NtArgs& g) {  // one workgroup per CU; the instance with the aux-operand epilogue when there is one
+  NtArgs g2 = g; g2.tiles_m = (int)((g.M + 32 * WMT - 1) / (32 * WMT)); g2.tiles_n = g.N / (64 * WNT);
+  constexpr int LDS = 163840;
+  if (g.aux) { set_max_lds<gemm_nt8pp_kernel<WMT, WNT, COARSE, true>, LDS>(); gemm_nt8pp_kernel<WMT, WNT, COARSE, true><<<256, 512, LDS, c->stream>>>(g2); }
+  else { set_max_lds<gemm_nt8pp_kernel<WMT, WNT, COARSE, false>, LDS>(); gemm_nt8pp_kernel<WMT, WNT, COARSE, false><<<256, 512, LDS, c->stream>>>(g2); }
+}
+
 void gemm_nt_bf16(spa3d_ctx* c, const GemmDesc& d, GemmKernel k) {
   NtArgs g;
   g.A = (const bf16_t*)d.A; g.Bt = (const bf16_t*)(d.Bt ? d.Bt : d.B); g.C = d.C; g.M = d.M; g.N = d.N; g.K = d.K; g.lda = d.sAm; g.ldb = d.Bt ? d.ldBt : d.sBn; g.ldc = d.sCm;
@@ -986,42 +907,22 @@ void gemm_nt_bf16(spa3d_ctx* c, const GemmDesc& d, GemmKernel k) {
 #endif
   g.nt_store = (!d.out_f32 && (double)d.M * d.N * 2.0 >= 512e6) ? 1 : 0;   // non-temporal stores for 16-bit outputs >= 512 MB
   const int64_t blocks = (int64_t)((g.tiles_m + 7) / 8) * 8 * g.tiles_n;
-  static bool attr_set = false;
-  if (!attr_set) { (void)hipFuncSetAttribute((const void*)gemm_nt_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 65536); attr_set = true; }
   // algorithmic bytes: A, B, C once, plus the residual / pre-activation operand read and the second (pre-activation) output
   ProfScope ps(c, PROF_GEMM_NT, 2.0 * (double)d.M * d.N * d.K,
                ((double)d.M * d.K + (double)d.K * d.N + (double)d.M * d.N * (d.out_f32 ? 2.0 : 1.0) * (d.accumulate ? 2.0 : 1.0) + (double)d.M * d.N * ((d.aux ? 1.0 : 0.0) + (d.pre_out ? 1.0 : 0.0))) * 2.0);
   ps.tag(d.M, d.N, d.K, gemm_prof_flags(k, d, 0));
   switch (k) {
     case GemmKernel::NtEmbed: g.nt_store = 0; launch_nt8p<4, 6, true>(c, g); break;
-    case GemmKernel::Nt8pp256: {
-      NtArgs g2 = g; g2.tiles_m = (int)((g.M + 255) / 256); g2.tiles_n = g.N / 256;
-      static bool attrp = false;
-      if (!attrp) {
-        (void)hipFuncSetAttribute((const void*)gemm_nt8pp_kernel<8, 4, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-        (void)hipFuncSetAttribute((const void*)gemm_nt8pp_kernel<8, 4, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-        attrp = true;
-      }
-      if (d.aux) gemm_nt8pp_kernel<8, 4, true, true><<<256, 512, 163840, c->stream>>>(g2);
-      else gemm_nt8pp_kernel<8, 4, true, false><<<256, 512, 163840, c->stream>>>(g2);
-      break;
-    }
-    case GemmKernel::Nt8pp384: {  // persistent 128x384: slower than the non-persistent kernel on a PLAIN epilogue at K = 768 (759 vs 840 TF/s), faster on every N = 384 shape of the step, whose epilogues mostly carry a residual (out-projection +19 %, MLP-out +12 %, dX shapes +1.5 %)
-      NtArgs g2 = g; g2.tiles_m = (int)((g.M + 127) / 128); g2.tiles_n = g.N / 384;
-      static bool attrq = false;
-      if (!attrq) {
-        (void)hipFuncSetAttribute((const void*)gemm_nt8pp_kernel<4, 6, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-        (void)hipFuncSetAttribute((const void*)gemm_nt8pp_kernel<4, 6, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-        attrq = true;
-      }
-      if (d.aux) gemm_nt8pp_kernel<4, 6, false, true><<<256, 512, 163840, c->stream>>>(g2);
-      else gemm_nt8pp_kernel<4, 6, false, false><<<256, 512, 163840, c->stream>>>(g2);
-      break;
-    }
+    case GemmKernel::Nt8pp256: launch_nt8pp<8, 4, true>(c, g); break;
+    // persistent 128x384: slower than the non-persistent kernel on a PLAIN epilogue at K = 768 (759 vs 840 TF/s), faster on every N = 384 shape of the step, whose epilogues mostly carry a residual (out-projection +19 %, MLP-out +12 %, dX shapes +1.5 %)
+    case GemmKernel::Nt8pp384: launch_nt8pp<4, 6, false>(c, g); break;
     case GemmKernel::Nt8p256: launch_nt8p<8, 4>(c, g); break;
     case GemmKernel::Nt8p384: launch_nt8p<4, 6>(c, g); break;
     case GemmKernel::NtOcc: gemm_nt_occ_kernel<<<(unsigned)blocks, 256, 32768, c->stream>>>(g); break;   // (+12 % at K = 384: 594 -> 667 TF/s)
-    default: gemm_nt_kernel<<<(unsigned)blocks, 256, 65536, c->stream>>>(g); break;
+    default:
+      set_max_lds<gemm_nt_kernel, 65536>();
+      gemm_nt_kernel<<<(unsigned)blocks, 256, 65536, c->stream>>>(g);
+      break;
   }
   SPA_LAUNCH_CHECK(c);
 }
@@ -1165,21 +1066,22 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(TnArgs g) {
 // TN, 8-phase form.  Output tile (64 WIT) x (128 WNT) with WIT + 2 WNT = 8: <4,2> = 256x256, <2,3> = 128x384, <6,1> = 384x128
 // (the 384-wide weight dimensions of the model fit without padding).  8 waves as 2 (i) x 4 (n), 32x32x16 MFMA.
 //   The reduction runs over "quarters" of 16 rows of m.  One quarter in LDS = four [16 rows][128 columns] sub-images (A's, then
-//   B's) in the transposed-read layout above = 16 KiB = 2 LDS-DMA per thread.  Phase q:
-//       12 (11 / 14) ds_read_b64_tr_b16 pairs of quarter q | 2 LDS-DMA of quarter q+8 | s_waitcnt vmcnt(14) (quarter q+1 landed)
-//       s_barrier | lgkmcnt(0) | 8 (6) MFMA | s_barrier
-//   Ring of 10 quarters = 160 KiB: quarter q+8 takes the slot of quarter q-2, two phases after its last read; both operands are
-//   streamed from HBM and get an 8-phase lead.  Wave-row 1 runs one barrier behind wave-row 0 (one wave of each per SIMD), so
-//   one reads/stages while the other issues MFMAs.  Hazard rules as in the NT kernel (cdna_hip_programming.md, 8-phase template).
+//   B's) in the transposed-read layout above = 16 KiB = 2 LDS-DMA per thread.  A phase takes QP = 2 quarters q, q+1:
+//       2 (WIT + WNT) = 12 (10 / 14) ds_read_b64_tr_b16 per quarter | 2 LDS-DMA each for quarters q+6, q+7 |
+//       s_waitcnt vmcnt(2 (D - QP) = 8) (quarters q+2, q+3 landed, four stay in flight) | s_barrier | lgkmcnt(0) |
+//       2 WIT WNT = 16 (12) MFMA | s_barrier
+//   16 MFMAs (512 cycles) between barrier pairs, so one wave-row's MFMA section covers the other's 24 transposed reads and their LDS
+//   latency (one quarter per phase left the read/stage section the longer one: ~46 % MFMA-busy, +7-10 % for two: NOTEBOOK.md, "How
+//   the GEMMs got ...", item 5).
+//   Ring of R = 10 quarters = 160 KiB, lead D = 6: quarter q+6 takes the slot of quarter q-4, last read two phases ago; both operands
+//   are streamed from HBM.  Wave-row 1 runs one barrier behind wave-row 0 (one wave of each per SIMD), so one reads/stages while the
+//   other issues MFMAs.  Hazard rules as in the NT kernel (cdna_hip_programming.md, 8-phase template).
 // =================================================================================================================
-// QP = quarters per phase.  QP = 2: 16 MFMAs (512 cycles) between barrier pairs instead of 8, so one wave-row's MFMA section covers
-// the other's 24 transposed reads and their LDS latency (with QP = 1 the read/stage section is the longer one: ~46 % MFMA-busy);
-// the lead shrinks to 6 quarters (the slot of quarter q+6 was last read two phases ago).
-template <int WIT, int WNT, int QP>
+template <int WIT, int WNT>
 __global__ __launch_bounds__(512, 2) void gemm_tn8p_kernel(TnArgs g) {
   constexpr int TI = 64 * WIT, TNN = 128 * WNT, NSA = TI / 128;
   static_assert(TI / 128 + TNN / 128 == 4, "four sub-images per quarter");
-  constexpr int R = 10, D = QP == 1 ? 8 : 6, QB = 16384;
+  constexpr int QP = 2, R = 10, D = 6, QB = 16384;  // quarters per phase, ring slots, lead in quarters, bytes per quarter
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int xcd = blockIdx.x & 7; int jb = blockIdx.x >> 3;
   const int ntile = g.tiles_i * g.tiles_n;
@@ -1362,38 +1264,28 @@ __global__ __launch_bounds__(512, 2) void gemm_tn8p_kernel(TnArgs g) {
     }
 }
 
-template <int WIT, int WNT, int QP>
-static void launch_tn8p_q(spa3d_ctx* c, TnArgs g, int rounds) {
+template <int WIT, int WNT>
+static void launch_tn8p(spa3d_ctx* c, TnArgs g) {
   constexpr int TI = 64 * WIT, TNN = 128 * WNT;
   g.tiles_i = (g.Ki + TI - 1) / TI; g.tiles_n = (g.N + TNN - 1) / TNN;
   const int64_t tiles = (int64_t)g.tiles_i * g.tiles_n;
   // M-splits: one workgroup per CU, equal-length splits.  Pick the count that minimises a makespan model:
   //   rounds on the fullest XCD x (M / s) rows x (time per row at ~4 TF/s per CU)  +  s x (Ki x N x 4 B of f32 atomics at ~1.3 TB/s)
-  int64_t splits;
-  if (rounds > 0) splits = std::max<int64_t>(8, (256 * (int64_t)rounds / tiles) / 8 * 8);
-  else {
-    const double t_row = 2.0 * TI * TNN / 4.0e12, t_atom = (double)g.Ki * g.N * 4.0 / 1.3e12;
-    const int64_t smax = std::max<int64_t>(1, std::min<int64_t>(g.M / 4096, 2048));
-    double best = 1e30; splits = 1;
-    for (int64_t sc = 1; sc <= smax; ++sc) {
-      const int64_t rps_c = ((g.M + sc - 1) / sc + 63) / 64 * 64;
-      const int64_t per_xcd = tiles * ((sc + 7) / 8);  // all tiles of a split run on one XCD (32 CUs), splits are dealt round-robin
-      const double t = (double)((per_xcd + 31) / 32) * (double)rps_c * t_row + (double)sc * t_atom;
-      if (t < best * 0.999) { best = t; splits = sc; }
-    }
+  const double t_row = 2.0 * TI * TNN / 4.0e12, t_atom = (double)g.Ki * g.N * 4.0 / 1.3e12;
+  const int64_t smax = std::max<int64_t>(1, std::min<int64_t>(g.M / 4096, 2048));
+  double best = 1e30; int64_t splits = 1;
+  for (int64_t sc = 1; sc <= smax; ++sc) {
+    const int64_t rps_c = ((g.M + sc - 1) / sc + 63) / 64 * 64;
+    const int64_t per_xcd = tiles * ((sc + 7) / 8);  // all tiles of a split run on one XCD (32 CUs), splits are dealt round-robin
+    const double t = (double)((per_xcd + 31) / 32) * (double)rps_c * t_row + (double)sc * t_atom;
+    if (t < best * 0.999) { best = t; splits = sc; }
   }
   splits = std::min<int64_t>(splits, std::max<int64_t>(1, g.M / 4096));
   int64_t rps = ((g.M + splits - 1) / splits + 63) / 64 * 64;
   splits = (g.M + rps - 1) / rps;
   g.splits = (int)splits; g.rows_per_split = rps;
-  static bool attr = false;
-  if (!attr) { (void)hipFuncSetAttribute((const void*)gemm_tn8p_kernel<WIT, WNT, QP>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840); attr = true; }
-  gemm_tn8p_kernel<WIT, WNT, QP><<<(unsigned)(tiles * ((splits + 7) / 8 * 8)), 512, 163840, c->stream>>>(g);
-}
-
-template <int WIT, int WNT>
-static void launch_tn8p(spa3d_ctx* c, const TnArgs& g, int rounds) {
-  launch_tn8p_q<WIT, WNT, 2>(c, g, rounds);  // two quarters per phase (+7-10 % over one: NOTEBOOK.md, "How the GEMMs got ...", item 5)
+  set_max_lds<gemm_tn8p_kernel<WIT, WNT>, 163840>();
+  gemm_tn8p_kernel<WIT, WNT><<<(unsigned)(tiles * ((splits + 7) / 8 * 8)), 512, 163840, c->stream>>>(g);
 }
 
 void gemm_tn_bf16(spa3d_ctx* c, const GemmDesc& d, GemmKernel k) {
@@ -1408,11 +1300,10 @@ void gemm_tn_bf16(spa3d_ctx* c, const GemmDesc& d, GemmKernel k) {
   if (k != GemmKernel::Tn) {
     ProfScope ps(c, PROF_GEMM_TN, 2.0 * (double)M * Ki * N, ((double)M * Ki + (double)M * N) * 2.0);
     ps.tag(M, N, Ki, gemm_prof_flags(k, d, 0));
-    const int rounds = 0;  // 8-phase kernels: M-split count from the makespan model
     if (k == GemmKernel::Tnb) gemm_tnb(c, g);
-    else if (k == GemmKernel::Tn8p256) launch_tn8p<4, 2>(c, g, rounds);
-    else if (k == GemmKernel::Tn8p128x384) launch_tn8p<2, 3>(c, g, rounds);
-    else launch_tn8p<6, 1>(c, g, rounds);
+    else if (k == GemmKernel::Tn8p256) launch_tn8p<4, 2>(c, g);
+    else if (k == GemmKernel::Tn8p128x384) launch_tn8p<2, 3>(c, g);
+    else launch_tn8p<6, 1>(c, g);
     SPA_LAUNCH_CHECK(c);
     return;
   }
@@ -1426,8 +1317,7 @@ void gemm_tn_bf16(spa3d_ctx* c, const GemmDesc& d, GemmKernel k) {
   int64_t rps = ((M + splits - 1) / splits + 63) / 64 * 64;
   splits = (M + rps - 1) / rps;
   g.splits = (int)splits; g.rows_per_split = rps;
-  static bool attr_set = false;
-  if (!attr_set) { (void)hipFuncSetAttribute((const void*)gemm_tn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 65536); attr_set = true; }
+  set_max_lds<gemm_tn_kernel, 65536>();
   ProfScope ps(c, PROF_GEMM_TN, 2.0 * (double)M * Ki * N, ((double)M * Ki + (double)M * N) * 2.0 + (double)Ki * N * 4.0 * splits);
   ps.tag(M, N, Ki, gemm_prof_flags(k, d, splits));
   gemm_tn_kernel<<<(unsigned)(tiles * ((splits + 7) / 8 * 8)), 256, 65536, c->stream>>>(g);

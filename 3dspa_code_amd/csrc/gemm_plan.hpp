@@ -46,7 +46,7 @@ struct GemmDesc {
 
 // every kernel a GEMM can run on.  Refuse: none the policy allows takes it (the model falls back, ops return SPA3D_ERR_ARG); Generic:
 // gemm_generic_kernel<T>.  NT (C = A . B): gemm_rs_kernel<false / true (EPI_MUL_GELU_GRAD)> on rs_pk; gemm_ntb_kernel<4,6,.> (384 | N) / <6,4,.> on
-// ntb_pk; mlp_fused_fwd_kernel (plan_mlp); gemm_nt8p_kernel<4,6,.,EMB=true> (one-pass embedding); gemm_nt8pp_kernel<8,4,..> / <4,6,..> (persistent
+// ntb_pk; mlp_fused_fwd_kernel (plan_mlp); gemm_nt8p_kernel<4,6,EMB=true> (one-pass embedding); gemm_nt8pp_kernel<8,4,..> / <4,6,..> (persistent
 // 256 x 256 / 128 x 384); gemm_nt8p_kernel<8,4> / <4,6>; gemm_nt_occ_kernel; gemm_nt_kernel.  dW (C += A^T . B): gemm_tnb_kernel (+ gemm_tn_tail_kernel);
 // gemm_tn8p_kernel<4,2> / <2,3> / <6,1> (256 x 256 / 128 x 384 / 384 x 128 tiles); gemm_tn_kernel.
 enum class GemmKernel { Refuse, Generic, Rs, Ntb, MlpFused, NtEmbed, Nt8pp256, Nt8pp384, Nt8p256, Nt8p384, NtOcc, Nt,
