@@ -138,6 +138,14 @@ _SIGS = {
     'spa3d_op_attention_bwd': (C.c_int, [C.c_void_p] * 3 + [C.c_int64] * 3 + [C.c_void_p] * 3 + [C.c_int64]
                                + [C.c_int32] * 4 + [C.c_void_p] * 8 + [C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
                                                                        C.c_void_p]),
+    'spa3d_op_attention_ragged': (C.c_int, [C.c_void_p] * 3 + [C.c_int64] * 3 + [C.c_void_p] * 3 + [C.POINTER(C.c_int32), C.c_int64] + [C.c_int32] * 3
+                                  + [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    'spa3d_op_attention_ragged_bwd': (C.c_int, [C.c_void_p] * 3 + [C.c_int64] * 3 + [C.c_void_p] * 3 + [C.POINTER(C.c_int32), C.c_int64] + [C.c_int32] * 3
+                                      + [C.c_void_p] * 8 + [C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    'spa3d_op_attention_varlen': (C.c_int, [C.c_void_p] * 3 + [C.c_int64] * 3 + [C.c_void_p] * 2 + [C.POINTER(C.c_int32), C.c_int64] + [C.c_int32] * 3
+                                  + [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    'spa3d_op_attention_varlen_bwd': (C.c_int, [C.c_void_p] * 3 + [C.c_int64] * 3 + [C.c_void_p] * 2 + [C.POINTER(C.c_int32), C.c_int64] + [C.c_int32] * 3
+                                      + [C.c_void_p] * 8 + [C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     'spa3d_op_attention_q1': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64]
                               + [C.c_int32] * 3 + [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     'spa3d_op_attention_q1_bwd': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64]

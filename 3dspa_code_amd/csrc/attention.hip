@@ -307,7 +307,7 @@ void attention_varlen_bwd(spa3d_ctx* c, const T* q, const T* k, const T* v, int6
   for (int64_t i = 0; i < nseq; ++i) {
     const int64_t k0 = koff_host[i];
     attention_bwd<T>(c, q + i * Sq * ldq, k + k0 * ldk, v + k0 * ldv, ldq, ldk, ldv, sq, sk, nullptr, 1, Sq, koff_host[i + 1] - koff_host[i], H, Dh,
-                     o + i * Sq * E, lse ? lse + i * H * Sq * 2 : nullptr, d_o + i * Sq * E, dq + i * Sq * ldq, dk + k0 * ldk, dv + k0 * ldv, dsq, dsk,
+                     o ? o + i * Sq * E : nullptr, lse ? lse + i * H * Sq * 2 : nullptr, d_o + i * Sq * E, dq + i * Sq * ldq, dk + k0 * ldk, dv + k0 * ldv, dsq, dsk,
                      impl, nullptr, 0);
   }
 }

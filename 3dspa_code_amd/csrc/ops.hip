@@ -88,6 +88,18 @@ int op_linear_bwd(OpCtx& c, const T* A, const T* B, const T* dC, T* dA, float* d
   if (dbias) { k_zero(&c, dbias, (int64_t)N * 4); k_colsum<T>(&c, dC, M, N, N, dbias); }
   return c.status();
 }
+
+// the device copy of nseq + 1 host offsets at the front of the workspace, then `body` (which reads *dev) once dry for its peak and once for real
+template <typename F> static int op_with_offsets(OpCtx& c, const int32_t* host, int64_t nseq, const int32_t** dev, F&& body) {
+  int32_t* d = c.alloc<int32_t>(nseq + 1);
+  if (c.ar.overflow) return SPA3D_ERR_WORKSPACE;
+  *dev = d;
+  const int64_t used = c.ar.off;
+  if (used + arena_peak(&c, body) + 256 > c.ar.cap) return SPA3D_ERR_WORKSPACE;
+  k_set_i32(&c, d, host, nseq + 1);
+  body();
+  return c.status();
+}
 }  // namespace
 }  // namespace SPA_NS
 
@@ -226,6 +238,101 @@ SPA3D_OP(spa3d_op_attention_bwd)(const void* q, const void* k, const void* v, in
   OP_BY_DTYPE(dtype, attention_bwd<T>(&c, (const T*)q, (const T*)k, (const T*)v, ldq, ldk, ldv, scale_q, scale_k, keymask, nseq, Sq, Sk, H, Dh, (const T*)o, lse,
                                       (const T*)d_o, (T*)dq, (T*)dk, (T*)dv, dscale_q, dscale_k, c.attn_impl));
   return c.status();
+}
+
+// ---- The two ragged forms of the fused attention on their own (tests/test_gpu_attn_ragged.py).  Offsets are HOST arrays: checked first, then copied into the
+// workspace (k_set_i32).  Whatever a launcher would record as a HIP-class error ("ragged sequences need the fused attention kernels", a shape the fused
+// kernels decline under impl 2) is an argument error here and launches nothing; the workspace is sized by a dry walk before the first launch.
+static bool ragged_args_ok(const void* const* ptrs, int np, const int32_t* seq_off, int64_t nseq, int64_t ldq, int64_t ldk, int64_t ldv, int32_t S, int32_t H,
+                           int32_t Dh, int32_t dtype, int32_t impl) {
+  if (!seq_off || dtype != OP_DT16 || Dh != 96 || S < 2 || S > 320 || H < 1 || nseq < 1 || nseq > (1 << 20) || nseq * H > 0x7fffffffLL) return false;
+  if (impl != 0 && impl != 2 && impl != 3 && impl != 4) return false;   // 1: no generic route for ragged rows; anything else names no kernel
+  const int64_t E = (int64_t)H * Dh;   // a row stride below the row: rows of dq / dk / dv would overlap
+  if (ldq < E || ldk < E || ldv < E || ldq % 8 || ldk % 8 || ldv % 8) return false;
+  for (int i = 0; i < np; ++i)
+    if (!ptrs[i] || !op_al16(ptrs[i])) return false;   // 16-byte vector accesses on every operand
+  if (seq_off[0] < 0) return false;
+  for (int64_t i = 0; i < nseq; ++i) {  // a length outside [1, S]: an empty or decreasing pair, a sequence longer than the instance (a sum past 2^31 wraps negative)
+    const int64_t n = (int64_t)seq_off[i + 1] - seq_off[i];
+    if (n < 1 || n > S) return false;
+  }
+  return true;
+}
+static bool varlen_args_ok(const int32_t* koff, int64_t nseq, int64_t ldq, int64_t ldk, int64_t ldv, int32_t Sq, int32_t H, int32_t Dh, int32_t dtype, int32_t impl) {
+  if (!koff || !OP_DTYPE_OK(dtype) || nseq < 1 || nseq > (1 << 20) || Sq < 1 || H < 1 || Dh < 1 || Dh > 128 || impl < 0 || impl > 2) return false;
+  if (ldq < (int64_t)H * Dh || ldk < (int64_t)H * Dh || ldv < (int64_t)H * Dh) return false;
+  if (impl == 2 && (Dh != 96 || Sq > 128 || dtype == SPA3D_F32 || ldq % 8 || ldk % 8 || ldv % 8)) return false;   // what the chunked-key kernels take
+  if (koff[0] != 0) return false;
+  for (int64_t i = 0; i < nseq; ++i)
+    if ((int64_t)koff[i + 1] - koff[i] < 1) return false;   // a sequence without a key
+  return true;
+}
+SPA3D_OP(spa3d_op_attention_ragged)(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* scale_q,
+                                    const float* scale_k, const float* keymask, const int32_t* seq_off, int64_t nseq, int32_t S, int32_t H, int32_t Dh,
+                                    void* o, float* lse, int32_t dtype, int32_t impl, void* ws, int64_t ws_bytes, void* stream) {
+  FWD16(spa3d_op_attention_ragged, q, k, v, ldq, ldk, ldv, scale_q, scale_k, keymask, seq_off, nseq, S, H, Dh, o, lse, dtype, impl, ws, ws_bytes, stream)
+  const void* ptrs[] = {q, k, v, o, scale_q, scale_k};
+  if (!ragged_args_ok(ptrs, 6, seq_off, nseq, ldq, ldk, ldv, S, H, Dh, dtype, impl)) return SPA3D_ERR_ARG;
+  OpCtx c(stream, ws, ws_bytes);
+  apply_attn_impl(&c, impl);
+  const int32_t* od = nullptr;
+  return op_with_offsets(c, seq_off, nseq, &od, [&] {
+    attention_fwd<bf16_t>(&c, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv, scale_q, scale_k, keymask, nseq, S, S, H, Dh, (bf16_t*)o, lse,
+                          c.attn_impl, od, seq_off[nseq]);
+  });
+}
+SPA3D_OP(spa3d_op_attention_ragged_bwd)(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* scale_q,
+                                        const float* scale_k, const float* keymask, const int32_t* seq_off, int64_t nseq, int32_t S, int32_t H, int32_t Dh,
+                                        const void* o, const float* lse, const void* d_o, void* dq, void* dk, void* dv, float* dscale_q, float* dscale_k,
+                                        int32_t dtype, int32_t impl, void* ws, int64_t ws_bytes, void* stream) {
+  FWD16(spa3d_op_attention_ragged_bwd, q, k, v, ldq, ldk, ldv, scale_q, scale_k, keymask, seq_off, nseq, S, H, Dh, o, lse, d_o, dq, dk, dv, dscale_q, dscale_k,
+        dtype, impl, ws, ws_bytes, stream)
+  const void* ptrs[] = {q, k, v, o, d_o, dq, dk, dv, scale_q, scale_k};
+  if (!lse || !dscale_q || !dscale_k || !ragged_args_ok(ptrs, 10, seq_off, nseq, ldq, ldk, ldv, S, H, Dh, dtype, impl)) return SPA3D_ERR_ARG;
+  OpCtx c(stream, ws, ws_bytes);
+  apply_attn_impl(&c, impl);
+  const int32_t* od = nullptr;
+  return op_with_offsets(c, seq_off, nseq, &od, [&] {
+    attention_bwd<bf16_t>(&c, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv, scale_q, scale_k, keymask, nseq, S, S, H, Dh, (const bf16_t*)o,
+                          lse, (const bf16_t*)d_o, (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, dscale_q, dscale_k, c.attn_impl, od, seq_off[nseq]);
+  });
+}
+
+SPA3D_OP(spa3d_op_attention_varlen)(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* scale_q,
+                                    const float* scale_k, const int32_t* koff, int64_t nseq, int32_t Sq, int32_t H, int32_t Dh, void* o, float* lse,
+                                    int32_t dtype, int32_t impl, void* ws, int64_t ws_bytes, void* stream) {
+  FWD16(spa3d_op_attention_varlen, q, k, v, ldq, ldk, ldv, scale_q, scale_k, koff, nseq, Sq, H, Dh, o, lse, dtype, impl, ws, ws_bytes, stream)
+  if (!q || !k || !v || !o || !scale_q || !scale_k || !varlen_args_ok(koff, nseq, ldq, ldk, ldv, Sq, H, Dh, dtype, impl)) return SPA3D_ERR_ARG;
+  if (impl == 2 && !(op_al16(q) && op_al16(k) && op_al16(v) && op_al16(o))) return SPA3D_ERR_ARG;
+  OpCtx c(stream, ws, ws_bytes);
+  apply_attn_impl(&c, impl);
+  const int32_t* kd = nullptr;
+  OP_BY_DTYPE(dtype, return op_with_offsets(c, koff, nseq, &kd, [&] {
+    attention_varlen_fwd<T>(&c, (const T*)q, (const T*)k, (const T*)v, ldq, ldk, ldv, scale_q, scale_k, nseq, Sq, koff, kd, H, Dh, (T*)o, lse, c.attn_impl);
+  }));
+}
+SPA3D_OP(spa3d_op_attention_varlen_bwd)(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* scale_q,
+                                        const float* scale_k, const int32_t* koff, int64_t nseq, int32_t Sq, int32_t H, int32_t Dh, const void* o,
+                                        const float* lse, const void* d_o, void* dq, void* dk, void* dv, float* dscale_q, float* dscale_k, int32_t dtype,
+                                        int32_t impl, void* ws, int64_t ws_bytes, void* stream) {
+  FWD16(spa3d_op_attention_varlen_bwd, q, k, v, ldq, ldk, ldv, scale_q, scale_k, koff, nseq, Sq, H, Dh, o, lse, d_o, dq, dk, dv, dscale_q, dscale_k, dtype, impl,
+        ws, ws_bytes, stream)
+  if (!q || !k || !v || !d_o || !dq || !dk || !dv || !scale_q || !scale_k || !dscale_q || !dscale_k || !varlen_args_ok(koff, nseq, ldq, ldk, ldv, Sq, H, Dh, dtype, impl))
+    return SPA3D_ERR_ARG;
+  // 16-bit, impl 0 / 2: the fused backward rebuilds P from the forward's o and lse, and a sequence the single launch declines is tried on the fused kernels
+  // again -- a missing one of the two is refused here, not discovered there.  fp32 and impl 1 (the generic composition) read neither.
+  if (dtype != SPA3D_F32 && impl != 1 && (!o || !lse)) return SPA3D_ERR_ARG;
+  if (impl == 2) {
+    for (const void* p : {q, k, v, o, d_o, (const void*)dq, (const void*)dk, (const void*)dv, (const void*)scale_q, (const void*)scale_k})
+      if (!op_al16(p)) return SPA3D_ERR_ARG;
+  }
+  OpCtx c(stream, ws, ws_bytes);
+  apply_attn_impl(&c, impl);
+  const int32_t* kd = nullptr;
+  OP_BY_DTYPE(dtype, return op_with_offsets(c, koff, nseq, &kd, [&] {
+    attention_varlen_bwd<T>(&c, (const T*)q, (const T*)k, (const T*)v, ldq, ldk, ldv, scale_q, scale_k, nseq, Sq, koff, kd, H, Dh, (const T*)o, lse, (const T*)d_o,
+                            (T*)dq, (T*)dk, (T*)dv, dscale_q, dscale_k, c.attn_impl);
+  }));
 }
 
 // Single-query attention and the rank-K projection: every shape their launchers would record as a HIP-class error (or decline) is an argument error here

@@ -7,8 +7,8 @@
 //     (36 x 16-byte loads per tile, all in flight at once);
 //   * the head's 384 x 288 weight slice streams through a 4-slot LDS ring as pre-packed 1-KiB MFMA A fragments in consumption order (12 k-steps of 18 KiB;
 //     the stream is continuous across problems, so the next problem's first three k-steps land under this problem's attention phase);
-//   * C^T = W^T . nq^T accumulates as [output column][token] tiles: a lane ends with 4 consecutive columns of ONE token, so the RMSNorm row sums are in-lane
-//     plus two xor-shuffles, q | k | v leave as 8-byte pieces (they are still stored: the backward's dW GEMM and RMSNorm backward read them), the normalised
+//   * C^T = W^T . nq^T accumulates as [output column][token] tiles: a lane ends with 4 consecutive columns of ONE token, so a token's 96 columns sit in its four lanes (the RMSNorm row sums
+//     are taken in the attention kernels' order, which costs lane reads: see the epilogue), q | k | v leave as 8-byte pieces (they are still stored: the backward's dW GEMM and RMSNorm backward read them), the normalised
 //     q^ of the wave's own tokens stay in REGISTERS as the B operands of S^T = K^ Q^T (the k index of an accumulator pair is a permutation of 32 d's; the K^ image
 //     is written with its columns permuted the same way), and only K^ and V go to LDS images;
 //   * the attention tile routine of attention_fused.hip (S^T in registers, softmax in-lane, V read transposed) runs on the wave's own query tiles.
@@ -151,12 +151,30 @@ __global__ __launch_bounds__(256, 1) void qkva_fwd_kernel(QkvaArgs g) {
           for (int r = 0; r < 4; ++r) raw[j][r] = f2bf(acc[t][j][r]);
           if (valid && !(QA_ABL & 2)) *(u16x4*)(qrow + (j / 6) * E + 16 * (j % 6)) = raw[j];
         }
-        // RMSNorm over the 96 columns of the token (24 in this lane, the rest in lanes fq ^ 1, 2, 3), from the ROUNDED values, as the attention kernel does it
+        // RMSNorm over the 96 columns of the token, from the ROUNDED values and in the attention kernels' own summation order (rows_store<NORM> / frag_norm of
+        // attention_fused.hip): lane group g sums the squares of d = 32 c + 8 g + e, c = 0..2, e = 0..7, one after the other, and the four partial sums add as
+        // (p0 + p1) + (p2 + p3).  Any other order moves the rsqrt argument by an fp32 ulp now and then, and about one element of q^ / k^ in 10^5 then rounds to
+        // the other 16-bit neighbour than in the two-kernel path (|d lse| up to 3e-3 in bf16; tests/test_gpu_qkv_attn.py).  This lane holds d = 16 j + 4 fq + r, so
+        // element (c, e) of group g = fq comes from lane group 2 (fq & 1) + (e >> 2) as raw[2 c + (fq >> 1)][e & 3]: both candidates j travel, the receiver picks.
+        // 48 32-bit lane reads per token tile on top of a kernel already measured 1.47x slower than the two-kernel pair (opt-in, attn_impl 6): their cost is NOT measured.
         float ssq = 0.f, ssk = 0.f;
+        {
+          const bool jodd = (fq >> 1) != 0;
 #pragma unroll
-        for (int j = 0; j < 6; ++j)
+          for (int c = 0; c < 3; ++c)
 #pragma unroll
-          for (int r = 0; r < 4; ++r) { const float a = bf2f(raw[j][r]), b = bf2f(raw[6 + j][r]); ssq += a * a; ssk += b * b; }
+            for (int hh = 0; hh < 2; ++hh) {
+              const int src = fr + 16 * (2 * (fq & 1) + hh);
+              const uint2 qe = __builtin_bit_cast(uint2, raw[2 * c]), qo = __builtin_bit_cast(uint2, raw[2 * c + 1]);
+              const uint2 ke = __builtin_bit_cast(uint2, raw[6 + 2 * c]), ko = __builtin_bit_cast(uint2, raw[6 + 2 * c + 1]);
+              const unsigned qe0 = __shfl(qe.x, src, 64), qe1 = __shfl(qe.y, src, 64), qo0 = __shfl(qo.x, src, 64), qo1 = __shfl(qo.y, src, 64);
+              const unsigned ke0 = __shfl(ke.x, src, 64), ke1 = __shfl(ke.y, src, 64), ko0 = __shfl(ko.x, src, 64), ko1 = __shfl(ko.y, src, 64);
+              const unsigned q0w = jodd ? qo0 : qe0, q1w = jodd ? qo1 : qe1, k0w = jodd ? ko0 : ke0, k1w = jodd ? ko1 : ke1;
+              float a;
+              a = unpack_lo(q0w); ssq += a * a; a = unpack_hi(q0w); ssq += a * a; a = unpack_lo(q1w); ssq += a * a; a = unpack_hi(q1w); ssq += a * a;
+              a = unpack_lo(k0w); ssk += a * a; a = unpack_hi(k0w); ssk += a * a; a = unpack_lo(k1w); ssk += a * a; a = unpack_hi(k1w); ssk += a * a;
+            }
+        }
         ssq += __shfl_xor(ssq, 16, 64); ssq += __shfl_xor(ssq, 32, 64);
         ssk += __shfl_xor(ssk, 16, 64); ssk += __shfl_xor(ssk, 32, 64);
         const float rq = rsqrtf(ssq / DH + 1e-6f), rk = rsqrtf(ssk / DH + 1e-6f);

@@ -599,6 +599,43 @@ int spa3d_op_attention_bwd(const void* q, const void* k, const void* v, int64_t 
                            const void* d_o, void* dq, void* dk, void* dv, float* dscale_q, float* dscale_k,
                            int32_t dtype, int32_t impl, void* ws, int64_t ws_bytes, void* stream);
 
+/* The two ragged forms of the fused attention on their own (tests/test_gpu_attn_ragged.py).  The offsets are HOST arrays [nseq + 1], checked and then
+ * copied into ws; ws also holds what the kernels carve (the chunked-key partials, the generic composition's intermediates) and is sized by a dry walk
+ * before the first launch (SPA3D_ERR_WORKSPACE).  1 <= nseq <= 2^20.  Every refusal below is SPA3D_ERR_ARG and launches nothing.
+ *
+ * Ragged self-attention (token pruning in the track encoder): sequence i is rows [seq_off[i], seq_off[i + 1]) of the packed q, k, v, o (row strides
+ * ldq / ldk / ldv, o dense), 1 <= its length S_i <= S, where S (2..320) picks the kernel instance as the longest length does in the model.  lse of
+ * (sequence i, head h, token t) sits at ((seq_off[i] * H + h * S_i) + t) * 2, H * 2 floats per packed row in all.  keymask: NULL, or f32 [seq_off[nseq]]
+ * indexed by PACKED row (non-zero = keep), not [nseq, S].  16-bit dtypes and Dh = 96 only, impl 0 / 2 (3 / 4 in the backward: the split-pass structures) --
+ * there is no generic route for ragged rows, so SPA3D_F32, impl 1 and any other impl are refused, as are a NULL required pointer, H < 1, a row stride
+ * below H*Dh or no multiple of 8, a pointer off 16 bytes, seq_off[0] < 0 and a length outside [1, S]. */
+int spa3d_op_attention_ragged(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldk, int64_t ldv,
+                              const float* scale_q, const float* scale_k, const float* keymask,
+                              const int32_t* seq_off /* HOST [nseq + 1] */, int64_t nseq, int32_t S, int32_t H, int32_t Dh, void* o,
+                              float* lse /* may be NULL */, int32_t dtype, int32_t impl, void* ws, int64_t ws_bytes, void* stream);
+/* gradients of the above from the forward's o and lse (both required); dq, dk, dv strided like q, k, v; dscale_q / dscale_k f32[Dh] accumulated into */
+int spa3d_op_attention_ragged_bwd(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldk, int64_t ldv,
+                                  const float* scale_q, const float* scale_k, const float* keymask,
+                                  const int32_t* seq_off /* HOST [nseq + 1] */, int64_t nseq, int32_t S, int32_t H, int32_t Dh,
+                                  const void* o, const float* lse, const void* d_o, void* dq, void* dk, void* dv,
+                                  float* dscale_q, float* dscale_k, int32_t dtype, int32_t impl, void* ws, int64_t ws_bytes, void* stream);
+/* Cross attention against ragged key sets (tracks_to_latents on a batch with per-sample support counts): q, o [nseq,Sq,H*Dh]; the keys of sequence i are
+ * rows [koff[i], koff[i + 1]) of the packed k, v; no key mask; lse [nseq,H,Sq,2].  impl 0 / 2: one launch of the chunked-key kernels (16-bit, Dh = 96,
+ * Sq <= 128); impl 1, SPA3D_F32 or another shape: the sequences one by one through spa3d_op_attention's routes.  Refused: koff[0] != 0, a sequence
+ * without a key, Sq < 1, H < 1, Dh outside 1..128, impl outside 0..2, a row stride below H*Dh, and impl 2 with a shape, dtype or alignment the fused
+ * kernels do not take. */
+int spa3d_op_attention_varlen(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldk, int64_t ldv,
+                              const float* scale_q, const float* scale_k, const int32_t* koff /* HOST [nseq + 1] */,
+                              int64_t nseq, int32_t Sq, int32_t H, int32_t Dh, void* o, float* lse, int32_t dtype, int32_t impl,
+                              void* ws, int64_t ws_bytes, void* stream);
+/* gradients of the above from the forward's o and lse: both are required for a 16-bit dtype under impl 0 / 2 (a NULL one is refused); SPA3D_F32 and impl 1 run the
+ * generic composition, which reads neither, and take NULL */
+int spa3d_op_attention_varlen_bwd(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldk, int64_t ldv,
+                                  const float* scale_q, const float* scale_k, const int32_t* koff /* HOST [nseq + 1] */,
+                                  int64_t nseq, int32_t Sq, int32_t H, int32_t Dh, const void* o, const float* lse, const void* d_o,
+                                  void* dq, void* dk, void* dv, float* dscale_q, float* dscale_k, int32_t dtype, int32_t impl,
+                                  void* ws, int64_t ws_bytes, void* stream);
+
 /* Single-query attention of a stack's last block (csrc/attn_q1.hip; track_autoencoder_3d.py:187-188, 286): only token 0 of each sequence
  * queries, every token is a key.  q0 [nseq,H*Dh] with row stride ldq0; k, v [rows,H*Dh] with row strides ldk / ldv; o0 [nseq,H*Dh] dense;
  * p0 [nseq*H,S] f32 = the softmax row of every (sequence, head), kept for the backward.  Scales, key mask and arithmetic as

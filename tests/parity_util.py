@@ -427,10 +427,11 @@ def row_errs_floored(got, ref64, floor, dim=-1):
   return (g - r).norm(dim=dim) / torch.clamp(n, min=floor * float((n * n).mean().sqrt()) + 1e-300)
 
 
-def attention_grad_gates(gates, got, emu, ref, H, Dh):
+def attention_grad_gates(gates, got, emu, ref, H, Dh, S=None):
   """The backward half of the row gate.  got / emu / ref: (dq, dk, dv, dsq, dsk) of the kernel, of emulate_attention_bwd and of the fp64 oracle.  Every
-  (sequence, token, head) row of dq, dk, dv and the whole vectors dsq, dsk within 2 x the emulation's worst, rows by row_errs_floored."""
-  floor = grad_row_floor(emu[0].dtype, Dh, max(ref[0].shape[1], ref[1].shape[1]))
+  (sequence, token, head) row of dq, dk, dv and the whole vectors dsq, dsk within 2 x the emulation's worst, rows by row_errs_floored.  S: the longest
+  sequence (queries or keys) where the tensors are ragged sequences' rows concatenated [rows, E] and their shape does not say it."""
+  floor = grad_row_floor(emu[0].dtype, Dh, max(ref[0].shape[1], ref[1].shape[1]) if S is None else S)
   for name, g, e, r in zip(('dq', 'dk', 'dv'), got[:3], emu[:3], ref[:3]):
     shp = r.shape[:-1] + (H, Dh)
     ke = row_errs_floored(g.reshape(shp), r.reshape(shp), floor)

@@ -61,6 +61,11 @@ def _oracle(lens, off, nq, w, sq, sk, km, H):
                                                           (9, 129, 8, BF16, False, False), (2, 160, 8, F16, False, True), (17, 151, 8, F16, True, False),
                                                           (3, 40, 2, BF16, False, True), (300, 151, 8, BF16, True, False)])
 def test_qkv_attention_fused_vs_oracle_and_two_kernel_path(lib, nseq, S, H, dtype, ragged, masked):
+  """Ragged cases take the two-kernel comparison through spa3d_op_attention_ragged (same offsets, from the host), under the dense cases' three assertions.
+  The first time it ran, [300-151-8-1-True-False] (bf16, 39 717 rows, 635 472 lse slots) missed |d lse| < 1e-3 with 3.13e-3 (29 slots above 1e-3): the fused
+  kernel summed x^2 for the two RMSNorms in another order than the attention kernels, its rsqrt argument differed by an fp32 ulp now and then, and about one
+  element of q^ / k^ in 10^5 rounded to the other bf16 neighbour.  qkva_fwd_kernel now sums in the attention kernels' order (csrc/qkv_attn.hip); measured
+  since: bf16 max |d lse| 1.2e-6 in every case, no slot above 1e-5.  The fp16 cases measure 1.1e-4 (dense) and 4.7e-4 (ragged), as before that change."""
   lens, off, nq, w, sq, sk, km = _case(nseq, S, H, dtype, ragged, masked)
   E, rows = H * 96, off[-1]
   tdt = nq.dtype
@@ -84,16 +89,20 @@ def test_qkv_attention_fused_vs_oracle_and_two_kernel_path(lib, nseq, S, H, dtyp
   assert max_abs(qkv.float(), qkv_ref) <= eps * float(qkv_ref.abs().max())
   assert rel_err(o.float(), o_ref) < (1.2e-2 if dtype == BF16 else 1.6e-3)   # the fused attention kernel's own bound (tests/test_gpu_ops.py)
   # against the two-kernel path on the SAME stored q | k | v: identical rounding points -> equal up to fp32 summation order of the two MFMA contractions
-  if not ragged:
-    o2 = torch.empty_like(o); lse2 = torch.empty(rows * H * 2, device='cuda')
+  # (ragged: the same offsets through spa3d_op_attention_ragged, which takes them from the host; both kernels put lse at the same ragged position)
+  o2 = torch.empty_like(o); lse2 = torch.full((rows * H * 2,), float('nan'), device='cuda')
+  if ragged:
+    rc = lib.spa3d_op_attention_ragged(qkv.data_ptr(), qkv[:, E:].data_ptr(), qkv[:, 2 * E:].data_ptr(), 3 * E, 3 * E, 3 * E, sqd.data_ptr(), skd.data_ptr(),
+                                       None, (C.c_int32 * len(off))(*off), nseq, S, H, 96, o2.data_ptr(), lse2.data_ptr(), dtype, 2, ws.data_ptr(), ws.numel(), _s())
+  else:
     rc = lib.spa3d_op_attention(qkv.data_ptr(), qkv[:, E:].data_ptr(), qkv[:, 2 * E:].data_ptr(), 3 * E, 3 * E, 3 * E, sqd.data_ptr(), skd.data_ptr(),
                                 None if kmd is None else kmd.data_ptr(), nseq, S, S, H, 96, o2.data_ptr(), lse2.data_ptr(), dtype, 2, ws.data_ptr(), ws.numel(), _s())
-    assert rc == 0
-    torch.cuda.synchronize()
-    frac = float((o2.view(torch.int16) != o.view(torch.int16)).float().mean())
-    print(f'fused vs two kernels: o differs in {frac:.2e} of the elements; lse max abs diff {float((lse2 - lse).abs().max()):.2e}')
-    assert rel_err(o.float(), o2.float()) < 2 * eps and frac < 0.05
-    assert float((lse2 - lse).abs().max()) < 1e-3
+  assert rc == 0
+  torch.cuda.synchronize()
+  frac = float((o2.view(torch.int16) != o.view(torch.int16)).float().mean())
+  print(f'fused vs two kernels: o differs in {frac:.2e} of the elements; lse max abs diff {float((lse2 - lse).abs().max()):.2e}')
+  assert rel_err(o.float(), o2.float()) < 2 * eps and frac < 0.05
+  assert float((lse2 - lse).abs().max()) < 1e-3
 
 
 @pytest.mark.parametrize('precision', ['bf16', 'fp16'])
