@@ -111,6 +111,7 @@ _SIGS = {
     'spa3d_get_loss': (C.c_int, [C.c_void_p, C.POINTER(LossConfig)]),
     'spa3d_set_point_weights': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     'spa3d_grad_segments': (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    'spa3d_trainable_range': (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     'spa3d_set_grad_events': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     'spa3d_grad_events_recorded': (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     'spa3d_detach': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -270,6 +270,8 @@ struct spa3d_ctx {
   // spa3d_set_point_weights: caller-owned device plane [B,Q,T_out] of the next calls' batch (null = every weight 1) and the B, Q it was stated for
   const float* pt_w = nullptr; int pt_B = 0, pt_Q = 0;
   int poison = 0;         // spa3d_set_option "poison": NaN-fill the workspace before every chunk and every op output before its launch (tests)
+  int freeze = 0;         // spa3d_set_option "freeze": spa3d_loss_and_grads stops its backward at a stage boundary -- 1: [0, b1) of the flat buffer (embeddings,
+                          // track encoder, state_init leaves) is frozen, 2: [0, b2) (the latent stacks too); run_chunk (model.hip) skips the stages whole
   Prof prof;
 };
 

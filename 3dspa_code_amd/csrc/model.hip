@@ -629,8 +629,8 @@ template <typename T> struct Net {
       k_layernorm<T>(c, k.r0, enc.norm_enc, k.enc_out, k.st_r0, nseq, d);                            // attention.py:49-51 (row 0 only)
     }
   }
-  // L1-L3: k.enc_out holds all k.Bc * k.Nk encoder outputs
-  void encode_latents(Chunk& k, bool train) {
+  // L1-L3: k.enc_out holds all k.Bc * k.Nk encoder outputs -> k.latents [Bc,L,Ld] f32 (written to lat_dst when given, else allocated here)
+  void encode_latents(Chunk& k, bool train, float* lat_dst = nullptr) {
     const int L = g.num_latent_tokens, dl = g.encoder_latent_dim;
     const T* x;
     if (k.packed) { k.koff_dev = alloc<int32_t>(k.Bc + 1); k_set_i32(c, k.koff_dev, k.noff.data(), k.Bc + 1); }
@@ -650,7 +650,7 @@ template <typename T> struct Net {
     k.t2l_last = const_cast<T*>(x);
     k.st_t2l = alloc<float>(k.Bc * L * 2); k.t2l_n = alloc<T>(k.Bc * L * dl);
     k_layernorm<T>(c, x, t2l.norm_enc, k.t2l_n, k.st_t2l, k.Bc * L, dl);
-    k.latents = alloc<float>(k.Bc * L * g.latent_token_dim);
+    k.latents = lat_dst ? lat_dst : alloc<float>(k.Bc * L * g.latent_token_dim);
     lin_fwd(comp, k.t2l_n, k.latents, k.Bc * L, EPI_NONE, nullptr, 1);                               // 3d:203
   }
 
@@ -754,10 +754,11 @@ template <typename T> struct Net {
   const float* scale_dev = nullptr;                  // fp16 mode: the call's loss scale (device)
   const float* ptw = nullptr;                        // the call's point weights (RunArgs::w)
   bool seg_unscaled[2] = {false, false};
+  bool seg_frozen[2] = {false, false};               // "freeze": the segment lies in the frozen range -- nothing to flush or unscale, its event is still recorded
   void grad_segment_done(int i) {
     if (c->dry || !c->last_chunk || !c->grad_ev[i]) return;
-    if (c->det && seg_hi[i] > seg_lo[i]) k_det_flush(c, seg_lo[i], seg_hi[i] - seg_lo[i]);   // the segment's shadow sums are final too
-    if (c->loss_scale != 1.f) {  // fp16: bring the finished segment back to true scale NOW (a power of two: exact) so that its all-reduce can start behind the event
+    if (c->det && seg_hi[i] > seg_lo[i] && !seg_frozen[i]) k_det_flush(c, seg_lo[i], seg_hi[i] - seg_lo[i]);   // the segment's shadow sums are final too
+    if (c->loss_scale != 1.f && !seg_frozen[i]) {  // fp16: bring the finished segment back to true scale NOW (a power of two: exact) so that its all-reduce can start behind the event
       if (!scale_dev || seg_hi[i] <= seg_lo[i]) return;
       k_unscale(c, G + seg_lo[i], scale_dev, seg_hi[i] - seg_lo[i]);
       seg_unscaled[i] = true;
@@ -802,7 +803,8 @@ template <typename T> struct Net {
     }
   }
   // decompress_attn, decompressor, straight-through clip, compressor, tracks_to_latents (+ state_init) from the latent-side gradient -> d enc_out [Bc * N, d]
-  T* backward_latents(Chunk& k, const float* dlatd32) {
+  // lat0_trains = false ("freeze" 1): state_init lies in the frozen range [0, b1) although this stage consumes it -- its gradient is not added
+  T* backward_latents(Chunk& k, const float* dlatd32, bool lat0_trains = true) {
     const int L = g.num_latent_tokens, Ld = g.latent_token_dim, dd = g.decoder_num_channels, Cl = dd - 128;
     const int d = g.track_token_dim, dl = g.encoder_latent_dim;
     const int64_t nl = k.Bc * L;
@@ -832,7 +834,7 @@ template <typename T> struct Net {
     for (int i = (int)t2l.blocks.size() - 1; i >= 0; --i)
       block_bwd(t2l.blocks[i], k.t2l_st[i], dt2l, dt2l, k.Bc, L, nullptr, k.enc_out, k.Nk, denc_out, Rag(), nullptr, k.packed ? k.noff.data() : nullptr, k.koff_dev);
     grad_segment_done(1);  // tracks_to_latents, compressor, decompressor, decompress_attn
-    k_bcast_grad<T>(c, dt2l, (int64_t)L * dl, k.Bc, (int64_t)L * dl, g_lat0);
+    if (lat0_trains) k_bcast_grad<T>(c, dt2l, (int64_t)L * dl, k.Bc, (int64_t)L * dl, g_lat0);
     return denc_out;
   }
   // track encoder (E7-E1) of the tracks of k (k.nseq sequences, stashed by encode_tracks(train = true)) against their rows denc_out [nseq, d]
@@ -962,7 +964,14 @@ static void run_chunk(spa3d_ctx* c, const RunArgs& a, Net<T>& net, typename Net<
   const int64_t ntrk = k.nseq, Qall = k.Qc;  // (track_chunk / query_chunk: k.Bc == 1)
   const int64_t tc = c->track_chunk > 0 ? std::min<int64_t>(c->track_chunk, ntrk) : ntrk, qc = c->query_chunk > 0 ? std::min<int64_t>(c->query_chunk, Qall) : Qall;
   auto track_slice = [&](int64_t n0) { k.n_off = n0; k.Nc = (int)std::min(tc, ntrk - n0); k.nseq = k.Nc; };
+  // "freeze" (train only): the backward stops at a stage boundary.  The stages below it are skipped whole, and a stage the backward no longer enters runs
+  // its forward without a stash: the same kernels (block_fwd and encode_tracks choose none by whether a stash is kept) into buffers released at once.
+  const int fz = train ? c->freeze : 0;
+  const bool stash_enc = train && fz < 1, stash_lat = train && fz < 2;
   if (a.mode != MODE_DECODE) {
+    // freeze 2: no backward reads anything below the latents -- they are all that stays of the two encoder stages for the rest of the chunk
+    float* lat_keep = fz >= 2 ? net.template alloc<float>(k.Bc * L * Ld) : nullptr;
+    const int64_t mk_lat = c->ar.mark();
     if (c->track_chunk > 0) {  // pass A
       T* enc_all = net.template alloc<T>(ntrk * d);
       for (int64_t n0 = 0; n0 < ntrk; n0 += tc) {
@@ -973,10 +982,18 @@ static void run_chunk(spa3d_ctx* c, const RunArgs& a, Net<T>& net, typename Net<
         c->ar.release(mk);
       }
       k.enc_out = enc_all; k.n_off = 0; k.Nc = (int)ntrk; k.nseq = ntrk;
+    } else if (fz > 0) {
+      // no encoder backward: enc_out is all backward_latents reads of this stage (with the packed key offsets, which encode_latents allocates), so the
+      // ping-pong buffers, the token rows and the packed copies of a ragged chunk go now, not at the end of the chunk -- as pass A above does per slice
+      T* enc_keep = net.template alloc<T>(ntrk * d);
+      const int64_t mk = c->ar.mark();
+      net.encode_tracks(k, b, b0, false, enc_keep);
+      c->ar.release(mk);
     } else {
-      net.encode_tracks(k, b, b0, train);
+      net.encode_tracks(k, b, b0, stash_enc);
     }
-    net.encode_latents(k, train);
+    net.encode_latents(k, stash_lat, lat_keep);
+    if (lat_keep) c->ar.release(mk_lat);
     float* lo = a.latents_out ? a.latents_out : (a.out && a.out->latents ? a.out->latents : nullptr);
     if (lo && !c->dry) (void)hipMemcpyAsync(lo + b0 * L * Ld, k.latents, (size_t)(k.Bc * L * Ld) * 4, hipMemcpyDeviceToDevice, c->stream);
   }
@@ -986,7 +1003,7 @@ static void run_chunk(spa3d_ctx* c, const RunArgs& a, Net<T>& net, typename Net<
     if (train) { net.grad_segment_done(0); net.grad_segment_done(1); }
     return;
   }
-  net.decode_latents(k, b, a.mode == MODE_DECODE ? a.latents_in + b0 * L * Ld : k.latents, noise, b0, train);
+  net.decode_latents(k, b, a.mode == MODE_DECODE ? a.latents_in + b0 * L * Ld : k.latents, noise, b0, stash_lat);
   float* dlatd32 = train ? net.template alloc<float>(k.Bc * L * Cl) : nullptr;
   for (int64_t q0 = 0; q0 < Qall; q0 += qc) {
     k.q_off = q0; k.Qc = (int)std::min(qc, Qall - q0);
@@ -999,7 +1016,9 @@ static void run_chunk(spa3d_ctx* c, const RunArgs& a, Net<T>& net, typename Net<
   }
   if (!train) return;
   net.grad_segment_done(0);  // track_readout_attn, query_encoder, track_predictor: final after the last query chunk of the LAST sample chunk (grad_segment_done checks)
-  const T* denc_out = net.backward_latents(k, dlatd32);
+  if (fz >= 2) { net.grad_segment_done(1); return; }  // the backward ends here: the latents event follows the readout event directly, as for nq() == 0 above
+  const T* denc_out = net.backward_latents(k, dlatd32, fz < 1);
+  if (fz >= 1) return;  // the backward ends with the latent stacks (their event is recorded there); d enc_out is dead, and pass B with its recompute is dropped
   if (c->track_chunk <= 0) { net.backward_tracks(k, denc_out); return; }
   k.count_plan = false;  // pass B: recompute + backward per track chunk
   for (int64_t n0 = 0; n0 < ntrk; n0 += tc) {
@@ -1087,6 +1106,11 @@ void run_body(spa3d_ctx* c, const RunArgs& a, int Bc) {
     if (spa3d_grad_segments(c, b4) == SPA3D_OK) { net.seg_lo[0] = b4[2]; net.seg_hi[0] = b4[3]; net.seg_lo[1] = b4[1]; net.seg_hi[1] = b4[2]; }
     if (c->loss_scale != 1.f) net.scale_dev = denom_dev + 1;
   }
+  // "freeze": [0, lo) of G is frozen -- zeroed above or left as the caller's (accumulate), and no launch below writes there: not the stages run_chunk skips,
+  // not the det_grads flush, not the unscaling
+  int64_t lo_n[2] = {0, c->nparams};
+  if (train) { (void)spa3d_trainable_range(c, lo_n); net.seg_frozen[1] = c->freeze >= 2; }
+  const int64_t glo = lo_n[0];
   // deterministic parameter gradients: every reduction into G goes through a 64-bit fixed-point shadow (common.hpp DetCfg, grad_add).  c->det belongs to this
   // call alone: every launch that adds into G passes it, and it is null again before the call returns (the shadow lives in this call's workspace)
   if (train && c->det_grads) {
@@ -1122,14 +1146,14 @@ void run_body(spa3d_ctx* c, const RunArgs& a, int Bc) {
     c->ar.release(mk);
   }
   if (c->det) {
-    k_det_flush(c, 0, c->nparams);   // what the segment flushes left (flushed ranges hold zeros)
+    k_det_flush(c, glo, c->nparams - glo);   // what the segment flushes left (flushed ranges hold zeros)
     c->det = nullptr;   // no later launch of this handle (an op backward, its next call) may add into the dead shadow (tests/test_gpu_det_edges.py)
   }
   if (train && c->loss_scale != 1.f) {  // fp32 gradient buffer back to true scale (exact: power of two); segments already unscaled at their events are skipped
-    const int64_t lo1 = net.seg_lo[1], lo0 = net.seg_lo[0];
-    if (!net.seg_unscaled[0] && !net.seg_unscaled[1]) k_unscale(c, a.G, denom_dev + 1, c->nparams);
+    const int64_t lo1 = std::max(net.seg_lo[1], glo), lo0 = std::max(net.seg_lo[0], glo);
+    if (!net.seg_unscaled[0] && !net.seg_unscaled[1]) k_unscale(c, a.G + glo, denom_dev + 1, c->nparams - glo);
     else {
-      k_unscale(c, a.G, denom_dev + 1, lo1);
+      k_unscale(c, a.G + glo, denom_dev + 1, lo1 - glo);
       if (!net.seg_unscaled[1]) k_unscale(c, a.G + lo1, denom_dev + 1, lo0 - lo1);
       if (!net.seg_unscaled[0]) k_unscale(c, a.G + lo0, denom_dev + 1, c->nparams - lo0);
     }
@@ -1336,7 +1360,7 @@ int spa3d_create(const spa3d_config* cfg, spa3d_handle* out) {
   // at loss x 2^k (k chosen per call from the loss denominator, k_set_loss_scale) and the fp32 parameter gradients are scaled back once
   // at the end (exact for powers of two)
   if (cfg->precision == SPA3D_F16) c->loss_scale = -16.f;
-  // the nine switches (include/spa3d.h, spa3d_set_option) may be preset from the environment; nothing else is read from it
+  // the ten switches (include/spa3d.h, spa3d_set_option) may be preset from the environment; nothing else is read from it
   const char* e = getenv("SPA3D_GEMM_IMPL"); if (e) set_gemm_impl(c, atoi(e));
   e = getenv("SPA3D_ATTN_IMPL"); if (e) apply_attn_impl(c, atoi(e));
   e = getenv("SPA3D_LOSS_SCALE"); if (e && cfg->precision == SPA3D_F16) c->loss_scale = (float)atof(e);
@@ -1346,6 +1370,7 @@ int spa3d_create(const spa3d_config* cfg, spa3d_handle* out) {
   e = getenv("SPA3D_DET_GRADS"); if (e) c->det_grads = atoi(e) != 0;
   e = getenv("SPA3D_QUERY_CHUNK"); if (e) c->query_chunk = std::max(0, atoi(e));
   e = getenv("SPA3D_TRACK_CHUNK"); if (e) c->track_chunk = std::max(0, atoi(e));
+  e = getenv("SPA3D_FREEZE"); if (e && atoi(e) >= 0 && atoi(e) <= 2) c->freeze = atoi(e);
   *out = c;
   return SPA3D_OK;
 }
@@ -1518,6 +1543,10 @@ int spa3d_set_option(spa3d_handle h, const char* name, double value) {
   }
   else if (n == "poison") h->poison = value != 0;
   else if (n == "det_grads") h->det_grads = value != 0;
+  else if (n == "freeze") {
+    if (value != 0 && value != 1 && value != 2) { h->err = "freeze must be 0 (nothing frozen), 1 (track encoder side) or 2 (the latent stacks too)"; return SPA3D_ERR_ARG; }
+    h->freeze = (int)value;
+  }
   else { h->err = "unknown option: " + n; return SPA3D_ERR_ARG; }
   return SPA3D_OK;
 }
@@ -1582,6 +1611,12 @@ int spa3d_grad_segments(spa3d_handle h, int64_t* bounds4) {
   }
   if (b1 < 0 || b2 < b1) return SPA3D_ERR_ARG;
   bounds4[0] = 0; bounds4[1] = b1; bounds4[2] = b2; bounds4[3] = h->nparams;
+  return SPA3D_OK;
+}
+int spa3d_trainable_range(spa3d_handle h, int64_t* lo_n) {
+  int64_t b4[4];
+  if (!h || !lo_n || spa3d_grad_segments(h, b4) != SPA3D_OK) return SPA3D_ERR_ARG;
+  lo_n[0] = b4[h->freeze]; lo_n[1] = b4[3];
   return SPA3D_OK;
 }
 int spa3d_grad_events_recorded(spa3d_handle h, int64_t* out4) {

@@ -411,6 +411,43 @@ def _loss_on(h, loss, weights, B, Q, nc):
       lib.spa3d_set_loss(h, None)
 
 
+FREEZE_ALIASES = {'none': 0, 'encoder': 1, 'encoder+latents': 2}
+
+
+def freeze_level(freeze) -> int:
+  """0 | 1 | 2, or the aliases 'none' | 'encoder' | 'encoder+latents' (include/spa3d.h, spa3d_set_option "freeze")."""
+  k = FREEZE_ALIASES.get(freeze, freeze) if isinstance(freeze, str) else freeze
+  if isinstance(k, bool) or not isinstance(k, int) or k not in (0, 1, 2):
+    raise ValueError(f"freeze must be 0, 1, 2 or one of {sorted(FREEZE_ALIASES)}, got {freeze!r}")
+  return k
+
+
+def trainable_range(h):
+  """(lo, n) of the handle's stored "freeze" option: the range of the flat buffer a training call writes gradients into (spa3d_trainable_range)."""
+  r = (C.c_int64 * 2)()
+  _lib.check(_lib.load().spa3d_trainable_range(h, r), h, 'spa3d_trainable_range')
+  return int(r[0]), int(r[1])
+
+
+@contextlib.contextmanager
+def _freeze_on(h, freeze):
+  """States the "freeze" option on the handle for the calls inside the block (sizing included: spa3d_workspace_bytes follows it) and puts the value it
+  found back afterwards, as _loss_on does with the objective: an SPA3D_FREEZE preset or another owner's setting survives the call."""
+  k = freeze_level(freeze)
+  lib = _lib.load()
+  b4 = (C.c_int64 * 4)()
+  _lib.check(lib.spa3d_grad_segments(h, b4), h, 'spa3d_grad_segments')
+  prev = list(b4[:3]).index(trainable_range(h)[0])
+  if prev == k:
+    yield
+    return
+  _lib.check(lib.spa3d_set_option(h, b'freeze', float(k)), h, 'spa3d_set_option')
+  try:
+    yield
+  finally:
+    lib.spa3d_set_option(h, b'freeze', float(prev))
+
+
 def _require_cuda(t: torch.Tensor, name: str):
   if not t.is_cuda:
     raise _lib.Spa3dError(f'{name} must live on the GPU: the 3DSPA hot path is HIP-only (no CPU fallback)')
@@ -916,8 +953,11 @@ class TrackAutoEncoder3D:
 
   # -------------------------------------------------------------------------------- value_and_grad
   def loss_and_grads(self, variables, batch, grads_flat: Optional[torch.Tensor] = None, accumulate: bool = False,
-                     denom: float = 0.0, discretize: bool = True, noise=None, return_predictions: bool = False, loss: Optional[LossConfig] = None):
+                     denom: float = 0.0, discretize: bool = True, noise=None, return_predictions: bool = False, loss: Optional[LossConfig] = None,
+                     freeze=0):
     """jax.value_and_grad(loss_fn)(params) of train.py:134-162 in one call.  Returns (loss_dict, grads_tree, preds|None).
+    `freeze`: 0 | 1 ('encoder') | 2 ('encoder+latents') -- the backward stops at that stage boundary (spa3d_set_option "freeze"): the gradients of the
+    frozen prefix [0, lo) of the flat buffer are zero (accumulate: left as they were), the rest and every forward result are those of freeze = 0.
     `denom`: the batch-GLOBAL sum(query_tracks_visible) under data parallelism (train.py:111-113).
     `loss`: the objective (LossConfig; None = the reference's); batch['query_weight'] ([B,Q,T] or [B,Q,T,1], in [0, 1]) weights single points."""
     params = variables['params'] if 'params' in variables and isinstance(variables['params'], dict) else variables
@@ -935,8 +975,8 @@ class TrackAutoEncoder3D:
     if return_predictions:
       res, out = self._alloc_outputs(b.B, b.Q, dev)
       outp = C.byref(out)
-    ws = self._workspace(h, b.B, b.N, b.Q, b.T, True, dev)
-    with _counts_on(h, b), _loss_on(h, loss, b.weights, b.B, b.Q, self._nc):
+    with _freeze_on(h, freeze), _counts_on(h, b), _loss_on(h, loss, b.weights, b.B, b.Q, self._nc):
+      ws = self._workspace(h, b.B, b.N, b.Q, b.T, True, dev)
       _lib.check(_lib.load().spa3d_loss_and_grads(h, flat.data_ptr(), C.byref(b), float(denom), grads_flat.data_ptr(),
                                                   1 if accumulate else 0, loss3.data_ptr(), outp, ws.data_ptr(), ws.numel(),
                                                   _stream(flat)), h, 'spa3d_loss_and_grads')

@@ -14,7 +14,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
-from .model import TrackAutoEncoder3D, _stream
+from .model import TrackAutoEncoder3D, _stream, freeze_level
 
 
 def create_learning_rate_schedule(base_lr: float, warmup_steps: int, total_steps: int):
@@ -81,21 +81,22 @@ def allreduce_flat_(flat: torch.Tensor, bucket_elems: int, group=None, extra=(),
     w.wait()
 
 
-def allreduce_segments_overlapped_(flat: torch.Tensor, bounds, events, side: 'torch.cuda.Stream', bucket_elems: int, group=None, extra=()):
+def allreduce_segments_overlapped_(flat: torch.Tensor, bounds, events, side: 'torch.cuda.Stream', bucket_elems: int, group=None, extra=(), lo: int = 0):
   """SUM all-reduce of the flat gradient buffer in the order its segments become final during the last sample chunk's backward
   (include/spa3d.h, spa3d_grad_segments): segment [b2, n) once `events[0]` has fired, [b1, b2) once `events[1]` has, both on the side stream
   `side` and therefore UNDER the rest of the backward that is still running on the launch stream; [0, b1) and the `extra` scalars on the
   launch stream behind everything.  The events were recorded by spa3d_loss_and_grads on the launch stream before it returned (the call
   enqueues; it does not wait), so waiting for them here is well ordered.  Returns when every reduction has been enqueued and the launch
-  stream has been made to wait for the side stream."""
+  stream has been made to wait for the side stream.  `lo`: start of the trainable range (TrainState `freeze`): what lies below it -- a whole segment, or two
+  -- holds zeros on every rank and is not reduced; both events are still waited for (the library records them whatever is frozen)."""
   main = torch.cuda.current_stream(flat.device)
   works = []
-  for ev, (lo, hi) in zip(events, ((bounds[2], bounds[3]), (bounds[1], bounds[2]))):
+  for ev, (lo_, hi) in zip(events, ((bounds[2], bounds[3]), (bounds[1], bounds[2]))):
     side.wait_event(ev)
     with torch.cuda.stream(side):
-      for s_ in range(lo, hi, bucket_elems):
+      for s_ in range(max(lo_, lo), hi, bucket_elems):
         works.append(dist.all_reduce(flat[s_:min(s_ + bucket_elems, hi)], op=dist.ReduceOp.SUM, group=group, async_op=True))
-  for s_ in range(0, bounds[1], bucket_elems):
+  for s_ in range(lo, bounds[1], bucket_elems):
     works.append(dist.all_reduce(flat[s_:min(s_ + bucket_elems, bounds[1])], op=dist.ReduceOp.SUM, group=group, async_op=True))
   for t in extra:
     works.append(dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group, async_op=True))
@@ -130,14 +131,21 @@ class TrainState:
     compute(params_tree, batch, grads_flat, denom, discretize, noise) -> {'total_loss','position_loss','visible_loss'}
     adamw(flat, grads, m, v, lr, step, clip, b1, b2, eps, wd, scratch) -> None  (scratch[0] := global grad norm)
     noise_fn(n, device) -> float32[n] = jax.random.uniform(PRNGKey(0), [n]) (track_autoencoder_3d.py:254-257)
-    evaluate(params_tree, batch, denom, discretize, noise) -> (loss dict, predictions)   (eval_step, train.py:189-213)"""
+    evaluate(params_tree, batch, denom, discretize, noise) -> (loss dict, predictions)   (eval_step, train.py:189-213)
+
+  `freeze` = 0 | 1 | 2 (aliases 'none' | 'encoder' | 'encoder+latents'; include/spa3d.h, spa3d_set_option "freeze") fine-tunes with the prefix [0, lo) of
+  the flat buffer frozen, lo = b1 or b2 of spa3d_grad_segments: the backward stops at that stage boundary, and clip + AdamW, the gradient all-reduce (bucketed
+  or overlapped) and the norm run on the trainable range [lo, n) alone.  Frozen parameters and their moments keep their bits -- no weight decay reaches
+  them -- and the clip norm and 'train/grad_norm' are those of the trainable range.  The adamw stand-in receives the slices [lo:] of flat, grads, m and v;
+  sync_from_rank0, checkpoints and load_train_state stay on the whole buffers."""
 
   def __init__(self, model: TrackAutoEncoder3D, params, learning_rate: float = 1e-4, warmup_steps: int = 10000,
                total_steps: int = 1000000, weight_decay: float = 0.01, clip_norm: float = 1.0, b1: float = 0.9,
                b2: float = 0.999, eps: float = 1e-8, process_group: Optional[dist.ProcessGroup] = None,
                grad_bucket_bytes: int = 128 << 20, compute=None, adamw=None, noise_fn=None, force_collectives: bool = False,
-               evaluate=None, overlap_allreduce: bool = True, loss=None):
+               evaluate=None, overlap_allreduce: bool = True, loss=None, freeze=0):
     self.model = model
+    self.freeze = freeze_level(freeze)
     # the objective of this state's steps (a LossConfig; None = the reference's): stated on the model's handle for each call and taken off after
     # it, so two states with different objectives on one model never see each other's
     self.loss = loss
@@ -147,6 +155,11 @@ class TrainState:
       dino, depth = model._dims_from_params(params)
       self.params = model.tree_from_flat(flat, dino, depth)
     self.flat = flat
+    # the trainable range [lo, n) of the flat buffers: the whole of them unless `freeze` cuts a prefix off at a stage boundary (spa3d_grad_segments)
+    h = model._handle(*model._dims_from_params(self.params))[0]
+    b4 = (C.c_int64 * 4)()
+    _lib.check(_lib.load().spa3d_grad_segments(h, b4), h, 'spa3d_grad_segments')
+    self.trainable_lo = int(b4[self.freeze])
     self.m = torch.zeros_like(flat)
     self.v = torch.zeros_like(flat)
     self.grads = torch.zeros_like(flat)
@@ -230,7 +243,7 @@ class TrainState:
   # ---- default (HIP) compute and optimizer
   def _hip_compute(self, params, batch, grads_flat, denom, discretize, noise):
     ld, _, _ = self.model.loss_and_grads(params, batch, grads_flat=grads_flat, accumulate=False, denom=denom,
-                                         discretize=discretize, noise=noise, loss=self.loss)
+                                         discretize=discretize, noise=noise, loss=self.loss, freeze=self.freeze)
     return ld
 
   def _hip_adamw(self, flat, grads, m, v, lr, step, clip, b1, b2, eps, wd, scratch):
@@ -270,14 +283,16 @@ class TrainState:
       self._ev_gen = gen
     if use_overlap:
       bounds, evs, side = self._overlap
-      allreduce_segments_overlapped_(self.grads, bounds, evs, side, self.bucket_elems, self.pg, extra=(l3,))
+      allreduce_segments_overlapped_(self.grads, bounds, evs, side, self.bucket_elems, self.pg, extra=(l3,), lo=self.trainable_lo)
     else:
-      allreduce_flat_(self.grads, self.bucket_elems, self.pg, extra=(l3,), force=self.force)
+      allreduce_flat_(self.grads[self.trainable_lo:], self.bucket_elems, self.pg, extra=(l3,), force=self.force)
     lr = self.schedule(self.step)
     # `step` counts CALLS.  A skipped update (non-finite gradient norm; scratch[3] counts them on the device) leaves m and v untouched, and
     # spa3d_adamw_step takes the Adam bias correction at step - skipped, so the optimizer count does not run ahead of the moments; the
     # learning-rate schedule is host arithmetic on `step` and does advance through a skip (reading the counter back would cost a sync).
-    self._adamw(self.flat, self.grads, self.m, self.v, lr, self.step, self.clip, self.b1, self.b2, self.eps, self.wd, self.scratch)
+    # (`freeze`: the trainable slices -- a pointer offset and a count; the frozen prefix of flat, m and v is never handed to the optimiser)
+    lo = self.trainable_lo
+    self._adamw(self.flat[lo:], self.grads[lo:], self.m[lo:], self.v[lo:], lr, self.step, self.clip, self.b1, self.b2, self.eps, self.wd, self.scratch)
     self.step += 1
     # metric keys of train.py:180-185 (device scalars)
     # 'train/skipped' = 1 when the update was skipped (non-finite gradient norm: fp16 overflow), 'train/loss_scale_mult' the dynamic multiplier

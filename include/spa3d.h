@@ -29,7 +29,7 @@
  * modes, two 4-byte plan counts per sample chunk (kept frame tokens; distinct query frames) are
  * read back to the host, which synchronises the stream at those points (spa3d_set_option(h, "prune", 0) and
  * spa3d_set_option(h, "ro_share", 0) remove the reads together with the savings they size; no compute path reads the environment --
- * the nine options may only be PRESET from it when spa3d_create runs);
+ * the ten options may only be PRESET from it when spa3d_create runs);
  * one handle per stream (thread-compatible, not thread-safe).  All tensors are row-major contiguous in the
  * reference's layouts.  Parameters and gradients are ONE flat float32 buffer each whose
  * leaf order / offsets the library defines (spa3d_leaf_*); names are the Flax paths of
@@ -417,8 +417,8 @@ int spa3d_adamw_step(float* params, const float* grads, float* m, float* v, int6
                      int64_t step, float clip, float b1, float b2, float eps, float wd,
                      float* scratch, void* stream);
 
-/* Per-handle switches -- the only ones the library has (nine + one test mode); each may be preset at spa3d_create from the environment variable of the same name in
- * capitals with an SPA3D_ prefix (SPA3D_PRUNE, SPA3D_QUERY_CHUNK, SPA3D_TRACK_CHUNK ...).  Unknown names return SPA3D_ERR_ARG.
+/* Per-handle switches -- the only ones the library has (ten + one test mode); each may be preset at spa3d_create from the environment variable of the same name in
+ * capitals with an SPA3D_ prefix (SPA3D_PRUNE, SPA3D_QUERY_CHUNK, SPA3D_TRACK_CHUNK, SPA3D_FREEZE ...).  Unknown names return SPA3D_ERR_ARG.
  *   "prune"      0/1  token pruning of the track encoder (16-bit modes)            } with both 0 every entry point is fully asynchronous
  *   "ro_share"   0/1  shared latent rows of the first readout block (16-bit modes) } (no plan count is read back)
  *   "loss_scale"      SPA3D_F16 handles: > 0 fixed, < 0 automatic with that head-gradient target
@@ -456,6 +456,22 @@ int spa3d_adamw_step(float* params, const float* grads, float* m, float* v, int6
  *                     entry points (always float atomics) never see it.
  *                     Costs 8 bytes of workspace per parameter and ~3.6 % of the step at BASELINE configs[2]
  *                     (1.82 -> 1.88 s: 64-bit atomics in the dW epilogues, the 1-channel depth gradient on the GEMM path); off by default.
+ *   "freeze"     k    fine-tuning with the backward cut at a stage boundary of the flat parameter buffer (spa3d_grad_segments: {0, b1, b2, n}).  Read by
+ *                     spa3d_loss_and_grads (and by spa3d_workspace_bytes(train = 1), which sizes that call); every other entry point ignores it.
+ *                     0 (default) nothing is frozen: the call as it has always been, launch for launch.
+ *                     1 [0, b1) is frozen -- embeddings, track encoder and the state_init leaves; the latent stacks and the readout train.
+ *                     2 [0, b2) is frozen -- only track_readout_attn, query_encoder and track_predictor train.
+ *                     Any other value (-1, 3, 0.5 ...) is refused with SPA3D_ERR_ARG and a message; the stored value stays.
+ *                     initializer/state_init sits at offset 0, so it is frozen from 1 on although tracks_to_latents consumes it.
+ *                     A call with k > 0: the forward results (outputs, loss3, latents, spa3d_plan_stats) are bit for bit those of k = 0 with the same
+ *                     "chunk" -- the frozen stages run the same kernels, only without a stash; with lo = b1 or b2 (spa3d_trainable_range), [lo, n)
+ *                     of `grads` receives what k = 0 gives, and [0, lo) is zero (accumulate == 0) or left untouched (accumulate != 0): no launch of the
+ *                     call writes there.  Stages are skipped whole on the host: from 1 on the track-encoder backward is not run ("track_chunk": no
+ *                     pass B, no recompute) and the encoder forward keeps only its [N, 384] output; with 2 the backward ends after the readout, and
+ *                     the latent stacks keep no stash either.  The workspace need falls accordingly.  The two gradient events (spa3d_set_grad_events)
+ *                     are still recorded once per call, in the last chunk, no later than where the shortened backward ends (2: the latents event
+ *                     right behind the readout event).  Works with every precision, both model kinds, "chunk", "query_chunk", "track_chunk", "prune",
+ *                     "ro_share", "det_grads", "poison", spa3d_set_counts, spa3d_set_point_weights and spa3d_set_loss.
  * and one test mode: "poison" 0/1 -- the workspace is filled with 16-bit NaN patterns before every sample chunk (and every track / query chunk), so a read of a row that this
  * call has not written (the rounded-up tails of pruned GEMMs, chunk-to-chunk reuse of the bump allocator) shows up as NaN instead of as a
  * plausible stale value (tests/test_gpu_poison.py). */
@@ -503,6 +519,10 @@ int spa3d_set_counts(spa3d_handle h, int32_t B, const int32_t* support_count, co
  * the last chunk; a collective on a side stream that waits for an event may then run under the rest of the backward.  Nothing is recorded
  * on SPA3D_F16 handles (the loss-scaled buffer is rescaled as a whole at the end): use stream order there. */
 int spa3d_grad_segments(spa3d_handle h, int64_t* bounds4);
+/* The range of the flat buffer that spa3d_loss_and_grads trains under the stored "freeze" option: lo_n = {lo, n} with lo = 0, b1 or b2 of
+ * spa3d_grad_segments for freeze 0, 1, 2.  [lo, n) is what the call writes gradients into; an optimiser step, a gradient norm or an all-reduce of a
+ * fine-tuning run covers that range only (spa3d_adamw_step on params + lo, grads + lo, m + lo, v + lo with n - lo elements). */
+int spa3d_trainable_range(spa3d_handle h, int64_t* lo_n /* [2] */);
 int spa3d_set_grad_events(spa3d_handle h, void* ev_readout, void* ev_latents);
 /* out4 = {records of the readout event so far, records of the latents event so far, the registered ev_readout, the registered ev_latents}
  * (host counters, bumped when a record is enqueued; the pointers as integers).  A caller about to wait on ITS events checks that they are
