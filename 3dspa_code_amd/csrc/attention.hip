@@ -1,28 +1,13 @@
 // attention.hip -- attention core of ImprovedMHDPAttention (attention.py:166-175): per-head RMSNorm of q,k,
 // q/sqrt(Dh), key mask with finfo.min fill, softmax, PV -- forward and backward.
-// impl 1 ("generic"): composition of the strided batched MFMA GEMM with the row-wise kernels below (RMSNorm, softmax); any Sq/Sk/Dh<=128,
-// both dtypes; the F32 parity path.  impl 2: fused LDS-resident kernels (attention_fused.hip) for bf16.
+// The two front ends plan (attn_plan.hpp) and run the plan: the generic composition of the strided batched MFMA GEMM with the row-wise kernels
+// below (RMSNorm, softmax) -- any Sq / Sk / Dh <= 128, both dtypes, the F32 parity path -- or the fused LDS-resident kernels (attention_fused.hip).
 #include <algorithm>
 #include <cmath>
 
 #include "common.hpp"
 
 namespace SPA_NS {
-
-bool attn_fused_fwd_bf16(spa3d_ctx* c, const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ldq, int64_t ldk, int64_t ldv,
-                         const float* sq, const float* sk, const float* km, int64_t nseq, int Sq, int Sk, int H, int Dh, bf16_t* o,
-                         float* lse, const int32_t* seq_off, int64_t total_rows);
-bool attn_fused_bwd_bf16(spa3d_ctx* c, const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ldq, int64_t ldk, int64_t ldv,
-                         const float* sq, const float* sk, const float* km, int64_t nseq, int Sq, int Sk, int H, int Dh, const bf16_t* o,
-                         const float* lse, const bf16_t* d_o, bf16_t* dq, bf16_t* dk, bf16_t* dv, float* dsq, float* dsk,
-                         const int32_t* seq_off, int64_t total_rows, const int32_t* koff = nullptr, int64_t total_keys = 0);
-bool xattn_varlen_fwd_bf16(spa3d_ctx* c, const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq,
-                           const float* sk, int64_t nseq, int Sq, int Skmax, int H, int Dh, bf16_t* o, float* lse, const int32_t* koff,
-                           int64_t total_keys);
-
-bool xattn_holdout_fwd_bf16(spa3d_ctx* c, const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq,
-                            const float* sk, int64_t nseq, int Sq, int Nk, int nmax, int H, int Dh, bf16_t* o, float* lse, const int32_t* hole,
-                            int64_t total_keys);
 
 // ---------------------------------------------------------------------------------------------
 // per-head RMSNorm over Dh (flax nn.RMSNorm eps 1e-6) attention.py:166-167.  one wave per (row, head)
@@ -185,16 +170,39 @@ static void scores(spa3d_ctx* c, const T* qn, const T* kn, T* s, int64_t ns, int
   gemm_generic<T>(c, d);
 }
 
+// ---- a fused plan: its fp32 partials from the arena (the same in the dry run, which needed only the plan), then the launcher
+void attn_launch(spa3d_ctx* c, const AttnDesc& d, const AttnPlan& pl) {
+  const int64_t mk = c->ar.mark();
+  float* part[2] = {nullptr, nullptr};
+  for (int i = 0; i < 2; ++i)
+    if (pl.part_bytes[i]) part[i] = (float*)c->ar.alloc(pl.part_bytes[i]);
+  if (!c->dry) { if (pl.kernel == AttnKernel::QkvFwd) qkv_attn_launch(c, d); else attn_fused_launch(c, d, pl, part); }
+  c->ar.release(mk);  // stream-ordered: whatever reuses the space is launched behind the route's kernels
+}
+static void attn_refuse(spa3d_ctx* c, AttnRefusal why, const char* dir) {
+  if (c->hip_err) return;
+  c->hip_err = -2;
+  c->err = why == AttnRefusal::RaggedNeedsFused ? "ragged sequences need the fused attention kernels" : std::string("fused attention ") + dir + " does not cover this shape/dtype";
+}
+// sequence i of a RaggedKeys / Hole problem as a Dense problem of its own (Hole: over the compact key copy kc / vc of E-wide rows)
 template <typename T>
-void attention_fwd(spa3d_ctx* c, const T* q, const T* k, const T* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq, const float* sk,
-              const float* km, int64_t nseq, int Sq, int Sk, int H, int Dh, T* o, float* lse, int impl, const int32_t* seq_off,
-              int64_t total_rows) {
-  const int E = H * Dh;
-  if constexpr (sizeof(T) == 2) {
-    if (impl != 1 && attn_fused_fwd_bf16(c, q, k, v, ldq, ldk, ldv, sq, sk, km, nseq, Sq, Sk, H, Dh, o, lse, seq_off, total_rows)) return;
-  }
-  if (seq_off) { if (!c->hip_err) { c->hip_err = -2; c->err = "ragged sequences need the fused attention kernels"; } return; }
-  if (impl == 2) { if (!c->hip_err) { c->hip_err = -2; c->err = "fused attention forward does not cover this shape/dtype"; } return; }
+static AttnDesc one_sequence(const AttnDesc& d, int64_t i, const T* kc = nullptr, const T* vc = nullptr) {
+  const bool hole = d.layout == AttnLayout::Hole;
+  const int64_t E = (int64_t)d.H * d.Dh, k0 = hole ? 0 : d.koff_host[i];
+  AttnDesc s = d;
+  s.layout = AttnLayout::Dense; s.nseq = 1; s.Sk = d.keys_of(i); s.km = nullptr;
+  s.q = (const T*)d.q + i * d.Sq * d.ldq; s.o = d.o ? (T*)d.o + i * d.Sq * E : nullptr; s.lse = d.lse ? d.lse + i * d.H * d.Sq * 2 : nullptr;
+  if (hole) { s.k = kc; s.v = vc; s.ldk = s.ldv = E; }
+  else { s.k = (const T*)d.k + k0 * d.ldk; s.v = (const T*)d.v + k0 * d.ldv; }
+  if (d.d_o) { s.d_o = (const T*)d.d_o + i * d.Sq * E; s.dq = (T*)d.dq + i * d.Sq * d.ldq; s.dk = (T*)d.dk + k0 * d.ldk; s.dv = (T*)d.dv + k0 * d.ldv; }
+  return s;
+}
+
+template <typename T>
+static void generic_fwd(spa3d_ctx* c, const AttnDesc& a) {
+  const T *q = (const T*)a.q, *k = (const T*)a.k, *v = (const T*)a.v; T* o = (T*)a.o;
+  const int64_t ldq = a.ldq, ldk = a.ldk, ldv = a.ldv, nseq = a.nseq; const float *sq = a.sq, *sk = a.sk, *km = a.km;
+  const int Sq = a.Sq, Sk = a.Sk, H = a.H, Dh = a.Dh, E = H * Dh;
   const int64_t cs = attn_chunk(nseq, Sq, Sk, H, E, (int)sizeof(T));
   int64_t mk = c->ar.mark();
   T* qn = aalloc<T>(c, cs * Sq * E); T* kn = aalloc<T>(c, cs * Sk * E); T* s = aalloc<T>(c, cs * H * Sq * Sk);
@@ -213,18 +221,45 @@ void attention_fwd(spa3d_ctx* c, const T* q, const T* k, const T* v, int64_t ldq
   }
   c->ar.release(mk);
 }
+// The generic route of a RaggedKeys / Hole problem: the sequences one by one, each planned again (a sequence the single launch declined may still run on the
+// fused kernels).  Hole: on a compact copy of the two key segments, so sequence i gets the bits of attention_fwd on a compacted copy either way.
 template <typename T>
-void attention_bwd(spa3d_ctx* c, const T* q, const T* k, const T* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq, const float* sk,
-              const float* km, int64_t nseq, int Sq, int Sk, int H, int Dh, const T* o, const float* lse, const T* d_o, T* dq, T* dk,
-              T* dv, float* dsq, float* dsk, int impl, const int32_t* seq_off, int64_t total_rows) {
-  const int E = H * Dh;
-  if constexpr (sizeof(T) == 2) {
-    if (impl != 1 && o && lse &&
-        attn_fused_bwd_bf16(c, q, k, v, ldq, ldk, ldv, sq, sk, km, nseq, Sq, Sk, H, Dh, o, lse, d_o, dq, dk, dv, dsq, dsk, seq_off, total_rows))
-      return;
+static void per_sequence_fwd(spa3d_ctx* c, const AttnDesc& d) {
+  if (d.layout == AttnLayout::RaggedKeys) {
+    for (int64_t i = 0; i < d.nseq; ++i) attention_fwd<T>(c, one_sequence<T>(d, i));
+    return;
   }
-  if (seq_off) { if (!c->hip_err) { c->hip_err = -2; c->err = "ragged sequences need the fused attention kernels"; } return; }
-  if (impl == 2) { if (!c->hip_err) { c->hip_err = -2; c->err = "fused attention backward does not cover this shape/dtype"; } return; }
+  const int E = d.H * d.Dh, Nk = d.Nk;
+  const T *k = (const T*)d.k, *v = (const T*)d.v;
+  const int64_t mk = c->ar.mark();
+  T* kc = aalloc<T>(c, (int64_t)d.max_keys() * E); T* vc = aalloc<T>(c, (int64_t)d.max_keys() * E);
+  auto seg = [&](T* dst, const T* src, int64_t ld_, int64_t r0, int64_t r1) {  // rows [r0, r1) of a strided [*, E] plane -> dense rows at dst
+    if (c->dry || r1 <= r0) return;
+    if (hipMemcpy2DAsync(dst, (size_t)E * sizeof(T), src + r0 * ld_, (size_t)ld_ * sizeof(T), (size_t)E * sizeof(T), (size_t)(r1 - r0), hipMemcpyDeviceToDevice,
+                         c->stream) != hipSuccess && !c->hip_err) { c->hip_err = -8; c->err = "hold-out attention: compacting the keys failed"; }
+  };
+  for (int64_t i = 0; i < d.nseq; ++i) {
+    const int lo = d.holes_host[2 * i], hi = d.holes_host[2 * i + 1];
+    seg(kc, k, d.ldk, 0, lo); seg(kc + (int64_t)lo * E, k, d.ldk, hi, Nk);
+    seg(vc, v, d.ldv, 0, lo); seg(vc + (int64_t)lo * E, v, d.ldv, hi, Nk);
+    attention_fwd<T>(c, one_sequence<T>(d, i, kc, vc));
+  }
+  c->ar.release(mk);
+}
+template <typename T>
+void attention_fwd(spa3d_ctx* c, const AttnDesc& d) {
+  const AttnPlan pl = plan_attn_fwd(d, c->attn);
+  if (pl.kernel == AttnKernel::Refuse) return attn_refuse(c, pl.why, "forward");
+  if (pl.kernel == AttnKernel::Generic) return generic_fwd<T>(c, d);
+  if (pl.kernel == AttnKernel::GenericPerSeq) return per_sequence_fwd<T>(c, d);
+  attn_launch(c, d, pl);
+}
+
+template <typename T>
+static void generic_bwd(spa3d_ctx* c, const AttnDesc& a) {
+  const T *q = (const T*)a.q, *k = (const T*)a.k, *v = (const T*)a.v, *d_o = (const T*)a.d_o; T *dq = (T*)a.dq, *dk = (T*)a.dk, *dv = (T*)a.dv;
+  const int64_t ldq = a.ldq, ldk = a.ldk, ldv = a.ldv, nseq = a.nseq; const float *sq = a.sq, *sk = a.sk, *km = a.km; float *dsq = a.dsq, *dsk = a.dsk;
+  const int Sq = a.Sq, Sk = a.Sk, H = a.H, Dh = a.Dh, E = H * Dh;
   const int64_t cs = attn_chunk(nseq, Sq, Sk, H, E, (int)sizeof(T));
   int64_t mk = c->ar.mark();
   T* qn = aalloc<T>(c, cs * Sq * E); T* kn = aalloc<T>(c, cs * Sk * E); T* s = aalloc<T>(c, cs * H * Sq * Sk);
@@ -274,88 +309,21 @@ void attention_bwd(spa3d_ctx* c, const T* q, const T* k, const T* v, int64_t ldq
   c->ar.release(mk);
 }
 
-// Cross attention of nseq sequences of Sq queries against RAGGED key sets (tracks_to_latents on a batch with per-sample support counts): the
-// keys of sequence i are rows [koff[i], koff[i + 1]) of the packed k / v.  koff_host and koff_dev hold the same nseq + 1 offsets.  16-bit modes:
-// one launch of the chunked-key kernels with per-sequence offsets (attention_fused.hip); the generic composition (fp32 parity mode, attn_impl 1,
-// shapes outside the fused kernel) runs the sequences one by one.
 template <typename T>
-void attention_varlen_fwd(spa3d_ctx* c, const T* q, const T* k, const T* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq, const float* sk,
-                          int64_t nseq, int Sq, const int32_t* koff_host, const int32_t* koff_dev, int H, int Dh, T* o, float* lse, int impl) {
-  const int E = H * Dh;
-  int Skmax = 0;
-  for (int64_t i = 0; i < nseq; ++i) Skmax = std::max(Skmax, koff_host[i + 1] - koff_host[i]);
-  if constexpr (sizeof(T) == 2) {
-    if (impl != 1 && xattn_varlen_fwd_bf16(c, q, k, v, ldq, ldk, ldv, sq, sk, nseq, Sq, Skmax, H, Dh, o, lse, koff_dev, koff_host[nseq])) return;
+void attention_bwd(spa3d_ctx* c, const AttnDesc& d) {
+  const AttnPlan pl = plan_attn_bwd(d, c->attn);
+  if (pl.kernel == AttnKernel::Refuse) return attn_refuse(c, pl.why, "backward");
+  if (pl.kernel == AttnKernel::Generic) return generic_bwd<T>(c, d);
+  if (pl.kernel == AttnKernel::GenericPerSeq) {   // ragged keys, sequence by sequence
+    for (int64_t i = 0; i < d.nseq; ++i) attention_bwd<T>(c, one_sequence<T>(d, i));
+    return;
   }
-  for (int64_t i = 0; i < nseq; ++i)
-    attention_fwd<T>(c, q + i * Sq * ldq, k + koff_host[i] * ldk, v + koff_host[i] * ldv, ldq, ldk, ldv, sq, sk, nullptr, 1, Sq,
-                     koff_host[i + 1] - koff_host[i], H, Dh, o + i * Sq * E, lse ? lse + i * H * Sq * 2 : nullptr, impl, nullptr, 0);
-}
-template <typename T>
-void attention_varlen_bwd(spa3d_ctx* c, const T* q, const T* k, const T* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq, const float* sk,
-                          int64_t nseq, int Sq, const int32_t* koff_host, const int32_t* koff_dev, int H, int Dh, const T* o, const float* lse,
-                          const T* d_o, T* dq, T* dk, T* dv, float* dsq, float* dsk, int impl) {
-  const int E = H * Dh;
-  int Skmax = 0;
-  for (int64_t i = 0; i < nseq; ++i) Skmax = std::max(Skmax, koff_host[i + 1] - koff_host[i]);
-  if constexpr (sizeof(T) == 2) {
-    if (impl != 1 && o && lse &&
-        attn_fused_bwd_bf16(c, q, k, v, ldq, ldk, ldv, sq, sk, nullptr, nseq, Sq, Skmax, H, Dh, o, lse, d_o, dq, dk, dv, dsq, dsk, nullptr, 0, koff_dev,
-                            koff_host[nseq]))
-      return;
-  }
-  for (int64_t i = 0; i < nseq; ++i) {
-    const int64_t k0 = koff_host[i];
-    attention_bwd<T>(c, q + i * Sq * ldq, k + k0 * ldk, v + k0 * ldv, ldq, ldk, ldv, sq, sk, nullptr, 1, Sq, koff_host[i + 1] - koff_host[i], H, Dh,
-                     o ? o + i * Sq * E : nullptr, lse ? lse + i * H * Sq * 2 : nullptr, d_o + i * Sq * E, dq + i * Sq * ldq, dk + k0 * ldk, dv + k0 * ldv, dsq, dsk,
-                     impl, nullptr, 0);
-  }
+  attn_launch(c, d, pl);
 }
 
-// Cross attention of nseq sequences of Sq queries over ONE shared key set, rows [0, Nk) of k / v, sequence i leaving out the rows [lo_i, hi_i) =
-// holes[2i], holes[2i + 1] (leave-fold-out scoring, spa3d_score_folds): its keys are the rows outside the hole, in row order.  holes_host and holes_dev
-// hold the same 2 nseq values; the caller has checked 0 <= lo <= hi <= Nk and hi - lo < Nk.  16-bit modes: one launch of the chunked-key kernel, which
-// addresses the keys by logical position (attention_fused.hip).  The generic composition (fp32 parity mode, attn_impl 1, shapes outside the fused kernel)
-// runs the sequences one by one on a compact copy of the two key segments.  Either way sequence i gets the bits of attention_fwd on a compacted copy.
-template <typename T>
-void attention_holdout_fwd(spa3d_ctx* c, const T* q, const T* k, const T* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq, const float* sk,
-                           int64_t nseq, int Sq, int Nk, const int32_t* holes_host, const int32_t* holes_dev, int H, int Dh, T* o, float* lse, int impl) {
-  const int E = H * Dh;
-  int nmax = 0; int64_t total = 0;
-  for (int64_t i = 0; i < nseq; ++i) { const int n = Nk - (holes_host[2 * i + 1] - holes_host[2 * i]); nmax = std::max(nmax, n); total += n; }
-  if constexpr (sizeof(T) == 2) {
-    if (impl != 1 && xattn_holdout_fwd_bf16(c, q, k, v, ldq, ldk, ldv, sq, sk, nseq, Sq, Nk, nmax, H, Dh, o, lse, holes_dev, total)) return;
-  }
-  const int64_t mk = c->ar.mark();
-  T* kc = aalloc<T>(c, (int64_t)nmax * E); T* vc = aalloc<T>(c, (int64_t)nmax * E);
-  auto seg = [&](T* dst, const T* src, int64_t ld_, int64_t r0, int64_t r1) {  // rows [r0, r1) of a strided [*, E] plane -> dense rows at dst
-    if (c->dry || r1 <= r0) return;
-    if (hipMemcpy2DAsync(dst, (size_t)E * sizeof(T), src + r0 * ld_, (size_t)ld_ * sizeof(T), (size_t)E * sizeof(T), (size_t)(r1 - r0), hipMemcpyDeviceToDevice,
-                         c->stream) != hipSuccess && !c->hip_err) { c->hip_err = -8; c->err = "hold-out attention: compacting the keys failed"; }
-  };
-  for (int64_t i = 0; i < nseq; ++i) {
-    const int lo = holes_host[2 * i], hi = holes_host[2 * i + 1], n = Nk - (hi - lo);
-    seg(kc, k, ldk, 0, lo); seg(kc + (int64_t)lo * E, k, ldk, hi, Nk);
-    seg(vc, v, ldv, 0, lo); seg(vc + (int64_t)lo * E, v, ldv, hi, Nk);
-    attention_fwd<T>(c, q + i * Sq * ldq, kc, vc, ldq, E, E, sq, sk, nullptr, 1, Sq, n, H, Dh, o + i * Sq * E, lse ? lse + i * H * Sq * 2 : nullptr, impl,
-                     nullptr, 0);
-  }
-  c->ar.release(mk);
-}
-
-#define INST_ATTN(T)                                                                                                                  \
-  template void attention_fwd<T>(spa3d_ctx*, const T*, const T*, const T*, int64_t, int64_t, int64_t, const float*, const float*,     \
-                                 const float*, int64_t, int, int, int, int, T*, float*, int, const int32_t*, int64_t);                       \
-  template void attention_bwd<T>(spa3d_ctx*, const T*, const T*, const T*, int64_t, int64_t, int64_t, const float*, const float*,     \
-                                 const float*, int64_t, int, int, int, int, const T*, const float*, const T*, T*, T*, T*, float*, float*, int, \
-                                 const int32_t*, int64_t);                                                                             \
-  template void attention_varlen_fwd<T>(spa3d_ctx*, const T*, const T*, const T*, int64_t, int64_t, int64_t, const float*, const float*, \
-                                        int64_t, int, const int32_t*, const int32_t*, int, int, T*, float*, int);                        \
-  template void attention_varlen_bwd<T>(spa3d_ctx*, const T*, const T*, const T*, int64_t, int64_t, int64_t, const float*, const float*, \
-                                        int64_t, int, const int32_t*, const int32_t*, int, int, const T*, const float*, const T*, T*, T*, T*,  \
-                                        float*, float*, int);                                                                              \
-  template void attention_holdout_fwd<T>(spa3d_ctx*, const T*, const T*, const T*, int64_t, int64_t, int64_t, const float*, const float*, \
-                                         int64_t, int, int, const int32_t*, const int32_t*, int, int, T*, float*, int);
+#define INST_ATTN(T)                                           \
+  template void attention_fwd<T>(spa3d_ctx*, const AttnDesc&); \
+  template void attention_bwd<T>(spa3d_ctx*, const AttnDesc&);
 INST_ATTN(float)
 INST_ATTN(bf16_t)
 }  // namespace SPA_NS

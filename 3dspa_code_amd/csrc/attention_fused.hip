@@ -268,6 +268,7 @@ static void launch_fwd(spa3d_ctx* c, const AttnArgs& a) {
 // Replaces a five-launch composition of strided GEMMs and row kernels that ran at 14-40 TFLOP/s (1.4 ms -> < 0.1 ms per block).
 // =================================================================================================================
 constexpr int XCHUNK = 128;
+static_assert(XCHUNK == ATTN_XCHUNK && DH == ATTN_DH, "attn_plan.hpp states these kernels' shape");
 struct XAttnArgs {
   const bf16_t *q, *k, *v; int64_t ldq, ldk, ldv;
   const float *sq, *sk, *km;
@@ -288,7 +289,7 @@ __global__ __launch_bounds__(256, 2) void xattn_fwd_kernel(XAttnArgs g) {
   constexpr int KT = XCHUNK / 16, NW = 4, S_pad = XCHUNK, RPP = NW * 16, NP = S_pad / RPP, NT = KT / NW;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* Ks = smem; char* Vs = smem + img_bytes(S_pad); float* kbias = (float*)(smem + 2 * img_bytes(S_pad));
-  const unsigned pi_u = blockIdx.x, prob_u = pi_u / (unsigned)g.nsplit, seq_u = prob_u / (unsigned)g.H;   // 32-bit: nprob * nsplit < 2^31 (xattn_fwd)
+  const unsigned pi_u = blockIdx.x, prob_u = pi_u / (unsigned)g.nsplit, seq_u = prob_u / (unsigned)g.H;   // 32-bit: nprob * nsplit < 2^31 (attn_plan_chunked, attn_plan.hpp)
   const int64_t pi = pi_u, prob = prob_u; const int sp = (int)(pi_u - prob_u * (unsigned)g.nsplit);
   const int64_t seq = seq_u; const int h = (int)(prob_u - seq_u * (unsigned)g.H);
   int hlo = 0, hgap = 0;
@@ -455,72 +456,29 @@ __global__ __launch_bounds__(256) void xattn_dq_finish_kernel(const float* __res
   if (tid < DH) grad_add(det_read(det), dsq + tid, red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid]);
 }
 
-static bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
-static bool xattn_fwd(spa3d_ctx* c, const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq,
-                      const float* sk, const float* km, int64_t nseq, int Sq, int Sk, int H, bf16_t* o, float* lse, const int32_t* seq_off,
-                      const int32_t* koff = nullptr, int64_t total_keys = 0, const int32_t* hole = nullptr, int Nk = 0) {
-  const int nsplit = (Sk + XCHUNK - 1) / XCHUNK;  // (hole: Sk is the longest sequence's key count, Nk the shared rows)
-  const int64_t nprob = nseq * H;
-  if (seq_off || Sq < 1 || Sq > XCHUNK || Sk < 1 || nprob * nsplit > 0x7fffffffLL) return false;
-  if (ldq % 8 || ldk % 8 || ldv % 8 || !al16(q) || !al16(k) || !al16(v) || !al16(o)) return false;
-  const int64_t mk = c->ar.mark();
-  XAttnArgs a; a.q = q; a.k = k; a.v = v; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.sq = sq; a.sk = sk; a.km = km;
-  a.Sq = Sq; a.Sk = hole ? Nk : Sk; a.H = H; a.nsplit = nsplit; a.nprob = nprob; a.koff = koff; a.hole = hole;
-  a.opart = (float*)c->ar.alloc(nprob * nsplit * Sq * DH * (int64_t)sizeof(float));
-  a.mlpart = (float*)c->ar.alloc(nprob * nsplit * Sq * 2 * (int64_t)sizeof(float));
-  if (!c->dry) {
-    const double keys = koff || hole ? (double)total_keys / (double)nseq : (double)Sk;  // keys per sequence actually present
-    ProfScope ps(c, PROF_ATTN_FWD, 4.0 * (double)nprob * Sq * keys * DH, (double)nprob * (2.0 * Sq + 2.0 * keys) * DH * 2.0);
-    ps.tag(nseq, Sk, H, Sq);
-    const int lds = 2 * img_bytes(XCHUNK) + XCHUNK * 4;
-    if (hole) xattn_fwd_kernel<true><<<(unsigned)(nprob * nsplit), 256, lds, c->stream>>>(a);
-    else xattn_fwd_kernel<false><<<(unsigned)(nprob * nsplit), 256, lds, c->stream>>>(a);
-    const int64_t nrows = nprob * Sq;
-    xattn_combine_kernel<<<(unsigned)((nrows + 3) / 4), 256, 0, c->stream>>>(a.opart, a.mlpart, nsplit, Sq, H, nrows, o, lse);
-    SPA_LAUNCH_CHECK(c);
-  }
-  c->ar.release(mk);  // stream-ordered: whatever reuses the space is launched behind the two kernels
-  return true;
+// ---- forward launchers: each launches the route attn_plan.hpp chose (never a refusal); the dry run stops in attn_launch (attention.hip)
+static void launch_xfwd(spa3d_ctx* c, const AttnDesc& d, const AttnPlan& pl, float* const part[2]) {
+  const int Sk = d.max_keys(); const int64_t nprob = d.nseq * d.H;
+  const bool hole = pl.kernel == AttnKernel::XFwdHole;
+  XAttnArgs a; a.q = (const bf16_t*)d.q; a.k = (const bf16_t*)d.k; a.v = (const bf16_t*)d.v; a.ldq = d.ldq; a.ldk = d.ldk; a.ldv = d.ldv;
+  a.sq = d.sq; a.sk = d.sk; a.km = d.km; a.Sq = d.Sq; a.Sk = hole ? d.Nk : Sk; a.H = d.H; a.nsplit = pl.nsplit; a.nprob = nprob;
+  a.koff = d.koff_dev; a.hole = d.holes_dev; a.opart = part[0]; a.mlpart = part[1];
+  const double keys = (double)d.total_keys() / (double)d.nseq;  // keys per sequence actually present
+  ProfScope ps(c, PROF_ATTN_FWD, 4.0 * (double)nprob * d.Sq * keys * DH, (double)nprob * (2.0 * d.Sq + 2.0 * keys) * DH * 2.0);
+  ps.tag(d.nseq, Sk, d.H, d.Sq);
+  const int lds = 2 * img_bytes(XCHUNK) + XCHUNK * 4;
+  if (hole) xattn_fwd_kernel<true><<<(unsigned)(nprob * pl.nsplit), 256, lds, c->stream>>>(a);
+  else xattn_fwd_kernel<false><<<(unsigned)(nprob * pl.nsplit), 256, lds, c->stream>>>(a);
+  const int64_t nrows = nprob * d.Sq;
+  xattn_combine_kernel<<<(unsigned)((nrows + 3) / 4), 256, 0, c->stream>>>(a.opart, a.mlpart, pl.nsplit, d.Sq, d.H, nrows, (bf16_t*)d.o, d.lse);
 }
-
-// cross attention over ragged key sets (tracks_to_latents on a batch with per-sample support counts): koff (device, [nseq + 1]) cuts the packed
-// key rows into sequences, Skmax = the longest.  false: shape outside the kernel (the caller then runs the sequences one by one)
-bool xattn_varlen_fwd_bf16(spa3d_ctx* c, const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq,
-                           const float* sk, int64_t nseq, int Sq, int Skmax, int H, int Dh, bf16_t* o, float* lse, const int32_t* koff,
-                           int64_t total_keys) {
-  if (Dh != DH || !koff) return false;
-  return xattn_fwd(c, q, k, v, ldq, ldk, ldv, sq, sk, nullptr, nseq, Sq, Skmax, H, o, lse, nullptr, koff, total_keys);
-}
-
-// cross attention of nseq sequences over ONE shared key set [0, Nk), sequence i leaving out rows [hole[2i], hole[2i + 1]) (device, [nseq][2]); nmax = the
-// longest sequence's key count, total_keys their sum (profiling).  false: shape outside the kernel (the caller then runs the sequences one by one)
-bool xattn_holdout_fwd_bf16(spa3d_ctx* c, const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq,
-                            const float* sk, int64_t nseq, int Sq, int Nk, int nmax, int H, int Dh, bf16_t* o, float* lse, const int32_t* hole,
-                            int64_t total_keys) {
-  if (Dh != DH || !hole || nmax < 1 || nmax > Nk) return false;
-  return xattn_fwd(c, q, k, v, ldq, ldk, ldv, sq, sk, nullptr, nseq, Sq, nmax, H, o, lse, nullptr, nullptr, total_keys, hole, Nk);
-}
-
-constexpr int ATTN_MAX_S = 320;  // K^ and V of one head resident: 2 x 320 x 192 B = 120 KiB of the CU's 160 KiB
-
-// returns false when the shape is outside what the fused kernels cover (the caller then composes the generic kernels)
-bool attn_fused_fwd_bf16(spa3d_ctx* c, const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ldq, int64_t ldk, int64_t ldv,
-                         const float* sq, const float* sk, const float* km, int64_t nseq, int Sq, int Sk, int H, int Dh, bf16_t* o,
-                         float* lse, const int32_t* seq_off, int64_t total_rows) {
-  if (Dh == DH && Sq != Sk) return xattn_fwd(c, q, k, v, ldq, ldk, ldv, sq, sk, km, nseq, Sq, Sk, H, o, lse, seq_off);
-  if (Dh != DH || Sq != Sk || Sk < 2 || Sk > ATTN_MAX_S) return false;
-  if (ldq % 8 || ldk % 8 || ldv % 8 || !al16(q) || !al16(k) || !al16(v) || !al16(o)) return false;
-  if (nseq * H > 0x7fffffffLL) return false;
-  if (c->dry) return true;
-  AttnArgs a; a.q = q; a.k = k; a.v = v; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.sq = sq; a.sk = sk; a.km = km;
-  a.S = Sk; a.H = H; a.nprob = nseq * H; a.o = o; a.lse = lse; a.seq_off = seq_off;
-  const double rows = total_rows > 0 ? (double)total_rows : (double)nseq * Sk;  // ragged: rows actually present
-  int KT = (Sk + 15) / 16;        // key / query tiles of 16; odd counts pair up (the last pair half empty) except nine (S = 129, the readout stack: its own instance)
-  if ((KT & 1) && KT != 9) KT += 1;
-  ProfScope ps(c, PROF_ATTN_FWD, 4.0 * rows * H * (rows / nseq) * Dh, rows * H * Dh * 2.0 * 4.0);
-  ps.tag(nseq, Sk, H, 0);
-  switch (KT) {
+static void launch_self_fwd(spa3d_ctx* c, const AttnDesc& d, const AttnPlan& pl) {
+  AttnArgs a; a.q = (const bf16_t*)d.q; a.k = (const bf16_t*)d.k; a.v = (const bf16_t*)d.v; a.ldq = d.ldq; a.ldk = d.ldk; a.ldv = d.ldv;
+  a.sq = d.sq; a.sk = d.sk; a.km = d.km; a.S = d.Sk; a.H = d.H; a.nprob = d.nseq * d.H; a.o = (bf16_t*)d.o; a.lse = d.lse; a.seq_off = d.seq_off;
+  const double rows = d.rows_present();  // ragged: rows actually present
+  ProfScope ps(c, PROF_ATTN_FWD, 4.0 * rows * d.H * (rows / d.nseq) * d.Dh, rows * d.H * d.Dh * 2.0 * 4.0);
+  ps.tag(d.nseq, d.Sk, d.H, 0);
+  switch (pl.KT) {
     case 2: launch_fwd<2, 4>(c, a); break;
     case 4: launch_fwd<4, 4>(c, a); break;
     case 6: launch_fwd<6, 4>(c, a); break;
@@ -528,14 +486,11 @@ bool attn_fused_fwd_bf16(spa3d_ctx* c, const bf16_t* q, const bf16_t* k, const b
     case 9: launch_fwd<9, 4>(c, a); break;
     case 10: launch_fwd<10, 4>(c, a); break;
     case 12: launch_fwd<12, 4>(c, a); break;
-    case 14: launch_fwd<14, 8>(c, a); break;   // > 80 KiB of LDS: one workgroup per CU, so eight waves
+    case 14: launch_fwd<14, 8>(c, a); break;
     case 16: launch_fwd<16, 8>(c, a); break;
     case 18: launch_fwd<18, 8>(c, a); break;
     case 20: launch_fwd<20, 8>(c, a); break;
-    default: return false;
   }
-  SPA_LAUNCH_CHECK(c);
-  return true;
 }
 
 
@@ -1148,113 +1103,100 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_split_kernel(AttnBwdArgs 
 }
 
 template <int KT>
-static void launch_bwd(spa3d_ctx* c, const AttnBwdArgs& a) {
+static void launch_bwd(spa3d_ctx* c, const AttnBwdArgs& a, AttnKernel kernel) {
   constexpr int S_pad = KT * 16;
   const int small = 4 * S_pad * 4 + 4 * DH * 4;
   const int lds4 = 4 * img_bytes(S_pad) + small + 8 * WTILE;
   auto lds2 = [&](int nw) { return 2 * img_bytes(S_pad) + small + nw * WTILE; };
-  // mode 1: four resident images, concurrent roles (S <= 160); 2: split-pass, 4 waves, two workgroups per CU; 3: split-pass, 8 waves
-  int mode = c->attn_bwd_mode;
-  if (S_pad > 160) mode = 3;  // four images + wave tiles fit 160 KiB up to S = 160
-  else if (mode == 0) mode = 1;
   static bool attr_set = false;
   if (!attr_set) {
-    if constexpr (S_pad <= 160) {
+    if constexpr (S_pad <= ATTN_BWD4_MAX_S) {
       (void)hipFuncSetAttribute((const void*)attn_bwd8_kernel<KT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds4);
       (void)hipFuncSetAttribute((const void*)attn_bwd_split_kernel<KT, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds2(4));
     }
     (void)hipFuncSetAttribute((const void*)attn_bwd_split_kernel<KT, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, lds2(8));
     attr_set = true;
   }
-  if constexpr (S_pad <= 160) {
-    if (mode == 1) {
+  if constexpr (S_pad <= ATTN_BWD4_MAX_S) {   // four resident images, concurrent roles; split-pass on 4 waves, two workgroups per CU
+    if (kernel == AttnKernel::Bwd4 || kernel == AttnKernel::Bwd4Fast) {
       static bool attrf = false;
       if (!attrf) { (void)hipFuncSetAttribute((const void*)attn_bwd8_kernel<KT, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds4); attrf = true; }
-      if (a.km) attn_bwd8_kernel<KT><<<(unsigned)std::min<int64_t>(a.nprob, 1024), 512, lds4, c->stream>>>(a);
+      if (kernel == AttnKernel::Bwd4) attn_bwd8_kernel<KT><<<(unsigned)std::min<int64_t>(a.nprob, 1024), 512, lds4, c->stream>>>(a);
       else attn_bwd8_kernel<KT, false, true><<<(unsigned)std::min<int64_t>(a.nprob, 1024), 512, lds4, c->stream>>>(a);  // no key mask: cheap score arithmetic
       return;
     }
-    if (mode == 2) { attn_bwd_split_kernel<KT, 4><<<(unsigned)std::min<int64_t>(a.nprob, 2048), 256, lds2(4), c->stream>>>(a); return; }
+    if (kernel == AttnKernel::BwdSplit4) { attn_bwd_split_kernel<KT, 4><<<(unsigned)std::min<int64_t>(a.nprob, 2048), 256, lds2(4), c->stream>>>(a); return; }
   }
   attn_bwd_split_kernel<KT, 8><<<(unsigned)std::min<int64_t>(a.nprob, 1024), 512, lds2(8), c->stream>>>(a);
 }
 
-bool attn_fused_bwd_bf16(spa3d_ctx* c, const bf16_t* q, const bf16_t* k, const bf16_t* v, int64_t ldq, int64_t ldk, int64_t ldv,
-                         const float* sq, const float* sk, const float* km, int64_t nseq, int Sq, int Sk, int H, int Dh, const bf16_t* o,
-                         const float* lse, const bf16_t* d_o, bf16_t* dq, bf16_t* dk, bf16_t* dv, float* dsq, float* dsk,
-                         const int32_t* seq_off, int64_t total_rows, const int32_t* koff, int64_t total_keys) {
-  if (koff && Dh != DH) return false;
-  if (koff || (Dh == DH && Sq != Sk)) {  // cross attention: chunked keys, see xattn_fwd_kernel (koff: ragged key sets, Sk = the longest)
-    const int nsplit = (Sk + XCHUNK - 1) / XCHUNK;
-    const int64_t nprob = nseq * H;
-    if (seq_off || !o || !lse || Sq < 1 || Sq > XCHUNK || Sk < 1 || nprob * nsplit > 0x7fffffffLL) return false;
-    if (ldq % 8 || ldk % 8 || ldv % 8 || !al16(q) || !al16(k) || !al16(v) || !al16(o) || !al16(d_o) || !al16(dq) || !al16(dk) || !al16(dv) ||
-        !al16(sq) || !al16(sk))
-      return false;
-    const int64_t mk = c->ar.mark();
-    float* dqpart = (float*)c->ar.alloc(nprob * nsplit * Sq * DH * (int64_t)sizeof(float));
-    if (!c->dry) {
-      AttnBwdArgs a; a.q = q; a.k = k; a.v = v; a.o = o; a.d_o = d_o; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.sq = sq; a.sk = sk; a.km = km;
-      a.lse = lse; a.S = Sq; a.H = H; a.nprob = nprob; a.dq = dq; a.dk = dk; a.dv = dv; a.dsq = dsq; a.dsk = dsk; a.seq_off = koff;
-      a.Sk = Sk; a.nsplit = nsplit; a.dqpart = dqpart; a.det = c->det;
+static AttnBwdArgs bwd_args(spa3d_ctx* c, const AttnDesc& d) {
+  AttnBwdArgs a; a.q = (const bf16_t*)d.q; a.k = (const bf16_t*)d.k; a.v = (const bf16_t*)d.v; a.o = (const bf16_t*)d.o; a.d_o = (const bf16_t*)d.d_o;
+  a.ldq = d.ldq; a.ldk = d.ldk; a.ldv = d.ldv; a.sq = d.sq; a.sk = d.sk; a.km = d.km; a.lse = d.lse; a.H = d.H; a.nprob = d.nseq * d.H;
+  a.dq = (bf16_t*)d.dq; a.dk = (bf16_t*)d.dk; a.dv = (bf16_t*)d.dv; a.dsq = d.dsq; a.dsk = d.dsk; a.det = c->det;
 #if SPA3D_ABL_ATTN
-      a.ablate = 0;
+  a.ablate = 0;
 #endif
-      const double keys = koff ? (double)total_keys / (double)nseq : (double)Sk;
-      ProfScope ps(c, PROF_ATTN_BWD, 14.0 * (double)nprob * Sq * keys * DH, (double)nprob * (4.0 * Sq + 4.0 * keys) * DH * 2.0);
-      ps.tag(nseq, Sk, H, Sq);
-      constexpr int KT = XCHUNK / 16;
-      const int lds4 = 4 * img_bytes(XCHUNK) + 4 * XCHUNK * 4 + 4 * DH * 4 + 8 * WTILE;
-      static bool attr_set = false;
-      if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)attn_bwd8_kernel<KT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds4);
-        (void)hipFuncSetAttribute((const void*)attn_bwd8_kernel<KT, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds4);
-        attr_set = true;
-      }
-      if (koff) {  // chunks past a sequence's keys write nothing: their dq^ partials are these zeros
-        (void)hipMemsetAsync(dqpart, 0, (size_t)(nprob * nsplit * Sq * DH) * sizeof(float), c->stream);
-        attn_bwd8_kernel<KT, true, false, true><<<(unsigned)std::min<int64_t>(nprob * nsplit, 1024), 512, lds4, c->stream>>>(a);
-      }
-      else attn_bwd8_kernel<KT, true><<<(unsigned)std::min<int64_t>(nprob * nsplit, 1024), 512, lds4, c->stream>>>(a);
-      const int64_t nrows = nprob * Sq;
-      xattn_dq_finish_kernel<<<(unsigned)std::min<int64_t>((nrows + 3) / 4, 512), 256, 0, c->stream>>>(dqpart, nsplit, Sq, H, nrows, q, ldq, sq, dq, dsq, c->det);
-      SPA_LAUNCH_CHECK(c);
-    }
-    c->ar.release(mk);
-    return true;
+  return a;
+}
+// cross attention: chunked keys, see xattn_fwd_kernel (ragged key sets: AttnBwdArgs::seq_off holds the KEY offsets, Sk the longest sequence's count)
+static void launch_xbwd(spa3d_ctx* c, const AttnDesc& d, const AttnPlan& pl, float* dqpart) {
+  const bool rk = pl.kernel == AttnKernel::XBwdRaggedKeys;
+  const int Sk = d.max_keys(), Sq = d.Sq, nsplit = pl.nsplit;
+  AttnBwdArgs a = bwd_args(c, d);
+  a.S = Sq; a.seq_off = d.koff_dev; a.Sk = Sk; a.nsplit = nsplit; a.dqpart = dqpart;
+  const int64_t nprob = a.nprob;
+  const double keys = (double)d.total_keys() / (double)d.nseq;
+  ProfScope ps(c, PROF_ATTN_BWD, 14.0 * (double)nprob * Sq * keys * DH, (double)nprob * (4.0 * Sq + 4.0 * keys) * DH * 2.0);
+  ps.tag(d.nseq, Sk, d.H, Sq);
+  constexpr int KT = XCHUNK / 16;
+  const int lds4 = 4 * img_bytes(XCHUNK) + 4 * XCHUNK * 4 + 4 * DH * 4 + 8 * WTILE;
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void*)attn_bwd8_kernel<KT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds4);
+    (void)hipFuncSetAttribute((const void*)attn_bwd8_kernel<KT, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds4);
+    attr_set = true;
   }
-  if (Dh != DH || Sq != Sk || Sk < 2 || Sk > ATTN_MAX_S || !o || !lse) return false;
-  if (ldq % 8 || ldk % 8 || ldv % 8 || !al16(q) || !al16(k) || !al16(v) || !al16(o) || !al16(d_o) || !al16(dq) || !al16(dk) || !al16(dv) ||
-      !al16(sq) || !al16(sk))
-    return false;
-  if (nseq * H > 0x7fffffffLL) return false;   // the kernels index problems in 32 bits
-  if (c->dry) return true;
-  AttnBwdArgs a; a.q = q; a.k = k; a.v = v; a.o = o; a.d_o = d_o; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.sq = sq; a.sk = sk; a.km = km;
-  a.lse = lse; a.S = Sk; a.H = H; a.nprob = nseq * H; a.dq = dq; a.dk = dk; a.dv = dv; a.dsq = dsq; a.dsk = dsk; a.seq_off = seq_off;
-  a.Sk = Sk; a.nsplit = 1; a.dqpart = nullptr; a.det = c->det;
-  const double rows = total_rows > 0 ? (double)total_rows : (double)nseq * Sk;
+  if (rk) {  // chunks past a sequence's keys write nothing: their dq^ partials are these zeros
+    (void)hipMemsetAsync(dqpart, 0, (size_t)(nprob * nsplit * Sq * DH) * sizeof(float), c->stream);
+    attn_bwd8_kernel<KT, true, false, true><<<(unsigned)std::min<int64_t>(nprob * nsplit, 1024), 512, lds4, c->stream>>>(a);
+  }
+  else attn_bwd8_kernel<KT, true><<<(unsigned)std::min<int64_t>(nprob * nsplit, 1024), 512, lds4, c->stream>>>(a);
+  const int64_t nrows = nprob * Sq;
+  xattn_dq_finish_kernel<<<(unsigned)std::min<int64_t>((nrows + 3) / 4, 512), 256, 0, c->stream>>>(dqpart, nsplit, Sq, d.H, nrows, a.q, d.ldq, d.sq, a.dq, d.dsq, c->det);
+}
+static void launch_self_bwd(spa3d_ctx* c, const AttnDesc& d, const AttnPlan& pl) {
+  AttnBwdArgs a = bwd_args(c, d);
+  a.S = d.Sk; a.seq_off = d.seq_off; a.Sk = d.Sk; a.nsplit = 1; a.dqpart = nullptr;
+  const double rows = d.rows_present();
 #if SPA3D_ABL_ATTN
   { const char* e = getenv("SPA3D_ABLATE"); a.ablate = e ? atoi(e) : 0; }
 #endif
-  // even tile counts only: the tile routines take an odd KT (the last pair half empty, as in the forward's nine-tile instance), but at S = 129 the backward
-  // measured the same with nine tiles as with ten (3.43 vs 3.44-3.6 ms: its third ROUND of tiles, not the tenth key tile, is what S = 129 pays for there)
-  const int KT = ((Sk + 31) / 32) * 2;
-  ProfScope ps(c, PROF_ATTN_BWD, 14.0 * rows * H * (rows / nseq) * Dh, rows * H * Dh * 2.0 * 8.0);
-  ps.tag(nseq, Sk, H, 0);
-  switch (KT) {
-    case 2: launch_bwd<2>(c, a); break;
-    case 4: launch_bwd<4>(c, a); break;
-    case 6: launch_bwd<6>(c, a); break;
-    case 8: launch_bwd<8>(c, a); break;
-    case 10: launch_bwd<10>(c, a); break;
-    case 12: launch_bwd<12>(c, a); break;
-    case 14: launch_bwd<14>(c, a); break;
-    case 16: launch_bwd<16>(c, a); break;
-    case 18: launch_bwd<18>(c, a); break;
-    case 20: launch_bwd<20>(c, a); break;
-    default: return false;
+  ProfScope ps(c, PROF_ATTN_BWD, 14.0 * rows * d.H * (rows / d.nseq) * d.Dh, rows * d.H * d.Dh * 2.0 * 8.0);
+  ps.tag(d.nseq, d.Sk, d.H, 0);
+  switch (pl.KT) {
+    case 2: launch_bwd<2>(c, a, pl.kernel); break;
+    case 4: launch_bwd<4>(c, a, pl.kernel); break;
+    case 6: launch_bwd<6>(c, a, pl.kernel); break;
+    case 8: launch_bwd<8>(c, a, pl.kernel); break;
+    case 10: launch_bwd<10>(c, a, pl.kernel); break;
+    case 12: launch_bwd<12>(c, a, pl.kernel); break;
+    case 14: launch_bwd<14>(c, a, pl.kernel); break;
+    case 16: launch_bwd<16>(c, a, pl.kernel); break;
+    case 18: launch_bwd<18>(c, a, pl.kernel); break;
+    case 20: launch_bwd<20>(c, a, pl.kernel); break;
+  }
+}
+
+// Launches a fused route of plan_attn_fwd / plan_attn_bwd (attn_plan.hpp): no refusal and no dry run reach it (attn_launch, attention.hip, which also takes the
+// route's fp32 partials `part` from the arena)
+void attn_fused_launch(spa3d_ctx* c, const AttnDesc& d, const AttnPlan& pl, float* const part[2]) {
+  switch (pl.kernel) {
+    case AttnKernel::SelfFwd: launch_self_fwd(c, d, pl); break;
+    case AttnKernel::XFwd: case AttnKernel::XFwdRaggedKeys: case AttnKernel::XFwdHole: launch_xfwd(c, d, pl, part); break;
+    case AttnKernel::XBwd: case AttnKernel::XBwdRaggedKeys: launch_xbwd(c, d, pl, part[0]); break;
+    default: launch_self_bwd(c, d, pl); break;
   }
   SPA_LAUNCH_CHECK(c);
-  return true;
 }
 }  // namespace SPA_NS

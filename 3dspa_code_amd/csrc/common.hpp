@@ -9,6 +9,7 @@
 #include "../../include/spa3d.h"
 #include "ablate.inc"  // every work-skipping diagnostic mask, all 0 in libspa3d_hip.so
 #include "gemm_plan.hpp"  // GemmDesc and the kernel choice (host-only)
+#include "attn_plan.hpp"  // AttnDesc and the attention kernel choice (host-only)
 #include "score_row.hpp"  // per-track score arithmetic (host- and device-callable)
 #include "loss_point.hpp"  // the training objective at one point (host- and device-callable)
 
@@ -243,7 +244,7 @@ struct spa3d_ctx {
   bool dry = false;   // orchestration runs without launching (workspace sizing)
   int hip_err = 0;
   GemmPolicy gemm;    // "gemm_impl": which kernels the GEMMs may run on (gemm_plan.hpp)
-  int attn_impl = 0;  // 0 auto, 1 generic, 2 fused (see apply_attn_impl)
+  AttnPolicy attn;    // "attn_impl": which kernels the attentions may run on (attn_plan.hpp)
   int chunk = 0;      // samples per chunk: 0 = as many as fit the workspace (spa3d_set_option "chunk")
   int query_chunk = 0;    // spa3d_set_option "query_chunk": readout over chunks of this many queries (0 = all Q at once); implies one sample per chunk
   int track_chunk = 0;    // spa3d_set_option "track_chunk": track encoder over chunks of this many tracks, recomputed in the backward (0 = off); one sample per chunk
@@ -256,10 +257,6 @@ struct spa3d_ctx {
   bool last_chunk = false;
   const float* loss_scale_state = nullptr;  // caller-owned device float (spa3d_set_loss_scale_state): dynamic multiplier of the loss scale
   double plan_stats[4] = {0, 0, 0, 0};  // last train call: encoder rows kept, encoder rows dense, readout slots, queries (spa3d_plan_stats)
-  // attention kernel-choice knobs behind attn_impl (spa3d_set_option; values 3+ are test hooks)
-  int attn_bwd_mode = 0;  // fused attention backward structure: 0 auto (1 up to S = 160, else 3), 1 four images + concurrent roles, 2 split-pass 4 waves, 3 split-pass 8 waves
-  int qkv_attn = 0;       // track-encoder QKV projection + attention forward as ONE kernel (qkv_attn.hip): built and measured in round 5, 1.47x SLOWER than the
-                          // projection GEMM + attention kernel pair (profiles/r05_qkv_attn_fused.log), so opt-in only: attn_impl 6
   int det_grads = 0;      // spa3d_set_option "det_grads": order-independent parameter gradients (fixed-point shadow accumulation, DetCfg above); costs a few %
   const DetCfg* det = nullptr;  // the running det_grads train call's mode, in its workspace, passed to every kernel that adds into G; nullptr = float atomics
   // spa3d_set_counts: per-sample live support tracks / live queries of the next calls' batch (host copies; cnt_B entries each)
@@ -274,14 +271,6 @@ struct spa3d_ctx {
                           // track encoder, state_init leaves) is frozen, 2: [0, b2) (the latent stacks too); run_chunk (model.hip) skips the stages whole
   Prof prof;
 };
-
-// attn_impl: 0 product dispatch | 1 generic composition (GEMMs + softmax kernels) | 2 fused kernels (ops: error when unusable) | 3 / 4 fused with the
-// split-pass backward on 4 / 8 waves also where the four-image kernel would run (S <= 160; tests) | 6 fused kernels with the track encoder's QKV projection + attention forward as ONE launch (qkv_attn.hip)
-inline void apply_attn_impl(spa3d_ctx* c, int v) {
-  c->attn_impl = v == 1 ? 1 : (v >= 2 ? 2 : 0);
-  c->attn_bwd_mode = v == 3 ? 2 : (v == 4 ? 3 : 0);
-  c->qkv_attn = v == 6;   // 6 = the fused kernels with the round-5 QKV projection + attention forward (opt-in: measured slower)
-}
 
 // ---- the scaffold of a call: sizing walk, sized call, query counts, live rows ----
 // Peak arena bytes of `body` walked with launches off (c->dry) against a counting arena; the arena and the mode come back as they were.
@@ -376,11 +365,12 @@ void gemm_ntb(spa3d_ctx* c, const GemmDesc& d);
 int64_t gemm_rs_pack_elems(int N);
 template <typename S> void gemm_rs_pack(spa3d_ctx* c, const S* w, int64_t sk, int64_t sn, int N, bf16_t* wpk);
 void gemm_rs(spa3d_ctx* c, const GemmDesc& d);
-// QKV projection + attention forward of one (sequence, head) per workgroup pass (qkv_attn.hip): d = 384, Dh = 96, S <= 160; false = shape not covered
+// QKV projection + attention forward of one (sequence, head) per workgroup pass (qkv_attn.hip): the weight stream, and the launcher of plan_qkv_attn's QkvFwd
 int64_t qkv_attn_pack_elems(int H);
 template <typename S> void qkv_attn_pack(spa3d_ctx* c, const S* wq, const S* wk, const S* wv /* [384][E] */, int E, int H, bf16_t* wpk);
-bool qkv_attn_fwd(spa3d_ctx* c, const bf16_t* nq, int64_t ldn, const bf16_t* wpk, const float* sq, const float* sk, const float* km, int64_t nseq, int S, int H,
-                  int Dh, int d, bf16_t* qkv, bf16_t* o, float* lse, const int32_t* seq_off, int64_t total_rows);
+void qkv_attn_launch(spa3d_ctx* c, const AttnDesc& d);
+// the fused attention kernels (attention_fused.hip): launches a fused route of plan_attn_fwd / plan_attn_bwd; `part`: the plan's fp32 partials
+void attn_fused_launch(spa3d_ctx* c, const AttnDesc& d, const AttnPlan& pl, float* const part[2]);
 // sequence-resident MLP forward for d = 384, mlp = 1536 (mlp_fused.hip): y = a + MLP(na), h / hpre kept; launched when plan_mlp says MlpFused
 template <typename S> void mlp_fused_pack(spa3d_ctx* c, const S* w_in /*[384][1536]*/, const S* w_out /*[1536][384]*/, bf16_t* wpk);
 int64_t mlp_fused_pack_elems();
@@ -405,25 +395,11 @@ template <typename T> void gemm_launch(spa3d_ctx* c, const GemmDesc& d, GemmKern
 template <typename T> void k_layernorm(spa3d_ctx*, const T* x, const float* scale, T* y, float* stats, int64_t rows, int d);
 template <typename T> void k_layernorm_bwd(spa3d_ctx*, const T* x, const float* scale, const float* stats, const T* dy, T* dx,
                                            float* dscale, int64_t rows, int d, const T* add);
-// attention.hip: the attention front ends (generic composition or the fused kernels of attention_fused.hip, by impl)
-template <typename T>
-void attention_fwd(spa3d_ctx* c, const T* q, const T* k, const T* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq,
-                   const float* sk, const float* km, int64_t nseq, int Sq, int Sk, int H, int Dh, T* o, float* lse, int impl,
-                   const int32_t* seq_off = nullptr, int64_t total_rows = 0);
-template <typename T>
-void attention_bwd(spa3d_ctx* c, const T* q, const T* k, const T* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq,
-                   const float* sk, const float* km, int64_t nseq, int Sq, int Sk, int H, int Dh, const T* o, const float* lse, const T* d_o,
-                   T* dq, T* dk, T* dv, float* dsq, float* dsk, int impl, const int32_t* seq_off = nullptr, int64_t total_rows = 0);
-template <typename T>
-void attention_varlen_fwd(spa3d_ctx* c, const T* q, const T* k, const T* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq, const float* sk,
-                          int64_t nseq, int Sq, const int32_t* koff_host, const int32_t* koff_dev, int H, int Dh, T* o, float* lse, int impl);
-template <typename T>
-void attention_varlen_bwd(spa3d_ctx* c, const T* q, const T* k, const T* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq, const float* sk,
-                          int64_t nseq, int Sq, const int32_t* koff_host, const int32_t* koff_dev, int H, int Dh, const T* o, const float* lse,
-                          const T* d_o, T* dq, T* dk, T* dv, float* dsq, float* dsk, int impl);
-template <typename T>
-void attention_holdout_fwd(spa3d_ctx* c, const T* q, const T* k, const T* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq, const float* sk,
-                           int64_t nseq, int Sq, int Nk, const int32_t* holes_host, const int32_t* holes_dev, int H, int Dh, T* o, float* lse, int impl);
+// attention.hip: the attention front ends -- plan (attn_plan.hpp), then the fused launchers, the generic composition (whole, or sequence by sequence for
+// ragged keys / a hole) or the refusal's error; and the launch of a fused plan, which in the dry run only takes the plan's partials from the arena
+template <typename T> void attention_fwd(spa3d_ctx* c, const AttnDesc& d);
+template <typename T> void attention_bwd(spa3d_ctx* c, const AttnDesc& d);
+void attn_launch(spa3d_ctx* c, const AttnDesc& d, const AttnPlan& pl);
 // embed.hip
 template <typename T> void k_sin_embed(spa3d_ctx*, const float* x, int64_t rows, int C, int nf, float prescale, T* out);
 template <typename T> void k_embed_tokens(spa3d_ctx*, const float* tracks, int64_t nrows, int T_, int nf, float prescale, T* sinbuf, int NC = 3);

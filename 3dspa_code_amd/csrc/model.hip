@@ -170,7 +170,7 @@ template <typename T> struct Net {
           w.mlp_pk = alloc<T>(mlp_fused_pack_elems());
           mlp_fused_pack<float>(c, w.mlp_in.src[0], w.mlp_out.src[0], w.mlp_pk);
         }
-        if (c->qkv_attn && !c->gemm.generic && c->attn_impl != 1 && !w.cross && d == 384 && Dh == 96) {
+        if (plan_qkv_pack(c->attn, c->gemm.generic, w.cross, d, Dh)) {
           w.qkv_pk = alloc<T>(qkv_attn_pack_elems(H));
           qkv_attn_pack<float>(c, w.qkv.src[0], w.qkv.src[1], w.qkv.src[2], E, H, w.qkv_pk);
         }
@@ -260,15 +260,27 @@ template <typename T> struct Net {
     }
   }
 
-  // ------------------------------------------------------------------ attention core (attention.hip)
-  void attn_fwd(const T* q, const T* k, const T* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq, const float* sk,
-                const float* km, int64_t nseq, int Sq, int Sk, T* o, float* lse, const Rag& rg = Rag()) {
-    attention_fwd<T>(c, q, k, v, ldq, ldk, ldv, sq, sk, km, nseq, Sq, Sk, H, Dh, o, lse, c->attn_impl, rg.off, rg.rows);
+  // ------------------------------------------------------------------ attention core (attention.hip): the descriptors of a block's two attentions
+  // qkv [rows][3 E] = q | k | v; the backward adds d_o and dqkv in qkv's layout.  rg: ragged rows after token pruning
+  AttnDesc self_desc(const BlockW<T>& w, const T* qkv, T* o, float* lse, const float* km, int64_t nseq, int S, const Rag& rg, const T* d_o = nullptr,
+                     T* dqkv = nullptr) {
+    AttnDesc a;
+    a.q = qkv; a.k = qkv + E; a.v = qkv + 2 * E; a.ldq = a.ldk = a.ldv = 3 * E; a.sq = w.sq; a.sk = w.sk; a.km = km; a.o = o; a.lse = lse;
+    a.nseq = nseq; a.Sq = a.Sk = S; a.H = H; a.Dh = Dh; a.esz = (int)sizeof(T);
+    if (rg.off) { a.layout = AttnLayout::RaggedRows; a.seq_off = rg.off; a.total_rows = rg.rows; }
+    if (d_o) { a.d_o = d_o; a.dq = dqkv; a.dk = dqkv + E; a.dv = dqkv + 2 * E; a.dsq = w.g_sq; a.dsk = w.g_sk; }
+    return a;
   }
-  void attn_bwd(const T* q, const T* k, const T* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq, const float* sk,
-                const float* km, int64_t nseq, int Sq, int Sk, const T* o, const float* lse, const T* d_o, T* dq, T* dk, T* dv,
-                float* dsq, float* dsk, const Rag& rg = Rag()) {
-    attention_bwd<T>(c, q, k, v, ldq, ldk, ldv, sq, sk, km, nseq, Sq, Sk, H, Dh, o, lse, d_o, dq, dk, dv, dsq, dsk, c->attn_impl, rg.off, rg.rows);
+  // cq [rows][E], ckv [keys][2 E] = k | v: Skv keys per sequence, or ragged key sets (koff_h / koff_d), or one shared key set with a hole per sequence (hl)
+  AttnDesc cross_desc(const BlockW<T>& w, const T* cq, const T* ckv, T* co, float* clse, int64_t nseq, int S, int Skv, const int32_t* koff_h,
+                      const int32_t* koff_d, const Holes* hl, const T* d_o = nullptr, T* dcq = nullptr, T* dckv = nullptr) {
+    AttnDesc a;
+    a.q = cq; a.k = ckv; a.v = ckv + E; a.ldq = E; a.ldk = a.ldv = 2 * E; a.sq = w.csq; a.sk = w.csk; a.o = co; a.lse = clse;
+    a.nseq = nseq; a.Sq = S; a.Sk = Skv; a.H = H; a.Dh = Dh; a.esz = (int)sizeof(T);
+    if (hl) { a.layout = AttnLayout::Hole; a.holes_host = hl->host; a.holes_dev = hl->dev; a.Nk = hl->Nk; }
+    else if (koff_h) { a.layout = AttnLayout::RaggedKeys; a.koff_host = koff_h; a.koff_dev = koff_d; }
+    if (d_o) { a.d_o = d_o; a.dq = dcq; a.dk = dckv; a.dv = dckv + E; a.dsq = w.g_csq; a.dsk = w.g_csk; }
+    return a;
   }
 
   // ------------------------------------------------------------------ ImprovedTransformerBlock (attention.py:67-108)
@@ -296,14 +308,14 @@ template <typename T> struct Net {
       qkv = alloc<T>(Mg * 3 * E);
     }
     T* o = alloc<T>(Mg * E); float* lse = alloc<float>(M * H * 2);
-    bool qa = false;
-    if constexpr (sizeof(T) == 2) {  // :154-175 as ONE kernel per (sequence, head): q | k | v are written once and never read back by the forward
-      if (!sh && w.qkv_pk && S <= 160)   // (opt-in: attn_impl 6)
-        qa = qkv_attn_fwd(c, nq, d, w.qkv_pk, w.sq, w.sk, km, nseq, S, H, Dh, d, qkv, o, lse, rg.off, rg.off ? rg.rows : 0);
-    }
-    if (!qa) {
+    AttnDesc sa = self_desc(w, qkv, o, lse, km, nseq, S, rg);
+    if (!sh) { sa.x = nq; sa.ldx = d; sa.d = d; sa.qkv_pk = w.qkv_pk; }
+    // :154-175 as ONE kernel per (sequence, head): q | k | v are written once and never read back by the forward (opt-in: attn_impl 6)
+    const AttnPlan qa = plan_qkv_attn(sa, c->attn);
+    if (qa.kernel == AttnKernel::QkvFwd) attn_launch(c, sa, qa);
+    else {
       if (!sh) lin_fwd(w.qkv, nq, qkv, Mg);                                              // :154-173
-      attn_fwd(qkv, qkv + E, qkv + 2 * E, 3 * E, 3 * E, 3 * E, w.sq, w.sk, km, nseq, S, S, o, lse, rg);  // :166-175
+      attention_fwd<T>(c, sa);                                                           // :166-175
     }
     T* a = alloc<T>(Mg * d);
     lin_fwd(w.out, o, a, Mg, EPI_NONE, x);                                              // :178-183 + residual :79,90
@@ -313,9 +325,7 @@ template <typename T> struct Net {
       const int64_t nkv = hl ? hl->Nk : (koff_h ? koff_h[nseq] : nseq * Skv);  // (shared keys: projected ONCE, not per sequence)
       ckv = alloc<T>(nkv * 2 * E); lin_fwd(w.ckv, kv, ckv, nkv);
       co = alloc<T>(M * E); clse = alloc<float>(M * H * 2);
-      if (hl) attention_holdout_fwd<T>(c, cq, ckv, ckv + E, E, 2 * E, 2 * E, w.csq, w.csk, nseq, S, hl->Nk, hl->host, hl->dev, H, Dh, co, clse, c->attn_impl);
-      else if (koff_h) attention_varlen_fwd<T>(c, cq, ckv, ckv + E, E, 2 * E, 2 * E, w.csq, w.csk, nseq, S, koff_h, koff_d, H, Dh, co, clse, c->attn_impl);
-      else attn_fwd(cq, ckv, ckv + E, E, 2 * E, 2 * E, w.csq, w.csk, nullptr, nseq, S, Skv, co, clse);
+      attention_fwd<T>(c, cross_desc(w, cq, ckv, co, clse, nseq, S, Skv, koff_h, koff_d, hl));
       lin_fwd(w.cout, co, a, M, EPI_NONE, a);
     }
     T* na = alloc<T>(Mg * d); float* st2 = alloc<float>(Mg * 2);
@@ -353,8 +363,7 @@ template <typename T> struct Net {
     T* d_o = alloc<T>(Mg * E);
     lin_bwd_x(w.out, da, d_o, Mg);
     T* dqkv = alloc<T>(Mg * 3 * E);
-    attn_bwd(s.qkv, s.qkv + E, s.qkv + 2 * E, 3 * E, 3 * E, 3 * E, w.sq, w.sk, km, nseq, S, S, s.o, s.lse, d_o, dqkv, dqkv + E,
-             dqkv + 2 * E, w.g_sq, w.g_sk, rg);
+    attention_bwd<T>(c, self_desc(w, s.qkv, s.o, s.lse, km, nseq, S, rg, d_o, dqkv));
     if (sh && sh->probe) {  // sizing pass: the Share branch's transients at its largest admissible slot count, then the dense path
       const int64_t MUg = (sh->rows(nseq, S) + 7) & ~int64_t(7), mk2 = c->ar.mark();
       (void)alloc<T>(MUg * 3 * E); (void)alloc<T>(MUg * d); (void)alloc<T>(MUg * d);
@@ -382,11 +391,8 @@ template <typename T> struct Net {
       T* dcq = dqkv;                  // reuse [M,E]
       const int64_t nkv = koff_h ? koff_h[nseq] : nseq * Skv;
       T* dckv = alloc<T>(nkv * 2 * E);
-      if (koff_h) attention_varlen_bwd<T>(c, s.cq, s.ckv, s.ckv + E, E, 2 * E, 2 * E, w.csq, w.csk, nseq, S, koff_h, koff_d, H, Dh, s.co, s.clse, d_o,
-                                          dcq, dckv, dckv + E, w.g_csq, w.g_csk, c->attn_impl);
-      else attn_bwd(s.cq, s.ckv, s.ckv + E, E, 2 * E, 2 * E, w.csq, w.csk, nullptr, nseq, S, Skv, s.co, s.clse, d_o, dcq, dckv, dckv + E,
-               w.g_csq, w.g_csk);
-      // attn_bwd writes dq with stride ldq = E into dcq: dense [M,E]
+      attention_bwd<T>(c, cross_desc(w, s.cq, s.ckv, s.co, s.clse, nseq, S, Skv, koff_h, koff_d, nullptr, d_o, dcq, dckv));
+      // the backward writes dq with stride ldq = E into dcq: dense [M,E]
       lin_bwd_w(w.cq, s.nq, dcq, M);
       lin_bwd_x(w.cq, dcq, dnq, M, nullptr, 1);
       lin_bwd_w(w.ckv, kv, dckv, nkv);
@@ -547,7 +553,7 @@ template <typename T> struct Net {
     // Token pruning (3DSPA, fused 16-bit attention): a frame token whose key is masked is attended to by nobody, and only token 0 leaves
     // the stack (3d:187-188), so its row influences neither the output nor any gradient: the encoder runs on the kept rows only.
     k.enc_rg = Rag(); k.row_src = nullptr;
-    const bool can_prune = !twoD && c->prune && sizeof(T) == 2 && Dh == 96 && S <= 320 && c->attn_impl != 1;
+    const bool can_prune = !twoD && c->prune && attn_takes_ragged_self(c->attn, S, Dh, (int)sizeof(T));
     if (can_prune) {
       int32_t* cnt = alloc<int32_t>(nseq); int32_t* off = alloc<int32_t>(nseq + 1); k.row_src = alloc<int32_t>(nseq * S);
       const int64_t kept = k_prune_plan(c, k.km, nseq, S, cnt, off, k.row_src);
@@ -1362,7 +1368,7 @@ int spa3d_create(const spa3d_config* cfg, spa3d_handle* out) {
   if (cfg->precision == SPA3D_F16) c->loss_scale = -16.f;
   // the ten switches (include/spa3d.h, spa3d_set_option) may be preset from the environment; nothing else is read from it
   const char* e = getenv("SPA3D_GEMM_IMPL"); if (e) set_gemm_impl(c, atoi(e));
-  e = getenv("SPA3D_ATTN_IMPL"); if (e) apply_attn_impl(c, atoi(e));
+  e = getenv("SPA3D_ATTN_IMPL"); if (e) c->attn = AttnPolicy::from_impl(atoi(e));
   e = getenv("SPA3D_LOSS_SCALE"); if (e && cfg->precision == SPA3D_F16) c->loss_scale = (float)atof(e);
   e = getenv("SPA3D_PRUNE"); if (e) c->prune = atoi(e);
   e = getenv("SPA3D_RO_SHARE"); if (e) c->ro_share = atoi(e);
@@ -1530,7 +1536,7 @@ int spa3d_set_option(spa3d_handle h, const char* name, double value) {
   if (n == "prune") h->prune = value != 0;
   else if (n == "ro_share") h->ro_share = value != 0;
   else if (n == "loss_scale") { if (h->cfg.precision != SPA3D_F16) { h->err = "loss_scale applies to SPA3D_F16 handles only"; return SPA3D_ERR_ARG; } h->loss_scale = (float)value; }
-  else if (n == "attn_impl") apply_attn_impl(h, (int)value);
+  else if (n == "attn_impl") h->attn = AttnPolicy::from_impl((int)value);
   else if (n == "gemm_impl") set_gemm_impl(h, (int)value);
   else if (n == "chunk") {
     if (value > 1 && (h->query_chunk > 0 || h->track_chunk > 0)) { h->err = "\"chunk\" > 1 cannot be combined with \"query_chunk\" / \"track_chunk\""; return SPA3D_ERR_ARG; }

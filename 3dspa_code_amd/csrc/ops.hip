@@ -100,6 +100,18 @@ template <typename F> static int op_with_offsets(OpCtx& c, const int32_t* host, 
   body();
   return c.status();
 }
+
+// the attention entry points' descriptor (attn_plan.hpp): the operands every form shares; a form adds its layout, the backward its gradients
+AttnDesc op_attn_desc(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* sq, const float* sk, const float* km,
+                      int64_t nseq, int Sq, int Sk, int H, int Dh, const void* o, const float* lse, int32_t dtype) {
+  AttnDesc a;
+  a.q = q; a.k = k; a.v = v; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.sq = sq; a.sk = sk; a.km = km; a.o = const_cast<void*>(o); a.lse = const_cast<float*>(lse);
+  a.nseq = nseq; a.Sq = Sq; a.Sk = Sk; a.H = H; a.Dh = Dh; a.esz = dtype == SPA3D_F32 ? 4 : 2;
+  return a;
+}
+void op_attn_grads(AttnDesc& a, const void* d_o, void* dq, void* dk, void* dv, float* dsq, float* dsk) {
+  a.d_o = d_o; a.dq = dq; a.dk = dk; a.dv = dv; a.dsq = dsq; a.dsk = dsk;
+}
 }  // namespace
 }  // namespace SPA_NS
 
@@ -176,8 +188,14 @@ SPA3D_OP(spa3d_op_qkv_attention)(const void* nq, int64_t ldn, const void* wq, co
   OpCtx c(stream, ws, ws_bytes);
   bf16_t* wpk = c.alloc<bf16_t>(qkv_attn_pack_elems(H));
   if (c.ar.overflow) return SPA3D_ERR_WORKSPACE;
-  qkv_attn_pack<bf16_t>(&c, (const bf16_t*)wq, (const bf16_t*)wk, (const bf16_t*)wv, H * 96, H, wpk);
-  if (!qkv_attn_fwd(&c, (const bf16_t*)nq, ldn, wpk, scale_q, scale_k, keymask, nseq, S, H, 96, 384, (bf16_t*)qkv, (bf16_t*)o, lse, seq_off, 0)) return SPA3D_ERR_ARG;
+  qkv_attn_pack<bf16_t>(&c, (const bf16_t*)wq, (const bf16_t*)wk, (const bf16_t*)wv, H * ATTN_DH, H, wpk);
+  const int E = H * ATTN_DH;
+  AttnDesc a = op_attn_desc(qkv, (const bf16_t*)qkv + E, (const bf16_t*)qkv + 2 * E, 3 * E, 3 * E, 3 * E, scale_q, scale_k, keymask, nseq, S, S, H, ATTN_DH, o, lse, dtype);
+  if (seq_off) { a.layout = AttnLayout::RaggedRows; a.seq_off = seq_off; }
+  a.x = nq; a.ldx = ldn; a.d = QKVA_D; a.qkv_pk = wpk;
+  const AttnPlan pl = plan_qkv_attn(a, AttnPolicy::from_impl(6));
+  if (pl.kernel != AttnKernel::QkvFwd) return SPA3D_ERR_ARG;
+  attn_launch(&c, a, pl);
   return c.status();
 }
 
@@ -203,9 +221,9 @@ SPA3D_OP(spa3d_op_attention)(const void* q, const void* k, const void* v, int64_
   FWD16(spa3d_op_attention, q, k, v, ldq, ldk, ldv, scale_q, scale_k, keymask, nseq, Sq, Sk, H, Dh, o, lse, dtype, impl, ws, ws_bytes, stream)
   if (!q || !k || !v || !o || !scale_q || !scale_k || Dh > 128) return SPA3D_ERR_ARG;
   OpCtx c(stream, ws, ws_bytes);
-  apply_attn_impl(&c, impl);
-  OP_BY_DTYPE(dtype, attention_fwd<T>(&c, (const T*)q, (const T*)k, (const T*)v, ldq, ldk, ldv, scale_q, scale_k, keymask, nseq, Sq, Sk, H, Dh, (T*)o, lse,
-                                      c.attn_impl));
+  c.attn = AttnPolicy::from_impl(impl);
+  const AttnDesc a = op_attn_desc(q, k, v, ldq, ldk, ldv, scale_q, scale_k, keymask, nseq, Sq, Sk, H, Dh, o, lse, dtype);
+  OP_BY_DTYPE(dtype, attention_fwd<T>(&c, a));
   return c.status();
 }
 SPA3D_OP(spa3d_op_attention_holdout)(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* scale_q,
@@ -218,12 +236,13 @@ SPA3D_OP(spa3d_op_attention_holdout)(const void* q, const void* k, const void* v
     if (lo < 0 || hi > Nk || lo > hi || hi - lo >= Nk) return SPA3D_ERR_ARG;
   }
   OpCtx c(stream, ws, ws_bytes);
-  apply_attn_impl(&c, impl);
+  c.attn = AttnPolicy::from_impl(impl);
   int32_t* hd = c.alloc<int32_t>(2 * nseq);
   if (c.ar.overflow) return SPA3D_ERR_WORKSPACE;
   k_set_i32(&c, hd, holes, 2 * nseq);
-  OP_BY_DTYPE(dtype, attention_holdout_fwd<T>(&c, (const T*)q, (const T*)k, (const T*)v, ldq, ldk, ldv, scale_q, scale_k, nseq, Sq, Nk, holes, hd, H, Dh,
-                                              (T*)o, lse, c.attn_impl));
+  AttnDesc a = op_attn_desc(q, k, v, ldq, ldk, ldv, scale_q, scale_k, nullptr, nseq, Sq, 0, H, Dh, o, lse, dtype);
+  a.layout = AttnLayout::Hole; a.holes_host = holes; a.holes_dev = hd; a.Nk = Nk;
+  OP_BY_DTYPE(dtype, attention_fwd<T>(&c, a));
   return c.status();
 }
 SPA3D_OP(spa3d_op_attention_bwd)(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* scale_q,
@@ -234,9 +253,10 @@ SPA3D_OP(spa3d_op_attention_bwd)(const void* q, const void* k, const void* v, in
         impl, ws, ws_bytes, stream)
   if (!q || !k || !v || !d_o || !dq || !dk || !dv || !dscale_q || !dscale_k || Dh > 128) return SPA3D_ERR_ARG;
   OpCtx c(stream, ws, ws_bytes);
-  apply_attn_impl(&c, impl);
-  OP_BY_DTYPE(dtype, attention_bwd<T>(&c, (const T*)q, (const T*)k, (const T*)v, ldq, ldk, ldv, scale_q, scale_k, keymask, nseq, Sq, Sk, H, Dh, (const T*)o, lse,
-                                      (const T*)d_o, (T*)dq, (T*)dk, (T*)dv, dscale_q, dscale_k, c.attn_impl));
+  c.attn = AttnPolicy::from_impl(impl);
+  AttnDesc a = op_attn_desc(q, k, v, ldq, ldk, ldv, scale_q, scale_k, keymask, nseq, Sq, Sk, H, Dh, o, lse, dtype);
+  op_attn_grads(a, d_o, dq, dk, dv, dscale_q, dscale_k);
+  OP_BY_DTYPE(dtype, attention_bwd<T>(&c, a));
   return c.status();
 }
 
@@ -245,7 +265,7 @@ SPA3D_OP(spa3d_op_attention_bwd)(const void* q, const void* k, const void* v, in
 // kernels decline under impl 2) is an argument error here and launches nothing; the workspace is sized by a dry walk before the first launch.
 static bool ragged_args_ok(const void* const* ptrs, int np, const int32_t* seq_off, int64_t nseq, int64_t ldq, int64_t ldk, int64_t ldv, int32_t S, int32_t H,
                            int32_t Dh, int32_t dtype, int32_t impl) {
-  if (!seq_off || dtype != OP_DT16 || Dh != 96 || S < 2 || S > 320 || H < 1 || nseq < 1 || nseq > (1 << 20) || nseq * H > 0x7fffffffLL) return false;
+  if (!seq_off || dtype != OP_DT16 || Dh != ATTN_DH || S < 2 || S > ATTN_MAX_S || H < 1 || nseq < 1 || nseq > (1 << 20) || nseq * H > 0x7fffffffLL) return false;
   if (impl != 0 && impl != 2 && impl != 3 && impl != 4) return false;   // 1: no generic route for ragged rows; anything else names no kernel
   const int64_t E = (int64_t)H * Dh;   // a row stride below the row: rows of dq / dk / dv would overlap
   if (ldq < E || ldk < E || ldv < E || ldq % 8 || ldk % 8 || ldv % 8) return false;
@@ -261,7 +281,7 @@ static bool ragged_args_ok(const void* const* ptrs, int np, const int32_t* seq_o
 static bool varlen_args_ok(const int32_t* koff, int64_t nseq, int64_t ldq, int64_t ldk, int64_t ldv, int32_t Sq, int32_t H, int32_t Dh, int32_t dtype, int32_t impl) {
   if (!koff || !OP_DTYPE_OK(dtype) || nseq < 1 || nseq > (1 << 20) || Sq < 1 || H < 1 || Dh < 1 || Dh > 128 || impl < 0 || impl > 2) return false;
   if (ldq < (int64_t)H * Dh || ldk < (int64_t)H * Dh || ldv < (int64_t)H * Dh) return false;
-  if (impl == 2 && (Dh != 96 || Sq > 128 || dtype == SPA3D_F32 || ldq % 8 || ldk % 8 || ldv % 8)) return false;   // what the chunked-key kernels take
+  if (impl == 2 && (Dh != ATTN_DH || Sq > ATTN_XCHUNK || dtype == SPA3D_F32 || ldq % 8 || ldk % 8 || ldv % 8)) return false;   // what the chunked-key kernels take
   if (koff[0] != 0) return false;
   for (int64_t i = 0; i < nseq; ++i)
     if ((int64_t)koff[i + 1] - koff[i] < 1) return false;   // a sequence without a key
@@ -274,12 +294,10 @@ SPA3D_OP(spa3d_op_attention_ragged)(const void* q, const void* k, const void* v,
   const void* ptrs[] = {q, k, v, o, scale_q, scale_k};
   if (!ragged_args_ok(ptrs, 6, seq_off, nseq, ldq, ldk, ldv, S, H, Dh, dtype, impl)) return SPA3D_ERR_ARG;
   OpCtx c(stream, ws, ws_bytes);
-  apply_attn_impl(&c, impl);
-  const int32_t* od = nullptr;
-  return op_with_offsets(c, seq_off, nseq, &od, [&] {
-    attention_fwd<bf16_t>(&c, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv, scale_q, scale_k, keymask, nseq, S, S, H, Dh, (bf16_t*)o, lse,
-                          c.attn_impl, od, seq_off[nseq]);
-  });
+  c.attn = AttnPolicy::from_impl(impl);
+  AttnDesc a = op_attn_desc(q, k, v, ldq, ldk, ldv, scale_q, scale_k, keymask, nseq, S, S, H, Dh, o, lse, dtype);
+  a.layout = AttnLayout::RaggedRows; a.total_rows = seq_off[nseq];
+  return op_with_offsets(c, seq_off, nseq, &a.seq_off, [&] { attention_fwd<bf16_t>(&c, a); });
 }
 SPA3D_OP(spa3d_op_attention_ragged_bwd)(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* scale_q,
                                         const float* scale_k, const float* keymask, const int32_t* seq_off, int64_t nseq, int32_t S, int32_t H, int32_t Dh,
@@ -290,12 +308,11 @@ SPA3D_OP(spa3d_op_attention_ragged_bwd)(const void* q, const void* k, const void
   const void* ptrs[] = {q, k, v, o, d_o, dq, dk, dv, scale_q, scale_k};
   if (!lse || !dscale_q || !dscale_k || !ragged_args_ok(ptrs, 10, seq_off, nseq, ldq, ldk, ldv, S, H, Dh, dtype, impl)) return SPA3D_ERR_ARG;
   OpCtx c(stream, ws, ws_bytes);
-  apply_attn_impl(&c, impl);
-  const int32_t* od = nullptr;
-  return op_with_offsets(c, seq_off, nseq, &od, [&] {
-    attention_bwd<bf16_t>(&c, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv, scale_q, scale_k, keymask, nseq, S, S, H, Dh, (const bf16_t*)o,
-                          lse, (const bf16_t*)d_o, (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, dscale_q, dscale_k, c.attn_impl, od, seq_off[nseq]);
-  });
+  c.attn = AttnPolicy::from_impl(impl);
+  AttnDesc a = op_attn_desc(q, k, v, ldq, ldk, ldv, scale_q, scale_k, keymask, nseq, S, S, H, Dh, o, lse, dtype);
+  a.layout = AttnLayout::RaggedRows; a.total_rows = seq_off[nseq];
+  op_attn_grads(a, d_o, dq, dk, dv, dscale_q, dscale_k);
+  return op_with_offsets(c, seq_off, nseq, &a.seq_off, [&] { attention_bwd<bf16_t>(&c, a); });
 }
 
 SPA3D_OP(spa3d_op_attention_varlen)(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* scale_q,
@@ -305,11 +322,10 @@ SPA3D_OP(spa3d_op_attention_varlen)(const void* q, const void* k, const void* v,
   if (!q || !k || !v || !o || !scale_q || !scale_k || !varlen_args_ok(koff, nseq, ldq, ldk, ldv, Sq, H, Dh, dtype, impl)) return SPA3D_ERR_ARG;
   if (impl == 2 && !(op_al16(q) && op_al16(k) && op_al16(v) && op_al16(o))) return SPA3D_ERR_ARG;
   OpCtx c(stream, ws, ws_bytes);
-  apply_attn_impl(&c, impl);
-  const int32_t* kd = nullptr;
-  OP_BY_DTYPE(dtype, return op_with_offsets(c, koff, nseq, &kd, [&] {
-    attention_varlen_fwd<T>(&c, (const T*)q, (const T*)k, (const T*)v, ldq, ldk, ldv, scale_q, scale_k, nseq, Sq, koff, kd, H, Dh, (T*)o, lse, c.attn_impl);
-  }));
+  c.attn = AttnPolicy::from_impl(impl);
+  AttnDesc a = op_attn_desc(q, k, v, ldq, ldk, ldv, scale_q, scale_k, nullptr, nseq, Sq, 0, H, Dh, o, lse, dtype);
+  a.layout = AttnLayout::RaggedKeys; a.koff_host = koff;
+  OP_BY_DTYPE(dtype, return op_with_offsets(c, koff, nseq, &a.koff_dev, [&] { attention_fwd<T>(&c, a); }));
 }
 SPA3D_OP(spa3d_op_attention_varlen_bwd)(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldk, int64_t ldv, const float* scale_q,
                                         const float* scale_k, const int32_t* koff, int64_t nseq, int32_t Sq, int32_t H, int32_t Dh, const void* o,
@@ -327,12 +343,11 @@ SPA3D_OP(spa3d_op_attention_varlen_bwd)(const void* q, const void* k, const void
       if (!op_al16(p)) return SPA3D_ERR_ARG;
   }
   OpCtx c(stream, ws, ws_bytes);
-  apply_attn_impl(&c, impl);
-  const int32_t* kd = nullptr;
-  OP_BY_DTYPE(dtype, return op_with_offsets(c, koff, nseq, &kd, [&] {
-    attention_varlen_bwd<T>(&c, (const T*)q, (const T*)k, (const T*)v, ldq, ldk, ldv, scale_q, scale_k, nseq, Sq, koff, kd, H, Dh, (const T*)o, lse, (const T*)d_o,
-                            (T*)dq, (T*)dk, (T*)dv, dscale_q, dscale_k, c.attn_impl);
-  }));
+  c.attn = AttnPolicy::from_impl(impl);
+  AttnDesc a = op_attn_desc(q, k, v, ldq, ldk, ldv, scale_q, scale_k, nullptr, nseq, Sq, 0, H, Dh, o, lse, dtype);
+  a.layout = AttnLayout::RaggedKeys; a.koff_host = koff;
+  op_attn_grads(a, d_o, dq, dk, dv, dscale_q, dscale_k);
+  OP_BY_DTYPE(dtype, return op_with_offsets(c, koff, nseq, &a.koff_dev, [&] { attention_bwd<T>(&c, a); }));
 }
 
 // Single-query attention and the rank-K projection: every shape their launchers would record as a HIP-class error (or decline) is an argument error here

@@ -296,27 +296,23 @@ template <typename S_> void qkv_attn_pack(spa3d_ctx* c, const S_* wq, const S_* 
 template void qkv_attn_pack<float>(spa3d_ctx*, const float*, const float*, const float*, int, int, bf16_t*);
 template void qkv_attn_pack<bf16_t>(spa3d_ctx*, const bf16_t*, const bf16_t*, const bf16_t*, int, int, bf16_t*);
 
-// qkv[rows][3 E] = nq . (Wq | Wk | Wv), o / lse = attention of every (sequence, head); false = shape not covered (the caller runs the GEMM and the attention kernel)
-bool qkv_attn_fwd(spa3d_ctx* c, const bf16_t* nq, int64_t ldn, const bf16_t* wpk, const float* sq, const float* sk, const float* km, int64_t nseq, int S, int H,
-                  int Dh, int d, bf16_t* qkv, bf16_t* o, float* lse, const int32_t* seq_off, int64_t total_rows) {
-  if (!wpk || Dh != DH || d != QA_D || S < 2 || S > QA_SPAD || H < 1 || nseq < 1 || ldn % 8) return false;
-  if ((((uintptr_t)nq) | ((uintptr_t)qkv) | ((uintptr_t)o) | ((uintptr_t)wpk)) & 15) return false;
-  if (nseq * H > 0x7fffffffLL) return false;
-  if (c->dry) return true;
+// qkv[rows][3 E] = x . (Wq | Wk | Wv), o / lse = attention of every (sequence, head): launches what plan_qkv_attn (attn_plan.hpp) took -- d.q is the q | k | v output
+void qkv_attn_launch(spa3d_ctx* c, const AttnDesc& d) {
+  static_assert(QA_SPAD == QKVA_MAX_S && QA_D == QKVA_D && DH == ATTN_DH, "attn_plan.hpp states this kernel's shape");
+  const int S = d.Sk, H = d.H; const int64_t nseq = d.nseq;
   QkvaArgs a{};
-  a.nq = nq; a.ldn = ldn; a.wpk = (const char*)wpk; a.sq = sq; a.sk = sk; a.km = km; a.seq_off = seq_off; a.S = S; a.H = H; a.nprob = nseq * H;
-  a.qkv = qkv; a.ldq = 3 * (int64_t)H * DH; a.o = o; a.lse = lse;
+  a.nq = (const bf16_t*)d.x; a.ldn = d.ldx; a.wpk = (const char*)d.qkv_pk; a.sq = d.sq; a.sk = d.sk; a.km = d.km; a.seq_off = d.seq_off; a.S = S; a.H = H; a.nprob = nseq * H;
+  a.qkv = (bf16_t*)const_cast<void*>(d.q); a.ldq = 3 * (int64_t)H * DH; a.o = (bf16_t*)d.o; a.lse = d.lse;
   static bool attr = false;
   if (!attr) { (void)hipFuncSetAttribute((const void*)qkva_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, QA_LDS); attr = true; }
-  const double rows = total_rows > 0 ? (double)total_rows : (double)nseq * S;
+  const double rows = d.rows_present();
   {
-    ProfScope ps(c, PROF_ATTN_FWD, 2.0 * rows * QA_D * 3.0 * H * DH + 4.0 * rows * H * (rows / nseq) * Dh, rows * (QA_D + 4.0 * H * DH) * 2.0);
+    ProfScope ps(c, PROF_ATTN_FWD, 2.0 * rows * QA_D * 3.0 * H * DH + 4.0 * rows * H * (rows / nseq) * d.Dh, rows * (QA_D + 4.0 * H * DH) * 2.0);
     ps.tag(nseq, S, H, 2);
     const unsigned grid = (unsigned)std::min<int64_t>(a.nprob, 256);
     qkva_fwd_kernel<<<grid, 256, QA_LDS, c->stream>>>(a);
   }
   SPA_LAUNCH_CHECK(c);
-  return true;
 }
 
 }  // namespace SPA_NS

@@ -321,7 +321,7 @@ def probe_inputs(nseq, Sq, Sk, H, Dh, dt, pos, seed):
 
 
 def cross_attention_ws_bytes(nseq, H, Sq, Sk):
-  """what the fused cross attention carves from its workspace (csrc/attention_fused.hip: xattn_fwd, attn_fused_bwd_bf16): per (sequence, head, 128-key chunk) an
+  """what the fused cross attention carves from its workspace (csrc/attn_plan.hpp: AttnPlan::part_bytes of the XFwd* / XBwd* routes): per (sequence, head, 128-key chunk) an
   fp32 [Sq, 96] partial and an [Sq, 2] (max, sum) pair in the forward, an fp32 [Sq, 96] dq^ partial in the backward; each released before the next call"""
   return nseq * H * ((Sk + 127) // 128) * Sq * (96 + 2) * 4 + (64 << 10)
 

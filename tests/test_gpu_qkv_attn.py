@@ -133,7 +133,7 @@ def test_qkv_attention_fused_in_model_equals_the_two_kernel_path(precision, tmp_
     assert lib_.spa3d_prof_dump(h, path.encode()) == 0
     lib_.spa3d_prof_enable(h, 0)
     spa3d._lib.check(lib_.spa3d_set_option(h, b'attn_impl', 0.0), h)
-    fused = sum(1 for line in open(path) if line.split(',')[0] == '3' and int(line.strip().split(',')[7]) == 2)   # class attention forward, tag[3] = 2: qkv_attn_fwd
+    fused = sum(1 for line in open(path) if line.split(',')[0] == '3' and int(line.strip().split(',')[7]) == 2)   # class attention forward, tag[3] = 2: qkv_attn_launch
     outs[impl] = (float(ld['total_loss']), preds.tracks.clone(), {k: v.clone() for k, v in O.tree_flatten(grads).items()}, fused)
   assert outs[6][3] >= 2 and outs[0][3] == 0, (outs[6][3], outs[0][3])   # the two full encoder blocks ran fused under 6, none by default
   e_t = rel_err(outs[6][1], outs[0][1])
