@@ -50,6 +50,11 @@ class LossConfig(C.Structure):
               ('axis_weight', C.c_float * 3), ('bce_pos_weight', C.c_float)]
 
 
+class ParamGroup(C.Structure):
+  """spa3d_param_group (include/spa3d.h): one range [begin, end) of the optimizer's buffers with its two multipliers, 24 bytes."""
+  _fields_ = [('begin', C.c_int64), ('end', C.c_int64), ('lr_scale', C.c_float), ('wd_scale', C.c_float)]
+
+
 class TapVid3D(C.Structure):
   """spa3d_tapvid3d (include/spa3d.h): the scaling mode, the threshold table switch, then device pointers."""
   _fields_ = [('scaling', C.c_int32), ('fixed_thresholds', C.c_int32), ('intrinsics', C.c_void_p), ('query_stats', C.c_void_p),
@@ -104,6 +109,10 @@ _SIGS = {
                                        C.c_void_p, C.POINTER(Outputs), C.c_void_p, C.c_int64, C.c_void_p]),
     'spa3d_adamw_step': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_int64,
                                    C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    'spa3d_adamw_groups_workspace_bytes': (C.c_int64, [C.c_int32]),
+    'spa3d_adamw_step_groups': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_int64,
+                                          C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(ParamGroup), C.c_int32,
+                                          C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     'spa3d_set_option': (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
     'spa3d_set_loss_scale_state': (C.c_int, [C.c_void_p, C.c_void_p]),
     'spa3d_set_counts': (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

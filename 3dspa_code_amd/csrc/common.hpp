@@ -12,6 +12,8 @@
 #include "attn_plan.hpp"  // AttnDesc and the attention kernel choice (host-only)
 #include "score_row.hpp"  // per-track score arithmetic (host- and device-callable)
 #include "loss_point.hpp"  // the training objective at one point (host- and device-callable)
+#include "adamw_point.hpp"   // clip -> AdamW -> EMA at one element (host- and device-callable)
+#include "adamw_groups.hpp"  // the range table of the grouped optimizer: validation and lookup (host- and device-callable)
 
 // One translation unit is compiled for exactly ONE 16-bit activation type: bf16 (default) or IEEE fp16 (-DSPA_F16=1, BASELINE
 // cfg#5).  The raw 16-bit storage type is `bf16_t` (unsigned short) in both builds; what differs -- the two conversions, the MFMA
@@ -473,6 +475,10 @@ void k_set_loss_scale(spa3d_ctx*, const float* denom_dev, float gmax, float sett
 void k_unscale(spa3d_ctx*, float* a, const float* scale_dev, int64_t n);
 void k_adamw(spa3d_ctx*, float* p, const float* g, float* m, float* v, int64_t n, float lr, int64_t step, float clip, float b1, float b2,
              float eps, float wd, float* scratch);
+// grouped AdamW + weight EMA (spa3d_adamw_step_groups): `groups` is a validated HOST table, `ws` holds adamw_groups_ws_bytes(num) device bytes
+int64_t adamw_groups_ws_bytes(int num);
+void k_adamw_groups(spa3d_ctx*, float* p, const float* g, float* m, float* v, int64_t n, float lr, int64_t step, float clip, float b1, float b2,
+                    float eps, float wd, const AdamwGroup* groups, int num, float* ema, float ema_decay, float* scratch, void* ws);
 void k_uniform_noise(spa3d_ctx*, float* out, int64_t n, uint32_t k0, uint32_t k1);
 // over [lo, lo + n) of c->det: g[i] += shadow[i] / scale; shadow[i] = 0; NaN when *flag or |shadow[i]| >= 2^62
 void k_det_flush(spa3d_ctx* c, int64_t lo, int64_t n);

@@ -367,6 +367,200 @@ void k_adamw(spa3d_ctx* c, float* p, const float* g, float* m, float* v, int64_t
 }
 
 // ---------------------------------------------------------------------------------------------
+// grouped AdamW + weight EMA (spa3d_adamw_step_groups, include/spa3d.h): the same three stages -- partial sums of squares, guard, update --
+// with a table of ranges that scale the learning rate and the weight decay or freeze their elements (adamw_groups.hpp), and an optional
+// exponential moving average of the new parameters written in the same pass.  The arithmetic of one element is adamw_point.hpp.
+// ---------------------------------------------------------------------------------------------
+// The table reaches the device BY VALUE in launch arguments, 160 ranges per launch, as k_set_i32 moves host offsets: no host-to-device copy,
+// nothing borrowed from the caller once the call has returned.
+constexpr int GROUPS_PER_LAUNCH = 160;
+struct GroupWords { int32_t v[GROUPS_PER_LAUNCH * ADAMW_GROUP_WORDS]; };
+__global__ __launch_bounds__(256) void set_groups_kernel(int32_t* __restrict__ dst, const GroupWords a, int nwords) {
+  for (int i = threadIdx.x; i < nwords; i += 256) dst[i] = a.v[i];
+}
+// What a workgroup knows about the run of elements [t0, t1) it is about to process, found ONCE for the run: k = the first range that ends beyond
+// t0, and, when one range covers the whole run or the run lies in a gap, the run's multipliers.  k is reached by walking forward from `k0` (any range
+// index not beyond it: the result of adamw_group_find, or the k of an earlier run) through loads every lane shares.  A run that a range boundary cuts
+// is not uniform: each of its elements walks forward from k on its own (adamw_group_at).
+struct GroupRun { int k; bool uniform; float lr_scale, wd_scale; };
+__device__ __forceinline__ GroupRun group_run(const AdamwGroup* __restrict__ tab, int num, int k0, int64_t t0, int64_t t1) {
+  GroupRun r; r.uniform = true; r.lr_scale = 1.f; r.wd_scale = 1.f;
+  r.k = k0;
+  while (r.k < num && tab[r.k].end <= t0) ++r.k;
+  if (r.k < num) {
+    const int64_t b = tab[r.k].begin, e = tab[r.k].end;
+    if (b <= t0 && e >= t1) { r.lr_scale = tab[r.k].lr_scale; r.wd_scale = tab[r.k].wd_scale; }
+    else if (b < t1) r.uniform = false;   // (b >= t1: the whole run lies in the gap before range k)
+  }
+  return r;
+}
+// sumsq_kernel with the frozen elements left out: the same thread -> element map, the same tree, the same partial layout, and a frozen element adds
+// +0.f -- its gradient is not even loaded, so a NaN or an inf there cannot reach the norm.  (The running sum is a sum of squares from +0.f: adding +0.f
+// and not adding are the same bits.)  The map makes a workgroup's runs of 256 elements lie gridDim.x * 256 apart, so each run searches the table afresh.
+// The host passes num = 0 for a table that freezes nothing.  Then every element counts, and the map's one 4-byte load per thread and round -- at most
+// 512 workgroups, so 2 KiB in flight per CU -- is issued SUMSQ_AHEAD rounds at a time before the squares are added in the order of sumsq_kernel: the same
+// bits at 16 times the loads in flight.
+constexpr int SUMSQ_AHEAD = 16;
+__global__ __launch_bounds__(256) void sumsq_groups_kernel(const float* __restrict__ g, int64_t n, const AdamwGroup* __restrict__ tab, int num,
+                                                           float* partial) {
+  __shared__ float red[4];
+  float s = 0.f;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  int64_t base = (int64_t)blockIdx.x * 256;
+  if (num == 0) {
+    for (; base + (SUMSQ_AHEAD - 1) * stride + 256 <= n; base += SUMSQ_AHEAD * stride) {   // SUMSQ_AHEAD whole runs
+      float x[SUMSQ_AHEAD];
+#pragma unroll
+      for (int u = 0; u < SUMSQ_AHEAD; ++u) x[u] = g[base + u * stride + threadIdx.x];
+#pragma unroll
+      for (int u = 0; u < SUMSQ_AHEAD; ++u) s += x[u] * x[u];
+    }
+  }
+  for (; base < n; base += stride) {
+    const GroupRun r = group_run(tab, num, adamw_group_find(tab, num, base), base, std::min<int64_t>(base + 256, n));
+    const int64_t i = base + threadIdx.x;
+    if (i >= n) continue;
+    float ls = r.lr_scale, ws = r.wd_scale;
+    if (!r.uniform) { int k = r.k; adamw_group_at(tab, num, k, i, ls, ws); }
+    if (ls != 0.f) s += g[i] * g[i];
+  }
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+struct AdamwGroupsArgs {
+  float* p; const float* g; float* m; float* v; float* ema;
+  int64_t n, head, nvec;   // elements [head, head + 4 nvec) are read and written 16 bytes at a time; what lies before and behind, one by one
+  float lr, tstep, clip, b1, b2, eps, wd, ema_d, ema_omd;
+  float* scratch;
+};
+template <bool EMA>
+__device__ __forceinline__ void adamw_groups_one(const AdamwGroupsArgs& a, const AdamwCoef& c, int64_t i, float ls, float ws) {
+  if (ls == 0.f) return;   // frozen: nothing is read, nothing is written
+  float mi = a.m[i], vi = a.v[i];
+  const float ei = EMA ? a.ema[i] : 0.f;
+  const float pn = adamw_point(c, a.lr * ls, a.wd * ws, a.p[i], a.g[i], mi, vi);
+  a.m[i] = mi; a.v[i] = vi; a.p[i] = pn;
+  if (EMA) a.ema[i] = adamw_ema_point(ei, a.ema_d, a.ema_omd, pn);
+}
+// The runs of `len` elements that tile [s0, s1) are dealt out in contiguous blocks, workgroup b taking runs [b * per, (b + 1) * per): its runs ascend
+// and adjoin, so the table is searched once and walked from there.  first / last = this workgroup's runs.
+__device__ __forceinline__ void group_block_of_runs(int64_t s0, int64_t s1, int len, int64_t& first, int64_t& last) {
+  const int64_t runs = (s1 - s0 + len - 1) / len, per = (runs + gridDim.x - 1) / gridDim.x;
+  first = std::min<int64_t>((int64_t)blockIdx.x * per, runs); last = std::min<int64_t>(first + per, runs);
+}
+// elements [s0, s1) one at a time, in runs of 256
+template <bool EMA>
+__device__ __forceinline__ void adamw_groups_span(const AdamwGroupsArgs& a, const AdamwCoef& c, const AdamwGroup* __restrict__ tab, int num, int64_t s0, int64_t s1) {
+  int64_t first, last;
+  group_block_of_runs(s0, s1, 256, first, last);
+  if (first >= last) return;
+  int k = adamw_group_find(tab, num, s0 + first * 256);
+  for (int64_t t = first; t < last; ++t) {
+    const int64_t base = s0 + t * 256;
+    const GroupRun r = group_run(tab, num, k, base, std::min<int64_t>(base + 256, s1));
+    k = r.k;
+    const int64_t i = base + threadIdx.x;
+    if (i >= s1) continue;
+    float ls = r.lr_scale, ws = r.wd_scale;
+    if (!r.uniform) { int kk = r.k; adamw_group_at(tab, num, kk, i, ls, ws); }
+    adamw_groups_one<EMA>(a, c, i, ls, ws);
+  }
+}
+// The update: 28 bytes of traffic per element (36 with the EMA), no reuse -- a streaming pass.  A workgroup takes runs of 1024 elements, four per
+// thread in one 16-byte load and store per stream; a run that one range covers (or none touches) resolves its multipliers once, a frozen run is
+// skipped without a load, and a run that a range boundary cuts goes element by element through the same adamw_point.  Plain stores, no atomics:
+// every element is written by one thread, from values that do not depend on the launch geometry.
+template <bool EMA>
+__global__ __launch_bounds__(256) void adamw_groups_kernel(const AdamwGroupsArgs a, const AdamwGroup* __restrict__ tab, int num) {
+  // (the prologue of adamw_kernel, expression for expression: the two must agree bit for bit)
+  const float teff = fmaxf(a.tstep - a.scratch[3], 1.f);
+  AdamwCoef c;
+  c.b1 = a.b1; c.b2 = a.b2; c.eps = a.eps;
+  c.bc1 = adamw_bias_correction(teff, a.b1); c.bc2 = adamw_bias_correction(teff, a.b2);
+  const float gn = sqrtf(a.scratch[1]);
+  c.sc = gn < a.clip ? 1.f : a.clip / gn;
+  if (blockIdx.x == 0 && threadIdx.x == 0) a.scratch[0] = gn;
+  if (!(gn <= 3.0e38f)) return;  // non-finite norm over the live elements: the step is skipped, nothing but the scratch words is written
+  const int64_t vend = a.head + 4 * a.nvec;
+  int64_t first, last;
+  group_block_of_runs(a.head, vend, 1024, first, last);
+  int k = first < last ? adamw_group_find(tab, num, a.head + first * 1024) : 0;
+  for (int64_t t = first; t < last; ++t) {
+    const int64_t t0 = a.head + t * 1024;
+    const GroupRun r = group_run(tab, num, k, t0, std::min<int64_t>(t0 + 1024, vend));
+    k = r.k;
+    const int64_t i = t0 + 4 * (int64_t)threadIdx.x;
+    if (i >= vend) continue;
+    if (!r.uniform) {
+      int kk = r.k;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float ls, ws;
+        adamw_group_at(tab, num, kk, i + j, ls, ws);
+        adamw_groups_one<EMA>(a, c, i + j, ls, ws);
+      }
+      continue;
+    }
+    if (r.lr_scale == 0.f) continue;
+    const float lr_g = a.lr * r.lr_scale, wd_g = a.wd * r.wd_scale;
+    const float4 p4 = *reinterpret_cast<const float4*>(a.p + i), g4 = *reinterpret_cast<const float4*>(a.g + i);
+    float4 m4 = *reinterpret_cast<const float4*>(a.m + i), v4 = *reinterpret_cast<const float4*>(a.v + i);
+    float4 e4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (EMA) e4 = *reinterpret_cast<const float4*>(a.ema + i);
+    float4 o4;
+    o4.x = adamw_point(c, lr_g, wd_g, p4.x, g4.x, m4.x, v4.x);
+    o4.y = adamw_point(c, lr_g, wd_g, p4.y, g4.y, m4.y, v4.y);
+    o4.z = adamw_point(c, lr_g, wd_g, p4.z, g4.z, m4.z, v4.z);
+    o4.w = adamw_point(c, lr_g, wd_g, p4.w, g4.w, m4.w, v4.w);
+    *reinterpret_cast<float4*>(a.m + i) = m4; *reinterpret_cast<float4*>(a.v + i) = v4; *reinterpret_cast<float4*>(a.p + i) = o4;
+    if (EMA) {
+      e4.x = adamw_ema_point(e4.x, a.ema_d, a.ema_omd, o4.x); e4.y = adamw_ema_point(e4.y, a.ema_d, a.ema_omd, o4.y);
+      e4.z = adamw_ema_point(e4.z, a.ema_d, a.ema_omd, o4.z); e4.w = adamw_ema_point(e4.w, a.ema_d, a.ema_omd, o4.w);
+      *reinterpret_cast<float4*>(a.ema + i) = e4;
+    }
+  }
+  adamw_groups_span<EMA>(a, c, tab, num, 0, a.head);
+  adamw_groups_span<EMA>(a, c, tab, num, vend, a.n);
+}
+int64_t adamw_groups_ws_bytes(int num) { return num <= 0 ? 0 : ((int64_t)num * (int64_t)sizeof(AdamwGroup) + 255) / 256 * 256 + 256; }
+// `groups`: HOST table, already validated (adamw_groups_check); `ws`: at least adamw_groups_ws_bytes(num) device bytes (unused with num == 0)
+void k_adamw_groups(spa3d_ctx* c, float* p, const float* g, float* m, float* v, int64_t n, float lr, int64_t step, float clip, float b1, float b2,
+                    float eps, float wd, const AdamwGroup* groups, int num, float* ema, float ema_decay, float* scratch, void* ws) {
+  const AdamwGroup* tab = nullptr;
+  if (num > 0) {
+    int32_t* dst = reinterpret_cast<int32_t*>(((uintptr_t)ws + 255) / 256 * 256);
+    tab = reinterpret_cast<const AdamwGroup*>(dst);
+    const int32_t* src = reinterpret_cast<const int32_t*>(groups);
+    for (int k0 = 0; k0 < num; k0 += GROUPS_PER_LAUNCH) {
+      GroupWords w;
+      const int nw = std::min(GROUPS_PER_LAUNCH, num - k0) * ADAMW_GROUP_WORDS;
+      for (int i = 0; i < GROUPS_PER_LAUNCH * ADAMW_GROUP_WORDS; ++i) w.v[i] = i < nw ? src[(int64_t)k0 * ADAMW_GROUP_WORDS + i] : 0;
+      set_groups_kernel<<<1, 256, 0, c->stream>>>(dst + (int64_t)k0 * ADAMW_GROUP_WORDS, w, nw);
+    }
+  }
+  (void)hipMemsetAsync(scratch, 0, 12, c->stream);
+  const unsigned gs = (unsigned)std::min<int64_t>(cdiv(n, 256), SUMSQ_MAXB);
+  sumsq_groups_kernel<<<gs, 256, 0, c->stream>>>(g, n, tab, adamw_groups_any_frozen(groups, num) ? num : 0, scratch + SUMSQ_OFF);   // (a table that freezes nothing: every element counts)
+  adamw_guard_kernel<<<1, 256, 0, c->stream>>>(scratch, (int)gs);
+  AdamwGroupsArgs a;
+  a.p = p; a.g = g; a.m = m; a.v = v; a.ema = ema; a.n = n;
+  a.lr = lr; a.tstep = (float)(step + 1); a.clip = clip; a.b1 = b1; a.b2 = b2; a.eps = eps; a.wd = wd;
+  a.ema_d = ema_decay; a.ema_omd = 1.f - ema_decay;
+  a.scratch = scratch;
+  // the 16-byte body needs every stream at the same offset from a 16-byte boundary; buffers that disagree go element by element throughout
+  const uintptr_t ph = ((uintptr_t)p >> 2) & 3;
+  const bool same = (((uintptr_t)g >> 2) & 3) == ph && (((uintptr_t)m >> 2) & 3) == ph && (((uintptr_t)v >> 2) & 3) == ph && (!ema || (((uintptr_t)ema >> 2) & 3) == ph);
+  a.head = same ? std::min<int64_t>((int64_t)((4 - ph) & 3), n) : n;
+  a.nvec = (n - a.head) / 4;
+  const int64_t runs = std::max<int64_t>(cdiv(4 * a.nvec, 1024), cdiv(n - 4 * a.nvec, 256));
+  const unsigned gr = (unsigned)std::min<int64_t>(std::max<int64_t>(runs, 1), 4096);
+  if (ema) adamw_groups_kernel<true><<<gr, 256, 0, c->stream>>>(a, tab, num); else adamw_groups_kernel<false><<<gr, 256, 0, c->stream>>>(a, tab, num);
+  SPA_LAUNCH_CHECK(c);
+}
+
+// ---------------------------------------------------------------------------------------------
 // jax.random.uniform(PRNGKey(k0,k1), [n]) legacy threefry layout
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t rotl32(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }

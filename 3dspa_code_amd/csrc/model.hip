@@ -1687,6 +1687,26 @@ int spa3d_adamw_step(float* params, const float* grads, float* m, float* v, int6
   k_adamw(&c, params, grads, m, v, n, lr, step, clip, b1, b2, eps, wd, scratch);
   return c.hip_err ? SPA3D_ERR_HIP : SPA3D_OK;
 }
+int64_t spa3d_adamw_groups_workspace_bytes(int32_t num_groups) {
+  if (num_groups < 0 || num_groups > ADAMW_MAX_GROUPS) return -1;
+  return adamw_groups_ws_bytes(num_groups);
+}
+static_assert(sizeof(spa3d_param_group) == sizeof(AdamwGroup) && offsetof(spa3d_param_group, end) == offsetof(AdamwGroup, end) &&
+              offsetof(spa3d_param_group, lr_scale) == offsetof(AdamwGroup, lr_scale) && offsetof(spa3d_param_group, wd_scale) == offsetof(AdamwGroup, wd_scale),
+              "the kernels read the caller's table as AdamwGroup (adamw_groups.hpp)");
+int spa3d_adamw_step_groups(float* params, const float* grads, float* m, float* v, int64_t n, float lr, int64_t step, float clip, float b1,
+                            float b2, float eps, float wd, const spa3d_param_group* groups, int32_t num_groups, float* ema, float ema_decay,
+                            float* scratch, void* ws, int64_t ws_bytes, void* stream) {
+  // every refusal comes before the first launch (include/spa3d.h)
+  if (!params || !grads || !m || !v || !scratch || n < 0) return SPA3D_ERR_ARG;
+  if (adamw_groups_check(groups, num_groups, n) != ADAMW_G_OK) return SPA3D_ERR_ARG;
+  if (ema && !(ema_decay >= 0.f && ema_decay < 1.f)) return SPA3D_ERR_ARG;   // (NaN fails both comparisons)
+  if (num_groups > 0 && (!ws || ws_bytes < adamw_groups_ws_bytes(num_groups))) return SPA3D_ERR_WORKSPACE;
+  if (n == 0) return SPA3D_OK;
+  spa3d_ctx c; c.stream = (hipStream_t)stream;
+  k_adamw_groups(&c, params, grads, m, v, n, lr, step, clip, b1, b2, eps, wd, reinterpret_cast<const AdamwGroup*>(groups), num_groups, ema, ema_decay, scratch, ws);
+  return c.hip_err ? SPA3D_ERR_HIP : SPA3D_OK;
+}
 int spa3d_uniform_noise(float* out, int64_t n, uint32_t key0, uint32_t key1, void* stream) {
   if (!out || n <= 0) return SPA3D_ERR_ARG;
   spa3d_ctx c; c.stream = (hipStream_t)stream;

@@ -433,7 +433,7 @@ def _unflatten_params(flat: Dict[str, Any]) -> Dict[str, Any]:
 def save_checkpoint(path: str, params, state=None):
   """The save the reference leaves as a log line (train.py:389-393).  Flat 'a/b/c' keys -- the third layout its own
   loader accepts (inference.py:483-485) -- so the file loads in the reference too; optimizer moments and the step go
-  under 'opt_m/...', 'opt_v/...', 'step' when a TrainState is given (resume)."""
+  under 'opt_m/...', 'opt_v/...', 'step' when a TrainState is given (resume), and its weight EMA, when it keeps one, under 'ema/...'."""
   flat = {k: v.detach().float().cpu().numpy() for k, v in _flatten(params).items()}
   if state is not None:
     names = list(_flatten(state.params).keys())
@@ -444,6 +444,9 @@ def save_checkpoint(path: str, params, state=None):
     flat['step'] = np.array(state.step, dtype=np.int64)
     # skipped-step counter, dynamic loss-scale multiplier and its good-step counter (spa3d_adamw_step scratch[3..5]) belong to the optimizer state
     flat['opt_scratch'] = state.scratch[3:6].detach().cpu().numpy()
+    if getattr(state, 'ema', None) is not None:  # the weight EMA of a state created with ema_decay; a state without one writes the keys it always wrote
+      e_tree = state.model.tree_from_flat(state.ema, *state.model._dims_from_params(state.params))
+      flat.update({f'ema/{k}': t.detach().cpu().numpy() for k, t in _flatten(e_tree).items()})
     assert names
   if not path.endswith('.npz'):
     path = path + '.npz'
@@ -452,13 +455,22 @@ def save_checkpoint(path: str, params, state=None):
   return path
 
 
-def load_checkpoint(checkpoint_path: str, model=None, allow_pickle: bool = False):
+def load_checkpoint(checkpoint_path: str, model=None, allow_pickle: bool = False, ema: bool = False):
   """inference.py:464-508 for `.npz` files.  Flat-key files (and files written by save_checkpoint) load with
   allow_pickle=False; the two pickled layouts ('params' / 'optimizer' object arrays) execute code from the file when
   unpickled, so they need an explicit allow_pickle=True from the caller.  Returns the nested parameter dict (optimizer
-  entries, if present, under the keys 'opt_m', 'opt_v', 'step' are stripped -- use load_train_state for those)."""
+  entries, if present, under the keys 'opt_m', 'opt_v', 'ema', 'step' are stripped -- use load_train_state for those).
+  `ema=True` returns the weight EMA of a save_checkpoint file (its 'ema/...' entries) in place of the parameters."""
   if not os.path.exists(checkpoint_path):
     raise FileNotFoundError(f'Checkpoint not found: {checkpoint_path}')
+  if ema:
+    if not checkpoint_path.endswith('.npz'):
+      raise ValueError('ema=True reads the flat-key .npz files of save_checkpoint')
+    data = np.load(checkpoint_path, allow_pickle=False)
+    flat = {k[len('ema/'):]: np.array(data[k]) for k in data.files if k.startswith('ema/')}
+    if not flat:
+      raise KeyError(f'{checkpoint_path} holds no weight EMA (no ema/ entries)')
+    return _unflatten_params(flat)
   if not checkpoint_path.endswith('.npz'):  # Flax format (evaluate_tapvid3d.py:278-285, inference.py:490-503)
     state_dict = restore_flax_checkpoint(checkpoint_path)
     if 'params' in state_dict:
@@ -475,7 +487,7 @@ def load_checkpoint(checkpoint_path: str, model=None, allow_pickle: bool = False
     opt = opt.item() if opt.ndim == 0 else dict(opt)
     params = opt.get('target', opt) if isinstance(opt, dict) else opt
   else:
-    flat = {k: np.array(data[k]) for k in data.files if not (k.startswith('opt_m/') or k.startswith('opt_v/') or k in ('step', 'opt_scratch'))}
+    flat = {k: np.array(data[k]) for k in data.files if not (k.startswith('opt_m/') or k.startswith('opt_v/') or k.startswith('ema/') or k in ('step', 'opt_scratch'))}
     params = _unflatten_params(flat)
   return params
 
@@ -601,6 +613,17 @@ def load_train_state(checkpoint_path: str, state, rank0_only: bool = False):
       if tuple(a.shape) != tuple(shape):
         raise ValueError(f'shape mismatch for {key}: expected {shape}, got {a.shape}')
       buf[off:off + n] = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).reshape(-1).to(buf.device)
+  if getattr(state, 'ema', None) is not None:
+    # the weight EMA: restored from 'ema/<leaf>'; a file without those keys (written by a state that kept none) starts it at the loaded parameters
+    state.ema.copy_(state.flat)
+    if any(k.startswith('ema/') for k in data.files):
+      for name, shape, off in leaves:
+        if 'ema/' + name not in data.files:
+          raise KeyError(f"checkpoint is missing {'ema/' + name!r}")
+        a = data['ema/' + name]
+        if tuple(a.shape) != tuple(shape):
+          raise ValueError(f'shape mismatch for ema/{name}: expected {shape}, got {a.shape}')
+        state.ema[off:off + int(np.prod(shape))] = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).reshape(-1).to(state.ema.device)
   state.step = int(data['step'])
   if 'opt_scratch' in data.files:  # absent in checkpoints written before round 4: counters start at 0, multiplier at 1
     state.scratch[3:6] = torch.from_numpy(np.asarray(data['opt_scratch'], dtype=np.float32)).to(state.scratch.device)

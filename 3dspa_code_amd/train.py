@@ -115,6 +115,119 @@ def broadcast_state_(tensors, src: int = 0, group=None, force=False):
     dist.broadcast(t, src=gsrc, group=group)
 
 
+MAX_PARAM_GROUPS = 4096  # spa3d_adamw_step_groups (include/spa3d.h)
+_F32_MAX = 3.4028234664e38
+_NO_DECAY_SUFFIXES = ('/bias', '/scale', '/state_init')
+
+
+def _check_scale(x, what) -> float:
+  x = float(x)
+  if not (0.0 <= x <= _F32_MAX):  # NaN fails the comparison too
+    raise ValueError(f'{what} must be finite and non-negative, got {x!r}')
+  return x
+
+
+def check_ranges(ranges, n: int):
+  """The table rules of spa3d_adamw_step_groups on the host: [(begin, end, lr_scale, wd_scale)] sorted, disjoint, inside [0, n], non-empty, at most 4096,
+  scales finite and non-negative.  Returns the ranges as a list of plain tuples; raises ValueError otherwise."""
+  out, prev = [], 0
+  for k, r in enumerate(ranges):
+    b, e = int(r[0]), int(r[1])
+    if not (0 <= b < e <= n):
+      raise ValueError(f'range {k} = [{b}, {e}) is empty or outside [0, {n}]')
+    if b < prev:
+      raise ValueError(f'range {k} = [{b}, {e}) begins before the previous one ends ({prev}): the table must be sorted and disjoint')
+    out.append((b, e, _check_scale(r[2], f'lr_scale of range {k}'), _check_scale(r[3], f'wd_scale of range {k}')))
+    prev = e
+  if len(out) > MAX_PARAM_GROUPS:
+    raise ValueError(f'{len(out)} ranges: the optimizer takes at most {MAX_PARAM_GROUPS}')
+  return out
+
+
+def clip_ranges(ranges, lo: int, hi: int):
+  """`ranges` intersected with [lo, hi) and shifted by -lo: the table of an optimizer call that is handed the slices [lo:hi] of the buffers."""
+  return [(max(b, lo) - lo, min(e, hi) - lo, ls, ws) for b, e, ls, ws in ranges if min(e, hi) > max(b, lo)]
+
+
+class ParamGroups:
+  """What param_groups returns.  `leaves`: one (name, begin, end, lr_scale, wd_scale) per leaf in flat-buffer order, [begin, end) running from the
+  leaf's offset to the next leaf's (the alignment padding behind a leaf holds zeros with zero gradients: it belongs to the leaf); `n`: the length of
+  the flat buffer; `ranges`: the optimizer's table."""
+
+  def __init__(self, leaves, n: int):
+    self.leaves, self.n = list(leaves), int(n)
+
+  @property
+  def ranges(self):
+    """[(begin, end, lr_scale, wd_scale)], sorted; neighbours with equal scales are one range, and what has both scales 1 is left out (an element
+    in no range has both scales 1)."""
+    out = []
+    for _, b, e, ls, ws in self.leaves:
+      if out and out[-1][1] == b and out[-1][2:] == (ls, ws):
+        out[-1] = (out[-1][0], e, ls, ws)
+      else:
+        out.append((b, e, ls, ws))
+    return [r for r in out if r[2:] != (1.0, 1.0)]
+
+  def describe(self) -> str:
+    """One line per leaf -- name, lr_scale, wd_scale -- for the training log."""
+    w = max((len(l[0]) for l in self.leaves), default=0)
+    return '\n'.join(f'{name:{w}s}  lr_scale={ls:.6g}  wd_scale={ws:.6g}' for name, _, _, ls, ws in self.leaves)
+
+
+def leaf_units(names):
+  """The layer-wise-decay unit of every leaf name, as an index in order of first appearance (the names come in flat-buffer order).  A unit is a top-level
+  module, or `<module>/layer_<i>` inside a transformer stack; a stack's closing `norm_encoder` belongs to the stack's last layer."""
+  import re
+  keys, last_layer = [], {}
+  for name in names:
+    parts = name.split('/')
+    if len(parts) > 1 and re.fullmatch(r'layer_\d+', parts[1]):
+      last_layer[parts[0]] = f'{parts[0]}/{parts[1]}'
+      keys.append(last_layer[parts[0]])
+    elif len(parts) > 1 and parts[1] == 'norm_encoder' and parts[0] in last_layer:
+      keys.append(last_layer[parts[0]])
+    else:
+      keys.append(parts[0])
+  order = {}
+  for k in keys:
+    order.setdefault(k, len(order))
+  return [order[k] for k in keys], len(order)
+
+
+def param_groups(model: TrackAutoEncoder3D, params, rules=(), no_decay: bool = False, layer_decay: Optional[float] = None) -> ParamGroups:
+  """Per-leaf learning-rate and weight-decay multipliers for TrainState(param_groups=...), built from the model's leaf table.
+
+  `rules`: a sequence of (regex, lr_scale, wd_scale); re.search runs on the leaf name ('tracks_to_latents/layer_0/MLP_in/kernel') and the FIRST rule
+    that matches fixes both scales of the leaf.  lr_scale = 0 freezes it: parameters, moments and EMA keep their bits, no weight decay reaches it,
+    and its gradient stays out of the clip norm.
+  `no_decay`: leaves that no rule matched and whose name ends in '/bias', '/scale' or '/state_init' get wd_scale = 0 (the reference decays every leaf).
+  `layer_decay` = r: lr_scale of a leaf that no rule matched is multiplied by r ** (U - 1 - u), u = the leaf's unit of U (leaf_units), numbered in
+    order of flat-buffer offset, so the last unit (the head) trains at the full rate.  The order is that of the buffer, which is the order of the
+    forward pass except that 'initializer/state_init' -- the latent stack's start tokens -- sits at offset 0 and therefore gets the smallest rate,
+    just as TrainState(freeze=1) freezes it with the encoder."""
+  import re
+  _, leaves, n = model._handle(*model._dims_from_params(params))
+  rules = [(re.compile(pat), _check_scale(ls, f'lr_scale of rule {pat!r}'), _check_scale(ws, f'wd_scale of rule {pat!r}')) for pat, ls, ws in rules]
+  if layer_decay is not None and not (0.0 < float(layer_decay) <= _F32_MAX):
+    raise ValueError(f'layer_decay must be positive and finite, got {layer_decay!r}')
+  leaves = sorted(leaves, key=lambda l: l[2])
+  units, U = leaf_units([l[0] for l in leaves])
+  out = []
+  for i, (name, _, off) in enumerate(leaves):
+    end = leaves[i + 1][2] if i + 1 < len(leaves) else n
+    hit = next(((ls, ws) for rx, ls, ws in rules if rx.search(name)), None)
+    if hit is None:
+      ls = float(layer_decay) ** (U - 1 - units[i]) if layer_decay is not None else 1.0
+      ws = 0.0 if no_decay and name.endswith(_NO_DECAY_SUFFIXES) else 1.0
+    else:
+      ls, ws = hit
+    out.append((name, int(off), int(end), ls, ws))
+  pg = ParamGroups(out, n)
+  check_ranges(pg.ranges, n)
+  return pg
+
+
 def _hip_uniform_noise(n: int, device) -> torch.Tensor:
   out = torch.empty(n, dtype=torch.float32, device=device)
   _lib.check(_lib.load().spa3d_uniform_noise(out.data_ptr(), n, 0, 0, _stream(out)), what='spa3d_uniform_noise')
@@ -137,13 +250,21 @@ class TrainState:
   the flat buffer frozen, lo = b1 or b2 of spa3d_grad_segments: the backward stops at that stage boundary, and clip + AdamW, the gradient all-reduce (bucketed
   or overlapped) and the norm run on the trainable range [lo, n) alone.  Frozen parameters and their moments keep their bits -- no weight decay reaches
   them -- and the clip norm and 'train/grad_norm' are those of the trainable range.  The adamw stand-in receives the slices [lo:] of flat, grads, m and v;
-  sync_from_rank0, checkpoints and load_train_state stay on the whole buffers."""
+  sync_from_rank0, checkpoints and load_train_state stay on the whole buffers.
+
+  `param_groups` (a ParamGroups from param_groups(), or a sequence of (begin, end, lr_scale, wd_scale) over the whole flat buffer) and `ema_decay` in
+  [0, 1) switch the optimizer call to spa3d_adamw_step_groups (include/spa3d.h): per-range learning-rate and weight-decay multipliers, frozen ranges
+  (lr_scale = 0) that keep their bits and stay out of the clip norm, and an exponential moving average of the weights written in the same pass --
+  `ema` (flat, created as a copy of the parameters; checkpointed, broadcast from rank 0) with the tree view `ema_params`, evaluated by
+  eval_step(batch, use_ema=True).  Under `freeze` the ranges are cut to [lo, n) and shifted by -lo, as the buffers are.  'train/grad_norm' is the norm
+  over the live elements.  With both unset the step makes exactly the call it always made; otherwise the adamw stand-in receives, after the same
+  twelve positional arguments, the keywords groups= (the cut and shifted ranges), ema= (the slice [lo:] or None) and ema_decay= (or None)."""
 
   def __init__(self, model: TrackAutoEncoder3D, params, learning_rate: float = 1e-4, warmup_steps: int = 10000,
                total_steps: int = 1000000, weight_decay: float = 0.01, clip_norm: float = 1.0, b1: float = 0.9,
                b2: float = 0.999, eps: float = 1e-8, process_group: Optional[dist.ProcessGroup] = None,
                grad_bucket_bytes: int = 128 << 20, compute=None, adamw=None, noise_fn=None, force_collectives: bool = False,
-               evaluate=None, overlap_allreduce: bool = True, loss=None, freeze=0):
+               evaluate=None, overlap_allreduce: bool = True, loss=None, freeze=0, param_groups=None, ema_decay: Optional[float] = None):
     self.model = model
     self.freeze = freeze_level(freeze)
     # the objective of this state's steps (a LossConfig; None = the reference's): stated on the model's handle for each call and taken off after
@@ -165,6 +286,23 @@ class TrainState:
     self.grads = torch.zeros_like(flat)
     self.scratch = torch.zeros(1024, dtype=torch.float32, device=flat.device)
     self.step = 0
+    # grouped optimizer (spa3d_adamw_step_groups): the table over the whole buffer and, cut to the trainable range, as the optimizer call takes it
+    self.param_groups = param_groups
+    self.groups = None
+    if param_groups is not None:
+      if isinstance(param_groups, ParamGroups) and param_groups.n != flat.numel():
+        raise ValueError(f'param_groups was built for a buffer of {param_groups.n} elements, this model has {flat.numel()}')
+      full = check_ranges(param_groups.ranges if hasattr(param_groups, 'ranges') else param_groups, flat.numel())
+      self.groups = clip_ranges(full, self.trainable_lo, flat.numel())
+    self.ema_decay = None
+    self.ema = self.ema_params = None
+    if ema_decay is not None:
+      if not (0.0 <= float(ema_decay) < 1.0):
+        raise ValueError(f'ema_decay must lie in [0, 1), got {ema_decay!r}')
+      self.ema_decay = float(ema_decay)
+      self.ema = flat.detach().clone()
+      self.ema_params = model.tree_from_flat(self.ema, *model._dims_from_params(self.params))
+    self._groups_arg = None  # (ctypes table, its workspace): built at the first grouped step
     self.schedule = create_learning_rate_schedule(learning_rate, warmup_steps, total_steps)
     self.wd, self.clip, self.b1, self.b2, self.eps = weight_decay, clip_norm, b1, b2, eps
     self.pg = process_group
@@ -174,7 +312,7 @@ class TrainState:
     self.bucket_elems = max(1, grad_bucket_bytes // 4)
     self.force = bool(force_collectives) and on  # run the collectives at world size 1 too (RCCL smoke test)
     self._compute = compute or self._hip_compute
-    self._adamw = adamw or self._hip_adamw
+    self._adamw = adamw or (self._hip_adamw if param_groups is None and ema_decay is None else self._hip_adamw_groups)
     self._noise_fn = noise_fn or _hip_uniform_noise
     self._evaluate = evaluate or self._hip_evaluate
     self._noise_cache = {}
@@ -238,7 +376,7 @@ class TrainState:
     """parameters + Adam moments + optimizer counters of every replica := rank 0's (also after load_train_state on rank 0 only).
     scratch[3:6] = skipped-update count (enters the Adam bias correction), loss-scale multiplier, its good-step counter: a replica that kept its own
     would apply a different update after a resume and drift apart silently."""
-    broadcast_state_((self.flat, self.m, self.v, self.scratch[3:6]), 0, self.pg, self.force)
+    broadcast_state_((self.flat, self.m, self.v, self.scratch[3:6]) + ((self.ema,) if self.ema is not None else ()), 0, self.pg, self.force)
 
   # ---- default (HIP) compute and optimizer
   def _hip_compute(self, params, batch, grads_flat, denom, discretize, noise):
@@ -249,6 +387,18 @@ class TrainState:
   def _hip_adamw(self, flat, grads, m, v, lr, step, clip, b1, b2, eps, wd, scratch):
     _lib.check(_lib.load().spa3d_adamw_step(flat.data_ptr(), grads.data_ptr(), m.data_ptr(), v.data_ptr(), flat.numel(), lr, step,
                                             clip, b1, b2, eps, wd, scratch.data_ptr(), _stream(flat)), what='spa3d_adamw_step')
+
+  def _hip_adamw_groups(self, flat, grads, m, v, lr, step, clip, b1, b2, eps, wd, scratch, groups=(), ema=None, ema_decay=None):
+    lib = _lib.load()
+    if self._groups_arg is None:  # the ranges of a state are fixed: one host table and one device workspace for all its steps
+      tab = (_lib.ParamGroup * max(len(groups), 1))(*[_lib.ParamGroup(*r) for r in groups])
+      nb = int(lib.spa3d_adamw_groups_workspace_bytes(len(groups)))
+      self._groups_arg = (tab, torch.empty(max(nb, 1), dtype=torch.uint8, device=flat.device), nb)
+    tab, ws, nb = self._groups_arg
+    _lib.check(lib.spa3d_adamw_step_groups(flat.data_ptr(), grads.data_ptr(), m.data_ptr(), v.data_ptr(), flat.numel(), lr, step, clip, b1, b2, eps, wd,
+                                           tab if groups else None, len(groups), ema.data_ptr() if ema is not None else None,
+                                           ema_decay if ema is not None else 0.0, scratch.data_ptr(), ws.data_ptr() if groups else None, nb, _stream(flat)),
+               what='spa3d_adamw_step_groups')
 
   def _hip_evaluate(self, params, batch, denom, discretize, noise):
     from .model import compute_loss_2d, compute_loss_3d
@@ -292,7 +442,11 @@ class TrainState:
     # learning-rate schedule is host arithmetic on `step` and does advance through a skip (reading the counter back would cost a sync).
     # (`freeze`: the trainable slices -- a pointer offset and a count; the frozen prefix of flat, m and v is never handed to the optimiser)
     lo = self.trainable_lo
-    self._adamw(self.flat[lo:], self.grads[lo:], self.m[lo:], self.v[lo:], lr, self.step, self.clip, self.b1, self.b2, self.eps, self.wd, self.scratch)
+    if self.groups is None and self.ema is None:
+      self._adamw(self.flat[lo:], self.grads[lo:], self.m[lo:], self.v[lo:], lr, self.step, self.clip, self.b1, self.b2, self.eps, self.wd, self.scratch)
+    else:
+      self._adamw(self.flat[lo:], self.grads[lo:], self.m[lo:], self.v[lo:], lr, self.step, self.clip, self.b1, self.b2, self.eps, self.wd, self.scratch,
+                  groups=self.groups or [], ema=self.ema[lo:] if self.ema is not None else None, ema_decay=self.ema_decay)
     self.step += 1
     # metric keys of train.py:180-185 (device scalars)
     # 'train/skipped' = 1 when the update was skipped (non-finite gradient norm: fp16 overflow), 'train/loss_scale_mult' the dynamic multiplier
@@ -310,17 +464,20 @@ class TrainState:
     if float(self.scratch[2].item()) != 0.0 and getattr(self.model, 'precision', 'fp16') != 'fp16':
       raise FloatingPointError(f'non-finite gradient norm at step {self.step - 1} ({self.skipped_steps()} skipped updates so far)')
 
-  def eval_step(self, batch, discretize: bool = True, noise=None):
+  def eval_step(self, batch, discretize: bool = True, noise=None, use_ema: bool = False):
     """train.py:189-213: forward pass + compute_loss on the current parameters, no update.  Returns (metrics, predictions) with the
     reference's metric keys 'eval/loss', 'eval/position_loss', 'eval/visible_loss' (device scalars).  Under data parallelism the two
     loss terms are normalised by the GLOBAL visible count and summed over ranks, exactly as the training loss is, and the rank
-    takes its slice of the global discretisation noise; predictions are the rank's own."""
+    takes its slice of the global discretisation noise; predictions are the rank's own.  `use_ema`: evaluate the weight EMA (`ema_params`; a state
+    created with ema_decay) instead of the parameters."""
+    if use_ema and self.ema_params is None:
+      raise ValueError('eval_step(use_ema=True) needs a TrainState created with ema_decay')
     multi = self.world > 1 or self.force
     denom = global_visible_count(batch['query_tracks_visible'], self.pg, self.force, check_equal_batches=True,
                                  query_count=batch.get('query_count')) if multi else 0.0
     if multi and discretize and noise is None:
       noise = self.rank_noise(batch['query_tracks_visible'].shape[0])
-    ld, preds = self._evaluate(self.params, batch, denom, discretize, noise)
+    ld, preds = self._evaluate(self.ema_params if use_ema else self.params, batch, denom, discretize, noise)
     l3 = torch.stack([torch.as_tensor(ld[k], dtype=torch.float32, device=self.flat.device).reshape(())
                       for k in ('total_loss', 'position_loss', 'visible_loss')])
     if _collectives_on(self.pg, self.force):

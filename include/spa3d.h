@@ -13,7 +13,9 @@
  *   spa3d_loss_and_grads            jax.value_and_grad(loss_fn)(params)  train.py:134-162
  *   spa3d_adamw_step                optax.chain(clip_by_global_norm(1.0), adamw(lr, 0.01)) + apply_updates
  *                                   train.py:164-165,239-242 (intended semantics, repair R6)
- *   spa3d_tapvid3d_from_preds       tapvid3d_metrics.compute_tapvid3d_metrics(...)  evaluate_tapvid3d.py:99-109,196-208
+ *   spa3d_adamw_step_groups         the same chain with per-range learning-rate / weight-decay scales, frozen ranges and a weight EMA
+ *                                   (optax.masked / multi_transform / ema; nothing in the reference: fine-tuning, product-only)
+ *   spa3d_tapvid3d_from_preds      tapvid3d_metrics.compute_tapvid3d_metrics(...)  evaluate_tapvid3d.py:99-109,196-208
  *                                   (third-party arithmetic upstream: restated from the published definition, parity unpinned)
  *   spa3d_render_tracks             project_all_tracks + normalize_scores + paint_point_track_with_colors
  *                                   visualize.py:15-175, visualizer.py:23-45,149-200 (own integer rasteriser, not cv2's)
@@ -416,6 +418,45 @@ int spa3d_set_point_weights(spa3d_handle h, int32_t B, int32_t Q, const float* w
 int spa3d_adamw_step(float* params, const float* grads, float* m, float* v, int64_t n, float lr,
                      int64_t step, float clip, float b1, float b2, float eps, float wd,
                      float* scratch, void* stream);
+
+/* spa3d_adamw_step with parameter groups and a weight EMA, in the same streaming pass: ranges of the buffers that scale the learning rate and
+ * the weight decay or are frozen, and an exponential moving average of the new parameters for evaluation.  spa3d_adamw_step is unchanged.
+ *
+ * Table.  `groups` is a HOST array of `num_groups` ranges [begin, end) of the n elements handed to the call (NULL with 0).  It is validated, then
+ *   carried to the device inside launch arguments into `ws` (>= spa3d_adamw_groups_workspace_bytes(num_groups) device bytes; may be NULL with
+ *   num_groups == 0): the call allocates nothing, reads nothing back to the host, and has consumed the caller's array when it returns.
+ *   0 <= num_groups <= 4096; the ranges are sorted ascending and disjoint; 0 <= begin < end <= n; lr_scale and wd_scale are finite and non-negative.
+ *   An element in no range has both scales 1.  Ranges start and end at any element.
+ * Frozen.  lr_scale == 0 freezes a range: its params, m, v and ema keep their bits, no weight decay reaches it, and its gradients are not read
+ *   for the norm -- a NaN or an inf there neither poisons the norm nor skips the step.
+ * Norm.  gn = sqrt(sum g^2) over the elements that are not frozen: the fixed-order two-stage reduction of spa3d_adamw_step, with the same
+ *   thread-to-element map and the same partial layout in scratch[256, 768); a frozen element contributes +0.f.  scratch (>= 4 KiB device, same
+ *   rules) means what it means there: [0] norm, [1] internal, [2] skipped-this-step, [3] skip count, [4] / [5] loss-scale multiplier and its
+ *   counter.  A non-finite norm skips the whole step: nothing is written except the scratch words.
+ * Update.  Per live element, in the order spa3d_adamw_step computes it: gi = g * sc (sc = 1 if gn < clip else clip / gn); m = b1 m + (1 - b1) gi;
+ *   v = b2 v + (1 - b2) gi gi; mh = m / bc1, vh = v / bc2 with the bias corrections at step + 1 - scratch[3];
+ *   p -= lr_g * (mh / (sqrtf(vh) + eps) + wd_g * p), where lr_g = lr * lr_scale and wd_g = wd * wd_scale are one fp32 product each.
+ * EMA.  With ema != NULL (device [n]), after the update: e = d * e + (1 - d) * p_new in fp32, d = ema_decay in [0, 1), 1 - d formed once.  No
+ *   bias correction: the caller initialises ema with a copy of the parameters.
+ * Identity.  With num_groups == 0 and ema == NULL, params, m, v and scratch[0..5] are bit for bit those of spa3d_adamw_step on the same inputs;
+ *   so they are with the single range [0, n) of scales (1, 1).  (Same expressions in the same order, and the library is built without
+ *   floating-point contraction.)  The elements are moved 16 bytes at a time where the five buffers share their offset from a 16-byte boundary,
+ *   one by one before and behind that and where they do not; both ways give the same bits, and two runs give the same bits (no atomics).
+ * Refusals, each before the first launch with nothing written.  SPA3D_ERR_ARG: a NULL required pointer or n < 0; num_groups out of range, or
+ *   groups == NULL with num_groups > 0; a range outside [0, n], empty, unsorted or overlapping; a scale that is negative or not finite;
+ *   ema != NULL with ema_decay outside [0, 1) or not finite.  SPA3D_ERR_WORKSPACE: num_groups > 0 with ws NULL or ws_bytes too small.
+ *   n == 0 (with a valid table, that is: none) returns SPA3D_OK and launches nothing.  The workspace query returns -1 for a count out of range. */
+typedef struct {
+  int64_t begin, end;  /* [begin, end) of the buffers handed to the call */
+  float lr_scale;      /* multiplies lr; 0 freezes the range */
+  float wd_scale;      /* multiplies wd */
+} spa3d_param_group;
+int64_t spa3d_adamw_groups_workspace_bytes(int32_t num_groups);
+int spa3d_adamw_step_groups(float* params, const float* grads, float* m, float* v, int64_t n, float lr,
+                            int64_t step, float clip, float b1, float b2, float eps, float wd,
+                            const spa3d_param_group* groups /* HOST [num_groups], NULL with 0 */, int32_t num_groups,
+                            float* ema /* device [n] or NULL */, float ema_decay,
+                            float* scratch, void* ws, int64_t ws_bytes, void* stream);
 
 /* Per-handle switches -- the only ones the library has (ten + one test mode); each may be preset at spa3d_create from the environment variable of the same name in
  * capitals with an SPA3D_ prefix (SPA3D_PRUNE, SPA3D_QUERY_CHUNK, SPA3D_TRACK_CHUNK, SPA3D_FREEZE ...).  Unknown names return SPA3D_ERR_ARG.
