@@ -77,6 +77,15 @@ class Clip(C.Structure):
               ('support_index', C.c_void_p), ('query_index', C.c_void_p), ('query_frame', C.c_void_p)]
 
 
+class Stitch(C.Structure):
+  """spa3d_stitch (include/spa3d.h): sizes and the blend, the HOST plan (t0, len), then device pointers."""
+  _fields_ = [('W', C.c_int32), ('N', C.c_int32), ('Tw', C.c_int32), ('TL', C.c_int32), ('NC', C.c_int32), ('blend', C.c_int32),
+              ('t0', C.POINTER(C.c_int32)), ('len', C.POINTER(C.c_int32)), ('row_track', C.c_void_p), ('tracks', C.c_void_p), ('visible_logits', C.c_void_p),
+              ('frame_err', C.c_void_p), ('out_tracks', C.c_void_p), ('out_visible_logits', C.c_void_p), ('out_frame_err', C.c_void_p), ('out_spread', C.c_void_p)]
+
+
+BLEND_MEAN, BLEND_HAT, BLEND_FIRST = 0, 1, 2  # SPA3D_BLEND_* (include/spa3d.h)
+
 _SIGS = {
     'spa3d_version': (C.c_char_p, []),
     'spa3d_create': (C.c_int, [C.POINTER(Config), C.POINTER(C.c_void_p)]),
@@ -104,6 +113,8 @@ _SIGS = {
     'spa3d_render_workspace_bytes': (C.c_int64, [C.c_void_p, C.c_int32, C.c_int32]),
     'spa3d_render_tracks': (C.c_int, [C.c_void_p, C.POINTER(Render), C.c_void_p, C.c_int64, C.c_void_p]),
     'spa3d_build_batch': (C.c_int, [C.c_void_p, C.POINTER(Clip), C.POINTER(Batch), C.c_void_p]),
+    'spa3d_build_windows': (C.c_int, [C.c_void_p, C.POINTER(Clip), C.c_int32, C.POINTER(C.c_int32), C.POINTER(Batch), C.c_void_p]),
+    'spa3d_stitch_windows': (C.c_int, [C.c_void_p, C.POINTER(Stitch), C.c_void_p]),
     'spa3d_op_median_rows': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     'spa3d_loss_and_grads': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Batch), C.c_float, C.c_void_p, C.c_int32,
                                        C.c_void_p, C.POINTER(Outputs), C.c_void_p, C.c_int64, C.c_void_p]),

@@ -1,4 +1,5 @@
-// batch_build.hip -- spa3d_build_batch (include/spa3d.h), the kernel first, the entry point below it: clips -> the padded model batch, in one launch per BB_CLIPS clips.
+// batch_build.hip -- spa3d_build_batch and spa3d_build_windows (include/spa3d.h), the kernel first, the entry points below it: clips -> the padded model batch, in one launch per BB_CLIPS clips.
+// A window of a long clip (spa3d_build_windows) is a clip whose descriptor carries a frame offset t0 and the long arrays' row stride TL: the same kernel reads it in place.
 // One wave per (clip, frame, slot); a clip's N support slots come first, then its Q query slots.  The arithmetic is build_row.hpp's (the
 // samplers' float32 operation order, the slot rule, one rounding to the feature type), which the g++ host test runs too.
 //
@@ -25,6 +26,7 @@ struct BbClip {
   int32_t n_tracks, T, H, W, Hp, Wp, n_support, n_query;
   BrIntr k; float sw, sh;
   int32_t depth_feat;   // the depth-feature channels come from the depth map (0: from depth_pool, or there are none)
+  int32_t t0, TL;       // the clip is frames [t0, t0 + T) of arrays that hold TL frames (spa3d_build_windows); spa3d_build_batch: 0 and T
 };
 struct BbArgs {
   BbClip clip[BB_CLIPS];
@@ -101,12 +103,13 @@ __global__ __launch_bounds__(256) void build_batch_kernel(const BbArgs a) {
       if (sup && a.depthf) bb_zero_row<OT>(a.depthf, orow * a.DD, a.DD, (a.vec & 2) != 0, lane);
       continue;
     }
-    const int64_t p = (int64_t)src * c.T + t;
+    const int ts = c.t0 + t;                    // the frame of the source arrays
+    const int64_t p = (int64_t)src * c.TL + ts;
     float x = 0.f, y = 0.f;
     if (c.tracks_2d) { x = c.tracks_2d[p * 2]; y = c.tracks_2d[p * 2 + 1]; }
     const bool depth_rows = sup && a.depthf && c.depth_feat;
     float d = 0.f;
-    if (!c.tracks_3d || depth_rows) d = br_depth_at(c.depth + (int64_t)t * c.H * c.W, c.H, c.W, x, y);
+    if (!c.tracks_3d || depth_rows) d = br_depth_at(c.depth + (int64_t)ts * c.H * c.W, c.H, c.W, x, y);
     float xyz[3];
     if (c.tracks_3d) { xyz[0] = c.tracks_3d[p * 3]; xyz[1] = c.tracks_3d[p * 3 + 1]; xyz[2] = c.tracks_3d[p * 3 + 2]; }
     else br_lift(x, y, d, c.k, xyz);
@@ -121,7 +124,7 @@ __global__ __launch_bounds__(256) void build_batch_kernel(const BbArgs a) {
         bb_copy_row<OT>(a.dino, o, c.dino_pool, p * D, D, (a.vec & 1) != 0, lane);
       } else {
         const BrCorner k = br_corners(x * c.sw, y * c.sh, c.Wp, c.Hp);
-        const float* base = c.dino_map + (int64_t)t * c.Hp * c.Wp * D;
+        const float* base = c.dino_map + (int64_t)ts * c.Hp * c.Wp * D;
         const float* r00 = base + ((int64_t)k.y0 * c.Wp + k.x0) * D; const float* r01 = base + ((int64_t)k.y0 * c.Wp + k.x1) * D;
         const float* r10 = base + ((int64_t)k.y1 * c.Wp + k.x0) * D; const float* r11 = base + ((int64_t)k.y1 * c.Wp + k.x1) * D;
         if (a.vec & 1) {
@@ -141,8 +144,8 @@ __global__ __launch_bounds__(256) void build_batch_kernel(const BbArgs a) {
       if (!c.depth_feat) {
         bb_copy_row<OT>(a.depthf, o, c.depth_pool, p * DD, DD, (a.vec & 2) != 0, lane);
       } else {
-        float dp = 0.f;  // the same track one frame earlier, at its own position there
-        if (t > 0) dp = br_depth_at(c.depth + (int64_t)(t - 1) * c.H * c.W, c.H, c.W, c.tracks_2d[(p - 1) * 2], c.tracks_2d[(p - 1) * 2 + 1]);
+        float dp = 0.f;  // the same track one frame earlier, at its own position there (t is the clip's frame: a window's first frame has no earlier one)
+        if (t > 0) dp = br_depth_at(c.depth + (int64_t)(ts - 1) * c.H * c.W, c.H, c.W, c.tracks_2d[(p - 1) * 2], c.tracks_2d[(p - 1) * 2 + 1]);
         if (a.vec & 2) {
           for (int ch = lane * 4; ch < DD; ch += 256)
             bb_store4<OT>(a.depthf, o + ch, br_depth_feature(ch, d, dp, t), br_depth_feature(ch + 1, d, dp, t), br_depth_feature(ch + 2, d, dp, t), br_depth_feature(ch + 3, d, dp, t));
@@ -166,17 +169,21 @@ void k_build_batch(spa3d_ctx* c, const BbArgs& a, int out_type) {
 
 }  // namespace SPA_NS
 
-// ---- the entry point ----
-extern "C" {
-
-// Everything is checked for every clip before the first launch; then one launch per BB_CLIPS clips, their descriptors by value.
-int spa3d_build_batch(spa3d_handle h, const spa3d_clip* clips, spa3d_batch* out, void* stream) {
+// ---- the entry points ----
+// Both entry points are this one walk.  t0 == nullptr: spa3d_build_batch, sample i is clips[i].  t0 given: spa3d_build_windows, sample w is
+// frames [t0[w], t0[w] + out->T) of the ONE clip clips[0], addressed in place.
+// Everything is checked for every clip before the first launch; then one launch per BB_CLIPS samples, their descriptors by value.
+static int bb_build(spa3d_handle h, const spa3d_clip* clips, int32_t W, const int32_t* t0, spa3d_batch* out, void* stream, bool windows) {
   if (!h) return SPA3D_ERR_ARG;
   h->err.clear(); h->hip_err = 0;
-  auto bad = [&](const std::string& m) { h->err = "build_batch: " + m; return SPA3D_ERR_ARG; };
+  auto bad = [&](const std::string& m) { h->err = std::string(windows ? "build_windows: " : "build_batch: ") + m; return SPA3D_ERR_ARG; };
   if (h->cfg.model_kind == 1) return bad("the 2-D model (model_kind 1) has no depth coordinate");
-  if (!clips) return bad("clips is required");
+  if (!clips) return bad(windows ? "clip is required" : "clips is required");
   if (!out) return bad("out is required");
+  if (windows) {
+    if (!t0) return bad("t0 is required");
+    if (W < 1 || out->B != W) return bad("W = " + std::to_string(W) + ", out->B = " + std::to_string(out->B) + " (W >= 1 and out->B == W)");
+  }
   if (out->B < 1 || out->N < 1 || out->Q < 0 || out->T < 1)
     return bad("out: B = " + std::to_string(out->B) + ", N = " + std::to_string(out->N) + ", Q = " + std::to_string(out->Q) + ", T = " + std::to_string(out->T) + " (B, N, T >= 1 and Q >= 0)");
   if (!out->support_tracks || !out->support_tracks_visible || !out->boundary_frame) return bad("out needs support_tracks, support_tracks_visible and boundary_frame");
@@ -186,11 +193,12 @@ int spa3d_build_batch(spa3d_handle h, const spa3d_clip* clips, spa3d_batch* out,
   if (out->depth_features && DD <= 0) return bad("out carries depth_features but the handle has no depth feature (depth_feature_dim = 0)");
   auto aligned = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
   bool vec_dino = (D & 3) == 0 && aligned(out->dino_features), vec_depth = (DD & 3) == 0 && aligned(out->depth_features);
-  for (int i = 0; i < out->B; ++i) {
+  for (int i = 0; i < (windows ? 1 : out->B); ++i) {
     const spa3d_clip& k = clips[i];
     auto cbad = [&](const std::string& m) { return bad("clip " + std::to_string(i) + ": " + m); };
     if (k.n_tracks < 1) return cbad("n_tracks = " + std::to_string(k.n_tracks) + " must be positive");
-    if (k.T < 1 || k.T > out->T) return cbad("T = " + std::to_string(k.T) + " is outside [1, " + std::to_string(out->T) + "] (the batch's T)");
+    if (windows && k.T < 1) return cbad("T = " + std::to_string(k.T) + " must be positive");
+    if (!windows && (k.T < 1 || k.T > out->T)) return cbad("T = " + std::to_string(k.T) + " is outside [1, " + std::to_string(out->T) + "] (the batch's T)");
     if (k.n_support < 1 || k.n_support > out->N) return cbad("n_support = " + std::to_string(k.n_support) + " is outside [1, " + std::to_string(out->N) + "]");
     if (k.n_query < 0 || k.n_query > out->Q) return cbad("n_query = " + std::to_string(k.n_query) + " is outside [0, " + std::to_string(out->Q) + "]");
     if (!k.visible) return cbad("visible is required");
@@ -211,6 +219,13 @@ int spa3d_build_batch(spa3d_handle h, const spa3d_clip* clips, spa3d_batch* out,
     vec_dino = vec_dino && aligned(k.dino_map) && aligned(k.dino_pool);
     vec_depth = vec_depth && aligned(k.depth_pool);
   }
+  if (windows) {
+    const int TL = clips[0].T;
+    for (int w = 0; w < W; ++w) {
+      if (t0[w] < 0 || t0[w] >= TL) return bad("t0[" + std::to_string(w) + "] = " + std::to_string(t0[w]) + " is outside [0, " + std::to_string(TL) + ") (the clip's T)");
+      if (w > 0 && t0[w] <= t0[w - 1]) return bad("t0 must increase strictly (t0[" + std::to_string(w) + "] = " + std::to_string(t0[w]) + ")");
+    }
+  }
   h->stream = (hipStream_t)stream; h->dry = false;
   for (int b0 = 0; b0 < out->B; b0 += BB_CLIPS) {
     BbArgs a{};
@@ -219,7 +234,7 @@ int spa3d_build_batch(spa3d_handle h, const spa3d_clip* clips, spa3d_batch* out,
     a.qv = (float*)out->query_tracks_visible; a.bf = (int32_t*)out->boundary_frame; a.dino = (void*)out->dino_features; a.depthf = (void*)out->depth_features;
     a.vec = (vec_dino ? 1 : 0) | (vec_depth ? 2 : 0);
     for (int g = 0; g < a.nclips; ++g) {
-      const spa3d_clip& k = clips[b0 + g];
+      const spa3d_clip& k = clips[windows ? 0 : b0 + g];
       BbClip& c = a.clip[g];
       c.tracks_2d = k.tracks_2d; c.tracks_3d = k.tracks_3d; c.visible = k.visible; c.depth = k.depth_map; c.dino_map = k.dino_map;
       c.dino_pool = k.dino_pool; c.depth_pool = k.depth_pool; c.sidx = k.support_index; c.qidx = k.query_index; c.qframe = k.query_frame;
@@ -227,10 +242,24 @@ int spa3d_build_batch(spa3d_handle h, const spa3d_clip* clips, spa3d_batch* out,
       c.k = br_intrinsics(k.intrinsics, k.H, k.W);
       c.sw = k.dino_map ? br_map_scale(k.Wp, k.W) : 0.f; c.sh = k.dino_map ? br_map_scale(k.Hp, k.H) : 0.f;
       c.depth_feat = (out->depth_features && !k.depth_pool) ? 1 : 0;
+      c.t0 = 0; c.TL = k.T;
+      if (windows) {  // a window is a clip that starts at t0[w]: its own length, its own row of window-relative query frames
+        const int w = b0 + g;
+        c.t0 = t0[w]; c.T = std::min(out->T, k.T - t0[w]);
+        if (k.n_query > 0) c.qframe = k.query_frame + (int64_t)w * k.n_query;
+      }
     }
     k_build_batch(h, a, h->cfg.precision);
   }
   return h->hip_err ? SPA3D_ERR_HIP : SPA3D_OK;
+}
+
+extern "C" {
+
+int spa3d_build_batch(spa3d_handle h, const spa3d_clip* clips, spa3d_batch* out, void* stream) { return bb_build(h, clips, 0, nullptr, out, stream, false); }
+
+int spa3d_build_windows(spa3d_handle h, const spa3d_clip* clip, int32_t W, const int32_t* t0, spa3d_batch* out, void* stream) {
+  return bb_build(h, clip, W, t0, out, stream, true);
 }
 
 }  // extern "C"

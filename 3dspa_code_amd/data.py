@@ -88,6 +88,103 @@ def _index_array(x, name, lo, hi, what):
   return a
 
 
+def _clip_sources(clip, model, bad, T):
+  """The host checks of one clip dict (build_batch, build_windows): shapes and sources.  T: the most frames it may have (None = any).  Returns
+  its plan (sizes, which source serves which output) and the DINO and depth-feature widths it carries (0 = none).  `bad` makes the exception."""
+  if clip.get('tracks_2d') is None or clip.get('visible') is None:
+    raise bad('tracks_2d and visible are required')
+  s2 = _shape(clip['tracks_2d'])
+  if len(s2) != 3 or s2[2] != 2 or s2[0] < 1 or s2[1] < 1:
+    raise bad(f'tracks_2d must be [n,T,2], got {s2}')
+  n, Tc = s2[:2]
+  if T is not None and Tc > T:
+    raise bad(f'has {Tc} frames, the batch has {T}')
+  sv = _shape(clip['visible'])
+  if sv not in ((n, Tc), (n, Tc, 1)):
+    raise bad(f'visible must be {(n, Tc)} or {(n, Tc, 1)}, got {sv}')
+  has3, depth = clip.get('tracks_3d') is not None, clip.get('depth')
+  if has3 and _shape(clip['tracks_3d']) != (n, Tc, 3):
+    raise bad(f'tracks_3d must be {(n, Tc, 3)}, got {_shape(clip["tracks_3d"])}')
+  H = W = 0
+  if depth is not None:
+    sd = _shape(depth)
+    if len(sd) == 4 and sd[3] == 1:
+      sd = sd[:3]
+    if len(sd) != 3 or sd[0] != Tc or sd[1] < 1 or sd[2] < 1:
+      raise bad(f'depth must be [T,H,W] or [T,H,W,1] with T = {Tc}, got {_shape(depth)}')
+    H, W = sd[1], sd[2]
+  if not has3 and depth is None:
+    raise bad('needs tracks_3d, or depth to lift tracks_2d with')
+  if clip.get('video_shape') is not None:
+    vs = tuple(int(v) for v in clip['video_shape'])
+    if len(vs) != 4 or vs[1] < 1 or vs[2] < 1:
+      raise bad(f'video_shape must be (T,H,W,3), got {vs}')
+    if depth is not None and (vs[1], vs[2]) != (H, W):
+      raise bad(f'video_shape {vs} and depth {(H, W)} disagree on the frame size')
+    H, W = vs[1], vs[2]
+  intr = None
+  if clip.get('intrinsics') is not None:
+    intr = [float(v) for v in np.asarray(clip['intrinsics'], dtype=np.float64).reshape(-1)]
+    if len(intr) != 4:
+      raise bad('intrinsics must be (fx, fy, cx, cy)')
+  dino, dino_dim = None, 0
+  if model.use_dino and (clip.get('dino_map') is not None or clip.get('dino_features') is not None):
+    if clip.get('dino_map') is not None and clip.get('dino_features') is not None:
+      raise bad('dino_map and dino_features are both given')
+    if clip.get('dino_map') is not None:
+      sm = _shape(clip['dino_map'])
+      if len(sm) != 4 or sm[0] != Tc or min(sm) < 1:
+        raise bad(f'dino_map must be [T,Hp,Wp,D] with T = {Tc}, got {sm}')
+      if H < 1:
+        raise bad('dino_map needs video_shape (or depth) for the frame size')
+      dino = ('map', sm)
+    else:
+      sm = _shape(clip['dino_features'])
+      if len(sm) != 3 or sm[:2] != (n, Tc) or sm[2] < 1:
+        raise bad(f'dino_features must be [{n},{Tc},D], got {sm}')
+      dino = ('pool', sm)
+    dino_dim = sm[-1]
+  dfeat, depth_dim = None, 0
+  if model.use_depth and (clip.get('depth_features') is not None or depth is not None):
+    if clip.get('depth_features') is not None:
+      sm = _shape(clip['depth_features'])
+      if len(sm) != 3 or sm[:2] != (n, Tc) or sm[2] < 1:
+        raise bad(f'depth_features must be [{n},{Tc},C], got {sm}')
+      if depth is not None and has3:
+        raise bad('depth and depth_features are both given (and tracks_3d needs no lift)')
+      dfeat = 'pool'
+      depth_dim = sm[2]
+    else:
+      dfeat = 'map'
+      depth_dim = int(model.depth_feature_dim)
+  return dict(n=n, Tc=Tc, H=H, W=W, has3=has3, dino=dino, dfeat=dfeat, intr=intr), dino_dim, depth_dim
+
+
+def _clip_upload(c, clip, p, up, act, keep):
+  """The device side of one clip's descriptor: uploads what the plan reads (a tensor already on the device in the right type is used as it is),
+  fills the sizes and pointers of the _lib.Clip `c`; what the pointers reference goes into `keep`."""
+  c.n_tracks, c.T, c.H, c.W = p['n'], p['Tc'], p['H'], p['W']
+  tens = {'tracks_2d': up(clip['tracks_2d']), 'visible': up(clip['visible'])}
+  if p['has3']:
+    tens['tracks_3d'] = up(clip['tracks_3d'])
+  if clip.get('depth') is not None and (not p['has3'] or p['dfeat'] == 'map'):
+    tens['depth_map'] = up(clip['depth'])
+  if p['dino'] is not None and p['dino'][0] == 'map':
+    tens['dino_map'] = up(clip['dino_map'])
+    c.Hp, c.Wp = p['dino'][1][1], p['dino'][1][2]
+  elif p['dino'] is not None:
+    tens['dino_pool'] = up(clip['dino_features'], act)
+  if p['dfeat'] == 'pool':
+    tens['depth_pool'] = up(clip['depth_features'], act)
+  for k, t in tens.items():
+    setattr(c, k, t.data_ptr())
+    keep.append(t)
+  if p['intr'] is not None:
+    intr = (C.c_double * 4)(*p['intr'])
+    keep.append(intr)
+    c.intrinsics = C.cast(intr, C.POINTER(C.c_double))
+
+
 def build_batch(clips, model=None, num_support_tracks: int = 2048, num_query_points: int = 512, num_frames: Optional[int] = None, splits=None,
                 device='cuda'):
   """Clips -> the batch dict that model.apply / model.score / model.tapvid3d / TrainState.train_step take, in ONE device call (spa3d_build_batch,
@@ -117,76 +214,10 @@ def build_batch(clips, model=None, num_support_tracks: int = 2048, num_query_poi
   plans, dino_dims, depth_dims = [], set(), set()
   for i, clip in enumerate(clips):
     bad = lambda m: ValueError(f'clip {i}: {m}')
-    if clip.get('tracks_2d') is None or clip.get('visible') is None:
-      raise bad('tracks_2d and visible are required')
-    s2 = _shape(clip['tracks_2d'])
-    if len(s2) != 3 or s2[2] != 2 or s2[0] < 1 or s2[1] < 1:
-      raise bad(f'tracks_2d must be [n,T,2], got {s2}')
-    n, Tc = s2[:2]
-    if Tc > T:
-      raise bad(f'has {Tc} frames, the batch has {T}')
-    sv = _shape(clip['visible'])
-    if sv not in ((n, Tc), (n, Tc, 1)):
-      raise bad(f'visible must be {(n, Tc)} or {(n, Tc, 1)}, got {sv}')
-    has3, depth = clip.get('tracks_3d') is not None, clip.get('depth')
-    if has3 and _shape(clip['tracks_3d']) != (n, Tc, 3):
-      raise bad(f'tracks_3d must be {(n, Tc, 3)}, got {_shape(clip["tracks_3d"])}')
-    H = W = 0
-    if depth is not None:
-      sd = _shape(depth)
-      if len(sd) == 4 and sd[3] == 1:
-        sd = sd[:3]
-      if len(sd) != 3 or sd[0] != Tc or sd[1] < 1 or sd[2] < 1:
-        raise bad(f'depth must be [T,H,W] or [T,H,W,1] with T = {Tc}, got {_shape(depth)}')
-      H, W = sd[1], sd[2]
-    if not has3 and depth is None:
-      raise bad('needs tracks_3d, or depth to lift tracks_2d with')
-    if clip.get('video_shape') is not None:
-      vs = tuple(int(v) for v in clip['video_shape'])
-      if len(vs) != 4 or vs[1] < 1 or vs[2] < 1:
-        raise bad(f'video_shape must be (T,H,W,3), got {vs}')
-      if depth is not None and (vs[1], vs[2]) != (H, W):
-        raise bad(f'video_shape {vs} and depth {(H, W)} disagree on the frame size')
-      H, W = vs[1], vs[2]
-    intr = None
-    if clip.get('intrinsics') is not None:
-      intr = [float(v) for v in np.asarray(clip['intrinsics'], dtype=np.float64).reshape(-1)]
-      if len(intr) != 4:
-        raise bad('intrinsics must be (fx, fy, cx, cy)')
-    dino = None
-    if model.use_dino and (clip.get('dino_map') is not None or clip.get('dino_features') is not None):
-      if clip.get('dino_map') is not None and clip.get('dino_features') is not None:
-        raise bad('dino_map and dino_features are both given')
-      if clip.get('dino_map') is not None:
-        sm = _shape(clip['dino_map'])
-        if len(sm) != 4 or sm[0] != Tc or min(sm) < 1:
-          raise bad(f'dino_map must be [T,Hp,Wp,D] with T = {Tc}, got {sm}')
-        if H < 1:
-          raise bad('dino_map needs video_shape (or depth) for the frame size')
-        dino = ('map', sm)
-      else:
-        sm = _shape(clip['dino_features'])
-        if len(sm) != 3 or sm[:2] != (n, Tc) or sm[2] < 1:
-          raise bad(f'dino_features must be [{n},{Tc},D], got {sm}')
-        dino = ('pool', sm)
-      dino_dims.add(sm[-1])
-    else:
-      dino_dims.add(0)
-    dfeat = None
-    if model.use_depth and (clip.get('depth_features') is not None or depth is not None):
-      if clip.get('depth_features') is not None:
-        sm = _shape(clip['depth_features'])
-        if len(sm) != 3 or sm[:2] != (n, Tc) or sm[2] < 1:
-          raise bad(f'depth_features must be [{n},{Tc},C], got {sm}')
-        if depth is not None and has3:
-          raise bad('depth and depth_features are both given (and tracks_3d needs no lift)')
-        dfeat = 'pool'
-        depth_dims.add(sm[2])
-      else:
-        dfeat = 'map'
-        depth_dims.add(int(model.depth_feature_dim))
-    else:
-      depth_dims.add(0)
+    plan, dd, dpd = _clip_sources(clip, model, bad, T)
+    dino_dims.add(dd)
+    depth_dims.add(dpd)
+    n, Tc = plan['n'], plan['Tc']
     if splits is None:
       ns = min(int(num_support_tracks), n)
       si, qi, qf = draw_split(n, ns, min(int(num_query_points), n - ns), Tc)
@@ -200,7 +231,7 @@ def build_batch(clips, model=None, num_support_tracks: int = 2048, num_query_poi
         raise bad(f'{len(qi)} query indices but {len(qf)} query frames')
     if len(si) < 1:
       raise bad('needs at least one support track')
-    plans.append(dict(n=n, Tc=Tc, H=H, W=W, has3=has3, dino=dino, dfeat=dfeat, intr=intr, si=si, qi=qi, qf=qf))
+    plans.append(dict(plan, si=si, qi=qi, qf=qf))
   if len(dino_dims) != 1 or len(depth_dims) != 1:
     raise ValueError('every clip of a batch must carry the same features with the same widths '
                      f'(DINO widths {sorted(dino_dims)}, depth widths {sorted(depth_dims)}; 0 = none)')
@@ -234,26 +265,7 @@ def build_batch(clips, model=None, num_support_tracks: int = 2048, num_query_poi
   arr, keep, off = (_lib.Clip * B)(), [index], 0
   for i, (clip, p) in enumerate(zip(clips, plans)):
     c = arr[i]
-    c.n_tracks, c.T, c.H, c.W = p['n'], p['Tc'], p['H'], p['W']
-    tens = {'tracks_2d': up(clip['tracks_2d']), 'visible': up(clip['visible'])}
-    if p['has3']:
-      tens['tracks_3d'] = up(clip['tracks_3d'])
-    if clip.get('depth') is not None and (not p['has3'] or p['dfeat'] == 'map'):
-      tens['depth_map'] = up(clip['depth'])
-    if p['dino'] is not None and p['dino'][0] == 'map':
-      tens['dino_map'] = up(clip['dino_map'])
-      c.Hp, c.Wp = p['dino'][1][1], p['dino'][1][2]
-    elif p['dino'] is not None:
-      tens['dino_pool'] = up(clip['dino_features'], act)
-    if p['dfeat'] == 'pool':
-      tens['depth_pool'] = up(clip['depth_features'], act)
-    for k, t in tens.items():
-      setattr(c, k, t.data_ptr())
-      keep.append(t)
-    if p['intr'] is not None:
-      intr = (C.c_double * 4)(*p['intr'])
-      keep.append(intr)
-      c.intrinsics = C.cast(intr, C.POINTER(C.c_double))
+    _clip_upload(c, clip, p, up, act, keep)
     ns, nq = len(p['si']), len(p['qi'])
     c.n_support, c.n_query = ns, nq
     c.support_index = index.data_ptr() + 4 * off
@@ -272,6 +284,224 @@ def build_batch(clips, model=None, num_support_tracks: int = 2048, num_query_poi
   batch['support_count'] = torch.tensor([len(p['si']) for p in plans], dtype=torch.int32, device=dev)
   batch['query_count'] = torch.tensor([len(p['qi']) for p in plans], dtype=torch.int32, device=dev)
   return batch
+
+
+# ------------------------------------------------------------------------------------------------ long clips: windows
+BLENDS = {'mean': _lib.BLEND_MEAN, 'hat': _lib.BLEND_HAT, 'first': _lib.BLEND_FIRST}
+MAX_WINDOWS = 256  # what spa3d_stitch_windows carries by value
+
+
+def window_starts(num_frames: int, window: int, stride: Optional[int] = None) -> np.ndarray:
+  """The plan that cuts a clip of num_frames frames into overlapping windows of `window` frames: the start frames, int32 [W].
+  stride defaults to window // 2 (at least 1); 1 <= stride <= window.  num_frames <= window: [0] (one, possibly short, window).  Otherwise
+  W = 1 + ceil((num_frames - window) / stride), start w = w * stride for w < W - 1, and the LAST start is num_frames - window, so that the last
+  window ends on the last frame.  The starts increase strictly, every frame is covered, none more than ceil(window / stride) + 1 times."""
+  for name, v in (('num_frames', num_frames), ('window', window)) + ((('stride', stride),) if stride is not None else ()):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+      raise ValueError(f'{name} must be an int, got {v!r}')
+  num_frames, window = int(num_frames), int(window)
+  if num_frames < 1 or window < 1:
+    raise ValueError(f'num_frames and window must be positive, got {num_frames}, {window}')
+  stride = max(window // 2, 1) if stride is None else int(stride)
+  if stride < 1 or stride > window:
+    raise ValueError(f'stride must lie in [1, window = {window}], got {stride}')
+  if num_frames <= window:
+    return np.zeros(1, np.int32)
+  W = 1 + -(-(num_frames - window) // stride)
+  starts = np.arange(W, dtype=np.int64) * stride
+  starts[-1] = num_frames - window
+  return starts.astype(np.int32)
+
+
+def _window_plan(starts, num_frames, window, stride, what):
+  """`starts` checked (one-dimensional ints in [0, num_frames), strictly increasing), or window_starts when None: int32 [W]."""
+  if starts is None:
+    return window_starts(num_frames, window, stride)
+  if stride is not None:
+    raise ValueError(f'{what}: give starts or stride, not both')
+  t0 = _index_array(starts, f'{what}: starts', 0, num_frames, f'the clip has {num_frames} frames')
+  if len(t0) < 1:
+    raise ValueError(f'{what}: needs at least one window')
+  if (t0[1:] <= t0[:-1]).any():
+    raise ValueError(f'{what}: starts must increase strictly, got {t0.tolist()}')
+  return t0.astype(np.int32)
+
+
+def build_windows(clip, model=None, starts=None, stride=None, order=None, device='cuda', queries=None):
+  """One LONG clip -> the batch dict of its W windows (B = W), in one device call per 16 windows (spa3d_build_windows, include/spa3d.h): window w
+  is frames [starts[w], starts[w] + model.num_output_frames) of the clip, cut in place -- no sliced copy of a pool or a map is made -- and holds
+  what build_batch gives for a clip whose arrays are those frame slices, bit for bit.  The clip dict is the one build_batch takes, with ANY
+  number of frames.  starts: window_starts(Tc, num_output_frames, stride) by default, or your own strictly increasing start frames.
+  order: the support index list shared by all windows (row r of every window is pool track order[r]); default: all tracks in order.
+  queries: None, or (query_index [nq], query_frame [W, nq]) with window-relative frames.  Returns the support keys, `boundary_frame` (the
+  windows' live frames) and `window_start` (int32 [W]); with queries also the query keys.  Validated on the host first (ValueError)."""
+  if model is None:
+    raise ValueError('build_windows needs the model (precision and feature widths come from it)')
+  if getattr(model, '_kind', 0) == 1:
+    raise ValueError('build_windows is not available for the 2-D model')
+  if not isinstance(clip, dict):
+    raise ValueError('build_windows takes ONE clip dict')
+  bad = lambda m: ValueError(f'clip: {m}')
+  p, D, DD = _clip_sources(clip, model, bad, None)
+  if D and D != model.dino_feature_dim:
+    raise ValueError(f'the clip carries {D} DINO channels, the model has dino_feature_dim = {model.dino_feature_dim}')
+  n, TL, Tw = p['n'], p['Tc'], int(model.num_output_frames)
+  t0 = _window_plan(starts, TL, Tw, stride, 'build_windows')
+  W = len(t0)
+  lens = np.minimum(Tw, TL - t0.astype(np.int64))
+  si = np.arange(n, dtype=np.int64) if order is None else _index_array(order, 'order', 0, n, f'the clip has {n} tracks')
+  if len(si) < 1:
+    raise bad('needs at least one support track')
+  qi, qf = np.zeros(0, np.int64), np.zeros((W, 0), np.int64)
+  if queries is not None:
+    if len(queries) != 2:
+      raise ValueError('queries is (query_index [nq], query_frame [W, nq])')
+    qi = _index_array(queries[0], 'query_index', 0, n, f'the clip has {n} tracks')
+    qf = queries[1].detach().cpu().numpy() if isinstance(queries[1], torch.Tensor) else np.asarray(queries[1])
+    if qf.shape != (W, len(qi)) or qf.dtype.kind not in 'iu':
+      raise ValueError(f'query_frame must be ints [W, nq] = {(W, len(qi))}, got {qf.shape} {qf.dtype}')
+    qf = qf.astype(np.int64)
+    if qf.size and ((qf < 0).any() or (qf >= lens[:, None]).any()):
+      raise ValueError('query_frame has entries outside their window ([0, the window\'s live frames))')
+  N, Q = len(si), len(qi)
+  # ---- device pass
+  dev = torch.device(device)
+  if dev.type != 'cuda':
+    raise _lib.Spa3dError('build_windows runs on the GPU: the 3DSPA hot path is HIP-only (no CPU fallback)')
+  if dev.index is None:
+    dev = torch.device('cuda', torch.cuda.current_device())
+  h = model._handle(D, DD)[0]
+  act = model.act_dtype
+
+  def up(x, dtype=torch.float32):
+    t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
+    return t.to(device=dev, dtype=dtype).contiguous()
+
+  index = torch.from_numpy(np.concatenate([si, qi, qf.reshape(-1)]).astype(np.int32)).to(dev)  # ONE upload
+  batch = {'support_tracks': torch.empty(W, N, Tw, 3, dtype=torch.float32, device=dev), 'support_tracks_visible': torch.empty(W, N, Tw, 1, dtype=torch.float32, device=dev),
+           'boundary_frame': torch.empty(W, dtype=torch.int32, device=dev)}
+  if Q:
+    batch.update({'query_points': torch.empty(W, Q, 4, dtype=torch.float32, device=dev), 'query_tracks': torch.empty(W, Q, Tw, 3, dtype=torch.float32, device=dev),
+                  'query_tracks_visible': torch.empty(W, Q, Tw, 1, dtype=torch.float32, device=dev)})
+  if D:
+    batch['dino_features'] = torch.empty(W, N, Tw, D, dtype=act, device=dev)
+  if DD:
+    batch['depth_features'] = torch.empty(W, N, Tw, DD, dtype=act, device=dev)
+  c, keep = _lib.Clip(), [index]
+  _clip_upload(c, clip, p, up, act, keep)
+  c.n_support, c.n_query = N, Q
+  c.support_index = index.data_ptr()
+  c.query_index = index.data_ptr() + 4 * N
+  c.query_frame = index.data_ptr() + 4 * (N + Q)
+  out = _lib.Batch()
+  out.B, out.N, out.Q, out.T = W, N, Q, Tw
+  for k in ('support_tracks', 'support_tracks_visible', 'query_points', 'query_tracks', 'query_tracks_visible', 'boundary_frame', 'dino_features', 'depth_features'):
+    if k in batch:
+      setattr(out, k, batch[k].data_ptr())
+  with torch.cuda.device(dev):
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(_lib.load().spa3d_build_windows(h, C.byref(c), W, (C.c_int32 * W)(*t0.tolist()), C.byref(out), stream), h, 'spa3d_build_windows')
+  del keep  # the call is enqueued: the allocator recycles these on the same stream only
+  batch['window_start'] = torch.from_numpy(t0.copy()).to(dev)
+  return batch
+
+
+_STITCH_HANDLE = []
+
+
+def _stitch_handle():
+  """A handle of the stitch calls' own: spa3d_stitch_windows uses its handle for the error message and the stream only, and must not reset
+  those of a handle a model is using."""
+  if not _STITCH_HANDLE:
+    from .model import TrackAutoEncoder3D
+    _STITCH_HANDLE.append(TrackAutoEncoder3D(num_output_frames=8, use_dino=False, use_depth=False, precision='fp32'))  # the model owns its handles
+  return _STITCH_HANDLE[0]._handle(0, 0)[0]
+
+
+def stitch_windows(starts, num_frames: int, tracks=None, visible_logits=None, frame_err=None, blend='hat', lengths=None, row_track=None, spread: bool = False):
+  """Per-window results of a long clip merged onto the clip's own time axis (spa3d_stitch_windows, include/spa3d.h, which defines the blend).
+  starts: int [W] window start frames; num_frames: TL; lengths: int [W] live frames per window (default min(Tw, TL - start)).
+  tracks [W,N,Tw,3 or 2], visible_logits and frame_err [W,N,Tw] or [W,N,Tw,1]: device tensors, each optional.  blend: 'mean' | 'hat' | 'first'.
+  row_track: None, or a permutation of range(N) (window row r is row row_track[r] of the results).  Returns a dict with the keys of the inputs
+  given ([N,TL,NC] / [N,TL]) and, with spread=True, `spread` [N,TL].  The plan and the permutation are validated on the host (ValueError)."""
+  if blend not in BLENDS:
+    raise ValueError(f'blend must be one of {sorted(BLENDS)}, got {blend!r}')
+  given = {k: v for k, v in (('tracks', tracks), ('visible_logits', visible_logits), ('frame_err', frame_err)) if v is not None}
+  if not given:
+    raise ValueError('stitch_windows needs tracks, visible_logits or frame_err')
+  if spread and tracks is None:
+    raise ValueError('spread needs tracks')
+  for k, v in given.items():
+    if not isinstance(v, torch.Tensor):
+      raise ValueError(f'{k} must be a tensor')
+  first = next(iter(given.values()))
+  if first.dim() < 3:
+    raise ValueError(f'inputs must be [W,N,Tw,...], got {tuple(first.shape)}')
+  W, N, Tw = (int(v) for v in first.shape[:3])
+  NC = 3
+  for k, v in given.items():
+    shp = tuple(int(x) for x in v.shape)
+    if k == 'tracks':
+      if len(shp) != 4 or shp[:3] != (W, N, Tw) or shp[3] not in (2, 3):
+        raise ValueError(f'tracks must be [W,N,Tw,3] (or 2), got {shp}')
+      NC = shp[3]
+    elif shp not in ((W, N, Tw), (W, N, Tw, 1)):
+      raise ValueError(f'{k} must be {(W, N, Tw)} or {(W, N, Tw, 1)}, got {shp}')
+  if isinstance(num_frames, bool) or not isinstance(num_frames, (int, np.integer)) or num_frames < 1:
+    raise ValueError(f'num_frames must be a positive int, got {num_frames!r}')
+  TL = int(num_frames)
+  if W < 1 or W > MAX_WINDOWS or N < 1 or Tw < 1:
+    raise ValueError(f'W = {W} must lie in [1, {MAX_WINDOWS}] and N, Tw be positive')
+  t0 = _window_plan(starts, TL, Tw, None, 'stitch_windows')
+  if len(t0) != W:
+    raise ValueError(f'{len(t0)} starts for W = {W} windows')
+  if lengths is None:
+    ln = np.minimum(Tw, TL - t0.astype(np.int64))
+  else:
+    ln = _index_array(lengths, 'lengths', 1, Tw + 1, f'a window has {Tw} frames')
+    if len(ln) != W:
+      raise ValueError(f'{len(ln)} lengths for W = {W} windows')
+    if (t0 + ln > TL).any():
+      raise ValueError(f'a window runs past num_frames = {TL}')
+  end = 0
+  for w in range(W):
+    if t0[w] > end:
+      raise ValueError(f'the windows leave a gap: frames [{end}, {int(t0[w])}) are covered by none')
+    end = max(end, int(t0[w] + ln[w]))
+  if end != TL:
+    raise ValueError(f'the windows leave a gap: frames [{end}, {TL}) are covered by none')
+  perm = None
+  if row_track is not None:
+    perm = _index_array(row_track, 'row_track', 0, N, f'there are {N} rows')
+    if len(perm) != N or len(np.unique(perm)) != N:
+      raise ValueError(f'row_track must be a permutation of range({N})')
+  # ---- device pass
+  dev = first.device
+  if dev.type != 'cuda':
+    raise _lib.Spa3dError('stitch_windows runs on the GPU: the 3DSPA hot path is HIP-only (no CPU fallback)')
+  s = _lib.Stitch()
+  s.W, s.N, s.Tw, s.TL, s.NC, s.blend = W, N, Tw, TL, NC, BLENDS[blend]
+  t0c, lnc = (C.c_int32 * W)(*t0.tolist()), (C.c_int32 * W)(*[int(v) for v in ln])
+  s.t0, s.len = t0c, lnc
+  keep, res = [], {}
+  if perm is not None:
+    keep.append(torch.from_numpy(perm.astype(np.int32)).to(dev))
+    s.row_track = keep[-1].data_ptr()
+  for k, v in given.items():
+    v = v.to(device=dev, dtype=torch.float32).contiguous()
+    keep.append(v)
+    setattr(s, k, v.data_ptr())
+    res[k] = torch.empty((N, TL, NC) if k == 'tracks' else (N, TL), dtype=torch.float32, device=dev)
+    setattr(s, 'out_' + k, res[k].data_ptr())
+  if spread:
+    res['spread'] = torch.empty(N, TL, dtype=torch.float32, device=dev)
+    s.out_spread = res['spread'].data_ptr()
+  h = _stitch_handle()
+  with torch.cuda.device(dev):
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(_lib.load().spa3d_stitch_windows(h, C.byref(s), stream), h, 'spa3d_stitch_windows')
+  del keep
+  return res
 
 
 def convert_predictions_to_tapvid3d_format(predictions, query_points=None):

@@ -162,6 +162,39 @@ class TrackScores(_ScoreProperties):
     return SampleScores(self.sample_stats, self.thresholds)
 
 
+@dataclasses.dataclass
+class VideoScores:
+  """What TrackAutoEncoder3D.score_video returns: one clip of n tracks over its own TL frames, in the clip's own track order."""
+  tracks: Optional[torch.Tensor]  # [n, TL, 3] blended predictions (None without return_predictions)
+  visible_logits: Optional[torch.Tensor]  # [n, TL]
+  frame_err: torch.Tensor  # [n, TL] the windows' per-point errors, blended
+  spread: torch.Tensor  # [n, TL] the windows' disagreement about the point (0 under one window)
+  targets_tracks: torch.Tensor  # [n, TL, 3] the clip's own (lifted) tracks, as the windows held them
+  targets_visible: torch.Tensor  # [n, TL]
+  scores: TrackScores  # score_predictions of the blended predictions against the targets: [1, n, ..], over all TL frames
+  window_start: Any  # np.int32 [W]
+  perm: Any  # np.int64 [n]: track perm[r] was row r of every window
+
+  @property
+  def targets(self):
+    """The targets as score_predictions takes them (a batch of one clip)."""
+    return {'query_tracks': self.targets_tracks[None], 'query_tracks_visible': self.targets_visible[None, :, :, None]}
+
+
+def _fold_offsets_of(folds, N):
+  """score_all's `folds`: an int (fold_offsets) or an offsets array [F + 1]; the checked offsets, ValueError otherwise."""
+  import numpy as np
+  if isinstance(folds, (int, np.integer)) and not isinstance(folds, bool):
+    return fold_offsets(N, int(folds))
+  off = folds.detach().cpu().numpy() if isinstance(folds, torch.Tensor) else np.asarray(folds)
+  if off.ndim != 1 or off.size < 3 or off.size > 65 or off.dtype.kind not in 'iu':
+    raise ValueError('folds must be an int or an integer offsets array [F + 1] with 2 <= F <= 64')
+  off = off.astype('int64')
+  if off[0] != 0 or off[-1] != N or (off[1:] <= off[:-1]).any():
+    raise ValueError(f'fold offsets must start at 0, increase strictly and end at N = {N}, got {off.tolist()}')
+  return off
+
+
 def _check_thresholds(thresholds):
   thr = tuple(float(t) for t in thresholds)
   if len(thr) > 8:
@@ -854,16 +887,7 @@ class TrackAutoEncoder3D:
       raise ValueError(f'support_tracks must be a [B,N,T,3] tensor, got {tuple(getattr(st, "shape", ()))}')
     B, N, T = (int(v) for v in st.shape[:3])
     To = self.num_output_frames
-    import numpy as np
-    if isinstance(folds, (int, np.integer)) and not isinstance(folds, bool):
-      off = fold_offsets(N, int(folds))
-    else:
-      off = folds.detach().cpu().numpy() if isinstance(folds, torch.Tensor) else np.asarray(folds)
-      if off.ndim != 1 or off.size < 3 or off.size > 65 or off.dtype.kind not in 'iu':
-        raise ValueError('folds must be an int or an integer offsets array [F + 1] with 2 <= F <= 64')
-      off = off.astype('int64')
-      if off[0] != 0 or off[-1] != N or (off[1:] <= off[:-1]).any():
-        raise ValueError(f'fold offsets must start at 0, increase strictly and end at N = {N}, got {off.tolist()}')
+    off = _fold_offsets_of(folds, N)
     F = len(off) - 1
     cn = validate_counts(batch.get('support_count'), B, N, 'support_count', 1)
     if cn is not None and any(c != N for c in cn):
@@ -932,6 +956,98 @@ class TrackAutoEncoder3D:
     _lib.check(lib.spa3d_score_folds(h, flat.data_ptr(), C.byref(b), F, offs, C.byref(sc), outp, ws.data_ptr(), ws.numel(), _stream(flat)),
                h, 'spa3d_score_folds')
     return res
+
+  def score_video(self, variables, clip, stride=None, folds=8, blend='hat', thresholds=(), perm=None, noise=None, windows_per_call=None,
+                  return_predictions: bool = True, discretize: bool = True) -> 'VideoScores':
+    """Scores for every track of a clip of ANY length.  The model is tied to num_output_frames frames, so the clip (the dict build_batch takes,
+    with any number of frames TL) is cut into overlapping windows of that length (window_starts(TL, num_output_frames, stride), built in place
+    by build_windows), every window goes through score_all, and the per-window predictions and errors are merged back onto the clip's own time
+    axis by stitch_windows with the `blend` ('hat' | 'mean' | 'first') that include/spa3d.h defines.
+      perm: the shuffle of the clip's n tracks that makes the contiguous folds random folds (np.random.permutation(n) when None); the same for
+        every window.  Track perm[r] is row r of every window; the results are back in the clip's own track order.
+      query frames: row r of window w is queried at the first frame of the window in which it is visible, frame 0 of the window if in none.
+      noise: [W, num_latent_tokens, latent_token_dim], one draw per window; None draws it here, once for all windows.
+      windows_per_call: at most this many windows per build_windows / score_all call (default: all).  score_all processes clips one at a
+        time, so the grouping changes memory, not results.
+    The targets are the windows' own support tracks carried onto the long axis by a 'first' stitch; `scores` is score_predictions of the
+    stitched predictions against them, over all TL frames.  Forward only; the 3-D model; no ragged counts; no intra-sample chunk options.
+
+      vs = model.score_video(variables, clip, stride=75)                         # clip: 4096 tracks x 600 frames, say
+      spa3d.save_scores_npz('scores.npz', vs.targets_tracks, vs.frame_err, vs.targets_visible, video=video, intrinsics=K, extrinsics=E)
+      frames = spa3d.render_tracks(video, vs.targets_tracks, vs.frame_err, vs.targets_visible, intrinsics=K, extrinsics=E)
+      unsure = vs.spread > 0.1                                                   # the windows disagree about the point: model uncertainty"""
+    import numpy as np
+    from .data import BLENDS, MAX_WINDOWS, _clip_sources, build_windows, stitch_windows, window_starts
+    thr = _check_thresholds(thresholds)
+    if self._kind == 1:
+      raise ValueError('score_video is not available for the 2-D model')
+    if self.decoder_scan_chunk_size is not None or self.track_chunk_size is not None:
+      raise ValueError('score_video cannot be combined with decoder_scan_chunk_size / track_chunk_size')
+    if not isinstance(clip, dict):
+      raise ValueError('score_video takes ONE clip dict')
+    if clip.get('support_count') is not None or clip.get('query_count') is not None:
+      raise ValueError('score_video does not take ragged counts')
+    if blend not in BLENDS:
+      raise ValueError(f'blend must be one of {sorted(BLENDS)}, got {blend!r}')
+    plan, _, _ = _clip_sources(clip, self, lambda m: ValueError(f'clip: {m}'), None)
+    n, TL, Tw = plan['n'], plan['Tc'], int(self.num_output_frames)
+    starts = window_starts(TL, Tw, stride)
+    W = len(starts)
+    if W > MAX_WINDOWS:
+      raise ValueError(f'{W} windows: a stitch takes at most {MAX_WINDOWS} (use a larger stride)')
+    _fold_offsets_of(folds, n)  # refused here as score_all would
+    if perm is None:
+      perm = np.random.permutation(n)
+    else:
+      perm = perm.detach().cpu().numpy() if isinstance(perm, torch.Tensor) else np.asarray(perm)
+      if perm.ndim != 1 or perm.dtype.kind not in 'iu' or len(perm) != n or not np.array_equal(np.sort(perm), np.arange(n)):
+        raise ValueError(f'perm must be a permutation of range({n})')
+    perm = perm.astype(np.int64)
+    L, Ld = self.num_latent_tokens, self.latent_token_dim
+    if noise is not None and (not isinstance(noise, torch.Tensor) or tuple(noise.shape) != (W, L, Ld)):
+      raise ValueError(f'noise must be a [W, num_latent_tokens, latent_token_dim] = {(W, L, Ld)} tensor, got {tuple(getattr(noise, "shape", ()))}')
+    if windows_per_call is None:
+      windows_per_call = W
+    if isinstance(windows_per_call, bool) or not isinstance(windows_per_call, (int, np.integer)) or windows_per_call < 1:
+      raise ValueError(f'windows_per_call must be a positive int, got {windows_per_call!r}')
+    # ---- device work from here on
+    params = variables['params'] if 'params' in variables and isinstance(variables['params'], dict) else variables
+    flat = self.flat_from_tree(params)
+    _require_cuda(flat, 'params')
+    dev = flat.device
+    # the clip goes to the device once, whatever the grouping: build_windows takes device tensors of the right type as they are
+    types = {'tracks_2d': torch.float32, 'visible': torch.float32, 'tracks_3d': torch.float32, 'depth': torch.float32, 'dino_map': torch.float32,
+             'dino_features': self.act_dtype, 'depth_features': self.act_dtype}
+    dclip = dict(clip)
+    for k, dt in types.items():
+      if clip.get(k) is not None:
+        t = clip[k] if isinstance(clip[k], torch.Tensor) else torch.as_tensor(np.asarray(clip[k]))
+        dclip[k] = t.to(device=dev, dtype=dt).contiguous()
+    if noise is None and discretize:  # one draw for all windows: a window's noise does not depend on the grouping
+      noise = torch.empty(W, L, Ld, dtype=torch.float32, device=dev)
+      _lib.check(_lib.load().spa3d_uniform_noise(noise.data_ptr(), noise.numel(), 0, 0, _stream(flat)), what='spa3d_uniform_noise')
+    parts = {k: [] for k in ('tracks', 'visible_logits', 'frame_err', 'support_tracks', 'support_tracks_visible')}
+    for g0 in range(0, W, int(windows_per_call)):
+      g1 = min(W, g0 + int(windows_per_call))
+      batch = build_windows(dclip, self, starts=starts[g0:g1], order=perm, device=dev)
+      vis = batch['support_tracks_visible'][..., 0] > 0.5
+      batch['query_frame'] = vis.to(torch.int32).argmax(dim=2).to(torch.int32)  # the first visible frame; 0 when there is none
+      sc = self.score_all(variables, batch, folds=folds, frame_errors=True, return_predictions=True, discretize=discretize,
+                          noise=None if noise is None else noise[g0:g1])
+      parts['tracks'].append(sc.predictions.tracks)
+      parts['visible_logits'].append(sc.predictions.visible_logits[..., 0])
+      parts['frame_err'].append(sc.frame_err)
+      parts['support_tracks'].append(batch['support_tracks'])
+      parts['support_tracks_visible'].append(batch['support_tracks_visible'][..., 0])
+    cat = {k: (v[0] if len(v) == 1 else torch.cat(v, 0)) for k, v in parts.items()}
+    out = stitch_windows(starts, TL, tracks=cat['tracks'], visible_logits=cat['visible_logits'], frame_err=cat['frame_err'], blend=blend, row_track=perm, spread=True)
+    tgt = stitch_windows(starts, TL, tracks=cat['support_tracks'], visible_logits=cat['support_tracks_visible'], blend='first', row_track=perm)
+    zeros = torch.zeros(1, n, TL, 1, dtype=torch.float32, device=dev)
+    preds = TrackAutoEncoderResults(out['tracks'][None], out['visible_logits'][None, :, :, None], zeros)
+    scores = score_predictions(preds, {'query_tracks': tgt['tracks'][None], 'query_tracks_visible': tgt['visible_logits'][None, :, :, None]}, thresholds=thr)
+    return VideoScores(tracks=out['tracks'] if return_predictions else None, visible_logits=out['visible_logits'] if return_predictions else None,
+                       frame_err=out['frame_err'], spread=out['spread'], targets_tracks=tgt['tracks'], targets_visible=tgt['visible_logits'], scores=scores,
+                       window_start=starts, perm=perm)
 
   def tapvid3d(self, variables, batch, scalings=('median',), fixed_thresholds: bool = False, ratios: bool = False, discretize: bool = True, noise=None):
     """evaluate_tapvid3d.py:62-115 for one batch: ONE forward pass, then one TAPVid-3D metric call per scaling on that forward's

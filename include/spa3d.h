@@ -355,6 +355,45 @@ typedef struct {            /* one clip; device pointers except intrinsics */
 } spa3d_clip;
 int spa3d_build_batch(spa3d_handle h, const spa3d_clip* clips /* host [B] */, spa3d_batch* out, void* stream);
 
+/* One LONG clip to W window samples in one call: the model is tied to num_output_frames frames (the head's width, the time embedding), so a clip
+ * of clip->T = TL frames, which may exceed out->T = Tw, is scored window by window.  Sample w of the batch (out->B == W) is frames
+ * [t0[w], min(t0[w] + Tw, TL)) of the clip; boundary_frame[w] is that length and the frames beyond it are zeros.  The support and query index
+ * lists are shared by all windows; clip->query_frame, when n_query > 0, is [W, n_query] and window-relative.
+ * Every output byte equals what spa3d_build_batch writes for W clips whose arrays are those frame slices of the long clip -- including channel
+ * 2 of the sampled depth feature (d - d_prev), which is 0 at a window's first frame: a window is a clip that starts there.  The long clip is
+ * addressed in place, no sliced copy of a pool or a map is made: pool rows are read at n * TL + t0 + t, maps at frame t0 + t.  The same kernel,
+ * one wave per (window, frame, slot), frame-major; window descriptors travel by value, 16 per launch; no atomics.
+ * SPA3D_ERR_ARG with a message, before the first launch: W < 1 or out->B != W; a t0[w] outside [0, TL); t0 not strictly increasing; and
+ * everything spa3d_build_batch refuses, except a clip T above out->T. */
+int spa3d_build_windows(spa3d_handle h, const spa3d_clip* clip, int32_t W, const int32_t* t0 /* HOST [W] */, spa3d_batch* out, void* stream);
+
+/* The per-window results of a long clip merged back onto the clip's own time axis.  Window w covers frames [t0[w], t0[w] + len[w]); window row
+ * r is row row_track[r] of every result (a permutation of [0, N); an entry outside that range writes nothing; not checked on the host: it is a
+ * device array).  Per output element, in fp32, over the windows that cover its frame, in increasing w, with the integer weight of the
+ * window-relative frame j of a window of L = len[w] frames -- SPA3D_BLEND_MEAN: 1, SPA3D_BLEND_HAT: min(j + 1, L - j):
+ *   num = sum float(wgt) * v, den = sum float(wgt), each added left to right; the result is num / den, one division.
+ *   A frame under exactly one window takes that window's value unchanged.  SPA3D_BLEND_FIRST: the lowest-numbered window that covers the
+ *   frame supplies the value unchanged (targets carried onto the long axis exactly).
+ *   out_spread[n][t] = sqrtf(max over the contributing windows of sum_c (p_w - p_blend)^2), 0 under one window, NaN if any distance is: the
+ *   windows' disagreement about one track point.
+ * csrc/window_row.hpp is the only implementation of the plan checks, the weights and the blend.  One wave per row, lanes along t; every output
+ * is written once by its owner, no atomics: two runs give the same bytes.  Asynchronous, allocates nothing, takes no workspace, reads nothing
+ * back; t0 and len are consumed before the call returns.
+ * SPA3D_ERR_ARG with a message, before the first launch: no output wanted; a wanted output whose input is missing (out_spread needs tracks); W
+ * outside [1, 256], N or TL outside [1, 2^24], Tw outside [1, 2^20], NC outside {2, 3}; blend outside the three values; a t0[w] outside [0, TL)
+ * or t0 not strictly increasing; len[w] outside [1, Tw] or running past TL; a frame of [0, TL) that no window covers. */
+#define SPA3D_BLEND_MEAN 0
+#define SPA3D_BLEND_HAT 1
+#define SPA3D_BLEND_FIRST 2
+typedef struct {
+  int32_t W, N, Tw, TL, NC, blend;           /* W <= 256: starts and lengths travel by value */
+  const int32_t* t0;  const int32_t* len;     /* HOST [W]; len NULL = min(Tw, TL - t0[w]) */
+  const int32_t* row_track;                   /* device [N] or NULL: window row r is row row_track[r] of the result (a permutation) */
+  const float *tracks, *visible_logits, *frame_err;                        /* device [W,N,Tw,NC] / [W,N,Tw] / [W,N,Tw]; each may be NULL */
+  float *out_tracks, *out_visible_logits, *out_frame_err, *out_spread;     /* device [N,TL,NC] / [N,TL] x 3; NULL = not wanted */
+} spa3d_stitch;
+int spa3d_stitch_windows(spa3d_handle h, const spa3d_stitch* s, void* stream);
+
 /* forward + loss + backward.  grads (flat f32, same layout as params) is OVERWRITTEN unless
  * accumulate!=0.  denom: global sum(query_tracks_visible) for data-parallel runs (the loss
  * normalisers are batch-global, train.py:111-113,119-121); <=0 = this batch's own.
