@@ -85,6 +85,8 @@ class Stitch(C.Structure):
 
 
 BLEND_MEAN, BLEND_HAT, BLEND_FIRST = 0, 1, 2  # SPA3D_BLEND_* (include/spa3d.h)
+POOL_TOKEN, POOL_CLIP = 0, 1                  # SPA3D_POOL_*
+PDIST_DOT, PDIST_SQDIST = 0, 1                # SPA3D_PDIST_*
 
 _SIGS = {
     'spa3d_version': (C.c_char_p, []),
@@ -115,6 +117,9 @@ _SIGS = {
     'spa3d_build_batch': (C.c_int, [C.c_void_p, C.POINTER(Clip), C.POINTER(Batch), C.c_void_p]),
     'spa3d_build_windows': (C.c_int, [C.c_void_p, C.POINTER(Clip), C.c_int32, C.POINTER(C.c_int32), C.POINTER(Batch), C.c_void_p]),
     'spa3d_stitch_windows': (C.c_int, [C.c_void_p, C.POINTER(Stitch), C.c_void_p]),
+    'spa3d_motion_codes': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'spa3d_motion_moments_add': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    'spa3d_motion_pdist': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     'spa3d_op_median_rows': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     'spa3d_loss_and_grads': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Batch), C.c_float, C.c_void_p, C.c_int32,
                                        C.c_void_p, C.POINTER(Outputs), C.c_void_p, C.c_int64, C.c_void_p]),

@@ -1,0 +1,310 @@
+// motion.hip -- the latent-set metrics' device side (include/spa3d.h), each kernel first, the entry points below them:
+//   spa3d_motion_codes        latents -> the integer codes the decoder's quantiser rounds to (streaming, 16-byte loads);
+//   spa3d_motion_moments_add  n, sum x, sum x x^T of token rows or of per-clip token sums, in 64-bit integers, ADDED into a caller-held state;
+//   spa3d_motion_pdist        all pairwise dot products / squared distances of two code sets: a tiled NT GEMM on mfma_f32_16x16x32_bf16 whose
+//                             fp32 accumulators are moved into int32 every MOTION_KCHUNK elements of K, so every result is an exact integer.
+// The code rounding, the state layout, the range checks and the chunk constant are motion_code.hpp's, which the g++ host test runs too.
+// Nothing here adds floats across threads: the only atomics are integer adds, which commute, so two runs -- and any batching, chunking or
+// rank split of the same clips -- give the same bits.  No 16-bit activations are touched: compiled once.  Plain loads and stores.
+#include "common.hpp"
+#include "motion_code.hpp"
+
+namespace SPA_NS {
+
+// ---------------------------------------------------------------------------------------------- codes
+__device__ __forceinline__ int16_t mo_code_count(float x, int& nb) {
+  bool nan = false;
+  const int16_t c = mc_code(x, &nan);
+  nb += nan ? 1 : 0;
+  return c;
+}
+
+// VEC: latents 16-byte and codes 8-byte aligned -- four latents per load, the n % 4 tail by scalar loads
+template <bool VEC> __global__ __launch_bounds__(256) void motion_codes_kernel(const float* __restrict__ lat, int64_t n, int16_t* __restrict__ codes, int32_t* bad) {
+  int nb = 0;
+  const int64_t t0 = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
+  int64_t done = 0;
+  if (VEC) {
+    const int64_t n4 = n >> 2;
+    for (int64_t i = t0; i < n4; i += stride) {
+      const float4 v = reinterpret_cast<const float4*>(lat)[i];
+      short4 o;
+      o.x = mo_code_count(v.x, nb); o.y = mo_code_count(v.y, nb); o.z = mo_code_count(v.z, nb); o.w = mo_code_count(v.w, nb);
+      reinterpret_cast<short4*>(codes)[i] = o;
+    }
+    done = n4 << 2;
+  }
+  for (int64_t i = done + t0; i < n; i += stride) codes[i] = mo_code_count(lat[i], nb);
+  // NaNs of the wave, one integer atomic per wave that saw any
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) nb += __shfl_down(nb, off);
+  if ((threadIdx.x & 63) == 0 && nb) atomicAdd(bad, nb);
+}
+
+void k_motion_codes(spa3d_ctx* c, const float* lat, int64_t n, int16_t* codes, int32_t* bad) {
+  if (c->dry) return;
+  hipError_t e = hipMemsetAsync(bad, 0, sizeof(int32_t), c->stream);
+  if (e != hipSuccess && c->hip_err == 0) { c->hip_err = (int)e; c->err = std::string("motion_codes: hipMemsetAsync failed: ") + hipGetErrorString(e); }
+  if (n == 0 || c->hip_err) return;
+  const bool vec = ((uintptr_t)lat & 15) == 0 && ((uintptr_t)codes & 7) == 0;
+  if (vec) motion_codes_kernel<true><<<GRID1D(cdiv(n, 4), 256), 256, 0, c->stream>>>(lat, n, codes, bad);
+  else motion_codes_kernel<false><<<GRID1D(n, 256), 256, 0, c->stream>>>(lat, n, codes, bad);
+  SPA_LAUNCH_CHECK(c);
+}
+
+// ---------------------------------------------------------------------------------------------- moments
+// One workgroup per (slice of samples, 64 x 64 tile of S).  A batch of MM_S samples is staged in LDS as int32 -- columns [i0, i0 + 64) and
+// [j0, j0 + 64), each a token row's code or, for the clip pool, the sum of the clip's R = L token rows -- and thread (ti, tj) adds its 4 x 4
+// products into 64-bit registers.  The tiles of the first tile column also sum s, tile (0, 0) of slice 0 adds n.
+constexpr int MM_TILE = 64, MM_S = 16, MM_SLICES = 64;
+
+__global__ __launch_bounds__(256) void motion_moments_kernel(const int16_t* __restrict__ codes, int64_t nsamp, int R, int D, unsigned long long* state) {
+  __shared__ __attribute__((aligned(16))) int32_t xi[MM_S][MM_TILE];
+  __shared__ __attribute__((aligned(16))) int32_t xj[MM_S][MM_TILE];
+  const int tiles = (D + MM_TILE - 1) / MM_TILE;
+  const int i0 = ((int)blockIdx.y / tiles) * MM_TILE, j0 = ((int)blockIdx.y % tiles) * MM_TILE;
+  const int ti = threadIdx.x >> 4, tj = threadIdx.x & 15;
+  int64_t acc[4][4];
+#pragma unroll
+  for (int p = 0; p < 4; ++p)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) acc[p][q] = 0;
+  int64_t ssum = 0;
+  for (int64_t base = (int64_t)blockIdx.x * MM_S; base < nsamp; base += (int64_t)gridDim.x * MM_S) {
+    __syncthreads();   // the previous batch has been read
+    for (int idx = threadIdx.x; idx < MM_S * 2 * MM_TILE; idx += 256) {
+      const int s = idx >> 7, c = idx & 127;
+      const int col = c < MM_TILE ? i0 + c : j0 + c - MM_TILE;
+      const int64_t m = base + s;
+      int32_t v = 0;
+      if (m < nsamp && col < D) {
+        const int16_t* p = codes + m * R * D + col;
+        for (int l = 0; l < R; ++l) v += (int32_t)p[(int64_t)l * D];   // |v| <= 128 * 4096 = 2^19
+      }
+      if (c < MM_TILE) xi[s][c] = v; else xj[s][c - MM_TILE] = v;
+    }
+    __syncthreads();
+#pragma unroll 4
+    for (int s = 0; s < MM_S; ++s) {
+      const int4 a = *reinterpret_cast<const int4*>(&xi[s][ti * 4]);
+      const int4 b = *reinterpret_cast<const int4*>(&xj[s][tj * 4]);
+      const int32_t av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+      for (int p = 0; p < 4; ++p)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[p][q] += (int64_t)av[p] * (int64_t)bv[q];
+    }
+    if (j0 == 0 && threadIdx.x < MM_TILE)
+      for (int s = 0; s < MM_S; ++s) ssum += xi[s][threadIdx.x];
+  }
+#pragma unroll
+  for (int p = 0; p < 4; ++p)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int i = i0 + ti * 4 + p, j = j0 + tj * 4 + q;
+      if (i < D && j < D && acc[p][q] != 0) atomicAdd(&state[mc_state_S(D, i, j)], (unsigned long long)acc[p][q]);
+    }
+  if (j0 == 0 && threadIdx.x < MM_TILE && i0 + (int)threadIdx.x < D && ssum != 0) atomicAdd(&state[mc_state_s(i0 + threadIdx.x)], (unsigned long long)ssum);
+  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) atomicAdd(&state[mc_state_n()], (unsigned long long)nsamp);
+}
+
+void k_motion_moments(spa3d_ctx* c, const int16_t* codes, int64_t M, int L, int D, int pool, int64_t* state) {
+  if (c->dry) return;
+  const int64_t nsamp = mc_samples(M, L, pool);
+  const int tiles = (D + MM_TILE - 1) / MM_TILE;
+  const dim3 grid((unsigned)std::min<int64_t>(cdiv(nsamp, MM_S), MM_SLICES), (unsigned)(tiles * tiles));
+  motion_moments_kernel<<<grid, 256, 0, c->stream>>>(codes, nsamp, pool == MC_POOL_TOKEN ? 1 : L, D, reinterpret_cast<unsigned long long*>(state));
+  SPA_LAUNCH_CHECK(c);
+}
+
+// ---------------------------------------------------------------------------------------------- pairwise distances
+// out[i][j] = sum_e a[i][e] b[j][e]: an NT GEMM, K contiguous in both operands.  A workgroup of 4 waves owns a 128 x 128 tile, a wave 64 x 64 of
+// it as 4 x 4 fragments of mfma_f32_16x16x32_bf16.  Per step of PD_BK = 64 elements of K each thread loads four 16-byte chunks (8 codes) of each
+// operand, converts them to bf16 (exact: |code| <= 128) and stores them into the LDS image; the next step's loads are issued before this
+// step's MFMAs.  LDS image: row-major, 8 chunks of 16 bytes per row, chunk s of row r at slot s ^ (r & 7) -- the 16 lanes ds_read_b128 serves
+// together (8 rows of one chunk column, 8 of the next) then fall into 16 different 16-byte slots of the 256-byte bank row: conflict-free.
+// A fragment is one ds_read_b128: lane l holds row l & 15, k = 8 (l >> 4) .. + 7 of the 32-wide step, for A and for B alike.
+// Rows past Ma / Mb and the K tail are zeros in LDS; the store is guarded.  Squared norms are summed from the very integers that are staged.
+constexpr int PD_BM = 128, PD_BN = 128, PD_BK = 64, PD_FLUSH = MOTION_KCHUNK / PD_BK;
+static_assert(MOTION_KCHUNK % PD_BK == 0, "a flush falls on a step boundary");
+typedef __attribute__((ext_vector_type(4))) float pd_f32x4;
+
+// chunk (8 codes from element k) of row r: zeros past the rows or past E.  vec: E % 8 == 0 and a 16-byte aligned base, so a chunk is whole
+__device__ __forceinline__ uint4 pd_load(const int16_t* __restrict__ base, int64_t rows, int E, int64_t r, int k, bool vec) {
+  uint4 v = make_uint4(0u, 0u, 0u, 0u);
+  if (r >= rows || k >= E) return v;
+  const int16_t* p = base + r * E + k;
+  if (vec) return *reinterpret_cast<const uint4*>(p);
+  unsigned e[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) e[j] = k + j < E ? (unsigned)(unsigned short)p[j] : 0u;
+  v.x = e[0] | (e[1] << 16); v.y = e[2] | (e[3] << 16); v.z = e[4] | (e[5] << 16); v.w = e[6] | (e[7] << 16);
+  return v;
+}
+// two int16 codes of a dword -> two bf16; sq += their squares
+__device__ __forceinline__ unsigned pd_cvt2(unsigned w, int& sq) {
+  const int lo = (int)(short)(w & 0xffffu), hi = (int)w >> 16;
+  sq += lo * lo + hi * hi;
+  return f2bf_pack2((float)lo, (float)hi);
+}
+__device__ __forceinline__ uint4 pd_cvt8(uint4 v, int& sq) { return make_uint4(pd_cvt2(v.x, sq), pd_cvt2(v.y, sq), pd_cvt2(v.z, sq), pd_cvt2(v.w, sq)); }
+
+template <bool SQ> __global__ __launch_bounds__(256) void motion_pdist_kernel(const int16_t* __restrict__ a, int64_t Ma, const int16_t* __restrict__ b, int64_t Mb, int E,
+                                                                              int32_t* __restrict__ out, int vec) {
+  __shared__ uint4 sA[PD_BM * 8];
+  __shared__ uint4 sB[PD_BN * 8];
+  __shared__ int32_t sNa[PD_BM], sNb[PD_BN];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, wm = wv >> 1, wn = wv & 1;
+  const int64_t i0 = (int64_t)blockIdx.y * PD_BM, j0 = (int64_t)blockIdx.x * PD_BN;
+  const int srow = tid >> 3, sslot = tid & 7;   // this thread stages chunk sslot of rows srow + 32 i, i = 0..3
+  pd_f32x4 facc[4][4];
+  int32_t iacc[4][4][4];
+#pragma unroll
+  for (int m = 0; m < 4; ++m)
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+      facc[m][n] = pd_f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int r = 0; r < 4; ++r) iacc[m][n][r] = 0;
+    }
+  int na[4] = {0, 0, 0, 0}, nb[4] = {0, 0, 0, 0};
+  uint4 ra[4], rb[4];
+  const int nk = (E + PD_BK - 1) / PD_BK;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    ra[i] = pd_load(a, Ma, E, i0 + srow + 32 * i, sslot * 8, vec != 0);
+    rb[i] = pd_load(b, Mb, E, j0 + srow + 32 * i, sslot * 8, vec != 0);
+  }
+  for (int kt = 0; kt < nk; ++kt) {
+    __syncthreads();   // the previous step's fragments have been read
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int r = srow + 32 * i;
+      sA[r * 8 + (sslot ^ (r & 7))] = pd_cvt8(ra[i], na[i]);
+      sB[r * 8 + (sslot ^ (r & 7))] = pd_cvt8(rb[i], nb[i]);
+    }
+    __syncthreads();
+    if (kt + 1 < nk) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        ra[i] = pd_load(a, Ma, E, i0 + srow + 32 * i, (kt + 1) * PD_BK + sslot * 8, vec != 0);
+        rb[i] = pd_load(b, Mb, E, j0 + srow + 32 * i, (kt + 1) * PD_BK + sslot * 8, vec != 0);
+      }
+    }
+#pragma unroll
+    for (int ks = 0; ks < PD_BK / 32; ++ks) {
+      const int slot = ks * 4 + (lane >> 4);
+      mfma16x8 fa[4], fb[4];
+#pragma unroll
+      for (int f = 0; f < 4; ++f) {
+        const int rA = wm * 64 + f * 16 + (lane & 15), rB = wn * 64 + f * 16 + (lane & 15);
+        fa[f] = __builtin_bit_cast(mfma16x8, sA[rA * 8 + (slot ^ (rA & 7))]);
+        fb[f] = __builtin_bit_cast(mfma16x8, sB[rB * 8 + (slot ^ (rB & 7))]);
+      }
+#pragma unroll
+      for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int n = 0; n < 4; ++n) facc[m][n] = MFMA16(fa[m], fb[n], facc[m][n]);
+    }
+    // the chunk rule (motion_code.hpp): MOTION_KCHUNK elements of K have gone into the fp32 accumulators, every partial sum an integer of at
+    // most 2^24 in magnitude; move them into the integers and start the next chunk from zero
+    if ((kt + 1) % PD_FLUSH == 0 || kt + 1 == nk) {
+#pragma unroll
+      for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int n = 0; n < 4; ++n) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) iacc[m][n][r] += __float2int_rn(facc[m][n][r]);
+          facc[m][n] = pd_f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    }
+  }
+  if (SQ) {
+    // the 8 threads that staged a row hold its squared norm in parts: lanes 8 q .. 8 q + 7 of a wave
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+      for (int off = 1; off < 8; off <<= 1) { na[i] += __shfl_xor(na[i], off); nb[i] += __shfl_xor(nb[i], off); }
+      if (sslot == 0) { sNa[srow + 32 * i] = na[i]; sNb[srow + 32 * i] = nb[i]; }
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int m = 0; m < 4; ++m)
+#pragma unroll
+    for (int n = 0; n < 4; ++n)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int li = wm * 64 + m * 16 + (lane >> 4) * 4 + r, lj = wn * 64 + n * 16 + (lane & 15);   // C/D: col = lane & 15, row = 4 (lane >> 4) + r
+        const int64_t i = i0 + li, j = j0 + lj;
+        if (i < Ma && j < Mb) out[i * Mb + j] = SQ ? sNa[li] + sNb[lj] - 2 * iacc[m][n][r] : iacc[m][n][r];
+      }
+}
+
+void k_motion_pdist(spa3d_ctx* c, const int16_t* a, int64_t Ma, const int16_t* b, int64_t Mb, int E, int kind, int32_t* out) {
+  if (c->dry) return;
+  const int vec = (E % 8 == 0 && ((uintptr_t)a & 15) == 0 && ((uintptr_t)b & 15) == 0) ? 1 : 0;
+  const dim3 grid((unsigned)cdiv(Mb, PD_BN), (unsigned)cdiv(Ma, PD_BM));
+  if (kind == MC_PDIST_SQDIST) motion_pdist_kernel<true><<<grid, 256, 0, c->stream>>>(a, Ma, b, Mb, E, out, vec);
+  else motion_pdist_kernel<false><<<grid, 256, 0, c->stream>>>(a, Ma, b, Mb, E, out, vec);
+  SPA_LAUNCH_CHECK(c);
+}
+
+}  // namespace SPA_NS
+
+// ---- the entry points ----
+static_assert(MC_POOL_TOKEN == SPA3D_POOL_TOKEN && MC_POOL_CLIP == SPA3D_POOL_CLIP && MC_PDIST_DOT == SPA3D_PDIST_DOT && MC_PDIST_SQDIST == SPA3D_PDIST_SQDIST,
+              "motion_code.hpp and include/spa3d.h name the same values");
+extern "C" {
+
+int spa3d_motion_codes(spa3d_handle h, const float* latents, int64_t n, int16_t* codes, int32_t* bad, void* stream) {
+  if (!h) return SPA3D_ERR_ARG;
+  h->err.clear(); h->hip_err = 0;
+  auto refuse = [&](const std::string& m) { h->err = "motion_codes: " + m; return SPA3D_ERR_ARG; };
+  if (!latents) return refuse("latents is required");
+  if (!codes) return refuse("codes is required");
+  if (!bad) return refuse("bad is required");
+  if (mc_codes_check(n) != MC_OK) return refuse("n = " + std::to_string(n) + " is negative");
+  h->stream = (hipStream_t)stream; h->dry = false;
+  SPA_NS::k_motion_codes(h, latents, n, codes, bad);
+  return h->hip_err ? SPA3D_ERR_HIP : SPA3D_OK;
+}
+
+int spa3d_motion_moments_add(spa3d_handle h, const int16_t* codes, int64_t M, int32_t L, int32_t D, int32_t pool, int64_t* state, void* stream) {
+  if (!h) return SPA3D_ERR_ARG;
+  h->err.clear(); h->hip_err = 0;
+  auto refuse = [&](const std::string& m) { h->err = "motion_moments_add: " + m; return SPA3D_ERR_ARG; };
+  if (!codes) return refuse("codes is required");
+  if (!state) return refuse("state is required");
+  switch (mc_moments_check(M, L, D, pool)) {
+    case MC_BAD_M: return refuse("M = " + std::to_string(M) + " is outside [1, 2^40]");
+    case MC_BAD_L: return refuse("L = " + std::to_string(L) + " is outside [1, " + std::to_string(MC_MAX_L) + "]");
+    case MC_BAD_D: return refuse("D = " + std::to_string(D) + " is outside [1, " + std::to_string(MC_MAX_D) + "]");
+    case MC_BAD_POOL: return refuse("pool = " + std::to_string(pool) + " is neither SPA3D_POOL_TOKEN nor SPA3D_POOL_CLIP");
+    default: break;
+  }
+  h->stream = (hipStream_t)stream; h->dry = false;
+  SPA_NS::k_motion_moments(h, codes, M, L, D, pool, state);
+  return h->hip_err ? SPA3D_ERR_HIP : SPA3D_OK;
+}
+
+int spa3d_motion_pdist(spa3d_handle h, const int16_t* a, int64_t Ma, const int16_t* b, int64_t Mb, int32_t E, int32_t kind, int32_t* out, void* stream) {
+  if (!h) return SPA3D_ERR_ARG;
+  h->err.clear(); h->hip_err = 0;
+  auto refuse = [&](const std::string& m) { h->err = "motion_pdist: " + m; return SPA3D_ERR_ARG; };
+  if (!a) return refuse("a is required");
+  if (!b) return refuse("b is required");
+  if (!out) return refuse("out is required");
+  switch (mc_pdist_check(Ma, Mb, E, kind)) {
+    case MC_BAD_M: return refuse("Ma = " + std::to_string(Ma) + " is outside [1, 2^22]");
+    case MC_BAD_MB: return refuse("Mb = " + std::to_string(Mb) + " is outside [1, 2^22]");
+    case MC_BAD_E: return refuse("E = " + std::to_string(E) + " is outside [1, " + std::to_string(MC_MAX_E) + "]");
+    case MC_BAD_KIND: return refuse("kind = " + std::to_string(kind) + " is neither SPA3D_PDIST_DOT nor SPA3D_PDIST_SQDIST");
+    default: break;
+  }
+  h->stream = (hipStream_t)stream; h->dry = false;
+  SPA_NS::k_motion_pdist(h, a, Ma, b, Mb, E, kind, out);
+  return h->hip_err ? SPA3D_ERR_HIP : SPA3D_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,70 @@
+// motion_code.hpp -- the integer side of the latent-set metrics (include/spa3d.h: spa3d_motion_codes, spa3d_motion_moments_add, spa3d_motion_pdist).
+// Plain C++, host- and device-callable: the kernels of motion.hip, the entry points' range checks and the g++ host test
+// (tests/host/motion_code_check.cpp) run THIS code.
+//
+// Four things live here.
+//   The code of a latent: c = (int16) rintf(clip(x, -1, 1) * 128.f), an integer in [-128, 128] -- the integer discretize_kernel (loss.hip) rounds to
+//     before it adds the dither.  The product is exact (a power of two), rintf rounds ties to even, +-inf clips to +-128, -0.0 gives 0.  A NaN has
+//     no code: it gives 0 and is reported, and the callers count it.
+//   The moment state of D-dimensional samples: int64 [1 + D + D * D] = n, s[D] = sum x, S[D][D] = sum x x^T (both triangles), with the index
+//     helpers below.  A sample is a token row c[m][l][:] (MC_POOL_TOKEN, |x| <= 128) or a clip's token sum (MC_POOL_CLIP, |x| <= 128 L).
+//   The chunk rule of the pairwise-distance GEMM: codes are exact in bf16 (integers up to 256 are), a product of two is at most 128 * 128 = 2^14,
+//     and a sum of MOTION_KCHUNK = 1024 of them is at most 2^24 in magnitude, every partial sum an integer of at most that magnitude: exact in the
+//     fp32 MFMA accumulator whatever the order.  So after every MOTION_KCHUNK elements of K the accumulator is moved into an int32 and cleared.
+//   The range checks of the three entries, as codes the entry points turn into messages.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define MC_HD __host__ __device__ __forceinline__
+#else
+#define MC_HD inline
+#endif
+
+constexpr int MC_CODE_MAX = 128;                       // |code| <= 128
+constexpr int MOTION_KCHUNK = 1024;                    // K elements between two flushes of the fp32 accumulator
+static_assert((int64_t)MOTION_KCHUNK * MC_CODE_MAX * MC_CODE_MAX == (int64_t)1 << 24, "a chunk's largest partial sum is the last integer run fp32 holds exactly");
+enum { MC_POOL_TOKEN = 0, MC_POOL_CLIP = 1 };          // = SPA3D_POOL_TOKEN, SPA3D_POOL_CLIP
+enum { MC_PDIST_DOT = 0, MC_PDIST_SQDIST = 1 };        // = SPA3D_PDIST_DOT, SPA3D_PDIST_SQDIST
+constexpr int MC_MAX_L = 4096, MC_MAX_D = 256;         // moments: tokens per clip, token width
+constexpr int MC_MAX_E = 32767;                        // pdist: E * 256^2 < 2^31, so |a|^2 + |b|^2 - 2 a.b fits an int32
+constexpr int64_t MC_MAX_M = (int64_t)1 << 22;         // pdist: rows of either set (the launch grid)
+static_assert((int64_t)MC_MAX_E * 256 * 256 < ((int64_t)1 << 31), "the squared distance fits an int32");
+
+// ---- the code ----
+// the code of x; a NaN gives 0 and sets *nan (left alone otherwise)
+MC_HD int16_t mc_code(float x, bool* nan) {
+  if (x != x) { *nan = true; return 0; }
+  const float c = x < -1.f ? -1.f : (x > 1.f ? 1.f : x);
+  return (int16_t)rintf(c * 128.f);
+}
+
+// ---- the moment state ----
+MC_HD int64_t mc_state_len(int D) { return 1 + (int64_t)D + (int64_t)D * D; }
+MC_HD int64_t mc_state_n() { return 0; }
+MC_HD int64_t mc_state_s(int i) { return 1 + (int64_t)i; }
+MC_HD int64_t mc_state_S(int D, int i, int j) { return 1 + (int64_t)D + (int64_t)i * D + j; }
+// samples a call adds, and the largest |x_i x_j| of one sample
+MC_HD int64_t mc_samples(int64_t M, int L, int pool) { return pool == MC_POOL_TOKEN ? M * L : M; }
+MC_HD int64_t mc_sample_sq_max(int L, int pool) { return pool == MC_POOL_TOKEN ? (int64_t)MC_CODE_MAX * MC_CODE_MAX : (int64_t)MC_CODE_MAX * L * MC_CODE_MAX * L; }
+// the largest n whose sums cannot pass 2^62: n * mc_sample_sq_max <= 2^62
+MC_HD int64_t mc_samples_max(int L, int pool) { return ((int64_t)1 << 62) / mc_sample_sq_max(L, pool); }
+
+// ---- the range checks ----
+enum { MC_OK = 0, MC_BAD_M = 1, MC_BAD_L = 2, MC_BAD_D = 3, MC_BAD_POOL = 4, MC_BAD_E = 5, MC_BAD_KIND = 6, MC_BAD_MB = 7, MC_BAD_N = 8 };
+MC_HD int mc_codes_check(int64_t n) { return n < 0 ? MC_BAD_N : MC_OK; }
+MC_HD int mc_moments_check(int64_t M, int L, int D, int pool) {
+  if (M < 1 || M > ((int64_t)1 << 40)) return MC_BAD_M;
+  if (L < 1 || L > MC_MAX_L) return MC_BAD_L;
+  if (D < 1 || D > MC_MAX_D) return MC_BAD_D;
+  if (pool != MC_POOL_TOKEN && pool != MC_POOL_CLIP) return MC_BAD_POOL;
+  return MC_OK;
+}
+MC_HD int mc_pdist_check(int64_t Ma, int64_t Mb, int E, int kind) {
+  if (Ma < 1 || Ma > MC_MAX_M) return MC_BAD_M;
+  if (Mb < 1 || Mb > MC_MAX_M) return MC_BAD_MB;
+  if (E < 1 || E > MC_MAX_E) return MC_BAD_E;
+  if (kind != MC_PDIST_DOT && kind != MC_PDIST_SQDIST) return MC_BAD_KIND;
+  return MC_OK;
+}

@@ -778,6 +778,12 @@ class TrackAutoEncoder3D:
                  h, 'spa3d_encode')
     return lat
 
+  def motion_codes(self, variables, inputs):
+    """The integer codes of the batch's latents (include/spa3d.h, "Latent-set metrics"): `encode`, then spa3d_motion_codes -> int16
+    [B, num_latent_tokens, latent_token_dim], what MotionStats.update, motion_pdist and precision_recall take.  ValueError on a NaN latent."""
+    from .motion import motion_codes
+    return motion_codes(self.encode(variables, inputs))
+
   def get_decoder_context(self, inputs):
     """3d:206-233."""
     qp = inputs.get('query_points')

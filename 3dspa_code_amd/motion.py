@@ -1,0 +1,275 @@
+"""Latent-set metrics on the integer codes of the bottleneck (include/spa3d.h, "Latent-set metrics": the library's own definitions, the
+reference has no counterpart).  The device work is csrc/motion.hip -- codes, exact integer moments, exact integer pairwise distances; what is
+left here is plumbing: the moment state and its merges, the Frechet distance in float64 NumPy, and the k-NN precision / recall selection."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+
+CODE_MAX = 128          # |code| <= 128 (csrc/motion_code.hpp)
+MAX_L, MAX_D, MAX_E = 4096, 256, 32767
+POOLS = {'token': _lib.POOL_TOKEN, 'clip': _lib.POOL_CLIP}
+KINDS = {'dot': _lib.PDIST_DOT, 'sqdist': _lib.PDIST_SQDIST}
+
+_MOTION_HANDLE = []
+
+
+def _motion_handle():
+  """A handle of the motion calls' own: they use it for the error message and the stream only, and must not reset those of a handle a model
+  is using."""
+  if not _MOTION_HANDLE:
+    from .model import TrackAutoEncoder3D
+    _MOTION_HANDLE.append(TrackAutoEncoder3D(num_output_frames=8, use_dino=False, use_depth=False, precision='fp32'))  # the model owns its handles
+  return _MOTION_HANDLE[0]._handle(0, 0)[0]
+
+
+def _on_device(t, name, what):
+  if not isinstance(t, torch.Tensor):
+    raise ValueError(f'{name} must be a tensor')
+  if t.device.type != 'cuda':
+    raise _lib.Spa3dError(f'{what} runs on the GPU: the 3DSPA hot path is HIP-only (no CPU fallback)')
+
+
+def _stream(t):
+  return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+
+
+def _codes_arg(codes, name, what):
+  _on_device(codes, name, what)
+  if codes.dtype != torch.int16:
+    raise ValueError(f'{name} must be int16 codes (motion_codes), got {codes.dtype}')
+  return codes.contiguous()
+
+
+# ------------------------------------------------------------------------------------------------ codes
+def motion_codes(latents):
+  """The integer codes of latents the caller already has (spa3d_motion_codes): c = rint(clip(x, -1, 1) * 128) as int16, the shape of the input.
+  ValueError when a latent is NaN (it has no code)."""
+  _on_device(latents, 'latents', 'motion_codes')
+  lat = latents.to(torch.float32).contiguous()
+  codes = torch.empty(lat.shape, dtype=torch.int16, device=lat.device)
+  bad = torch.empty(1, dtype=torch.int32, device=lat.device)
+  h = _motion_handle()
+  with torch.cuda.device(lat.device):
+    _lib.check(_lib.load().spa3d_motion_codes(h, lat.data_ptr(), lat.numel(), codes.data_ptr(), bad.data_ptr(), _stream(lat)), h, 'spa3d_motion_codes')
+  nbad = int(bad.item())
+  if nbad > 0:
+    raise ValueError(f'{nbad} of {lat.numel()} latents are NaN: they have no code')
+  return codes
+
+
+# ------------------------------------------------------------------------------------------------ moments
+def samples_max(L: int, pool: str) -> int:
+  """the largest sample count whose integer sums cannot pass 2^62 (mc_samples_max of csrc/motion_code.hpp): n * 2^14 (token pool) or
+  n * (128 L)^2 (clip pool) stays at or below 2^62"""
+  return (1 << 62) // (CODE_MAX * CODE_MAX if pool == 'token' else (CODE_MAX * L) ** 2)
+
+
+class MotionStats:
+  """Count, sum and sum of outer products of D-dimensional latent samples, as exact integers: one int64 tensor [1 + D + D * D] = n, s, S
+  (spa3d_motion_moments_add adds into it).  pool='token': every token row of every clip is a sample (x = c / 128); pool='clip': every clip's
+  mean token (x = sum_l c[l] / (128 L)).  The state is the same bits however the clips were batched, and two states merge by integer addition
+  (merge, all_reduce).  n, mean and cov are float64 on the host, in latent units; cov is the biased S / n - mu mu^T."""
+
+  def __init__(self, D: int, L: int, pool: str = 'clip'):
+    if pool not in POOLS:
+      raise ValueError(f'pool must be one of {sorted(POOLS)}, got {pool!r}')
+    for name, v, hi in (('D', D, MAX_D), ('L', L, MAX_L)):
+      if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1 or v > hi:
+        raise ValueError(f'{name} = {v!r} is outside [1, {hi}]')
+    self.D, self.L, self.pool = int(D), int(L), pool
+    self.state = torch.zeros(1 + self.D + self.D * self.D, dtype=torch.int64)
+    self._n = 0   # tracked on the host: update() needs no read-back
+
+  # ---- sizes
+  @property
+  def n(self) -> int:
+    return self._n
+
+  @property
+  def divisor(self) -> int:
+    """codes per latent unit of one sample coordinate"""
+    return CODE_MAX if self.pool == 'token' else CODE_MAX * self.L
+
+  def _check_n(self, n):
+    if n > samples_max(self.L, self.pool):
+      raise OverflowError(f'{n} samples of the {self.pool} pool (L = {self.L}) could carry a sum past 2^62; the limit is {samples_max(self.L, self.pool)}')
+
+  # ---- adding samples
+  def update(self, codes):
+    """codes: int16 device tensor [M, L, D] (motion_codes).  Adds its samples into the state, which moves to the codes' device."""
+    codes = _codes_arg(codes, 'codes', 'MotionStats.update')
+    if codes.dim() != 3 or tuple(codes.shape[1:]) != (self.L, self.D) or codes.shape[0] < 1:
+      raise ValueError(f'codes must be [M >= 1, L = {self.L}, D = {self.D}], got {tuple(codes.shape)}')
+    M = int(codes.shape[0])
+    self._check_n(self._n + (M * self.L if self.pool == 'token' else M))
+    if self.state.device != codes.device:
+      self.state = self.state.to(codes.device)
+    h = _motion_handle()
+    with torch.cuda.device(codes.device):
+      _lib.check(_lib.load().spa3d_motion_moments_add(h, codes.data_ptr(), M, self.L, self.D, POOLS[self.pool], self.state.data_ptr(), _stream(codes)),
+                 h, 'spa3d_motion_moments_add')
+    self._n += M * self.L if self.pool == 'token' else M
+    return self
+
+  def _same_kind(self, other):
+    if not isinstance(other, MotionStats) or (other.D, other.L, other.pool) != (self.D, self.L, self.pool):
+      raise ValueError(f'statistics of another kind: D, L, pool = {(self.D, self.L, self.pool)} here')
+
+  def merge(self, other):
+    """adds another state of the same D, L and pool: integer addition, equal to one state updated with both sets of clips"""
+    self._same_kind(other)
+    self._check_n(self._n + other._n)
+    self.state += other.state.to(self.state.device)
+    self._n += other._n
+    return self
+
+  def all_reduce(self, group=None):
+    """int64 SUM over the process group: every rank ends with the same bits.  Without an initialised process group: nothing to do."""
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized():
+      dist.all_reduce(self.state, op=dist.ReduceOp.SUM, group=group)
+      self._n = int(self.state[0].item())
+      self._check_n(self._n)
+    return self
+
+  # ---- persistence
+  def state_dict(self):
+    return {'D': self.D, 'L': self.L, 'pool': self.pool, 'state': self.state.detach().cpu().clone()}
+
+  def load_state_dict(self, sd):
+    state = torch.as_tensor(np.asarray(sd['state'])) if not isinstance(sd['state'], torch.Tensor) else sd['state']
+    if (int(sd['D']), int(sd['L']), str(sd['pool'])) != (self.D, self.L, self.pool):
+      raise ValueError(f'state of another kind: D, L, pool = {(int(sd["D"]), int(sd["L"]), str(sd["pool"]))}, here {(self.D, self.L, self.pool)}')
+    if state.dtype != torch.int64 or tuple(state.shape) != (1 + self.D + self.D * self.D,):
+      raise ValueError(f'state must be int64 [{1 + self.D + self.D * self.D}], got {state.dtype} {tuple(state.shape)}')
+    n = int(state[0].item())
+    if n < 0:
+      raise ValueError(f'state holds a negative count {n}')
+    self._check_n(n)
+    self.state = state.detach().clone().to(self.state.device)
+    self._n = n
+    return self
+
+  def save(self, path):
+    sd = self.state_dict()
+    np.savez(path, D=np.int64(sd['D']), L=np.int64(sd['L']), pool=np.str_(sd['pool']), state=sd['state'].numpy())
+    return path if str(path).endswith('.npz') else str(path) + '.npz'
+
+  @classmethod
+  def load(cls, path):
+    z = np.load(path)
+    return cls(int(z['D']), int(z['L']), str(z['pool'])).load_state_dict({'D': z['D'], 'L': z['L'], 'pool': str(z['pool']), 'state': z['state']})
+
+  # ---- the statistics, float64 on the host
+  def _host(self):
+    if self._n < 1:
+      raise ValueError('no samples yet')
+    st = self.state.detach().cpu().numpy()
+    D = self.D
+    return st[1:1 + D].astype(np.float64), st[1 + D:].reshape(D, D).astype(np.float64)
+
+  @property
+  def mean(self):
+    s, _ = self._host()
+    return s / (float(self._n) * self.divisor)
+
+  @property
+  def cov(self):
+    s, S = self._host()
+    mu = s / (float(self._n) * self.divisor)
+    return S / (float(self._n) * float(self.divisor) ** 2) - np.outer(mu, mu)
+
+
+def _mean_cov(x):
+  if isinstance(x, MotionStats):
+    return x.mean, x.cov
+  mu, cov = x
+  mu, cov = np.asarray(mu, np.float64), np.asarray(cov, np.float64)
+  if mu.ndim != 1 or cov.shape != (mu.shape[0], mu.shape[0]):
+    raise ValueError(f'statistics must be (mean [D], cov [D, D]), got {mu.shape} and {cov.shape}')
+  return mu, cov
+
+
+def frechet_distance(a, b) -> float:
+  """The Frechet distance of two Gaussians with the statistics a and b (MotionStats, or (mean, cov) pairs), as include/spa3d.h states it:
+      |mu_a - mu_b|^2 + tr Sigma_a + tr Sigma_b - 2 sum_i sqrt(max(lambda_i, 0)),
+  lambda the eigenvalues of R Sigma_b R, R the symmetric square root of Sigma_a (eigh, negative eigenvalues clipped to 0).  R Sigma_b R is
+  symmetric positive semi-definite and has the eigenvalues of Sigma_a Sigma_b, so no general matrix square root is needed.  float64 NumPy."""
+  mu_a, cov_a = _mean_cov(a)
+  mu_b, cov_b = _mean_cov(b)
+  if mu_a.shape != mu_b.shape:
+    raise ValueError(f'statistics of {mu_a.shape[0]} and {mu_b.shape[0]} dimensions')
+  w, V = np.linalg.eigh((cov_a + cov_a.T) * 0.5)
+  R = (V * np.sqrt(np.maximum(w, 0.0))) @ V.T
+  G = R @ ((cov_b + cov_b.T) * 0.5) @ R
+  lam = np.linalg.eigvalsh((G + G.T) * 0.5)
+  d = mu_a - mu_b
+  return float(d @ d + np.trace(cov_a) + np.trace(cov_b) - 2.0 * np.sqrt(np.maximum(lam, 0.0)).sum())
+
+
+# ------------------------------------------------------------------------------------------------ pairwise distances
+def _flat_codes(codes, name):
+  codes = _codes_arg(codes, name, 'motion_pdist')
+  if codes.dim() < 2 or codes.shape[0] < 1:
+    raise ValueError(f'{name} must be [M >= 1, ...], got {tuple(codes.shape)}')
+  return codes.reshape(codes.shape[0], -1)
+
+
+def motion_pdist(codes_a, codes_b=None, kind='sqdist'):
+  """All pairwise integer distances of two sets of codes (spa3d_motion_pdist): an int32 device tensor [Ma, Mb], every entry exact.  Codes
+  [M, L, D] are flattened to [M, L * D]; codes_b=None compares the set with itself.  kind: 'sqdist' (sum of squared differences) | 'dot'.
+  The flat distance compares token l of one clip with token l of the other; the latent tokens are index-aligned across clips because they all
+  start from the learned `initializer`.  The entries must be codes (|c| <= 128): that is the caller's contract."""
+  if kind not in KINDS:
+    raise ValueError(f'kind must be one of {sorted(KINDS)}, got {kind!r}')
+  a = _flat_codes(codes_a, 'codes_a')
+  b = a if codes_b is None else _flat_codes(codes_b, 'codes_b')
+  if b.device != a.device:
+    raise ValueError(f'codes_a is on {a.device}, codes_b on {b.device}')
+  E = int(a.shape[1])
+  if int(b.shape[1]) != E:
+    raise ValueError(f'codes_a has {E} elements per sample, codes_b {int(b.shape[1])}')
+  if E < 1 or E > MAX_E:
+    raise ValueError(f'E = {E} elements per sample is outside [1, {MAX_E}]')
+  out = torch.empty(a.shape[0], b.shape[0], dtype=torch.int32, device=a.device)
+  h = _motion_handle()
+  with torch.cuda.device(a.device):
+    _lib.check(_lib.load().spa3d_motion_pdist(h, a.data_ptr(), a.shape[0], b.data_ptr(), b.shape[0], E, KINDS[kind], out.data_ptr(), _stream(a)), h, 'spa3d_motion_pdist')
+  return out
+
+
+def knn_precision_recall(d_rr, d_gg, d_rg, k: int):
+  """The selection of precision_recall on the three distance matrices (real-real [R, R], generated-generated [G, G], real-generated [R, G]),
+  any integer or float tensors: (precision, recall) as Python floats.  <= throughout."""
+  R, G = int(d_rr.shape[0]), int(d_gg.shape[0])
+  for name, m in (('real', R), ('generated', G)):
+    if m < k + 1:
+      raise ValueError(f'the {name} set has {m} samples, k = {k} needs at least {k + 1}')
+  # a sample's radius: its k-th smallest distance to the OTHER samples of its own set -- the (k + 1)-th smallest of its row with the diagonal
+  # (its distance to itself, the row's minimum 0) left in
+  rad_r = torch.kthvalue(d_rr, k + 1, dim=1).values
+  rad_g = torch.kthvalue(d_gg, k + 1, dim=1).values
+  inside_real = int((d_rg <= rad_r[:, None]).any(dim=0).sum().item())   # generated samples inside some real sample's ball
+  inside_gen = int((d_rg <= rad_g[None, :]).any(dim=1).sum().item())     # real samples inside some generated sample's ball
+  return inside_real / G, inside_gen / R   # integer counts, one division each: the same float on every device
+
+
+def precision_recall(codes_real, codes_gen, k: int = 3):
+  """The k-NN manifold estimate of precision and recall on the exact integer squared distances of the flat codes.  A sample's radius is its
+  k-th smallest distance to the other samples of its own set; precision is the share of generated samples within (<=) the radius of at least
+  one real sample, recall the share of real samples within the radius of at least one generated sample.  Integer distances make ties exact
+  and the estimate reproducible.  -> (precision, recall)"""
+  if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+    raise ValueError(f'k must be a positive int, got {k!r}')
+  for name, c in (('codes_real', codes_real), ('codes_gen', codes_gen)):
+    if isinstance(c, torch.Tensor) and c.dim() >= 1 and c.shape[0] < k + 1:
+      raise ValueError(f'{name} has {c.shape[0]} samples, k = {k} needs at least {k + 1}')
+  d_rr = motion_pdist(codes_real)
+  d_gg = motion_pdist(codes_gen)
+  d_rg = motion_pdist(codes_real, codes_gen)
+  return knn_precision_recall(d_rr, d_gg, d_rg, int(k))

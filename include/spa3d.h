@@ -394,6 +394,44 @@ typedef struct {
 } spa3d_stitch;
 int spa3d_stitch_windows(spa3d_handle h, const spa3d_stitch* s, void* stream);
 
+/* ---- Latent-set metrics.  These are this library's own definitions: the reference stops at the predictions and has no counterpart. ----
+ * The decoder sees a latent only through its quantiser, so the metrics are stated on what the quantiser keeps: the integer CODE
+ *   c = (int16) rintf(clip(x, -1, 1) * 128.f)   in [-128, 128]
+ * (the integer the latent quantiser rounds to before it adds the dither; ties to even, +-inf clips to +-128, -0.0 gives 0).  Sums of codes and of
+ * code products are integers: exact, the same however the clips are batched, chunked or spread over ranks, and merged by integer addition.
+ * csrc/motion_code.hpp is the only implementation of the rounding, the state layout, the range checks and the chunk constant.
+ * In all three calls `h` serves the error message only; asynchronous on `stream`, no workspace, nothing read back.
+ *
+ * spa3d_motion_codes: codes[i] of latents[i], i < n (n == 0 only zeroes *bad).  A NaN has no code: it gives 0 and is counted in *bad, one
+ *   device word the call itself zeroes first.  SPA3D_ERR_ARG with a message, before any launch: a NULL pointer, n < 0.
+ *
+ * spa3d_motion_moments_add: codes is [M][L][D].  state is a device array int64 [1 + D + D * D] = n, s[D], S[D][D] (both triangles), and the
+ *   call ADDS the samples' count, sum and sum of outer products into it (zero it before the first call).  SPA3D_POOL_TOKEN: the samples are the
+ *   M * L token rows c[m][l][:]; SPA3D_POOL_CLIP: the M per-clip token sums t[m][:] = sum_l c[m][l][:].  Exact 64-bit integer arithmetic, finished
+ *   by 64-bit integer atomic adds (which commute): no float is added anywhere, the resulting bits do not depend on the order, on how clips were
+ *   grouped into calls, or on which rank saw them.  The caller keeps n * 2^14 (token pool) or n * (128 L)^2 (clip pool) below 2^62.
+ *   SPA3D_ERR_ARG with a message, before any launch: a NULL pointer, M < 1 (or above 2^40), L outside [1, 4096], D outside [1, 256], an unknown pool.
+ *   In latent units a sample is x = c / 128 (token pool) or t / (128 L) (clip pool): mean mu = s / (n q), covariance Sigma = S / (n q^2) - mu mu^T
+ *   (biased), q the divisor.  The Frechet distance of two such statistics, as the Python layer evaluates it in float64, is
+ *     |mu_a - mu_b|^2 + tr Sigma_a + tr Sigma_b - 2 sum_i sqrt(max(lambda_i, 0)),
+ *   lambda the eigenvalues of R Sigma_b R, R the symmetric square root of Sigma_a taken from its eigendecomposition with negative eigenvalues
+ *   clipped to 0.  With fewer samples than dimensions the covariances are rank-deficient and the distance says little.
+ *
+ * spa3d_motion_pdist: a is [Ma][E], b is [Mb][E] (the same pointer is allowed), out is [Ma][Mb] int32.  SPA3D_PDIST_DOT: sum_e a_e b_e;
+ *   SPA3D_PDIST_SQDIST: sum_e (a_e - b_e)^2, computed as |a|^2 + |b|^2 - 2 a.b in int32 (E <= 32767 keeps E * 256^2 below 2^31).  Every result
+ *   is the exact integer: a tiled NT GEMM on the bf16 MFMA (codes are exact in bf16) whose fp32 accumulators are moved into int32 accumulators
+ *   after every MOTION_KCHUNK = 1024 elements of E -- 1024 * 128 * 128 = 2^24, so no partial sum ever leaves the integers fp32 holds exactly.
+ *   Every element of a and b must be a code, i.e. lie in [-128, 128]; this is the caller's contract (device data, not checked on the host), and
+ *   other values give unspecified integers, never a store outside `out`.
+ *   SPA3D_ERR_ARG with a message, before any launch: a NULL pointer, Ma or Mb outside [1, 2^22], E outside [1, 32767], an unknown kind. */
+#define SPA3D_POOL_TOKEN 0
+#define SPA3D_POOL_CLIP 1
+#define SPA3D_PDIST_DOT 0
+#define SPA3D_PDIST_SQDIST 1
+int spa3d_motion_codes(spa3d_handle h, const float* latents, int64_t n, int16_t* codes, int32_t* bad, void* stream);
+int spa3d_motion_moments_add(spa3d_handle h, const int16_t* codes, int64_t M, int32_t L, int32_t D, int32_t pool, int64_t* state, void* stream);
+int spa3d_motion_pdist(spa3d_handle h, const int16_t* a, int64_t Ma, const int16_t* b, int64_t Mb, int32_t E, int32_t kind, int32_t* out, void* stream);
+
 /* forward + loss + backward.  grads (flat f32, same layout as params) is OVERWRITTEN unless
  * accumulate!=0.  denom: global sum(query_tracks_visible) for data-parallel runs (the loss
  * normalisers are batch-global, train.py:111-113,119-121); <=0 = this batch's own.
