@@ -2,7 +2,7 @@
 // Plain C++, host- and device-callable: the kernels of motion.hip, the entry points' range checks and the g++ host test
 // (tests/host/motion_code_check.cpp) run THIS code.
 //
-// Four things live here.
+// Five things live here.
 //   The code of a latent: c = (int16) rintf(clip(x, -1, 1) * 128.f), an integer in [-128, 128] -- the integer discretize_kernel (loss.hip) rounds to
 //     before it adds the dither.  The product is exact (a power of two), rintf rounds ties to even, +-inf clips to +-128, -0.0 gives 0.  A NaN has
 //     no code: it gives 0 and is reported, and the callers count it.
@@ -11,7 +11,9 @@
 //   The chunk rule of the pairwise-distance GEMM: codes are exact in bf16 (integers up to 256 are), a product of two is at most 128 * 128 = 2^14,
 //     and a sum of MOTION_KCHUNK = 1024 of them is at most 2^24 in magnitude, every partial sum an integer of at most that magnitude: exact in the
 //     fp32 MFMA accumulator whatever the order.  So after every MOTION_KCHUNK elements of K the accumulator is moved into an int32 and cleared.
-//   The range checks of the three entries, as codes the entry points turn into messages.
+//   The range checks of the entries, as codes the entry points turn into messages.
+//   The candidate order, the split plan and the workspace size of spa3d_motion_knn, and the checks it shares with spa3d_motion_ball_hits
+//     (tests/host/motion_knn_check.cpp runs them under g++).
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -52,7 +54,8 @@ MC_HD int64_t mc_sample_sq_max(int L, int pool) { return pool == MC_POOL_TOKEN ?
 MC_HD int64_t mc_samples_max(int L, int pool) { return ((int64_t)1 << 62) / mc_sample_sq_max(L, pool); }
 
 // ---- the range checks ----
-enum { MC_OK = 0, MC_BAD_M = 1, MC_BAD_L = 2, MC_BAD_D = 3, MC_BAD_POOL = 4, MC_BAD_E = 5, MC_BAD_KIND = 6, MC_BAD_MB = 7, MC_BAD_N = 8 };
+enum { MC_OK = 0, MC_BAD_M = 1, MC_BAD_L = 2, MC_BAD_D = 3, MC_BAD_POOL = 4, MC_BAD_E = 5, MC_BAD_KIND = 6, MC_BAD_MB = 7, MC_BAD_N = 8,
+       MC_BAD_K = 9, MC_BAD_SELF = 10, MC_BAD_SPLITS = 11 };
 MC_HD int mc_codes_check(int64_t n) { return n < 0 ? MC_BAD_N : MC_OK; }
 MC_HD int mc_moments_check(int64_t M, int L, int D, int pool) {
   if (M < 1 || M > ((int64_t)1 << 40)) return MC_BAD_M;
@@ -67,4 +70,54 @@ MC_HD int mc_pdist_check(int64_t Ma, int64_t Mb, int E, int kind) {
   if (E < 1 || E > MC_MAX_E) return MC_BAD_E;
   if (kind != MC_PDIST_DOT && kind != MC_PDIST_SQDIST) return MC_BAD_KIND;
   return MC_OK;
+}
+
+// ---- streaming k-NN and ball hits (spa3d_motion_knn, spa3d_motion_ball_hits) ----
+// A candidate of row i is a column j with the squared distance d = d(i, j), 0 <= d < 2^31, and the ORDER of candidates is that of the 64-bit key
+// d << 32 | j: by distance, equal distances by the lower column.  Keys of one row are distinct (the columns are), so the order is total and the
+// k smallest keys are the same set, in the same order, however the columns were split.  All ones is no key: j never reaches 2^32 - 1.
+constexpr int MC_KNN_MAX_K = 64;                         // a wave's lanes hold a row's list
+constexpr int MC_KNN_TILE = 128;                         // columns (and rows) of one tile of the distance GEMM
+constexpr int MC_KNN_MAX_SPLITS = 4096;                  // forced column ranges (the launch grid's second dimension)
+constexpr int MC_KNN_TARGET_GROUPS = 512, MC_KNN_MIN_TILES = 4;   // the plan: two workgroups for each of the 256 CUs, no range below four tiles
+constexpr uint64_t MC_KNN_NONE = ~(uint64_t)0;
+MC_HD uint64_t mc_knn_key(int32_t d, int64_t j) { return ((uint64_t)(uint32_t)d << 32) | (uint64_t)(uint32_t)j; }
+MC_HD int32_t mc_knn_key_dist(uint64_t key) { return (int32_t)(key >> 32); }
+MC_HD int32_t mc_knn_key_idx(uint64_t key) { return (int32_t)(key & 0xffffffffu); }
+// the column row i leaves out (self_offset >= 0: column i + self_offset; -1: none, returned as -1)
+MC_HD int64_t mc_knn_excluded(int64_t i, int64_t self_offset) { return self_offset < 0 ? -1 : i + self_offset; }
+// the fewest admissible columns any row has: row 0's own column self_offset lies inside b or no row's does
+MC_HD int64_t mc_knn_admissible(int64_t Mb, int64_t self_offset) { return self_offset >= 0 && self_offset < Mb ? Mb - 1 : Mb; }
+MC_HD int64_t mc_knn_tiles(int64_t M) { return (M + MC_KNN_TILE - 1) / MC_KNN_TILE; }
+// the planned number of column ranges: enough workgroups to fill the chip, as long as every range keeps MC_KNN_MIN_TILES tiles.  Only time
+// depends on it.
+MC_HD int mc_knn_splits(int64_t Ma, int64_t Mb) {
+  const int64_t rt = mc_knn_tiles(Ma), ct = mc_knn_tiles(Mb);
+  const int64_t want = (MC_KNN_TARGET_GROUPS + rt - 1) / rt, most = ct / MC_KNN_MIN_TILES;
+  const int64_t s = want < most ? want : most;
+  return s < 1 ? 1 : (int)s;
+}
+// column tiles [*t0, *t1) of range s of `splits`: near-equal, in order, empty where there are more ranges than tiles
+MC_HD void mc_knn_tile_range(int64_t tiles, int splits, int s, int64_t* t0, int64_t* t1) {
+  *t0 = tiles * s / splits;
+  *t1 = tiles * (s + 1) / splits;
+}
+MC_HD int mc_knn_check(int64_t Ma, int64_t Mb, int E, int k, int64_t self_offset, int splits) {
+  const int r = mc_pdist_check(Ma, Mb, E, MC_PDIST_SQDIST);
+  if (r != MC_OK) return r;
+  if (self_offset < -1) return MC_BAD_SELF;
+  if (k < 1 || k > MC_KNN_MAX_K || k > mc_knn_admissible(Mb, self_offset)) return MC_BAD_K;
+  if (splits < 0 || splits > MC_KNN_MAX_SPLITS) return MC_BAD_SPLITS;
+  return MC_OK;
+}
+// uint64 [splits][Ma][k] when there is more than one range (splits = 0: the plan's); -1 for sizes mc_knn_check refuses
+MC_HD int64_t mc_knn_ws_bytes(int64_t Ma, int64_t Mb, int k, int splits) {
+  if (Ma < 1 || Ma > MC_MAX_M || Mb < 1 || Mb > MC_MAX_M || k < 1 || k > MC_KNN_MAX_K || splits < 0 || splits > MC_KNN_MAX_SPLITS) return -1;
+  const int n = splits == 0 ? mc_knn_splits(Ma, Mb) : splits;
+  return n == 1 ? 0 : (int64_t)n * Ma * k * (int64_t)sizeof(uint64_t);
+}
+MC_HD int mc_ball_check(int64_t Ma, int64_t Mb, int E, int64_t self_offset) {
+  const int r = mc_pdist_check(Ma, Mb, E, MC_PDIST_SQDIST);
+  if (r != MC_OK) return r;
+  return self_offset < -1 ? MC_BAD_SELF : MC_OK;
 }

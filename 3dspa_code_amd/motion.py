@@ -1,9 +1,11 @@
 """Latent-set metrics on the integer codes of the bottleneck (include/spa3d.h, "Latent-set metrics": the library's own definitions, the
-reference has no counterpart).  The device work is csrc/motion.hip -- codes, exact integer moments, exact integer pairwise distances; what is
-left here is plumbing: the moment state and its merges, the Frechet distance in float64 NumPy, and the k-NN precision / recall selection."""
+reference has no counterpart).  The device work is csrc/motion.hip -- codes, exact integer moments, exact integer pairwise distances, and the
+streaming k-NN and ball hits that reduce those distances tile by tile; what is left here is plumbing: the moment state and its merges, the
+Frechet distance in float64 NumPy, the k-NN precision / recall selection on the matrix route, and the counts-to-ratios of manifold_metrics."""
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 
 import numpy as np
 import torch
@@ -241,6 +243,141 @@ def motion_pdist(codes_a, codes_b=None, kind='sqdist'):
   with torch.cuda.device(a.device):
     _lib.check(_lib.load().spa3d_motion_pdist(h, a.data_ptr(), a.shape[0], b.data_ptr(), b.shape[0], E, KINDS[kind], out.data_ptr(), _stream(a)), h, 'spa3d_motion_pdist')
   return out
+
+
+# ------------------------------------------------------------------------------------------------ streaming k-NN, ball hits, manifold metrics
+MAX_K = 64              # MC_KNN_MAX_K (csrc/motion_code.hpp): a wave's lanes hold a row's list
+
+
+def _int_arg(v, name, lo):
+  if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo:
+    raise ValueError(f'{name} must be an int >= {lo}, got {v!r}')
+  return int(v)
+
+
+def _same_width(named):
+  """two named code sets are int16 tensors [M >= 1, ...] with the same number E of elements per sample, 1 <= E <= MAX_E; no device is asked for"""
+  for name, t in named:
+    if not isinstance(t, torch.Tensor):
+      raise ValueError(f'{name} must be a tensor')
+    if t.dtype != torch.int16:
+      raise ValueError(f'{name} must be int16 codes (motion_codes), got {t.dtype}')
+    if t.dim() < 2 or t.shape[0] < 1:
+      raise ValueError(f'{name} must be [M >= 1, ...], got {tuple(t.shape)}')
+  (na, a), (nb, b) = named
+  E, Eb = a[0].numel(), b[0].numel()
+  if Eb != E:
+    raise ValueError(f'{na} has {E} elements per sample, {nb} {Eb}')
+  if E < 1 or E > MAX_E:
+    raise ValueError(f'E = {E} elements per sample is outside [1, {MAX_E}]')
+
+
+def _set_pair(codes, codes_ref, query_offset, what):
+  """(a, b, self_offset) of a query set against a reference set.  codes_ref=None: the set against itself, every sample left out of its own
+  row; query_offset=s: codes is codes_ref[s : s + M], each sample again left out; otherwise nothing is left out (-1)."""
+  # what is wrong with the arguments themselves is said first (ValueError), where they live after that
+  if codes_ref is None and query_offset is not None:
+    raise ValueError('query_offset names the slice of codes_ref the queries are: it needs codes_ref')
+  ref = codes if codes_ref is None else codes_ref
+  _same_width((('codes', codes), ('codes_ref', ref)))
+  self_offset = 0 if codes_ref is None else (-1 if query_offset is None else _int_arg(query_offset, 'query_offset', 0))
+  if self_offset > 0 and self_offset + codes.shape[0] > ref.shape[0]:
+    raise ValueError(f'query_offset = {self_offset} with {codes.shape[0]} queries runs past the {ref.shape[0]} samples of codes_ref')
+  if ref.device != codes.device:
+    raise ValueError(f'codes is on {codes.device}, codes_ref on {ref.device}')
+  _on_device(codes, 'codes', what)
+  a = codes.contiguous().reshape(codes.shape[0], -1)
+  b = a if codes_ref is None else codes_ref.contiguous().reshape(codes_ref.shape[0], -1)
+  return a, b, self_offset
+
+
+def motion_knn(codes, codes_ref=None, k: int = 1, query_offset=None, splits: int = 0):
+  """The k nearest samples of codes_ref for every sample of codes, on the exact integer squared distances of the flat codes
+  (spa3d_motion_knn): (dist int32 [M, k], idx int64 [M, k]), ascending by (distance, index) -- equal distances go to the lower index, so the
+  result is the same however the search was split.  No [M, Mref] matrix is built: the distance tiles are reduced where they are computed.
+  codes_ref=None searches the set itself with each sample left out; query_offset=s says codes is codes_ref[s : s + M], each sample again
+  left out (a large set against itself, in pieces).  Retrieval: dist, idx = motion_knn(codes_gen, codes_real, k=5).
+  k <= 64 and at most the samples a row may take; splits: 0 = the library's plan, n = n column ranges (only time depends on it)."""
+  k = _int_arg(k, 'k', 1)
+  splits = _int_arg(splits, 'splits', 0)
+  if k > MAX_K:
+    raise ValueError(f'k = {k} is above {MAX_K}')
+  ref = codes if codes_ref is None else codes_ref
+  if isinstance(ref, torch.Tensor) and ref.dim() >= 1:
+    own = 0 if codes_ref is None else (query_offset if isinstance(query_offset, (int, np.integer)) else -1)
+    most = int(ref.shape[0]) - 1 if 0 <= own < ref.shape[0] else int(ref.shape[0])
+    if k > most:
+      raise ValueError(f'k = {k} needs at least {k} samples a row may take, there are {most}')
+  a, b, self_offset = _set_pair(codes, codes_ref, query_offset, 'motion_knn')
+  Ma, Mb, E = int(a.shape[0]), int(b.shape[0]), int(a.shape[1])
+  lib, h = _lib.load(), _motion_handle()
+  need = int(lib.spa3d_motion_knn_workspace_bytes(Ma, Mb, k, splits))
+  if need < 0:
+    raise ValueError(f'sizes out of range: {Ma} x {Mb} samples, k = {k}, splits = {splits}')
+  dist = torch.empty(Ma, k, dtype=torch.int32, device=a.device)
+  idx = torch.empty(Ma, k, dtype=torch.int32, device=a.device)
+  ws = torch.empty(need // 8, dtype=torch.int64, device=a.device) if need else None
+  with torch.cuda.device(a.device):
+    _lib.check(lib.spa3d_motion_knn(h, a.data_ptr(), Ma, b.data_ptr(), Mb, E, k, self_offset, splits, dist.data_ptr(), idx.data_ptr(),
+                                    ws.data_ptr() if need else None, need, _stream(a)), h, 'spa3d_motion_knn')
+  return dist, idx.to(torch.int64)
+
+
+def motion_ball_hits(codes, codes_ref, radius, query_offset=None, rows: bool = True, cols: bool = True):
+  """Counts of hit(i, j) = d(codes[i], codes_ref[j]) <= radius[i] on the exact integer squared distances (spa3d_motion_ball_hits):
+  (row_hits int32 [M] = hits of sample i's ball, col_hits int32 [Mref] = balls reference sample j lies in); the one not asked for is None.
+  radius: int32 [M]; <= throughout, a negative radius hits nothing.  codes_ref=None / query_offset as motion_knn.  No [M, Mref] matrix."""
+  if not rows and not cols:
+    raise ValueError('one of rows and cols must be asked for')
+  a, b, self_offset = _set_pair(codes, codes_ref, query_offset, 'motion_ball_hits')
+  _on_device(radius, 'radius', 'motion_ball_hits')
+  if radius.dtype != torch.int32 or tuple(radius.shape) != (a.shape[0],) or radius.device != a.device:
+    raise ValueError(f'radius must be int32 [{a.shape[0]}] on {a.device}, got {radius.dtype} {tuple(radius.shape)} on {radius.device}')
+  radius = radius.contiguous()
+  row_hits = torch.empty(a.shape[0], dtype=torch.int32, device=a.device) if rows else None
+  col_hits = torch.empty(b.shape[0], dtype=torch.int32, device=a.device) if cols else None
+  h = _motion_handle()
+  with torch.cuda.device(a.device):
+    _lib.check(_lib.load().spa3d_motion_ball_hits(h, a.data_ptr(), a.shape[0], b.data_ptr(), b.shape[0], int(a.shape[1]), radius.data_ptr(), self_offset,
+                                                  row_hits.data_ptr() if rows else None, col_hits.data_ptr() if cols else None, _stream(a)), h, 'spa3d_motion_ball_hits')
+  return row_hits, col_hits
+
+
+@dataclasses.dataclass
+class ManifoldMetrics:
+  """manifold_metrics' result.  The four estimates are integer counts followed by one division; the tensors are per sample, on the device."""
+  precision: float
+  recall: float
+  density: float
+  coverage: float
+  k: int
+  real_radius: torch.Tensor          # int32 [R]: squared distance to the k-th nearest other real sample
+  gen_radius: torch.Tensor           # int32 [G]
+  gen_in_real_balls: torch.Tensor    # int32 [G]: real balls generated sample j lies in; 0 = outside the real manifold
+  real_in_gen_balls: torch.Tensor    # int32 [R]: generated balls real sample i lies in
+  real_ball_hits: torch.Tensor       # int32 [R]: generated samples inside real sample i's ball
+
+
+def manifold_metrics(codes_real, codes_gen, k: int = 3) -> ManifoldMetrics:
+  """Precision, recall (as precision_recall, to the bit), density and coverage (Naeem et al. 2020, with <=) of a generated set against a real
+  one, on the exact integer squared distances of the flat codes, as include/spa3d.h states them.  A sample's radius is its k-th smallest
+  distance to the other samples of its own set (two motion_knn calls); the counts come from two ball-hits calls.  No [R, G] matrix is built,
+  so the set size is bounded by time, not by memory."""
+  k = _int_arg(k, 'k', 1)
+  if k > MAX_K:
+    raise ValueError(f'k = {k} is above {MAX_K}')
+  _same_width((('codes_real', codes_real), ('codes_gen', codes_gen)))
+  for name, c in (('codes_real', codes_real), ('codes_gen', codes_gen)):
+    if c.shape[0] < k + 1:
+      raise ValueError(f'{name} has {c.shape[0]} samples, k = {k} needs at least {k + 1}')
+  rad_r = motion_knn(codes_real, k=k)[0][:, k - 1].contiguous()
+  rad_g = motion_knn(codes_gen, k=k)[0][:, k - 1].contiguous()
+  real_ball_hits, gen_in_real = motion_ball_hits(codes_real, codes_gen, rad_r)
+  _, real_in_gen = motion_ball_hits(codes_gen, codes_real, rad_g, rows=False)
+  R, G = int(rad_r.shape[0]), int(rad_g.shape[0])
+  counts = torch.stack([(gen_in_real > 0).sum(), (real_in_gen > 0).sum(), gen_in_real.sum(dtype=torch.int64), (real_ball_hits > 0).sum()]).tolist()   # one read-back
+  return ManifoldMetrics(precision=counts[0] / G, recall=counts[1] / R, density=counts[2] / (k * G), coverage=counts[3] / R, k=k, real_radius=rad_r, gen_radius=rad_g,
+                         gen_in_real_balls=gen_in_real, real_in_gen_balls=real_in_gen, real_ball_hits=real_ball_hits)
 
 
 def knn_precision_recall(d_rr, d_gg, d_rg, k: int):

@@ -423,7 +423,37 @@ int spa3d_stitch_windows(spa3d_handle h, const spa3d_stitch* s, void* stream);
  *   after every MOTION_KCHUNK = 1024 elements of E -- 1024 * 128 * 128 = 2^24, so no partial sum ever leaves the integers fp32 holds exactly.
  *   Every element of a and b must be a code, i.e. lie in [-128, 128]; this is the caller's contract (device data, not checked on the host), and
  *   other values give unspecified integers, never a store outside `out`.
- *   SPA3D_ERR_ARG with a message, before any launch: a NULL pointer, Ma or Mb outside [1, 2^22], E outside [1, 32767], an unknown kind. */
+ *   SPA3D_ERR_ARG with a message, before any launch: a NULL pointer, Ma or Mb outside [1, 2^22], E outside [1, 32767], an unknown kind.
+ *
+ * Streaming k-NN and ball hits.  spa3d_motion_knn and spa3d_motion_ball_hits run the tile and the K loop of spa3d_motion_pdist (SQDIST; the same
+ *   contract on a, b, Ma, Mb and E, the same exact integers d(i, j) = sum_e (a_ie - b_je)^2) and reduce each tile where it was computed: no
+ *   [Ma][Mb] matrix is written.  No float is compared or added.  Both take self_offset: >= 0 leaves column j == i + self_offset out of row i (0: a
+ *   is b; s: a is the slice of b that starts at row s, so a large set is searched against itself in pieces); -1 leaves nothing out.  The columns
+ *   left for a row are its ADMISSIBLE columns.
+ *
+ * spa3d_motion_knn: dist[i][0 .. k) and idx[i][0 .. k) (int32 [Ma][k] each) are the k nearest admissible rows of b for row i of a, ascending in
+ *   the TOTAL order of the 64-bit key (uint64) d(i, j) << 32 | j: by distance, equal distances by the lower column index.  The order is part of
+ *   the definition, so the result does not depend on how the work was split.  1 <= k <= 64, and k may not exceed the admissible columns of any
+ *   row: Mb - 1 when self_offset lies in [0, Mb) (row 0's own column is then inside b), Mb otherwise.
+ *   splits: the columns are searched in `splits` ranges of whole 128-column tiles by separate workgroups.  0 takes the library's plan
+ *   (mc_knn_splits of csrc/motion_code.hpp), n >= 1 forces n ranges (at most 4096; ranges past the tiles are empty); only time depends on it.  One
+ *   range writes dist / idx directly and needs no workspace (NULL, 0).  More write their k best keys per row to the workspace, uint64
+ *   [splits][Ma][k] with all ones where a range had fewer than k admissible columns, and a merge kernel, one wave per row, writes the result.
+ *   spa3d_motion_knn_workspace_bytes gives the bytes for the same Ma, Mb, k and splits (0 for one range, -1 for sizes the call refuses).
+ *   SPA3D_ERR_ARG with a message, before any launch or store: a NULL a, b, dist or idx, Ma or Mb outside [1, 2^22], E outside [1, 32767],
+ *   self_offset < -1, k out of range, splits outside [0, 4096], a workspace that is NULL, not 8-byte aligned or too small when one is needed.
+ *
+ * spa3d_motion_ball_hits: hit(i, j) = d(i, j) <= radius[i] (int32 [Ma]; <=, a negative radius hits nothing) over the admissible columns;
+ *   row_hits[i] = sum_j hit(i, j) (int32 [Ma]), col_hits[j] = sum_i hit(i, j) (int32 [Mb]); either may be NULL, not both.  The call zeroes the
+ *   outputs on the stream, then adds tile sums with 32-bit integer atomics, which commute: two runs give equal bits.
+ *   SPA3D_ERR_ARG with a message, before any launch or store: a NULL a, b or radius, both outputs NULL, the size refusals above, self_offset < -1.
+ *
+ * The manifold estimates the Python layer builds from the two (spa3d.manifold_metrics; real set r [R], generated set g [G], k >= 1):
+ *   radius of a sample = its k-th smallest distance to the OTHER samples of its own set (spa3d_motion_knn, self_offset 0, column k - 1);
+ *   hits_r = ball_hits(a = r with the real radii, b = g), hits_g = ball_hits(a = g with the generated radii, b = r), nothing left out;
+ *   precision = #{j : hits_r.col_hits[j] > 0} / G     recall   = #{i : hits_g.col_hits[i] > 0} / R     (as spa3d.precision_recall)
+ *   density   = sum_j hits_r.col_hits[j] / (k G)       coverage = #{i : hits_r.row_hits[i] > 0} / R     (Naeem et al. 2020, with <=)
+ *   each an integer count followed by one division. */
 #define SPA3D_POOL_TOKEN 0
 #define SPA3D_POOL_CLIP 1
 #define SPA3D_PDIST_DOT 0
@@ -431,6 +461,11 @@ int spa3d_stitch_windows(spa3d_handle h, const spa3d_stitch* s, void* stream);
 int spa3d_motion_codes(spa3d_handle h, const float* latents, int64_t n, int16_t* codes, int32_t* bad, void* stream);
 int spa3d_motion_moments_add(spa3d_handle h, const int16_t* codes, int64_t M, int32_t L, int32_t D, int32_t pool, int64_t* state, void* stream);
 int spa3d_motion_pdist(spa3d_handle h, const int16_t* a, int64_t Ma, const int16_t* b, int64_t Mb, int32_t E, int32_t kind, int32_t* out, void* stream);
+int64_t spa3d_motion_knn_workspace_bytes(int64_t Ma, int64_t Mb, int32_t k, int32_t splits);
+int spa3d_motion_knn(spa3d_handle h, const int16_t* a, int64_t Ma, const int16_t* b, int64_t Mb, int32_t E, int32_t k, int64_t self_offset, int32_t splits, int32_t* dist,
+                     int32_t* idx, void* workspace, int64_t workspace_bytes, void* stream);
+int spa3d_motion_ball_hits(spa3d_handle h, const int16_t* a, int64_t Ma, const int16_t* b, int64_t Mb, int32_t E, const int32_t* radius, int64_t self_offset, int32_t* row_hits,
+                           int32_t* col_hits, void* stream);
 
 /* forward + loss + backward.  grads (flat f32, same layout as params) is OVERWRITTEN unless
  * accumulate!=0.  denom: global sum(query_tracks_visible) for data-parallel runs (the loss
