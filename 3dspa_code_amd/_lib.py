@@ -84,6 +84,24 @@ class Stitch(C.Structure):
               ('frame_err', C.c_void_p), ('out_tracks', C.c_void_p), ('out_visible_logits', C.c_void_p), ('out_frame_err', C.c_void_p), ('out_spread', C.c_void_p)]
 
 
+class GemmArgs(C.Structure):
+  """spa3d_gemm_args (include/spa3d.h): one GEMM as the planner's descriptor states it; device pointers, element strides."""
+  _fields_ = [('A', C.c_void_p), ('B', C.c_void_p), ('C', C.c_void_p), ('M', C.c_int64), ('N', C.c_int32), ('K', C.c_int32),
+              ('sAm', C.c_int64), ('sAk', C.c_int64), ('sBk', C.c_int64), ('sBn', C.c_int64), ('sCm', C.c_int64), ('nb1', C.c_int32), ('nb2', C.c_int32),
+              ('bA1', C.c_int64), ('bA2', C.c_int64), ('bB1', C.c_int64), ('bB2', C.c_int64), ('bC1', C.c_int64), ('bC2', C.c_int64),
+              ('alpha', C.c_float), ('bias', C.c_void_p), ('epi', C.c_int32), ('aux', C.c_void_p), ('aux_is_residual', C.c_int32),
+              ('out_f32', C.c_int32), ('accumulate', C.c_int32), ('pre_out', C.c_void_p),
+              ('crow_group', C.c_int32), ('crow_skip', C.c_int32), ('brow_group', C.c_int32), ('brow_skip', C.c_int32),
+              ('seg_n', C.c_int32), ('C_seg', C.c_void_p * 2), ('colsum_out', C.c_void_p),
+              ('A2', C.c_void_p), ('sA2m', C.c_int64), ('K1', C.c_int32), ('arow_idx', C.c_void_p), ('crow_idx', C.c_void_p),
+              ('r1_x', C.c_void_p), ('r1_w', C.c_void_p), ('Bt', C.c_void_p), ('ldBt', C.c_int64)]
+
+
+EPI_NONE, EPI_GELU, EPI_MUL_GELU_GRAD = 0, 1, 2  # SPA3D_EPI_*
+# SPA3D_GEMM_*: the kernel spa3d_op_gemm reports, by the planner's names (csrc/gemm_plan.hpp GemmKernel)
+GEMM_KERNELS = ('Refuse', 'Generic', 'Rs', 'Ntb', 'MlpFused', 'NtEmbed', 'Nt8pp256', 'Nt8pp384', 'Nt8p256', 'Nt8p384', 'NtOcc', 'Nt',
+                'Tnb', 'Tn8p256', 'Tn8p128x384', 'Tn8p384x128', 'Tn')
+
 BLEND_MEAN, BLEND_HAT, BLEND_FIRST = 0, 1, 2  # SPA3D_BLEND_* (include/spa3d.h)
 POOL_TOKEN, POOL_CLIP = 0, 1                  # SPA3D_POOL_*
 PDIST_DOT, PDIST_SQDIST = 0, 1                # SPA3D_PDIST_*
@@ -154,6 +172,7 @@ _SIGS = {
                                   C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     'spa3d_op_linear_bwd': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                       C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    'spa3d_op_gemm': (C.c_int, [C.POINTER(GemmArgs), C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_int64, C.c_void_p]),
     'spa3d_op_mlp_fused': (C.c_int, [C.c_void_p] * 9 + [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     'spa3d_op_layernorm': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                      C.c_void_p]),

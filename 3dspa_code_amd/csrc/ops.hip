@@ -89,6 +89,62 @@ int op_linear_bwd(OpCtx& c, const T* A, const T* B, const T* dC, T* dA, float* d
   return c.status();
 }
 
+// the header's kernel ids are GemmKernel's values (tests/test_gemm_desc_host.py compares the names as well)
+#define OP_GEMM_ID(id, k) static_assert(id == (int)GemmKernel::k, #id)
+OP_GEMM_ID(SPA3D_GEMM_REFUSE, Refuse); OP_GEMM_ID(SPA3D_GEMM_GENERIC, Generic); OP_GEMM_ID(SPA3D_GEMM_RS, Rs); OP_GEMM_ID(SPA3D_GEMM_NTB, Ntb);
+OP_GEMM_ID(SPA3D_GEMM_MLP_FUSED, MlpFused); OP_GEMM_ID(SPA3D_GEMM_NT_EMBED, NtEmbed); OP_GEMM_ID(SPA3D_GEMM_NT8PP256, Nt8pp256);
+OP_GEMM_ID(SPA3D_GEMM_NT8PP384, Nt8pp384); OP_GEMM_ID(SPA3D_GEMM_NT8P256, Nt8p256); OP_GEMM_ID(SPA3D_GEMM_NT8P384, Nt8p384);
+OP_GEMM_ID(SPA3D_GEMM_NT_OCC, NtOcc); OP_GEMM_ID(SPA3D_GEMM_NT, Nt); OP_GEMM_ID(SPA3D_GEMM_TNB, Tnb); OP_GEMM_ID(SPA3D_GEMM_TN8P256, Tn8p256);
+OP_GEMM_ID(SPA3D_GEMM_TN8P128X384, Tn8p128x384); OP_GEMM_ID(SPA3D_GEMM_TN8P384X128, Tn8p384x128); OP_GEMM_ID(SPA3D_GEMM_TN, Tn);
+#undef OP_GEMM_ID
+static_assert(SPA3D_EPI_NONE == EPI_NONE && SPA3D_EPI_GELU == EPI_GELU && SPA3D_EPI_MUL_GELU_GRAD == EPI_MUL_GELU_GRAD, "epilogue ids");
+
+// spa3d_op_gemm: the descriptor as given, planned by plan_gemm (fp32: the generic kernel), launched on that kernel
+template <typename T>
+int op_gemm(OpCtx& c, const spa3d_gemm_args& a, int impl, int32_t* kernel_out) {
+  GemmDesc d{};
+  d.A = a.A; d.B = a.B; d.C = a.C; d.M = a.M; d.N = a.N; d.K = a.K; d.sAm = a.sAm; d.sAk = a.sAk; d.sBk = a.sBk; d.sBn = a.sBn; d.sCm = a.sCm;
+  d.nb1 = a.nb1; d.nb2 = a.nb2; d.bA1 = a.bA1; d.bA2 = a.bA2; d.bB1 = a.bB1; d.bB2 = a.bB2; d.bC1 = a.bC1; d.bC2 = a.bC2;
+  d.alpha = a.alpha; d.bias = a.bias; d.epi = a.epi; d.aux = a.aux; d.aux_is_residual = a.aux_is_residual; d.out_f32 = a.out_f32; d.accumulate = a.accumulate;
+  d.pre_out = a.pre_out; d.crow_group = a.crow_group; d.crow_skip = a.crow_skip; d.brow_group = a.brow_group; d.brow_skip = a.brow_skip;
+  d.seg_n = a.seg_n; d.C_seg[0] = a.C_seg[0]; d.C_seg[1] = a.C_seg[1]; d.colsum_out = a.colsum_out;
+  d.A2 = a.A2; d.sA2m = a.sA2m; d.K1 = a.K1; d.arow_idx = a.arow_idx; d.crow_idx = a.crow_idx; d.r1_x = a.r1_x; d.r1_w = a.r1_w; d.Bt = a.Bt; d.ldBt = a.ldBt;
+  const bool unbatched = d.nb1 == 1 && d.nb2 == 1;
+  GemmKernel k = GemmKernel::Generic;
+  void* zp = nullptr; T* own_bt = nullptr;   // workspace slots: carved and planned with first, written (zeroed, transposed into) once nothing is refused
+  if constexpr (sizeof(T) == 2) {
+    const GemmPolicy p = GemmPolicy::from_impl(impl);
+    if (d.sAm == 1 && d.sBn == 1 && d.out_f32 && d.accumulate) {  // the dW form: the tiled kernels read rows past the reduction from a page of zeros
+      zp = c.alloc<char>(256); d.zero_page = zp;
+      if (c.ar.overflow) return SPA3D_ERR_WORKSPACE;
+    }
+    // the tiled NT kernels read B as [N][K]: a dense [K][N] B is transposed into the workspace when one of them takes the GEMM with such a copy (A stands
+    // in for the copy while asking: 16-byte aligned, as every workspace slot is)
+    if (!d.Bt && d.sBk != 1 && d.sBn == 1 && d.sBk == d.N && d.sAk == 1 && unbatched) {
+      d.Bt = d.A; d.ldBt = d.K;
+      if (plan_nt(d, p) != GemmKernel::Refuse) {
+        own_bt = c.alloc<T>((int64_t)d.K * d.N); d.Bt = own_bt;
+        if (c.ar.overflow) return SPA3D_ERR_WORKSPACE;
+      } else { d.Bt = nullptr; d.ldBt = 0; }
+    }
+    k = plan_gemm(d, p);
+    if (k == GemmKernel::Generic && impl >= 2) k = GemmKernel::Refuse;   // tiled or an error, as spa3d_op_linear
+  }
+  if (kernel_out) *kernel_out = (int32_t)k;
+  if (k == GemmKernel::Refuse) return SPA3D_ERR_ARG;
+  // what the generic kernel does not implement, and the column sums where the entry cannot add them
+  const bool entry_colsum = d.colsum_out && !gemm_tn_fuses_colsum(k, d);
+  if ((k == GemmKernel::Generic && (d.seg_n > 0 || gemm_emb(d))) || (entry_colsum && (sizeof(T) == 4 || d.sBn != 1 || !unbatched))) {
+    if (kernel_out) *kernel_out = (int32_t)GemmKernel::Refuse;
+    return SPA3D_ERR_ARG;
+  }
+  if (zp) k_zero(&c, zp, 256);
+  if (own_bt) k_transpose<T>(&c, (const T*)d.B, d.K, d.N, own_bt);
+  gemm_launch<T>(&c, d, k);
+  if (entry_colsum) k_colsum<T>(&c, (const T*)d.B, d.K, d.N, d.sBk, d.colsum_out, d.brow_group, d.brow_skip);
+  return c.status();
+}
+
 // the device copy of nseq + 1 host offsets at the front of the workspace, then `body` (which reads *dev) once dry for its peak and once for real
 template <typename F> static int op_with_offsets(OpCtx& c, const int32_t* host, int64_t nseq, const int32_t** dev, F&& body) {
   int32_t* d = c.alloc<int32_t>(nseq + 1);
@@ -162,6 +218,19 @@ SPA3D_OP(spa3d_op_linear_bwd)(const void* A, const void* B, const void* dC, void
   if (!A || !B || !dC) return SPA3D_ERR_ARG;
   OpCtx c(stream, ws, ws_bytes);
   OP_BY_DTYPE(dtype, return op_linear_bwd<T>(c, (const T*)A, (const T*)B, (const T*)dC, (T*)dA, dB, dbias, M, N, K, impl));
+}
+
+SPA3D_OP(spa3d_op_gemm)(const spa3d_gemm_args* g, int32_t dtype, int32_t impl, int32_t* kernel_out, void* ws, int64_t ws_bytes, void* stream) {
+  FWD16(spa3d_op_gemm, g, dtype, impl, kernel_out, ws, ws_bytes, stream)
+  if (kernel_out) *kernel_out = SPA3D_GEMM_REFUSE;
+  if (!g || !g->A || !g->B || !g->C || !OP_DTYPE_OK(dtype) || g->M < 1 || g->N < 1 || g->K < 1 || g->nb1 < 1 || g->nb2 < 1) return SPA3D_ERR_ARG;
+  if (g->epi < SPA3D_EPI_NONE || g->epi > SPA3D_EPI_MUL_GELU_GRAD || (g->epi == SPA3D_EPI_MUL_GELU_GRAD && !g->aux)) return SPA3D_ERR_ARG;
+  if (g->crow_group < 0 || g->crow_skip < 0 || g->brow_group < 0 || g->brow_skip < 0 || g->seg_n < 0 || g->K1 < 0) return SPA3D_ERR_ARG;
+  if (g->seg_n > 0 && (g->N % g->seg_n || g->N / g->seg_n > 3 || (g->N / g->seg_n > 1 && !g->C_seg[0]) || (g->N / g->seg_n > 2 && !g->C_seg[1]))) return SPA3D_ERR_ARG;
+  if ((g->A2 && (g->K1 < 1 || g->K1 >= g->K)) || (g->r1_x && !g->r1_w)) return SPA3D_ERR_ARG;
+  if (dtype == SPA3D_F32 && (g->seg_n > 0 || g->colsum_out || g->A2 || g->arow_idx || g->crow_idx || g->r1_x)) return SPA3D_ERR_ARG;
+  OpCtx c(stream, ws, ws_bytes);
+  OP_BY_DTYPE(dtype, return op_gemm<T>(c, *g, impl, kernel_out));
 }
 
 SPA3D_OP(spa3d_op_mlp_fused)(const void* na, const void* a, const void* w_in, const float* b_in, const void* w_out, const float* b_out, void* y,

@@ -724,6 +724,50 @@ int spa3d_op_linear_bwd(const void* A, const void* B, const void* dC, void* dA, 
                         int64_t M, int32_t N, int32_t K, int32_t dtype, int32_t impl,
                         void* ws, int64_t ws_bytes, void* stream);
 
+/* One GEMM as the model describes it to the planner (csrc/gemm_plan.hpp: the fields of GemmDesc, same names and meanings, without the packed-weight
+ * streams):  C[b][m'][n] (op)= epi(alpha * sum_k A[b][m][k] * B[b][k'][n] + bias[n]) with element strides, a two-level batch, the row remaps
+ * m' = m + (m / crow_group + 1) * crow_skip (C, aux and pre_out) and k' = k + (k / brow_group + 1) * brow_skip (B), column segments of a dW output
+ * (columns [s seg_n, (s + 1) seg_n) in C_seg[s - 1] for s >= 1), the fused column sums of B and the one-pass input embedding operands (A2 .. r1_w).
+ * Zero-initialise the struct, then set what the GEMM uses: alpha = 0 is a factor of zero, nb1 = nb2 = 0 is refused. */
+typedef struct {
+  const void* A; const void* B; void* C;
+  int64_t M; int32_t N; int32_t K;
+  int64_t sAm, sAk, sBk, sBn, sCm;           /* element strides; C is n-contiguous */
+  int32_t nb1, nb2;                          /* two-level batch (>= 1 each) and its element strides */
+  int64_t bA1, bA2, bB1, bB2, bC1, bC2;
+  float alpha;
+  const float* bias;                         /* f32[N] or NULL */
+  int32_t epi;                               /* SPA3D_EPI_* */
+  const void* aux; int32_t aux_is_residual;  /* C layout, `dtype`: residual, or the pre-activation of SPA3D_EPI_MUL_GELU_GRAD */
+  int32_t out_f32, accumulate;               /* C is f32 whatever `dtype`; C += */
+  void* pre_out;                             /* C layout, `dtype`: the value before the activation, or NULL */
+  int32_t crow_group, crow_skip, brow_group, brow_skip;
+  int32_t seg_n; void* C_seg[2];             /* dW kernels only */
+  float* colsum_out;                         /* f32[N], accumulated into: the column sums of B's rows k' (the bias gradient of a dW GEMM) */
+  const void* A2; int64_t sA2m; int32_t K1;  /* one-pass input embedding: K columns [0, K1) from A, [K1, K) from A2 */
+  const int32_t* arow_idx;                   /* input row of output row m (A, A2 and r1_x) */
+  const int32_t* crow_idx;                   /* row of C that output row m is stored at; < 0: dropped */
+  const void* r1_x; const float* r1_w;       /* C[m][n] += r1_x[input row] * r1_w[n] in f32; r1_x in `dtype` */
+  const void* Bt; int64_t ldBt;              /* optional copy of B stored [N][K], K contiguous, row stride ldBt */
+} spa3d_gemm_args;
+enum { SPA3D_EPI_NONE = 0, SPA3D_EPI_GELU = 1, SPA3D_EPI_MUL_GELU_GRAD = 2 };
+/* the kernels a GEMM can run on (GemmKernel of csrc/gemm_plan.hpp, same order) */
+enum { SPA3D_GEMM_REFUSE = 0, SPA3D_GEMM_GENERIC = 1, SPA3D_GEMM_RS = 2, SPA3D_GEMM_NTB = 3, SPA3D_GEMM_MLP_FUSED = 4, SPA3D_GEMM_NT_EMBED = 5,
+       SPA3D_GEMM_NT8PP256 = 6, SPA3D_GEMM_NT8PP384 = 7, SPA3D_GEMM_NT8P256 = 8, SPA3D_GEMM_NT8P384 = 9, SPA3D_GEMM_NT_OCC = 10, SPA3D_GEMM_NT = 11,
+       SPA3D_GEMM_TNB = 12, SPA3D_GEMM_TN8P256 = 13, SPA3D_GEMM_TN8P128X384 = 14, SPA3D_GEMM_TN8P384X128 = 15, SPA3D_GEMM_TN = 16 };
+/* Plans the descriptor with the model's planner under the kernel-choice switches of `impl` ("gemm_impl" above), writes the chosen SPA3D_GEMM_* to
+ * *kernel_out (may be NULL; SPA3D_GEMM_REFUSE when the call fails before or at its plan) and launches that kernel.  fp32 always runs
+ * on the generic kernel.  From the workspace: 256 zero bytes for a dW descriptor (sAm = sBn = 1, out_f32, accumulate), and the [N][K] copy of B (K N
+ * elements) when Bt is NULL, B is dense [K][N] and a tiled NT kernel takes the GEMM with it.
+ * colsum_out: the 8-phase and large-tile dW kernels add the sums themselves; for every other 16-bit kernel (SPA3D_GEMM_TN, SPA3D_GEMM_GENERIC with
+ * sBn = 1 and no batch) the entry adds them with the column-sum kernel after the GEMM, so the result does not depend on the kernel.
+ * SPA3D_ERR_ARG, before any launch: A, B or C NULL; M, N or K < 1; nb1 or nb2 < 1; a dtype other than fp32 / bf16 / fp16; epi outside 0..2, or 2 without
+ * aux; a negative group, skip, seg_n or K1; seg_n > 0 with N % seg_n, more than three segments or a missing C_seg; A2 with K1 outside (0, K); r1_x
+ * without r1_w; impl >= 2 when no tiled kernel takes the GEMM; and what no kernel for the type implements -- fp32 with seg_n, colsum_out or an
+ * embedding operand (A2, arow_idx, crow_idx, r1_x), 16-bit with seg_n or an embedding operand when the plan is the generic kernel, colsum_out on the
+ * generic kernel with sBn != 1 or a batch.  SPA3D_ERR_WORKSPACE: a workspace too small for the two items above. */
+int spa3d_op_gemm(const spa3d_gemm_args* g, int32_t dtype, int32_t impl, int32_t* kernel_out, void* ws, int64_t ws_bytes, void* stream);
+
 /* The MLP of ImprovedTransformerBlock (attention.py:103-108) as ONE sequence-resident kernel, 16-bit dtypes, d = 384 and mlp = 1536 only
  * (the track encoder's widths; anything else returns SPA3D_ERR_ARG):  hpre = na @ w_in + b_in, h = tanh-gelu(hpre), y = a + h @ w_out + b_out.
  * na, a, y [M,d]; h, hpre [M,mlp]; w_in [d,mlp], w_out [mlp,d] in `dtype`; biases f32.  ws >= 4 MiB. */

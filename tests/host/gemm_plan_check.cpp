@@ -1,5 +1,5 @@
 // Host driver for tests/test_gemm_plan_host.py: reads one case per line from stdin and prints what 3dspa_code_amd/csrc/gemm_plan.hpp decides.
-//   <fn> <impl> [field=value ...]      fn: gemm | nt | tn | mlp | lin | embed      impl: GemmPolicy::from_impl's argument
+//   <fn> <impl> [field=value ...]      fn: gemm | nt | tn | mlp | lin | embed | kernels      impl: GemmPolicy::from_impl's argument
 // Descriptor fields take integers (pointers as addresses; A, B, C default to 16-byte aligned addresses).  Output per line: the kernel name,
 // and for tn / gemm "+colsum" when the dW plan fuses the column sums; lin prints its four stream flags, embed 0 / 1.
 #include <cstdio>
@@ -43,6 +43,10 @@ int main() {
     d.A2 = P(get("A2", 0)); d.sA2m = get("sA2m", 0); d.K1 = (int32_t)get("K1", 0);
     d.arow_idx = (const int32_t*)P(get("arow", 0)); d.crow_idx = (const int32_t*)P(get("crow", 0));
     d.r1_x = P(get("r1_x", 0)); d.r1_w = (const float*)P(get("r1_w", 0)); d.seg_n = (int32_t)get("seg_n", 0);
+    if (fn == "kernels") {  // the catalogue: one "<GemmKernel value> <name>" line per kernel
+      for (int i = 0; i <= (int)GemmKernel::Tn; ++i) std::printf("%d %s\n", i, name((GemmKernel)i));
+      continue;
+    }
     if (fn == "lin") {
       const LinStreams s = plan_lin_streams(p, (int)get("K", 0), (int)get("N", 0), (int)get("segw", get("N", 0)), (int)get("nseg", 1), get("train", 1) != 0);
       std::printf("rs=%d rs_t=%d ntb=%d ntb_t=%d\n", s.rs, s.rs_t, s.ntb, s.ntb_t);

@@ -208,6 +208,142 @@ def int_lane_tn(M, N, K, seed):
   return Wt.t().contiguous(), dC, ref, dC.sum(0)
 
 
+# ------------------------------------------------------------------------------------------------ exact-integer lane of a GEMM descriptor
+# spa3d_op_gemm (tests/test_gpu_gemm_desc.py): the lane above with everything that changes an address -- padded strides, the crow / brow row remaps,
+# gather and scatter maps, two A sources, a rank-1 term, an initial C, an initial column sum, alpha a power of two.  Host only; the references are
+# gathers / index_add_ in float64 built from the index maps (tests/test_gemm_desc_host.py checks the maps and that every expected value is exact).
+def row_map(n, group, skip):
+  """Where rows 0 .. n - 1 of a remapped operand sit: row m at m + (m // group + 1) * skip -- behind every `group` rows `skip` rows that do not belong
+  to the GEMM (the readout rows), the first of them before row 0.  group 0: no remap.  The one place in tests/ where the formula is written."""
+  m = torch.arange(n)
+  return m if group == 0 else m + (m // group + 1) * skip
+
+
+def pattern(rows, cols):
+  """The recognisable fill of a destination: -(512 + 4 ((7 row + 3 col) % 64)), multiples of 4 in [-764, -512] -- exact in bf16, fp16 and fp32, outside the
+  lane's results (|.| <= 256), and different in neighbouring rows and columns, so a row stored in the wrong place is not mistaken for an untouched one."""
+  return -(512.0 + 4.0 * ((7 * torch.arange(rows)[:, None] + 3 * torch.arange(cols)[None, :]) % 64)).double()
+
+
+def assert_exact_in(ref, dtype, what='reference'):
+  """every value of `ref` (float64) is exactly representable in `dtype`: the lane compares with torch.equal, so this is a condition, not a tolerance"""
+  assert bool(torch.isfinite(ref).all()), what
+  if dtype == torch.float32:
+    assert float(ref.abs().max()) < 2 ** 24 and torch.equal(ref, ref.round()), f'{what}: not an integer below 2^24'
+  else:
+    assert torch.equal(ref.to(dtype).double(), ref), f'{what}: not exact in {dtype}'
+
+
+def padded(x, ld, rows=None, at=None, fill=float('nan')):
+  """x [m, n] inside a [rows, ld] buffer of `fill` (NaN: what the kernel must not read): row i of x at buffer row at[i] (default i), columns [0, n)"""
+  m, n = x.shape
+  rows = m if rows is None else rows
+  buf = torch.full((rows, ld), fill, dtype=torch.float64)
+  buf[torch.arange(m) if at is None else at, :n] = x.double()
+  return buf
+
+
+def desc_nt_case(M, N, K, seed, lda=None, ldc=None, crow=(0, 0), res=False, bias=True, alpha=1.0, acc=False, emb=None):
+  """C = alpha A . W (+ bias)(+ rank-1)(+ R)(+ C0) on the integer lane, as a dict of float64 host tensors.
+  A in [-a, a] (x 1 / alpha for alpha < 1, so alpha A stays an integer), W = sparse_sign_matrix(K, N), bias in [-3, 3], R in [-5, 5], C0 (the initial C of
+  `acc`) in [-7, 7], rank-1 term r1_x in [-2, 2] times r1_w in [-3, 3]: a = min(100, 235 // (r max(alpha, 1))) keeps every sum within 256.
+  crow = (group, skip): C, R and pre_out rows through row_map.  emb = dict(K1, src_rows, lda2, r1): the one-pass embedding -- input rows gathered through
+  `arow` (with repeats, from src_rows > M rows; rows it never names are NaN), columns [0, K1) from A and [K1, K) from A2 (K1 = 0: one source), output
+  rows scattered through `cidx`, an injective map into M + M // 2 rows with about a quarter dropped (-1), rows 0 and 127 (first and last of a tile) and
+  the last row among them.
+  Keys: A, A2 (padded buffers, NaN in the pad columns and unnamed rows), W [K, N], bias, r1_x [src_rows], r1_w [N], arow, cidx (int32), cmap (row of C per output
+  row, -1 dropped), rows (of C), R (padded [rows, ldc], NaN outside the image), C0 [rows, N] (pattern(); the integers of `acc` in the image), pre [M, N] (before R / C0),
+  C [rows, N] and P [rows, N] (the expected C and pre_out: pattern() outside the image)."""
+  lda = K if lda is None else lda
+  ldc = N if ldc is None else ldc
+  r = (K + 63) // 64
+  a = min(100, 235 // int(r * max(alpha, 1.0)))
+  assert a >= 1
+  g = torch.Generator().manual_seed(seed)
+  W, idx, sgn = sparse_sign_matrix(K, N)
+  o = dict(W=W.double(), bias=None, A2=None, r1_x=None, r1_w=None, arow=None, cidx=None)
+  scale = 1.0 if alpha >= 1.0 else 1.0 / alpha
+  if emb is None:
+    Aeff = torch.randint(-a, a + 1, (M, K), generator=g).double() * scale
+    o['A'] = padded(Aeff, lda)
+    src = torch.arange(M)
+  else:
+    S, K1 = emb['src_rows'], emb['K1']
+    assert S > M
+    src = torch.randint(0, S, (M,), generator=g)
+    src[1] = src[0]                                   # a repeat for sure
+    named = torch.zeros(S, dtype=torch.bool); named[src] = True
+    full = torch.randint(-a, a + 1, (S, K), generator=g).double() * scale
+    full[~named] = float('nan')
+    if K1:
+      o['A'], o['A2'] = padded(full[:, :K1], lda), padded(full[:, K1:], emb['lda2'])
+      Aeff = torch.cat([o['A'][src, :K1], o['A2'][src, :K - K1]], 1)   # gather, then concatenate: the multi-pass form
+    else:
+      o['A'] = padded(full, lda)
+      Aeff = o['A'][src, :K]
+    o['arow'] = src.int()
+  pre = torch.zeros(M, N, dtype=torch.float64)
+  for j in range(r):
+    pre += Aeff[:, idx[j]] * sgn[j].double()
+  pre *= alpha
+  if bias:
+    o['bias'] = torch.randint(-3, 4, (N,), generator=g).double()
+    pre += o['bias']
+  if emb is not None and emb.get('r1'):
+    x = torch.randint(-2, 3, (emb['src_rows'],), generator=g).double()
+    x[~named] = float('nan')
+    o['r1_x'], o['r1_w'] = x, torch.randint(-3, 4, (N,), generator=g).double()
+    pre += x[src][:, None] * o['r1_w'][None, :]
+  if emb is None:
+    cmap = row_map(M, *crow)
+    rows = int(cmap[-1]) + 1 + crow[1] + 2            # the rows behind the last one stay untouched too
+  else:
+    rows = M + M // 2
+    cmap = torch.randperm(rows, generator=g)[:M]
+    drop = torch.rand(M, generator=g) < 0.25
+    drop[[0, 127, M - 1]] = True
+    drop[[1, 126]] = False
+    cmap[drop] = -1
+    o['cidx'] = cmap.int()
+  keep = cmap >= 0
+  out = pre.clone()
+  o['R'] = None
+  if res:
+    R = torch.randint(-5, 6, (M, N), generator=g).double()
+    o['R'] = padded(R[keep], ldc, rows, cmap[keep])
+    out += R
+  o['C0'] = pattern(rows, N)
+  if acc:
+    c0 = torch.randint(-7, 8, (M, N), generator=g).double()
+    o['C0'][cmap[keep]] = c0[keep]
+    out += c0
+  o['C'], o['P'] = pattern(rows, N), pattern(rows, N)
+  o['C'][cmap[keep]] = out[keep]
+  o['P'][cmap[keep]] = pre[keep]
+  assert float(out[keep].abs().max()) <= 256 and float(pre[keep].abs().max()) <= 256
+  o.update(pre=pre, cmap=cmap, rows=rows, Aeff=Aeff, lda=lda, ldc=ldc)
+  return o
+
+
+def desc_tn_case(M, N, Ki, seed, lda=None, ldb=None, brow=(0, 0)):
+  """dW[Ki, N] = C0 + X^T . dY and colsum = cs0 + colsum(dY) over M rows on the integer lane (int_lane_tn), float64 host tensors: X [M, Ki] with +-1 entries,
+  dY in [-4, 4], C0 in [-7, 7], cs0 in [-9, 9]; every sum is an integer below 2^24.  brow = (group, skip): dY's rows sit at row_map() of a taller buffer
+  whose other rows (the skipped ones and two behind the last) are NaN, as are the pad columns of both operands.  The references are an index_add_ and a
+  column sum of the COMPACT dY: the map enters only where the buffer is laid out.
+  Keys: X (padded [M, lda]), dY (padded [rows, ldb]), C0, dW [Ki, N], cs0, cs [N]."""
+  lda = Ki if lda is None else lda
+  ldb = N if ldb is None else ldb
+  X, dC, ref, cs = int_lane_tn(M, N, Ki, seed)
+  g = torch.Generator().manual_seed(seed + 1)
+  C0 = torch.randint(-7, 8, (Ki, N), generator=g).double()
+  cs0 = torch.randint(-9, 10, (N,), generator=g).double()
+  at = row_map(M, *brow)
+  o = dict(X=padded(X, lda), dY=padded(dC, ldb, int(at[-1]) + 3, at), C0=C0, dW=C0 + ref.double(), cs0=cs0, cs=cs0 + cs.double(), lda=lda, ldb=ldb)
+  assert_exact_in(o['dW'], torch.float32, 'dW')
+  assert_exact_in(o['cs'], torch.float32, 'colsum')
+  return o
+
+
 def linear_bound(A, B, bias, R, act, ref64, pre64, out_dtype):
   """elementwise_bound of C = act(A . B + bias) + R for a test's own operands (act: 0 none, 1 tanh-gelu; pre64 = the fp64 pre-activation)"""
   ap = abs_product(A, B)
