@@ -5,7 +5,9 @@
 //                             fp32 accumulators are moved into int32 every MOTION_KCHUNK elements of K, so every result is an exact integer;
 //   spa3d_motion_knn          the k nearest rows of b for every row of a, and
 //   spa3d_motion_ball_hits    per-row and per-column counts of d(i, j) <= radius[i]: the pdist tile and K loop with a reducing epilogue in place
-//                             of the store, so no [Ma, Mb] matrix exists anywhere.
+//                             of the store, so no [Ma, Mb] matrix exists anywhere;
+//   spa3d_motion_kernel_sums  per-row and per-column sums of the polynomial kernel's numerator (a.b + C)^deg as 128-bit integers: the third such
+//                             epilogue, what the unbiased MMD of two code sets (spa3d.kernel_distance) is made of.
 // The code rounding, the state layout, the range checks and the chunk constant are motion_code.hpp's, which the g++ host test runs too.
 // Nothing here adds floats across threads: the only atomics are integer adds, which commute, so two runs -- and any batching, chunking or
 // rank split of the same clips -- give the same bits.  No 16-bit activations are touched: compiled once.  Plain loads and stores.
@@ -463,6 +465,94 @@ void k_motion_ball_hits(spa3d_ctx* c, const int16_t* a, int64_t Ma, const int16_
   SPA_LAUNCH_CHECK(c);
 }
 
+// ---------------------------------------------------------------------------------------------- kernel sums
+// The pdist grid and K loop; the store is replaced by 128-bit integer sums of p^DEG, p = a.b + C (mc_kernel_pow of motion_code.hpp), over the
+// admitted pairs of the tile: a column inside b that is not the row's own, of a row inside a.  A padded row or column has p = C, not 0, so it is
+// masked.  A lane adds its four column fragments of a row, the 16 lanes that share the row add theirs by shuffles of the limbs (mc_u128_add
+// carries), the two waves that share it meet in LDS (plain writes, a barrier, one add), and the tile's sum goes into global memory by
+// ks_atomic_add.  Columns likewise: 16 values in the lane, lanes ^ 16 and ^ 32, the two waves.
+__device__ __forceinline__ mc_u128 ks_shfl_xor(mc_u128 v, int off) {
+  mc_u128 r;
+  r.lo = __shfl_xor((unsigned long long)v.lo, off);
+  r.hi = __shfl_xor((unsigned long long)v.hi, off);
+  return r;
+}
+// dst (two 64-bit words: lo, hi) += x as a 128-bit integer, by two 64-bit integer atomics.  The adder whose addend wrapped lo sees it in the value
+// its own atomic returns and carries 1 into hi, so every wrap is carried exactly once: the final pair is the exact sum whatever the order of the
+// adders, and two runs give equal bits.  The pair is only read after the kernel has finished.
+__device__ __forceinline__ void ks_atomic_add(unsigned long long* dst, mc_u128 x) {
+  if ((x.lo | x.hi) == 0) return;
+  const unsigned long long old = atomicAdd(&dst[0], (unsigned long long)x.lo);
+  const unsigned long long up = x.hi + ((old + x.lo) < x.lo ? 1u : 0u);
+  if (up) atomicAdd(&dst[1], up);
+}
+
+template <int DEG> __global__ __launch_bounds__(256) void motion_kernel_sums_kernel(const int16_t* __restrict__ a, int64_t Ma, const int16_t* __restrict__ b, int64_t Mb, int E,
+                                                                                    int64_t self_offset, unsigned long long* row_sums, unsigned long long* col_sums, int vec) {
+  __shared__ uint4 sA[PD_BM * 8];
+  __shared__ uint4 sB[PD_BN * 8];
+  __shared__ mc_u128 sRow[2][PD_BM], sCol[2][PD_BN];   // [the wave column wn that summed it][row], [the wave row wm][column]: every slot written once
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, wm = wv >> 1, wn = wv & 1;
+  const int64_t i0 = (int64_t)blockIdx.y * PD_BM, j0 = (int64_t)blockIdx.x * PD_BN;
+  int32_t iacc[4][4][4] = {};
+  int na[4] = {0, 0, 0, 0}, nb[4] = {0, 0, 0, 0};
+  pd_kloop(a, Ma, b, Mb, E, i0, j0, vec != 0, sA, sB, iacc, na, nb);
+  mc_u128 cs[4];
+#pragma unroll
+  for (int n = 0; n < 4; ++n) cs[n] = mc_u128{0, 0};
+#pragma unroll
+  for (int m = 0; m < 4; ++m)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int li = wm * 64 + m * 16 + (lane >> 4) * 4 + r;
+      const int64_t i = i0 + li, excl = mc_knn_excluded(i, self_offset);
+      mc_u128 rs = mc_u128{0, 0};
+#pragma unroll
+      for (int n = 0; n < 4; ++n) {
+        const int64_t j = j0 + wn * 64 + n * 16 + (lane & 15);
+        if (i < Ma && j < Mb && j != excl) {
+          const mc_u128 v = mc_kernel_pow(mc_kernel_p(iacc[m][n][r], E), DEG);
+          rs = mc_u128_add(rs, v);
+          cs[n] = mc_u128_add(cs[n], v);
+        }
+      }
+#pragma unroll
+      for (int off = 1; off < 16; off <<= 1) rs = mc_u128_add(rs, ks_shfl_xor(rs, off));
+      if ((lane & 15) == 0) sRow[wn][li] = rs;
+    }
+#pragma unroll
+  for (int n = 0; n < 4; ++n) {
+    cs[n] = mc_u128_add(cs[n], ks_shfl_xor(cs[n], 16));
+    cs[n] = mc_u128_add(cs[n], ks_shfl_xor(cs[n], 32));
+    if (lane < 16) sCol[wm][wn * 64 + n * 16 + lane] = cs[n];
+  }
+  __syncthreads();
+  if (tid < PD_BM) {
+    if (row_sums && i0 + tid < Ma) ks_atomic_add(row_sums + 2 * (i0 + tid), mc_u128_add(sRow[0][tid], sRow[1][tid]));
+  } else {
+    const int t = tid - PD_BM;
+    if (col_sums && j0 + t < Mb) ks_atomic_add(col_sums + 2 * (j0 + t), mc_u128_add(sCol[0][t], sCol[1][t]));
+  }
+}
+
+void k_motion_kernel_sums(spa3d_ctx* c, const int16_t* a, int64_t Ma, const int16_t* b, int64_t Mb, int E, int degree, int64_t self_offset, uint64_t* row_sums,
+                          uint64_t* col_sums) {
+  if (c->dry) return;
+  hipError_t e = hipSuccess;
+  if (row_sums) e = hipMemsetAsync(row_sums, 0, sizeof(mc_u128) * Ma, c->stream);
+  if (col_sums && e == hipSuccess) e = hipMemsetAsync(col_sums, 0, sizeof(mc_u128) * Mb, c->stream);
+  if (e != hipSuccess && c->hip_err == 0) { c->hip_err = (int)e; c->err = std::string("motion_kernel_sums: hipMemsetAsync failed: ") + hipGetErrorString(e); }
+  if (c->hip_err) return;
+  const int vec = (E % 8 == 0 && ((uintptr_t)a & 15) == 0 && ((uintptr_t)b & 15) == 0) ? 1 : 0;
+  const dim3 grid((unsigned)cdiv(Mb, PD_BN), (unsigned)cdiv(Ma, PD_BM));
+  unsigned long long* rs = reinterpret_cast<unsigned long long*>(row_sums);
+  unsigned long long* cs = reinterpret_cast<unsigned long long*>(col_sums);
+  if (degree == 1) motion_kernel_sums_kernel<1><<<grid, 256, 0, c->stream>>>(a, Ma, b, Mb, E, self_offset, rs, cs, vec);
+  else if (degree == 2) motion_kernel_sums_kernel<2><<<grid, 256, 0, c->stream>>>(a, Ma, b, Mb, E, self_offset, rs, cs, vec);
+  else motion_kernel_sums_kernel<3><<<grid, 256, 0, c->stream>>>(a, Ma, b, Mb, E, self_offset, rs, cs, vec);
+  SPA_LAUNCH_CHECK(c);
+}
+
 }  // namespace SPA_NS
 
 // ---- the entry points ----
@@ -520,7 +610,7 @@ int spa3d_motion_pdist(spa3d_handle h, const int16_t* a, int64_t Ma, const int16
   return h->hip_err ? SPA3D_ERR_HIP : SPA3D_OK;
 }
 
-// what the two streaming entries say about the sizes they share with spa3d_motion_pdist and about self_offset; empty: not one of those
+// what the streaming entries say about the sizes they share with spa3d_motion_pdist and about self_offset; empty: not one of those
 static std::string motion_set_refusal(int code, int64_t Ma, int64_t Mb, int32_t E, int64_t self_offset) {
   switch (code) {
     case MC_BAD_M: return "Ma = " + std::to_string(Ma) + " is outside [1, 2^22]";
@@ -571,6 +661,24 @@ int spa3d_motion_ball_hits(spa3d_handle h, const int16_t* a, int64_t Ma, const i
   if (code != MC_OK) return refuse(motion_set_refusal(code, Ma, Mb, E, self_offset));
   h->stream = (hipStream_t)stream; h->dry = false;
   SPA_NS::k_motion_ball_hits(h, a, Ma, b, Mb, E, radius, self_offset, row_hits, col_hits);
+  return h->hip_err ? SPA3D_ERR_HIP : SPA3D_OK;
+}
+
+int spa3d_motion_kernel_sums(spa3d_handle h, const int16_t* a, int64_t Ma, const int16_t* b, int64_t Mb, int32_t E, int32_t degree, int64_t self_offset, uint64_t* row_sums,
+                             uint64_t* col_sums, void* stream) {
+  if (!h) return SPA3D_ERR_ARG;
+  h->err.clear(); h->hip_err = 0;
+  auto refuse = [&](const std::string& m) { h->err = "motion_kernel_sums: " + m; return SPA3D_ERR_ARG; };
+  if (!a) return refuse("a is required");
+  if (!b) return refuse("b is required");
+  if (!row_sums && !col_sums) return refuse("one of row_sums and col_sums is required");
+  const int code = mc_ksum_check(Ma, Mb, E, degree, self_offset);
+  if (code == MC_BAD_DEGREE) return refuse("degree = " + std::to_string(degree) + " is outside [1, " + std::to_string(MC_KERNEL_MAX_DEGREE) + "]");
+  if (code != MC_OK) return refuse(motion_set_refusal(code, Ma, Mb, E, self_offset));
+  if (((uintptr_t)row_sums & 7) != 0) return refuse("row_sums is not 8-byte aligned");
+  if (((uintptr_t)col_sums & 7) != 0) return refuse("col_sums is not 8-byte aligned");
+  h->stream = (hipStream_t)stream; h->dry = false;
+  SPA_NS::k_motion_kernel_sums(h, a, Ma, b, Mb, E, degree, self_offset, row_sums, col_sums);
   return h->hip_err ? SPA3D_ERR_HIP : SPA3D_OK;
 }
 

@@ -2,7 +2,7 @@
 // Plain C++, host- and device-callable: the kernels of motion.hip, the entry points' range checks and the g++ host test
 // (tests/host/motion_code_check.cpp) run THIS code.
 //
-// Five things live here.
+// Six things live here.
 //   The code of a latent: c = (int16) rintf(clip(x, -1, 1) * 128.f), an integer in [-128, 128] -- the integer discretize_kernel (loss.hip) rounds to
 //     before it adds the dither.  The product is exact (a power of two), rintf rounds ties to even, +-inf clips to +-128, -0.0 gives 0.  A NaN has
 //     no code: it gives 0 and is reported, and the callers count it.
@@ -14,6 +14,8 @@
 //   The range checks of the entries, as codes the entry points turn into messages.
 //   The candidate order, the split plan and the workspace size of spa3d_motion_knn, and the checks it shares with spa3d_motion_ball_hits
 //     (tests/host/motion_knn_check.cpp runs them under g++).
+//   The integer side of spa3d_motion_kernel_sums: the polynomial kernel's numerator p^deg as a 128-bit integer of two 64-bit limbs, the limb add,
+//     and the range check (tests/host/motion_kernel_check.cpp runs them under g++).
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -55,7 +57,7 @@ MC_HD int64_t mc_samples_max(int L, int pool) { return ((int64_t)1 << 62) / mc_s
 
 // ---- the range checks ----
 enum { MC_OK = 0, MC_BAD_M = 1, MC_BAD_L = 2, MC_BAD_D = 3, MC_BAD_POOL = 4, MC_BAD_E = 5, MC_BAD_KIND = 6, MC_BAD_MB = 7, MC_BAD_N = 8,
-       MC_BAD_K = 9, MC_BAD_SELF = 10, MC_BAD_SPLITS = 11 };
+       MC_BAD_K = 9, MC_BAD_SELF = 10, MC_BAD_SPLITS = 11, MC_BAD_DEGREE = 12 };
 MC_HD int mc_codes_check(int64_t n) { return n < 0 ? MC_BAD_N : MC_OK; }
 MC_HD int mc_moments_check(int64_t M, int L, int D, int pool) {
   if (M < 1 || M > ((int64_t)1 << 40)) return MC_BAD_M;
@@ -119,5 +121,41 @@ MC_HD int64_t mc_knn_ws_bytes(int64_t Ma, int64_t Mb, int k, int splits) {
 MC_HD int mc_ball_check(int64_t Ma, int64_t Mb, int E, int64_t self_offset) {
   const int r = mc_pdist_check(Ma, Mb, E, MC_PDIST_SQDIST);
   if (r != MC_OK) return r;
+  return self_offset < -1 ? MC_BAD_SELF : MC_OK;
+}
+
+// ---- kernel sums (spa3d_motion_kernel_sums) ----
+// The polynomial kernel (x.y / E + 1)^deg of x = a / 128 is p^deg / C^deg with C = 16384 E and p = a.b + C, an integer in [0, 2 C], 2 C < 2^30.
+// p^deg < 2^90, and a sum of at most MC_MAX_M = 2^22 of them is below 2^112: an unsigned 128-bit integer, kept as two 64-bit limbs.
+struct mc_u128 { uint64_t lo, hi; };
+// a + b mod 2^128: lo wrapped exactly when the wrapped sum is below the addend's lo
+MC_HD mc_u128 mc_u128_add(mc_u128 a, mc_u128 b) {
+  mc_u128 r;
+  r.lo = a.lo + b.lo;
+  r.hi = a.hi + b.hi + (r.lo < b.lo ? 1u : 0u);
+  return r;
+}
+constexpr int MC_KERNEL_MAX_DEGREE = 3;
+MC_HD int64_t mc_kernel_base(int E) { return (int64_t)16384 * E; }
+static_assert((int64_t)2 * 16384 * MC_MAX_E < ((int64_t)1 << 30), "p = a.b + C stays below 2^30");
+// p of the exact dot product of two rows of codes, |dot| <= C
+MC_HD uint32_t mc_kernel_p(int32_t dot, int E) { return (uint32_t)((int64_t)dot + mc_kernel_base(E)); }
+// p^deg for p < 2^30, deg in {1, 2, 3}.  p^2 < 2^60 fits the low limb; p^3 = p^2 p is a 64 x 32 -> 96-bit product taken in two halves of p^2:
+// q_lo p < 2^62 and q_hi p < 2^58 (q_hi < 2^28), the second shifted up 32 bits.
+MC_HD mc_u128 mc_kernel_pow(uint32_t p, int deg) {
+  mc_u128 r;
+  r.hi = 0;
+  if (deg == 1) { r.lo = p; return r; }
+  const uint64_t q = (uint64_t)p * p;
+  if (deg == 2) { r.lo = q; return r; }
+  const uint64_t t0 = (q & 0xffffffffu) * p, t1 = (q >> 32) * p;
+  r.lo = t0 + (t1 << 32);
+  r.hi = (t1 >> 32) + (r.lo < t0 ? 1u : 0u);
+  return r;
+}
+MC_HD int mc_ksum_check(int64_t Ma, int64_t Mb, int E, int deg, int64_t self_offset) {
+  const int r = mc_pdist_check(Ma, Mb, E, MC_PDIST_DOT);
+  if (r != MC_OK) return r;
+  if (deg < 1 || deg > MC_KERNEL_MAX_DEGREE) return MC_BAD_DEGREE;
   return self_offset < -1 ? MC_BAD_SELF : MC_OK;
 }

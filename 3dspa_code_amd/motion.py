@@ -1,7 +1,8 @@
 """Latent-set metrics on the integer codes of the bottleneck (include/spa3d.h, "Latent-set metrics": the library's own definitions, the
 reference has no counterpart).  The device work is csrc/motion.hip -- codes, exact integer moments, exact integer pairwise distances, and the
-streaming k-NN and ball hits that reduce those distances tile by tile; what is left here is plumbing: the moment state and its merges, the
-Frechet distance in float64 NumPy, the k-NN precision / recall selection on the matrix route, and the counts-to-ratios of manifold_metrics."""
+streaming k-NN, ball hits and kernel sums that reduce those products tile by tile; what is left here is plumbing: the moment state and its
+merges, the Frechet distance in float64 NumPy, the k-NN precision / recall selection on the matrix route, the counts-to-ratios of
+manifold_metrics, and the exact rationals of kernel_distance."""
 from __future__ import annotations
 
 import ctypes as C
@@ -378,6 +379,109 @@ def manifold_metrics(codes_real, codes_gen, k: int = 3) -> ManifoldMetrics:
   counts = torch.stack([(gen_in_real > 0).sum(), (real_in_gen > 0).sum(), gen_in_real.sum(dtype=torch.int64), (real_ball_hits > 0).sum()]).tolist()   # one read-back
   return ManifoldMetrics(precision=counts[0] / G, recall=counts[1] / R, density=counts[2] / (k * G), coverage=counts[3] / R, k=k, real_radius=rad_r, gen_radius=rad_g,
                          gen_in_real_balls=gen_in_real, real_in_gen_balls=real_in_gen, real_ball_hits=real_ball_hits)
+
+
+# ------------------------------------------------------------------------------------------------ kernel sums and the kernel distance
+MAX_DEGREE = 3          # MC_KERNEL_MAX_DEGREE (csrc/motion_code.hpp)
+
+
+def kernel_base(E: int) -> int:
+  """C = 16384 E (mc_kernel_base): the kernel (x.y / E + 1)^deg of x = codes / 128 is (a.b + C)^deg / C^deg"""
+  return 16384 * int(E)
+
+
+def _degree_arg(degree):
+  if isinstance(degree, bool) or not isinstance(degree, (int, np.integer)) or degree < 1 or degree > MAX_DEGREE:
+    raise ValueError(f'degree must be 1, 2 or {MAX_DEGREE}, got {degree!r}')
+  return int(degree)
+
+
+def motion_kernel_sums(codes, codes_ref=None, degree: int = 3, query_offset=None, rows: bool = True, cols: bool = True):
+  """Per-row and per-column sums of p(i, j)^degree, p = codes[i] . codes_ref[j] + C with C = 16384 E, over the admitted pairs
+  (spa3d_motion_kernel_sums): (row_sums int64 [M, 2], col_sums int64 [Mref, 2]) on the device, each row the BIT PATTERNS of the {lo, hi} limbs of
+  an unsigned 128-bit integer (limbs_to_ints reads them); the one not asked for is None.  Exact, and additive over disjoint column or row
+  ranges.  codes_ref=None / query_offset as motion_knn.  No [M, Mref] matrix."""
+  degree = _degree_arg(degree)
+  if not rows and not cols:
+    raise ValueError('one of rows and cols must be asked for')
+  a, b, self_offset = _set_pair(codes, codes_ref, query_offset, 'motion_kernel_sums')
+  row_sums = torch.empty(a.shape[0], 2, dtype=torch.int64, device=a.device) if rows else None
+  col_sums = torch.empty(b.shape[0], 2, dtype=torch.int64, device=a.device) if cols else None
+  h = _motion_handle()
+  with torch.cuda.device(a.device):
+    _lib.check(_lib.load().spa3d_motion_kernel_sums(h, a.data_ptr(), a.shape[0], b.data_ptr(), b.shape[0], int(a.shape[1]), degree, self_offset,
+                                                    row_sums.data_ptr() if rows else None, col_sums.data_ptr() if cols else None, _stream(a)), h, 'spa3d_motion_kernel_sums')
+  return row_sums, col_sums
+
+
+def limbs_to_ints(t):
+  """int64 [M, 2] limb bit patterns (motion_kernel_sums) -> a list of M Python ints: lo & (2^64 - 1) | hi << 64"""
+  if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != 2 or t.shape[1] != 2:
+    raise ValueError('limbs must be an int64 tensor [M, 2]')
+  mask = (1 << 64) - 1
+  return [(lo & mask) | ((hi & mask) << 64) for lo, hi in t.detach().cpu().tolist()]
+
+
+@dataclasses.dataclass
+class KernelDistance:
+  """kernel_distance's result.  mmd2 and the witness values are each ONE rounding of an exact rational; the sums are exact Python ints."""
+  mmd2: float
+  degree: int
+  base: int                          # C = 16384 E
+  sum_rr: int                        # A = sum over ordered pairs i != i' of p(r_i, r_i')^degree
+  sum_gg: int                        # B, likewise for the generated set
+  sum_rg: int                        # X = sum over every (generated, real) pair
+  witness_real: np.ndarray           # float64 [R]: mean kernel to the other real samples minus mean kernel to the generated set
+  witness_gen: np.ndarray            # float64 [G]: mean kernel to the real set minus to the other generated samples; > 0: looks real
+  subset_mean: float | None = None   # with subset_size: mean, population standard deviation and values of the per-subset mmd2
+  subset_std: float | None = None
+  subset_values: list | None = None
+
+
+def _kernel_distance_once(real, gen, degree):
+  from fractions import Fraction
+  R, G = int(real.shape[0]), int(gen.shape[0])
+  C = kernel_base(real[0].numel())
+  rr = motion_kernel_sums(real, degree=degree, cols=False)[0]
+  gg = motion_kernel_sums(gen, degree=degree, cols=False)[0]
+  gr_rows, gr_cols = motion_kernel_sums(gen, real, degree=degree)
+  rr, gg, gr_rows, gr_cols = (limbs_to_ints(t) for t in (rr, gg, gr_rows, gr_cols))
+  A, B, X = sum(rr), sum(gg), sum(gr_rows)
+  Cd = C ** degree
+  mmd2 = float(Fraction(A, R * (R - 1) * Cd) + Fraction(B, G * (G - 1) * Cd) - Fraction(2 * X, R * G * Cd))
+  # a witness value x / (R Cd) - s / ((G - 1) Cd) is the ONE rational (x (G - 1) - s R) / (R (G - 1) Cd); Python's int / int is the correctly
+  # rounded float64 of the quotient, as float(Fraction) is, without a gcd per element
+  den_g, den_r = R * (G - 1) * Cd, (R - 1) * G * Cd
+  w_gen = np.array([(x * (G - 1) - s * R) / den_g for x, s in zip(gr_rows, gg)], np.float64)
+  w_real = np.array([(s * G - x * (R - 1)) / den_r for s, x in zip(rr, gr_cols)], np.float64)
+  return KernelDistance(mmd2=mmd2, degree=degree, base=C, sum_rr=A, sum_gg=B, sum_rg=X, witness_real=w_real, witness_gen=w_gen)
+
+
+def kernel_distance(codes_real, codes_gen, degree: int = 3, subset_size=None) -> KernelDistance:
+  """The kernel distance of a generated set against a real one as include/spa3d.h states it: the unbiased MMD^2 with the polynomial kernel
+  (x.y / E + 1)^degree on the flat codes x = c / 128 (degree 3: KID's kernel, Binkowski et al. 2018 -- on motion codes, not Inception features, so
+  not comparable with published KID values).  Three motion_kernel_sums calls give exact integer sums; mmd2 is one exact rational rounded once.
+  It needs no covariance and is unbiased at any set size, where the Frechet distance of fewer samples than dimensions says little.  The witness
+  says which samples pull the sets apart (KernelDistance).  subset_size=s adds the mean and population standard deviation of the estimate over
+  the contiguous subsets real[t s : (t + 1) s] against gen[t s : (t + 1) s], t < min(R, G) // s (shuffle first for random subsets).  No
+  [R, G] matrix is built."""
+  degree = _degree_arg(degree)
+  _same_width((('codes_real', codes_real), ('codes_gen', codes_gen)))
+  R, G = int(codes_real.shape[0]), int(codes_gen.shape[0])
+  for name, m in (('codes_real', R), ('codes_gen', G)):
+    if m < 2:
+      raise ValueError(f'{name} has {m} sample, the unbiased estimate needs at least 2')
+  if subset_size is not None:
+    s = _int_arg(subset_size, 'subset_size', 2)
+    if s > min(R, G):
+      raise ValueError(f'subset_size = {s} is above the smaller set\'s {min(R, G)} samples')
+  res = _kernel_distance_once(codes_real, codes_gen, degree)
+  if subset_size is not None:
+    vals = [_kernel_distance_once(codes_real[t * s:(t + 1) * s], codes_gen[t * s:(t + 1) * s], degree).mmd2 for t in range(min(R, G) // s)]
+    res.subset_values = vals
+    res.subset_mean = float(np.mean(vals))
+    res.subset_std = float(np.std(vals))
+  return res
 
 
 def knn_precision_recall(d_rr, d_gg, d_rg, k: int):

@@ -453,7 +453,37 @@ int spa3d_stitch_windows(spa3d_handle h, const spa3d_stitch* s, void* stream);
  *   hits_r = ball_hits(a = r with the real radii, b = g), hits_g = ball_hits(a = g with the generated radii, b = r), nothing left out;
  *   precision = #{j : hits_r.col_hits[j] > 0} / G     recall   = #{i : hits_g.col_hits[i] > 0} / R     (as spa3d.precision_recall)
  *   density   = sum_j hits_r.col_hits[j] / (k G)       coverage = #{i : hits_r.row_hits[i] > 0} / R     (Naeem et al. 2020, with <=)
- *   each an integer count followed by one division. */
+ *   each an integer count followed by one division.
+ *
+ * Kernel sums and the kernel distance.  The kernel is KID's (Binkowski et al. 2018: the unbiased MMD^2 with the cubic polynomial kernel); the
+ *   features are the motion codes, not Inception's, so values are NOT comparable with published KID numbers.  On codes a[i][e], b[j][e] in
+ *   [-128, 128] of flat width E, with C(E) = 16384 E and p(i, j) = sum_e a[i][e] b[j][e] + C -- an integer, 0 <= p <= 2 C < 2^30 -- the kernel is
+ *     k_deg(i, j) = p(i, j)^deg / C^deg = (x.y / E + 1)^deg   for x = a / 128,   deg in {1, 2, 3} (3: KID's)
+ *   so every sum of kernel values is an integer sum over C^deg: exact, and the same bits however the pairs were split over calls.
+ *
+ * spa3d_motion_kernel_sums: row_sums[i] = sum_j p(i, j)^degree over the admissible columns j of row i (self_offset as above: >= 0 leaves
+ *   j == i + self_offset out, -1 nothing), col_sums[j] = sum_i p(i, j)^degree over the same admitted pairs.  Each sum is an unsigned 128-bit
+ *   integer stored as uint64 [M][2] = {lo, hi}; the largest possible one is 2^22 (2^30)^3 = 2^112.  Either output may be NULL, not both.  The
+ *   tile and K loop of spa3d_motion_pdist (DOT; the same contract on a, b, Ma, Mb and E); no [Ma][Mb] matrix is written.  The call zeroes the
+ *   outputs on the stream, then adds tile sums as 128 bits by two 64-bit integer atomics, the carry taken by the one adder whose addend wrapped
+ *   the low limb: the result is the exact sum whatever the order, two runs give equal bits, and the sums of disjoint column (row) ranges taken
+ *   in separate calls add up to the one call's.  The limbs are complete when the call's work on the stream is.
+ *   SPA3D_ERR_ARG with a message, before any launch or store: a NULL a or b, both outputs NULL, Ma or Mb outside [1, 2^22], E outside
+ *   [1, 32767], degree outside [1, 3], self_offset < -1, an output that is not 8-byte aligned.
+ *
+ * The kernel distance the Python layer builds from three such calls (spa3d.kernel_distance; real set r [R], generated set g [G], R, G >= 2):
+ *   A = sum_{i != i'} p(r_i, r_i')^deg  (r against r, self_offset 0),   B = sum_{j != j'} p(g_j, g_j')^deg,   X = sum_{i, j} p(g_j, r_i)^deg
+ *   mmd2 = A / (R (R - 1) C^deg) + B / (G (G - 1) C^deg) - 2 X / (R G C^deg)
+ *   formed as ONE exact rational and rounded to float64 once.  It is an unbiased estimate: small negative values are expected for equal sets.
+ *   The witness, per sample, each element the float64 of its exact rational (rowsum_xy: row sums of x against y; colsum_gr: column sums of g
+ *   against r):
+ *     witness_gen[j]  = rowsum_gr[j] / (R C^deg) - rowsum_gg[j] / ((G - 1) C^deg)      mean kernel to the real set minus to its own set
+ *     witness_real[i] = rowsum_rr[i] / ((R - 1) C^deg) - colsum_gr[i] / (G C^deg)      mean kernel to its own set minus to the generated set
+ *   Sign convention: a large POSITIVE witness_gen[j] means generated clip j looks like the real set more than like its own; a large positive
+ *   witness_real[i] means real clip i is far better covered by the real set than by the generated one.  mean_i witness_real[i] -
+ *   mean_j witness_gen[j] = mmd2.
+ *   subset_size = s: the estimate on the contiguous subsets real[t s : (t + 1) s] against gen[t s : (t + 1) s], t < min(R, G) / s (integer
+ *   division), with the mean and the POPULATION standard deviation of the per-subset mmd2; shuffle first and the subsets are random ones. */
 #define SPA3D_POOL_TOKEN 0
 #define SPA3D_POOL_CLIP 1
 #define SPA3D_PDIST_DOT 0
@@ -466,6 +496,8 @@ int spa3d_motion_knn(spa3d_handle h, const int16_t* a, int64_t Ma, const int16_t
                      int32_t* idx, void* workspace, int64_t workspace_bytes, void* stream);
 int spa3d_motion_ball_hits(spa3d_handle h, const int16_t* a, int64_t Ma, const int16_t* b, int64_t Mb, int32_t E, const int32_t* radius, int64_t self_offset, int32_t* row_hits,
                            int32_t* col_hits, void* stream);
+int spa3d_motion_kernel_sums(spa3d_handle h, const int16_t* a, int64_t Ma, const int16_t* b, int64_t Mb, int32_t E, int32_t degree, int64_t self_offset, uint64_t* row_sums,
+                             uint64_t* col_sums, void* stream);
 
 /* forward + loss + backward.  grads (flat f32, same layout as params) is OVERWRITTEN unless
  * accumulate!=0.  denom: global sum(query_tracks_visible) for data-parallel runs (the loss
