@@ -122,6 +122,7 @@ _SIGS = {
     'spa3d_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Batch), C.POINTER(Outputs), C.c_void_p, C.c_int64,
                                 C.c_void_p]),
     'spa3d_loss': (C.c_int, [C.c_void_p, C.POINTER(Batch), C.POINTER(Outputs), C.c_float, C.c_void_p, C.c_void_p]),
+    'spa3d_op_head_loss': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.POINTER(Outputs), C.c_void_p, C.c_void_p, C.c_void_p]),
     'spa3d_score': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Batch), C.POINTER(Scores), C.POINTER(Outputs), C.c_void_p, C.c_int64,
                               C.c_void_p]),
     'spa3d_score_folds_workspace_bytes': (C.c_int64, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),

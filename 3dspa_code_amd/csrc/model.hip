@@ -1178,6 +1178,10 @@ void run_body32(spa3d_ctx* c, const RunArgs& a, int Bc) { run_body<float>(c, a, 
 
 #if !SPA_F16  // everything below exists once: host-side tree / sizing / C-ABI, dispatching on spa3d_config::precision
 namespace h_f16 { void run_body16(spa3d_ctx* c, const RunArgs& a, int Bc); }
+namespace h_f16 {  // loss.hip's fp16 build instantiates it (spa3d_op_head_loss)
+template <typename T> void k_loss_bwd(spa3d_ctx*, const float* head, int64_t nq, int T_, const float* tgt, const float* tvis, const float* denom_dev,
+                                      const spa3d_loss_config& lc, const float* wgt, T* dhead, int NC, const float* scale_dev);
+}
 
 // ---------------------------------------------------------------------------------------------
 // parameter tree: canonical leaf order = sorted Flax paths grouped per module
@@ -1527,6 +1531,41 @@ int spa3d_loss(spa3d_handle h, const spa3d_batch* b, const spa3d_outputs* preds,
                       h->loss, at_rows(h->pt_w, r));
   });
   k_loss_finalize(h, scratch, poison, scratch + 6, h->loss.l1_weight, h->loss.bce_weight, loss3);
+  return h->hip_err ? SPA3D_ERR_HIP : SPA3D_OK;
+}
+
+// The head loss of the train path on its own (tests/test_gpu_loss_ops.py): the launchers run_body / emit_outputs / backward_queries call, in their order,
+// on one span of nq rows.  loss3[4..11] is laid out as run_body's `sums` block: accumulators, denominator, loss scale; [3] is the sticky flag.
+int spa3d_op_head_loss(spa3d_handle h, const float* head, int64_t nq, const float* targets, const float* visible, float denom, const spa3d_outputs* out,
+                       float* loss3, void* dhead, void* stream) {
+  if (!h) return SPA3D_ERR_ARG;
+  h->err.clear(); h->hip_err = 0;
+  auto refuse = [&](const std::string& m) { h->err = "op_head_loss: " + m; return SPA3D_ERR_ARG; };
+  if (!head || !targets || !visible || !loss3) return refuse("head, targets, visible and loss3 are required");
+  if (nq < 0) return refuse("nq = " + std::to_string(nq) + " is negative");
+  if (((uintptr_t)loss3) & 7) return refuse("loss3 must be 8-byte aligned");
+  if (h->pt_w && (int64_t)h->pt_B * h->pt_Q != nq)
+    return refuse("point weights were set for B = " + std::to_string(h->pt_B) + ", Q = " + std::to_string(h->pt_Q) + ", this call has nq = " + std::to_string(nq));
+  if (nq == 0) return SPA3D_OK;
+  h->stream = (hipStream_t)stream; h->dry = false;
+  const int To = h->cfg.num_output_frames, NC = h->cfg.model_kind == 1 ? 2 : 3;
+  float* sums = loss3 + 4; float* denom_dev = sums + 6;
+  unsigned* poison = (unsigned*)(loss3 + 3);
+  const bool scaled = h->loss_scale != 1.f;
+  k_zero(h, loss3 + 3, 36);
+  k_vis_count(h, visible, nq * To, sums + 4, poison);
+  k_set_denom(h, sums, poison, denom, denom_dev);
+  if (scaled) k_set_loss_scale(h, denom_dev, h->loss_gmax, h->loss_scale, denom_dev + 1);
+  else if (hipMemsetD32Async((hipDeviceptr_t)(denom_dev + 1), 0x3f800000, 1, h->stream) != hipSuccess && !h->hip_err) { h->hip_err = -7; h->err = "op_head_loss: writing loss3[11] failed"; }
+  k_loss_fwd(h, head, nq, To, targets, visible, out ? out->tracks : nullptr, out ? out->visible_logits : nullptr, out ? out->certain_logits : nullptr, sums, poison, NC,
+             h->loss, h->pt_w);
+  if (dhead) {
+    const float* sc = scaled ? denom_dev + 1 : nullptr;
+    if (h->cfg.precision == SPA3D_F32) k_loss_bwd<float>(h, head, nq, To, targets, visible, denom_dev, h->loss, h->pt_w, (float*)dhead, NC, sc);
+    else if (h->cfg.precision == SPA3D_F16) h_f16::k_loss_bwd<bf16_t>(h, head, nq, To, targets, visible, denom_dev, h->loss, h->pt_w, (bf16_t*)dhead, NC, sc);
+    else k_loss_bwd<bf16_t>(h, head, nq, To, targets, visible, denom_dev, h->loss, h->pt_w, (bf16_t*)dhead, NC, sc);
+  }
+  k_loss_finalize(h, sums, poison, denom_dev, h->loss.l1_weight, h->loss.bce_weight, loss3);
   return h->hip_err ? SPA3D_ERR_HIP : SPA3D_OK;
 }
 

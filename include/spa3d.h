@@ -139,6 +139,21 @@ int spa3d_forward(spa3d_handle h, const float* params, const spa3d_batch* b, spa
 int spa3d_loss(spa3d_handle h, const spa3d_batch* b, const spa3d_outputs* preds, float denom,
                float* loss3, void* stream);
 
+/* The head loss of spa3d_loss_and_grads on its own: the launches that call makes between the head GEMM and the head's backward, in its order, on
+ * nq query rows of head[q][c * T_out + t] (c < NC coordinates, then the visibility logit; the 2-D twin's 4th block: certainty logits).
+ * Reads from the handle: num_output_frames, the model kind (NC), the precision, the objective (spa3d_set_loss), the point-weight plane
+ * (spa3d_set_point_weights, stated for B * Q == nq), the "loss_scale" option and the loss-scale state (spa3d_set_loss_scale_state).
+ * spa3d_set_counts is IGNORED: all nq rows are live.
+ *   out    NULL, or the split predictions to write: tracks [nq,T_out,NC], visible_logits and certain_logits [nq,T_out] (zeros on the 3-D model);
+ *          NULL members are not written, latents is not looked at.
+ *   loss3  device, 12 floats, 8-byte aligned, as spa3d_loss; additionally [10] = the denominator used and [11] = the loss scale used (1 when the
+ *          handle's "loss_scale" is 1, whatever the state: the train call then runs unscaled).
+ *   dhead  NULL, or [nq, 4 * T_out] in the handle's storage type (fp32 / bf16 / fp16): the head cotangent times the loss scale.
+ * SPA3D_ERR_ARG with a message, before the first launch: a NULL handle, head, targets, visible or loss3; nq < 0; loss3 not 8-byte aligned; a weight
+ * plane with B * Q != nq.  nq == 0 is SPA3D_OK and launches nothing. */
+int spa3d_op_head_loss(spa3d_handle h, const float* head /* [nq, 4*T_out] */, int64_t nq, const float* targets /* [nq,T_out,NC] */,
+                       const float* visible /* [nq,T_out] */, float denom, const spa3d_outputs* out, float* loss3, void* dhead, void* stream);
+
 /* Per-track reconstruction scores (no reference counterpart in the model code: upstream's tooling consumes per-point scores, and this is
  * what produces them).  For every query row, over its T_out frames, in fp32: e1 = sum_c |p - g| (the training loss's L1), e2 = the
  * Euclidean distance sqrtf(sum_c (p - g)^2), pv = visible_logit > 0, vis = target visibility y > 0.5, bce as in spa3d_loss.

@@ -144,6 +144,38 @@ def test_point_weights_for_another_shape_are_refused_before_any_launch(spa3d):
   assert lib.spa3d_loss_and_grads(h, fake, C.byref(b), 0.0, fake, 0, fake, None, fake, 0, None) == 2   # only the workspace is missing now
 
 
+def test_op_head_loss_refusals_before_any_launch(spa3d):
+  """spa3d_op_head_loss: a NULL required pointer, a negative row count, a misaligned loss3 and a weight plane stated for another row count are
+  SPA3D_ERR_ARG with a message; nq == 0 is SPA3D_OK.  No call here reaches a launch."""
+  lib = spa3d._lib.load()
+  _, h = _handle(spa3d)
+  fake = 0x100000  # never dereferenced
+  out = spa3d._lib.Outputs(fake, fake, fake, None)
+  call = lambda head=fake, nq=4, tgt=fake, vis=fake, loss3=fake, handle=h: lib.spa3d_op_head_loss(handle, head, nq, tgt, vis, 0.0, C.byref(out), loss3, fake, None)
+  for kw in (dict(head=None), dict(tgt=None), dict(vis=None), dict(loss3=None)):
+    assert call(**kw) == 1 and lib.spa3d_last_error(h).startswith(b'op_head_loss') and b'required' in lib.spa3d_last_error(h), kw
+  assert call(handle=None) == 1
+  assert call(nq=-1) == 1 and b'negative' in lib.spa3d_last_error(h)
+  assert call(loss3=fake + 4) == 1 and b'8-byte aligned' in lib.spa3d_last_error(h)
+  assert call(nq=0) == 0 and lib.spa3d_last_error(h) == b''
+  assert lib.spa3d_op_head_loss(h, fake, 0, fake, fake, 0.0, None, fake, None, None) == 0   # out and dhead are optional
+  assert lib.spa3d_set_point_weights(h, 2, 3, fake) == 0
+  try:
+    for nq in (5, 7, 0):
+      assert call(nq=nq) == 1
+      msg = lib.spa3d_last_error(h)
+      assert b'point weights were set for B = 2, Q = 3' in msg and f'nq = {nq}'.encode() in msg, msg
+  finally:
+    assert lib.spa3d_set_point_weights(h, 0, 0, None) == 0
+  assert call(nq=0) == 0
+  # counts on the handle are ignored: the call does not look at them
+  assert lib.spa3d_set_counts(h, 3, None, (C.c_int32 * 3)(1, 2, 3)) == 0
+  try:
+    assert call(nq=0) == 0 and call(nq=-2) == 1
+  finally:
+    assert lib.spa3d_set_counts(h, 0, None, None) == 0
+
+
 def test_cpu_tensors_are_refused(spa3d):
   preds = spa3d.TrackAutoEncoderResults(torch.zeros(2, 3, 8, 3), torch.zeros(2, 3, 8, 1), torch.zeros(2, 3, 8, 1))
   batch = {'query_tracks': torch.zeros(2, 3, 8, 3), 'query_tracks_visible': torch.ones(2, 3, 8, 1), 'query_weight': torch.ones(2, 3, 8)}
