@@ -69,6 +69,15 @@ class Render(C.Structure):
               ('trail', C.c_int32), ('point_size', C.c_int32), ('pixels', C.c_void_p)]
 
 
+class Heatmap(C.Structure):
+  """spa3d_heatmap (include/spa3d.h): one clip's sizes, device pointers and the options of the map and of its overlay."""
+  _fields_ = [('N', C.c_int32), ('T', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('tracks', C.c_void_p), ('coords', C.c_int32),
+              ('intrinsics', C.c_void_p), ('extrinsics', C.c_void_p), ('resize_h', C.c_int32), ('resize_w', C.c_int32), ('values', C.c_void_p),
+              ('visible', C.c_void_p), ('use_visibility', C.c_int32), ('radius', C.c_int32), ('power', C.c_int32), ('map', C.c_void_p), ('weight', C.c_void_p),
+              ('video', C.c_void_p), ('out', C.c_void_p), ('normalize', C.c_int32), ('lo', C.c_float), ('hi', C.c_float), ('alpha', C.c_int32),
+              ('colour_bgr', C.c_int32)]
+
+
 class Clip(C.Structure):
   """spa3d_clip (include/spa3d.h): one clip of spa3d_build_batch -- device pointers, except `intrinsics` (host double[4] or NULL)."""
   _fields_ = [('n_tracks', C.c_int32), ('T', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('tracks_2d', C.c_void_p), ('tracks_3d', C.c_void_p),
@@ -133,6 +142,8 @@ _SIGS = {
     'spa3d_tapvid3d_from_preds': (C.c_int, [C.c_void_p, C.POINTER(Batch), C.POINTER(Outputs), C.POINTER(TapVid3D), C.c_void_p, C.c_int64, C.c_void_p]),
     'spa3d_render_workspace_bytes': (C.c_int64, [C.c_void_p, C.c_int32, C.c_int32]),
     'spa3d_render_tracks': (C.c_int, [C.c_void_p, C.POINTER(Render), C.c_void_p, C.c_int64, C.c_void_p]),
+    'spa3d_heatmap_workspace_bytes': (C.c_int64, [C.c_void_p, C.c_int32, C.c_int32]),
+    'spa3d_render_heatmap': (C.c_int, [C.c_void_p, C.POINTER(Heatmap), C.c_void_p, C.c_int64, C.c_void_p]),
     'spa3d_build_batch': (C.c_int, [C.c_void_p, C.POINTER(Clip), C.POINTER(Batch), C.c_void_p]),
     'spa3d_build_windows': (C.c_int, [C.c_void_p, C.POINTER(Clip), C.c_int32, C.POINTER(C.c_int32), C.POINTER(Batch), C.c_void_p]),
     'spa3d_stitch_windows': (C.c_int, [C.c_void_p, C.POINTER(Stitch), C.c_void_p]),

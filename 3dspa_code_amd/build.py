@@ -9,9 +9,9 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libspa3d_hip.so')
-SOURCES = ['layernorm.hip', 'embed.hip', 'rows.hip', 'attn_q1.hip', 'loss.hip', 'gemm_generic.hip', 'gemm_fast.hip', 'gemm_tnb.hip', 'gemm_ntb.hip', 'gemm_rs.hip', 'mlp_fused.hip', 'attention.hip', 'attention_fused.hip', 'qkv_attn.hip', 'ops.hip', 'samplers.hip', 'tapvid3d.hip', 'render.hip', 'batch_build.hip', 'windows.hip', 'motion.hip', 'model.hip']
+SOURCES = ['layernorm.hip', 'embed.hip', 'rows.hip', 'attn_q1.hip', 'loss.hip', 'gemm_generic.hip', 'gemm_fast.hip', 'gemm_tnb.hip', 'gemm_ntb.hip', 'gemm_rs.hip', 'mlp_fused.hip', 'attention.hip', 'attention_fused.hip', 'qkv_attn.hip', 'ops.hip', 'samplers.hip', 'tapvid3d.hip', 'render.hip', 'heatmap.hip', 'batch_build.hip', 'windows.hip', 'motion.hip', 'model.hip']
 F16_SOURCES = ['layernorm.hip', 'embed.hip', 'rows.hip', 'attn_q1.hip', 'loss.hip', 'gemm_generic.hip', 'gemm_fast.hip', 'gemm_tnb.hip', 'gemm_ntb.hip', 'gemm_rs.hip', 'mlp_fused.hip', 'attention.hip', 'attention_fused.hip', 'qkv_attn.hip', 'ops.hip', 'model.hip']
-HEADERS = [os.path.join(CSRC, h) for h in ('common.hpp', 'gemm_plan.hpp', 'attn_plan.hpp', 'tn_args.hpp', 'ablate.inc', 'attn_common.hpp', 'score_row.hpp', 'tapvid3d_row.hpp', 'render_px.hpp',
+HEADERS = [os.path.join(CSRC, h) for h in ('common.hpp', 'gemm_plan.hpp', 'attn_plan.hpp', 'tn_args.hpp', 'ablate.inc', 'attn_common.hpp', 'score_row.hpp', 'tapvid3d_row.hpp', 'render_px.hpp', 'heatmap_px.hpp',
                                             'build_row.hpp', 'window_row.hpp', 'motion_code.hpp', 'loss_point.hpp', 'adamw_point.hpp', 'adamw_groups.hpp')] + [os.path.join(HERE, '..', 'include', 'spa3d.h')]
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off', '-Wall', '-Wno-unused-function', '-Wno-inline-asm',
          '-Wno-unused-variable', '-Wno-unused-but-set-variable']

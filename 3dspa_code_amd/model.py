@@ -1282,9 +1282,10 @@ def _plane(t, N, T, name):
   return t.to(torch.float32).contiguous()
 
 
-def _render_call(r, tracks, intrinsics, extrinsics, resize):
-  """Fills the coordinate fields of a _lib.Render, sizes the workspace and calls spa3d_render_tracks on tracks' stream.  The converted tensors
-  and the workspace live until the call is enqueued; the caching allocator orders any reuse of their memory after it on that stream."""
+def _render_call(r, tracks, intrinsics, extrinsics, resize, entry='spa3d_render_tracks', sizer='spa3d_render_workspace_bytes'):
+  """Fills the coordinate fields of a _lib.Render (or a _lib.Heatmap: the same names), sizes the workspace and calls `entry` on tracks' stream.
+  The converted tensors and the workspace live until the call is enqueued; the caching allocator orders any reuse of their memory after it on
+  that stream."""
   lib = _lib.load()
   N, T, nc = tracks.shape
   dev = tracks.device
@@ -1297,8 +1298,8 @@ def _render_call(r, tracks, intrinsics, extrinsics, resize):
     r.intrinsics, r.extrinsics = k.data_ptr(), e.data_ptr()
     r.resize_h, r.resize_w = int(resize[0]), int(resize[1])
   h = _render_handle()
-  ws = torch.empty(max(int(lib.spa3d_render_workspace_bytes(h, N, T)), 256), dtype=torch.uint8, device=dev)
-  _lib.check(lib.spa3d_render_tracks(h, C.byref(r), ws.data_ptr(), ws.numel(), _stream(tracks)), h, 'spa3d_render_tracks')
+  ws = torch.empty(max(int(getattr(lib, sizer)(h, N, T)), 256), dtype=torch.uint8, device=dev)
+  _lib.check(getattr(lib, entry)(h, C.byref(r), ws.data_ptr(), ws.numel(), _stream(tracks)), h, entry)
 
 
 _RENDER_HANDLE = []
@@ -1368,11 +1369,74 @@ def project_tracks(tracks_3d, intrinsics, extrinsics, H: int, W: int, resize=(10
   return pixels
 
 
-def visualize_npz(path: str, device='cuda', **options):
+def render_heatmap(tracks, values, H: Optional[int] = None, W: Optional[int] = None, video=None, visibs=None, intrinsics=None, extrinsics=None, radius: int = 12,
+                   power: int = 2, normalize: bool = True, value_range=None, alpha: float = 0.5, use_visibility: bool = False, colour_bgr: bool = False,
+                   resize=(1024, 1024), out=None, return_weight: bool = False):
+  """Dense per-frame maps of track values on the GPU (spa3d_render_heatmap; the library's own definition, include/spa3d.h): per pixel the
+  average of the values of the tracks within `radius` of it, weighted by q = radius^2 + 1 - d^2 (power 1) or q^2 (power 2), NaN where no track is
+  near.  One clip, track-major, the inputs of render_tracks: tracks [N, T, 3] with intrinsics / extrinsics, or [N, T, 2] pixel coordinates;
+  values, visibs [N, T] or [N, T, 1].  Returns the float32 [T, H, W] map; with a video (uint8 [T, H, W, 3] or float [T, 3, H, W], which also
+  gives H and W) also the uint8 overlay (`out`, which may be the video itself, when given); with return_weight also the float32 [T, H, W] sum of
+  weights.  The overlay colours s = (map - lo) / (hi - lo) as render_tracks colours a score and blends it with weight alpha in [0, 1] (a
+  multiple of 1 / 4096): (lo, hi) is value_range when given, else the min and max of the finite values (normalize) or (0, 1)."""
+  a = float(alpha) * 4096
+  if not (0 <= a <= 4096) or a != int(a):
+    raise ValueError(f'alpha = {alpha} must be a multiple of 1 / 4096 in [0, 1]')
+  if video is None and out is not None:
+    raise ValueError('out needs video')
+  if video is None and (H is None or W is None):
+    raise ValueError('without a video H and W are required')
+  if use_visibility and visibs is None:
+    raise ValueError('use_visibility needs visibs')
+  if value_range is not None and len(value_range) != 2:
+    raise ValueError('value_range must be (lo, hi)')
+  trk = _tracks_f32(tracks)
+  N, T = trk.shape[:2]
+  dev = trk.device
+  m = _lib.Heatmap()
+  if video is not None:
+    _require_cuda(video, 'video')
+    vid = _video_u8(video).contiguous()
+    if vid.shape[0] != T:
+      raise ValueError(f'video has {vid.shape[0]} frames, tracks have {T}')
+    if (H is not None and int(H) != vid.shape[1]) or (W is not None and int(W) != vid.shape[2]):
+      raise ValueError(f'H, W = {H}, {W} disagree with the video ({vid.shape[1]}, {vid.shape[2]})')
+    H, W = vid.shape[1], vid.shape[2]
+    if out is None:
+      out = torch.empty_like(vid)
+    _require_cuda(out, 'out')
+    if out.dtype != torch.uint8 or tuple(out.shape) != tuple(vid.shape) or not out.is_contiguous():
+      raise ValueError(f'out must be a contiguous uint8 {tuple(vid.shape)} tensor')
+    m.video, m.out = vid.data_ptr(), out.data_ptr()
+  m.H, m.W = int(H), int(W)
+  val = _plane(values, N, T, 'values')
+  m.values = val.data_ptr()
+  if visibs is not None:
+    vs = _plane(visibs, N, T, 'visibs')
+    m.visible = vs.data_ptr()
+  m.use_visibility, m.radius, m.power, m.alpha, m.colour_bgr = int(bool(use_visibility)), int(radius), int(power), int(a), int(bool(colour_bgr))
+  if value_range is not None:
+    m.normalize, m.lo, m.hi = 0, float(value_range[0]), float(value_range[1])
+  else:
+    m.normalize, m.lo, m.hi = int(bool(normalize)), 0.0, 1.0
+  if m.H < 1 or m.W < 1:
+    raise ValueError(f'H, W = {m.H}, {m.W} must be positive')
+  hmap = torch.empty(T, m.H, m.W, dtype=torch.float32, device=dev)
+  m.map = hmap.data_ptr()
+  weight = torch.empty(T, m.H, m.W, dtype=torch.float32, device=dev) if return_weight else None
+  m.weight = weight.data_ptr() if return_weight else None
+  _render_call(m, trk, intrinsics, extrinsics, resize, 'spa3d_render_heatmap', 'spa3d_heatmap_workspace_bytes')
+  res = (hmap,) + ((out,) if video is not None else ()) + ((weight,) if return_weight else ())
+  return res if len(res) > 1 else hmap
+
+
+def visualize_npz(path: str, device='cuda', mode: str = 'tracks', **options):
   """Counterpart of visualizer.py's main (:149-203) up to the painted frames: reads the TIME-major file data.save_scores_npz writes (coords
   [T, N, 3], coords_score [T, N] or [T, N, 1], video [T, 3, H, W] float or [T, H, W, 3] uint8, intrinsics, extrinsics, optional visibs),
-  transposes to track-major, renders on `device` and returns RGB uint8 [T, H, W, 3].  options: those of render_tracks.  Encoding a video
-  file is the caller's job."""
+  transposes to track-major, renders on `device` and returns RGB uint8 [T, H, W, 3].  mode 'tracks': dots and trails, options those of
+  render_tracks; mode 'heatmap': the overlay of render_heatmap, options those of render_heatmap.  Encoding a video file is the caller's job."""
+  if mode not in ('tracks', 'heatmap'):
+    raise ValueError(f"mode must be 'tracks' or 'heatmap', got {mode!r}")
   import numpy as np
   d = np.load(path)
   coords, score = np.asarray(d['coords']), np.asarray(d['coords_score'])
@@ -1386,7 +1450,10 @@ def visualize_npz(path: str, device='cuda', **options):
   cam = {}
   if coords.shape[-1] == 3:
     cam = dict(intrinsics=to(d['intrinsics'], torch.float64), extrinsics=to(d['extrinsics'], torch.float64))
-  return render_tracks(to(d['video']), to(coords.transpose(1, 0, 2), torch.float32), to(score.T, torch.float32), visibs, **cam, **options)
+  trk, sc = to(coords.transpose(1, 0, 2), torch.float32), to(score.T, torch.float32)
+  if mode == 'heatmap':
+    return render_heatmap(trk, sc, video=to(d['video']), visibs=visibs, **cam, **options)[1]
+  return render_tracks(to(d['video']), trk, sc, visibs, **cam, **options)
 
 
 _LOSS_HANDLES: Dict[Any, Any] = {}

@@ -19,6 +19,7 @@
  *                                   (third-party arithmetic upstream: restated from the published definition, parity unpinned)
  *   spa3d_render_tracks             project_all_tracks + normalize_scores + paint_point_track_with_colors
  *                                   visualize.py:15-175, visualizer.py:23-45,149-200 (own integer rasteriser, not cv2's)
+ *   spa3d_render_heatmap            dense per-frame maps of the track values (nothing in the reference: the library's own definition)
  *   spa3d_build_batch               split + lift_2d_to_3d + sample_*_features_for_tracks + batch dict, for many clips at once
  *                                   inference.py:541-590, data_loader.py:56-110
  *   spa3d_uniform_noise             jax.random.uniform(PRNGKey(0), shape) track_autoencoder_3d.py:254-257
@@ -320,6 +321,52 @@ int64_t spa3d_render_workspace_bytes(spa3d_handle h, int32_t N, int32_t T);
  * or resize missing with coords == 3, a size, trail or point_size out of range, a workspace that is too small (the message names the bytes
  * needed), more than 2^31 point-frames, or, when frames are drawn, 2^24 or more (frame, 64 x 16 tile) pairs: what one launch holds. */
 int spa3d_render_tracks(spa3d_handle h, const spa3d_render* r, void* ws, int64_t ws_bytes, void* stream);
+
+/* Dense per-frame score maps from track values: per pixel the kernel-weighted average of the values of the tracks around it, NaN where no
+ * track is near, and optionally a translucent overlay of that map on the video.  The library's own definition -- the reference has no
+ * counterpart (its visualiser paints dots, spa3d_render_tracks above); this comment is the contract, csrc/heatmap_px.hpp is its only
+ * implementation and tests/heatmap_util.py restates it in NumPy.  One clip per call, track-major layouts, the inputs of spa3d_render.
+ *
+ * Position of point i in frame t: that of the track overlays -- coords == 3: the projection above; coords == 2: truncation, no position beyond
+ *   2^30 or when not finite.  Point-frame (i, t) CONTRIBUTES when its position exists and is in bounds (0 <= x < W, 0 <= y < H), values[i][t]
+ *   is finite and, with use_visibility != 0, visible[i][t] > 0.5.
+ * Weight of a contributing point at (x, y) for pixel (X, Y): d2 = (X - x)^2 + (Y - y)^2, R2 = radius^2.  The point reaches the pixel iff
+ *   d2 <= R2; then q = R2 + 1 - d2 and w = q (power == 1) or q q (power == 2): an integer, 1 <= w < 2^25 (radius <= 64).
+ * Sums per pixel of frame t over the contributing points that reach it: den = sum of w, an unsigned 64-bit integer; num = sum of
+ *   (double) w x (double) values[i][t] IN INCREASING i, starting from +0.0, one double addition per point (each product is exact in double).
+ * map[t][Y][X] = (float) (num / (double) den) if den > 0, else NaN (0x7fc00000);  weight[t][Y][X] = (float) den.
+ * Overlay (out given): a function of m = map[t][Y][X] widened to double, den and the input byte.  lo, hi: with normalize != 0 the min and max
+ *   over the finite values[][] of the clip, else the caller's.  In double: s = (m - lo) / (hi - lo) if hi > lo, else m - lo;  s' = (float) s.
+ *   If den == 0 or s' is not finite the pixel keeps its three bytes.  Otherwise the colour is score_to_color_bgr of s' as stated above for the
+ *   track overlays, colour_bgr giving the byte order, and per channel out = (in (4096 - alpha) + col alpha + 2048) >> 12.
+ * No fp32 division and no atomics anywhere; every output element is written once by the thread that owns its pixel (out == video is legal);
+ * the sum has the fixed order above and the min / max is an order-independent reduction: the same inputs give the same bits on every run. */
+typedef struct {
+  int32_t N, T, H, W;              /* N, T >= 1; 1 <= H, W <= 16384 */
+  const float* tracks;             /* device [N,T,3] camera/world points, or [N,T,2] pixel coordinates when coords == 2 */
+  int32_t coords;                  /* 2 | 3 */
+  const double* intrinsics;        /* device [T,3,3], coords == 3 only */
+  const double* extrinsics;        /* device [T,4,4], coords == 3 only */
+  int32_t resize_h, resize_w;      /* as in spa3d_render; >= 1, coords == 3 only */
+  const float* values;             /* device [N,T] */
+  const float* visible;            /* device [N,T] or NULL */
+  int32_t use_visibility, radius, power;   /* radius 1..64, power 1 | 2 */
+  float* map;                      /* device [T,H,W] or NULL */
+  float* weight;                   /* device [T,H,W] or NULL */
+  const uint8_t* video;            /* device [T,H,W,3]; required when out is given, not read otherwise */
+  uint8_t* out;                    /* device [T,H,W,3] or NULL; may be == video (in place) */
+  int32_t normalize;               /* overlay range: != 0 the clip's finite min / max of values, 0 the caller's lo, hi */
+  float lo, hi;                    /* read when normalize == 0 and out is given; both finite */
+  int32_t alpha, colour_bgr;       /* alpha 0..4096 (4096: the pure colour) */
+} spa3d_heatmap;
+/* a sufficient workspace for any option */
+int64_t spa3d_heatmap_workspace_bytes(spa3d_handle h, int32_t N, int32_t T);
+/* Asynchronous, allocates nothing, reads nothing back to the host.  SPA3D_ERR_ARG with a message, before the first launch: a missing pointer
+ * (tracks, values; video when out is given; map, weight and out all NULL; visible with use_visibility), coords outside {2, 3}, camera matrices
+ * or resize missing with coords == 3, N, T, H, W, radius, power or alpha out of range, lo or hi not finite when they are read, a workspace
+ * that is too small (the message names the bytes needed), more than 2^31 point-frames, or 2^24 or more (frame, 64 x 16 tile) pairs: what one
+ * launch holds. */
+int spa3d_render_heatmap(spa3d_handle h, const spa3d_heatmap* m, void* ws, int64_t ws_bytes, void* stream);
 
 /* Clips to model batches in one call: the support / query split, the 2-D -> 3-D lift, the DINO and depth-feature sampling and the padded,
  * ragged batch layout that spa3d_forward, spa3d_score, spa3d_loss_and_grads and spa3d_tapvid3d_from_preds read -- what inference.py:541-590 and
